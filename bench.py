@@ -322,6 +322,44 @@ def oracle_check(synth, pipe, batch_of_step, rows, cols, nfeatures, sample=(0, 1
     return {"frames": len(frames), "match_jobs": jobs, "result": "identical to the oracle" if not bad else "MISMATCH: " + ", ".join(bad)}
 
 
+DUMP_BYTES_MAX = 60_000_000   # array bytes: the .npy files stay under 64 MB with their headers
+KP_FIELDS = ("x", "y", "size", "angle", "response", "octave", "class_id")   # KP_DTYPE, in order
+
+
+def dump_outputs(out_dir, pipe, pipelined, matched=True, budget=DUMP_BYTES_MAX):
+    """`--dump-outputs DIR`: what the timed path's LAST step handed its caller, as float32 .npy files under DIR — the extraction of
+    batch i (n, keypoints, descriptors) and the match jobs enqueued in the same step (batch i - 1 when pipelined, batch i when serial).
+    Entries past a frame's keypoint / query count are zero (keypoints, descriptors) or -1 (matches), so two builds compare output for
+    output.  If all B frames exceed `budget` bytes, a fixed seeded sample of frames is written (frames.npy: the frame indices)."""
+    os.makedirs(out_dir, exist_ok=True)
+    i = pipe.i - 1
+    j = i - 1 if pipelined else i
+    B, cap = pipe.B, pipe.cap
+    per_frame = 4 * (1 + cap * (7 + 32) + (1 + 2 * cap))
+    frames = np.arange(B)
+    if B * per_frame > budget:
+        frames = np.sort(np.random.default_rng(0).choice(B, max(1, budget // per_frame), replace=False))
+    n, kps, desc = pipe.outputs(i)
+    n, kps, desc = n[frames], kps[frames], desc[frames]
+    valid = np.arange(cap)[None, :] < n[:, None]
+    kp = np.stack([kps[f].astype(np.float32) for f in KP_FIELDS], axis=-1)
+    arrays = {"frames": frames.astype(np.float32), "n_keypoints": n.astype(np.float32),
+              "keypoints": np.where(valid[..., None], kp, 0).astype(np.float32),
+              "descriptors": np.where(valid[..., None], desc, 0).astype(np.float32)}
+    if matched and j >= 0:
+        nq = pipe.outputs(j)[0][frames]
+        idx, dst = pipe.matches(j)
+        q = np.arange(cap)[None, :] < nq[:, None]
+        arrays["match_n_queries"] = nq.astype(np.float32)
+        arrays["match_train_idx"] = np.where(q, idx[frames], -1).astype(np.float32)
+        arrays["match_distance"] = np.where(q, dst[frames], -1).astype(np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= budget
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "extract_batch": i, "match_batch": j if "match_distance" in arrays else None, "frames": len(frames),
+            "files": sorted(arrays)}
+
+
 def frame_seed(batch_index, NB, rank):
     """seed of the scene that rank `rank` extracts in step `batch_index` (make_batches: one scene per (rank, resident batch))"""
     return 1234 + 101 * (batch_index % NB) + 7 * rank
@@ -493,7 +531,14 @@ def main():
     ap.add_argument("--loopback", type=int, default=0, help="rehearsal of the N > 1 path on ONE GPU: N logical ranks of this process "
                     "(dvs_comm_create_loopback, a host thread each), --global-batch frames split over them; prints a DIAGNOSTIC line with the same `rccl` object")
     ap.add_argument("--dry-launch", action="store_true", help="only start the ranks and report them (no GPU work): launcher self-test")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (keypoints, descriptors, matches) as float32 DIR/<name>.npy, "
+                         "at most 64 MB; one GPU, frame-sharded mode only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.gpus != 1 or args.loopback or args.shard != "frames" or args.dry_launch):
+        ap.error("--dump-outputs needs --gpus 1 and the default frame-sharded run")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -617,6 +662,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = dump_outputs(args.dump_outputs, pipe, args.pipelined, matched=not diag_no_match) if args.dump_outputs else None
 
     # checks of what was just timed (outside the timed region)
     match_check = ocheck = None
@@ -735,6 +781,8 @@ def main():
             "rccl": rccl, "match_check": match_check,
             "oracle_check": ocheck,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if diag_no_match:
             out["diagnostic"] = "BENCH_DIAG_NO_MATCH=1: the match was NOT enqueued in the timed region — not a result, a diagnostic"
             out["metric"] = "DIAGNOSTIC (extraction only) " + out["metric"]
