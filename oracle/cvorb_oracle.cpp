@@ -95,6 +95,7 @@ struct CvOrb {
   int run(const u8* img, int rows, int cols, size_t step, std::vector<KeyPoint>& keypoints, std::vector<u8>& desc) {
     keypoints.clear(); desc.clear();
     if (!img || rows <= 0 || cols <= 0) return 0;                    // _image.empty(): returns without touching the outputs
+    blurred.clear();  // blurred only once keypoints exist (detectAndCompute releases the descriptors of an empty set first)
     // pyramid: level sizes from the float scale table, every level resized from the previous one (orb.cpp: prevImg = currImg)
     pyr.assign(nlevels, Image()); layerScale.assign(nlevels, 1.f);
     for (int level = 0; level < nlevels; level++) {
@@ -225,6 +226,7 @@ int orc_cvorb_detect_and_compute(void* h, const uint8_t* img, int rows, int cols
 int orc_cvorb_level(void* h, int level, int blurredFlag, uint8_t* dst, int cap, int* w, int* hh) {
   CvOrb* o = (CvOrb*)h;
   if (level < 0 || level >= (int)o->pyr.size()) return -6;
+  if (blurredFlag && level >= (int)o->blurred.size()) return -1;  // this image had no keypoints: nothing was blurred
   const Image& im = blurredFlag ? o->blurred[level] : o->pyr[level];
   *w = im.cols; *hh = im.rows;
   if ((int)im.d.size() > cap) return -3;

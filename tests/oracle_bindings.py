@@ -182,7 +182,10 @@ class OracleCvORB:
     def level(self, l, blurred=False):
         w, h = C.c_int(), C.c_int()
         buf = np.zeros(1 << 24, np.uint8)
-        assert self._L.orc_cvorb_level(self._h, l, int(blurred), _p(buf), buf.size, C.byref(w), C.byref(h)) == 0
+        rc = self._L.orc_cvorb_level(self._h, l, int(blurred), _p(buf), buf.size, C.byref(w), C.byref(h))
+        if rc == -1 and blurred:
+            return None                      # no keypoints in the last image: cv::ORB never blurs the pyramid
+        assert rc == 0, rc
         return buf[:w.value * h.value].reshape(h.value, w.value).copy()
 
 

@@ -3,6 +3,7 @@ oracle/cvorb_oracle.cpp.  Bar: bit-exact — every pyramid level (INTER_LINEAR_E
 cv::KeyPoint fields, float bit patterns, in retainBest's libstdc++ order) and the 256-bit descriptors."""
 import numpy as np
 import pytest
+import adversarial_images as ai
 from dvslam_amd import synth
 from test_oracle_cvorb import disc_image
 
@@ -45,6 +46,45 @@ def test_parity_on_textured_frames(gpu, oracle, rows, cols, nf, nl, score, frame
     assert len(ko) > 20
     _same(kg, dg, ko, do)
     kg2, dg2 = g.detectAndCompute(img)                  # handle reuse
+    _same(kg2, dg2, ko, do)
+    g.close()
+
+
+@pytest.mark.parametrize("shape", [(720, 1280), (481, 643)], ids=["720p", "481x643"])
+@pytest.mark.parametrize("name", list(ai.GENERATORS))
+def test_parity_on_adversarial_content(gpu, oracle, name, shape):
+    """cv::ORB::create(500) on the adversarial images of tests/adversarial_images.py: dense and saturated content, tied scores (the
+    posterised frame: retainBest keeps the ties with the 500th response, so more than 500 rows come back), frames without corners"""
+    from dvslam_amd import CvORB
+    img = ai.make(name, *shape)
+    g = CvORB(500)
+    o = oracle.OracleCvORB(500)
+    kg, dg = g.detectAndCompute(img)
+    ko, do = o.detectAndCompute(img)
+    for l in range(8):
+        assert (g.level(l) == o.level(l)).all(), f"pyramid level {l}"
+        if len(ko):                                       # without keypoints cv::ORB blurs nothing
+            assert (g.level(l, blurred=True) == o.level(l, blurred=True)).all(), f"blurred level {l}"
+    assert (len(ko) == 0) == name.startswith("stripes")
+    if name == "posterised":
+        assert len(ko) > 500
+    _same(kg, dg, ko, do)
+    g.close()
+
+
+@pytest.mark.parametrize("name,nf", [("lattice0", 100), ("binary_noise", 50)])
+def test_fast_score_ties_past_the_capacity(gpu, oracle, name, nf):
+    """FAST_SCORE responses are integers: retainBest keeps thousands of ties, more than the handle's first capacity (nfeatures + 64),
+    so detectAndCompute runs its DVS_ERR_CAPACITY retry"""
+    from dvslam_amd import CvORB
+    img = ai.make(name, 720, 1280)
+    g = CvORB(nf, scoreType=CvORB.FAST_SCORE)
+    o = oracle.OracleCvORB(nf, scoreType=1)
+    kg, dg = g.detectAndCompute(img)
+    ko, do = o.detectAndCompute(img)
+    assert len(ko) > nf + 64
+    _same(kg, dg, ko, do)
+    kg2, dg2 = g.detectAndCompute(img)                  # the grown capacity is kept
     _same(kg2, dg2, ko, do)
     g.close()
 

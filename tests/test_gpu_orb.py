@@ -97,7 +97,7 @@ def test_threshold_fallback_cells(gpu, oracle):
 
 
 @pytest.mark.parametrize("ini,mn", [(5, 12), (20, 20), (40, 3), (7, 20)])
-@pytest.mark.parametrize("cols", [640, 643])   # aligned rows: k_fast_wave; odd width: k_fast_cell
+@pytest.mark.parametrize("cols", [640, 643])   # odd width: partial 4-column groups (host entry: level 0 is copied to the aligned pyramid, FAST is k_fast_wave)
 def test_threshold_orders_follow_the_two_literal_calls(gpu, oracle, ini, mn, cols):
     """cv::FAST at iniThFAST, then — only for a cell left empty — at minThFAST, whatever the order of the two numbers
     (ORBextractor.cpp:826-846): with minTh > iniTh the second call can only find a subset of nothing"""

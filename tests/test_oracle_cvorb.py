@@ -89,3 +89,17 @@ def test_adversarial_depth_limit(hiplib, oracle):
         for npts in (1, n // 3, n - 1):
             want = oracle.retain_best(r, npts); got = cvorb.retain_best_host(r, npts)
             assert len(got) == len(want) and (got == want).all(), (n, npts)
+
+
+def test_frame_without_keypoints_leaves_no_blurred_pyramid(oracle):
+    """cv::ORB blurs the pyramid only once keypoints exist.  After a frame without corners the oracle reports no blurred level
+    (it used to index an empty level list, or hand back the previous frame's blurred levels), while the pyramid stays readable."""
+    import adversarial_images as ai
+    o = oracle.OracleCvORB(500)
+    k, _ = o.detectAndCompute(ai.make("checker1", 240, 320))
+    assert len(k) > 0 and o.level(2, blurred=True).shape == o.level(2).shape
+    flat = ai.make("stripes3y", 240, 320)
+    k, d = o.detectAndCompute(flat)
+    assert len(k) == 0 and len(d) == 0
+    assert all(o.level(l, blurred=True) is None for l in range(8))
+    assert (o.level(0) == flat).all()

@@ -60,3 +60,35 @@ def test_intensity_centroid_against_numpy(oracle):
         want = np.degrees(np.arctan2(float(m01), float(m10))) % 360
         got = L.orc_ic_angle(oracle._p(img), 200, float(x), float(y))
         assert abs(((got - want + 180) % 360) - 180) < 0.02, (x, y, got, want)
+
+
+@pytest.mark.parametrize("name", ["binary_noise", "stripes2x", "stripes2y", "stripes3x", "stripes3y", "stripes4x", "stripes5y", "checker1",
+                                  "saturated"])
+def test_resize_and_blur_brackets_on_saturated_content(oracle, name):
+    """The two brackets above on 0 / 255 content edge to edge (binary noise, period-2..5 stripes that alias under every resize,
+    1-px checker, saturated blocks), where the fixed-point coefficients and roundings are driven to their extremes.  The blur is
+    also held to the float result of its own Q8 kernel: the 8-bit path is that correlation rounded once (<= 0.5), so a wrong tap,
+    border or rounding shows even where the Q8 kernel's Nyquist gain differs from the float Gaussian's (period-2 stripes)."""
+    torch = pytest.importorskip("torch")
+    ndi = pytest.importorskip("scipy.ndimage")
+    import adversarial_images as ai
+    L = oracle.lib()
+    img = ai.make(name, 480, 640)
+    for (dw, dh) in [(533, 400), (444, 333), (320, 240), (639, 479), (371, 277)]:
+        dst = np.zeros((dh, dw), np.uint8)
+        L.orc_resize_linear_u8(oracle._p(img), 640, 480, 640, oracle._p(dst), dw, dh, dw)
+        ref = torch.nn.functional.interpolate(torch.from_numpy(img.astype(np.float64))[None, None], size=(dh, dw), mode="bilinear",
+                                              align_corners=False)[0, 0].numpy()
+        err = np.abs(dst.astype(np.float64) - ref)
+        assert err.max() <= 1.0 + 1e-9, (dw, dh, err.max())
+        assert (err > 0.75).mean() < 0.02
+    k = np.array([18, 34, 48, 56, 48, 34, 18], np.int32)
+    g = np.exp(-np.arange(-3, 4) ** 2 / 8.0); g /= g.sum()
+    out = np.zeros_like(img)
+    L.orc_gauss7(oracle._p(img), 640, 480, oracle._p(out), oracle._p(k))
+    blur = lambda kern: ndi.correlate1d(ndi.correlate1d(img.astype(np.float64), kern, axis=1, mode="mirror"), kern, axis=0, mode="mirror")
+    err = np.abs(out.astype(np.float64) - blur(g))
+    assert err.max() <= 4.0
+    if not name.startswith("stripes2"):
+        assert err.mean() < 0.6 and err[:4].mean() < 0.7 and err[:, :4].mean() < 0.7
+    assert np.abs(out.astype(np.float64) - blur(k / 256.0)).max() <= 0.5 + 1e-9

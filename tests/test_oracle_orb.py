@@ -157,3 +157,30 @@ def test_fast_against_independent_numpy_definition(oracle):
         out = np.zeros((4096, 3), np.int32)
         n = oracle.lib().orc_fast(oracle._p(img), W, H, W, t, oracle._p(out), 4096)
         assert [tuple(r) for r in out[:n].tolist()] == exp, t
+
+
+@pytest.mark.parametrize("rows,cols,ini,mn", [(720, 1280, 20, 7), (481, 643, 20, 7), (481, 643, 5, 12)])
+@pytest.mark.parametrize("name", ["iid_noise", "binary_noise", "checker1", "checker2", "checker3", "lattice0", "lattice2", "posterised",
+                                  "square_grid", "saturated"])
+def test_cell_loop_against_numpy_statement(oracle, name, rows, cols, ini, mn):
+    """The oracle's per-cell FAST loop (ComputeKeyPointsOctTree, ORBextractor.cpp:781-872: cell grid, (w + 6) x (h + 6) sub-image,
+    detection inset 3, strict 3x3 NMS with non-corners as 0, minThFAST only for a cell left empty, emission order) against the
+    vectorised numpy statement of tests/adversarial_images.py, on every level of content where candidates are dense, scores tie
+    and pixels saturate.  Input of each level: the oracle's own pyramid level (the resize is bracketed separately)."""
+    import adversarial_images as ai
+    img = ai.make(name, rows, cols)
+    o = oracle.OracleORB(1000, 1.2, 8, ini, mn)
+    o.extract(img)
+    stats = {}
+    for l in range(8):
+        want = ai.cell_fast_candidates(o.level(l), ini, mn, stats)
+        got = o.candidates(l)
+        assert got.shape == want.shape and (got == want).all(), f"{name} level {l}: {len(got)} vs {len(want)} candidates"
+    if (rows, cols, ini) == (720, 1280, 20):                    # the content still reaches what it is here for
+        cand = [len(o.candidates(l)) for l in range(8)]
+        if name in ("iid_noise", "binary_noise"):
+            assert sum(c > 6144 for c in cand) >= 4, cand
+        if name in ("posterised", "square_grid"):
+            assert stats["tied_cells"] > 0
+        if name == "binary_noise":
+            assert max(int(o.candidates(l)[:, 2].max()) for l in range(8) if cand[l]) == 254
