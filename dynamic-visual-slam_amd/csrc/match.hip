@@ -515,6 +515,7 @@ dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq,
   return DVS_OK;
 }
 int matcher_device(dvs_matcher* m) { return m->device; }
+int matcher_use_mfma(dvs_matcher* m) { return m->use_mfma; }
 
 // every (query, train) pair with distance < max_dist as (q, t, dist) triplets in (q, t) order, LEFT ON THE DEVICE:
 // offsets[nq + 1] (exclusive, 64-bit) and the triplet array.  Host inputs are staged; synchronises once for the total.

@@ -98,6 +98,11 @@ def _bind(L):
     L.dvs_match_hamming.argtypes = [vp, vp, i32, vp, i32, vp, vp]
     L.dvs_match_hamming_batch_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp]
     L.dvs_match_hamming_thresh.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, C.POINTER(i32)]
+    L.dvs_match_hamming_knn.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
+    L.dvs_match_hamming_knn_batch_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp]
+    L.dvs_match_hamming_cross.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+    L.dvs_match_hamming_cross_batch_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp]
+    L.dvs_match_hamming_radius.argtypes = [vp, vp, i32, vp, i32, C.c_float, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.dvs_comm_get_unique_id.argtypes = [vp]
     L.dvs_comm_create.argtypes = [i32, i32, i32, vp, C.POINTER(vp)]
     L.dvs_comm_create_loopback.argtypes = [i32, i32, C.POINTER(vp)]

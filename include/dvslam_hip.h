@@ -165,6 +165,30 @@ dvs_status dvs_match_hamming_sequence_device(dvs_matcher* m, const uint8_t* d_de
  * triplets (q, t, dist).  *n_pairs = total found (may exceed cap; only the first cap are written). Host pointers. */
 dvs_status dvs_match_hamming_thresh(dvs_matcher* m, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt,
                                     int32_t max_dist, int32_t* pairs, int32_t cap, int32_t* n_pairs);
+/* BFMatcher(NORM_HAMMING).knnMatch(query, train, matches, k): per query row the first min(k, nt) train rows in ascending
+ * (distance, train index), at train_idx/dist + i*k; unused slots -1 / INT32_MAX.  k >= 1 (else DVS_ERR_ARG); k = 1 is
+ * dvs_match_hamming.  Host pointers. */
+dvs_status dvs_match_hamming_knn(dvs_matcher* m, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t k,
+                                 int32_t* train_idx, int32_t* dist);
+/* the same for npairs device-resident jobs (layout of dvs_match_hamming_batch_device); outputs at (p*q_stride_rows + i)*k.
+ * Asynchronous. */
+dvs_status dvs_match_hamming_knn_batch_device(dvs_matcher* m, const uint8_t* d_q, const int32_t* d_nq, int32_t q_stride_rows,
+                                              const uint8_t* d_t, const int32_t* d_nt, int32_t t_stride_rows, int32_t npairs, int32_t k,
+                                              int32_t* d_idx, int32_t* d_dist);
+/* BFMatcher(NORM_HAMMING, crossCheck = true).match / knnMatch(k = 1): query i keeps j = argmin_j d(i, .) only if
+ * i = argmin_i d(., j) (lowest index on ties on both sides); otherwise train_idx = -1, dist = INT32_MAX.  Host pointers. */
+dvs_status dvs_match_hamming_cross(dvs_matcher* m, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt,
+                                   int32_t* train_idx, int32_t* dist);
+/* the same for npairs device-resident jobs (layout of dvs_match_hamming_batch_device).  Asynchronous. */
+dvs_status dvs_match_hamming_cross_batch_device(dvs_matcher* m, const uint8_t* d_q, const int32_t* d_nq, int32_t q_stride_rows,
+                                                const uint8_t* d_t, const int32_t* d_nt, int32_t t_stride_rows, int32_t npairs,
+                                                int32_t* d_idx, int32_t* d_dist);
+/* BFMatcher(NORM_HAMMING).radiusMatch(query, train, matches, max_distance): every pair with (float)dist <= max_distance
+ * (inclusive; negative or NaN: none), per query in the order std::sort by distance gives the train-ordered list.  CSR result:
+ * offsets[nq + 1] (always written), then (train, dist) int32 pairs.  *n_total = pairs found (may exceed cap; only the first
+ * cap are written).  Host pointers. */
+dvs_status dvs_match_hamming_radius(dvs_matcher* m, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, float max_distance,
+                                    int64_t* offsets, int32_t* pairs, int64_t cap, int64_t* n_total);
 
 /* ======================= E: the multi-GPU exchange step ========================== */
 /* One process per GPU; frames (or, for small batches, pyramid levels) are sharded over the ranks and extraction needs no
