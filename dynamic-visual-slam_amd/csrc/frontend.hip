@@ -6,28 +6,17 @@
 //   dvs_backproject         publishKeyframe's depth back-projection               frontend.cpp:732-776
 //   dvs_associate           associateObservation + reprojectPoint on a database snapshot  backend.cpp:1064-1173
 // All of it is byte/integer or explicitly rounded float/double work: gathers and stream compactions, HBM/latency bound.
-// The context is a dvs_matcher handle (stream + grow-only scratch), declared in match.hip.
+// The context is a dvs_matcher handle (stream + grow-only scratch), declared in matcher.h.
 #include <float.h>
 #include <limits.h>
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
-#include "common.h"
 #include "io_pinned.h"
+#include "matcher.h"
 
 namespace dvs {
-
-typedef unsigned long long u64;
-
-// scratch + stream access to the matcher handle (match.hip)
-dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out);
-dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq, int** counter);
-hipStream_t matcher_stream(dvs_matcher* m);
-int matcher_device(dvs_matcher* m);
-// match.hip: candidate pairs (Hamming < max_dist) as (q, t, dist) triplets + per-query offsets, left on the device
-dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,
-                                 const int** d_pairs, long long* total);
 
 __device__ __forceinline__ int blk_excl_scan(int v, int* wsum, int& total) {  // 256 threads
   int incl = v;
@@ -378,9 +367,9 @@ dvs_status dvs_bgr_to_gray_device(dvs_matcher* ctx, const uint8_t* d_bgr, int32_
   DVS_ARG(ctx && d_bgr && d_gray && nimg >= 0 && rows > 0 && cols > 0 && step >= (size_t)cols * 3 && gray_step >= (size_t)cols);
   DVS_ARG(variant == 0 || variant == 1);
   if (nimg == 0) return DVS_OK;
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
+  DVS_HIP(hipSetDevice(ctx->device));
   const int cb = variant == 0 ? 3735 : 1868, cg = variant == 0 ? 19235 : 9617, cr = variant == 0 ? 9798 : 4899, shift = variant == 0 ? 15 : 14;
-  hipLaunchKernelGGL(k_bgr2gray, dim3((cols + 255) / 256, (rows + 3) / 4, nimg), dim3(64, 4), 0, matcher_stream(ctx), d_bgr, (uint64_t)step,
+  hipLaunchKernelGGL(k_bgr2gray, dim3((cols + 255) / 256, (rows + 3) / 4, nimg), dim3(64, 4), 0, ctx->stream, d_bgr, (uint64_t)step,
                      (uint64_t)frame_stride, rows, cols, d_gray, (uint64_t)gray_step, (uint64_t)gray_frame_stride, cb, cg, cr, shift);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
@@ -389,11 +378,11 @@ dvs_status dvs_bgr_to_gray_device(dvs_matcher* ctx, const uint8_t* d_bgr, int32_
 dvs_status dvs_bgr_to_gray(dvs_matcher* ctx, const uint8_t* bgr, int32_t rows, int32_t cols, size_t step, uint8_t* gray, size_t gray_step,
                            int32_t variant) {
   DVS_ARG(ctx && bgr && gray && rows > 0 && cols > 0);
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
+  DVS_HIP(hipSetDevice(ctx->device));
   void *d_in, *d_out;
   DVS_TRY(matcher_scratch(ctx, 0, (size_t)rows * cols * 3, &d_in));
   DVS_TRY(matcher_scratch(ctx, 1, (size_t)rows * cols, &d_out));
-  hipStream_t st = matcher_stream(ctx);
+  hipStream_t st = ctx->stream;
   DVS_HIP(hipMemcpy2DAsync(d_in, (size_t)cols * 3, bgr, step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, st));
   DVS_TRY(dvs_bgr_to_gray_device(ctx, (const uint8_t*)d_in, 1, rows, cols, (size_t)cols * 3, 0, (uint8_t*)d_out, cols, 0, variant));
   DVS_HIP(hipMemcpy2DAsync(gray, gray_step, d_out, cols, cols, rows, hipMemcpyDeviceToHost, st));
@@ -408,8 +397,8 @@ dvs_status dvs_filter_depth_batch_device(dvs_matcher* ctx, const dvs_keypoint* d
   DVS_ARG(ctx && d_kps && d_n && d_depth && d_out_kps && d_n_out && nframes >= 0 && stride_rows > 0 && rows > 0 && cols > 0);
   DVS_ARG(!d_desc || d_out_desc);
   if (nframes == 0) return DVS_OK;
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipLaunchKernelGGL(k_filter_depth, dim3(nframes), dim3(256), 0, matcher_stream(ctx), d_kps, d_desc, d_n, 0, stride_rows, d_depth,
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_filter_depth, dim3(nframes), dim3(256), 0, ctx->stream, d_kps, d_desc, d_n, 0, stride_rows, d_depth,
                      (uint64_t)step_bytes, (uint64_t)frame_stride_bytes, rows, cols, min_depth, max_depth, d_out_kps, d_out_desc, d_out_index, d_n_out,
                      (int*)nullptr, 0);
   DVS_HIP(hipGetLastError());
@@ -423,8 +412,8 @@ dvs_status dvs_filter_depth(dvs_matcher* ctx, const dvs_keypoint* kps, const uin
   *n_out = 0;
   if (n == 0) return DVS_OK;
   DVS_ARG(kps && out_kps && (!desc || out_desc));
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   // Everything through the matcher's pinned block, read and written by the kernel itself over PCIe (each byte once; of the depth
   // image only the n pixels under the keypoints): no copy commands, and the host polls the sequence number the kernel publishes.
   const size_t kb = ((size_t)n * sizeof(dvs_keypoint) + 15) & ~(size_t)15, db = (size_t)n * 32, ib = ((size_t)n * 4 + 16 + 15) & ~(size_t)15;
@@ -460,8 +449,8 @@ dvs_status dvs_filter_matches(dvs_matcher* ctx, const int32_t* train_idx, const 
   *n_out = 0;
   if (n == 0) return DVS_OK;
   DVS_ARG(train_idx && dist && out_triplets);
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   int* base;
   DVS_TRY(matcher_scratch(ctx, 0, (size_t)n * 4 * 5 + 16, (void**)&base));
   int *d_i = base, *d_d = base + n, *d_o = base + 2 * n, *d_n = base + 5 * n;
@@ -487,8 +476,8 @@ dvs_status dvs_backproject(dvs_matcher* ctx, const dvs_keypoint* kps, int32_t n,
   // a keypoint whose rounded position lies outside the depth image is DROPPED, on this host entry point exactly as in
   // k_backproject / k_publish_keyframe / filterDepth's bounds check (the reference indexes the depth image unchecked there,
   // frontend.cpp:737: undefined behaviour, never a result to reproduce)
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   const size_t kb = ((size_t)n * sizeof(dvs_keypoint) + 15) & ~(size_t)15;
   uint8_t* base;
   DVS_TRY(matcher_scratch(ctx, 0, kb + 96 + (size_t)n * 24 + (size_t)n * 4 + 16 + (size_t)rows * cols * 2 + 32, (void**)&base));
@@ -531,8 +520,8 @@ static dvs_status associate_impl(dvs_matcher* ctx, const uint8_t* obs_desc, cons
   for (int i = 0; i < nobs; i++) best[i] = -1;
   if (nlm == 0) return DVS_OK;
   DVS_ARG(lm_desc && lm_xyz);
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   // (float)d < max_desc with integer d  <=>  d < ceil(max_desc)
   const int thr = (int)std::min<double>(ceil(max_descriptor_distance), 257.0);
   const long long* d_offs; const int* d_pairs; long long total = 0;
@@ -616,8 +605,8 @@ dvs_status dvs_publish_keyframe_device(dvs_matcher* ctx, const dvs_keyframe_head
   DVS_ARG(n == 0 || (d_kps && d_desc && d_depth));
   KfHead H;
   DVS_TRY(kf_head(hdr, &H));
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   double* d_Rt;
   DVS_TRY(matcher_scratch(ctx, 3, 96, (void**)&d_Rt));
   double Rt[12];
@@ -635,8 +624,8 @@ dvs_status dvs_publish_keyframe(dvs_matcher* ctx, const dvs_keyframe_header* hdr
   DVS_ARG(ctx && hdr && out && out_size && n >= 0 && rows > 0 && cols > 0 && R && t);
   DVS_ARG(n == 0 || (kps && desc && depth));
   const size_t need = dvs_keyframe_cdr_capacity(hdr->frame_id, n);
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   uint8_t* base;
   const size_t kb = ((size_t)n * sizeof(dvs_keypoint) + 63) & ~(size_t)63, db = ((size_t)n * 32 + 63) & ~(size_t)63,
                zb = ((size_t)rows * cols * 2 + 63) & ~(size_t)63, ob = (need + 63) & ~(size_t)63;
@@ -721,8 +710,8 @@ dvs_status dvs_harris_responses_device(dvs_matcher* ctx, const uint8_t* d_img, i
   DVS_ARG(ctx && n >= 0 && rows > 0 && cols > 0 && step >= (size_t)cols && block_size >= 1 && block_size <= 8);
   if (n == 0) return DVS_OK;
   DVS_ARG(d_img && d_x && d_y && d_response);
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipLaunchKernelGGL(k_harris, dim3((n + 3) / 4), dim3(256), 0, matcher_stream(ctx), d_img, rows, cols, (uint64_t)step, d_x, d_y, n, block_size, k,
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_harris, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_img, rows, cols, (uint64_t)step, d_x, d_y, n, block_size, k,
                      d_response);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
@@ -733,8 +722,8 @@ dvs_status dvs_harris_responses(dvs_matcher* ctx, const uint8_t* img, int32_t ro
   DVS_ARG(ctx && n >= 0 && rows > 0 && cols > 0 && step >= (size_t)cols && block_size >= 1 && block_size <= 8);
   if (n == 0) return DVS_OK;
   DVS_ARG(img && x && y && response);
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   uint8_t* base;
   const size_t ib = ((size_t)rows * cols + 63) & ~(size_t)63, nb = ((size_t)n * 4 + 63) & ~(size_t)63;
   DVS_TRY(matcher_scratch(ctx, 0, ib + 3 * nb, (void**)&base));

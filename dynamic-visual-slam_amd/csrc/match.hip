@@ -16,12 +16,10 @@
 #include <vector>
 #include <atomic>
 #include <algorithm>
-#include "common.h"
 #include "io_pinned.h"
+#include "matcher.h"
 
 namespace dvs {
-
-typedef unsigned long long u64;
 
 // kSplit: train-set slices per workgroup (one wavefront each): finer waves balance the last scheduling round
 // kQPL:   queries per lane: every scalar train row feeds kQPL independent popcount chains
@@ -156,35 +154,27 @@ __global__ __launch_bounds__(1024) void k_match_lds(const u64* __restrict__ q, c
   }
   const int qi = q0 + ql;
   const u64* qp = q + ((size_t)pair * qStrideRows + (qi < nq ? qi : q0)) * 4;
-  const u64 a0 = qp[0], a1 = qp[1], a2 = qp[2], a3 = qp[3];
+  const u64 a[4] = {qp[0], qp[1], qp[2], qp[3]};
   __syncthreads();
   const int slice = w * 4 + quarter;            // 64 slices of the train set
   const int chunk = (nt + 63) / 64;
   const int jb = min(nt, slice * chunk), je = min(nt, jb + chunk);
   unsigned bestp = 0xFFFFFFFFu;
-  auto dist = [&](u64 r0, u64 r1, u64 r2, u64 r3) -> unsigned {
-    return (unsigned)(__popcll(a0 ^ r0) + __popcll(a1 ^ r1) + __popcll(a2 ^ r2) + __popcll(a3 ^ r3));
-  };
+  auto dist = [&](const u64* r) -> unsigned { return (unsigned)hamming256(a, r); };
   const u64* rows = staged ? trows : tp;
   if (staged) {
     int j = jb;
     for (; j + 4 <= je; j += 4) {   // four rows' reads in flight
       const ulonglong2* r = reinterpret_cast<const ulonglong2*>(trows + (size_t)j * 4);
-      ulonglong2 v[8];
+      u64 v[16];
 #pragma unroll
-      for (int k = 0; k < 8; k++) v[k] = r[k];
+      for (int k = 0; k < 8; k++) { const ulonglong2 x = r[k]; v[2 * k] = x.x; v[2 * k + 1] = x.y; }
 #pragma unroll
-      for (int k = 0; k < 4; k++) bestp = min(bestp, (dist(v[2 * k].x, v[2 * k].y, v[2 * k + 1].x, v[2 * k + 1].y) << 23) | (unsigned)(j + k));
+      for (int k = 0; k < 4; k++) bestp = min(bestp, (dist(v + 4 * k) << 23) | (unsigned)(j + k));
     }
-    for (; j < je; j++) {
-      const u64* r = trows + (size_t)j * 4;
-      bestp = min(bestp, (dist(r[0], r[1], r[2], r[3]) << 23) | (unsigned)j);
-    }
+    for (; j < je; j++) bestp = min(bestp, (dist(trows + (size_t)j * 4) << 23) | (unsigned)j);
   } else {
-    for (int j = jb; j < je; j++) {
-      const u64* r = rows + (size_t)j * 4;
-      bestp = min(bestp, (dist(r[0], r[1], r[2], r[3]) << 23) | (unsigned)j);
-    }
+    for (int j = jb; j < je; j++) bestp = min(bestp, (dist(rows + (size_t)j * 4) << 23) | (unsigned)j);
   }
   bestp = min(bestp, (unsigned)__shfl_xor((int)bestp, 16));
   bestp = min(bestp, (unsigned)__shfl_xor((int)bestp, 32));
@@ -256,17 +246,42 @@ static inline void launch_match_few(hipStream_t st, dim3 grid, const u64* q, con
 // kernel of >= 32 jobs; fewer jobs take NQ = 2 (twice the workgroups: at 8..31 jobs the machine is not full and latency counts).
 // Same-box (64-frame step): 0.4673 ms (rounds 2-4's kernels) -> 0.4426 (int8 in-kernel) -> 0.436 (this).  HBM: 9.2 MB per 64 jobs = the
 // algorithmic bytes.  Bit-exact against the oracle: tests/test_gpu_match.py, tests/test_gpu_pipeline.py.
+// Top-K (K = 2..4: knnMatch, match_modes.hip).  The key of a (query, train row) pair is 64 (|q| - d) + 63 - code, unique within a lane's
+// chunk, so the order of keys is (distance asc, row asc).  The epilogue keeps a per-lane top-K of the keys instead of one maximum: for
+// each accumulator value v, from the bottom of the list up, key[s] = med3(key[s-1], key[s], v), then key[0] = max(key[0], v) — K VALU
+// operations per value where the arg-min takes one.  After each chunk the lane's K keys are decoded to (cval, row) and merged into the
+// running list (later chunks hold higher rows: existing entries win ties); rows past the count (the clamped repeats of row nt - 1,
+// which rank below every real row) are dropped there.  At the end the two half-lane lists of a query (interleaved rows) are merged
+// through one exchange of K (cval, row) pairs.  K = 1 (the arg-min) shares everything but the per-chunk update, which stays its own.
 // =============================================================================================================================
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-template <int NQ>
+// (cval, row) ordering of the top-K lists: larger cval (= smaller distance) first, lower train row on ties.  A function of its own: written
+// into knn_insert's `if`, hipcc branches where it now selects (K = 2..4: a quarter to a half more instructions)
+__device__ __forceinline__ bool knn_before(int c, int i, int bc, int bi) { return c > bc || (c == bc && i < bi); }
+
+// insert (c, i) into the sorted list (bc, bi)[0, K): the displaced element moves one place down, the last one falls off
+template <int K>
+__device__ __forceinline__ void knn_insert(int* bc, int* bi, int c, int i) {
+#pragma unroll
+  for (int s = 0; s < K; s++) {
+    if (knn_before(c, i, bc[s], bi[s])) {
+      const int tc = bc[s], ti = bi[s];
+      bc[s] = c; bi[s] = i; c = tc; i = ti;
+    }
+  }
+}
+
+template <int NQ, int K>
 __global__ __launch_bounds__(256) void k_match_fp4(const uint8_t* __restrict__ q, const int* __restrict__ nqArr, int qStrideRows,
                                                    const uint8_t* __restrict__ t, const int* __restrict__ ntArr, int tStrideRows,
                                                    const uint8_t* __restrict__ t0, const int* __restrict__ nt0,
                                                    int* __restrict__ outIdx, int* __restrict__ outDist) {
   constexpr int kTile = 4 * 1024 + 128;   // four 1-KB fragments (k-steps) + the 32 row constants (f32) of a 32-row tile
+  // the tile loop is unrolled for the arg-min only: with four tiles in flight the top-K lists spill
+  constexpr int kTileUnroll = K == 1 ? 4 : 1;
   __shared__ uint32_t lut[256];           // 8 descriptor bits -> 8 FP4 nibbles of 0 / 1.0
   __shared__ __attribute__((aligned(16))) uint8_t tl[2][kTile];
   int pair = blockIdx.y, qt = blockIdx.x;
@@ -307,9 +322,11 @@ __global__ __launch_bounds__(256) void k_match_fp4(const uint8_t* __restrict__ q
     for (int j = 0; j < 4; j++) bq[u][j] = nib(word(v, j));
   }
   const int nchunks = (nt + 127) >> 7, ntiles = nchunks * 4;
-  int bestc[NQ], besti[NQ];
+  int bc[NQ][K], bi[NQ][K];   // the running lists: (cval, row), INT_MIN / INT_MAX while empty
 #pragma unroll
-  for (int u = 0; u < NQ; u++) { bestc[u] = INT_MIN; besti[u] = -1; }
+  for (int u = 0; u < NQ; u++)
+#pragma unroll
+    for (int s = 0; s < K; s++) { bc[u][s] = INT_MIN; bi[u][s] = INT_MAX; }
   const int lanePart = (r >> 3) * 4 + (r & 3);   // the row's place among the 16 accumulator registers of the lane that holds it
   // this wavefront's k-step of a tile (word w of every row half) and, for the wavefront whose turn it is, the tile's row constants
   auto expand = [&](int tile, const uint4& v, uint8_t* buf) {
@@ -323,6 +340,11 @@ __global__ __launch_bounds__(256) void k_match_fp4(const uint8_t* __restrict__ q
       if (h == 0) *reinterpret_cast<float*>(buf + 4096 + (((r >> 2) & 1) * 16 + lanePart) * 4) = (float)c;
     }
   };
+  // the train row of an accumulator key of chunk c (exact as an int: every term is an integer below 2^24); k >> 6 is |q| - distance
+  auto key_row = [&](int c, int k) {
+    const int code = 63 - (k & 63);
+    return c * 128 + (code >> 4) * 32 + ((code >> 2) & 3) * 8 + h * 4 + (code & 3);
+  };
   auto load = [&](int tile) -> uint4 { return *reinterpret_cast<const uint4*>(tb + (size_t)min(tile * 32 + r, nt - 1) * 32); };
   uint4 wnext = make_uint4(0u, 0u, 0u, 0u);
   if (ntiles > 0) {
@@ -331,10 +353,12 @@ __global__ __launch_bounds__(256) void k_match_fp4(const uint8_t* __restrict__ q
   }
   __syncthreads();
   for (int c = 0; c < nchunks; c++) {
-    float key[NQ];
+    float key[NQ][K];
 #pragma unroll
-    for (int u = 0; u < NQ; u++) key[u] = -3.0e38f;
+    for (int u = 0; u < NQ; u++)
 #pragma unroll
+      for (int s = 0; s < K; s++) key[u][s] = -3.0e38f;
+#pragma unroll kTileUnroll
     for (int m = 0; m < 4; m++) {
       const int tile = c * 4 + m;
       const uint4 wcur = wnext;
@@ -363,26 +387,48 @@ __global__ __launch_bounds__(256) void k_match_fp4(const uint8_t* __restrict__ q
 #pragma unroll
       for (int u = 0; u < NQ; u++)
 #pragma unroll
-        for (int i = 0; i < 16; i++) key[u] = fmaxf(key[u], acc[u][i]);
+        for (int i = 0; i < 16; i++) {
+          const float v = acc[u][i];
+#pragma unroll
+          for (int s = K - 1; s > 0; s--) key[u][s] = __builtin_amdgcn_fmed3f(key[u][s - 1], key[u][s], v);
+          key[u][0] = fmaxf(key[u][0], v);
+        }
       __syncthreads();   // tile + 1 is complete for everyone; everyone has read tile's buffer, which tile + 2 overwrites
     }
 #pragma unroll
     for (int u = 0; u < NQ; u++) {
-      const int k = (int)key[u];   // exact: every term is an integer below 2^24
-      const int cval = k >> 6, code = 63 - (k & 63);
-      const int row = c * 128 + (code >> 4) * 32 + ((code >> 2) & 3) * 8 + h * 4 + (code & 3);
-      if (cval > bestc[u]) { bestc[u] = cval; besti[u] = row; }   // later chunks hold higher rows: strict '>' keeps the lowest on ties
+      if constexpr (K == 1) {
+        // the arg-min keeps its own epilogue, with no list loop: the generic one cost 3 % (43.4 -> 45.0 us on 64 jobs of 2000 x 2000;
+        // even a one-trip loop here changes how hipcc lays out the tile loop).  A row past the count cannot win (its constant is 32768
+        // lower), and later chunks hold higher rows: strict '>' keeps the lowest on ties
+        const int k = (int)key[u][0];
+        if ((k >> 6) > bc[u][0]) { bc[u][0] = k >> 6; bi[u][0] = key_row(c, k); }
+      } else {
+#pragma unroll
+        for (int s = 0; s < K; s++) {   // every lane sees 64 values per chunk: the list is full
+          const int k = (int)key[u][s], row = key_row(c, k);
+          if (row < nt) knn_insert<K>(bc[u], bi[u], k >> 6, row);
+        }
+      }
     }
   }
 #pragma unroll
   for (int u = 0; u < NQ; u++) {
-    const int oc = __shfl_xor(bestc[u], 32), oi = __shfl_xor(besti[u], 32);   // the two lane halves hold interleaved rows of the same query
-    int bc = bestc[u], bi = besti[u];
-    if (oc > bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
+    int oc[K], oi[K];   // the two lane halves hold interleaved rows of the same query
+#pragma unroll
+    for (int s = 0; s < K; s++) { oc[s] = __shfl_xor(bc[u][s], 32); oi[s] = __shfl_xor(bi[u][s], 32); }
+#pragma unroll
+    for (int s = 0; s < K; s++) knn_insert<K>(bc[u], bi[u], oc[s], oi[s]);
     const int qi = (qtile0 + u) * 32 + r;
     if (lane < 32 && qi < nq) {
-      outIdx[(size_t)pair * qStrideRows + qi] = nt > 0 ? bi : -1;
-      outDist[(size_t)pair * qStrideRows + qi] = nt > 0 ? popq[u] - bc : INT_MAX;
+      int* oI = outIdx + ((size_t)pair * qStrideRows + qi) * K;
+      int* oD = outDist + ((size_t)pair * qStrideRows + qi) * K;
+#pragma unroll
+      for (int s = 0; s < K; s++) {
+        const bool ok = K == 1 ? nt > 0 : bi[u][s] != INT_MAX;
+        oI[s] = ok ? bi[u][s] : -1;
+        oD[s] = ok ? popq[u] - bc[u][s] : INT_MAX;
+      }
     }
   }
 }
@@ -398,13 +444,9 @@ __global__ __launch_bounds__(256) void k_thresh_count(const u64* __restrict__ q,
   if (qi >= nq) return;
   const int lane = (int)(threadIdx.x & 63);
   const u64* qp = q + (size_t)qi * 4;
-  const u64 a0 = qp[0], a1 = qp[1], a2 = qp[2], a3 = qp[3];
+  const u64 a[4] = {qp[0], qp[1], qp[2], qp[3]};
   int c = 0;
-  for (int j = lane; j < nt; j += 64) {
-    const u64* r = t + (size_t)j * 4;
-    const int d = __popcll(a0 ^ r[0]) + __popcll(a1 ^ r[1]) + __popcll(a2 ^ r[2]) + __popcll(a3 ^ r[3]);
-    c += d < maxDist ? 1 : 0;
-  }
+  for (int j = lane; j < nt; j += 64) c += hamming256(a, t + (size_t)j * 4) < maxDist ? 1 : 0;
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
   if (lane == 0) counts[qi] = c;
 }
@@ -416,15 +458,14 @@ __global__ __launch_bounds__(256) void k_thresh_write(const u64* __restrict__ q,
   if (qi >= nq) return;
   const int lane = (int)(threadIdx.x & 63);
   const u64* qp = q + (size_t)qi * 4;
-  const u64 a0 = qp[0], a1 = qp[1], a2 = qp[2], a3 = qp[3];
+  const u64 a[4] = {qp[0], qp[1], qp[2], qp[3]};
   long long o = offs[qi];
   for (int j0 = 0; j0 < nt; j0 += 64) {
     const int j = j0 + lane;
     int d = 0;
     bool hit = false;
     if (j < nt) {
-      const u64* r = t + (size_t)j * 4;
-      d = __popcll(a0 ^ r[0]) + __popcll(a1 ^ r[1]) + __popcll(a2 ^ r[2]) + __popcll(a3 ^ r[3]);
+      d = hamming256(a, t + (size_t)j * 4);
       hit = d < maxDist;
     }
     const unsigned long long b = __ballot(hit);
@@ -459,32 +500,6 @@ __global__ __launch_bounds__(1024) void k_scan_counts(const int* __restrict__ co
 
 using namespace dvs;
 
-// NQ = 4 query tiles per wavefront from 32 jobs on (a full machine: 64 jobs x 4 workgroups of 512 queries), NQ = 2 below (twice the
-// workgroups: 8 frames per step 82 -> 89 k frames/s against NQ = 4, 16 frames 116 -> 119 k; NQ = 1 gains nothing more)
-static inline void launch_match_fp4(hipStream_t st, int npairs, const uint8_t* q, const int* nq, int qStrideRows, const uint8_t* t, const int* nt, int tStrideRows,
-                                    const uint8_t* t0, const int* nt0, int* idx, int* dist) {
-  if (npairs >= 32)
-    hipLaunchKernelGGL(dvs::k_match_fp4<4>, dim3((qStrideRows + 511) / 512, npairs), dim3(256), 0, st, q, nq, qStrideRows, t, nt, tStrideRows, t0, nt0, idx, dist);
-  else
-    hipLaunchKernelGGL(dvs::k_match_fp4<2>, dim3((qStrideRows + 255) / 256, npairs), dim3(256), 0, st, q, nq, qStrideRows, t, nt, tStrideRows, t0, nt0, idx, dist);
-}
-
-struct dvs_matcher {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  // grow-only staging for the host entry points
-  void *d_q = nullptr, *d_t = nullptr, *d_idx = nullptr, *d_dist = nullptr, *d_counts = nullptr, *d_offs = nullptr, *d_pairs = nullptr;
-  size_t cq = 0, ct = 0, cidx = 0, ccounts = 0, cpairs = 0;
-  void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};  // grow-only buffers of the glue entry points (frontend.hip)
-  size_t cscratch[4] = {0, 0, 0, 0};
-  void* d_zero = nullptr;  // 64 zero bytes: the empty predecessor of dvs_match_hamming_sequence_device
-  int use_mfma = 1;        // DVS_MATCH_MFMA=0 keeps every job on the popcount kernel
-  // pinned in / out block of the small host entry points (RANSAC stages): inputs are placed here and imported by a kernel, results
-  // are exported by a kernel that publishes a sequence number the host polls — no copy commands, no stream wait
-  void* h_io = nullptr; size_t cio = 0;
-  int* h_seq = nullptr; int io_seq = 0;
-};
-
 namespace {
 dvs_status grow(void** p, size_t* cap, size_t need) {
   if (need <= *cap && *p) return DVS_OK;
@@ -494,15 +509,67 @@ dvs_status grow(void** p, size_t* cap, size_t need) {
   *cap = need;
   return DVS_OK;
 }
+
+template <int NQ>
+void launch_match_fp4_nq(hipStream_t st, int k, int npairs, const uint8_t* q, const int* nq, int qs, const uint8_t* t, const int* nt, int ts,
+                         const uint8_t* t0, const int* nt0, int* idx, int* dist) {
+  const dim3 grid((qs + 128 * NQ - 1) / (128 * NQ), npairs), block(256);
+  switch (k) {
+    case 1: hipLaunchKernelGGL((k_match_fp4<NQ, 1>), grid, block, 0, st, q, nq, qs, t, nt, ts, t0, nt0, idx, dist); break;
+    case 2: hipLaunchKernelGGL((k_match_fp4<NQ, 2>), grid, block, 0, st, q, nq, qs, t, nt, ts, t0, nt0, idx, dist); break;
+    case 3: hipLaunchKernelGGL((k_match_fp4<NQ, 3>), grid, block, 0, st, q, nq, qs, t, nt, ts, t0, nt0, idx, dist); break;
+    default: hipLaunchKernelGGL((k_match_fp4<NQ, 4>), grid, block, 0, st, q, nq, qs, t, nt, ts, t0, nt0, idx, dist); break;
+  }
+}
+
+// The arg-min of npairs jobs (job p: query rows q[p] against train rows t[p]; job 0 against t0 / nt0 when t0 is given), on the
+// matrix cores above mfma_above_rows query rows in all (and with 16-byte aligned bases), else on the popcount kernels: a few jobs
+// favour wavefront count over per-wave efficiency, many take the throughput shape <8, 2>.
+void enqueue_argmin(dvs_matcher* m, const uint8_t* q, const int* nq, int qs, const uint8_t* t, const int* nt, int ts, int npairs,
+                    const uint8_t* t0, const int* nt0, int* idx, int* dist, long long mfma_above_rows) {
+  const long long rows = (long long)npairs * qs;
+  if (m->use_mfma && rows > mfma_above_rows && ts > 0 && (((uintptr_t)q | (uintptr_t)t | (uintptr_t)t0) & 15) == 0)
+    launch_match_fp4(m->stream, 1, npairs, q, nq, qs, t, nt, ts, t0, nt0, idx, dist);
+  else if (rows <= 16384)
+    launch_match_few(m->stream, dim3((qs + 63) / 64, npairs), (const u64*)q, nq, 0, qs, (const u64*)t, nt, 0, ts, idx, dist, ts, (const u64*)t0, nt0);
+  else
+    hipLaunchKernelGGL((k_match<8, 2>), dim3((qs + 127) / 128, npairs), dim3(512), 0, m->stream, (const u64*)q, nq, 0, qs, (const u64*)t, nt, 0, ts,
+                       idx, dist, (const u64*)t0, nt0);
+}
+
+dvs_status create_matcher(int device, bool own_stream, hipStream_t stream, dvs_matcher** out) {
+  DVS_ARG(out);
+  *out = nullptr;
+  DVS_TRY(check_device(device));
+  dvs_matcher* m = new (std::nothrow) dvs_matcher();
+  if (!m) { set_error("out of host memory"); return DVS_ERR_HIP; }
+  m->device = device;
+  if (own_stream) {
+    hipError_t e = hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { delete m; set_error("hipStreamCreate: %s", hipGetErrorString(e)); return DVS_ERR_HIP; }
+    stream = m->own_stream;
+  }
+  m->stream = stream;
+  m->use_mfma = env_switch("DVS_MATCH_MFMA", 1) != 0;
+  *out = m;
+  return DVS_OK;
+}
 }  // namespace
 
 namespace dvs {
+// NQ = 4 query tiles per wavefront from 32 jobs on (a full machine: 64 jobs x 4 workgroups of 512 queries), NQ = 2 below (twice the
+// workgroups: 8 frames per step 82 -> 89 k frames/s against NQ = 4, 16 frames 116 -> 119 k; NQ = 1 gains nothing more)
+void launch_match_fp4(hipStream_t st, int k, int npairs, const uint8_t* q, const int* nq, int qStrideRows, const uint8_t* t, const int* nt,
+                      int tStrideRows, const uint8_t* t0, const int* nt0, int* idx, int* dist) {
+  if (npairs >= 32) launch_match_fp4_nq<4>(st, k, npairs, q, nq, qStrideRows, t, nt, tStrideRows, t0, nt0, idx, dist);
+  else launch_match_fp4_nq<2>(st, k, npairs, q, nq, qStrideRows, t, nt, tStrideRows, t0, nt0, idx, dist);
+}
+
 dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out) {
   DVS_TRY(grow(&m->scratch[slot], &m->cscratch[slot], bytes));
   *out = m->scratch[slot];
   return DVS_OK;
 }
-hipStream_t matcher_stream(dvs_matcher* m) { return m->stream; }
 dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq, int** counter) {
   if (bytes > m->cio || !m->h_io) {
     if (m->h_io) { DVS_HIP(hipStreamSynchronize(m->stream)); DVS_HIP(hipHostFree(m->h_io)); m->h_io = nullptr; m->cio = 0; }
@@ -514,11 +581,7 @@ dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq,
   *out = m->h_io; *h_seq = m->h_seq; *counter = &m->io_seq;
   return DVS_OK;
 }
-int matcher_device(dvs_matcher* m) { return m->device; }
-int matcher_use_mfma(dvs_matcher* m) { return m->use_mfma; }
 
-// every (query, train) pair with distance < max_dist as (q, t, dist) triplets in (q, t) order, LEFT ON THE DEVICE:
-// offsets[nq + 1] (exclusive, 64-bit) and the triplet array.  Host inputs are staged; synchronises once for the total.
 dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,
                                  const int** d_pairs, long long* total) {
   DVS_HIP(hipSetDevice(m->device));
@@ -550,32 +613,11 @@ dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const
 
 extern "C" {
 
-dvs_status dvs_matcher_create(int32_t device, dvs_matcher** out) {
-  DVS_ARG(out);
-  *out = nullptr;
-  DVS_TRY(check_device(device));
-  dvs_matcher* m = new (std::nothrow) dvs_matcher();
-  if (!m) { set_error("out of host memory"); return DVS_ERR_HIP; }
-  m->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) { delete m; set_error("hipStreamCreate: %s", hipGetErrorString(e)); return DVS_ERR_HIP; }
-  m->stream = m->own_stream;
-  m->use_mfma = dvs::env_switch("DVS_MATCH_MFMA", 1) != 0;
-  *out = m;
-  return DVS_OK;
-}
+dvs_status dvs_matcher_create(int32_t device, dvs_matcher** out) { return create_matcher(device, true, nullptr, out); }
 
+// no stream of its own: every HIP stream is a hardware queue
 dvs_status dvs_matcher_create_on_stream(int32_t device, void* hip_stream, dvs_matcher** out) {
-  DVS_ARG(out);
-  *out = nullptr;
-  DVS_TRY(check_device(device));
-  dvs_matcher* m = new (std::nothrow) dvs_matcher();
-  if (!m) { set_error("out of host memory"); return DVS_ERR_HIP; }
-  m->device = device;
-  m->stream = (hipStream_t)hip_stream;  // no stream of its own: every HIP stream is a hardware queue
-  m->use_mfma = dvs::env_switch("DVS_MATCH_MFMA", 1) != 0;
-  *out = m;
-  return DVS_OK;
+  return create_matcher(device, false, (hipStream_t)hip_stream, out);
 }
 
 void dvs_matcher_destroy(dvs_matcher* m) {
@@ -619,23 +661,8 @@ dvs_status dvs_match_hamming_batch_device(dvs_matcher* m, const uint8_t* d_q, co
   DVS_ARG(t_stride_rows < (1 << 23));  // k_match packs the train index into 23 bits
   if (npairs == 0) return DVS_OK;
   DVS_HIP(hipSetDevice(m->device));
-  const bool few = (long long)npairs * q_stride_rows <= 16384;  // a few jobs: favour wavefront count over per-wave efficiency
-  if (few) {
-    launch_match_few(m->stream, dim3((q_stride_rows + 63) / 64, npairs), (const u64*)d_q, d_nq, 0, q_stride_rows, (const u64*)d_t, d_nt, 0, t_stride_rows,
-                     d_idx, d_dist, t_stride_rows);
-    DVS_HIP(hipGetLastError());
-    return DVS_OK;
-  }
-  // many large jobs: the contraction runs on the matrix cores, operands built in the kernel (16-byte row loads: other bases take k_match)
-  if (m->use_mfma && t_stride_rows > 0 && (((uintptr_t)d_q | (uintptr_t)d_t) & 15) == 0) {
-    launch_match_fp4(m->stream, npairs, d_q, d_nq, q_stride_rows, d_t, d_nt, t_stride_rows, nullptr, nullptr, d_idx, d_dist);
-    DVS_HIP(hipGetLastError());
-    return DVS_OK;
-  }
-  constexpr int kSplit = 8, kQPL = 2;
-  dim3 grid((q_stride_rows + 64 * kQPL - 1) / (64 * kQPL), npairs);
-  hipLaunchKernelGGL((k_match<kSplit, kQPL>), grid, dim3(64 * kSplit), 0, m->stream, (const u64*)d_q, d_nq, 0, q_stride_rows, (const u64*)d_t, d_nt, 0,
-                     t_stride_rows, d_idx, d_dist);
+  // up to 16 384 query rows the few-jobs kernels, above them the matrix cores (operands built in the kernel: 16-byte row loads)
+  enqueue_argmin(m, d_q, d_nq, q_stride_rows, d_t, d_nt, t_stride_rows, npairs, nullptr, nullptr, d_idx, d_dist, 16384);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
@@ -656,25 +683,14 @@ dvs_status dvs_match_hamming_sequence_device(dvs_matcher* m, const uint8_t* d_de
     }
     d_prev_desc = (const uint8_t*)m->d_zero; d_prev_n = (const int32_t*)m->d_zero;
   }
-  // from 7 frames of 2 000 descriptors on (the four-stream schedule's match stream; up to 6 frames a lane matches from LDS, k_match_lds):
-  // with the operands built in the kernel the matrix-core match needs no second launch and wins earlier than rounds 2-4's 16 384 rows
-  // (8 frames per step 82.2 -> 90 k frames/s, 7: 77.2 -> 81.5 k; 6 frames on a lane: no gain)
-  constexpr long long kMfmaMinRows = 14000;
-  if (m->use_mfma && (long long)nframes * stride_rows > kMfmaMinRows && (((uintptr_t)d_desc | (uintptr_t)d_prev_desc) & 15) == 0) {
-    // job p = frame p against frame p - 1 (job 0: the predecessor block): train base shifted back by one frame, never dereferenced for job 0
-    launch_match_fp4(m->stream, nframes, d_desc, d_n, stride_rows, d_desc - (size_t)stride_rows * 32, d_n - 1, stride_rows, d_prev_desc, d_prev_n, d_idx, d_dist);
-    DVS_HIP(hipGetLastError());
-    return DVS_OK;
-  }
-  // a few jobs (everything below the matrix-core threshold): favour wavefront count over per-wave efficiency, as the batch entry point does —
-  // one 2000 x 2000 job on <8, 2> occupies 16 workgroups for 39 us
-  // train of job p >= 1 = frame p - 1: the base pointers are shifted back by one frame and never dereferenced for job 0
-  if ((long long)nframes * stride_rows <= 16384)
-    launch_match_few(m->stream, dim3((stride_rows + 63) / 64, nframes), (const u64*)d_desc, d_n, 0, stride_rows,
-                     (const u64*)(d_desc - (size_t)stride_rows * 32), d_n - 1, 0, stride_rows, d_idx, d_dist, stride_rows, (const u64*)d_prev_desc, d_prev_n);
-  else   // DVS_MATCH_MFMA=0 with many jobs: the throughput shape
-    hipLaunchKernelGGL((k_match<8, 2>), dim3((stride_rows + 127) / 128, nframes), dim3(512), 0, m->stream, (const u64*)d_desc, d_n, 0, stride_rows,
-                       (const u64*)(d_desc - (size_t)stride_rows * 32), d_n - 1, 0, stride_rows, d_idx, d_dist, (const u64*)d_prev_desc, d_prev_n);
+  // the matrix cores from 7 frames of 2 000 descriptors on (the four-stream schedule's match stream; up to 6 frames a lane matches from
+  // LDS, k_match_lds): with the operands built in the kernel the matrix-core match needs no second launch and wins earlier than rounds
+  // 2-4's 16 384 rows (8 frames per step 82.2 -> 90 k frames/s, 7: 77.2 -> 81.5 k; 6 frames on a lane: no gain).  Below: the few-jobs
+  // kernels, as the batch entry point — one 2000 x 2000 job on <8, 2> occupies 16 workgroups for 39 us.
+  // Job p = frame p against frame p - 1 (job 0: the predecessor block): the train base is shifted back by one frame, never dereferenced
+  // for job 0.
+  enqueue_argmin(m, d_desc, d_n, stride_rows, d_desc - (size_t)stride_rows * 32, d_n - 1, stride_rows, nframes, d_prev_desc, d_prev_n, d_idx, d_dist,
+                 14000);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }

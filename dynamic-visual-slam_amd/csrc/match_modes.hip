@@ -5,198 +5,19 @@
 //   cross:    query i keeps j = argmin_j d(i, .) only if i = argmin_i d(., j) (lowest index on ties on both sides)
 //   radius:   every pair with (float)d <= maxDistance, per query in train order, then ordered as std::sort by distance alone orders it
 // Kernels:
-//   k_knn_fp4<NQ, K>  2 <= k <= 4 on the matrix cores: k_match_fp4's operand build and MFMA loop, a top-K epilogue
-//   k_knn_hist        any k (and every k under DVS_MATCH_MFMA=0): one wavefront per query, distance histogram + ordered emit
-//   k_cross_keep      the mutual-pair filter over two runs of the existing arg-min (q -> t and t -> q)
-//   k_radius_sort     per-query std::sort replica (lsort.h) of the pairs k_thresh_count / k_thresh_write found
+//   k_match_fp4<NQ, K>  2 <= k <= 4 on the matrix cores (match.hip): the arg-min's operand build and MFMA loop, a top-K epilogue
+//   k_knn_hist          any k (and every k under DVS_MATCH_MFMA=0): one wavefront per query, distance histogram + ordered emit
+//   k_cross_keep        the mutual-pair filter over two runs of the existing arg-min (q -> t and t -> q)
+//   k_radius_sort       per-query std::sort replica (lsort.h) of the pairs k_thresh_count / k_thresh_write found
 #include <limits.h>
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
-#include "common.h"
+#include "matcher.h"
 #include "lsort.h"
 
 namespace dvs {
-
-typedef unsigned long long u64;
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-// match.hip
-dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out);
-hipStream_t matcher_stream(dvs_matcher* m);
-int matcher_device(dvs_matcher* m);
-int matcher_use_mfma(dvs_matcher* m);
-dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,
-                                 const int** d_pairs, long long* total);
-
-// (cval, row) ordering of the top-K lists: larger cval (= smaller distance) first, lower train row on ties
-__device__ __forceinline__ bool knn_before(int c, int i, int bc, int bi) { return c > bc || (c == bc && i < bi); }
-
-// insert (c, i) into the sorted list (bc, bi)[0, K): the displaced element moves one place down, the last one falls off
-template <int K>
-__device__ __forceinline__ void knn_insert(int* bc, int* bi, int c, int i) {
-#pragma unroll
-  for (int s = 0; s < K; s++) {
-    if (knn_before(c, i, bc[s], bi[s])) {
-      const int tc = bc[s], ti = bi[s];
-      bc[s] = c; bi[s] = i; c = tc; i = ti;
-    }
-  }
-}
-
-// =============================================================================================================================
-// Top-K on the matrix cores (2 <= K <= 4).  Operands, row constants and the MFMA loop are k_match_fp4's (match.hip: the key of a
-// (query, train row) pair is 64 (|q| - d) + 63 - code, code = the row's place among the 64 rows a lane holds per 128-row chunk, so keys
-// are unique within a lane's chunk and their order is (distance asc, row asc)).  The epilogue keeps a per-lane top-K of the keys
-// instead of one maximum: for each accumulator value v, from the bottom of the list up, key[s] = med3(key[s-1], key[s], v), then
-// key[0] = max(key[0], v) — K VALU operations per value where the arg-min takes one.  After each chunk the lane's K keys are decoded
-// to (cval, row) and merged into the running list (later chunks hold higher rows: existing entries win ties); rows past the count
-// (the clamped repeats of row nt - 1, which rank below every real row) are dropped there.  At the end the two half-lane lists of a
-// query (interleaved rows) are merged through one exchange of K (cval, row) pairs.
-// =============================================================================================================================
-template <int NQ, int K>
-__global__ __launch_bounds__(256) void k_knn_fp4(const uint8_t* __restrict__ q, const int* __restrict__ nqArr, int qStrideRows,
-                                                 const uint8_t* __restrict__ t, const int* __restrict__ ntArr, int tStrideRows,
-                                                 int* __restrict__ outIdx, int* __restrict__ outDist) {
-  constexpr int kTile = 4 * 1024 + 128;
-  __shared__ uint32_t lut[256];
-  __shared__ __attribute__((aligned(16))) uint8_t tl[2][kTile];
-  int pair = blockIdx.y, qt = blockIdx.x;
-  if ((gridDim.y & 7) == 0) {   // pair p entirely on XCD p % 8 (as k_match_fp4)
-    const int lid = blockIdx.x + gridDim.x * blockIdx.y, xcd = lid & 7, k = lid >> 3;
-    pair = xcd + 8 * (k / (int)gridDim.x);
-    qt = k % (int)gridDim.x;
-  }
-  const int nq = min(max(nqArr[pair], 0), qStrideRows);
-  const int nt = min(max(ntArr[pair], 0), tStrideRows);
-  if (qt * 128 * NQ >= nq) return;   // uniform over the workgroup
-  const int lane = threadIdx.x & 63, h = lane >> 5, r = lane & 31;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  {
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) o |= ((threadIdx.x >> i) & 1u) ? 2u << (4 * i) : 0u;
-    lut[threadIdx.x] = o;
-  }
-  __syncthreads();
-  auto nib = [&](uint32_t x) -> v4i {
-    return v4i{(int)lut[x & 255u], (int)lut[(x >> 8) & 255u], (int)lut[(x >> 16) & 255u], (int)lut[x >> 24]};
-  };
-  auto word = [](const uint4& v, int i) -> uint32_t { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); };
-  const uint8_t* qb = q + (size_t)pair * qStrideRows * 32 + 16 * h;
-  const uint8_t* tb = t + (ptrdiff_t)pair * tStrideRows * 32 + 16 * h;
-  v4i bq[NQ][4];
-  int popq[NQ];
-  const int qtile0 = (qt * 4 + w) * NQ;
-#pragma unroll
-  for (int u = 0; u < NQ; u++) {
-    const int row = min((qtile0 + u) * 32 + r, nq - 1);
-    const uint4 v = *reinterpret_cast<const uint4*>(qb + (size_t)row * 32);
-    const int ph = __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
-    popq[u] = ph + __shfl_xor(ph, 32);
-#pragma unroll
-    for (int j = 0; j < 4; j++) bq[u][j] = nib(word(v, j));
-  }
-  const int nchunks = (nt + 127) >> 7, ntiles = nchunks * 4;
-  int bc[NQ][K], bi[NQ][K];
-#pragma unroll
-  for (int u = 0; u < NQ; u++)
-#pragma unroll
-    for (int s = 0; s < K; s++) { bc[u][s] = INT_MIN; bi[u][s] = INT_MAX; }
-  const int lanePart = (r >> 3) * 4 + (r & 3);
-  auto expand = [&](int tile, const uint4& v, uint8_t* buf) {
-    *reinterpret_cast<v4i*>(buf + w * 1024 + lane * 16) = nib(w == 0 ? v.x : (w == 1 ? v.y : (w == 2 ? v.z : v.w)));
-    if ((tile & 3) == w) {
-      const int ph = __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
-      const int pop = ph + __shfl_xor(ph, 32);
-      const int code = (tile & 3) * 16 + lanePart;
-      const int c = 63 - code - 64 * pop - (tile * 32 + r < nt ? 0 : 32768);
-      if (h == 0) *reinterpret_cast<float*>(buf + 4096 + (((r >> 2) & 1) * 16 + lanePart) * 4) = (float)c;
-    }
-  };
-  auto load = [&](int tile) -> uint4 { return *reinterpret_cast<const uint4*>(tb + (size_t)min(tile * 32 + r, nt - 1) * 32); };
-  uint4 wnext = make_uint4(0u, 0u, 0u, 0u);
-  if (ntiles > 0) {
-    expand(0, load(0), tl[0]);
-    wnext = load(1);
-  }
-  __syncthreads();
-  for (int c = 0; c < nchunks; c++) {
-    float key[NQ][K];
-#pragma unroll
-    for (int u = 0; u < NQ; u++)
-#pragma unroll
-      for (int s = 0; s < K; s++) key[u][s] = -3.0e38f;
-#pragma unroll 1
-    for (int m = 0; m < 4; m++) {   // (not unrolled: with four tiles in flight the top-K lists spill)
-      const int tile = c * 4 + m;
-      const uint4 wcur = wnext;
-      wnext = load(tile + 2);
-      if (tile + 1 < ntiles) expand(tile + 1, wcur, tl[(tile + 1) & 1]);
-      const uint8_t* buf = tl[tile & 1];
-      v16f rc;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const float4 f = *reinterpret_cast<const float4*>(buf + 4096 + h * 64 + i * 16);
-        rc[4 * i] = f.x; rc[4 * i + 1] = f.y; rc[4 * i + 2] = f.z; rc[4 * i + 3] = f.w;
-      }
-      v16f acc[NQ];
-#pragma unroll
-      for (int u = 0; u < NQ; u++) acc[u] = rc;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const v4i a4 = *reinterpret_cast<const v4i*>(buf + j * 1024 + lane * 16);
-        const v8i a = v8i{a4.x, a4.y, a4.z, a4.w, 0, 0, 0, 0};
-#pragma unroll
-        for (int u = 0; u < NQ; u++) {
-          const v8i b = v8i{bq[u][j].x, bq[u][j].y, bq[u][j].z, bq[u][j].w, 0, 0, 0, 0};
-          acc[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc[u], 4, 4, 0, 0x7f7f7f7f, 0, (int)0x86868686u);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < NQ; u++)
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-          const float v = acc[u][i];
-#pragma unroll
-          for (int s = K - 1; s > 0; s--) key[u][s] = __builtin_amdgcn_fmed3f(key[u][s - 1], key[u][s], v);
-          key[u][0] = fmaxf(key[u][0], v);
-        }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int u = 0; u < NQ; u++)
-#pragma unroll
-      for (int s = 0; s < K; s++) {
-        const int k = (int)key[u][s];   // every lane sees 64 values per chunk: the list is full
-        const int cval = k >> 6, code = 63 - (k & 63);
-        const int row = c * 128 + (code >> 4) * 32 + ((code >> 2) & 3) * 8 + h * 4 + (code & 3);
-        if (row < nt) knn_insert<K>(bc[u], bi[u], cval, row);
-      }
-  }
-#pragma unroll
-  for (int u = 0; u < NQ; u++) {
-    int oc[K], oi[K];
-#pragma unroll
-    for (int s = 0; s < K; s++) { oc[s] = __shfl_xor(bc[u][s], 32); oi[s] = __shfl_xor(bi[u][s], 32); }
-#pragma unroll
-    for (int s = 0; s < K; s++) knn_insert<K>(bc[u], bi[u], oc[s], oi[s]);
-    const int qi = (qtile0 + u) * 32 + r;
-    if (lane < 32 && qi < nq) {
-      int* oI = outIdx + ((size_t)pair * qStrideRows + qi) * K;
-      int* oD = outDist + ((size_t)pair * qStrideRows + qi) * K;
-#pragma unroll
-      for (int s = 0; s < K; s++) {
-        const bool ok = bi[u][s] != INT_MAX;
-        oI[s] = ok ? bi[u][s] : -1;
-        oD[s] = ok ? popq[u] - bc[u][s] : INT_MAX;
-      }
-    }
-  }
-}
 
 // =============================================================================================================================
 // Any k: one wavefront per query, two passes over the job's train rows (64 consecutive rows per trip, coalesced).
@@ -219,17 +40,14 @@ __global__ __launch_bounds__(256) void k_knn_hist(const u64* __restrict__ q, con
   if (qi >= nq) return;   // the waves of a workgroup share no data: no workgroup barrier below
   int* hb = hist[w];
   const u64* qp = q + ((size_t)pair * qStrideRows + qi) * 4;
-  const u64 a0 = qp[0], a1 = qp[1], a2 = qp[2], a3 = qp[3];
+  const u64 a[4] = {qp[0], qp[1], qp[2], qp[3]};
   const u64* tp = t + (size_t)pair * tStrideRows * 4;
   int* oI = outIdx + ((size_t)pair * qStrideRows + qi) * (size_t)k;
   int* oD = outDist + ((size_t)pair * qStrideRows + qi) * (size_t)k;
   const int kk = min(k, nt);
   for (int s = kk + lane; s < k; s += 64) { oI[s] = -1; oD[s] = INT_MAX; }
   if (kk == 0) return;
-  auto dist = [&](int j) -> int {
-    const u64* r = tp + (size_t)j * 4;
-    return __popcll(a0 ^ r[0]) + __popcll(a1 ^ r[1]) + __popcll(a2 ^ r[2]) + __popcll(a3 ^ r[3]);
-  };
+  auto dist = [&](int j) -> int { return hamming256(a, tp + (size_t)j * 4); };
   for (int i = lane; i < kHistBins; i += 64) hb[i] = 0;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -318,16 +136,6 @@ __global__ __launch_bounds__(256) void k_radius_sort(const long long* __restrict
 
 using namespace dvs;
 
-template <int K>
-static void launch_knn_fp4(hipStream_t st, int npairs, const uint8_t* q, const int* nq, int qs, const uint8_t* t, const int* nt, int ts, int* idx, int* dist) {
-  // k_match_fp4's shapes: NQ = 4 query tiles per wavefront from 32 jobs on, 2 below.  With the tile loop rolled neither spills
-  // (kernel-resource-usage, K = 2 / 3 / 4: NQ = 4 195 / 216 / 225 VGPRs, NQ = 2 125 / 127 / 118)
-  if (npairs >= 32)
-    hipLaunchKernelGGL((k_knn_fp4<4, K>), dim3((qs + 511) / 512, npairs), dim3(256), 0, st, q, nq, qs, t, nt, ts, idx, dist);
-  else
-    hipLaunchKernelGGL((k_knn_fp4<2, K>), dim3((qs + 255) / 256, npairs), dim3(256), 0, st, q, nq, qs, t, nt, ts, idx, dist);
-}
-
 extern "C" {
 
 dvs_status dvs_match_hamming_knn_batch_device(dvs_matcher* m, const uint8_t* d_q, const int32_t* d_nq, int32_t q_stride_rows,
@@ -338,16 +146,12 @@ dvs_status dvs_match_hamming_knn_batch_device(dvs_matcher* m, const uint8_t* d_q
   DVS_ARG(t_stride_rows < (1 << 23));
   if (npairs == 0) return DVS_OK;
   if (k == 1) return dvs_match_hamming_batch_device(m, d_q, d_nq, q_stride_rows, d_t, d_nt, t_stride_rows, npairs, d_idx, d_dist);
-  DVS_HIP(hipSetDevice(matcher_device(m)));
-  hipStream_t st = matcher_stream(m);
-  if (matcher_use_mfma(m) && k <= 4 && t_stride_rows > 0 && (((uintptr_t)d_q | (uintptr_t)d_t) & 15) == 0) {
-    if (k == 2) launch_knn_fp4<2>(st, npairs, d_q, d_nq, q_stride_rows, d_t, d_nt, t_stride_rows, d_idx, d_dist);
-    else if (k == 3) launch_knn_fp4<3>(st, npairs, d_q, d_nq, q_stride_rows, d_t, d_nt, t_stride_rows, d_idx, d_dist);
-    else launch_knn_fp4<4>(st, npairs, d_q, d_nq, q_stride_rows, d_t, d_nt, t_stride_rows, d_idx, d_dist);
-  } else {
-    hipLaunchKernelGGL(k_knn_hist, dim3((q_stride_rows + 3) / 4, npairs), dim3(256), 0, st, (const u64*)d_q, d_nq, q_stride_rows, (const u64*)d_t, d_nt,
-                       t_stride_rows, k, d_idx, d_dist);
-  }
+  DVS_HIP(hipSetDevice(m->device));
+  if (m->use_mfma && k <= 4 && t_stride_rows > 0 && (((uintptr_t)d_q | (uintptr_t)d_t) & 15) == 0)
+    launch_match_fp4(m->stream, k, npairs, d_q, d_nq, q_stride_rows, d_t, d_nt, t_stride_rows, nullptr, nullptr, d_idx, d_dist);
+  else
+    hipLaunchKernelGGL(k_knn_hist, dim3((q_stride_rows + 3) / 4, npairs), dim3(256), 0, m->stream, (const u64*)d_q, d_nq, q_stride_rows, (const u64*)d_t,
+                       d_nt, t_stride_rows, k, d_idx, d_dist);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
@@ -363,7 +167,7 @@ dvs_status dvs_match_hamming_cross_batch_device(dvs_matcher* m, const uint8_t* d
   int* r = nullptr;   // the reverse arg-min (train -> query), idx then dist
   DVS_TRY(matcher_scratch(m, 3, (size_t)npairs * t_stride_rows * 8, (void**)&r));
   DVS_TRY(dvs_match_hamming_batch_device(m, d_t, d_nt, t_stride_rows, d_q, d_nq, q_stride_rows, npairs, r, r + (size_t)npairs * t_stride_rows));
-  hipLaunchKernelGGL(k_cross_keep, dim3((q_stride_rows + 255) / 256, npairs), dim3(256), 0, matcher_stream(m), d_nq, q_stride_rows, (const int*)r,
+  hipLaunchKernelGGL(k_cross_keep, dim3((q_stride_rows + 255) / 256, npairs), dim3(256), 0, m->stream, d_nq, q_stride_rows, (const int*)r,
                      t_stride_rows, d_idx, d_dist);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
@@ -375,8 +179,8 @@ namespace {
 // host entry points: q / t staged in scratch slots 0 / 1, the two counts and the outputs in slot 2, one job on the device entry point
 template <class F>
 dvs_status run_host_job(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int width, int32_t* idx, int32_t* dist, F&& device_call) {
-  DVS_HIP(hipSetDevice(matcher_device(m)));
-  hipStream_t st = matcher_stream(m);
+  DVS_HIP(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
   uint8_t *dq = nullptr, *dt = nullptr, *dio = nullptr;
   const size_t nout = (size_t)nq * width;
   DVS_TRY(matcher_scratch(m, 0, (size_t)nq * 32, (void**)&dq));
@@ -440,7 +244,7 @@ dvs_status dvs_match_hamming_radius(dvs_matcher* m, const uint8_t* q, int32_t nq
   const int bound = max_distance >= 256.f ? 257 : (int)floorf(max_distance) + 1;
   const long long* d_offs; const int* d_trip; long long total = 0;
   DVS_TRY(matcher_thresh_device(m, q, nq, t, nt, bound, &d_offs, &d_trip, &total));
-  hipStream_t st = matcher_stream(m);
+  hipStream_t st = m->stream;
   DVS_HIP(hipMemcpyAsync(offsets, d_offs, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, st));
   if (total) {
     uint8_t* buf = nullptr;   // keys, then (train, dist) pairs

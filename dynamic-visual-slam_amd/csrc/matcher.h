@@ -1,0 +1,51 @@
+// matcher.h — the matcher handle (dvs_matcher, include/dvslam_hip.h) and the internal entry points of match.hip that the other
+// translation units use.  The handle is also the context of the glue (frontend.hip) and RANSAC (ransac.hip) entry points: its stream,
+// its grow-only device scratch and its pinned in / out block.
+#pragma once
+#include "common.h"
+
+struct dvs_matcher {
+  int device = 0;
+  hipStream_t own_stream = nullptr, stream = nullptr;
+  // grow-only staging for the host entry points
+  void *d_q = nullptr, *d_t = nullptr, *d_idx = nullptr, *d_dist = nullptr, *d_counts = nullptr, *d_offs = nullptr, *d_pairs = nullptr;
+  size_t cq = 0, ct = 0, cidx = 0, ccounts = 0, cpairs = 0;
+  void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};  // grow-only buffers of matcher_scratch
+  size_t cscratch[4] = {0, 0, 0, 0};
+  void* d_zero = nullptr;  // 64 zero bytes: the empty predecessor of dvs_match_hamming_sequence_device
+  int use_mfma = 1;        // DVS_MATCH_MFMA=0 keeps every job on the popcount kernels
+  // pinned in / out block of the small host entry points (RANSAC stages): inputs are placed here and imported by a kernel, results
+  // are exported by a kernel that publishes a sequence number the host polls — no copy commands, no stream wait
+  void* h_io = nullptr; size_t cio = 0;
+  int* h_seq = nullptr; int io_seq = 0;
+};
+
+namespace dvs {
+
+typedef unsigned long long u64;
+
+// popcount(a XOR b) of two 256-bit descriptors (four 64-bit words each)
+__device__ __forceinline__ int hamming256(const u64* a, const u64* b) {
+  return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);
+}
+
+// Slot `slot` (0..3) of the handle's grow-only device scratch, at least `bytes` long.  A slot's contents live until the next call that
+// takes the same slot, so entry points that nest must take different ones:
+//   0  host staging of frontend.hip (dvs_bgr_to_gray input, dvs_filter_matches, dvs_backproject, dvs_publish_keyframe,
+//      dvs_harris_responses) and of every ransac.hip stage; the query rows of match_modes.hip's host entry points
+//   1  dvs_bgr_to_gray output; the train rows of match_modes.hip's host entry points
+//   2  dvs_associate*; the counts and outputs of match_modes.hip's host entry points
+//   3  dvs_publish_keyframe_device's pose; the reverse arg-min of dvs_match_hamming_cross_batch_device; dvs_match_hamming_radius's sort
+dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out);
+// the pinned in / out block (at least `bytes`), its published sequence number and the host-side counter of the last one issued
+dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq, int** counter);
+// candidate pairs (Hamming < max_dist) as (q, t, dist) triplets in (q, t) order + per-query offsets, left on the device (own staging,
+// no scratch slot); synchronises once for the total
+dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,
+                                 const int** d_pairs, long long* total);
+// enqueue k_match_fp4<NQ, k> (1 <= k <= 4) for npairs jobs on st: outputs k (idx, dist) slots per query; q / t / t0 16-byte aligned,
+// tStrideRows > 0; job 0 matches against t0 / nt0 when t0 is given
+void launch_match_fp4(hipStream_t st, int k, int npairs, const uint8_t* q, const int* nq, int qStrideRows, const uint8_t* t, const int* nt,
+                      int tStrideRows, const uint8_t* t0, const int* nt0, int* idx, int* dist);
+
+}  // namespace dvs

@@ -27,13 +27,9 @@
 #include "../../include/dvslam_hip_test.h"
 #endif
 #include "io_pinned.h"
+#include "matcher.h"
 
 namespace dvs {
-
-dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out);
-dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq, int** counter);
-hipStream_t matcher_stream(dvs_matcher* m);
-int matcher_device(dvs_matcher* m);
 
 __host__ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -1030,7 +1026,7 @@ static dvs_status fm_cv_pass(dvs_matcher* ctx, int32_t nprob, const int32_t* off
   int maxn = 0;
   for (int b = 0; b < nprob; b++) maxn = std::max(maxn, offsets[b + 1] - offsets[b]);
   const int total = offsets[nprob];
-  hipStream_t st = matcher_stream(ctx);
+  hipStream_t st = ctx->stream;
   const int H3 = 3 * H;
   const size_t hb = ((size_t)nprob * sizeof(RansacProb) + 15) & ~(size_t)15, pb = ((size_t)total * 8 + 15) & ~(size_t)15;
   const size_t sb = ((size_t)nprob * H * 7 * 4 + 15) & ~(size_t)15;
@@ -1176,8 +1172,8 @@ dvs_status dvs_find_fundamental_ransac_batch(dvs_matcher* ctx, int32_t nprob, co
   if (F9) memset(F9, 0, (size_t)nprob * 72);
   if (total) memset(inlier_mask, 0, (size_t)total);
   if (maxn < 8) return DVS_OK;   // cv::findFundamentalMat needs >= 7 points for FM_RANSAC (8 for our kernel): empty F, masks of zeros
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   const int H = max_iters;
   const size_t hb = ((size_t)nprob * sizeof(RansacProb) + 15) & ~(size_t)15, pb = ((size_t)total * 8 + 15) & ~(size_t)15;
   const size_t inb = hb + 2 * pb;
@@ -1238,7 +1234,7 @@ dvs_status dvs_find_fundamental_cv_batch(dvs_matcher* ctx, int32_t nprob, const 
     if (n < 8) { set_error("dvs_find_fundamental_cv: problem %d has %d correspondences (the reference calls with >= 8, frontend.cpp:627)", b, n); return DVS_ERR_UNSUPPORTED; }
     (n >= 15 ? big : small).push_back(b);
   }
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
+  DVS_HIP(hipSetDevice(ctx->device));
   // ---- >= 15 points: RANSAC.  The adaptive rule ends most loops after a few dozen iterations (10 % outliers: ~10), and the sample
   // sequence is the same whatever the number of samples drawn: first the models of 96 iterations for every problem, then — only for
   // the problems whose loop wanted more — all max_iters (the same result a full run gives, by construction: a prefix of the same sequence).
@@ -1302,8 +1298,8 @@ dvs_status dvs_solve_pnp_ransac_cv_batch(dvs_matcher* ctx, int32_t nprob, const 
   if (n_inliers) memset(n_inliers, 0, (size_t)nprob * 4);
   if (iterations_run) memset(iterations_run, 0, (size_t)nprob * 4);
   memset(rvec3, 0, (size_t)nprob * 24); memset(tvec3, 0, (size_t)nprob * 24);
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   const int H = iterations;
   const size_t hb = ((size_t)nprob * sizeof(RansacProb) + 15) & ~(size_t)15, ob = ((size_t)total * 12 + 15) & ~(size_t)15, ib = ((size_t)total * 8 + 15) & ~(size_t)15;
   const size_t sb = ((size_t)nprob * H * 5 * 4 + 15) & ~(size_t)15;
@@ -1395,8 +1391,8 @@ dvs_status dvs_solve_pnp_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int
   if (n_inliers) memset(n_inliers, 0, (size_t)nprob * 4);
   memset(rvec3, 0, (size_t)nprob * 24); memset(tvec3, 0, (size_t)nprob * 24);
   if (maxn < 4) return DVS_OK;   // cv::solvePnPRansac: "npoints >= 4"
-  DVS_HIP(hipSetDevice(matcher_device(ctx)));
-  hipStream_t st = matcher_stream(ctx);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
   const int H = iterations, H4 = 4 * H;
   const size_t hb = ((size_t)nprob * sizeof(RansacProb) + 15) & ~(size_t)15, ob = ((size_t)total * 12 + 15) & ~(size_t)15, ib = ((size_t)total * 8 + 15) & ~(size_t)15;
   const size_t inb = hb + ob + ib;

@@ -219,7 +219,7 @@ def test_matrix_core_extreme_popcounts_and_unaligned_bases(gpu, oracle):
 
 
 def test_matrix_core_full_machine_shape(gpu, oracle):
-    """from 32 jobs on the matrix-core kernel takes four query tiles per wavefront (k_match_fp4<4>): 40 ragged jobs — counts around the
+    """from 32 jobs on the matrix-core kernel takes four query tiles per wavefront (k_match_fp4<4, 1>): 40 ragged jobs — counts around the
     512-query workgroup, the 128-row chunk and the 32-row tile boundaries, tie-heavy sets — against the oracle, and the XCD re-deal of
     the job index (40 = a multiple of 8)"""
     from dvslam_amd import BFMatcher
