@@ -17,6 +17,10 @@
 
 namespace dvs {
 
+// orb_mask.hip: the keep-mask filter of FAST's candidate lists, cells [c0, c1) of nimg frames
+void launch_cand_mask(const Geom* d_geom, const Cell* d_cells, const CandMask& mk, uint32_t* cand, int* cellCount, int nimg, int c0, int c1,
+                      hipStream_t st);
+
 static inline int cv_round_f(float v) { return (int)lrintf(v); }  // cvRound: round-half-even
 static inline int cv_round_d(double v) { return (int)lrint(v); }
 static inline int cv_floor_f(float v) { int i = (int)v; return i - (i > v); }
@@ -147,6 +151,10 @@ struct dvs_orb {
   int oct_l0[4] = {0, 0, 0, 0};
   size_t oct_smem_cls[3] = {0, 0, 0};
   int oct_nmax_cls[3] = {0, 0, 0}, oct_ptscap_cls[3] = {0, 0, 0};
+  // keep-mask of the call being enqueued (dvs_orb_extract*_masked; null: unmasked).  launch_fast follows every FAST launch with the
+  // candidate filter while it is set; the entry points set it around enqueue_extract only.
+  CandMask mask{};
+  u8* d_mask = nullptr;            // the host entry points' staging copy of the masks [max_batch][rows][cols]: allocated on the first masked call
   int last_nimg = 0;
   ImgSrc last_src{};
   StageTimer timer;
@@ -167,6 +175,8 @@ void free_workspace(dvs_orb* h) {
                   h->d_pyr_alt, h->d_pyr_3rd, h->d_pyr_4th, h->d_pts, h->d_lvlkp3[0], h->d_lvlkp3[1], h->d_lvlkp3[2], h->d_lvlkp3[3], h->d_nodeof, h->d_celloff, h->d_candtotal,
                   h->d_lvlcount3[0], h->d_lvlcount3[1], h->d_lvlcount3[2], h->d_lvlcount3[3], h->d_kps, h->d_desc, h->d_nout, h->d_ticket, h->d_kpsorted, h->d_kpsortidx, h->d_kpident};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  if (h->d_mask) (void)hipFree(h->d_mask);
+  h->d_mask = nullptr;
   for (int k = 1; k < 4; k++) { if (h->d_blur3[k]) (void)hipFree(h->d_blur3[k]); h->d_blur3[k] = nullptr; }   // ([0] = the workspace's block, freed above)
   h->d_blur3[0] = nullptr; h->bset = 0;
   for (int k = 0; k < 4; k++) {   // (set 0 is the pair allocated with the workspace; h->d_cand / h->d_cellcount point at the set in use)
@@ -702,15 +712,18 @@ void launch_fast(dvs_orb* h, const ImgSrc& src, int nimg, hipStream_t fs, int c0
   const Geom& G = h->geom;
   if ((((uintptr_t)src.img0) | src.step0 | src.fstride0) % 4 != 0) {   // rows not dword aligned: the generic workgroup-per-cell kernel
     hipLaunchKernelGGL(k_fast_cell, dim3(c1 - c0, nimg), dim3(256), 0, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0);
-    return;
+  } else {
+    const dim3 grid((c1 - c0 + 3) / 4, nimg);
+    const size_t lds = 4 * (size_t)G.fastWaveLds;
+    // n / grid.x == umulhi(n, 2^32 / grid.x + 1) for every workgroup id n of this grid (n * grid.x < 2^32), else 0: the kernel divides
+    const uint32_t magic = grid.x > 1 && (uint64_t)grid.x * grid.x * nimg < (1ull << 32) ? (uint32_t)((1ull << 32) / grid.x + 1) : 0u;
+    if (G.fastP == 48) hipLaunchKernelGGL(k_fast_wave<48>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
+    else if (G.fastP == 64) hipLaunchKernelGGL(k_fast_wave<64>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
+    else hipLaunchKernelGGL(k_fast_wave<80>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
   }
-  const dim3 grid((c1 - c0 + 3) / 4, nimg);
-  const size_t lds = 4 * (size_t)G.fastWaveLds;
-  // n / grid.x == umulhi(n, 2^32 / grid.x + 1) for every workgroup id n of this grid (n * grid.x < 2^32), else 0: the kernel divides
-  const uint32_t magic = grid.x > 1 && (uint64_t)grid.x * grid.x * nimg < (1ull << 32) ? (uint32_t)((1ull << 32) / grid.x + 1) : 0u;
-  if (G.fastP == 48) hipLaunchKernelGGL(k_fast_wave<48>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
-  else if (G.fastP == 64) hipLaunchKernelGGL(k_fast_wave<64>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
-  else hipLaunchKernelGGL(k_fast_wave<80>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
+  // masked call: the same cells' lists filtered right behind FAST, on its stream — before any after-FAST event, so every schedule
+  // (overlap, async quad-tree, candidate-set ring, lanes) reads filtered lists without an event of its own
+  if (h->mask.mask) launch_cand_mask(h->d_geom, h->d_cells, h->mask, h->d_cand, h->d_cellcount, nimg, c0, c1, fs);
 }
 
 // The announced next batch's level chain on pf_stream into d_pyr_alt, beside THIS batch's FAST: the chain is latency-bound, FAST is
@@ -1244,7 +1257,14 @@ dvs_status dvs_orb_level_size(const dvs_orb* h, int32_t rows, int32_t cols, int3
 dvs_status dvs_orb_extract_batch_device(dvs_orb* h, const uint8_t* d_imgs, int32_t nimg, int32_t rows, int32_t cols,
                                         size_t step, size_t frame_stride, dvs_keypoint* d_kps, uint8_t* d_desc,
                                         int32_t capacity, int32_t* d_n_out) {
+  return dvs_orb_extract_batch_device_masked(h, d_imgs, nimg, rows, cols, step, frame_stride, nullptr, 0, 0, d_kps, d_desc, capacity, d_n_out);
+}
+
+dvs_status dvs_orb_extract_batch_device_masked(dvs_orb* h, const uint8_t* d_imgs, int32_t nimg, int32_t rows, int32_t cols, size_t step,
+                                               size_t frame_stride, const uint8_t* d_masks, size_t mask_step, size_t mask_frame_stride,
+                                               dvs_keypoint* d_kps, uint8_t* d_desc, int32_t capacity, int32_t* d_n_out) {
   DVS_ARG(h && d_kps && d_desc && d_n_out && nimg >= 0);
+  DVS_ARG(!d_masks || mask_step >= (size_t)std::max(cols, 0));
   if (!d_imgs || rows <= 0 || cols <= 0) { set_error("empty image"); return DVS_ERR_EMPTY; }
   DVS_ARG(step >= (size_t)cols);
   if (nimg > h->max_batch) { set_error("nimg %d exceeds max_batch %d", nimg, h->max_batch); return DVS_ERR_CAPACITY; }
@@ -1255,7 +1275,10 @@ dvs_status dvs_orb_extract_batch_device(dvs_orb* h, const uint8_t* d_imgs, int32
   ImgSrc src{d_imgs, (uint64_t)step, (uint64_t)frame_stride, h->d_pyr, ~0u, 0};
   const u8* next = h->next_hint;
   h->next_hint = nullptr;
-  return enqueue_extract(h, src, nimg, d_kps, d_desc, capacity, d_n_out, next, true);
+  h->mask = CandMask{d_masks, (uint64_t)mask_step, (uint64_t)mask_frame_stride};
+  const dvs_status st = enqueue_extract(h, src, nimg, d_kps, d_desc, capacity, d_n_out, next, true);
+  h->mask = CandMask{};
+  return st;
 }
 
 // ---- level-sharded extraction -----------------------------------------------------------------------------------
@@ -1338,23 +1361,42 @@ DVS_HOOK dvs_status dvs_orb_hint_next_batch_device(dvs_orb* h, const uint8_t* d_
 
 dvs_status dvs_orb_extract_batch(dvs_orb* h, const uint8_t* const* imgs, int32_t nimg, int32_t rows, int32_t cols, size_t step,
                                  dvs_keypoint* kps, uint8_t* desc, int32_t capacity, int32_t* n_out) {
+  return dvs_orb_extract_batch_masked(h, imgs, nimg, rows, cols, step, nullptr, 0, kps, desc, capacity, n_out);
+}
+
+dvs_status dvs_orb_extract_batch_masked(dvs_orb* h, const uint8_t* const* imgs, int32_t nimg, int32_t rows, int32_t cols, size_t step,
+                                        const uint8_t* const* masks, size_t mask_step, dvs_keypoint* kps, uint8_t* desc, int32_t capacity,
+                                        int32_t* n_out) {
   DVS_ARG(h && n_out && nimg >= 0);
   for (int i = 0; i < nimg; i++) n_out[i] = 0;
   if (!imgs || rows <= 0 || cols <= 0) { set_error("empty image"); return DVS_ERR_EMPTY; }
   for (int i = 0; i < nimg; i++) if (!imgs[i]) { set_error("empty image %d", i); return DVS_ERR_EMPTY; }
   DVS_ARG(kps && desc && step >= (size_t)cols);
+  if (masks) {
+    DVS_ARG(mask_step >= (size_t)cols);
+    for (int i = 0; i < nimg; i++) if (!masks[i]) { set_error("mask %d is NULL (pass masks = NULL for an unmasked call)", i); return DVS_ERR_ARG; }
+  }
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(ensure_workspace(h, rows, cols));
   const Geom& G = h->geom;
   const int cap = G.outCap;
+  const uint64_t mbytes = (uint64_t)rows * cols;
+  if (masks && !h->d_mask) DVS_HIP(hipMalloc((void**)&h->d_mask, (size_t)h->max_batch * mbytes));   // (freed with the workspace)
   for (int b0 = 0; b0 < nimg; b0 += h->max_batch) {
     const int nb = std::min(h->max_batch, nimg - b0);
     // level 0 staged into the frame's pyramid block (the reference copies it too: copyMakeBorder, :1189)
     for (int i = 0; i < nb; i++)
       DVS_HIP(hipMemcpy2DAsync(h->d_pyr + (uint64_t)i * G.frameBytes + G.lv[0].off, G.lv[0].pitch, imgs[b0 + i], step, cols, rows,
                                hipMemcpyHostToDevice, h->stream));
+    // ... and the masks, packed (the previous chunk's filter read them on this stream before)
+    if (masks)
+      for (int i = 0; i < nb; i++)
+        DVS_HIP(hipMemcpy2DAsync(h->d_mask + (uint64_t)i * mbytes, cols, masks[b0 + i], mask_step, cols, rows, hipMemcpyHostToDevice, h->stream));
     ImgSrc src{h->d_pyr + G.lv[0].off, (uint64_t)G.lv[0].pitch, G.frameBytes, h->d_pyr, ~0u, 0};
-    DVS_TRY(enqueue_extract(h, src, nb, h->d_kps, h->d_desc, cap, h->d_nout));
+    h->mask = masks ? CandMask{h->d_mask, (uint64_t)cols, mbytes} : CandMask{};
+    const dvs_status est = enqueue_extract(h, src, nb, h->d_kps, h->d_desc, cap, h->d_nout);
+    h->mask = CandMask{};
+    DVS_TRY(est);
     if (h->env_host_poll) {
       // results by k_export_host into the pinned block; poll its sequence number (bounded spin, then the stream wait)
       static_assert(sizeof(dvs_keypoint) == 28, "k_export_host copies keypoints as 7 dwords");
@@ -1394,6 +1436,16 @@ dvs_status dvs_orb_extract(dvs_orb* h, const uint8_t* gray, int32_t rows, int32_
   if (!gray || rows <= 0 || cols <= 0) { set_error("empty image"); return DVS_ERR_EMPTY; }
   const uint8_t* one[1] = {gray};
   return dvs_orb_extract_batch(h, one, 1, rows, cols, step, kps, desc, capacity, n_out);
+}
+
+dvs_status dvs_orb_extract_masked(dvs_orb* h, const uint8_t* gray, int32_t rows, int32_t cols, size_t step, const uint8_t* mask, size_t mask_step,
+                                  dvs_keypoint* kps, uint8_t* desc, int32_t capacity, int32_t* n_out) {
+  DVS_ARG(h && n_out);
+  *n_out = 0;
+  if (!gray || rows <= 0 || cols <= 0) { set_error("empty image"); return DVS_ERR_EMPTY; }
+  const uint8_t* one[1] = {gray};
+  const uint8_t* onem[1] = {mask};
+  return dvs_orb_extract_batch_masked(h, one, 1, rows, cols, step, mask ? onem : nullptr, mask_step, kps, desc, capacity, n_out);
 }
 
 dvs_status dvs_orb_get_level(dvs_orb* h, int32_t frame, int32_t level, int32_t blurred, uint8_t* dst, int32_t cap_bytes) {

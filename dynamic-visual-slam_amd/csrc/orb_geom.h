@@ -72,6 +72,9 @@ struct Cell {       // one FAST cell (ORBextractor.cpp:805-827)
   float inv_ng;            // 1.0f / ng — host-made: the two divisions were ~12 vector instructions per cell on the device
 };
 
+// keep-mask of a masked extraction (orb_mask.hip): level-0 sized, nonzero = keep; frame f at mask + f * fstride (0: one mask for all)
+struct CandMask { const uint8_t* mask; uint64_t step, fstride; };
+
 struct BlurTile { int16_t level, tx, ty, pad; };
 
 // resize: one entry per group of 4 output columns — dword-aligned source byte `base`, bit shift that moves the group's first

@@ -85,6 +85,9 @@ def _bind(L):
     L.dvs_event_record.argtypes = [vp, vp]
     L.dvs_stream_wait_event.argtypes = [vp, vp]
     L.dvs_orb_extract_batch_device.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, vp, i32, vp]
+    L.dvs_orb_extract_masked.argtypes = [vp, vp, i32, i32, sz, vp, sz, vp, vp, i32, C.POINTER(i32)]
+    L.dvs_orb_extract_batch_masked.argtypes = [vp, vp, i32, i32, i32, sz, vp, sz, vp, vp, i32, vp]
+    L.dvs_orb_extract_batch_device_masked.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, sz, sz, vp, vp, i32, vp]
     L.dvs_orb_level_block_bytes.argtypes = [vp, i32]; L.dvs_orb_level_block_bytes.restype = sz
     L.dvs_orb_extract_levels_device.argtypes = [vp, vp, i32, i32, i32, sz, sz, C.c_uint32, vp]
     L.dvs_orb_merge_levels_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp]

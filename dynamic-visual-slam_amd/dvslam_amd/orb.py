@@ -25,6 +25,7 @@ class ORBextractor:
         self._h = h
         self.nfeatures, self.nlevels, self.scaleFactor, self.device, self.max_batch = nfeatures, nlevels, scaleFactor, device, max_batch
         self.capacity = self._L.dvs_orb_max_keypoints(self._h)
+        self._honour_mask = False
 
     @classmethod
     def from_handle(cls, handle, nfeatures, nlevels, scaleFactor, device, max_batch, L=None):
@@ -34,6 +35,7 @@ class ORBextractor:
         o.hooks = L is not None and L is not lib()
         o.nfeatures, o.nlevels, o.scaleFactor, o.device, o.max_batch = nfeatures, nlevels, scaleFactor, device, max_batch
         o.capacity = o._L.dvs_orb_max_keypoints(o._h)
+        o._honour_mask = False
         return o
 
     def close(self):
@@ -85,7 +87,14 @@ class ORBextractor:
         return c.value, r.value  # (w, h)
 
     # -- operator() --
+    def honour_mask(self, on=True):
+        """opt in to operator()'s mask argument (default off: ignored, as in the reference).  On, a mask drops FAST candidates on
+        its zero pixels before the quad-tree distributes the quotas (INTEGRATION.md §B1 "Keep masks")"""
+        self._honour_mask = bool(on)
+
     def __call__(self, image, mask=None, vLappingArea=(0, 0)):
+        if self._honour_mask and mask is not None and np.asarray(mask).size:
+            return self.extract_masked(image, mask)
         image = np.asarray(image)
         if image.size == 0:
             return -1, np.zeros(0, KP_DTYPE), np.zeros((0, 32), np.uint8)
@@ -102,7 +111,31 @@ class ORBextractor:
         self._shape = (rows, cols)
         return n.value, kps[:n.value].copy(), desc[:n.value].copy()
 
-    def extract_batch(self, images):
+    @staticmethod
+    def _check_mask(mask, shape):
+        mask = np.asarray(mask)
+        assert mask.dtype == np.uint8 and mask.ndim == 2 and mask.shape == shape, "CV_8UC1 mask of the image's size expected"
+        assert mask.strides[1] == 1
+        return mask
+
+    def extract_masked(self, image, mask):
+        """operator() with a keep mask (uint8, image-sized, nonzero = keep); mask=None is the unmasked call"""
+        image = np.asarray(image)
+        if image.size == 0:
+            return -1, np.zeros(0, KP_DTYPE), np.zeros((0, 32), np.uint8)
+        assert image.dtype == np.uint8 and image.ndim == 2 and image.strides[1] == 1, "CV_8UC1 expected (ORBextractor.cpp:1094)"
+        rows, cols = image.shape
+        mask = None if mask is None else self._check_mask(mask, image.shape)
+        kps = np.zeros(self.capacity, KP_DTYPE)
+        desc = np.zeros((self.capacity, 32), np.uint8)
+        n = C.c_int32()
+        check(self._L.dvs_orb_extract_masked(self._h, ptr(image), rows, cols, image.strides[0], ptr(mask) if mask is not None else None,
+                                             mask.strides[0] if mask is not None else 0, ptr(kps), ptr(desc), self.capacity, C.byref(n)))
+        self._shape = (rows, cols)
+        return n.value, kps[:n.value].copy(), desc[:n.value].copy()
+
+    def extract_batch(self, images, masks=None):
+        """masks: None, or one keep mask per image (dvs_orb_extract_batch_masked)"""
         images = [np.ascontiguousarray(im) for im in images]
         rows, cols = images[0].shape
         n = len(images)
@@ -110,7 +143,14 @@ class ORBextractor:
         kps = np.zeros((n, self.capacity), KP_DTYPE)
         desc = np.zeros((n, self.capacity, 32), np.uint8)
         nout = np.zeros(n, np.int32)
-        check(self._L.dvs_orb_extract_batch(self._h, arr, n, rows, cols, images[0].strides[0], ptr(kps), ptr(desc), self.capacity, ptr(nout)))
+        if masks is not None:
+            masks = [np.ascontiguousarray(self._check_mask(m, (rows, cols))) for m in masks]
+            assert len(masks) == n
+            marr = (C.c_void_p * n)(*[m.ctypes.data for m in masks])
+            check(self._L.dvs_orb_extract_batch_masked(self._h, arr, n, rows, cols, images[0].strides[0], marr, cols, ptr(kps), ptr(desc),
+                                                       self.capacity, ptr(nout)))
+        else:
+            check(self._L.dvs_orb_extract_batch(self._h, arr, n, rows, cols, images[0].strides[0], ptr(kps), ptr(desc), self.capacity, ptr(nout)))
         self._shape = (rows, cols)
         return nout, kps, desc
 
@@ -134,9 +174,17 @@ class ORBextractor:
         """hipEvent_t (int, 0 to clear) recorded behind FAST by every following extract_batch_device (scheduling hook)"""
         check(self._L.dvs_orb_set_after_fast_event(self._h, hip_event or None))
 
-    def extract_batch_device(self, d_imgs, nimg, rows, cols, step, frame_stride, d_kps, d_desc, capacity, d_nout):
-        """raw device pointers (ints); asynchronous on the handle's stream"""
-        check(self._L.dvs_orb_extract_batch_device(self._h, d_imgs, nimg, rows, cols, step, frame_stride, d_kps, d_desc, capacity, d_nout))
+    def extract_batch_device(self, d_imgs, nimg, rows, cols, step, frame_stride, d_kps, d_desc, capacity, d_nout,
+                             d_masks=None, mask_step=None, mask_frame_stride=None):
+        """raw device pointers (ints); asynchronous on the handle's stream.  d_masks: device keep masks, frame f's at
+        d_masks + f * mask_frame_stride (0: one mask for every frame); mask_step defaults to cols, mask_frame_stride to rows * mask_step"""
+        if d_masks:
+            ms = cols if mask_step is None else mask_step
+            mfs = rows * ms if mask_frame_stride is None else mask_frame_stride
+            check(self._L.dvs_orb_extract_batch_device_masked(self._h, d_imgs, nimg, rows, cols, step, frame_stride, d_masks, ms, mfs,
+                                                              d_kps, d_desc, capacity, d_nout))
+        else:
+            check(self._L.dvs_orb_extract_batch_device(self._h, d_imgs, nimg, rows, cols, step, frame_stride, d_kps, d_desc, capacity, d_nout))
         self._shape = (rows, cols)
 
     def level_block_bytes(self, nimg):

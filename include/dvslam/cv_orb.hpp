@@ -69,6 +69,7 @@ class ORB {
   void detectAndCompute(cv::InputArray image, cv::InputArray mask, std::vector<cv::KeyPoint>& keypoints, cv::OutputArray descriptors,
                         bool useProvidedKeypoints = false) {
     if (useProvidedKeypoints) throw std::runtime_error("dvslam::ORB: useProvidedKeypoints is not built");
+    // (cv::ORB resizes the mask to every pyramid level — other semantics than the extractor's keep masks, dvs_orb_extract*_masked)
     if (!mask.empty()) throw std::runtime_error("dvslam::ORB: detection masks are not built");
     if (image.empty()) return;                       // orb.cpp: returns before touching the outputs
     cv::Mat img = image.getMat();

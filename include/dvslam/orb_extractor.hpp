@@ -36,12 +36,19 @@ class OrbExtractor {
   // returns the number of keypoints, or -1 for an empty image; descriptors is resized to n*32 bytes
   int operator()(const uint8_t* gray, int rows, int cols, size_t step, std::vector<dvs_keypoint>& keypoints,
                  std::vector<uint8_t>& descriptors) {
+    return (*this)(gray, rows, cols, step, nullptr, 0, keypoints, descriptors);
+  }
+  // with a keep mask (rows x cols bytes, mask_step between rows, nonzero = keep; NULL = unmasked): FAST candidates on zero pixels are
+  // dropped before the quad-tree shares out the quotas (dvs_orb_extract_masked)
+  int operator()(const uint8_t* gray, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
+                 std::vector<dvs_keypoint>& keypoints, std::vector<uint8_t>& descriptors) {
     keypoints.assign(cap_, dvs_keypoint{});
     descriptors.assign((size_t)cap_ * 32, 0);
     int32_t n = 0;
-    const dvs_status st = dvs_orb_extract(h_, gray, rows, cols, step, keypoints.data(), descriptors.data(), cap_, &n);
+    const dvs_status st = mask ? dvs_orb_extract_masked(h_, gray, rows, cols, step, mask, mask_step, keypoints.data(), descriptors.data(), cap_, &n)
+                               : dvs_orb_extract(h_, gray, rows, cols, step, keypoints.data(), descriptors.data(), cap_, &n);
     if (st == DVS_ERR_EMPTY) { keypoints.clear(); descriptors.clear(); return -1; }
-    if (st != DVS_OK) throw std::runtime_error(std::string("dvs_orb_extract: ") + dvs_last_error());
+    if (st != DVS_OK) throw std::runtime_error(std::string(mask ? "dvs_orb_extract_masked: " : "dvs_orb_extract: ") + dvs_last_error());
     keypoints.resize(n);
     descriptors.resize((size_t)n * 32);
     return n;
@@ -91,14 +98,20 @@ class ORBextractor {
   ORBextractor(int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST)
       : impl_(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST) {}
   ~ORBextractor() {}
-  int operator()(cv::InputArray _image, cv::InputArray /*_mask: ignored, ORBextractor.hpp:57*/, std::vector<cv::KeyPoint>& _keypoints,
+  // _mask: ignored as in the reference (ORBextractor.hpp:57) unless honourMask(true)
+  int operator()(cv::InputArray _image, cv::InputArray _mask, std::vector<cv::KeyPoint>& _keypoints,
                  cv::OutputArray _descriptors, std::vector<int>& /*vLappingArea = {0,0}: stereo branch never fires*/) {
     if (_image.empty()) return -1;
     cv::Mat image = _image.getMat();
     CV_Assert(image.type() == CV_8UC1);
+    cv::Mat mask;
+    if (honour_mask_ && !_mask.empty()) {
+      mask = _mask.getMat();
+      CV_Assert(mask.type() == CV_8UC1 && mask.rows == image.rows && mask.cols == image.cols);
+    }
     std::vector<dvs_keypoint> kps;
     std::vector<uint8_t> desc;
-    const int n = impl_(image.data, image.rows, image.cols, image.step, kps, desc);
+    const int n = impl_(image.data, image.rows, image.cols, image.step, mask.empty() ? nullptr : mask.data, mask.step, kps, desc);
     if (keep_pyramid_) {  // the reference leaves the pyramid of the last frame in this public member (ORBextractor.cpp:1169-1194)
       mvImagePyramid.resize(impl_.GetLevels());
       for (int l = 0; l < impl_.GetLevels(); l++) {
@@ -128,10 +141,15 @@ class ORBextractor {
   // frame: callers that do not need it switch the copy off.
   std::vector<cv::Mat> mvImagePyramid;
   void keepImagePyramid(bool on) { keep_pyramid_ = on; if (!on) mvImagePyramid.clear(); }
+  // Opt-in (default off, as the reference): operator() applies a non-empty _mask — CV_8UC1, the image's size, nonzero = keep — and
+  // drops corners on its zero pixels before the quad-tree shares out the quotas (DynaSLAM / DS-SLAM).  Any other
+  // mask fails CV_Assert.
+  void honourMask(bool on) { honour_mask_ = on; }
 
  private:
   dvslam::OrbExtractor impl_;
   bool keep_pyramid_ = true;
+  bool honour_mask_ = false;
 };
 }  // namespace ORB_SLAM3
 #endif

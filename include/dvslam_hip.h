@@ -117,6 +117,27 @@ dvs_status dvs_orb_extract_batch(dvs_orb* h, const uint8_t* const* imgs, int32_t
 dvs_status dvs_orb_extract_batch_device(dvs_orb* h, const uint8_t* d_imgs, int32_t nimg, int32_t rows, int32_t cols,
                                         size_t step, size_t frame_stride, dvs_keypoint* d_kps, uint8_t* d_desc,
                                         int32_t capacity, int32_t* d_n_out);
+/* ---- keep masks (INTEGRATION.md §B1 "Keep masks"): drop corners on dynamic regions before the quad-tree shares out the quotas ----
+ * A mask is 8-bit, level-0 sized (rows x cols, `mask_step` bytes between rows), nonzero = keep, as in OpenCV.  A FAST candidate of
+ * level l at region-relative (cx, cy) is kept iff mask[min(rows-1, floor(Y))][min(cols-1, floor(X))] != 0 with
+ * X = (float)(cx + 16) * mvScaleFactor[l] (Y alike): the coordinates the keypoint would carry, so no output keypoint lies on a masked
+ * pixel.  Per-cell FAST (threshold 20, else 7), the quotas, the quad-tree, orientation, blur and descriptors are unchanged: a cell
+ * whose threshold-20 corners are all masked does NOT fall back to threshold 7.  An all-nonzero mask gives the unmasked result bit for
+ * bit, an all-zero one 0 keypoints.  A NULL mask (masks array) is exactly the unmasked entry point; mask_step < cols is DVS_ERR_ARG.
+ * After a masked call the candidate hook (dvs_orb_get_candidates) returns the filtered lists.
+ * Not offered: masks for dvs_pipeline_* and the level-sharded dvs_orb_extract_levels_device, dvslam::ORB (OpenCV resizes the mask
+ * per level: other semantics), box lists, and skipping FAST on fully masked cells. */
+dvs_status dvs_orb_extract_masked(dvs_orb* h, const uint8_t* gray, int32_t rows, int32_t cols, size_t step, const uint8_t* mask, size_t mask_step,
+                                  dvs_keypoint* kps, uint8_t* desc, int32_t capacity, int32_t* n_out);
+/* masks[nimg] host masks (NULL: unmasked; otherwise every entry must be set) */
+dvs_status dvs_orb_extract_batch_masked(dvs_orb* h, const uint8_t* const* imgs, int32_t nimg, int32_t rows, int32_t cols, size_t step,
+                                        const uint8_t* const* masks, size_t mask_step, dvs_keypoint* kps, uint8_t* desc, int32_t capacity,
+                                        int32_t* n_out);
+/* frame f's mask at d_masks + f * mask_frame_stride; mask_frame_stride = 0: one mask for every frame (a static hood mask, say).
+ * Read on the handle's stream by the filter behind FAST: keep it unchanged until the call's outputs are complete. */
+dvs_status dvs_orb_extract_batch_device_masked(dvs_orb* h, const uint8_t* d_imgs, int32_t nimg, int32_t rows, int32_t cols, size_t step,
+                                               size_t frame_stride, const uint8_t* d_masks, size_t mask_step, size_t mask_frame_stride,
+                                               dvs_keypoint* d_kps, uint8_t* d_desc, int32_t capacity, int32_t* d_n_out);
 /* ---- level-sharded extraction for SMALL batches on several GPUs (SURVEY.md §8e "Partitioning") --------------------------------
  * With fewer frames in flight than GPUs, frame sharding leaves GPUs idle; the stages after the pyramid are independent per
  * level (ORBextractor.cpp:787, 894, 1123), so every rank takes the same frames and a subset of the LEVELS: it rebuilds the
