@@ -32,10 +32,11 @@ __device__ __forceinline__ int hamming256(const u64* a, const u64* b) {
 // Slot `slot` (0..3) of the handle's grow-only device scratch, at least `bytes` long.  A slot's contents live until the next call that
 // takes the same slot, so entry points that nest must take different ones:
 //   0  host staging of frontend.hip (dvs_bgr_to_gray input, dvs_filter_matches, dvs_backproject, dvs_publish_keyframe,
-//      dvs_harris_responses) and of every ransac.hip stage; the query rows of match_modes.hip's host entry points
+//      dvs_harris_responses) and of dvs_triangulate_landmarks and of every ransac.hip stage; the query rows of match_modes.hip's host entry points
 //   1  dvs_bgr_to_gray output; the train rows of match_modes.hip's host entry points
 //   2  dvs_associate*; the counts and outputs of match_modes.hip's host entry points
-//   3  dvs_publish_keyframe_device's pose; the reverse arg-min of dvs_match_hamming_cross_batch_device; dvs_match_hamming_radius's sort
+//   3  dvs_publish_keyframe_device's pose; the reverse arg-min of dvs_match_hamming_cross_batch_device; dvs_match_hamming_radius's sort;
+//      the At rows of dvs_triangulate_landmarks* for landmarks with more than eight views
 dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out);
 // the pinned in / out block (at least `bytes`), its published sequence number and the host-side counter of the last one issued
 dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq, int** counter);

@@ -17,6 +17,8 @@ class FrontendGlue:
         L.dvs_filter_matches.argtypes = [vp, vp, vp, i32, f32, vp, C.POINTER(i32)]
         L.dvs_backproject.argtypes = [vp, vp, i32, vp, i32, i32, sz, f32, f32, f32, f32, vp, vp, vp, vp, C.POINTER(i32)]
         L.dvs_associate.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, dbl, dbl, dbl, dbl, dbl, dbl, vp]
+        L.dvs_triangulate_landmarks.argtypes = [vp, i32, vp, vp, dbl, dbl, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
+        L.dvs_triangulate_landmarks_device.argtypes = [vp, i32, vp, vp, dbl, dbl, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
         L.dvs_harris_responses.argtypes = [vp, vp, i32, i32, sz, vp, vp, i32, i32, f32, vp]
         L.dvs_keyframe_cdr_capacity.argtypes = [C.c_char_p, i32]; L.dvs_keyframe_cdr_capacity.restype = sz
         L.dvs_publish_keyframe.argtypes = [vp, C.POINTER(KeyframeHeader), vp, vp, i32, vp, i32, i32, sz, f32, f32, f32, f32, vp, vp, vp, sz,
@@ -196,6 +198,19 @@ class FrontendGlue:
         check(self._L.dvs_associate(self._h, ptr(obs_desc), ptr(obs_px), len(obs_desc), ptr(lm_desc), ptr(lm_xyz), len(lm_desc), ptr(R), ptr(t),
                                     fx, fy, cx, cy, max_desc, max_reproj, ptr(best)))
         return best
+
+    def triangulate_landmarks(self, R, t, fx, fy, cx, cy, view_offsets, view_kf, view_px, lm_xyz):
+        """LandmarkInfo::triangulate (backend.cpp:439-613) for every landmark: R (nkf x 3 x 3, x_cam = R X + t), t (nkf x 3); landmark l's
+        views are [view_offsets[l], view_offsets[l + 1]) of view_kf (keyframe index, < 0 skips) / view_px -> (positions float32 (nlm, 3),
+        status int32 (nlm,), dvs_tri_status)"""
+        R = np.ascontiguousarray(R, np.float64).reshape(-1, 9); t = np.ascontiguousarray(t, np.float64).reshape(-1, 3)
+        offs = np.ascontiguousarray(view_offsets, np.int64); vkf = np.ascontiguousarray(view_kf, np.int32)
+        vpx = np.ascontiguousarray(view_px, np.float32).reshape(-1, 2); xyz = np.ascontiguousarray(lm_xyz, np.float32).reshape(-1, 3)
+        nlm = len(offs) - 1
+        out = np.empty_like(xyz); st = np.zeros(nlm, np.int32)
+        check(self._L.dvs_triangulate_landmarks(self._h, len(R), ptr(R), ptr(t), fx, fy, cx, cy, nlm, ptr(offs), ptr(vkf), ptr(vpx), ptr(xyz),
+                                                ptr(out), ptr(st)))
+        return out, st
 
 
 def unpack_keyframe(payload, cap_n=4096):

@@ -490,6 +490,26 @@ dvs_status dvs_associate_candidates(dvs_matcher* ctx, const uint8_t* obs_desc, c
                                     double cy, double max_descriptor_distance, double max_reprojection_distance, int32_t* best,
                                     int64_t* cand_offsets, int32_t* cand_lm, int64_t cand_cap, int64_t* n_cand);
 
+/* LandmarkInfo::triangulate (backend.cpp:439-613) for nlm landmarks in one launch (csrc/triangulate.hip; INTEGRATION.md "Triangulation").
+ * Landmark l's views are [view_offsets[l], view_offsets[l + 1]) of view_kf / view_px, in observation_ids order: keyframe index into R
+ * (nkf x 9, row-major) / t (nkf x 3) and the float pixel.  view_kf < 0 skips the view, as the reference skips an id its find_if does not
+ * find; skipped views do not count.  The pose convention is x_cam = R X + t (P = K [R | t], C = -R^T t): KeyframeInfo::R / t unchanged
+ * reproduce the reference (whose reprojectPoint reads the same R, t the other way round); (R^T, -R^T t) is the consistent binding.
+ * Steps and roundings are the reference's, with two documented departures: the SVD's gamma is sqrt(p * p + beta * beta), not hypot,
+ * and the parallax gate's atan2 is the device's (1 ulp).  status[l] says why a landmark kept its position (lm_xyz_out = lm_xyz_in, bit
+ * for bit, unless DVS_TRI_UPDATED); lm_xyz_out may alias lm_xyz_in.  view_kf >= nkf, view_offsets[0] < 0 or decreasing offsets:
+ * DVS_ERR_ARG.  Host pointers. */
+typedef enum { DVS_TRI_UPDATED = 0, DVS_TRI_FEW_VIEWS, DVS_TRI_LOW_PARALLAX, DVS_TRI_DEGENERATE, DVS_TRI_REPROJECTION, DVS_TRI_DEPTH } dvs_tri_status;
+dvs_status dvs_triangulate_landmarks(dvs_matcher* ctx, int32_t nkf, const double* R, const double* t, double fx, double fy, double cx, double cy,
+                                     int32_t nlm, const int64_t* view_offsets /* nlm + 1 */, const int32_t* view_kf, const float* view_px /* 2 per view */,
+                                     const float* lm_xyz_in, float* lm_xyz_out, int32_t* status);
+/* the same on device pointers, enqueued on the context's stream; it reads view_offsets[nlm] back first (one 8-byte copy) to size the
+ * scratch of landmarks with more than eight views.  The argument checks of the host form run per landmark on the device: a landmark
+ * whose offsets or keyframe indices are out of range keeps its position with status DVS_ERR_ARG. */
+dvs_status dvs_triangulate_landmarks_device(dvs_matcher* ctx, int32_t nkf, const double* d_R, const double* d_t, double fx, double fy, double cx,
+                                            double cy, int32_t nlm, const int64_t* d_view_offsets, const int32_t* d_view_kf, const float* d_view_px,
+                                            const float* d_lm_xyz_in, float* d_lm_xyz_out, int32_t* d_status);
+
 /* ======================================= B3: bundle adjustment ================================= */
 
 typedef struct dvs_ba dvs_ba;
