@@ -20,6 +20,8 @@
 #ifdef DVS_TEST_HOOKS
 #include "../../include/dvslam_hip_test.h"
 #endif
+#include "cv_round.h"
+#include "device_mem.h"
 #include "glibc_sincosf.h"
 #include "orb_device_common.h"
 
@@ -389,20 +391,16 @@ struct dvs_cvorb {
   CvGeom G;
   uint64_t blockBytes = 0;
   int maxw = 0, maxh = 0, totalKeys = 0, totalRows = 0;
-  u8 *d_pyr = nullptr, *d_blur = nullptr, *d_score = nullptr;
-  int *d_xofs = nullptr, *d_yofs = nullptr; uint32_t *d_xc = nullptr, *d_yc = nullptr;
-  int *d_rowCount = nullptr, *d_rowBase = nullptr, *d_levelCount = nullptr, *d_finalCount = nullptr, *d_Lp = nullptr, *d_Rp = nullptr, *d_nout = nullptr;
-  unsigned long long* d_keys = nullptr;
-  CvKeypoint* d_kps = nullptr; u8* d_desc = nullptr;
+  struct Workspace {   // one resolution's device memory (cv_prepare)
+    DeviceBuf<u8> pyr, blur, score;
+    DeviceBuf<int> xofs, yofs; DeviceBuf<uint32_t> xc, yc;
+    DeviceBuf<int> rowCount, rowBase, levelCount, finalCount, Lp, Rp, nout;
+    DeviceBuf<unsigned long long> keys;
+    DeviceBuf<CvKeypoint> kps; DeviceBuf<u8> desc;
+  } ws;
 };
 
 namespace {
-
-inline int cv_round_f(float v) { return (int)lrintf(v); }
-inline int cv_round_d(double v) { return (int)lrint(v); }
-inline int cv_floor_d(double v) { int i = (int)v; return i - (i > v); }
-inline int cv_floor_f(float v) { int i = (int)v; return i - (i > v); }
-inline int cv_ceil_f(float v) { int i = (int)v; return i + (i < v); }
 
 // interpolationLinear<uchar>::getcoeff over one axis (resize.cpp): softdouble arithmetic = IEEE double, one rounding per operation
 // (this file is compiled -ffp-contract=off); coefficients are ufixedpoint16 = cvRound(fraction * 256)
@@ -423,27 +421,11 @@ void build_axis(int ssize, int dsize, std::vector<int>& ofs, std::vector<uint32_
   }
 }
 
-void cv_free(dvs_cvorb* h) {
-  void* p[] = {h->d_pyr, h->d_blur, h->d_score, h->d_xofs, h->d_yofs, h->d_xc, h->d_yc, h->d_rowCount, h->d_rowBase, h->d_levelCount, h->d_finalCount,
-               h->d_Lp, h->d_Rp, h->d_nout, h->d_keys, h->d_kps, h->d_desc};
-  for (void* q : p) if (q) (void)hipFree(q);
-  h->d_pyr = h->d_blur = h->d_score = nullptr; h->d_xofs = h->d_yofs = nullptr; h->d_xc = h->d_yc = nullptr;
-  h->d_rowCount = h->d_rowBase = h->d_levelCount = h->d_finalCount = h->d_Lp = h->d_Rp = h->d_nout = nullptr;
-  h->d_keys = nullptr; h->d_kps = nullptr; h->d_desc = nullptr; h->rows = h->cols = 0;
-}
-
-template <class T>
-dvs_status up(T** d, const std::vector<T>& v) {
-  DVS_HIP(hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  if (!v.empty()) DVS_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return DVS_OK;
-}
-
 // level sizes, quotas, umax (orb.cpp: detectAndCompute / computeKeyPoints) and the device workspace for one resolution
 dvs_status cv_prepare(dvs_cvorb* h, int rows, int cols, int capacity) {
-  if (h->rows == rows && h->cols == cols && h->capacity >= capacity && h->d_pyr) return DVS_OK;
+  if (h->rows == rows && h->cols == cols && h->capacity >= capacity && h->ws.pyr.get()) return DVS_OK;
   DVS_HIP(hipStreamSynchronize(h->stream));
-  cv_free(h);
+  h->ws = dvs_cvorb::Workspace{};   // (a failure below leaves the handle without one: the next call prepares again)
   CvGeom& G = h->G;
   memset(&G, 0, sizeof(G));
   const dvs_cvorb_params& P = h->prm;
@@ -493,12 +475,14 @@ dvs_status cv_prepare(dvs_cvorb* h, int rows, int cols, int capacity) {
     }
   }
   h->blockBytes = off; h->totalKeys = keyOff; h->totalRows = rowOff;
-  DVS_HIP(hipMalloc((void**)&h->d_pyr, off)); DVS_HIP(hipMalloc((void**)&h->d_blur, off)); DVS_HIP(hipMalloc((void**)&h->d_score, off));
-  DVS_TRY(up(&h->d_xofs, xofs)); DVS_TRY(up(&h->d_yofs, yofs)); DVS_TRY(up(&h->d_xc, xc)); DVS_TRY(up(&h->d_yc, yc));
-  DVS_HIP(hipMalloc((void**)&h->d_rowCount, (size_t)rowOff * 4)); DVS_HIP(hipMalloc((void**)&h->d_rowBase, (size_t)rowOff * 4));
-  DVS_HIP(hipMalloc((void**)&h->d_levelCount, nl * 4)); DVS_HIP(hipMalloc((void**)&h->d_finalCount, nl * 4)); DVS_HIP(hipMalloc((void**)&h->d_nout, 4));
-  DVS_HIP(hipMalloc((void**)&h->d_keys, (size_t)keyOff * 8)); DVS_HIP(hipMalloc((void**)&h->d_Lp, (size_t)keyOff * 4)); DVS_HIP(hipMalloc((void**)&h->d_Rp, (size_t)keyOff * 4));
-  DVS_HIP(hipMalloc((void**)&h->d_kps, (size_t)std::max(capacity, 1) * sizeof(CvKeypoint))); DVS_HIP(hipMalloc((void**)&h->d_desc, (size_t)std::max(capacity, 1) * 32));
+  dvs_cvorb::Workspace W;   // moved into the handle only when complete
+  DVS_TRY(W.pyr.alloc(off)); DVS_TRY(W.blur.alloc(off)); DVS_TRY(W.score.alloc(off));
+  DVS_TRY(W.xofs.upload(xofs)); DVS_TRY(W.yofs.upload(yofs)); DVS_TRY(W.xc.upload(xc)); DVS_TRY(W.yc.upload(yc));
+  DVS_TRY(W.rowCount.alloc(rowOff)); DVS_TRY(W.rowBase.alloc(rowOff));
+  DVS_TRY(W.levelCount.alloc(nl)); DVS_TRY(W.finalCount.alloc(nl)); DVS_TRY(W.nout.alloc(1));
+  DVS_TRY(W.keys.alloc(keyOff)); DVS_TRY(W.Lp.alloc(keyOff)); DVS_TRY(W.Rp.alloc(keyOff));
+  DVS_TRY(W.kps.alloc(capacity)); DVS_TRY(W.desc.alloc((size_t)std::max(capacity, 1) * 32));
+  h->ws = std::move(W);
   h->rows = rows; h->cols = cols; h->capacity = capacity;
   return DVS_OK;
 }
@@ -532,9 +516,8 @@ void dvs_cvorb_destroy(dvs_cvorb* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  cv_free(h);
   (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // (frees the workspace)
 }
 
 dvs_status dvs_cvorb_detect_and_compute(dvs_cvorb* h, const uint8_t* gray, int32_t rows, int32_t cols, size_t step, dvs_keypoint* kps, uint8_t* desc,
@@ -546,31 +529,32 @@ dvs_status dvs_cvorb_detect_and_compute(dvs_cvorb* h, const uint8_t* gray, int32
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(cv_prepare(h, rows, cols, capacity));
   const CvGeom& G = h->G;
+  const dvs_cvorb::Workspace& W = h->ws;
   hipStream_t st = h->stream;
-  DVS_HIP(hipMemcpy2DAsync(h->d_pyr + G.lv[0].off, G.lv[0].pitch, gray, step, cols, rows, hipMemcpyHostToDevice, st));
+  DVS_HIP(hipMemcpy2DAsync(W.pyr.get() + G.lv[0].off, G.lv[0].pitch, gray, step, cols, rows, hipMemcpyHostToDevice, st));
   for (int l = 1; l < G.nlevels; l++) {
     const CvLevel &S = G.lv[l - 1], &D = G.lv[l];
-    hipLaunchKernelGGL(k_cv_resize, dim3((D.w + 255) / 256, D.h), dim3(256), 0, st, h->d_pyr + S.off, S.w, S.h, S.pitch, h->d_pyr + D.off, D.w, D.h, D.pitch,
-                       h->d_xofs + D.tx, h->d_xc + D.tx, h->d_yofs + D.ty, h->d_yc + D.ty, D.xlo, D.xhi, D.ylo, D.yhi);
+    hipLaunchKernelGGL(k_cv_resize, dim3((D.w + 255) / 256, D.h), dim3(256), 0, st, W.pyr.get() + S.off, S.w, S.h, S.pitch, W.pyr.get() + D.off, D.w, D.h, D.pitch,
+                       W.xofs.get() + D.tx, W.xc.get() + D.tx, W.yofs.get() + D.ty, W.yc.get() + D.ty, D.xlo, D.xhi, D.ylo, D.yhi);
   }
   const dim3 pix((h->maxw + 255) / 256, h->maxh, G.nlevels);
-  hipLaunchKernelGGL(k_cv_fast, pix, dim3(256), 0, st, G, h->d_pyr, h->d_score);
-  hipLaunchKernelGGL(k_cv_nms<0>, dim3(h->maxh, G.nlevels), dim3(256), 0, st, G, h->d_score, h->d_rowCount, h->d_rowBase, h->d_keys);
-  hipLaunchKernelGGL(k_cv_rowscan, dim3(G.nlevels), dim3(256), 0, st, G, h->d_rowCount, h->d_rowBase, h->d_levelCount);
-  hipLaunchKernelGGL(k_cv_nms<1>, dim3(h->maxh, G.nlevels), dim3(256), 0, st, G, h->d_score, h->d_rowCount, h->d_rowBase, h->d_keys);
-  hipLaunchKernelGGL(k_cv_retain, dim3(G.nlevels), dim3(64), 0, st, G, h->d_pyr, h->d_keys, h->d_Lp, h->d_Rp, h->d_levelCount, h->d_finalCount);
-  hipLaunchKernelGGL(k_cv_blur, pix, dim3(256), 0, st, G, h->d_pyr, h->d_blur);
+  hipLaunchKernelGGL(k_cv_fast, pix, dim3(256), 0, st, G, W.pyr.get(), W.score.get());
+  hipLaunchKernelGGL(k_cv_nms<0>, dim3(h->maxh, G.nlevels), dim3(256), 0, st, G, W.score.get(), W.rowCount.get(), W.rowBase.get(), W.keys.get());
+  hipLaunchKernelGGL(k_cv_rowscan, dim3(G.nlevels), dim3(256), 0, st, G, W.rowCount.get(), W.rowBase.get(), W.levelCount.get());
+  hipLaunchKernelGGL(k_cv_nms<1>, dim3(h->maxh, G.nlevels), dim3(256), 0, st, G, W.score.get(), W.rowCount.get(), W.rowBase.get(), W.keys.get());
+  hipLaunchKernelGGL(k_cv_retain, dim3(G.nlevels), dim3(64), 0, st, G, W.pyr.get(), W.keys.get(), W.Lp.get(), W.Rp.get(), W.levelCount.get(), W.finalCount.get());
+  hipLaunchKernelGGL(k_cv_blur, pix, dim3(256), 0, st, G, W.pyr.get(), W.blur.get());
   // upper bound of the result without a round trip: the caller's capacity; rows past the count do nothing
   if (capacity > 0)
-    hipLaunchKernelGGL(k_cv_describe, dim3((capacity + 3) / 4), dim3(256), 0, st, G, h->d_pyr, h->d_blur, h->d_keys, h->d_finalCount, (CvKeypoint*)h->d_kps,
-                       h->d_desc, capacity, h->d_nout);
+    hipLaunchKernelGGL(k_cv_describe, dim3((capacity + 3) / 4), dim3(256), 0, st, G, W.pyr.get(), W.blur.get(), W.keys.get(), W.finalCount.get(), W.kps.get(),
+                       W.desc.get(), capacity, W.nout.get());
   DVS_HIP(hipGetLastError());
   int n = 0;
   if (capacity > 0) {
-    DVS_HIP(hipMemcpyAsync(&n, h->d_nout, 4, hipMemcpyDeviceToHost, st));
+    DVS_HIP(hipMemcpyAsync(&n, W.nout.get(), 4, hipMemcpyDeviceToHost, st));
   } else {   // count only
     int fc[kCvMaxLevels];
-    DVS_HIP(hipMemcpyAsync(fc, h->d_finalCount, G.nlevels * 4, hipMemcpyDeviceToHost, st));
+    DVS_HIP(hipMemcpyAsync(fc, W.finalCount.get(), G.nlevels * 4, hipMemcpyDeviceToHost, st));
     DVS_HIP(hipStreamSynchronize(st));
     for (int l = 0; l < G.nlevels; l++) n += fc[l];
   }
@@ -579,29 +563,26 @@ dvs_status dvs_cvorb_detect_and_compute(dvs_cvorb* h, const uint8_t* gray, int32
   if (n > capacity) { set_error("%d keypoints > capacity %d (retainBest keeps every keypoint that ties with the last one)", n, capacity); return DVS_ERR_CAPACITY; }
   static_assert(sizeof(CvKeypoint) == sizeof(dvs_keypoint), "cv::KeyPoint layout");
   if (n) {
-    DVS_HIP(hipMemcpy(kps, h->d_kps, (size_t)n * sizeof(dvs_keypoint), hipMemcpyDeviceToHost));
-    DVS_HIP(hipMemcpy(desc, h->d_desc, (size_t)n * 32, hipMemcpyDeviceToHost));
+    DVS_HIP(hipMemcpy(kps, W.kps.get(), (size_t)n * sizeof(dvs_keypoint), hipMemcpyDeviceToHost));
+    DVS_HIP(hipMemcpy(desc, W.desc.get(), (size_t)n * 32, hipMemcpyDeviceToHost));
   }
   return DVS_OK;
 }
 
 dvs_status dvs_cvorb_get_level(dvs_cvorb* h, int32_t level, int32_t blurred, uint8_t* dst, int32_t cap_bytes, int32_t* w, int32_t* hh) {
-  DVS_ARG(h && dst && w && hh && h->d_pyr && level >= 0 && level < h->G.nlevels);
+  DVS_ARG(h && dst && w && hh && h->ws.pyr.get() && level >= 0 && level < h->G.nlevels);
   const CvLevel& L = h->G.lv[level];
   *w = L.w; *hh = L.h;
   if ((int64_t)L.w * L.h > cap_bytes) return DVS_ERR_CAPACITY;
   DVS_HIP(hipSetDevice(h->device));
   DVS_HIP(hipStreamSynchronize(h->stream));
-  DVS_HIP(hipMemcpy2D(dst, L.w, (blurred ? h->d_blur : h->d_pyr) + L.off, L.pitch, L.w, L.h, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy2D(dst, L.w, (blurred ? h->ws.blur : h->ws.pyr).get() + L.off, L.pitch, L.w, L.h, hipMemcpyDeviceToHost));
   return DVS_OK;
 }
 
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h)
-// test hook: KeyPointsFilter::retainBest on bare responses through the kernel's wavefront routine; perm[i] = original index
-dvs_status dvs_test_retain_best_device(const float* responses, int32_t n, int32_t n_points, int32_t* perm, int32_t* n_kept) {
-  DVS_ARG(n >= 0 && n_kept && (n == 0 || (responses && perm)));
-  *n_kept = 0;
-  if (n == 0) return DVS_OK;
+// keys of the retainBest hooks: order word of the response (desc_order on the host) << 32 | original index
+static std::vector<unsigned long long> retain_keys(const float* responses, int n) {
   std::vector<unsigned long long> v(n);
   for (int i = 0; i < n; i++) {
     float r = responses[i]; if (r == 0.f) r = 0.f;
@@ -609,31 +590,28 @@ dvs_status dvs_test_retain_best_device(const float* responses, int32_t n, int32_
     const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     v[i] = ((unsigned long long)(~asc) << 32) | (unsigned)i;
   }
-  unsigned long long* d = nullptr; int *lp = nullptr, *rp = nullptr, *dn = nullptr;
-  hipError_t e = hipMalloc(&d, 8 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc(&lp, 4 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc(&rp, 4 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc(&dn, 4);
-  if (e == hipSuccess) e = hipMemcpy(d, v.data(), 8 * (size_t)n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) { hipLaunchKernelGGL(k_test_retain, dim3(1), dim3(64), 0, 0, d, n, n_points, lp, rp, dn); e = hipGetLastError(); }
+  return v;
+}
+// test hook: KeyPointsFilter::retainBest on bare responses through the kernel's wavefront routine; perm[i] = original index
+dvs_status dvs_test_retain_best_device(const float* responses, int32_t n, int32_t n_points, int32_t* perm, int32_t* n_kept) {
+  DVS_ARG(n >= 0 && n_kept && (n == 0 || (responses && perm)));
+  *n_kept = 0;
+  if (n == 0) return DVS_OK;
+  std::vector<unsigned long long> v = retain_keys(responses, n);
+  DeviceBuf<unsigned long long> d; DeviceBuf<int> lp, rp, dn;
+  DVS_TRY(d.upload(v)); DVS_TRY(lp.alloc(n)); DVS_TRY(rp.alloc(n)); DVS_TRY(dn.alloc(1));
+  hipLaunchKernelGGL(k_test_retain, dim3(1), dim3(64), 0, 0, d.get(), n, n_points, lp.get(), rp.get(), dn.get());
+  DVS_HIP(hipGetLastError());
   int kept = 0;
-  if (e == hipSuccess) e = hipMemcpy(&kept, dn, 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(v.data(), d, 8 * (size_t)n, hipMemcpyDeviceToHost);
-  (void)hipFree(d); (void)hipFree(lp); (void)hipFree(rp); (void)hipFree(dn);
-  DVS_HIP(e);
+  DVS_HIP(hipMemcpy(&kept, dn.get(), 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(v.data(), d.get(), 8 * (size_t)n, hipMemcpyDeviceToHost));
   *n_kept = kept;
   for (int i = 0; i < kept; i++) perm[i] = (int)(uint32_t)v[i];
   return DVS_OK;
 }
 // the same through the sequential statement in lsort.h (host, no GPU): what the wavefront routine restates
 void dvs_test_retain_best_host(const float* responses, int32_t n, int32_t n_points, int32_t* perm, int32_t* n_kept) {
-  std::vector<unsigned long long> v(n);
-  for (int i = 0; i < n; i++) {
-    float r = responses[i]; if (r == 0.f) r = 0.f;
-    uint32_t u; memcpy(&u, &r, 4);
-    const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    v[i] = ((unsigned long long)(~asc) << 32) | (unsigned)i;
-  }
+  std::vector<unsigned long long> v = retain_keys(responses, n);
   int kept = n;
   if (n_points >= 0 && n > n_points) {
     if (n_points == 0) kept = 0;

@@ -1,0 +1,66 @@
+// device_mem.h — owners of what a handle holds on the device: hipMalloc / hipHostMalloc blocks, events, and the rings of buffer sets a
+// pipelined caller's batches rotate through.  Internal to the library; nothing here is exported.  Each resource is freed exactly once
+// because its owner cannot be copied: a handle's "free everything" is the assignment of an empty struct of these.
+#pragma once
+#include <algorithm>
+#include <memory>
+#include <type_traits>
+#include <vector>
+#include "common.h"
+
+namespace dvs {
+
+// Move-only owner of `count` elements of device (Pinned: page-locked host) memory.  Kernels take get(), never the owner.
+template <class T, bool Pinned>
+class Buf {
+ public:
+  T* get() const { return p_.get(); }
+  dvs_status alloc(size_t count) {   // frees what it held; never a zero-byte block
+    p_.reset();
+    T* p = nullptr;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    DVS_HIP(Pinned ? hipHostMalloc((void**)&p, bytes) : hipMalloc((void**)&p, bytes));
+    p_.reset(p);
+    return DVS_OK;
+  }
+  dvs_status upload(const std::vector<T>& v) {
+    DVS_TRY(alloc(v.size()));
+    if (!v.empty()) DVS_HIP(hipMemcpy(get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return DVS_OK;
+  }
+ private:
+  struct Free { void operator()(T* p) const { (void)(Pinned ? hipHostFree(p) : hipFree(p)); } };
+  std::unique_ptr<T, Free> p_;
+};
+template <class T> using DeviceBuf = Buf<T, false>;
+template <class T> using PinnedBuf = Buf<T, true>;
+
+// Move-only owner of an event without timing.  Empty until create(): a handle can be built (and destroyed) without a device.
+class Event {
+ public:
+  hipError_t create() {
+    hipEvent_t e = nullptr;
+    const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    e_.reset(e);
+    return r;
+  }
+  operator hipEvent_t() const { return e_.get(); }
+ private:
+  struct Destroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+  std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Destroy> e_;
+};
+
+// Four slots of which the first `depth` (3 or 4) are used in turn.  A slot is a small struct of owners; its user allocates a slot when
+// the rotation first reaches it.
+template <class Slot>
+struct Ring {
+  Slot slot[4];
+  int idx = 0, depth = 3;
+  Slot& cur() { return slot[idx]; }
+  Slot& next() { return slot[(idx + 1) % depth]; }
+  Slot& at(int k) { return slot[k]; }
+  void advance() { idx = (idx + 1) % depth; }
+  void rewind(int d) { idx = 0; depth = d; }   // everything idle: restart at the first slot, `d` slots from now on
+};
+
+}  // namespace dvs

@@ -10,6 +10,8 @@
 #include <chrono>
 #include <vector>
 #include "common.h"
+#include "cv_round.h"
+#include "device_mem.h"
 #ifdef DVS_TEST_HOOKS
 #include "../../include/dvslam_hip_test.h"
 #endif
@@ -21,10 +23,6 @@ namespace dvs {
 void launch_cand_mask(const Geom* d_geom, const Cell* d_cells, const CandMask& mk, uint32_t* cand, int* cellCount, int nimg, int c0, int c1,
                       hipStream_t st);
 
-static inline int cv_round_f(float v) { return (int)lrintf(v); }  // cvRound: round-half-even
-static inline int cv_round_d(double v) { return (int)lrint(v); }
-static inline int cv_floor_f(float v) { int i = (int)v; return i - (i > v); }
-static inline int cv_ceil_f(float v) { int i = (int)v; return i + (i < v); }
 static inline short sat_short(int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
 static inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
@@ -34,20 +32,120 @@ using namespace dvs;
 
 static int env_int(const char* name, int dflt) { return dvs::env_switch(name, dflt); }   // (util.hip: the one table of switches)
 
+// ---- the rings a pipelined caller's batches rotate through (device_mem.h: Ring).  A slot is allocated when the rotation first reaches it.
+struct PyrSlot { DeviceBuf<u8> pyr; };
+struct BlurSlot { DeviceBuf<u8> blur; };
+struct CandSlot { DeviceBuf<uint32_t> cand; DeviceBuf<int> cellcount; Event done; bool done_valid = false; };   // done: the quad-tree that read the set
+struct LvlSlot { DeviceBuf<uint32_t> lvlkp; DeviceBuf<int> lvlcount; };
+
+// pyramid blocks: cur() = this batch; alt = the announced next batch (built on pf_stream beside this batch's FAST, taken by the next
+// call); third = with deferred descriptor stages the pyramid of the batch before is still being read while the next one is built, so the
+// three rotate (four in the four-stream form).  All but the first are allocated on first use.  Slots A B C (D) over successive calls:
+//   pipelined (every call prefetched, the previous call's stage deferred)      depth 3:  call  1  2  3  4      depth 4:  1  2  3  4  5
+//                                                                                       reads A  B  C  A                A  B  C  D  A
+//                                                                                      builds B  C  A  B                B  C  D  A  B
+//   prefetched, nothing deferred: reads A B A B, builds B A B A at either depth (the third block is never allocated)
+// The chain-graph cache (launch_prefetch) is keyed on the block built into, so these periods set how soon an argument set comes back.
+// The roles are kept as they are, not as offsets from cur(): a call without a pending stage builds into the block the call before
+// read, so after a mix of the two patterns "the block that is neither read nor still being read" is not the next one round the ring.
+struct PyrRing : Ring<PyrSlot> {
+  int alt = 1, third = 2, fourth = 3;
+  void take() { std::swap(idx, alt); }   // the prefetched pyramid becomes this batch's
+  void retire_alt() {   // alt is still being read: build into the oldest instead (depth 4: alt <- third <- fourth <- alt)
+    std::swap(alt, third);
+    if (depth == 4) std::swap(third, fourth);
+  }
+  bool is_own(const u8* p, uint64_t off) const {
+    for (const PyrSlot& s : slot) if (s.pyr.get() && p == s.pyr.get() + off) return true;
+    return false;
+  }
+};
+
+// everything ensure_workspace builds for one resolution; `Workspace{}` frees it
+struct Workspace {
+  size_t batch = 1;                // frames every block is sized for (dvs_orb::max_batch)
+  Geom geom;
+  DeviceBuf<Geom> d_geom;
+  DeviceBuf<Cell> d_cells;
+  DeviceBuf<BlurTile> d_tiles;
+  DeviceBuf<BlurStrip> d_strips;
+  DeviceBuf<BlurCol> d_blurcols;   // matrix-core blur: work items + operand fragment table (k_blur_mfma)
+  DeviceBuf<uint4> d_blurtab;
+  int n_blurcols = 0, blur_avt = 0;
+  bool blur_mfma_ok = false;       // weights fit the int8 band products (0 .. 127, sum 256)
+  DeviceBuf<ResizeGroup> d_rgroups;
+  DeviceBuf<PyrTile> d_pyrtiles;
+  DeviceBuf<int> d_xofs, d_alpha, d_yofs, d_beta;
+  PyrRing pyr;
+  // ... and its blur on the MAIN stream ahead of FAST in the four-stream form (main: blur + FAST, prefetch: level chain, auxiliary:
+  // quad-tree, tail: descriptors + the caller's match — four streams of similar length for batches whose kernels do not fill the machine).
+  // The blurred block then rotates too: blur k + 1 rewrites the block descriptor stage k - 2 read, which the level chain FAST k + 1
+  // waited for was gated on.
+  Ring<BlurSlot> blur;
+  // candidate sets in turn under asynchronous quad-trees: FAST k + 1 writes while tree k reads, and the level chain of call k + 2 —
+  // launched in call k + 1, ahead of FAST k + 1 — is gated on tree k - 1, the last reader of the set FAST k + 2 will write: a tree that
+  // finished a whole step ago (with two sets the gate would be the tree still running beside that FAST)
+  Ring<CandSlot> cand;
+  // level keypoint lists: deferred descriptor stages k - 1 and k - 2 may both still read theirs when call k's quad-tree writes (stage
+  // k - 3 precedes the level chain call k's FAST waited for) — no wait on the main stream in front of it
+  Ring<LvlSlot> lvl;
+  DeviceBuf<uint32_t> d_pts;
+  DeviceBuf<uint32_t> d_kpident;   // idx[slot] = slot's position in its level's list: the visiting order of DVS_DESC_ORDER=0
+  DeviceBuf<uint32_t> d_kpsorted, d_kpsortidx;   // a level's keypoints in the descriptor stage's visiting order + their list positions (k_kp_order)
+  DeviceBuf<int> d_nodeof, d_celloff, d_candtotal;
+  DeviceBuf<dvs_keypoint> d_kps;   // internal outputs for the host entry points [max_batch][outCap]
+  DeviceBuf<u8> d_desc;
+  DeviceBuf<int> d_nout;
+  PinnedBuf<dvs_keypoint> h_kps;
+  PinnedBuf<u8> h_desc;
+  PinnedBuf<int> h_nout;
+  DeviceBuf<u8> d_mask;            // the host entry points' staging copy of the masks [max_batch][rows][cols]: allocated on the first masked call
+  size_t octree_smem = 0;
+  int octree_nmax = 0, octree_ptscap = 0;
+  int oct_ncls = 0;                // level classes of the graded launches (0 = no grading): class c = levels [oct_l0[c], oct_l0[c + 1])
+  int oct_l0[4] = {0, 0, 0, 0};
+  size_t oct_smem_cls[3] = {0, 0, 0};
+  int oct_nmax_cls[3] = {0, 0, 0}, oct_ptscap_cls[3] = {0, 0, 0};
+
+  // a ring's slot before its first use: the one place that holds each slot's size
+  dvs_status ready(PyrSlot& s) { return s.pyr.get() ? DVS_OK : s.pyr.alloc(batch * geom.frameBytes + 256); }   // + slack: k_resize4 reads whole 12-byte windows at a row's end
+  dvs_status ready(BlurSlot& s) { return s.blur.get() ? DVS_OK : s.blur.alloc(batch * geom.frameBytes); }
+  dvs_status ready(CandSlot& s) {
+    if (s.cellcount.get()) return DVS_OK;
+    if (!s.done) DVS_HIP(s.done.create());
+    DVS_TRY(s.cand.alloc(batch * geom.candPerFrame));
+    return s.cellcount.alloc(batch * geom.totalCells);
+  }
+  dvs_status ready(LvlSlot& s) {
+    if (s.lvlkp.get()) return DVS_OK;
+    DVS_TRY(s.lvlcount.alloc(batch * geom.nlevels));
+    return s.lvlkp.alloc(batch * (size_t)geom.kpBlock);
+  }
+  template <class Slot> dvs_status turn(Ring<Slot>& r) { r.advance(); return ready(r.cur()); }   // on to the ring's next slot
+  void rewind(int depth) { blur.rewind(depth); cand.rewind(depth); lvl.rewind(depth); pyr.depth = depth; }   // (the pyramids keep their roles)
+};
+
+// the handle's own events (dvs_orb::ev), created with it, all without timing
+enum {
+  kEvFork,         // FAST finished (main stream): the blur's fork when the caller gave no after-FAST event
+  kEvBlur,         // blur finished (auxiliary stream): the descriptor stage's join
+  kEvStart,        // start of a call on the main stream: gate of an in-step level chain on the auxiliary stream
+  kEvChainGate,    // gate of the next batch's chain when the previous call left no end-of-call event
+  kEvOct,          // quad-tree finished (main stream): the deferred stage's join
+  kEvEnd,          // end of the previous call (gate of the next call's prefetch chain: no extra record)
+  kEvPrefetch,     // + pf_idx: the announced batch's chain is complete; two in turn: this call may still wait for its own chain
+  kEvCount = kEvPrefetch + 2   // after it has launched (and recorded) the next batch's
+};
+
 struct dvs_orb {
   dvs_orb_params prm;
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
   hipStream_t pf_stream = nullptr;         // highest priority: the NEXT batch's level chain (dvs_orb_hint_next_batch_device)
   hipStream_t aux_stream = nullptr;        // lowest priority: in-step level chain, blur, a deferred descriptor stage
-  hipEvent_t ev_fork = nullptr;            // FAST finished (main stream): the blur's fork when the caller gave no after-FAST event
-  hipEvent_t ev_blur = nullptr;            // blur finished (auxiliary stream): the descriptor stage's join
-  hipEvent_t ev_start = nullptr;           // start of a call on the main stream: gate of an in-step level chain on the auxiliary stream
-  hipEvent_t ev_chain_gate = nullptr;      // gate of the next batch's chain when the previous call left no end-of-call event
-  hipEvent_t ev_prefetch = nullptr;        // the announced batch's chain is complete; alternates between ev_pf2[]: this call may still
-  hipEvent_t ev_pf2[2] = {nullptr, nullptr};   // wait for its own chain after it has launched (and recorded) the next batch's
+  Event ev[kEvCount];
   int pf_idx = 0;
-  hipEvent_t ev_level[DVS_MAX_LEVELS] = {};  // level l of the pyramid is complete (in-step chain beside FAST)
+  Event ev_level[DVS_MAX_LEVELS];          // level l of the pyramid is complete (in-step chain beside FAST)
   bool overlap = true;
   bool single_stream = false;              // dvs_orb_create_single_stream: no auxiliary / prefetch streams exist, overlap stays off
   int max_batch = 1;
@@ -57,22 +155,7 @@ struct dvs_orb {
   int umax[16];
   // per-resolution state
   int rows = 0, cols = 0;
-  Geom geom;
-  Geom* d_geom = nullptr;
-  Cell* d_cells = nullptr;
-  BlurTile* d_tiles = nullptr;
-  BlurStrip* d_strips = nullptr;
-  BlurCol* d_blurcols = nullptr;   // matrix-core blur: work items + operand fragment table (k_blur_mfma)
-  uint4* d_blurtab = nullptr;
-  int n_blurcols = 0, blur_avt = 0;
-  bool blur_mfma_ok = false;       // weights fit the int8 band products (0 .. 127, sum 256)
-  ResizeGroup* d_rgroups = nullptr;
-  PyrTile* d_pyrtiles = nullptr;
-  int *d_xofs = nullptr, *d_alpha = nullptr, *d_yofs = nullptr, *d_beta = nullptr;
-  // pyramid blocks: d_pyr = this batch; d_pyr_alt = the announced next batch (built on pf_stream beside this batch's FAST, swapped in
-  // by the next call); d_pyr_3rd = with deferred descriptor stages the pyramid of the batch before is still being read while the next
-  // one is built, so the three rotate.  The last two are allocated on first use.
-  u8 *d_pyr = nullptr, *d_pyr_alt = nullptr, *d_pyr_3rd = nullptr, *d_pyr_4th = nullptr, *d_blur = nullptr;
+  Workspace ws;
   // Depth of the rings a pipelined caller's batches rotate through (pyramids, candidate-list sets, level keypoint sets, blurred blocks): 3, or 4
   // in the four-stream form (dvs_orb_set_tail_stream).  A batch passes chain -> blur -> FAST -> quad-tree -> descriptors on four streams; the
   // chain of batch i + 1 waits for the descriptor stage that last read its buffer — batch i + 1 - ring — so ring periods of the schedule
@@ -80,15 +163,13 @@ struct dvs_orb {
   int ring = 3;
   int async_run = 0;               // consecutive asynchronous (prefetched + deferred) calls so far
   // deferred descriptor stage (dvs_orb_set_output_event + dvs_orb_set_defer_outputs): ordered on the auxiliary stream only
-  hipEvent_t ev_outs[3] = {nullptr, nullptr, nullptr};   // completion of the last ring - 1 deferred stages (ev_out = the latest)
-  hipEvent_t ev_out = nullptr, ev_oct = nullptr;  // ... / quad-tree finished (main stream): the deferred stage's join
+  Ring<Event> ev_outs;                     // completion of the last ring - 1 deferred stages: cur() = the latest, next() = the oldest
   int out_gen = 0;                         // deferred stages enqueued so far
   bool out_pending = false;                // the previous call's descriptor stage has not been joined with the main stream
   bool defer_outputs = false;              // dvs_orb_set_defer_outputs
   hipEvent_t output_event = nullptr;       // caller's event: outputs complete
   hipEvent_t guard_event = nullptr;        // caller's event: outputs may only be overwritten behind it (one-shot)
   hipEvent_t after_fast_event = nullptr;   // caller's event, recorded on the main stream behind FAST
-  hipEvent_t ev_end = nullptr;             // end of the previous call (gate of the next call's prefetch chain: no extra record)
   hipEvent_t gate_event = nullptr;         // = ev_end or the caller's output event, whichever the last call recorded at its end
   bool pf_joined = false;                  // the prefetched pyramid's completion already precedes the main stream (joined through the blur)
   const u8* next_hint = nullptr;           // one-shot, set by the hint call, consumed by the next extract_batch_device
@@ -100,7 +181,7 @@ struct dvs_orb {
   std::vector<ChainGraph> chain_graphs;
   int env_chain_graph = -1;
   int64_t chain_graph_launches = 0;
-  bool pf_valid = false;                   // d_pyr_alt holds (or is being filled with) the pyramid of exactly this announced batch:
+  bool pf_valid = false;                   // the pyramid ring's alt holds (or is being filled with) the pyramid of exactly this announced batch:
   const u8* pf_img = nullptr; uint64_t pf_step = 0, pf_fstride = 0; int pf_nimg = 0;
   // switches read ONCE at creation (dvs_orb_create); each is covered by tests/test_gpu_orb.py::test_opt_in_kernel_variants_are_bit_identical
   int env_cascade = -1;            // DVS_CASCADE=1 / 0: all-levels-in-one-launch pyramid always / never (-1 = automatic: <= 8 frames)
@@ -108,53 +189,18 @@ struct dvs_orb {
   int env_blur_mfma = 0;           // DVS_BLUR_MFMA=1: the matrix-core blur (k_blur_mfma), 2: its LDS-free form; measured slower in the step, DESIGN.md 4b
   int env_oct_threads = 0;         // DVS_OCT_T=256 / 512: quad-tree workgroup size for every batch size (0 = by batch size)
   int env_host_poll = 1;           // DVS_HOST_POLL=0: three device-to-host copy commands and a stream wait instead of k_export_host
-  uint32_t *d_cand = nullptr, *d_pts = nullptr, *d_lvlkp = nullptr;
-  uint32_t* d_kpident = nullptr;   // idx[slot] = slot's position in its level's list: the visiting order of DVS_DESC_ORDER=0
   int env_desc_order = 1;          // DVS_DESC_ORDER=0: the descriptor stage visits a level's keypoints in list order instead of tile by tile (k_kp_order)
-  uint32_t *d_kpsorted = nullptr, *d_kpsortidx = nullptr;   // a level's keypoints in the descriptor stage's visiting order + their list positions (k_kp_order)
-  // level keypoint lists, three sets in rotation: deferred descriptor stages k - 1 and k - 2 may both still read theirs when call k's
-  // quad-tree writes (stage k - 3 precedes the level chain call k's FAST waited for) — no wait on the main stream in front of it
-  uint32_t* d_lvlkp3[4] = {nullptr, nullptr, nullptr, nullptr};   // (the fourth of each ring: allocated when first used)
-  int* d_lvlcount3[4] = {nullptr, nullptr, nullptr, nullptr};
-  int lset = 0;
-  int *d_nodeof = nullptr, *d_cellcount = nullptr, *d_celloff = nullptr, *d_candtotal = nullptr, *d_lvlcount = nullptr;
-  dvs_keypoint* d_kps = nullptr;   // internal outputs for the host entry points [max_batch][outCap]
-  u8* d_desc = nullptr;
-  int* d_nout = nullptr;
-  dvs_keypoint* h_kps = nullptr;   // pinned
-  u8* h_desc = nullptr;
-  int* h_nout = nullptr;
-  int* h_seq = nullptr;            // pinned: sequence number k_export_host publishes (dvs_orb_extract[_batch] poll it)
-  int* d_ticket = nullptr;         // ... its last-workgroup ticket
+  PinnedBuf<int> h_seq;            // sequence number k_export_host publishes (dvs_orb_extract[_batch] poll it); allocated once, outlives a resolution change
+  DeviceBuf<int> d_ticket;         // ... its last-workgroup ticket
   int export_seq = 0;
-  size_t octree_smem = 0;
-  int octree_nmax = 0, octree_ptscap = 0;
   // The quad-tree off the main stream (dvs_orb_set_async_quadtree): it runs on the auxiliary stream beside the NEXT call's FAST.  FAST then
-  // writes the candidate lists of two sets in turn; launches are graded by level class — the dynamic LDS of a dispatch is uniform, so the
+  // writes the candidate lists of the ring's sets in turn; launches are graded by level class — the dynamic LDS of a dispatch is uniform, so the
   // small levels get a launch of their own with their own (smaller) node / point capacities instead of the level-0 footprint.
   bool async_oct = false, last_async = false;
   hipStream_t tail_stream = nullptr;       // dvs_orb_set_tail_stream: the descriptor stage of an asynchronous call runs there (the caller's match stream)
-  // ... and its blur on the MAIN stream ahead of FAST (main: blur + FAST, prefetch: level chain, auxiliary: quad-tree, tail: descriptors +
-  // the caller's match — four streams of similar length for batches whose kernels do not fill the machine).  The blurred block then exists
-  // three times: blur k + 1 rewrites the block descriptor stage k - 2 read, which the level chain FAST k + 1 waited for was gated on.
-  u8* d_blur3[4] = {nullptr, nullptr, nullptr, nullptr};
-  int bset = 0;
-  // THREE candidate sets in turn (the second and third allocated on first use): FAST k + 1 writes while tree k reads, and the level chain
-  // of call k + 2 — launched in call k + 1, ahead of FAST k + 1 — is gated on tree k - 1, the last reader of the set FAST k + 2 will write:
-  // a tree that finished a whole step ago (with two sets the gate would be the tree still running beside that FAST)
-  uint32_t* d_cand2[4] = {nullptr, nullptr, nullptr, nullptr};
-  int* d_cellcount2[4] = {nullptr, nullptr, nullptr, nullptr};
-  int cset = 0;
-  hipEvent_t ev_octdone[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool octdone_valid[4] = {false, false, false, false};
-  int oct_ncls = 0;                        // level classes of the graded launches (0 = no grading): class c = levels [oct_l0[c], oct_l0[c + 1])
-  int oct_l0[4] = {0, 0, 0, 0};
-  size_t oct_smem_cls[3] = {0, 0, 0};
-  int oct_nmax_cls[3] = {0, 0, 0}, oct_ptscap_cls[3] = {0, 0, 0};
   // keep-mask of the call being enqueued (dvs_orb_extract*_masked; null: unmasked).  launch_fast follows every FAST launch with the
   // candidate filter while it is set; the entry points set it around enqueue_extract only.
   CandMask mask{};
-  u8* d_mask = nullptr;            // the host entry points' staging copy of the masks [max_batch][rows][cols]: allocated on the first masked call
   int last_nimg = 0;
   ImgSrc last_src{};
   StageTimer timer;
@@ -171,34 +217,20 @@ void drop_chain_graphs(dvs_orb* h) {
 }
 
 void free_workspace(dvs_orb* h) {
-  void* ptrs[] = {h->d_blurcols, h->d_blurtab, h->d_pyrtiles, h->d_rgroups, h->d_strips, h->d_geom, h->d_cells, h->d_tiles, h->d_xofs, h->d_alpha, h->d_yofs, h->d_beta, h->d_pyr, h->d_blur3[0],
-                  h->d_pyr_alt, h->d_pyr_3rd, h->d_pyr_4th, h->d_pts, h->d_lvlkp3[0], h->d_lvlkp3[1], h->d_lvlkp3[2], h->d_lvlkp3[3], h->d_nodeof, h->d_celloff, h->d_candtotal,
-                  h->d_lvlcount3[0], h->d_lvlcount3[1], h->d_lvlcount3[2], h->d_lvlcount3[3], h->d_kps, h->d_desc, h->d_nout, h->d_ticket, h->d_kpsorted, h->d_kpsortidx, h->d_kpident};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (h->d_mask) (void)hipFree(h->d_mask);
-  h->d_mask = nullptr;
-  for (int k = 1; k < 4; k++) { if (h->d_blur3[k]) (void)hipFree(h->d_blur3[k]); h->d_blur3[k] = nullptr; }   // ([0] = the workspace's block, freed above)
-  h->d_blur3[0] = nullptr; h->bset = 0;
-  for (int k = 0; k < 4; k++) {   // (set 0 is the pair allocated with the workspace; h->d_cand / h->d_cellcount point at the set in use)
-    if (h->d_cand2[k]) (void)hipFree(h->d_cand2[k]);
-    if (h->d_cellcount2[k]) (void)hipFree(h->d_cellcount2[k]);
-    h->d_cand2[k] = nullptr; h->d_cellcount2[k] = nullptr; h->octdone_valid[k] = false;
-  }
-  h->cset = 0;
+  h->ws = Workspace{};
   drop_chain_graphs(h);
-  void* pinned[] = {h->h_kps, h->h_desc, h->h_nout, h->h_seq};
-  for (void* p : pinned) if (p) (void)hipHostFree(p);
-  h->h_seq = nullptr; h->d_ticket = nullptr;
-  h->d_blurcols = nullptr; h->d_blurtab = nullptr;
-  h->d_strips = nullptr; h->d_rgroups = nullptr; h->d_pyrtiles = nullptr;
-  h->d_geom = nullptr; h->d_cells = nullptr; h->d_tiles = nullptr; h->d_xofs = h->d_alpha = h->d_yofs = h->d_beta = nullptr;
-  h->d_pyr = h->d_blur = nullptr; h->d_cand = h->d_pts = h->d_lvlkp = nullptr;
-  for (int k = 0; k < 4; k++) { h->d_lvlkp3[k] = nullptr; h->d_lvlcount3[k] = nullptr; }
-  h->d_pyr_alt = nullptr; h->d_pyr_3rd = nullptr; h->d_pyr_4th = nullptr; h->out_gen = 0; h->pf_valid = false; h->next_hint = nullptr;
-  h->d_nodeof = h->d_cellcount = h->d_celloff = h->d_candtotal = h->d_lvlcount = nullptr;
-  h->d_kpsorted = nullptr; h->d_kpsortidx = nullptr; h->d_kpident = nullptr;
-  h->d_kps = nullptr; h->d_desc = nullptr; h->d_nout = nullptr; h->h_kps = nullptr; h->h_desc = nullptr; h->h_nout = nullptr;
   h->rows = h->cols = 0;
+  h->out_gen = 0; h->pf_valid = false; h->next_hint = nullptr;
+}
+
+// Everything the handle has enqueued is complete: its streams, and a deferred descriptor stage on the caller's tail stream.
+dvs_status quiesce(dvs_orb* h) {
+  DVS_HIP(hipStreamSynchronize(h->stream));
+  if (h->aux_stream) DVS_HIP(hipStreamSynchronize(h->aux_stream));
+  if (h->pf_stream) DVS_HIP(hipStreamSynchronize(h->pf_stream));
+  if (h->out_pending) DVS_HIP(hipEventSynchronize(h->ev_outs.cur()));
+  h->out_pending = false;
+  return DVS_OK;
 }
 
 // ORBextractor ctor tables.  NOTE the member `scaleFactor` is a double holding the float argument
@@ -261,9 +293,13 @@ void build_axis_table(int ssize, int dsize, bool clamp_like_x, std::vector<int>&
   }
 }
 
-dvs_status build_geometry(dvs_orb* h, int rows, int cols, Geom& G, std::vector<Cell>& cells, std::vector<BlurTile>& tiles,
-                          std::vector<BlurStrip>& strips, std::vector<ResizeGroup>& rgroups, std::vector<PyrTile>& ptiles,
-                          std::vector<int>& xofs, std::vector<int>& alpha, std::vector<int>& yofs, std::vector<int>& beta) {
+// the host tables build_geometry fills beside Geom (uploaded by ensure_workspace)
+struct GeomTables {
+  std::vector<Cell> cells; std::vector<BlurTile> tiles; std::vector<BlurStrip> strips; std::vector<ResizeGroup> rgroups; std::vector<PyrTile> ptiles;
+  std::vector<int> xofs, alpha, yofs, beta;
+};
+
+dvs_status build_geometry(dvs_orb* h, int rows, int cols, Geom& G, GeomTables& tb) {
   memset(&G, 0, sizeof(G));
   const int nl = h->prm.nlevels;
   G.nlevels = nl; G.rows = rows; G.cols = cols;
@@ -318,7 +354,7 @@ dvs_status build_geometry(dvs_orb* h, int rows, int cols, Geom& G, std::vector<C
     L.pitch = (int)align_up(L.w + 8, 64);  // >= 8 spare columns: k_resize4 writes the REFLECT_101 continuation there
     L.off = off;
     off += align_up((uint64_t)L.pitch * L.h, 256);
-    L.cellBase = (int)cells.size();
+    L.cellBase = (int)tb.cells.size();
     L.cellCap = ((L.wCell + 1) / 2) * ((L.hCell + 1) / 2);
     int slot = 0;
     for (int i = 0; i < nRows; i++) {
@@ -343,7 +379,7 @@ dvs_status build_geometry(dvs_orb* h, int rows, int cols, Geom& G, std::vector<C
           c.rpt = (int16_t)(rpt | (tail << 8)); c.inv_ng = 1.0f / (float)ng;
         }
         c.slot = slot++;
-        cells.push_back(c);
+        tb.cells.push_back(c);
       }
     }
     L.nCells = slot;
@@ -354,19 +390,19 @@ dvs_status build_geometry(dvs_orb* h, int rows, int cols, Geom& G, std::vector<C
     L.kpOff = kpOff; kpOff += L.N + 4;
     G.maxN = std::max(G.maxN, std::max(L.N + 3, 4 * nIni));
     for (int ty = 0; ty < (L.h + 15) / 16; ty++)
-      for (int tx = 0; tx < (L.w + 63) / 64; tx++) tiles.push_back(BlurTile{(int16_t)l, (int16_t)tx, (int16_t)ty, 0});
+      for (int tx = 0; tx < (L.w + 63) / 64; tx++) tb.tiles.push_back(BlurTile{(int16_t)l, (int16_t)tx, (int16_t)ty, 0});
     {  // streaming blur: equal-width strips of <= 248 columns (multiples of 4), bands of kBlurBand rows
       const int ns = (L.w + 247) / 248;  // 62 output lanes + 2 halo lanes per wavefront
       const int sw = ((L.w + ns - 1) / ns + 3) / 4 * 4;
       for (int y0 = 0; y0 < L.h; y0 += G.blurBand)
-        for (int x0 = 0; x0 < L.w; x0 += sw) strips.push_back(BlurStrip{(int16_t)l, (int16_t)x0, (int16_t)std::min(sw, L.w - x0), (int16_t)y0});
+        for (int x0 = 0; x0 < L.w; x0 += sw) tb.strips.push_back(BlurStrip{(int16_t)l, (int16_t)x0, (int16_t)std::min(sw, L.w - x0), (int16_t)y0});
     }
     if (l > 0) {
-      L.xtab = (int)xofs.size(); L.ytab = (int)yofs.size();
-      build_axis_table(G.lv[l - 1].w, L.w, true, xofs, alpha);
-      build_axis_table(G.lv[l - 1].h, L.h, false, yofs, beta);
+      L.xtab = (int)tb.xofs.size(); L.ytab = (int)tb.yofs.size();
+      build_axis_table(G.lv[l - 1].w, L.w, true, tb.xofs, tb.alpha);
+      build_axis_table(G.lv[l - 1].h, L.h, false, tb.yofs, tb.beta);
       // 4-column groups for k_resize4 (valid while the four left taps span <= 8 bytes, i.e. scale factor <= 2)
-      L.gtab = (int)rgroups.size();
+      L.gtab = (int)tb.rgroups.size();
       bool fits = true;
       for (int x4 = 0; x4 < L.w + 8; x4 += 4) {  // 2 extra groups: columns >= w mirror column 2w-2-x (blur border)
         ResizeGroup rg{};
@@ -375,25 +411,25 @@ dvs_status build_geometry(dvs_orb* h, int rows, int cols, Geom& G, std::vector<C
           int x = x4 + i;
           if (x >= L.w) x = std::max(0, 2 * L.w - 2 - x);
           cols4[i] = x;
-          mn = std::min(mn, xofs[L.xtab + x]);
+          mn = std::min(mn, tb.xofs[L.xtab + x]);
         }
         rg.base = mn & ~3;
         rg.shift = (uint32_t)(mn & 3) * 8;
         for (int i = 0; i < 4; i++) {
-          const int o = xofs[L.xtab + cols4[i]] - mn;  // both taps (o, o + 1) must lie inside the 8-byte window
+          const int o = tb.xofs[L.xtab + cols4[i]] - mn;  // both taps (o, o + 1) must lie inside the 8-byte window
           if (o < 0 || o > 6) fits = false;
           rg.sel[i] = (uint32_t)o | (0x0cu << 8) | ((uint32_t)(o + 1) << 16) | (0x0cu << 24);
-          rg.alpha[i] = alpha[L.xtab + cols4[i]];
+          rg.alpha[i] = tb.alpha[L.xtab + cols4[i]];
         }
-        rgroups.push_back(rg);
+        tb.rgroups.push_back(rg);
       }
       if (!fits) L.gtab = -1;
     }
   }
   // ---- pyramid cascade tiles (k_pyr_cascade) --------------------------------------------------------------------
   if (nl >= 2) {
-    auto srcx = [&](int k, int x) { return xofs[G.lv[k].xtab + x]; };                                    // left tap (already clamped)
-    auto srcy = [&](int k, int y) { return std::min(std::max(yofs[G.lv[k].ytab + y], 0), G.lv[k - 1].h - 1); };  // top tap
+    auto srcx = [&](int k, int x) { return tb.xofs[G.lv[k].xtab + x]; };                                    // left tap (already clamped)
+    auto srcy = [&](int k, int y) { return std::min(std::max(tb.yofs[G.lv[k].ytab + y], 0), G.lv[k - 1].h - 1); };  // top tap
     int maxBytes = 0;
     bool cascade_ok = true;
     // tile = the level-1 pixels a workgroup owns (results do not depend on the tiling).  The cascade's latency is its seven dependent levels
@@ -453,20 +489,20 @@ dvs_status build_geometry(dvs_orb* h, int rows, int cols, Geom& G, std::vector<C
           if (cwp > cascT || chh > cascT) cascade_ok = false;   // k_pyr_cascade: one table entry per thread and level
         }
         if (tabx > kPyrTabX || taby > kPyrTabY) cascade_ok = false;
-        ptiles.push_back(T);
+        tb.ptiles.push_back(T);
       }
-    G.pyrTiles = cascade_ok ? (int)ptiles.size() : 0;
+    G.pyrTiles = cascade_ok ? (int)tb.ptiles.size() : 0;
     G.pyrLds = (int)align_up(maxBytes, 16);
   }
   G.frameBytes = off;
   G.candPerFrame = candOff; G.ptsPerFrame = ptsOff;
-  G.totalCells = (int)cells.size();
+  G.totalCells = (int)tb.cells.size();
   G.kpBlock = kpOff;
-  G.blurTiles = (int)tiles.size();
-  G.blurStrips = (int)strips.size();
+  G.blurTiles = (int)tb.tiles.size();
+  G.blurStrips = (int)tb.strips.size();
   {  // wave-per-cell FAST: LDS tile geometry (pitch keeps the <= 3 byte phase of the aligned staging)
     int maxw = 0, maxh = 0;
-    for (const Cell& c : cells) { maxw = std::max<int>(maxw, c.cw); maxh = std::max<int>(maxh, c.ch); }
+    for (const Cell& c : tb.cells) { maxw = std::max<int>(maxw, c.cw); maxh = std::max<int>(maxh, c.ch); }
     const int need = std::max(maxw + 3, maxh - 4);   // tile pitch: the widest cell at any byte phase; tile rows: <= pitch + 4 (fast_tile_bytes)
     G.fastP = need <= 48 ? 48 : (need <= 64 ? 64 : 80);
     G.fastRows = maxh;
@@ -476,13 +512,6 @@ dvs_status build_geometry(dvs_orb* h, int rows, int cols, Geom& G, std::vector<C
     // tile (fast_tile_bytes) + score tile (rows of the tallest cell) + work list
     G.fastWaveLds = (int)align_up((size_t)G.fastTile + (size_t)G.fastRows * G.fastP + listBytes, 16);
   }
-  return DVS_OK;
-}
-
-template <class T>
-dvs_status upload(T** dptr, const std::vector<T>& v) {
-  DVS_HIP(hipMalloc((void**)dptr, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  if (!v.empty()) DVS_HIP(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return DVS_OK;
 }
 
@@ -544,66 +573,54 @@ static int probe_byte_dma(int device, hipStream_t st) {
   if (done[device]) return cache[device];
   uint8_t hsrc[512]; uint32_t hout[64];
   for (int i = 0; i < 512; i++) hsrc[i] = (uint8_t)(i * 7 + 3);
-  uint8_t* d = nullptr; uint32_t* o = nullptr;
+  DeviceBuf<uint8_t> d; DeviceBuf<uint32_t> o;
   int ok = 1;
-  if (hipMalloc((void**)&d, 512) != hipSuccess || hipMalloc((void**)&o, 256) != hipSuccess) ok = 0;
-  if (ok && hipMemcpy(d, hsrc, 512, hipMemcpyHostToDevice) != hipSuccess) ok = 0;
+  if (d.alloc(512) != DVS_OK || o.alloc(64) != DVS_OK) ok = 0;
+  if (ok && hipMemcpy(d.get(), hsrc, 512, hipMemcpyHostToDevice) != hipSuccess) ok = 0;
   for (int shift = 1; ok && shift < 4; shift++) {
-    hipLaunchKernelGGL(k_probe_lds_dma, dim3(1), dim3(64), 0, st, d, o, shift);
-    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(hout, o, 256, hipMemcpyDeviceToHost) != hipSuccess) { ok = 0; break; }
+    hipLaunchKernelGGL(k_probe_lds_dma, dim3(1), dim3(64), 0, st, d.get(), o.get(), shift);
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(hout, o.get(), 256, hipMemcpyDeviceToHost) != hipSuccess) { ok = 0; break; }
     for (int l = 0; l < 64; l++) { uint32_t e; memcpy(&e, hsrc + shift + 4 * l, 4); if (e != hout[l]) ok = 0; }
   }
-  if (d) (void)hipFree(d);
-  if (o) (void)hipFree(o);
   cache[device] = ok; done[device] = true;
   return ok;
 }
 
 dvs_status ensure_workspace(dvs_orb* h, int rows, int cols) {
-  if (h->rows == rows && h->cols == cols && h->d_geom) return DVS_OK;
-  DVS_HIP(hipStreamSynchronize(h->stream));
-  if (h->aux_stream) DVS_HIP(hipStreamSynchronize(h->aux_stream));
-  if (h->pf_stream) DVS_HIP(hipStreamSynchronize(h->pf_stream));
-  if (h->out_pending) DVS_HIP(hipEventSynchronize(h->ev_out));   // a deferred descriptor stage on the tail stream
-  h->out_pending = false; h->pf_joined = false; h->pf_valid = false;
+  if (h->rows == rows && h->cols == cols && h->ws.d_geom.get()) return DVS_OK;
+  DVS_TRY(quiesce(h));
+  h->pf_joined = false;
   free_workspace(h);
-  Geom G;
-  std::vector<Cell> cells; std::vector<BlurTile> tiles; std::vector<BlurStrip> strips; std::vector<ResizeGroup> rgroups;
-  std::vector<PyrTile> ptiles;
-  std::vector<int> xofs, alpha, yofs, beta;
-  DVS_TRY(build_geometry(h, rows, cols, G, cells, tiles, strips, rgroups, ptiles, xofs, alpha, yofs, beta));
-  h->geom = G;
-  const size_t B = (size_t)h->max_batch;
-  DVS_HIP(hipMalloc((void**)&h->d_geom, sizeof(Geom)));
-  DVS_HIP(hipMemcpy(h->d_geom, &G, sizeof(Geom), hipMemcpyHostToDevice));
-  DVS_TRY(upload(&h->d_cells, cells));
-  DVS_TRY(upload(&h->d_tiles, tiles));
-  DVS_TRY(upload(&h->d_strips, strips));
+  Workspace W;   // moved into the handle only when complete: a failure leaves the handle without a workspace, never with part of one
+  Geom& G = W.geom;
+  GeomTables tb;
+  DVS_TRY(build_geometry(h, rows, cols, G, tb));
+  const size_t B = W.batch = (size_t)h->max_batch;
+  W.rewind(h->ring);
+  DVS_TRY(W.d_geom.upload(std::vector<Geom>(1, G)));
+  DVS_TRY(W.d_cells.upload(tb.cells));
+  DVS_TRY(W.d_tiles.upload(tb.tiles));
+  DVS_TRY(W.d_strips.upload(tb.strips));
   {
     std::vector<BlurCol> bcols; std::vector<uint4> btab;
-    h->blur_mfma_ok = build_blur_mfma(G, bcols, btab, h->blur_avt);
-    if (h->blur_mfma_ok) { DVS_TRY(upload(&h->d_blurcols, bcols)); DVS_TRY(upload(&h->d_blurtab, btab)); h->n_blurcols = (int)bcols.size(); }
+    W.blur_mfma_ok = build_blur_mfma(G, bcols, btab, W.blur_avt);
+    if (W.blur_mfma_ok) { DVS_TRY(W.d_blurcols.upload(bcols)); DVS_TRY(W.d_blurtab.upload(btab)); W.n_blurcols = (int)bcols.size(); }
   }
-  DVS_TRY(upload(&h->d_rgroups, rgroups));
-  DVS_TRY(upload(&h->d_pyrtiles, ptiles));
+  DVS_TRY(W.d_rgroups.upload(tb.rgroups));
+  DVS_TRY(W.d_pyrtiles.upload(tb.ptiles));
   if (G.pyrLds > 0) DVS_HIP(hipFuncSetAttribute((const void*)k_pyr_cascade<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G.pyrLds));
-  DVS_TRY(upload(&h->d_xofs, xofs)); DVS_TRY(upload(&h->d_alpha, alpha));
-  DVS_TRY(upload(&h->d_yofs, yofs)); DVS_TRY(upload(&h->d_beta, beta));
-  DVS_HIP(hipMalloc((void**)&h->d_pyr, B * G.frameBytes + 256));   // + slack: k_resize4 reads whole 12-byte windows at a row's end
-  DVS_HIP(hipMalloc((void**)&h->d_blur, B * G.frameBytes));
-  DVS_HIP(hipMalloc((void**)&h->d_cand, B * G.candPerFrame * 4));
-  DVS_HIP(hipMalloc((void**)&h->d_pts, B * G.ptsPerFrame * 4));
-  DVS_HIP(hipMalloc((void**)&h->d_nodeof, B * G.ptsPerFrame * 4));
-  DVS_HIP(hipMalloc((void**)&h->d_cellcount, B * G.totalCells * 4));
-  DVS_HIP(hipMalloc((void**)&h->d_celloff, B * G.totalCells * 4));
-  DVS_HIP(hipMalloc((void**)&h->d_candtotal, B * G.nlevels * 4));
-  for (int k = 0; k < 3; k++) {
-    DVS_HIP(hipMalloc((void**)&h->d_lvlcount3[k], B * G.nlevels * 4));
-    DVS_HIP(hipMalloc((void**)&h->d_lvlkp3[k], B * (size_t)G.kpBlock * 4));
-  }
-  h->lset = 0; h->d_lvlcount = h->d_lvlcount3[0]; h->d_lvlkp = h->d_lvlkp3[0];
-  DVS_HIP(hipMalloc((void**)&h->d_kpsorted, B * (size_t)G.kpBlock * 4));
-  DVS_HIP(hipMalloc((void**)&h->d_kpsortidx, B * (size_t)G.kpBlock * 4));
+  DVS_TRY(W.d_xofs.upload(tb.xofs)); DVS_TRY(W.d_alpha.upload(tb.alpha));
+  DVS_TRY(W.d_yofs.upload(tb.yofs)); DVS_TRY(W.d_beta.upload(tb.beta));
+  DVS_TRY(W.ready(W.pyr.cur()));
+  DVS_TRY(W.ready(W.blur.cur()));
+  DVS_TRY(W.ready(W.cand.cur()));
+  DVS_TRY(W.d_pts.alloc(B * G.ptsPerFrame));
+  DVS_TRY(W.d_nodeof.alloc(B * G.ptsPerFrame));
+  DVS_TRY(W.d_celloff.alloc(B * G.totalCells));
+  DVS_TRY(W.d_candtotal.alloc(B * G.nlevels));
+  for (int k = 0; k < 3; k++) DVS_TRY(W.ready(W.lvl.at(k)));
+  DVS_TRY(W.d_kpsorted.alloc(B * (size_t)G.kpBlock));
+  DVS_TRY(W.d_kpsortidx.alloc(B * (size_t)G.kpBlock));
   {
     std::vector<uint32_t> ident(B * (size_t)G.kpBlock);
     for (size_t f = 0; f < B; f++)
@@ -611,66 +628,66 @@ dvs_status ensure_workspace(dvs_orb* h, int rows, int cols) {
         const int end = l + 1 < G.nlevels ? G.lv[l + 1].kpOff : G.kpBlock;
         for (int sl = G.lv[l].kpOff; sl < end; sl++) ident[f * G.kpBlock + sl] = (uint32_t)(sl - G.lv[l].kpOff);
       }
-    DVS_TRY(upload(&h->d_kpident, ident));
+    DVS_TRY(W.d_kpident.upload(ident));
   }
-  DVS_HIP(hipMalloc((void**)&h->d_kps, B * (size_t)G.outCap * sizeof(dvs_keypoint)));
-  DVS_HIP(hipMalloc((void**)&h->d_desc, B * (size_t)G.outCap * 32));
-  DVS_HIP(hipMalloc((void**)&h->d_nout, B * 4));
-  DVS_HIP(hipHostMalloc((void**)&h->h_kps, B * (size_t)G.outCap * sizeof(dvs_keypoint)));
-  DVS_HIP(hipHostMalloc((void**)&h->h_desc, B * (size_t)G.outCap * 32));
-  DVS_HIP(hipHostMalloc((void**)&h->h_nout, B * 4));
-  if (!h->h_seq) {
-    DVS_HIP(hipHostMalloc((void**)&h->h_seq, 64));
-    *h->h_seq = 0; h->export_seq = 0;
-    DVS_HIP(hipMalloc((void**)&h->d_ticket, 4));
-    DVS_HIP(hipMemset(h->d_ticket, 0, 4));
+  DVS_TRY(W.d_kps.alloc(B * (size_t)G.outCap));
+  DVS_TRY(W.d_desc.alloc(B * (size_t)G.outCap * 32));
+  DVS_TRY(W.d_nout.alloc(B));
+  DVS_TRY(W.h_kps.alloc(B * (size_t)G.outCap));
+  DVS_TRY(W.h_desc.alloc(B * (size_t)G.outCap * 32));
+  DVS_TRY(W.h_nout.alloc(B));
+  if (!h->d_ticket.get()) {
+    DVS_TRY(h->h_seq.alloc(16));
+    *h->h_seq.get() = 0; h->export_seq = 0;
+    DVS_TRY(h->d_ticket.alloc(1));
+    DVS_HIP(hipMemset(h->d_ticket.get(), 0, 4));
   }
-  h->octree_nmax = G.maxN + 8;
+  W.octree_nmax = G.maxN + 8;
   {
     int maxPts = 0;
     for (int l = 0; l < G.nlevels; l++) maxPts = std::max(maxPts, G.lv[l].ptsCap);
-    h->octree_ptscap = std::min(6144, maxPts);
+    W.octree_ptscap = std::min(6144, maxPts);
     // two quad-tree workgroups per CU (the launch is latency-bound: frames x levels workgroups, all resident at once) need
     // <= 80 KB each including k_octree's static LDS; give up a few point slots rather than half the residency
-    const long fixed = (long)h->octree_nmax * (long)(2 * sizeof(QNode) + 8 + 16 + 4 * 4) + 2048;
+    const long fixed = (long)W.octree_nmax * (long)(2 * sizeof(QNode) + 8 + 16 + 4 * 4) + 2048;
     const long fit = (80 * 1024 - fixed) / 8;
-    if (fit >= 4096 && h->octree_ptscap > fit) h->octree_ptscap = (int)fit;
+    if (fit >= 4096 && W.octree_ptscap > fit) W.octree_ptscap = (int)fit;
   }
-  h->octree_smem = (size_t)h->octree_nmax * (2 * sizeof(QNode) + 8 + 16 + 4 * 4) + (size_t)h->octree_ptscap * 8;
-  DVS_HIP(hipFuncSetAttribute((const void*)k_octree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->octree_smem));
-  DVS_HIP(hipFuncSetAttribute((const void*)k_octree_blur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->octree_smem));
-  h->d_cand2[0] = h->d_cand; h->d_cellcount2[0] = h->d_cellcount; h->cset = 0;
-  h->d_blur3[0] = h->d_blur; h->bset = 0;
+  W.octree_smem = (size_t)W.octree_nmax * (2 * sizeof(QNode) + 8 + 16 + 4 * 4) + (size_t)W.octree_ptscap * 8;
+  DVS_HIP(hipFuncSetAttribute((const void*)k_octree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W.octree_smem));
+  DVS_HIP(hipFuncSetAttribute((const void*)k_octree_blur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W.octree_smem));
   {
     // level classes for graded launches ({L0, L1}, {L2, L3}, {L4 ..}): node capacity from the class's largest quota, point capacity =
     // level 0's scaled by the level's share of pixels (a level whose candidates exceed it keeps them in HBM — slower, never wrong)
     const long per_node = (long)(2 * sizeof(QNode) + 8 + 16 + 4 * 4);
-    h->oct_ncls = G.nlevels >= 6 ? 3 : (G.nlevels >= 4 ? 2 : 0);
-    h->oct_l0[0] = 0; h->oct_l0[1] = 2; h->oct_l0[2] = h->oct_ncls == 3 ? 4 : G.nlevels; h->oct_l0[3] = G.nlevels;
-    for (int c = 0; c < h->oct_ncls; c++) {
-      const int l0 = h->oct_l0[c], l1 = h->oct_l0[c + 1];
+    W.oct_ncls = G.nlevels >= 6 ? 3 : (G.nlevels >= 4 ? 2 : 0);
+    W.oct_l0[0] = 0; W.oct_l0[1] = 2; W.oct_l0[2] = W.oct_ncls == 3 ? 4 : G.nlevels; W.oct_l0[3] = G.nlevels;
+    for (int c = 0; c < W.oct_ncls; c++) {
+      const int l0 = W.oct_l0[c], l1 = W.oct_l0[c + 1];
       int nmax = 0; long pts = 0;
       for (int l = l0; l < l1; l++) {
         nmax = std::max(nmax, std::max(G.lv[l].N + 3, 4 * G.lv[l].nIni) + 8);
         const double share = (double)G.lv[l].w * G.lv[l].h / ((double)G.lv[0].w * G.lv[0].h);
-        pts = std::max(pts, std::min<long>(G.lv[l].ptsCap, (long)(share * h->octree_ptscap) + 64));
+        pts = std::max(pts, std::min<long>(G.lv[l].ptsCap, (long)(share * W.octree_ptscap) + 64));
       }
-      h->oct_nmax_cls[c] = nmax;
-      h->oct_ptscap_cls[c] = (int)std::min<long>(pts, h->octree_ptscap);
-      h->oct_smem_cls[c] = (size_t)nmax * per_node + (size_t)h->oct_ptscap_cls[c] * 8;
-      if (h->oct_smem_cls[c] > h->octree_smem) { h->oct_smem_cls[c] = h->octree_smem; h->oct_nmax_cls[c] = h->octree_nmax; h->oct_ptscap_cls[c] = h->octree_ptscap; }
+      W.oct_nmax_cls[c] = nmax;
+      W.oct_ptscap_cls[c] = (int)std::min<long>(pts, W.octree_ptscap);
+      W.oct_smem_cls[c] = (size_t)nmax * per_node + (size_t)W.oct_ptscap_cls[c] * 8;
+      if (W.oct_smem_cls[c] > W.octree_smem) { W.oct_smem_cls[c] = W.octree_smem; W.oct_nmax_cls[c] = W.octree_nmax; W.oct_ptscap_cls[c] = W.octree_ptscap; }
     }
   }
   DVS_HIP(hipFuncSetAttribute((const void*)k_fast_wave<48>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * G.fastWaveLds));
   DVS_HIP(hipFuncSetAttribute((const void*)k_fast_wave<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * G.fastWaveLds));
   DVS_HIP(hipFuncSetAttribute((const void*)k_fast_wave<80>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * G.fastWaveLds));
+  h->ws = std::move(W);
   h->rows = rows; h->cols = cols;
   return DVS_OK;
 }
 
 // the level chain: level l from level l-1 (ORBextractor.cpp:1171-1192) into `pyr`, one launch per level on `pst`
 dvs_status launch_pyramid_chain(dvs_orb* h, const ImgSrc& src, int nimg, u8* pyr, hipStream_t pst, bool level_events, int top_level = -1) {
-  const Geom& G = h->geom;
+  Workspace& W = h->ws;
+  const Geom& G = W.geom;
   const int last = top_level < 0 ? G.nlevels - 1 : std::min(top_level, G.nlevels - 1);   // level sharding: only up to the highest level owned
   for (int l = 1; l <= last; l++) {
     const LevelGeom& S = G.lv[l - 1];
@@ -692,13 +709,13 @@ dvs_status launch_pyramid_chain(dvs_orb* h, const ImgSrc& src, int nimg, u8* pyr
       auto magic = [](uint64_t nmax, uint32_t d) -> uint32_t { return d > 1 && nmax * d < (1ull << 32) ? (uint32_t)((1ull << 32) / d + 1) : 0u; };
       hipLaunchKernelGGL(k_resize4, dim3(tiles, ngroups), block, 0, pst,
                          sp, sfs, S.w, S.h, spitch, pyr + D.off, G.frameBytes, dwp, D.h, D.pitch,
-                         h->d_rgroups + D.gtab, h->d_yofs + D.ytab, h->d_beta + D.ytab,
-                         l == 1 && sp != h->d_pyr + G.lv[0].off && sp != h->d_pyr_alt + G.lv[0].off && sp != h->d_pyr_3rd + G.lv[0].off && sp != h->d_pyr_4th + G.lv[0].off ? nimg - 1 : -1,   // caller's buffer: no slack behind its last row
+                         W.d_rgroups.get() + D.gtab, W.d_yofs.get() + D.ytab, W.d_beta.get() + D.ytab,
+                         l == 1 && !W.pyr.is_own(sp, G.lv[0].off) ? nimg - 1 : -1,   // caller's buffer: no slack behind its last row
                          (int)tx, magic((uint64_t)tiles * ngroups, tiles), magic(tiles, tx), ngx, fpg, magic((uint64_t)tx * 64, (uint32_t)ngx), nimg);
     }
     else
       hipLaunchKernelGGL(k_resize, grid, block, 0, pst, sp, sfs, S.w, S.h, spitch, pyr + D.off, G.frameBytes, D.w, D.h,
-                         D.pitch, h->d_xofs + D.xtab, h->d_alpha + D.xtab, h->d_yofs + D.ytab, h->d_beta + D.ytab);
+                         D.pitch, W.d_xofs.get() + D.xtab, W.d_alpha.get() + D.xtab, W.d_yofs.get() + D.ytab, W.d_beta.get() + D.ytab);
     if (level_events) DVS_HIP(hipEventRecord(h->ev_level[l], pst));
   }
   return DVS_OK;
@@ -709,54 +726,50 @@ dvs_status launch_pyramid_chain(dvs_orb* h, const ImgSrc& src, int nimg, u8* pyr
 // FAST on cells [c0, c1) of the level-major cell table
 void launch_fast(dvs_orb* h, const ImgSrc& src, int nimg, hipStream_t fs, int c0, int c1) {
   if (c1 <= c0) return;
-  const Geom& G = h->geom;
+  Workspace& W = h->ws;
+  const Geom& G = W.geom;
   if ((((uintptr_t)src.img0) | src.step0 | src.fstride0) % 4 != 0) {   // rows not dword aligned: the generic workgroup-per-cell kernel
-    hipLaunchKernelGGL(k_fast_cell, dim3(c1 - c0, nimg), dim3(256), 0, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0);
+    hipLaunchKernelGGL(k_fast_cell, dim3(c1 - c0, nimg), dim3(256), 0, fs, W.d_geom.get(), W.d_cells.get(), src, W.cand.cur().cand.get(), W.cand.cur().cellcount.get(), c0);
   } else {
     const dim3 grid((c1 - c0 + 3) / 4, nimg);
     const size_t lds = 4 * (size_t)G.fastWaveLds;
     // n / grid.x == umulhi(n, 2^32 / grid.x + 1) for every workgroup id n of this grid (n * grid.x < 2^32), else 0: the kernel divides
     const uint32_t magic = grid.x > 1 && (uint64_t)grid.x * grid.x * nimg < (1ull << 32) ? (uint32_t)((1ull << 32) / grid.x + 1) : 0u;
-    if (G.fastP == 48) hipLaunchKernelGGL(k_fast_wave<48>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
-    else if (G.fastP == 64) hipLaunchKernelGGL(k_fast_wave<64>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
-    else hipLaunchKernelGGL(k_fast_wave<80>, grid, dim3(256), lds, fs, h->d_geom, h->d_cells, src, h->d_cand, h->d_cellcount, c0, c1, magic);
+    if (G.fastP == 48) hipLaunchKernelGGL(k_fast_wave<48>, grid, dim3(256), lds, fs, W.d_geom.get(), W.d_cells.get(), src, W.cand.cur().cand.get(), W.cand.cur().cellcount.get(), c0, c1, magic);
+    else if (G.fastP == 64) hipLaunchKernelGGL(k_fast_wave<64>, grid, dim3(256), lds, fs, W.d_geom.get(), W.d_cells.get(), src, W.cand.cur().cand.get(), W.cand.cur().cellcount.get(), c0, c1, magic);
+    else hipLaunchKernelGGL(k_fast_wave<80>, grid, dim3(256), lds, fs, W.d_geom.get(), W.d_cells.get(), src, W.cand.cur().cand.get(), W.cand.cur().cellcount.get(), c0, c1, magic);
   }
   // masked call: the same cells' lists filtered right behind FAST, on its stream — before any after-FAST event, so every schedule
   // (overlap, async quad-tree, candidate-set ring, lanes) reads filtered lists without an event of its own
-  if (h->mask.mask) launch_cand_mask(h->d_geom, h->d_cells, h->mask, h->d_cand, h->d_cellcount, nimg, c0, c1, fs);
+  if (h->mask.mask) launch_cand_mask(W.d_geom.get(), W.d_cells.get(), h->mask, W.cand.cur().cand.get(), W.cand.cur().cellcount.get(), nimg, c0, c1, fs);
 }
 
-// The announced next batch's level chain on pf_stream into d_pyr_alt, beside THIS batch's FAST: the chain is latency-bound, FAST is
+// The announced next batch's level chain on pf_stream into the pyramid ring's alt, beside THIS batch's FAST: the chain is latency-bound, FAST is
 // VALU-bound and insensitive to its cache traffic (beside the fetch-bound descriptor stage the chain doubled that stage's time), and
 // with its pyramid built ahead the next call launches FAST on all levels at once.  `pend`: the previous call's deferred descriptor
-// stage still reads that batch's pyramid (d_pyr_alt after the caller's swap).
+// stage still reads that batch's pyramid (alt after the caller's take()).
 dvs_status launch_prefetch(dvs_orb* h, const ImgSrc& src, int nimg, const u8* next_img0, bool pend) {
-  const Geom& G = h->geom;
-  if (!h->d_pyr_alt) DVS_HIP(hipMalloc((void**)&h->d_pyr_alt, (size_t)h->max_batch * G.frameBytes + 256));
+  Workspace& W = h->ws;
   if (pend) {
     // build into the THIRD buffer instead of waiting for that stage — the chain then runs beside FAST from the start, as without
     // deferral (when it waited it ended after FAST and became the critical path).  The third buffer held the pyramid of two batches
     // ago; its last reader is that batch's descriptor stage, whose event is the only gate (nothing on the main stream).
-    if (!h->d_pyr_3rd) DVS_HIP(hipMalloc((void**)&h->d_pyr_3rd, (size_t)h->max_batch * G.frameBytes + 256));
-    if (h->ring == 4) {   // the oldest of four: alt <- 3rd <- 4th <- alt
-      if (!h->d_pyr_4th) DVS_HIP(hipMalloc((void**)&h->d_pyr_4th, (size_t)h->max_batch * G.frameBytes + 256));
-      u8* a = h->d_pyr_alt; h->d_pyr_alt = h->d_pyr_3rd; h->d_pyr_3rd = h->d_pyr_4th; h->d_pyr_4th = a;
-    } else {
-      std::swap(h->d_pyr_alt, h->d_pyr_3rd);
-    }
+    W.pyr.retire_alt();
     // its last reader: the descriptor stage of ring - 1 batches ago (the slot the NEXT deferred stage records into)
-    if (h->out_gen >= h->ring - 1) DVS_HIP(hipStreamWaitEvent(h->pf_stream, h->ev_outs[h->out_gen % (h->ring - 1)], 0));
+    if (h->out_gen >= h->ring - 1) DVS_HIP(hipStreamWaitEvent(h->pf_stream, h->ev_outs.next(), 0));
   } else {
-    // d_pyr_alt's last readers are the previous call's kernels: its end-of-call event if it left one (no extra record), else this
+    // alt's last readers are the previous call's kernels: its end-of-call event if it left one (no extra record), else this
     // point of the main stream
     hipEvent_t gate = h->gate_event;
-    if (!gate) { gate = h->ev_chain_gate; DVS_HIP(hipEventRecord(gate, h->stream)); }
+    if (!gate) { gate = h->ev[kEvChainGate]; DVS_HIP(hipEventRecord(gate, h->stream)); }
     DVS_HIP(hipStreamWaitEvent(h->pf_stream, gate, 0));
   }
-  // asynchronous quad-trees: the FAST that follows this chain writes candidate set cset + 1, last read by the tree of two calls ago
+  DVS_TRY(W.ready(W.pyr.at(W.pyr.alt)));
+  u8* const pyr = W.pyr.at(W.pyr.alt).pyr.get();
+  // asynchronous quad-trees: the FAST that follows this chain writes the next candidate set, last read by the tree of two calls ago
   // (after `ring` asynchronous calls in a row the wait above — the descriptor stage of that very batch, which followed its tree — covers it)
-  if (h->async_oct && h->octdone_valid[(h->cset + 1) % h->ring] && !(pend && h->async_run >= h->ring))
-    DVS_HIP(hipStreamWaitEvent(h->pf_stream, h->ev_octdone[(h->cset + 1) % h->ring], 0));
+  if (h->async_oct && W.cand.next().done_valid && !(pend && h->async_run >= h->ring))
+    DVS_HIP(hipStreamWaitEvent(h->pf_stream, W.cand.next().done, 0));
   ImgSrc nsrc = src;
   nsrc.img0 = next_img0;
   h->timer.begin(DVS_STAGE_PYRAMID, h->pf_stream);  // the pyramid stage of the overlapped schedule IS this prefetch chain
@@ -764,17 +777,17 @@ dvs_status launch_prefetch(dvs_orb* h, const ImgSrc& src, int nimg, const u8* ne
   // frames per step: 0.103 / 0.119 ms against 0.092 / 0.103, its LDS tiles take FAST's workgroup slots; EXPERIMENTS.md)
   const bool want_graph = h->env_chain_graph >= 0 ? h->env_chain_graph == 1 : nimg <= 12;
   if (!want_graph) {
-    DVS_TRY(launch_pyramid_chain(h, nsrc, nimg, h->d_pyr_alt, h->pf_stream, false));
+    DVS_TRY(launch_pyramid_chain(h, nsrc, nimg, pyr, h->pf_stream, false));
   } else {
     dvs_orb::ChainGraph* cg = nullptr;
     for (auto& c : h->chain_graphs)
-      if (c.img0 == next_img0 && c.step0 == src.step0 && c.fstride0 == src.fstride0 && c.nimg == nimg && c.pyr == h->d_pyr_alt) { cg = &c; break; }
+      if (c.img0 == next_img0 && c.step0 == src.step0 && c.fstride0 == src.fstride0 && c.nimg == nimg && c.pyr == pyr) { cg = &c; break; }
     if (cg && cg->exec) {
       DVS_HIP(hipGraphLaunch(cg->exec, h->pf_stream));
       h->chain_graph_launches++;
     } else if (cg) {   // second time: capture (nothing runs), instantiate, launch
       DVS_HIP(hipStreamBeginCapture(h->pf_stream, hipStreamCaptureModeThreadLocal));
-      const dvs_status cs = launch_pyramid_chain(h, nsrc, nimg, h->d_pyr_alt, h->pf_stream, false);
+      const dvs_status cs = launch_pyramid_chain(h, nsrc, nimg, pyr, h->pf_stream, false);
       const hipError_t ce = hipStreamEndCapture(h->pf_stream, &cg->graph);
       if (cs != DVS_OK) return cs;
       DVS_HIP(ce);
@@ -786,14 +799,13 @@ dvs_status launch_prefetch(dvs_orb* h, const ImgSrc& src, int nimg, const u8* ne
         DVS_HIP(hipStreamSynchronize(h->pf_stream));
         drop_chain_graphs(h);
       }
-      h->chain_graphs.push_back({next_img0, src.step0, src.fstride0, nimg, h->d_pyr_alt, nullptr, nullptr});
-      DVS_TRY(launch_pyramid_chain(h, nsrc, nimg, h->d_pyr_alt, h->pf_stream, false));
+      h->chain_graphs.push_back({next_img0, src.step0, src.fstride0, nimg, pyr, nullptr, nullptr});
+      DVS_TRY(launch_pyramid_chain(h, nsrc, nimg, pyr, h->pf_stream, false));
     }
   }
   h->timer.end(h->pf_stream);
   h->pf_idx ^= 1;
-  h->ev_prefetch = h->ev_pf2[h->pf_idx];
-  DVS_HIP(hipEventRecord(h->ev_prefetch, h->pf_stream));
+  DVS_HIP(hipEventRecord(h->ev[kEvPrefetch + h->pf_idx], h->pf_stream));
   h->pf_valid = true; h->pf_img = next_img0; h->pf_step = src.step0; h->pf_fstride = src.fstride0; h->pf_nimg = nimg;
   return DVS_OK;
 }
@@ -802,40 +814,44 @@ dvs_status launch_prefetch(dvs_orb* h, const ImgSrc& src, int nimg, const u8* ne
 // streaming blur kernel: dword-aligned level-0 rows of width % 4 == 0 (border by byte permutes) and levels >= 1 written by
 // k_resize4 / k_pyr_cascade (which also write the reflected border columns); anything else takes the generic tile kernel
 bool blur_stream_ok(const dvs_orb* h, const ImgSrc& src, bool cascade) {
-  const Geom& G = h->geom;
+  const Geom& G = h->ws.geom;
   bool stream_ok = (((uintptr_t)src.img0) | src.step0 | src.fstride0) % 4 == 0 && G.lv[0].w % 4 == 0;
   for (int l = 1; l < G.nlevels; l++) stream_ok = stream_ok && (cascade || G.lv[l].gtab >= 0);
   return stream_ok;
 }
 
 void launch_blur(dvs_orb* h, const ImgSrc& src, int nimg, hipStream_t bst, bool cascade) {
-  const Geom& G = h->geom;
+  Workspace& W = h->ws;
+  const Geom& G = W.geom;
   const bool stream_ok = blur_stream_ok(h, src, cascade);
   // matrix-core blur: 16-byte aligned rows (the pyramid block always is; a caller's level 0 when its pointer and strides are)
-  const bool mfma_ok = h->env_blur_mfma && h->blur_mfma_ok && stream_ok &&
+  const bool mfma_ok = h->env_blur_mfma && W.blur_mfma_ok && stream_ok &&
                        (((uintptr_t)src.img0 | src.step0 | src.fstride0) % 16 == 0) && src.step0 >= 16;
   if (mfma_ok && h->env_blur_mfma == 2)
-    hipLaunchKernelGGL(k_blur_mfma_direct, dim3(h->n_blurcols, nimg), dim3(256), 0, bst, h->d_geom, h->d_blurcols, h->n_blurcols, src, h->d_blur,
-                       h->d_blurtab, h->blur_avt);
+    hipLaunchKernelGGL(k_blur_mfma_direct, dim3(W.n_blurcols, nimg), dim3(256), 0, bst, W.d_geom.get(), W.d_blurcols.get(), W.n_blurcols, src, W.blur.cur().blur.get(),
+                       W.d_blurtab.get(), W.blur_avt);
   else if (mfma_ok)
-    hipLaunchKernelGGL(k_blur_mfma, dim3(h->n_blurcols, nimg), dim3(256), 0, bst, h->d_geom, h->d_blurcols, h->n_blurcols, src, h->d_blur,
-                       h->d_blurtab, h->blur_avt);
+    hipLaunchKernelGGL(k_blur_mfma, dim3(W.n_blurcols, nimg), dim3(256), 0, bst, W.d_geom.get(), W.d_blurcols.get(), W.n_blurcols, src, W.blur.cur().blur.get(),
+                       W.d_blurtab.get(), W.blur_avt);
   else if (stream_ok)
-    hipLaunchKernelGGL(k_blur_stream, dim3((G.blurStrips + 3) / 4, nimg), dim3(256), 0, bst, h->d_geom, h->d_strips, G.blurStrips, src, h->d_blur);
+    hipLaunchKernelGGL(k_blur_stream, dim3((G.blurStrips + 3) / 4, nimg), dim3(256), 0, bst, W.d_geom.get(), W.d_strips.get(), G.blurStrips, src, W.blur.cur().blur.get());
   else
-    hipLaunchKernelGGL(k_blur, dim3(G.blurTiles, nimg), dim3(256), 0, bst, h->d_geom, h->d_tiles, src, h->d_blur);
+    hipLaunchKernelGGL(k_blur, dim3(G.blurTiles, nimg), dim3(256), 0, bst, W.d_geom.get(), W.d_tiles.get(), src, W.blur.cur().blur.get());
 }
 
 // quad-tree of every (frame, level) on `qs`.  graded: one launch per level class with that class's capacities (LDS) instead of level 0's
 void launch_octree(dvs_orb* h, int nimg, hipStream_t qs, uint32_t levelMask, bool graded) {
-  const Geom& G = h->geom;
-  if (graded && h->oct_ncls >= 2) {
-    for (int c = 0; c < h->oct_ncls; c++) {
-      const int l0 = h->oct_l0[c], nl = h->oct_l0[c + 1] - l0;
+  Workspace& W = h->ws;
+  const Geom& G = W.geom;
+  const CandSlot& C = W.cand.cur();
+  const LvlSlot& K = W.lvl.cur();
+  if (graded && W.oct_ncls >= 2) {
+    for (int c = 0; c < W.oct_ncls; c++) {
+      const int l0 = W.oct_l0[c], nl = W.oct_l0[c + 1] - l0;
       if (nl <= 0) continue;
       // the first class holds the long workgroups (levels 0 and 1): 512 threads each; the others 256
-      hipLaunchKernelGGL(k_octree, dim3(nimg, nl), dim3(c == 0 ? kOctTMax : kOctT), h->oct_smem_cls[c], qs, h->d_geom, h->d_cand, h->d_cellcount, h->d_celloff,
-                         h->d_pts, h->d_nodeof, h->d_candtotal, h->d_lvlkp, h->d_lvlcount, h->oct_nmax_cls[c], h->oct_ptscap_cls[c], levelMask, l0);
+      hipLaunchKernelGGL(k_octree, dim3(nimg, nl), dim3(c == 0 ? kOctTMax : kOctT), W.oct_smem_cls[c], qs, W.d_geom.get(), C.cand.get(), C.cellcount.get(), W.d_celloff.get(),
+                         W.d_pts.get(), W.d_nodeof.get(), W.d_candtotal.get(), K.lvlkp.get(), K.lvlcount.get(), W.oct_nmax_cls[c], W.oct_ptscap_cls[c], levelMask, l0);
     }
     return;
   }
@@ -843,8 +859,8 @@ void launch_octree(dvs_orb* h, int nimg, hipStream_t qs, uint32_t levelMask, boo
   // two 256-thread workgroups per CU run beside the blur and a pipelined caller's match, and the wave slots 512 threads hold cost
   // those more than the shorter tree returns (64 frames: 0.681 -> 0.664 ms per step; 128 / 384 threads: 0.729 / 0.690)
   const int oct_t = h->env_oct_threads ? h->env_oct_threads : (G.nlevels * nimg <= 256 ? kOctTMax : kOctT);
-  hipLaunchKernelGGL(k_octree, dim3(nimg, G.nlevels), dim3(oct_t), h->octree_smem, qs, h->d_geom, h->d_cand, h->d_cellcount,
-                     h->d_celloff, h->d_pts, h->d_nodeof, h->d_candtotal, h->d_lvlkp, h->d_lvlcount, h->octree_nmax, h->octree_ptscap, levelMask, 0);
+  hipLaunchKernelGGL(k_octree, dim3(nimg, G.nlevels), dim3(oct_t), W.octree_smem, qs, W.d_geom.get(), C.cand.get(), C.cellcount.get(),
+                     W.d_celloff.get(), W.d_pts.get(), W.d_nodeof.get(), W.d_candtotal.get(), K.lvlkp.get(), K.lvlcount.get(), W.octree_nmax, W.octree_ptscap, levelMask, 0);
 }
 
 // Enqueue the whole extraction of `nimg` frames whose level 0 is described by `src`.  Schedule:
@@ -854,12 +870,13 @@ void launch_octree(dvs_orb* h, int nimg, hipStream_t qs, uint32_t levelMask, boo
 // A caller stream released by the after-FAST event runs beside quad-tree and blur (bench.py: the previous batch's match).
 dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps, u8* d_desc, int capacity, int* d_nout,
                            const u8* next_img0 = nullptr, bool may_defer = false) {
-  const Geom& G = h->geom;
+  Workspace& W = h->ws;
+  const Geom& G = W.geom;
   hipStream_t st = h->stream;
   const bool aligned0 = (((uintptr_t)src.img0) | src.step0 | src.fstride0) % 4 == 0;
   const uint32_t allLevels = G.nlevels >= 32 ? ~0u : ((1u << G.nlevels) - 1u);
   const bool sharded = (src.levelMask & allLevels) != allLevels || src.slotted;   // level-sharded call: the chain up to its top level, its levels only
-  // a pyramid prefetched for exactly this batch (same buffer, layout and count)?  then it is already (being) built in d_pyr_alt
+  // a pyramid prefetched for exactly this batch (same buffer, layout and count)?  then it is already (being) built in the pyramid ring's alt
   const bool prefetched = h->pf_valid && h->overlap && h->pf_img == src.img0 && h->pf_step == src.step0 &&
                           h->pf_fstride == src.fstride0 && h->pf_nimg == nimg;
   h->pf_valid = false;
@@ -870,7 +887,7 @@ dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps
   bool pend = h->out_pending;
   h->out_pending = false;
   if (pend && !(prefetched && may_defer)) {
-    DVS_HIP(hipStreamWaitEvent(st, h->ev_out, 0));
+    DVS_HIP(hipStreamWaitEvent(st, h->ev_outs.cur(), 0));
     pend = false;
   }
   // this call defers its own descriptor stage: outputs by event, stage on the auxiliary stream, main stream not joined
@@ -880,19 +897,10 @@ dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps
   // auxiliary work above — its tree included — and keeps the current set.)
   const bool async = h->async_oct && prefetched && will_defer && aligned0;
   if (async) {
-    h->cset = (h->cset + 1) % h->ring;
-    if (!h->d_cand2[h->cset]) {
-      DVS_HIP(hipMalloc((void**)&h->d_cand2[h->cset], (size_t)h->max_batch * G.candPerFrame * 4));
-      DVS_HIP(hipMalloc((void**)&h->d_cellcount2[h->cset], (size_t)h->max_batch * G.totalCells * 4));
-    }
-    h->d_cand = h->d_cand2[h->cset]; h->d_cellcount = h->d_cellcount2[h->cset];
-    if (h->tail_stream) {
-      h->bset = (h->bset + 1) % h->ring;
-      if (!h->d_blur3[h->bset]) DVS_HIP(hipMalloc((void**)&h->d_blur3[h->bset], (size_t)h->max_batch * G.frameBytes));
-      h->d_blur = h->d_blur3[h->bset];
-    }
+    DVS_TRY(W.turn(W.cand));
+    if (h->tail_stream) DVS_TRY(W.turn(W.blur));
   } else if (h->last_async) {
-    DVS_HIP(hipStreamWaitEvent(st, h->ev_octdone[h->cset], 0));   // this call's FAST rewrites the set the previous call's tree reads
+    DVS_HIP(hipStreamWaitEvent(st, W.cand.cur().done, 0));   // this call's FAST rewrites the set the previous call's tree reads
   }
   h->last_async = async;
   h->async_run = async ? h->async_run + 1 : 0;
@@ -903,11 +911,11 @@ dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps
   //    ONE launch (k_pyr_cascade: +26 % at 2 frames, +12 % at 8, -2 % at 16; beside FAST at 64 frames the chain wins, 0.20 vs 0.29 ms);
   //    otherwise the seven launches run on the auxiliary stream while FAST starts on level 0 and follows level by level.
   if (prefetched) {
-    std::swap(h->d_pyr, h->d_pyr_alt);
-    if (!h->pf_joined) DVS_HIP(hipStreamWaitEvent(st, h->ev_prefetch, 0));
+    W.pyr.take();
+    if (!h->pf_joined) DVS_HIP(hipStreamWaitEvent(st, h->ev[kEvPrefetch + h->pf_idx], 0));
   }
   h->pf_joined = false;
-  src.pyr = h->d_pyr;
+  src.pyr = W.pyr.cur().pyr.get();
   int topLevel = 0;
   for (int l = 0; l < G.nlevels; l++) if ((src.levelMask >> l) & 1u) topLevel = l;
   const bool want_cascade = h->env_cascade >= 0 ? h->env_cascade == 1 : nimg <= 8;
@@ -915,18 +923,18 @@ dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps
   const bool ov = !prefetched && !cascade && !sharded && h->overlap && G.nlevels >= 2;   // in-step chain beside FAST
   if (cascade) {
     h->timer.begin(DVS_STAGE_PYRAMID, st);
-    hipLaunchKernelGGL(k_pyr_cascade<256>, dim3(G.pyrTiles, nimg), dim3(256), 2 * (size_t)G.pyrLds, st, h->d_geom, h->d_pyrtiles, src,
-                       h->d_xofs, h->d_alpha, h->d_yofs, h->d_beta, G.pyrLds);
+    hipLaunchKernelGGL(k_pyr_cascade<256>, dim3(G.pyrTiles, nimg), dim3(256), 2 * (size_t)G.pyrLds, st, W.d_geom.get(), W.d_pyrtiles.get(), src,
+                       W.d_xofs.get(), W.d_alpha.get(), W.d_yofs.get(), W.d_beta.get(), G.pyrLds);
     h->timer.end(st);
   } else if (!prefetched) {
     hipStream_t pst = st;
     if (ov) {
       pst = h->aux_stream;
-      DVS_HIP(hipEventRecord(h->ev_start, st));          // inputs ready / previous call's consumers of the pyramid done
-      DVS_HIP(hipStreamWaitEvent(pst, h->ev_start, 0));
+      DVS_HIP(hipEventRecord(h->ev[kEvStart], st));          // inputs ready / previous call's consumers of the pyramid done
+      DVS_HIP(hipStreamWaitEvent(pst, h->ev[kEvStart], 0));
     }
     h->timer.begin(DVS_STAGE_PYRAMID, pst);
-    DVS_TRY(launch_pyramid_chain(h, src, nimg, h->d_pyr, pst, ov, sharded ? topLevel : -1));
+    DVS_TRY(launch_pyramid_chain(h, src, nimg, W.pyr.cur().pyr.get(), pst, ov, sharded ? topLevel : -1));
     h->timer.end(pst);
   }
   if (next_img0 && h->overlap && G.nlevels >= 2) DVS_TRY(launch_prefetch(h, src, nimg, next_img0, pend));
@@ -938,7 +946,7 @@ dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps
   // takes the guard right in front of its descriptor stage instead, so that a slow reader does not hold up the blur as well.
   if (h->overlap) {
     if (h->guard_event && !will_defer) { DVS_HIP(hipStreamWaitEvent(h->aux_stream, h->guard_event, 0)); h->guard_event = nullptr; }
-    if (h->pf_valid && !sharded && !(h->defer_outputs && h->output_event)) { DVS_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_prefetch, 0)); h->pf_joined = true; }
+    if (h->pf_valid && !sharded && !(h->defer_outputs && h->output_event)) { DVS_HIP(hipStreamWaitEvent(h->aux_stream, h->ev[kEvPrefetch + h->pf_idx], 0)); h->pf_joined = true; }
   }
 
   // (tail mode: this call's blur first — it needs the pyramid only, which the main stream has just joined; the one record behind FAST
@@ -976,19 +984,14 @@ dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps
   // fills the machine while the latency-bound quad-tree (one workgroup per frame x level) runs beside it; forked before FAST the two
   // throughput-bound kernels merely shared the CUs.  One record behind FAST serves the caller and the blur's fork.
   hipStream_t bst = h->overlap ? h->aux_stream : st;
-  hipEvent_t ev_fastdone = h->after_fast_event ? h->after_fast_event : h->ev_fork;
+  hipEvent_t ev_fastdone = h->after_fast_event ? h->after_fast_event : h->ev[kEvFork];
   if (h->after_fast_event || h->overlap) DVS_HIP(hipEventRecord(ev_fastdone, st));
 
   // 3. quad-tree (latency-bound: launched first so that its workgroups become resident ahead of the blur's).  After a deferred stage
   //    it takes the next of the three level keypoint sets: stages k - 1 and k - 2 may still read theirs; stage k - 3 wrote its event
   //    before the level chain of THIS batch started, which this call's FAST waited for.
   if (pend) {
-    h->lset = (h->lset + 1) % h->ring;
-    if (!h->d_lvlkp3[h->lset]) {
-      DVS_HIP(hipMalloc((void**)&h->d_lvlcount3[h->lset], (size_t)h->max_batch * G.nlevels * 4));
-      DVS_HIP(hipMalloc((void**)&h->d_lvlkp3[h->lset], (size_t)h->max_batch * (size_t)G.kpBlock * 4));
-    }
-    h->d_lvlkp = h->d_lvlkp3[h->lset]; h->d_lvlcount = h->d_lvlcount3[h->lset];
+    DVS_TRY(W.turn(W.lvl));
   }
   //    Asynchronous (dvs_orb_set_async_quadtree, pipelined callers): on the auxiliary stream behind this call's FAST — nothing on the main
   //    stream needs it, so the next call's FAST follows this one's immediately and the tree runs beside it.
@@ -997,19 +1000,19 @@ dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps
   // a lane (one stream, a few frames): quad-trees and streaming blur in one launch (k_octree_blur) — the blur then runs beside the trees
   // instead of behind them (the lane's chain: -13 us of ~140 at one frame)
   const int blurRows = (G.blurStrips + kOctTMax / 64 - 1) / (kOctTMax / 64);
-  const bool fuse_blur = h->single_stream && !async && !sharded && !(h->env_blur_mfma && h->blur_mfma_ok) &&
+  const bool fuse_blur = h->single_stream && !async && !sharded && !(h->env_blur_mfma && W.blur_mfma_ok) &&
                          blur_stream_ok(h, src, cascade) && (long)nimg * (G.nlevels + blurRows) <= 256;
   h->timer.begin(DVS_STAGE_OCTREE, qs);
   if (fuse_blur) {
     if (h->guard_event) { DVS_HIP(hipStreamWaitEvent(qs, h->guard_event, 0)); h->guard_event = nullptr; }   // (the blur's place below takes it otherwise)
-    hipLaunchKernelGGL(k_octree_blur, dim3(nimg, G.nlevels + blurRows), dim3(kOctTMax), h->octree_smem, qs, h->d_geom, h->d_cand, h->d_cellcount,
-                       h->d_celloff, h->d_pts, h->d_nodeof, h->d_candtotal, h->d_lvlkp, h->d_lvlcount, h->octree_nmax, h->octree_ptscap, src.levelMask,
-                       G.nlevels, h->d_strips, G.blurStrips, src, h->d_blur);
+    hipLaunchKernelGGL(k_octree_blur, dim3(nimg, G.nlevels + blurRows), dim3(kOctTMax), W.octree_smem, qs, W.d_geom.get(), W.cand.cur().cand.get(), W.cand.cur().cellcount.get(),
+                       W.d_celloff.get(), W.d_pts.get(), W.d_nodeof.get(), W.d_candtotal.get(), W.lvl.cur().lvlkp.get(), W.lvl.cur().lvlcount.get(), W.octree_nmax, W.octree_ptscap, src.levelMask,
+                       G.nlevels, W.d_strips.get(), G.blurStrips, src, W.blur.cur().blur.get());
   } else {
     launch_octree(h, nimg, qs, src.levelMask, async && G.nlevels * nimg > 256);
   }
   h->timer.end(qs);
-  if (async) { DVS_HIP(hipEventRecord(h->ev_octdone[h->cset], qs)); h->octdone_valid[h->cset] = true; }
+  if (async) { DVS_HIP(hipEventRecord(W.cand.cur().done, qs)); W.cand.cur().done_valid = true; }
 
   // 4. blur
   if (async) {}   // (the auxiliary stream already waited for FAST in front of the quad-tree)
@@ -1030,36 +1033,36 @@ dvs_status enqueue_extract(dvs_orb* h, ImgSrc src, int nimg, dvs_keypoint* d_kps
     // light on memory) starts at once and runs beside it (fetch-bound).  Consumers order themselves on the caller's output event.
     dst = tail ? h->tail_stream : bst;
     if (tail) {     // the quad-tree's own event: the tree followed FAST, FAST followed the blur
-      DVS_HIP(hipStreamWaitEvent(dst, h->ev_octdone[h->cset], 0));
+      DVS_HIP(hipStreamWaitEvent(dst, W.cand.cur().done, 0));
     } else if (!async) {   // (asynchronous: the quad-tree precedes on this very stream)
-      DVS_HIP(hipEventRecord(h->ev_oct, st));
-      DVS_HIP(hipStreamWaitEvent(bst, h->ev_oct, 0));
+      DVS_HIP(hipEventRecord(h->ev[kEvOct], st));
+      DVS_HIP(hipStreamWaitEvent(bst, h->ev[kEvOct], 0));
     }
     if (late_guard) DVS_HIP(hipStreamWaitEvent(dst, late_guard, 0));   // the caller's readers of the output buffers
   } else if (bst != st) {
-    DVS_HIP(hipEventRecord(h->ev_blur, bst));
-    DVS_HIP(hipStreamWaitEvent(st, h->ev_blur, 0));
+    DVS_HIP(hipEventRecord(h->ev[kEvBlur], bst));
+    DVS_HIP(hipStreamWaitEvent(st, h->ev[kEvBlur], 0));
   }
   h->timer.begin(DVS_STAGE_DESCRIBE, dst);
   // tile-by-tile visiting order from 16 frames on: below, the descriptor stage is latency and the ranking kernel's 12 us count
   if (h->env_desc_order && nimg >= 16) {
-    hipLaunchKernelGGL(k_kp_order, dim3(nimg, G.nlevels), dim3(256), 0, dst, h->d_geom, h->d_lvlkp, h->d_lvlcount, h->d_kpsorted, h->d_kpsortidx);
-    hipLaunchKernelGGL(k_describe, dim3((G.kpBlock + 4 * kDescKP - 1) / (4 * kDescKP), nimg), dim3(256), 0, dst, h->d_geom, src, h->d_blur,
-                       h->d_kpsorted, h->d_kpsortidx, h->d_lvlcount, d_kps, d_desc, d_nout, capacity);
+    hipLaunchKernelGGL(k_kp_order, dim3(nimg, G.nlevels), dim3(256), 0, dst, W.d_geom.get(), W.lvl.cur().lvlkp.get(), W.lvl.cur().lvlcount.get(), W.d_kpsorted.get(), W.d_kpsortidx.get());
+    hipLaunchKernelGGL(k_describe, dim3((G.kpBlock + 4 * kDescKP - 1) / (4 * kDescKP), nimg), dim3(256), 0, dst, W.d_geom.get(), src, W.blur.cur().blur.get(),
+                       W.d_kpsorted.get(), W.d_kpsortidx.get(), W.lvl.cur().lvlcount.get(), d_kps, d_desc, d_nout, capacity);
   } else {   // list order: the identity index table
-    hipLaunchKernelGGL(k_describe, dim3((G.kpBlock + 4 * kDescKP - 1) / (4 * kDescKP), nimg), dim3(256), 0, dst, h->d_geom, src, h->d_blur,
-                       h->d_lvlkp, h->d_kpident, h->d_lvlcount, d_kps, d_desc, d_nout, capacity);
+    hipLaunchKernelGGL(k_describe, dim3((G.kpBlock + 4 * kDescKP - 1) / (4 * kDescKP), nimg), dim3(256), 0, dst, W.d_geom.get(), src, W.blur.cur().blur.get(),
+                       W.lvl.cur().lvlkp.get(), W.d_kpident.get(), W.lvl.cur().lvlcount.get(), d_kps, d_desc, d_nout, capacity);
   }
   h->timer.end(dst);
   if (will_defer) {
-    h->ev_out = h->ev_outs[h->out_gen % (h->ring - 1)];
+    h->ev_outs.advance();
     h->out_gen++;
-    DVS_HIP(hipEventRecord(h->ev_out, dst));
+    DVS_HIP(hipEventRecord(h->ev_outs.cur(), dst));
     DVS_HIP(hipEventRecord(h->output_event, dst));
     h->out_pending = true;
     h->gate_event = nullptr;   // the next call's chain is gated on ev_outs (launch_prefetch)
   } else {   // end of the call on the main stream: the caller's output event, or our own — the next call's prefetch gate
-    h->gate_event = (may_defer && h->output_event) ? h->output_event : h->ev_end;
+    h->gate_event = (may_defer && h->output_event) ? h->output_event : h->ev[kEvEnd];
     DVS_HIP(hipEventRecord(h->gate_event, st));
   }
   DVS_HIP(hipGetLastError());
@@ -1129,10 +1132,10 @@ static dvs_status orb_create(const dvs_orb_params* params, int32_t device, bool 
   // 0.628 -> 0.592 ms, neutral below 64)
   bool ok = single_stream || (hipStreamCreateWithPriority(&h->aux_stream, hipStreamNonBlocking, prio_lo) == hipSuccess &&
                               hipStreamCreateWithPriority(&h->pf_stream, hipStreamNonBlocking, prio_hi) == hipSuccess);
-  hipEvent_t* evs[] = {&h->ev_fork, &h->ev_blur, &h->ev_start, &h->ev_chain_gate, &h->ev_pf2[0], &h->ev_pf2[1], &h->ev_outs[0], &h->ev_outs[1], &h->ev_outs[2],
-                       &h->ev_oct, &h->ev_end, &h->ev_octdone[0], &h->ev_octdone[1], &h->ev_octdone[2], &h->ev_octdone[3]};
-  for (hipEvent_t* ev : evs) ok = ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
-  for (int l = 1; l < params->nlevels; l++) ok = ok && hipEventCreateWithFlags(&h->ev_level[l], hipEventDisableTiming) == hipSuccess;
+  for (Event& e : h->ev) ok = ok && e.create() == hipSuccess;
+  for (Event& e : h->ev_outs.slot) ok = ok && e.create() == hipSuccess;
+  for (int l = 1; l < params->nlevels; l++) ok = ok && h->ev_level[l].create() == hipSuccess;
+  h->ev_outs.rewind(h->ring - 1);
   if (!ok) {
     dvs_orb_destroy(h);
     set_error("stream / event creation failed");
@@ -1146,19 +1149,13 @@ static dvs_status orb_create(const dvs_orb_params* params, int32_t device, bool 
 void dvs_orb_destroy(dvs_orb* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  if (h->aux_stream) (void)hipStreamSynchronize(h->aux_stream);
-  if (h->pf_stream) (void)hipStreamSynchronize(h->pf_stream);
+  (void)quiesce(h);
   h->timer.resolve();
   free_workspace(h);
   if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
   if (h->pf_stream) (void)hipStreamDestroy(h->pf_stream);
-  hipEvent_t evs[] = {h->ev_fork, h->ev_blur, h->ev_start, h->ev_chain_gate, h->ev_pf2[0], h->ev_pf2[1], h->ev_outs[0], h->ev_outs[1], h->ev_outs[2], h->ev_oct, h->ev_end,
-                      h->ev_octdone[0], h->ev_octdone[1], h->ev_octdone[2], h->ev_octdone[3]};
-  for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->ev_level) if (e) (void)hipEventDestroy(e);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
+  delete h;   // (its events and the export ticket go with it)
 }
 
 int32_t dvs_orb_max_keypoints(const dvs_orb* h) { return h ? h->prm.nfeatures + 3 * h->prm.nlevels : 0; }
@@ -1174,12 +1171,8 @@ DVS_HOOK dvs_status dvs_orb_set_overlap(dvs_orb* h, int32_t on) {
   DVS_ARG(h);
   DVS_HIP(hipSetDevice(h->device));
   if (on && h->single_stream) { set_error("dvs_orb_set_overlap: this extractor was created with one stream only"); return DVS_ERR_UNSUPPORTED; }
-  DVS_HIP(hipStreamSynchronize(h->stream));
-  if (h->aux_stream) DVS_HIP(hipStreamSynchronize(h->aux_stream));
-  if (h->pf_stream) DVS_HIP(hipStreamSynchronize(h->pf_stream));
+  DVS_TRY(quiesce(h));
   h->pf_valid = false; h->pf_joined = false;
-  if (h->out_pending) DVS_HIP(hipEventSynchronize(h->ev_out));
-  h->out_pending = false;   // everything, a deferred descriptor stage included, has completed above
   h->overlap = on != 0;
   return DVS_OK;
 }
@@ -1187,11 +1180,8 @@ DVS_HOOK dvs_status dvs_orb_set_async_quadtree(dvs_orb* h, int32_t on) {
   DVS_ARG(h);
   if (on && h->single_stream) { set_error("dvs_orb_set_async_quadtree: this extractor was created with one stream only"); return DVS_ERR_UNSUPPORTED; }
   DVS_HIP(hipSetDevice(h->device));
-  DVS_HIP(hipStreamSynchronize(h->stream));
-  if (h->aux_stream) DVS_HIP(hipStreamSynchronize(h->aux_stream));
-  if (h->pf_stream) DVS_HIP(hipStreamSynchronize(h->pf_stream));
-  if (h->out_pending) DVS_HIP(hipEventSynchronize(h->ev_out));
-  h->out_pending = false; h->last_async = false;
+  DVS_TRY(quiesce(h));
+  h->last_async = false;
   h->async_oct = on != 0;
   return DVS_OK;
 }
@@ -1200,17 +1190,12 @@ DVS_HOOK int64_t dvs_orb_chain_graph_launches(const dvs_orb* h) { return h ? h->
 DVS_HOOK dvs_status dvs_orb_set_tail_stream(dvs_orb* h, void* hip_stream) {
   DVS_ARG(h);
   DVS_HIP(hipSetDevice(h->device));
-  DVS_HIP(hipStreamSynchronize(h->stream));
-  if (h->aux_stream) DVS_HIP(hipStreamSynchronize(h->aux_stream));
-  if (h->pf_stream) DVS_HIP(hipStreamSynchronize(h->pf_stream));
-  if (h->out_pending) { DVS_HIP(hipEventSynchronize(h->ev_out)); h->out_pending = false; }
+  DVS_TRY(quiesce(h));
   h->tail_stream = (hipStream_t)hip_stream;
   // the four-stream form rotates over rings of four (see `ring`); everything is idle here: restart every rotation at its first set
   h->ring = hip_stream ? 4 : 3;
-  h->cset = h->bset = h->lset = 0; h->out_gen = 0; h->async_run = 0;
-  for (bool& v : h->octdone_valid) v = false;
-  h->d_cand = h->d_cand2[0]; h->d_cellcount = h->d_cellcount2[0]; h->d_blur = h->d_blur3[0];
-  h->d_lvlkp = h->d_lvlkp3[0]; h->d_lvlcount = h->d_lvlcount3[0];
+  h->ws.rewind(h->ring); h->ev_outs.rewind(h->ring - 1); h->out_gen = 0; h->async_run = 0;
+  for (CandSlot& c : h->ws.cand.slot) c.done_valid = false;
   h->last_async = false;
   return DVS_OK;
 }
@@ -1227,10 +1212,7 @@ void* dvs_orb_get_stream(dvs_orb* h) { return h ? (void*)h->stream : nullptr; }
 dvs_status dvs_orb_synchronize(dvs_orb* h) {
   DVS_ARG(h);
   DVS_HIP(hipSetDevice(h->device));
-  DVS_HIP(hipStreamSynchronize(h->stream));
-  if (h->out_pending) { DVS_HIP(hipEventSynchronize(h->ev_out)); h->out_pending = false; }   // a deferred descriptor stage (auxiliary or tail stream)
-  if (h->pf_stream) DVS_HIP(hipStreamSynchronize(h->pf_stream));  // an announced next batch's pyramid may still be reading the caller's images
-  return DVS_OK;
+  return quiesce(h);   // a deferred descriptor stage (auxiliary or tail stream) and an announced next batch's chain, which reads the caller's images, included
 }
 
 dvs_status dvs_orb_get_tables(const dvs_orb* h, float* scale, float* inv_scale, float* sigma2, float* inv_sigma2,
@@ -1272,7 +1254,7 @@ dvs_status dvs_orb_extract_batch_device_masked(dvs_orb* h, const uint8_t* d_imgs
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(ensure_workspace(h, rows, cols));
   if (nimg == 0) return DVS_OK;
-  ImgSrc src{d_imgs, (uint64_t)step, (uint64_t)frame_stride, h->d_pyr, ~0u, 0};
+  ImgSrc src{d_imgs, (uint64_t)step, (uint64_t)frame_stride, h->ws.pyr.cur().pyr.get(), ~0u, 0};
   const u8* next = h->next_hint;
   h->next_hint = nullptr;
   h->mask = CandMask{d_masks, (uint64_t)mask_step, (uint64_t)mask_frame_stride};
@@ -1306,9 +1288,9 @@ dvs_status dvs_orb_extract_levels_device(dvs_orb* h, const uint8_t* d_imgs, int3
   DVS_TRY(ensure_workspace(h, rows, cols));
   if (nimg == 0) return DVS_OK;
   const LevelBlockLayout Y = level_block_layout(h, nimg);
-  if (Y.kpBlock != h->geom.kpBlock) { set_error("level block layout mismatch"); return DVS_ERR_ARG; }
+  if (Y.kpBlock != h->ws.geom.kpBlock) { set_error("level block layout mismatch"); return DVS_ERR_ARG; }
   const uint32_t all = h->prm.nlevels >= 32 ? ~0u : ((1u << h->prm.nlevels) - 1u);
-  ImgSrc src{d_imgs, (uint64_t)step, (uint64_t)frame_stride, h->d_pyr, level_mask & all, 1};
+  ImgSrc src{d_imgs, (uint64_t)step, (uint64_t)frame_stride, h->ws.pyr.cur().pyr.get(), level_mask & all, 1};
   h->next_hint = nullptr;
   return enqueue_extract(h, src, nimg, (dvs_keypoint*)(d_block + Y.kpsOff), d_block + Y.descOff, Y.kpBlock, (int*)d_block, nullptr);
 }
@@ -1378,33 +1360,34 @@ dvs_status dvs_orb_extract_batch_masked(dvs_orb* h, const uint8_t* const* imgs, 
   }
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(ensure_workspace(h, rows, cols));
-  const Geom& G = h->geom;
+  Workspace& W = h->ws;
+  const Geom& G = W.geom;
   const int cap = G.outCap;
   const uint64_t mbytes = (uint64_t)rows * cols;
-  if (masks && !h->d_mask) DVS_HIP(hipMalloc((void**)&h->d_mask, (size_t)h->max_batch * mbytes));   // (freed with the workspace)
+  if (masks && !W.d_mask.get()) DVS_TRY(W.d_mask.alloc((size_t)h->max_batch * mbytes));   // (freed with the workspace)
   for (int b0 = 0; b0 < nimg; b0 += h->max_batch) {
     const int nb = std::min(h->max_batch, nimg - b0);
     // level 0 staged into the frame's pyramid block (the reference copies it too: copyMakeBorder, :1189)
     for (int i = 0; i < nb; i++)
-      DVS_HIP(hipMemcpy2DAsync(h->d_pyr + (uint64_t)i * G.frameBytes + G.lv[0].off, G.lv[0].pitch, imgs[b0 + i], step, cols, rows,
+      DVS_HIP(hipMemcpy2DAsync(W.pyr.cur().pyr.get() + (uint64_t)i * G.frameBytes + G.lv[0].off, G.lv[0].pitch, imgs[b0 + i], step, cols, rows,
                                hipMemcpyHostToDevice, h->stream));
     // ... and the masks, packed (the previous chunk's filter read them on this stream before)
     if (masks)
       for (int i = 0; i < nb; i++)
-        DVS_HIP(hipMemcpy2DAsync(h->d_mask + (uint64_t)i * mbytes, cols, masks[b0 + i], mask_step, cols, rows, hipMemcpyHostToDevice, h->stream));
-    ImgSrc src{h->d_pyr + G.lv[0].off, (uint64_t)G.lv[0].pitch, G.frameBytes, h->d_pyr, ~0u, 0};
-    h->mask = masks ? CandMask{h->d_mask, (uint64_t)cols, mbytes} : CandMask{};
-    const dvs_status est = enqueue_extract(h, src, nb, h->d_kps, h->d_desc, cap, h->d_nout);
+        DVS_HIP(hipMemcpy2DAsync(W.d_mask.get() + (uint64_t)i * mbytes, cols, masks[b0 + i], mask_step, cols, rows, hipMemcpyHostToDevice, h->stream));
+    ImgSrc src{W.pyr.cur().pyr.get() + G.lv[0].off, (uint64_t)G.lv[0].pitch, G.frameBytes, W.pyr.cur().pyr.get(), ~0u, 0};
+    h->mask = masks ? CandMask{W.d_mask.get(), (uint64_t)cols, mbytes} : CandMask{};
+    const dvs_status est = enqueue_extract(h, src, nb, W.d_kps.get(), W.d_desc.get(), cap, W.d_nout.get());
     h->mask = CandMask{};
     DVS_TRY(est);
     if (h->env_host_poll) {
       // results by k_export_host into the pinned block; poll its sequence number (bounded spin, then the stream wait)
       static_assert(sizeof(dvs_keypoint) == 28, "k_export_host copies keypoints as 7 dwords");
       const int seq = ++h->export_seq;
-      hipLaunchKernelGGL(k_export_host, dim3(4, nb), dim3(256), 0, h->stream, nb, cap, (const uint32_t*)h->d_kps, (const uint32_t*)h->d_desc,
-                         h->d_nout, (uint32_t*)h->h_kps, (uint32_t*)h->h_desc, h->h_nout, h->d_ticket, h->h_seq, seq);
+      hipLaunchKernelGGL(k_export_host, dim3(4, nb), dim3(256), 0, h->stream, nb, cap, (const uint32_t*)W.d_kps.get(), (const uint32_t*)W.d_desc.get(),
+                         W.d_nout.get(), (uint32_t*)W.h_kps.get(), (uint32_t*)W.h_desc.get(), W.h_nout.get(), h->d_ticket.get(), h->h_seq.get(), seq);
       DVS_HIP(hipGetLastError());
-      const volatile int* ps = h->h_seq;
+      const volatile int* ps = h->h_seq.get();
       const auto t0 = std::chrono::steady_clock::now();
       for (int spin = 1; *ps != seq; spin++) {
         __builtin_ia32_pause();
@@ -1413,17 +1396,17 @@ dvs_status dvs_orb_extract_batch_masked(dvs_orb* h, const uint8_t* const* imgs, 
       __atomic_thread_fence(__ATOMIC_ACQUIRE);
       if (*ps != seq) DVS_HIP(hipStreamSynchronize(h->stream));
     } else {
-      DVS_HIP(hipMemcpyAsync(h->h_nout, h->d_nout, nb * 4, hipMemcpyDeviceToHost, h->stream));
-      DVS_HIP(hipMemcpyAsync(h->h_kps, h->d_kps, (size_t)nb * cap * sizeof(dvs_keypoint), hipMemcpyDeviceToHost, h->stream));
-      DVS_HIP(hipMemcpyAsync(h->h_desc, h->d_desc, (size_t)nb * cap * 32, hipMemcpyDeviceToHost, h->stream));
+      DVS_HIP(hipMemcpyAsync(W.h_nout.get(), W.d_nout.get(), nb * 4, hipMemcpyDeviceToHost, h->stream));
+      DVS_HIP(hipMemcpyAsync(W.h_kps.get(), W.d_kps.get(), (size_t)nb * cap * sizeof(dvs_keypoint), hipMemcpyDeviceToHost, h->stream));
+      DVS_HIP(hipMemcpyAsync(W.h_desc.get(), W.d_desc.get(), (size_t)nb * cap * 32, hipMemcpyDeviceToHost, h->stream));
       DVS_HIP(hipStreamSynchronize(h->stream));
     }
     for (int i = 0; i < nb; i++) {
-      const int n = h->h_nout[i];
+      const int n = W.h_nout.get()[i];
       if (n > capacity) { set_error("frame %d: %d keypoints > capacity %d", b0 + i, n, capacity); return DVS_ERR_CAPACITY; }
       n_out[b0 + i] = n;
-      memcpy(kps + (size_t)(b0 + i) * capacity, h->h_kps + (size_t)i * cap, (size_t)n * sizeof(dvs_keypoint));
-      memcpy(desc + (size_t)(b0 + i) * capacity * 32, h->h_desc + (size_t)i * cap * 32, (size_t)n * 32);
+      memcpy(kps + (size_t)(b0 + i) * capacity, W.h_kps.get() + (size_t)i * cap, (size_t)n * sizeof(dvs_keypoint));
+      memcpy(desc + (size_t)(b0 + i) * capacity * 32, W.h_desc.get() + (size_t)i * cap * 32, (size_t)n * 32);
     }
   }
   return DVS_OK;
@@ -1449,15 +1432,15 @@ dvs_status dvs_orb_extract_masked(dvs_orb* h, const uint8_t* gray, int32_t rows,
 }
 
 dvs_status dvs_orb_get_level(dvs_orb* h, int32_t frame, int32_t level, int32_t blurred, uint8_t* dst, int32_t cap_bytes) {
-  DVS_ARG(h && dst && h->d_geom && frame >= 0 && frame < h->last_nimg && level >= 0 && level < h->geom.nlevels);
-  const LevelGeom& L = h->geom.lv[level];
+  DVS_ARG(h && dst && h->ws.d_geom.get() && frame >= 0 && frame < h->last_nimg && level >= 0 && level < h->ws.geom.nlevels);
+  const LevelGeom& L = h->ws.geom.lv[level];
   if ((int64_t)L.w * L.h > cap_bytes) return DVS_ERR_CAPACITY;
   DVS_HIP(hipSetDevice(h->device));
   DVS_HIP(hipStreamSynchronize(h->stream));
   if (level == 0 && !blurred) {
     DVS_HIP(hipMemcpy2D(dst, L.w, h->last_src.img0 + (uint64_t)frame * h->last_src.fstride0, h->last_src.step0, L.w, L.h, hipMemcpyDeviceToHost));
   } else {
-    const u8* base = (blurred ? h->d_blur : h->d_pyr) + (uint64_t)frame * h->geom.frameBytes + L.off;
+    const u8* base = (blurred ? h->ws.blur.cur().blur.get() : h->ws.pyr.cur().pyr.get()) + (uint64_t)frame * h->ws.geom.frameBytes + L.off;
     DVS_HIP(hipMemcpy2D(dst, L.w, base, L.pitch, L.w, L.h, hipMemcpyDeviceToHost));
   }
   return DVS_OK;
@@ -1471,25 +1454,25 @@ static dvs_status read_packed(dvs_orb* h, const uint32_t* dsrc, int n, int32_t* 
 }
 
 DVS_HOOK dvs_status dvs_orb_get_candidates(dvs_orb* h, int32_t frame, int32_t level, int32_t* xys, int32_t cap, int32_t* n) {
-  DVS_ARG(h && xys && n && h->d_geom && frame >= 0 && frame < h->last_nimg && level >= 0 && level < h->geom.nlevels);
+  DVS_ARG(h && xys && n && h->ws.d_geom.get() && frame >= 0 && frame < h->last_nimg && level >= 0 && level < h->ws.geom.nlevels);
   DVS_HIP(hipSetDevice(h->device));
   DVS_HIP(hipStreamSynchronize(h->stream));
   int cnt = 0;
-  DVS_HIP(hipMemcpy(&cnt, h->d_candtotal + frame * h->geom.nlevels + level, 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(&cnt, h->ws.d_candtotal.get() + frame * h->ws.geom.nlevels + level, 4, hipMemcpyDeviceToHost));
   *n = cnt;
   if (cnt > cap) return DVS_ERR_CAPACITY;
-  return read_packed(h, h->d_pts + (uint64_t)frame * h->geom.ptsPerFrame + h->geom.lv[level].ptsOff, cnt, xys);
+  return read_packed(h, h->ws.d_pts.get() + (uint64_t)frame * h->ws.geom.ptsPerFrame + h->ws.geom.lv[level].ptsOff, cnt, xys);
 }
 
 DVS_HOOK dvs_status dvs_orb_get_level_keypoints(dvs_orb* h, int32_t frame, int32_t level, int32_t* xys, int32_t cap, int32_t* n) {
-  DVS_ARG(h && xys && n && h->d_geom && frame >= 0 && frame < h->last_nimg && level >= 0 && level < h->geom.nlevels);
+  DVS_ARG(h && xys && n && h->ws.d_geom.get() && frame >= 0 && frame < h->last_nimg && level >= 0 && level < h->ws.geom.nlevels);
   DVS_HIP(hipSetDevice(h->device));
   DVS_HIP(hipStreamSynchronize(h->stream));
   int cnt = 0;
-  DVS_HIP(hipMemcpy(&cnt, h->d_lvlcount + frame * h->geom.nlevels + level, 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(&cnt, h->ws.lvl.cur().lvlcount.get() + frame * h->ws.geom.nlevels + level, 4, hipMemcpyDeviceToHost));
   *n = cnt;
   if (cnt > cap) return DVS_ERR_CAPACITY;
-  return read_packed(h, h->d_lvlkp + (uint64_t)frame * h->geom.kpBlock + h->geom.lv[level].kpOff, cnt, xys);
+  return read_packed(h, h->ws.lvl.cur().lvlkp.get() + (uint64_t)frame * h->ws.geom.kpBlock + h->ws.geom.lv[level].kpOff, cnt, xys);
 }
 
 DVS_HOOK dvs_status dvs_orb_enable_stage_timing(dvs_orb* h, int32_t on) {
@@ -1529,13 +1512,11 @@ dvs_status dvs_test_sort_nodes_device(const int32_t* count, const int32_t* ulx, 
   if (n == 0) return DVS_OK;
   std::vector<unsigned long long> v(n);
   for (int i = 0; i < n; i++) v[i] = ((unsigned long long)(uint32_t)count[i] << 28) | ((unsigned long long)(uint16_t)ulx[i] << 12) | (unsigned long long)i;
-  unsigned long long* d = nullptr;
-  DVS_HIP(hipMalloc(&d, sizeof(unsigned long long) * n));
-  hipError_t e = hipMemcpy(d, v.data(), sizeof(unsigned long long) * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) { hipLaunchKernelGGL(k_test_sort, dim3(1), dim3(kOctT), 0, 0, d, n); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipMemcpy(v.data(), d, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  DVS_HIP(e);
+  DeviceBuf<unsigned long long> d;
+  DVS_TRY(d.upload(v));
+  hipLaunchKernelGGL(k_test_sort, dim3(1), dim3(kOctT), 0, 0, d.get(), n);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipMemcpy(v.data(), d.get(), sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
   for (int i = 0; i < n; i++) perm[i] = (int)(v[i] & 0xFFFull);
   return DVS_OK;
 }
@@ -1548,9 +1529,8 @@ dvs_status dvs_test_geometry(const dvs_orb_params* params, int32_t rows, int32_t
   h.prm = *params;
   build_ctor_tables(&h);
   Geom G;
-  std::vector<Cell> cells; std::vector<BlurTile> tiles; std::vector<BlurStrip> strips; std::vector<ResizeGroup> rg; std::vector<PyrTile> pt;
-  std::vector<int> xo, al, yo, be;
-  DVS_TRY(build_geometry(&h, rows, cols, G, cells, tiles, strips, rg, pt, xo, al, yo, be));
+  GeomTables tb;
+  DVS_TRY(build_geometry(&h, rows, cols, G, tb));
   for (int l = 0; l < G.nlevels; l++) {
     if (level_w) level_w[l] = G.lv[l].w;
     if (level_h) level_h[l] = G.lv[l].h;

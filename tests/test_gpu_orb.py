@@ -186,6 +186,54 @@ def test_resolution_changes_and_large_batch(gpu, oracle):
         _assert_same_result(int(nout[i]), kps[i, :nout[i]], desc[i, :nout[i]], n2, k2, d2)
 
 
+def test_ring_rewind_across_resolution_changes(gpu, oracle):
+    """one hooks-enabled handle: resolution A -> tail stream set (rings of four) -> prefetched, deferred steps -> resolution B (the
+    workspace is rebuilt while the rings are four deep and have turned) -> tail stream cleared (rings rewound to three) -> resolution A
+    again.  Keypoints and descriptors equal the oracle's at each stop, through the host entry point and through the pipelined steps."""
+    from dvslam_amd import ORBextractor, _lib
+    from dvslam_amd._lib import KP_DTYPE
+    L = _lib.lib(); T = _lib.test_lib()
+    nf, B, NB = 300, 2, 6
+    g = ORBextractor(nf, 1.2, 8, 20, 7, max_batch=B, hooks=True)
+    o = oracle.OracleORB(nf, 1.2, 8, 20, 7)
+    cap = g.capacity
+    tail = _lib.stream_create(0)
+    ev = [_lib.event_create(0) for _ in range(NB)]
+
+    def stop(rows, cols, seed):
+        img = synth.make_frame(seed, cols=cols, rows=rows)
+        _assert_same_result(*g(img), *o.extract(img))             # host entry point: rebuilds the workspace on a new resolution
+        frames = [np.stack([synth.make_frame(seed + B * b + i, cols=cols, rows=rows) for i in range(B)]) for b in range(3)]
+        d_img = [_lib.DeviceBuffer(f.nbytes).upload(f) for f in frames]
+        outs = [(_lib.DeviceBuffer(B * cap * 28), _lib.DeviceBuffer(B * cap * 32), _lib.DeviceBuffer(B * 4)) for _ in range(NB)]
+        for b in range(NB):                                        # every call but the first prefetched, every stage deferred
+            k, d, n = outs[b]
+            g.set_output_event(ev[b], defer=True)
+            if b + 1 < NB:
+                g.hint_next_batch_device(d_img[(b + 1) % 3].ptr)
+            g.extract_batch_device(d_img[b % 3].ptr, B, rows, cols, cols, rows * cols, k.ptr, d.ptr, cap, n.ptr)
+        g.synchronize(); _lib.stream_synchronize(tail)
+        for b in range(NB):
+            k, d, n = outs[b]
+            n1 = n.download(np.int32, B)
+            k1 = k.download(KP_DTYPE, B * cap).reshape(B, cap); d1 = d.download(np.uint8, B * cap * 32).reshape(B, cap, 32)
+            for f in range(B):
+                _assert_same_result(int(n1[f]), k1[f, :n1[f]], d1[f, :n1[f]], *o.extract(frames[b % 3][f]))
+
+    assert T.dvs_orb_set_async_quadtree(g._h, 1) == 0
+    stop(240, 320, 1)                                             # resolution A, rings of three
+    assert T.dvs_orb_set_tail_stream(g._h, tail) == 0
+    stop(240, 320, 11)                                            # ... of four: descriptor stages on the tail stream
+    stop(300, 404, 21)                                            # resolution B with the tail stream still set
+    assert T.dvs_orb_set_tail_stream(g._h, None) == 0
+    stop(300, 404, 31)                                            # rewound to three on the rebuilt workspace
+    stop(240, 320, 41)                                            # resolution A again
+    g.set_output_event(0, defer=False)
+    for e in ev:
+        L.dvs_event_destroy(e)
+    _lib.stream_destroy(tail)
+
+
 def test_overlap_on_off_identical(gpu):
     from dvslam_amd import ORBextractor
     img = synth.make_frame(3)
