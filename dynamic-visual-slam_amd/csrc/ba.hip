@@ -735,6 +735,212 @@ __global__ __launch_bounds__(kCholThreads) void k_lm_chol(int K, int n, const in
   }
 }
 
+// ---- tiled solver: 17..63 free cameras (n = 102..378; dvs_ba_set_device_window) ------------------------------------------------------
+// The augmented system (n + 1) x n no longer fits one workgroup's LDS (1.15 MB at n = 378), so it stays in global memory (it sits in
+// L2) and is factored right-looking in block columns of kTileW = 48 (eight cameras), every step a launch of its own on the handle's
+// stream — no grid-wide barrier, no flag between workgroups:
+//   k_lm_tile_assemble   A = S - sum of the Schur splits, the right-hand side as row n (what k_lm_chol does while loading its LDS)
+//   per block column c0: k_lm_tile_panel   one workgroup holds rows c0 .. n of the block column in LDS (<= 379 x 48 doubles = 145.5 KB)
+//                                          and factors it by k_lm_chol's scheme: six columns at a time, panel wavefronts with the rows in
+//                                          registers, look-ahead, the other wavefronts on the trailing columns of the block column;
+//                        k_lm_tile_update  the block column's rank-48 product leaves the trailing triangle (and row n), 16 x 16
+//                                          elements per workgroup
+//   k_lm_tile_backsolve  L^T x = y, one workgroup walking 48 rows of the factor at a time from the last.
+// Every element (i, k) still receives its subtractions l_ij l_kj in column order j = 0, 1, ... (block columns in order, the columns of
+// a block column in order, one rounded product and one rounded subtraction each): the factor and the forward-substituted y are
+// bit-identical to chol_solve's, as k_lm_chol's are.  The backward substitution subtracts from the last unknown down, like
+// k_lm_chol's (rounding-level difference from the host).  A non-positive pivot sets st->ok = 0; the launches behind it return at
+// once and the camera step stays zero.
+constexpr int kTileW = 48;
+constexpr int kTileMaxN = 6 * 63;
+constexpr int kTilePanelLds = (kTileMaxN + 1) * kTileW * 8;
+constexpr int kTileBackLds = kTileW * kTileMaxN * 8;
+
+__device__ __forceinline__ double lane_bcast(double v, int src) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src), hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+__global__ __launch_bounds__(256) void k_lm_tile_assemble(int K, int n, const double* __restrict__ S, const double* __restrict__ rhs,
+                                                          double* __restrict__ A, double* __restrict__ step) {
+  const int r = blockIdx.x, tid = threadIdx.x;   // a workgroup per row of A
+  if (r < n) {
+    const int cend = 6 * (r / 6) + 6;
+    for (int c = tid; c < n; c += 256) {
+      const size_t i = (size_t)r * n + c;
+      double v = 0.0;
+      if (c < cend) {
+        double tot = S[(size_t)n * n + i];
+#pragma unroll
+        for (int sp = 1; sp < kSchurSplit; sp++) tot += S[(size_t)(sp + 1) * n * n + i];
+        v = S[i] - tot;
+      }
+      A[i] = v;
+    }
+  } else {
+    for (int i = tid; i < n; i += 256) {
+      double tot = rhs[n + i];
+      for (int sp = 1; sp < kSchurSplit; sp++) tot += rhs[(size_t)(sp + 1) * n + i];
+      A[(size_t)n * n + i] = rhs[i] - tot;
+    }
+    for (int i = tid; i < 6 * K; i += 256) step[i] = 0.0;
+  }
+}
+
+// k_lm_chol's panel step over a row range of the m x w block column P (LDS): a0 = the six entries of columns c .. c + 5 of row
+// c + lane (lanes 0..5: the diagonal block), a1 = of row r1.  Factors the diagonal block, scales both rows, writes a1 (and a0 if this
+// wavefront owns those rows: every panel wavefront carries a0 — it needs the pivots and the block's l_tj on its own lanes — one stores it).
+__device__ __forceinline__ void tile_panel6(double* __restrict__ P, int w, int m, int c, int r1, int lane, bool ownsA0, double (&a0)[6],
+                                            double (&a1)[6], int* bad) {
+  const int r0 = c + lane;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    const double piv = lane_bcast(a0[j], j);
+    if (!(piv > 0) && lane == 0 && ownsA0) *bad = 1;   // the factorisation runs on (NaNs from here), as in k_lm_chol
+    const double d = sqrt(piv);
+    a0[j] = lane == j ? d : a0[j] / d;
+    a1[j] = a1[j] / d;
+#pragma unroll
+    for (int t = j + 1; t < 6; t++) {
+      const double lt = lane_bcast(a0[j], t);          // l of row c + t, column c + j
+      a0[t] -= a0[j] * lt;
+      a1[t] -= a1[j] * lt;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    if (ownsA0 && lane >= j && r0 < m) P[(size_t)r0 * w + c + j] = a0[j];
+    if (r1 < m) P[(size_t)r1 * w + c + j] = a1[j];
+  }
+}
+
+// block column c0 .. c0 + w - 1 of rows c0 .. n (m = n + 1 - c0 rows, the last one the right-hand side), all earlier block columns applied
+__global__ __launch_bounds__(kCholThreads) void k_lm_tile_panel(int n, int c0, int w, double* __restrict__ A, LmStatus* __restrict__ st) {
+  extern __shared__ double lds[];
+  __shared__ int bad;
+  if (!st->ok) return;
+  double* P = lds;
+  const int m = n + 1 - c0;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int r = wave; r < m; r += kCholThreads / 64)
+    for (int j = lane; j < w; j += 64) P[(size_t)r * w + j] = A[(size_t)(c0 + r) * n + c0 + j];
+  if (tid == 0) bad = 0;
+  __syncthreads();
+  // panel wavefront p: rows c + lane (shared) and c + 64 (p + 1) + lane; the rest tile the trailing columns kTy x 16
+  const int nPanel = (max(m - 64, 1) + 63) / 64;      // <= 5 at m = 379
+  const bool isPanel = wave < nPanel;
+  const int t3 = tid - 64 * nPanel, ty = t3 >> 4, tx = t3 & 15, kTy = (kCholThreads - 64 * nPanel) / 16;
+  double a0[6], a1[6];
+  if (isPanel) {
+    const int r0 = min(lane, m - 1), r1 = min(64 * (wave + 1) + lane, m - 1);
+#pragma unroll
+    for (int j = 0; j < 6; j++) { a0[j] = P[(size_t)r0 * w + j]; a1[j] = P[(size_t)r1 * w + j]; }
+    tile_panel6(P, w, m, 0, 64 * (wave + 1) + lane, lane, wave == 0, a0, a1, &bad);
+  }
+  __syncthreads();
+  for (int c = 0; c < w; c += 6) {
+    const int c1 = c + 6;
+    if (isPanel) {
+      if (c1 < w) {
+        // look-ahead: columns c1 .. c1 + 5 of this wavefront's rows minus the panel's product, then their factorisation from the registers
+        const int q1 = c1 + 64 * (wave + 1) + lane;
+        const int r0 = min(c1 + lane, m - 1), r1 = min(q1, m - 1);
+        double l0[6], l1[6];
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+          l0[j] = P[(size_t)r0 * w + c + j]; l1[j] = P[(size_t)r1 * w + c + j];
+          a0[j] = P[(size_t)r0 * w + c1 + j]; a1[j] = P[(size_t)r1 * w + c1 + j];
+        }
+#pragma unroll
+        for (int kk = 0; kk < 6; kk++)
+#pragma unroll
+          for (int j = 0; j < 6; j++) {
+            const double lk = lane_bcast(l0[j], kk);   // l of row c1 + kk, column c + j
+            a0[kk] -= l0[j] * lk;
+            a1[kk] -= l1[j] * lk;
+          }
+        tile_panel6(P, w, m, c1, q1, lane, wave == 0, a0, a1, &bad);
+      }
+    } else {
+      const int s0 = c1 + 6;               // first column the look-ahead does not cover
+      for (int i = s0 + ty; i < m; i += kTy) {
+        double li[6];
+#pragma unroll
+        for (int j = 0; j < 6; j++) li[j] = P[(size_t)i * w + c + j];
+        const int kmax = min(i, w - 1);
+        for (int k = s0 + tx; k <= kmax; k += 16) {
+          double acc = P[(size_t)i * w + k];
+#pragma unroll
+          for (int j = 0; j < 6; j++) acc -= li[j] * P[(size_t)k * w + c + j];
+          P[(size_t)i * w + k] = acc;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (bad) { if (tid == 0) st->ok = 0; return; }
+  for (int r = wave; r < m; r += kCholThreads / 64)
+    for (int j = lane; j < w; j += 64) A[(size_t)(c0 + r) * n + c0 + j] = P[(size_t)r * w + j];
+}
+
+// trailing update of block column c0 .. c0 + w - 1: element (i, k), c1 <= k <= i <= n (k < n), loses sum_j l_ij l_kj, j in column order
+__global__ __launch_bounds__(256) void k_lm_tile_update(int n, int c0, int w, double* __restrict__ A, const LmStatus* __restrict__ st) {
+  if (blockIdx.x > blockIdx.y) return;     // lower triangle of 16 x 16 tiles
+  if (!st->ok) return;
+  __shared__ double sI[kTileW][16], sK[kTileW][16];   // [column][row of the tile]: the inner loop reads along rows
+  const int c1 = c0 + w, i0 = c1 + 16 * blockIdx.y, k0 = c1 + 16 * blockIdx.x, tid = threadIdx.x;
+  for (int e = tid; e < 16 * w; e += 256) {
+    const int r = e / w, j = e - r * w;
+    sI[j][r] = i0 + r <= n ? A[(size_t)(i0 + r) * n + c0 + j] : 0.0;
+    sK[j][r] = k0 + r < n ? A[(size_t)(k0 + r) * n + c0 + j] : 0.0;
+  }
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15, i = i0 + ty, k = k0 + tx;
+  if (i > n || k > min(i, n - 1)) return;
+  double acc = A[(size_t)i * n + k];
+  for (int j = 0; j < w; j++) acc -= sI[j][ty] * sK[j][tx];
+  A[(size_t)i * n + k] = acc;
+}
+
+// L^T x = y (y = row n of A), kTileW rows of the factor in LDS at a time from the last: the first wavefront runs the chain inside the
+// chunk, then every thread takes the chunk's columns out of one earlier unknown, last column first (the same order of subtractions per
+// unknown as the plain loop).  Writes the (not yet negated) camera steps.
+__global__ __launch_bounds__(kCholThreads) void k_lm_tile_backsolve(int K, int n, const int* __restrict__ slotCam, const double* __restrict__ A,
+                                                                    double* __restrict__ step, const LmStatus* __restrict__ st) {
+  extern __shared__ double lds[];
+  __shared__ double b[kTileMaxN + 6];
+  if (!st->ok) return;
+  double* Lc = lds;                          // rows r0 .. r0 + h - 1, row stride n
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int i = tid; i < n; i += kCholThreads) b[i] = A[(size_t)n * n + i];
+  for (int r0 = ((n - 1) / kTileW) * kTileW; r0 >= 0; r0 -= kTileW) {
+    const int h = min(kTileW, n - r0);
+    __syncthreads();
+    for (int r = wave; r < h; r += kCholThreads / 64)
+      for (int j = lane; j <= r0 + r; j += 64) Lc[(size_t)r * n + j] = A[(size_t)(r0 + r) * n + j];
+    __syncthreads();
+    if (wave == 0) {
+      for (int j = r0 + h - 1; j >= r0; j--) {
+        const double* Lj = Lc + (size_t)(j - r0) * n;
+        const double xj = b[j] / Lj[j];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+        if (lane == 0) b[j] = xj;
+        if (r0 + lane < j) b[r0 + lane] -= Lj[r0 + lane] * xj;     // h <= 48 < 64: one pass
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < r0; i += kCholThreads) {
+      double v = b[i];
+      for (int j = r0 + h - 1; j >= r0; j--) v -= Lc[(size_t)(j - r0) * n + i] * b[j];
+      b[i] = v;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += kCholThreads) step[6 * slotCam[i / 6] + i % 6] = b[i];
+}
+
 // landmark steps by back-substitution (already negated), and each landmark's share of step.g and step^T H step.
 // Four lanes per landmark (three of them carry one coordinate m each): the kernel is a latency chain of ~10 observations x 2 passes
 // per landmark over 2000 landmarks, i.e. 8 workgroups with a thread per landmark (24 us); with a lane per coordinate it is 32
@@ -998,6 +1204,7 @@ struct dvs_ba {
   bool lm_poll = true, lm_speculate = true;   // DVS_LM_POLL=0 / DVS_LM_SPECULATE=0 (read once in dvs_ba_create): A/B switches of dvs_ba_solve_device
   bool lm_ready = false;   // dvs_ba_solve_device: structure tables built and uploaded
   int lm_nc = 0;           // ... free cameras
+  int device_window = 16;  // dvs_ba_set_device_window: most free cameras dvs_ba_solve_device takes; above 16 the tiled solver factors the system
   // device
   double *d_q = nullptr, *d_t = nullptr, *d_X = nullptr, *d_uv = nullptr;
   int *d_cam = nullptr, *d_lm = nullptr, *d_camChunkStart = nullptr, *d_lmStart = nullptr, *d_lmObs = nullptr;
@@ -1010,7 +1217,8 @@ struct dvs_ba {
   // device LM (dvs_ba_solve_device): accepted point, scaling, LM diagonal, step, per-landmark inverses, scaled W, Y = W V^-1,
   // reduced system, observation-of-(landmark, camera) table
   double *d_q0 = nullptr, *d_t0 = nullptr, *d_X0 = nullptr, *d_scale = nullptr, *d_diag = nullptr, *d_step = nullptr, *d_Vinv = nullptr,
-         *d_Ws = nullptr, *d_Y = nullptr, *d_S = nullptr, *d_rhs = nullptr, *d_lmPart = nullptr, *d_normPart = nullptr;
+         *d_Ws = nullptr, *d_Y = nullptr, *d_S = nullptr, *d_rhs = nullptr, *d_lmPart = nullptr, *d_normPart = nullptr,
+         *d_A = nullptr;   // the tiled solver's augmented system (n + 1) x n
   int *d_obsOf = nullptr, *d_slotCam = nullptr;
   unsigned char* d_active = nullptr;
   dvs::LmStatus* d_status = nullptr;
@@ -1031,7 +1239,7 @@ namespace {
 // forget the current problem (the arenas and pinned blocks stay)
 void ba_reset(dvs_ba* h) {
   if (h->d_raw) (void)hipFree(h->d_raw);
-  h->d_q0 = h->d_t0 = h->d_X0 = h->d_scale = h->d_diag = h->d_step = h->d_Vinv = h->d_Ws = h->d_Y = h->d_S = h->d_rhs = h->d_lmPart = h->d_normPart = nullptr;
+  h->d_q0 = h->d_t0 = h->d_X0 = h->d_scale = h->d_diag = h->d_step = h->d_Vinv = h->d_Ws = h->d_Y = h->d_S = h->d_rhs = h->d_lmPart = h->d_normPart = h->d_A = nullptr;
   h->d_obsOf = h->d_slotCam = nullptr; h->d_active = nullptr; h->d_status = nullptr;
   h->lm_ready = false;
   h->d_q = h->d_t = h->d_X = h->d_uv = nullptr; h->d_cam = h->d_lm = h->d_camChunkStart = h->d_lmStart = h->d_lmObs = nullptr;
@@ -1113,7 +1321,7 @@ void quat_plus(const double* x, const double* d, double* o) {
   o[2] = dw * x[2] + dz * x[3] + dx * x[1] - dy * x[0];
 }
 
-bool chol_solve(std::vector<double>& A, int n, std::vector<double>& b) {
+bool chol_solve(std::vector<double>& A, int n, std::vector<double>& b, std::vector<double>* y = nullptr) {   // y: b after the forward substitution
   for (int j = 0; j < n; j++) {
     double d = A[(size_t)j * n + j];
     for (int k = 0; k < j; k++) d -= A[(size_t)j * n + k] * A[(size_t)j * n + k];
@@ -1127,6 +1335,7 @@ bool chol_solve(std::vector<double>& A, int n, std::vector<double>& b) {
     }
   }
   for (int i = 0; i < n; i++) { double s = b[i]; for (int k = 0; k < i; k++) s -= A[(size_t)i * n + k] * b[k]; b[i] = s / A[(size_t)i * n + i]; }
+  if (y) *y = b;
   for (int i = n - 1; i >= 0; i--) { double s = b[i]; for (int k = i + 1; k < n; k++) s -= A[(size_t)k * n + i] * b[k]; b[i] = s / A[(size_t)i * n + i]; }
   return true;
 }
@@ -1140,6 +1349,24 @@ bool inv3(const double* A, double* B) {
   B[3] = (f * g - d * i) * id; B[4] = (a * i - c * g) * id; B[5] = (c * d - a * f) * id;
   B[6] = (d * hh - e * g) * id; B[7] = (b * g - a * hh) * id; B[8] = (a * e - b * d) * id;
   return true;
+}
+
+// the tiled solver's launches on the augmented system A (see k_lm_tile_panel): panel and trailing update per block column, then L^T x = y
+void enqueue_tiled_factor(hipStream_t st, int K, int n, const int* slotCam, double* A, double* step, LmStatus* status) {
+  for (int c0 = 0; c0 < n; c0 += kTileW) {
+    const int w = std::min(kTileW, n - c0), c1 = c0 + w;
+    hipLaunchKernelGGL(k_lm_tile_panel, dim3(1), dim3(kCholThreads), (size_t)(n + 1 - c0) * w * 8, st, n, c0, w, A, status);
+    if (c1 < n) {
+      const int tiles = (n + 1 - c1 + 15) / 16;
+      hipLaunchKernelGGL(k_lm_tile_update, dim3(tiles, tiles), dim3(256), 0, st, n, c0, w, A, status);
+    }
+  }
+  hipLaunchKernelGGL(k_lm_tile_backsolve, dim3(1), dim3(kCholThreads), (size_t)std::min(kTileW, n) * n * 8, st, K, n, slotCam, A, step, status);
+}
+dvs_status tiled_kernels_prepare() {
+  DVS_HIP(hipFuncSetAttribute((const void*)k_lm_tile_panel, hipFuncAttributeMaxDynamicSharedMemorySize, kTilePanelLds));
+  DVS_HIP(hipFuncSetAttribute((const void*)k_lm_tile_backsolve, hipFuncAttributeMaxDynamicSharedMemorySize, kTileBackLds));
+  return DVS_OK;
 }
 
 }  // namespace
@@ -1178,6 +1405,13 @@ dvs_status dvs_ba_set_stream(dvs_ba* h, void* s) {
   h->stream = (hipStream_t)s;
   return DVS_OK;
 }
+dvs_status dvs_ba_set_device_window(dvs_ba* h, int32_t max_free_cameras) {
+  DVS_ARG(h && max_free_cameras >= 1 && max_free_cameras <= 63);
+  h->device_window = max_free_cameras;
+  h->lm_ready = false;   // the next dvs_ba_solve_device plans its arena again
+  return DVS_OK;
+}
+int32_t dvs_ba_get_device_window(const dvs_ba* h) { return h ? h->device_window : 0; }
 dvs_status dvs_ba_synchronize(dvs_ba* h) {
   DVS_ARG(h);
   DVS_HIP(hipSetDevice(h->device));
@@ -1569,8 +1803,8 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
     for (int c = 0; c < K; c++) if (!h->pose_fixed[c] && camUsed[c]) { slotCam.push_back(c); for (int a = 0; a < 6; a++) active[6 * c + a] = 1; }
     for (int l = 0; l < L; l++) if (!h->lm_fixed[l] && lmUsed[l]) for (int a = 0; a < 3; a++) active[6 * K + 3 * l + a] = 1;
     const int nc = (int)slotCam.size();
-    if (K > 64 || nc > 16 || nc == 0) {
-      set_error("dvs_ba_solve_device handles sliding windows (<= 64 cameras, 1..16 of them free); this problem has %d / %d", K, nc);
+    if (K > 64 || nc > h->device_window || nc == 0) {
+      set_error("dvs_ba_solve_device handles sliding windows (<= 64 cameras, 1..%d of them free); this problem has %d / %d", h->device_window, K, nc);
       return DVS_ERR_UNSUPPORTED;
     }
     std::vector<int> obsOf((size_t)L * K, -1);
@@ -1583,13 +1817,15 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
       }
     hipStream_t st = h->stream;
     {
+      const size_t n = 6 * (size_t)nc;
       ArenaPlan pl;
       const size_t Rz = std::max(R, 1), Kz = std::max(K, 1), Lz = std::max(L, 1);
       const size_t o_obsOf = pl.take(obsOf.size() * 4 + 4), o_slot = pl.take(64 * 4), o_active = pl.take((size_t)NT + 1);
       const size_t uploadBytes = pl.used;
       const size_t o_q0 = pl.take(Kz * 32), o_t0 = pl.take(Kz * 24), o_X0 = pl.take(Lz * 24), o_scale = pl.take((size_t)NT * 8), o_diag = pl.take((size_t)NT * 8),
                    o_step = pl.take((size_t)NT * 8), o_Vinv = pl.take(Lz * 72), o_Ws = pl.take(Rz * 144), o_Y = pl.take(Rz * 144),
-                   o_S = pl.take((size_t)(1 + kSchurSplit) * 96 * 96 * 8), o_rhs = pl.take((size_t)(1 + kSchurSplit) * 96 * 8), o_lmPart = pl.take(Lz * 16),
+                   o_S = pl.take((size_t)(1 + kSchurSplit) * n * n * 8), o_rhs = pl.take((size_t)(1 + kSchurSplit) * n * 8),
+                   o_A = pl.take(nc > 16 ? (size_t)(n + 1) * n * 8 : 0), o_lmPart = pl.take(Lz * 16),
                    o_normPart = pl.take((size_t)((K + L + 255) / 256 + 1) * 16), o_status = pl.take(sizeof(LmStatus));
       DVS_TRY(arena_fit(h->lm_arena, pl.used));
       if (uploadBytes > h->h_stage_cap) {
@@ -1603,11 +1839,12 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
       h->d_obsOf = (int*)(B + o_obsOf); h->d_slotCam = (int*)(B + o_slot); h->d_active = B + o_active;
       h->d_q0 = (double*)(B + o_q0); h->d_t0 = (double*)(B + o_t0); h->d_X0 = (double*)(B + o_X0); h->d_scale = (double*)(B + o_scale);
       h->d_diag = (double*)(B + o_diag); h->d_step = (double*)(B + o_step); h->d_Vinv = (double*)(B + o_Vinv); h->d_Ws = (double*)(B + o_Ws); h->d_Y = (double*)(B + o_Y);
-      h->d_S = (double*)(B + o_S); h->d_rhs = (double*)(B + o_rhs); h->d_lmPart = (double*)(B + o_lmPart); h->d_normPart = (double*)(B + o_normPart);
+      h->d_S = (double*)(B + o_S); h->d_rhs = (double*)(B + o_rhs); h->d_A = (double*)(B + o_A); h->d_lmPart = (double*)(B + o_lmPart); h->d_normPart = (double*)(B + o_normPart);
       h->d_status = (LmStatus*)(B + o_status);
       if (!h->h_status) {
         DVS_HIP(hipHostMalloc((void**)&h->h_status, 2 * sizeof(LmStatus)));   // [0]: the trial's record (k_lm_norms), [1]: the point's (k_lm_gmax)
         DVS_HIP(hipFuncSetAttribute((const void*)k_lm_chol, hipFuncAttributeMaxDynamicSharedMemorySize, 97 * 96 * 8));
+        DVS_TRY(tiled_kernels_prepare());
       }
       const size_t outBytes = ((size_t)7 * Kz + 3 * Lz) * 8;
       if (outBytes > h->h_out_cap) {
@@ -1696,7 +1933,12 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
     reuse_diagonal = true;
     hipLaunchKernelGGL(k_lm_schur, dim3(nc, nc, kSchurSplit), dim3(256), 0, st, K, L, n, h->d_slotCam, h->d_obsOf, h->d_active, h->d_Hpp, h->d_g, h->d_scale,
                        h->d_diag, radius, h->d_Ws, h->d_Y, h->d_S, h->d_rhs);
-    hipLaunchKernelGGL(k_lm_chol, dim3(1), dim3(kCholThreads), (size_t)(n + 1) * n * 8, st, K, n, h->d_slotCam, h->d_S, h->d_rhs, h->d_step, h->d_status);
+    if (nc <= 16) {
+      hipLaunchKernelGGL(k_lm_chol, dim3(1), dim3(kCholThreads), (size_t)(n + 1) * n * 8, st, K, n, h->d_slotCam, h->d_S, h->d_rhs, h->d_step, h->d_status);
+    } else {
+      hipLaunchKernelGGL(k_lm_tile_assemble, dim3(n + 1), dim3(256), 0, st, K, n, h->d_S, h->d_rhs, h->d_A, h->d_step);
+      enqueue_tiled_factor(st, K, n, h->d_slotCam, h->d_A, h->d_step, h->d_status);
+    }
     hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, h->d_Hll, h->d_g, h->d_lmStart, h->d_lmObs, h->d_cam,
                        h->d_scale, h->d_active, h->d_Vinv, h->d_Ws, h->d_step, h->d_lmPart, h->d_status);
     hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, h->d_q0, h->d_t0, h->d_X0, h->d_step, h->d_scale, h->d_active,
@@ -1753,6 +1995,49 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
   memcpy(h->X.data(), ho + 7 * (size_t)K, (size_t)L * 24);
   return DVS_OK;
 }
+
+#ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h)
+// one linear solve S x = rhs (S n x n row-major, its lower triangle is read; n a multiple of 6, 6..378) through the tiled solver's
+// launches and through chol_solve: the forward-substituted y and the solution of each, and whether every pivot was positive
+dvs_status dvs_ba_factor_probe(int32_t device, int32_t n, const double* S, const double* rhs, double* y_dev, double* x_dev, double* y_host,
+                               double* x_host, int32_t* ok_dev, int32_t* ok_host) {
+  DVS_ARG(S && rhs && y_dev && x_dev && y_host && x_host && ok_dev && ok_host && n >= 6 && n <= kTileMaxN && n % 6 == 0);
+  DVS_TRY(check_device(device));
+  std::vector<double> Ah((size_t)n * n), bh(rhs, rhs + n), yh(n, 0.0);
+  for (int i = 0; i < n; i++) for (int k = 0; k < n; k++) Ah[(size_t)i * n + k] = k <= i ? S[(size_t)i * n + k] : 0.0;
+  std::vector<double> aug(Ah);
+  aug.insert(aug.end(), rhs, rhs + n);
+  *ok_host = chol_solve(Ah, n, bh, &yh) ? 1 : 0;
+  memcpy(y_host, yh.data(), (size_t)n * 8); memcpy(x_host, bh.data(), (size_t)n * 8);
+  const int K = n / 6;
+  std::vector<int> slot(K);
+  for (int c = 0; c < K; c++) slot[c] = c;
+  const size_t bytesA = (size_t)(n + 1) * n * 8;
+  uint8_t* d = nullptr;
+  DVS_HIP(hipMalloc((void**)&d, bytesA + (size_t)n * 8 + 256 + sizeof(LmStatus)));
+  double* dA = (double*)d; double* dStep = (double*)(d + bytesA); int* dSlot = (int*)(d + bytesA + (size_t)n * 8);
+  LmStatus* dSt = (LmStatus*)(d + bytesA + (size_t)n * 8 + 256);
+  LmStatus stat{};
+  dvs_status rc = DVS_OK;
+  auto run = [&]() -> dvs_status {
+    DVS_TRY(tiled_kernels_prepare());
+    DVS_HIP(hipMemcpy(dA, aug.data(), bytesA, hipMemcpyHostToDevice));
+    DVS_HIP(hipMemset(dStep, 0, (size_t)n * 8));
+    DVS_HIP(hipMemcpy(dSlot, slot.data(), (size_t)K * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, nullptr, dSt);
+    enqueue_tiled_factor(nullptr, K, n, dSlot, dA, dStep, dSt);
+    DVS_HIP(hipGetLastError());
+    DVS_HIP(hipMemcpy(y_dev, dA + (size_t)n * n, (size_t)n * 8, hipMemcpyDeviceToHost));
+    DVS_HIP(hipMemcpy(x_dev, dStep, (size_t)n * 8, hipMemcpyDeviceToHost));
+    DVS_HIP(hipMemcpy(&stat, dSt, sizeof(stat), hipMemcpyDeviceToHost));
+    return DVS_OK;
+  };
+  rc = run();
+  (void)hipFree(d);
+  *ok_dev = stat.ok;
+  return rc;
+}
+#endif  // DVS_TEST_HOOKS
 
 // CameraPose::fromRt / toRt (bundle_adjustment.hpp:138-165, 192-212) with Eigen 3.4's Quaterniond(Matrix3d),
 // normalize() and toRotationMatrix() arithmetic.  R is row-major 3x3, poses in the caller's convention (the backend

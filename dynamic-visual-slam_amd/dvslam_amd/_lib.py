@@ -151,6 +151,8 @@ def _bind(L):
         L.dvs_ba_evaluate_device.argtypes = [vp, i32]
         L.dvs_ba_solve.argtypes = [vp, i32, dbl, dbl, dbl, C.POINTER(BaSummary)]
         L.dvs_ba_solve_device.argtypes = [vp, i32, dbl, dbl, dbl, C.POINTER(BaSummary)]
+        L.dvs_ba_set_device_window.argtypes = [vp, i32]
+        L.dvs_ba_get_device_window.argtypes = [vp]; L.dvs_ba_get_device_window.restype = i32
         L.dvs_ba_get_parameters.argtypes = [vp, vp, vp, vp]
         L.dvs_ba_get_trace.argtypes = [vp, vp, i32, C.POINTER(i32)]
         L.dvs_ba_pose_from_rt.argtypes = [vp, vp, vp, vp]
@@ -224,6 +226,7 @@ def test_lib():
     L.dvs_test_geometry.argtypes = [C.POINTER(OrbParams), i32, i32, vp, vp, vp, vp, vp, vp]
     L.dvs_test_retain_best_host.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]; L.dvs_test_retain_best_host.restype = None
     L.dvs_test_retain_best_device.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]
+    L.dvs_ba_factor_probe.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
     _test_lib = L
     return L
 

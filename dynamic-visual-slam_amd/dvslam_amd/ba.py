@@ -25,6 +25,15 @@ class BAProblem:
         check(self._L.dvs_ba_set_problem(self._h, self.K, ptr(q), ptr(t), self.L, ptr(X), self.R, ptr(cam), ptr(lm), ptr(uv), ptr(pf),
                                          ptr(lf), prob["fx"], prob["fy"], prob["cx"], prob["cy"], prob["sigma"], prob["huber"]))
 
+    def set_device_window(self, max_free_cameras):
+        """dvs_ba_set_device_window: the most free cameras solve_device takes on this handle, 1..63 (default 16; above 16 the
+        tiled solver factors the reduced camera system).  Returns self."""
+        check(self._L.dvs_ba_set_device_window(self._h, int(max_free_cameras)))
+        return self
+
+    def device_window(self):
+        return int(self._L.dvs_ba_get_device_window(self._h))
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.dvs_ba_destroy(self._h)
@@ -96,10 +105,16 @@ class SlidingWindowBA:
       keyframes   : list of (frame_id, R 3x3, t 3) in the caller's convention (fromRt inverts it, :138-165)
       landmarks   : list of (id, category, (x, y, z), fixed)
       observations: list of ((u, v), landmark_id, category, frame_id)
-    returns a dict with the OptimizationResult fields (:419-432)."""
+    returns a dict with the OptimizationResult fields (:419-432).
 
-    def __init__(self, fx, fy, cx, cy, sigma_pixels=1.0, device=0):
+    device_window (not in the reference): the most free keyframes the device solver takes, 1..63; the default 16 leaves larger
+    windows to the host-Schur solver as before."""
+
+    def __init__(self, fx, fy, cx, cy, sigma_pixels=1.0, device=0, device_window=16):
+        if not 1 <= int(device_window) <= 63:
+            raise ValueError(f"device_window must be in 1..63, got {device_window}")
         self.fx, self.fy, self.cx, self.cy, self.sigma, self.device = fx, fy, cx, cy, sigma_pixels, device
+        self.device_window = int(device_window)
 
     def optimize(self, keyframes, landmarks, observations, max_iterations=10):
         L_ = lib()
@@ -130,6 +145,8 @@ class SlidingWindowBA:
                     lm_idx=np.array(lm, np.int32), uv=np.array(uv, np.float64), pose_fixed=pose_fixed, lm_fixed=np.array(fixed, np.uint8),
                     fx=self.fx, fy=self.fy, cx=self.cx, cy=self.cy, sigma=self.sigma, huber=1.345)
         p = BAProblem(prob, self.device)
+        if self.device_window != 16:
+            p.set_device_window(self.device_window)
         try:                                                                        # options at :839-847
             s = p.solve_device(max_iterations, 1e-6, 1e-10, 1e-8)
         except DvsError as e:                                                       # shapes outside the device solver's window limits

@@ -74,8 +74,10 @@ class BaEngine {
   BaEngine& operator=(const BaEngine&) = delete;
   bool warned_host_solver = false;   // the fall-back to host linear algebra announces itself once per object
   int last_linear_solver = 0;        // dvs_ba_summary::linear_solver of the last optimize(): 1 = device, 2 = host, 0 = none ran
+  int device_window = 16;            // dvs_ba_set_device_window: the most free keyframes the device solver takes (applied to the handle)
   dvs_ba* get() {
     if (!h_ && dvs_ba_create(device_, &h_) != DVS_OK) h_ = nullptr;
+    if (h_ && dvs_ba_get_device_window(h_) != device_window && dvs_ba_set_device_window(h_, device_window) != DVS_OK) return nullptr;
     return h_;
   }
 
@@ -153,7 +155,7 @@ typename Traits::Result optimize_impl(BaEngine& eng, const Intrinsics& K_, const
     dvs_status st = dvs_ba_solve_device(h, max_iterations, 1e-6, 1e-10, 1e-8, &s);
     if (st == DVS_ERR_UNSUPPORTED) {
       // NOT silent: the device solver takes windows of up to 16 free keyframes (the reference's live window is 5-10,
-      // backend.cpp:895); a larger one still optimises — GPU evaluation, normal equations on the host, ~40x slower per solve — and says so
+      // backend.cpp:895) unless setDeviceWindow raised the limit (up to 63); a larger one still optimises — GPU evaluation, normal equations on the host, ~40x slower per solve — and says so
       // once per object on stderr, in last_linear_solver() and in dvs_ba_summary::linear_solver
       if (!eng.warned_host_solver) {
         std::fprintf(stderr, "dvslam::SlidingWindowBA: %s — solving the normal equations on the host for this window\n", dvs_last_error());
@@ -209,8 +211,13 @@ class SlidingWindowBA {
                               const std::vector<Observation>& observations, int max_iterations = 10) {
     return detail::optimize_impl<detail::PlainTraits>(eng_, k_, keyframes, landmarks, observations, max_iterations);
   }
-  // (not in the reference) who solved the normal equations of the last optimize(): 1 = the device, 2 = the host (> 16 free keyframes), 0 = nobody
+  // (not in the reference) who solved the normal equations of the last optimize(): 1 = the device, 2 = the host (more free keyframes
+  // than the device window: 16 unless setDeviceWindow changed it), 0 = nobody
   int last_linear_solver() const { return eng_.last_linear_solver; }
+  // (not in the reference) the most free keyframes optimize() solves on the device, 1..63 (dvs_ba_set_device_window).  Default 16:
+  // larger windows go to the host solver as before.  Above 16 the tiled device solver takes them.  Out of range: the call is refused
+  // by the library at the next optimize(), which then reports "Bundle adjustment exception".
+  void setDeviceWindow(int max_free_keyframes) { eng_.device_window = max_free_keyframes; }
 
  private:
   detail::Intrinsics k_;

@@ -554,9 +554,17 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double function_toler
  * reduced camera system, back-substitution, model cost change, candidate point): one 64-byte status record crosses PCIe per
  * trial step instead of the W blocks.  Same trust-region decisions, fixed-order reductions; sums are associated differently
  * from dvs_ba_solve, so costs agree to rounding (tests: 1e-9 relative), not bit for bit.  Sliding-window shapes only:
- * <= 64 cameras, 1..16 of them free, a landmark observed at most once per camera; DVS_ERR_UNSUPPORTED otherwise. */
+ * <= 64 cameras, 1..16 of them free (more, up to 63, once dvs_ba_set_device_window allows it on this handle), a landmark observed
+ * at most once per camera; DVS_ERR_UNSUPPORTED otherwise. */
 dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double function_tolerance, double gradient_tolerance,
                                double parameter_tolerance, dvs_ba_summary* summary);
+/* largest number of free cameras dvs_ba_solve_device accepts on this handle: 1..63.  Default 16 (the in-LDS solver).
+ * Above 16 the reduced camera system (up to 378 x 378) is factored by the tiled solver: block columns in global memory, one launch
+ * per step on the handle's stream; dvs_ba_summary::linear_solver is 1 for both.  Windows of 1..16 free cameras run the in-LDS solver
+ * whatever the setting.  K <= 64 and "a landmark at most once per camera" are unchanged; beyond the limit dvs_ba_solve_device returns
+ * DVS_ERR_UNSUPPORTED as before.  Outside 1..63: DVS_ERR_ARG.  May be called before or after dvs_ba_set_problem; no GPU work. */
+dvs_status dvs_ba_set_device_window(dvs_ba* h, int32_t max_free_cameras);
+int32_t dvs_ba_get_device_window(const dvs_ba* h);
 /* Trust-region log of the last dvs_ba_solve / dvs_ba_solve_device (what ceres::Solver::Summary::iterations holds): one row of
  * 6 doubles per iteration = {radius the step was computed with, kind, cost change, model cost change, relative decrease,
  * candidate cost}; kind 0 = invalid step, 1 = accepted, 2 = rejected, 3 / 4 = parameter / function tolerance reached.

@@ -32,6 +32,13 @@ dvs_status dvs_test_retain_best_device(const float* responses, int32_t n, int32_
 dvs_status dvs_test_geometry(const dvs_orb_params* params, int32_t rows, int32_t cols, int32_t* level_w, int32_t* level_h,
                              int32_t* ncells, int32_t* quota, int32_t* wcell, int32_t* hcell);
 
+/* (needs a GPU) one linear solve S x = rhs of the bundle adjustment's reduced camera system through the tiled solver's launches
+ * (dvs_ba_set_device_window) and through the host routine dvs_ba_solve uses: S n x n row-major (the lower triangle is read), n a
+ * multiple of 6 in 6..378.  y_*: the right-hand side after the forward substitution, x_*: the solution, ok_*: every pivot positive
+ * (y_dev / x_dev are meaningful only then). */
+dvs_status dvs_ba_factor_probe(int32_t device, int32_t n, const double* S, const double* rhs, double* y_dev, double* x_dev, double* y_host,
+                               double* x_host, int32_t* ok_dev, int32_t* ok_host);
+
 /* ======================================= scheduling hooks of the extractor ====================== */
 /* What csrc/pipeline.hip composes the streaming step from.  Until round 4 these were part of the product ABI; a maintainer calls
  * dvs_pipeline_* (or the plain extract / match entry points), so the product library keeps them internal (hidden visibility) and only

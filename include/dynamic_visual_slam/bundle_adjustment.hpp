@@ -75,8 +75,11 @@ class SlidingWindowBA {  // (:652-904)
                               const std::vector<Observation>& observations, int max_iterations = 10) {
     return dvslam::detail::optimize_impl<CvTraits>(eng_, k_, keyframes, landmarks, observations, max_iterations);
   }
-  // (not in the reference) who solved the normal equations of the last optimize(): 1 = the device, 2 = the host (> 16 free keyframes), 0 = nobody
+  // (not in the reference) who solved the normal equations of the last optimize(): 1 = the device, 2 = the host (more free keyframes
+  // than the device window: 16 unless setDeviceWindow changed it), 0 = nobody
   int last_linear_solver() const { return eng_.last_linear_solver; }
+  // (not in the reference) the most free keyframes optimize() solves on the device, 1..63; default 16 (see dvslam::SlidingWindowBA)
+  void setDeviceWindow(int max_free_keyframes) { eng_.device_window = max_free_keyframes; }
 
  private:
   struct CvTraits {

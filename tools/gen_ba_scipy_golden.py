@@ -2,7 +2,7 @@
 """Independent statement of the sliding-window BA optimum (the LM loop of dvs_ba_solve* was only ever
 checked against its own transcription in oracle/ba_oracle.cpp).
 
-Solves the synthetic windows 3x60, 5x200 and 10x2000 (dvslam_amd.synth.make_ba_problem, the generator bench.py and the tests
+Solves the synthetic windows 3x60, 5x200, 10x2000 and 24x300 (dvslam_amd.synth.make_ba_problem, the generator bench.py and the tests
 use) with scipy.optimize.least_squares(method="trf") to convergence and stores the optimum under
 tests/golden/ba_scipy_*.npz.  Nothing here shares code with csrc/ba.hip or oracle/ba_oracle.cpp:
 
@@ -35,7 +35,9 @@ HUBER = 1.345
 # 3x60 without the 2 % outlier observations: with only three views per landmark and a linear-growth loss, a landmark that carries an
 # outlier has several local minima (fit the outlier or fit the other two views), and the two solvers settle in different ones
 # (measured: 804.2 vs 1539.1 — the LM loop found the LOWER one); with >= 5 views the outliers cannot win and the basins coincide.
-CASES = [("3x60", dict(K=3, L=60, seed=9, outlier_frac=0.0)), ("5x200", dict(K=5, L=200, seed=7)), ("10x2000", dict(K=10, L=2000, seed=42))]
+CASES = [("3x60", dict(K=3, L=60, seed=9, outlier_frac=0.0)), ("5x200", dict(K=5, L=200, seed=7)), ("10x2000", dict(K=10, L=2000, seed=42)),
+         # a window beyond 16 free keyframes with partial co-visibility (dvs_ba_set_device_window; tests/test_gpu_ba_window.py)
+         ("24x300", dict(K=24, L=300, seed=24, visibility=0.6))]
 
 
 def rot_from_quat(q):
