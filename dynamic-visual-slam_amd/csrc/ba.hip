@@ -14,6 +14,8 @@
 //                fold the chunk partials per camera and the total cost in chunk order.
 // Every reduction has a fixed order, so cost / gradient are bit-reproducible run to run.
 // dvs_ba_solve: host LM around the two launches (reduced camera system <= 6K x 6K); dvs_ba_solve_device: the k_lm_* kernels.
+// Host side: the handle owns two device arenas and three pinned blocks (device_mem.h) and reaches them through ProbView / LmView, each
+// laid out by one carve(); both solvers follow one TrustRegion.
 #include <float.h>
 #include <math.h>
 #include <string.h>
@@ -22,6 +24,7 @@
 #include <chrono>
 #include <vector>
 #include "common.h"
+#include "device_mem.h"
 
 namespace dvs {
 
@@ -1187,6 +1190,64 @@ __global__ void k_lm_reset(LmStatus* st) { st->ok = 1; st->finite = 1; st->model
 
 using namespace dvs;
 
+namespace {
+
+// Lays the buffers of an arena out: run over a null base for the size, then over the arena for the pointers.  256-byte aligned, never
+// a zero-byte block.
+struct Carver {
+  uint8_t* base;
+  size_t used = 0;
+  template <class T> void take(T*& p, size_t count) {
+    p = base ? (T*)(base + used) : nullptr;
+    used += (std::max<size_t>(count * sizeof(T), 1) + 255) & ~(size_t)255;
+  }
+};
+
+// A problem's device memory (dvs_ba_set_problem): [tables uploaded from the host | buffers that start at zero | evaluation outputs]
+struct ProbView {
+  double *q, *t, *X, *uv;
+  int *cam, *lm, *camChunkStart, *lmStart, *lmObs;
+  unsigned char *pf, *lf;
+  BaChunk* chunks;
+  double *Hpp, *Hll, *g, *cost, *costCam;
+  int* ticket;   // k_ba_reduce: arrival counter of its camera workgroups (the last one sums the cost)
+  double *res, *Jp, *Jl, *W, *partial;
+  size_t uploadBytes, zeroBytes, bytes;
+  void carve(uint8_t* base, int K, int L, int R, int nChunks) {
+    const size_t Rz = std::max(R, 1), Kz = std::max(K, 1), Lz = std::max(L, 1), Cz = std::max(nChunks, 1);
+    Carver c{base};
+    c.take(q, Kz * 4); c.take(t, Kz * 3); c.take(X, Lz * 3); c.take(uv, Rz * 2); c.take(cam, Rz); c.take(lm, Rz);
+    c.take(camChunkStart, (size_t)K + 1); c.take(lmStart, (size_t)L + 1); c.take(lmObs, Rz); c.take(pf, Kz); c.take(lf, Lz); c.take(chunks, Cz);
+    uploadBytes = c.used;
+    c.take(Hpp, Kz * 36); c.take(Hll, Lz * 9); c.take(g, (size_t)(6 * K + 3 * L + 1)); c.take(cost, 1); c.take(costCam, Kz); c.take(ticket, 1);
+    zeroBytes = c.used - uploadBytes;
+    c.take(res, Rz * 2); c.take(Jp, Rz * 12); c.take(Jl, Rz * 6); c.take(W, Rz * 18); c.take(partial, Cz * 28);
+    bytes = c.used;
+  }
+};
+
+// The workspace of dvs_ba_solve_device: [tables uploaded from the host | accepted point, scaling, LM diagonal, step, per-landmark
+// inverses, scaled W, Y = W V^-1, reduced system, the tiled solver's augmented system (n + 1) x n, partial sums, status record]
+struct LmView {
+  int *obsOf, *slotCam;   // observation of (landmark, camera); camera of a slot of the reduced system
+  unsigned char* active;
+  double *q0, *t0, *X0, *scale, *diag, *step, *Vinv, *Ws, *Y, *S, *rhs, *A, *lmPart, *normPart;
+  LmStatus* status;
+  size_t uploadBytes, bytes;
+  void carve(uint8_t* base, int K, int L, int R, int nc) {
+    const size_t Rz = std::max(R, 1), Kz = std::max(K, 1), Lz = std::max(L, 1), NT = 6 * (size_t)K + 3 * (size_t)L, n = 6 * (size_t)nc;
+    Carver c{base};
+    c.take(obsOf, (size_t)L * K + 1); c.take(slotCam, 64); c.take(active, NT + 1);
+    uploadBytes = c.used;
+    c.take(q0, Kz * 4); c.take(t0, Kz * 3); c.take(X0, Lz * 3); c.take(scale, NT); c.take(diag, NT); c.take(step, NT); c.take(Vinv, Lz * 9);
+    c.take(Ws, Rz * 18); c.take(Y, Rz * 18); c.take(S, (1 + kSchurSplit) * n * n); c.take(rhs, (1 + kSchurSplit) * n);
+    c.take(A, nc > 16 ? (n + 1) * n : 0); c.take(lmPart, Lz * 2); c.take(normPart, (size_t)((K + L + 255) / 256 + 1) * 2); c.take(status, 1);
+    bytes = c.used;
+  }
+};
+
+}  // namespace
+
 struct dvs_ba {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
@@ -1197,36 +1258,22 @@ struct dvs_ba {
   std::vector<int> lmStart, lmObs;
   std::vector<unsigned char> pose_fixed, lm_fixed;
   // Device memory of a problem is ONE grow-only arena (dvs_ba_set_problem) and of the LM workspace another (dvs_ba_solve_device); the
-  // host-side tables reach the first through ONE pinned staging block and ONE asynchronous copy on the handle's stream.  A new window
-  // of the same or a smaller shape (SlidingWindowBA::optimize, every 2 s in the reference) allocates nothing.
-  struct Arena { uint8_t* base = nullptr; size_t cap = 0; } prob_arena, lm_arena;
-  uint8_t* h_stage = nullptr; size_t h_stage_cap = 0;   // pinned
+  // host-side tables reach them through ONE pinned staging block and ONE asynchronous copy on the handle's stream.  A new window of
+  // the same or a smaller shape (SlidingWindowBA::optimize, every 2 s in the reference) allocates nothing.  The handle owns the blocks
+  // (device_mem.h); `prob` and `work` are views into the arenas, empty while there is no problem / no plan.
+  // All blocks are bytes; the views and the three accessors below give them their types.
+  DeviceBuf<uint8_t> prob_arena, work_arena, raw_buf;
+  PinnedBuf<uint8_t> stage, status_buf, out_buf;
+  size_t prob_cap = 0, work_cap = 0, stage_cap = 0, out_cap = 0;
+  double* raw() const { return (double*)raw_buf.get(); }              // dvs_ba_evaluate_raw: R * (2 + 8 + 6 + 6)
+  LmStatus* status() const { return (LmStatus*)status_buf.get(); }    // [0]: the trial's record (k_lm_norms), [1]: the point's (k_lm_gmax)
+  double* out() const { return (double*)out_buf.get(); }              // staging of the solved parameters (q, t, X)
+  ProbView prob{};
+  LmView work{};
   bool lm_poll = true, lm_speculate = true;   // DVS_LM_POLL=0 / DVS_LM_SPECULATE=0 (read once in dvs_ba_create): A/B switches of dvs_ba_solve_device
   bool lm_ready = false;   // dvs_ba_solve_device: structure tables built and uploaded
   int lm_nc = 0;           // ... free cameras
   int device_window = 16;  // dvs_ba_set_device_window: most free cameras dvs_ba_solve_device takes; above 16 the tiled solver factors the system
-  // device
-  double *d_q = nullptr, *d_t = nullptr, *d_X = nullptr, *d_uv = nullptr;
-  int *d_cam = nullptr, *d_lm = nullptr, *d_camChunkStart = nullptr, *d_lmStart = nullptr, *d_lmObs = nullptr;
-  unsigned char *d_pf = nullptr, *d_lf = nullptr;
-  BaChunk* d_chunks = nullptr;
-  double *d_res = nullptr, *d_Jp = nullptr, *d_Jl = nullptr, *d_W = nullptr, *d_partial = nullptr;
-  double *d_Hpp = nullptr, *d_Hll = nullptr, *d_g = nullptr, *d_cost = nullptr, *d_costCam = nullptr;
-  int* d_ticket = nullptr;   // k_ba_reduce: arrival counter of its camera workgroups (the last one sums the cost)
-  double *d_raw = nullptr;  // R*(2+8+6+6)
-  // device LM (dvs_ba_solve_device): accepted point, scaling, LM diagonal, step, per-landmark inverses, scaled W, Y = W V^-1,
-  // reduced system, observation-of-(landmark, camera) table
-  double *d_q0 = nullptr, *d_t0 = nullptr, *d_X0 = nullptr, *d_scale = nullptr, *d_diag = nullptr, *d_step = nullptr, *d_Vinv = nullptr,
-         *d_Ws = nullptr, *d_Y = nullptr, *d_S = nullptr, *d_rhs = nullptr, *d_lmPart = nullptr, *d_normPart = nullptr,
-         *d_A = nullptr;   // the tiled solver's augmented system (n + 1) x n
-  int *d_obsOf = nullptr, *d_slotCam = nullptr;
-  unsigned char* d_active = nullptr;
-  dvs::LmStatus* d_status = nullptr;
-  dvs::LmStatus* h_status = nullptr;  // pinned
-  double* h_out = nullptr;            // pinned staging of the solved parameters (q, t, X)
-  size_t h_out_cap = 0;
-  const int* eval_gate = nullptr;     // see BaDev::gate
-  bool eval_accept = false;           // see BaDev::acc_*
   std::vector<double> trace;          // dvs_ba_get_trace: 6 doubles per trust-region iteration of the last solve
   void log(double radius, int kind, double dc, double dm, double rel, double cand) {
     const double row[6] = {radius, (double)kind, dc, dm, rel, cand};
@@ -1238,76 +1285,107 @@ namespace {
 
 // forget the current problem (the arenas and pinned blocks stay)
 void ba_reset(dvs_ba* h) {
-  if (h->d_raw) (void)hipFree(h->d_raw);
-  h->d_q0 = h->d_t0 = h->d_X0 = h->d_scale = h->d_diag = h->d_step = h->d_Vinv = h->d_Ws = h->d_Y = h->d_S = h->d_rhs = h->d_lmPart = h->d_normPart = h->d_A = nullptr;
-  h->d_obsOf = h->d_slotCam = nullptr; h->d_active = nullptr; h->d_status = nullptr;
+  h->prob = {}; h->work = {}; h->raw_buf = {};
   h->lm_ready = false;
-  h->d_q = h->d_t = h->d_X = h->d_uv = nullptr; h->d_cam = h->d_lm = h->d_camChunkStart = h->d_lmStart = h->d_lmObs = nullptr;
-  h->d_pf = h->d_lf = nullptr; h->d_chunks = nullptr; h->d_res = h->d_Jp = h->d_Jl = h->d_W = h->d_partial = nullptr;
-  h->d_Hpp = h->d_Hll = h->d_g = h->d_cost = nullptr; h->d_raw = nullptr; h->d_costCam = nullptr; h->d_ticket = nullptr;
 }
 
-void ba_release(dvs_ba* h) {
-  ba_reset(h);
-  if (h->prob_arena.base) (void)hipFree(h->prob_arena.base);
-  if (h->lm_arena.base) (void)hipFree(h->lm_arena.base);
-  h->prob_arena = dvs_ba::Arena{}; h->lm_arena = dvs_ba::Arena{};
-  if (h->h_stage) (void)hipHostFree(h->h_stage);
-  if (h->h_status) (void)hipHostFree(h->h_status);
-  if (h->h_out) (void)hipHostFree(h->h_out);
-  h->h_stage = nullptr; h->h_stage_cap = 0; h->h_status = nullptr; h->h_out = nullptr; h->h_out_cap = 0;
+// copies a host table into the staging block S at the place its buffer `dev` has in the arena at B
+template <class T> void stage_table(uint8_t* S, const uint8_t* B, const T* dev, const std::vector<T>& v) {
+  if (!v.empty()) memcpy(S + ((const uint8_t*)dev - B), v.data(), v.size() * sizeof(T));
 }
 
-// layout of an arena: take() hands out 256-byte aligned offsets; bind() resolves them once the arena is large enough
-struct ArenaPlan {
-  size_t used = 0;
-  size_t take(size_t bytes) { const size_t o = used; used += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; }
-};
-dvs_status arena_fit(dvs_ba::Arena& A, size_t need) {
-  if (need <= A.cap) return DVS_OK;
-  if (A.base) DVS_HIP(hipFree(A.base));
-  A.base = nullptr; A.cap = 0;
-  const size_t cap = need + need / 4;
-  DVS_HIP(hipMalloc((void**)&A.base, cap));
-  A.cap = cap;
+// a camera-sorted device array of `width` doubles per observation, copied to the host in the caller's observation order
+dvs_status unpermute(const dvs_ba* h, double* dst, const double* dsrc, int width) {
+  if (!dst || h->R == 0) return DVS_OK;
+  std::vector<double> tmp((size_t)h->R * width);
+  DVS_HIP(hipMemcpy(tmp.data(), dsrc, tmp.size() * 8, hipMemcpyDeviceToHost));
+  for (int p = 0; p < h->R; p++) memcpy(dst + (size_t)h->perm[p] * width, &tmp[(size_t)p * width], (size_t)width * 8);
   return DVS_OK;
 }
 
-BaDev dev_view(const dvs_ba* h) {
+// gate, accept: see BaDev::gate, BaDev::acc_*
+BaDev dev_view(const dvs_ba* h, const int* gate, bool accept) {
+  const ProbView& dev = h->prob;
   BaDev P;
-  P.q = h->d_q; P.t = h->d_t; P.X = h->d_X; P.uv = h->d_uv; P.cam = h->d_cam; P.lm = h->d_lm;
-  P.pose_fixed = h->d_pf; P.lm_fixed = h->d_lf;
+  P.q = dev.q; P.t = dev.t; P.X = dev.X; P.uv = dev.uv; P.cam = dev.cam; P.lm = dev.lm;
+  P.pose_fixed = dev.pf; P.lm_fixed = dev.lf;
   P.fx = h->fx; P.fy = h->fy; P.cx = h->cx; P.cy = h->cy; P.inv_sigma = 1.0 / h->sigma; P.huber_a = h->huber;
-  P.gate = h->eval_gate;
+  P.gate = gate;
   P.acc_blocks = 0; P.acc_K = h->K; P.acc_L = h->L; P.acc_q0 = P.acc_t0 = P.acc_X0 = nullptr;
-  if (h->eval_accept) { P.acc_blocks = std::max(1, (3 * h->L + 1023) / 1024); P.acc_q0 = h->d_q0; P.acc_t0 = h->d_t0; P.acc_X0 = h->d_X0; }
+  if (accept) { P.acc_blocks = std::max(1, (3 * h->L + 1023) / 1024); P.acc_q0 = h->work.q0; P.acc_t0 = h->work.t0; P.acc_X0 = h->work.X0; }
   return P;
 }
 
 // flags as k_ba_eval; withLm: also reduce landmark blocks
-dvs_status enqueue_eval(dvs_ba* h, int flags, bool withLm) {
+dvs_status enqueue_eval(dvs_ba* h, int flags, bool withLm, const int* gate = nullptr, bool accept = false) {
   if (h->R == 0) return DVS_OK;
-  const BaDev P = dev_view(h);
-  double* raw = h->d_raw;
-  hipLaunchKernelGGL(k_ba_eval, dim3(h->nChunks + P.acc_blocks), dim3(256), 0, h->stream, P, h->d_chunks, flags, h->d_res, h->d_Jp, h->d_Jl, h->d_W,
-                     h->d_partial, raw, raw ? raw + 2 * (size_t)h->R : nullptr, raw ? raw + 10 * (size_t)h->R : nullptr,
+  const BaDev P = dev_view(h, gate, accept);
+  const ProbView& dev = h->prob;
+  double* raw = h->raw();
+  hipLaunchKernelGGL(k_ba_eval, dim3(h->nChunks + P.acc_blocks), dim3(256), 0, h->stream, P, dev.chunks, flags, dev.res, dev.Jp, dev.Jl, dev.W,
+                     dev.partial, raw, raw ? raw + 2 * (size_t)h->R : nullptr, raw ? raw + 10 * (size_t)h->R : nullptr,
                      raw ? raw + 16 * (size_t)h->R : nullptr);
   // the reductions need every chunk's records: a second launch.  (Chained into the evaluation launch by arrival tickets they were
   // bit-identical and SLOWER — 17.2 vs 13.2 us for one window, 6.3 vs 1.33 us per window in a 64-window batch: an agent-scope release
   // per workgroup writes back the XCD's L2; profiles/r03_ba_chained_reduction_experiment.json.)
-  hipLaunchKernelGGL(k_ba_reduce, dim3(h->lmBlocks + (h->K + 7) / 8), dim3(256), 0, h->stream, P, h->K, h->L, h->nChunks, h->d_chunks,
-                     h->d_camChunkStart, h->d_lmStart, h->d_lmObs, h->d_res, h->d_Jl, h->d_partial, h->lmBlocks, withLm ? 1 : 0,
-                     flags == 0 ? 1 : 0, h->d_Hpp, h->d_Hll, h->d_g, h->d_cost, h->d_costCam, h->d_ticket);
+  hipLaunchKernelGGL(k_ba_reduce, dim3(h->lmBlocks + (h->K + 7) / 8), dim3(256), 0, h->stream, P, h->K, h->L, h->nChunks, dev.chunks,
+                     dev.camChunkStart, dev.lmStart, dev.lmObs, dev.res, dev.Jl, dev.partial, h->lmBlocks, withLm ? 1 : 0,
+                     flags == 0 ? 1 : 0, dev.Hpp, dev.Hll, dev.g, dev.cost, dev.costCam, dev.ticket);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
 
 dvs_status upload_params(dvs_ba* h, const std::vector<double>& q, const std::vector<double>& t, const std::vector<double>& X) {
-  DVS_HIP(hipMemcpyAsync(h->d_q, q.data(), q.size() * 8, hipMemcpyHostToDevice, h->stream));
-  DVS_HIP(hipMemcpyAsync(h->d_t, t.data(), t.size() * 8, hipMemcpyHostToDevice, h->stream));
-  DVS_HIP(hipMemcpyAsync(h->d_X, X.data(), X.size() * 8, hipMemcpyHostToDevice, h->stream));
+  DVS_HIP(hipMemcpyAsync(h->prob.q, q.data(), q.size() * 8, hipMemcpyHostToDevice, h->stream));
+  DVS_HIP(hipMemcpyAsync(h->prob.t, t.data(), t.size() * 8, hipMemcpyHostToDevice, h->stream));
+  DVS_HIP(hipMemcpyAsync(h->prob.X, X.data(), X.size() * 8, hipMemcpyHostToDevice, h->stream));
   return DVS_OK;
 }
+
+// The blocks a solve moves: active[j] per tangent coordinate, and the free cameras in order (slotCam; camSlot is its inverse).  Fixed
+// for the life of a problem: the observation structure and the fixed flags are set by dvs_ba_set_problem.
+struct FreeBlocks { std::vector<unsigned char> active; std::vector<int> slotCam; };
+FreeBlocks free_blocks(const dvs_ba* h) {
+  const int K = h->K, L = h->L;
+  std::vector<unsigned char> lmUsed(L, 0), camUsed(K, 0);
+  for (int p = 0; p < h->R; p++) { lmUsed[h->lm[p]] = 1; camUsed[h->cam[p]] = 1; }
+  FreeBlocks f;
+  f.active.assign(6 * K + 3 * L, 0);
+  for (int c = 0; c < K; c++) if (!h->pose_fixed[c] && camUsed[c]) { f.slotCam.push_back(c); for (int a = 0; a < 6; a++) f.active[6 * c + a] = 1; }
+  for (int l = 0; l < L; l++) if (!h->lm_fixed[l] && lmUsed[l]) for (int a = 0; a < 3; a++) f.active[6 * K + 3 * l + a] = 1;
+  return f;
+}
+
+// The trust-region policy both solvers follow, ceres::Solver defaults (trust_region_minimizer.cc / levenberg_marquardt_strategy.cc,
+// Ceres 2.x): initial radius 1e4; a step is accepted when its relative decrease exceeds 1e-3; radius /= max(1/3, 1 - (2 rho - 1)^3)
+// on success, /= 2, 4, 8 .. on failure; the LM diagonal is kept across a rejected step and rebuilt after any other.
+struct TrustRegion {
+  static constexpr double kMinRelativeDecrease = 1e-3;
+  double radius = 1e4, decrease_factor = 2.0;
+  bool reuse_diagonal = false;
+  int iteration = 0, invalid = 0;
+  // loop head: counts the iteration, or ends the solve (false) with summary->termination set
+  bool next(int max_iterations, double gmax, double gtol, dvs_ba_summary* summary) {
+    if (iteration >= max_iterations) { summary->termination = 1; return false; }
+    if (gmax <= gtol || radius < 1e-32) { summary->termination = 0; return false; }
+    iteration++;
+    return true;
+  }
+  bool invalid_step() {   // true: the fifth in a row, the solve has failed
+    if (++invalid >= 5) return true;
+    shrink(false);
+    return false;
+  }
+  void accepted(double rel) {
+    invalid = 0;
+    radius = radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
+    radius = std::min(1e16, radius);
+    decrease_factor = 2.0; reuse_diagonal = false;
+  }
+  void rejected() { invalid = 0; shrink(true); }
+ private:
+  void shrink(bool reuse) { radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = reuse; }
+};
 
 // ceres::EigenQuaternionManifold::Plus on the raw (w,x,y,z) memory read as Eigen (x,y,z,w)
 void quat_plus(const double* x, const double* d, double* o) {
@@ -1393,7 +1471,6 @@ void dvs_ba_destroy(dvs_ba* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  ba_release(h);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
 }
@@ -1468,39 +1545,19 @@ dvs_status dvs_ba_set_problem(dvs_ba* h, int32_t K, const double* q_wxyz, const 
     for (int p = 0; p < R; p++) h->lmObs[cur[h->lm[p]]++] = p;
   }
   h->lmBlocks = (L + 255) / 256;
-  // one arena: [tables uploaded from the host | buffers that start at zero | evaluation outputs]
-  ArenaPlan pl;
-  const size_t Rz = std::max(R, 1), Kz = std::max(K, 1), Lz = std::max(L, 1), Cz = std::max(h->nChunks, 1);
-  const size_t o_q = pl.take(Kz * 32), o_t = pl.take(Kz * 24), o_X = pl.take(Lz * 24), o_uv = pl.take(Rz * 16), o_cam = pl.take(Rz * 4), o_lm = pl.take(Rz * 4),
-               o_ccs = pl.take((size_t)(K + 1) * 4), o_lms = pl.take((size_t)(L + 1) * 4), o_lmo = pl.take(Rz * 4), o_pf = pl.take(Kz), o_lf = pl.take(Lz),
-               o_chunks = pl.take(Cz * sizeof(BaChunk));
-  const size_t uploadBytes = pl.used;
-  const size_t o_Hpp = pl.take(Kz * 36 * 8), o_Hll = pl.take(Lz * 9 * 8), o_g = pl.take((size_t)(6 * K + 3 * L + 1) * 8), o_cost = pl.take(8), o_costCam = pl.take(Kz * 8),
-               o_ticket = pl.take(4);
-  const size_t zeroBytes = pl.used - uploadBytes;
-  const size_t o_res = pl.take(Rz * 2 * 8), o_Jp = pl.take(Rz * 12 * 8), o_Jl = pl.take(Rz * 6 * 8), o_W = pl.take(Rz * 18 * 8), o_partial = pl.take(Cz * 28 * 8);
-  DVS_TRY(arena_fit(h->prob_arena, pl.used));
-  if (uploadBytes > h->h_stage_cap) {
-    if (h->h_stage) DVS_HIP(hipHostFree(h->h_stage));
-    h->h_stage = nullptr; h->h_stage_cap = 0;
-    DVS_HIP(hipHostMalloc((void**)&h->h_stage, uploadBytes + uploadBytes / 4));
-    h->h_stage_cap = uploadBytes + uploadBytes / 4;
-  }
-  uint8_t* B = h->prob_arena.base; uint8_t* S = h->h_stage;
-  auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(S + off, src, bytes); };
-  put(o_q, h->q.data(), h->q.size() * 8); put(o_t, h->t.data(), h->t.size() * 8); put(o_X, h->X.data(), h->X.size() * 8);
-  put(o_uv, uvp.data(), uvp.size() * 8); put(o_cam, h->cam.data(), h->cam.size() * 4); put(o_lm, h->lm.data(), h->lm.size() * 4);
-  put(o_ccs, camChunkStart.data(), camChunkStart.size() * 4); put(o_lms, h->lmStart.data(), h->lmStart.size() * 4); put(o_lmo, h->lmObs.data(), h->lmObs.size() * 4);
-  put(o_pf, h->pose_fixed.data(), h->pose_fixed.size()); put(o_lf, h->lm_fixed.data(), h->lm_fixed.size()); put(o_chunks, chunks.data(), chunks.size() * sizeof(BaChunk));
-  h->d_q = (double*)(B + o_q); h->d_t = (double*)(B + o_t); h->d_X = (double*)(B + o_X); h->d_uv = (double*)(B + o_uv);
-  h->d_cam = (int*)(B + o_cam); h->d_lm = (int*)(B + o_lm); h->d_camChunkStart = (int*)(B + o_ccs); h->d_lmStart = (int*)(B + o_lms); h->d_lmObs = (int*)(B + o_lmo);
-  h->d_pf = B + o_pf; h->d_lf = B + o_lf; h->d_chunks = (BaChunk*)(B + o_chunks);
-  h->d_Hpp = (double*)(B + o_Hpp); h->d_Hll = (double*)(B + o_Hll); h->d_g = (double*)(B + o_g); h->d_cost = (double*)(B + o_cost);
-  h->d_costCam = (double*)(B + o_costCam); h->d_ticket = (int*)(B + o_ticket);
-  h->d_res = (double*)(B + o_res); h->d_Jp = (double*)(B + o_Jp); h->d_Jl = (double*)(B + o_Jl); h->d_W = (double*)(B + o_W); h->d_partial = (double*)(B + o_partial);
+  ProbView& dev = h->prob;
+  dev.carve(nullptr, K, L, R, h->nChunks);
+  DVS_TRY(grow(h->prob_arena, h->prob_cap, dev.bytes));
+  DVS_TRY(grow(h->stage, h->stage_cap, dev.uploadBytes));
+  uint8_t* B = h->prob_arena.get(); uint8_t* S = h->stage.get();
+  dev.carve(B, K, L, R, h->nChunks);
+  stage_table(S, B, dev.q, h->q); stage_table(S, B, dev.t, h->t); stage_table(S, B, dev.X, h->X); stage_table(S, B, dev.uv, uvp);
+  stage_table(S, B, dev.cam, h->cam); stage_table(S, B, dev.lm, h->lm); stage_table(S, B, dev.camChunkStart, camChunkStart);
+  stage_table(S, B, dev.lmStart, h->lmStart); stage_table(S, B, dev.lmObs, h->lmObs); stage_table(S, B, dev.pf, h->pose_fixed);
+  stage_table(S, B, dev.lf, h->lm_fixed); stage_table(S, B, dev.chunks, chunks);
   // one copy, one fill, both on the handle's stream: whatever the caller enqueues next on it is ordered behind them
-  DVS_HIP(hipMemcpyAsync(B, S, uploadBytes, hipMemcpyHostToDevice, h->stream));
-  DVS_HIP(hipMemsetAsync(B + uploadBytes, 0, zeroBytes, h->stream));
+  DVS_HIP(hipMemcpyAsync(B, S, dev.uploadBytes, hipMemcpyHostToDevice, h->stream));
+  DVS_HIP(hipMemsetAsync(B + dev.uploadBytes, 0, dev.zeroBytes, h->stream));
   return DVS_OK;
 }
 
@@ -1509,20 +1566,14 @@ dvs_status dvs_ba_evaluate(dvs_ba* h, double* cost, double* residuals, double* J
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(enqueue_eval(h, 1, true));
   DVS_HIP(hipStreamSynchronize(h->stream));
-  const int R = h->R;
-  if (cost) { *cost = 0; if (R) DVS_HIP(hipMemcpy(cost, h->d_cost, 8, hipMemcpyDeviceToHost)); }
-  auto unpermute = [&](double* dst, const double* dsrc, int width) -> dvs_status {
-    std::vector<double> tmp((size_t)R * width);
-    if (R) DVS_HIP(hipMemcpy(tmp.data(), dsrc, tmp.size() * 8, hipMemcpyDeviceToHost));
-    for (int p = 0; p < R; p++) memcpy(dst + (size_t)h->perm[p] * width, &tmp[(size_t)p * width], (size_t)width * 8);
-    return DVS_OK;
-  };
-  if (residuals) DVS_TRY(unpermute(residuals, h->d_res, 2));
-  if (J_pose) DVS_TRY(unpermute(J_pose, h->d_Jp, 12));
-  if (J_lm) DVS_TRY(unpermute(J_lm, h->d_Jl, 6));
+  const ProbView& dev = h->prob;
+  if (cost) { *cost = 0; if (h->R) DVS_HIP(hipMemcpy(cost, dev.cost, 8, hipMemcpyDeviceToHost)); }
+  DVS_TRY(unpermute(h, residuals, dev.res, 2));
+  DVS_TRY(unpermute(h, J_pose, dev.Jp, 12));
+  DVS_TRY(unpermute(h, J_lm, dev.Jl, 6));
   if (grad) {
     memset(grad, 0, (size_t)(6 * h->K + 3 * h->L) * 8);
-    if (R) DVS_HIP(hipMemcpy(grad, h->d_g, (size_t)(6 * h->K + 3 * h->L) * 8, hipMemcpyDeviceToHost));
+    if (h->R) DVS_HIP(hipMemcpy(grad, dev.g, (size_t)(6 * h->K + 3 * h->L) * 8, hipMemcpyDeviceToHost));
   }
   return DVS_OK;
 }
@@ -1530,20 +1581,16 @@ dvs_status dvs_ba_evaluate(dvs_ba* h, double* cost, double* residuals, double* J
 dvs_status dvs_ba_evaluate_raw(dvs_ba* h, double* residuals, double* J_q, double* J_t, double* J_X) {
   DVS_ARG(h);
   DVS_HIP(hipSetDevice(h->device));
-  const int R = h->R;
+  const size_t R = h->R;
   if (R == 0) return DVS_OK;
-  if (!h->d_raw) DVS_HIP(hipMalloc((void**)&h->d_raw, (size_t)R * 22 * 8));
+  if (!h->raw()) DVS_TRY(h->raw_buf.alloc(R * 22 * 8));
   DVS_TRY(enqueue_eval(h, 4, false));
   DVS_HIP(hipStreamSynchronize(h->stream));
-  std::vector<double> tmp((size_t)R * 22);
-  DVS_HIP(hipMemcpy(tmp.data(), h->d_raw, tmp.size() * 8, hipMemcpyDeviceToHost));
-  for (int p = 0; p < R; p++) {
-    const size_t i = h->perm[p];
-    if (residuals) memcpy(residuals + 2 * i, &tmp[2 * (size_t)p], 16);
-    if (J_q) memcpy(J_q + 8 * i, &tmp[2 * (size_t)R + 8 * (size_t)p], 64);
-    if (J_t) memcpy(J_t + 6 * i, &tmp[10 * (size_t)R + 6 * (size_t)p], 48);
-    if (J_X) memcpy(J_X + 6 * i, &tmp[16 * (size_t)R + 6 * (size_t)p], 48);
-  }
+  const double* raw = h->raw();
+  DVS_TRY(unpermute(h, residuals, raw, 2));
+  DVS_TRY(unpermute(h, J_q, raw + 2 * R, 8));
+  DVS_TRY(unpermute(h, J_t, raw + 10 * R, 6));
+  DVS_TRY(unpermute(h, J_X, raw + 16 * R, 6));
   return DVS_OK;
 }
 
@@ -1552,17 +1599,13 @@ dvs_status dvs_ba_normal_equations(dvs_ba* h, double* H_pp, double* H_ll, double
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(enqueue_eval(h, 1 | 2, true));
   DVS_HIP(hipStreamSynchronize(h->stream));
-  const int R = h->R, K = h->K, L = h->L;
-  if (H_pp) DVS_HIP(hipMemcpy(H_pp, h->d_Hpp, (size_t)K * 36 * 8, hipMemcpyDeviceToHost));
-  if (H_ll) DVS_HIP(hipMemcpy(H_ll, h->d_Hll, (size_t)L * 9 * 8, hipMemcpyDeviceToHost));
-  if (g) DVS_HIP(hipMemcpy(g, h->d_g, (size_t)(6 * K + 3 * L) * 8, hipMemcpyDeviceToHost));
-  if (cost) DVS_HIP(hipMemcpy(cost, h->d_cost, 8, hipMemcpyDeviceToHost));
-  if (W && R) {
-    std::vector<double> tmp((size_t)R * 18);
-    DVS_HIP(hipMemcpy(tmp.data(), h->d_W, tmp.size() * 8, hipMemcpyDeviceToHost));
-    for (int p = 0; p < R; p++) memcpy(W + 18 * (size_t)h->perm[p], &tmp[18 * (size_t)p], 144);
-  }
-  return DVS_OK;
+  const int K = h->K, L = h->L;
+  const ProbView& dev = h->prob;
+  if (H_pp) DVS_HIP(hipMemcpy(H_pp, dev.Hpp, (size_t)K * 36 * 8, hipMemcpyDeviceToHost));
+  if (H_ll) DVS_HIP(hipMemcpy(H_ll, dev.Hll, (size_t)L * 9 * 8, hipMemcpyDeviceToHost));
+  if (g) DVS_HIP(hipMemcpy(g, dev.g, (size_t)(6 * K + 3 * L) * 8, hipMemcpyDeviceToHost));
+  if (cost) DVS_HIP(hipMemcpy(cost, dev.cost, 8, hipMemcpyDeviceToHost));
+  return unpermute(h, W, dev.W, 18);
 }
 
 dvs_status dvs_ba_evaluate_device(dvs_ba* h, int32_t iters) {
@@ -1588,9 +1631,7 @@ dvs_status dvs_ba_get_parameters(dvs_ba* h, double* q_wxyz, double* t, double* X
   return DVS_OK;
 }
 
-// Levenberg-Marquardt with ceres::Solver defaults (trust_region_minimizer.cc / levenberg_marquardt_strategy.cc, Ceres 2.x):
-// initial radius 1e4, Jacobi column scaling fixed at the first Jacobian, LM diagonal clamped to [1e-6, 1e32], step
-// accepted when relative decrease > 1e-3, radius /= max(1/3, 1 - (2 rho - 1)^3) on success, /= 2,4,8.. on failure;
+// Levenberg-Marquardt under TrustRegion: Jacobi column scaling fixed at the first Jacobian, LM diagonal clamped to [1e-6, 1e32],
 // parameter / function tolerance tested on the candidate BEFORE acceptance; landmarks eliminated by a Schur complement.
 dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double gtol, double ptol, dvs_ba_summary* summary) {
   DVS_ARG(h && summary && max_iterations >= 0);
@@ -1600,15 +1641,16 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
   DVS_HIP(hipSetDevice(h->device));
   const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
   if (R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
+  const ProbView& dev = h->prob;
   std::vector<double> Hpp((size_t)K * 36), Hll((size_t)L * 9), W((size_t)R * 18), g(NT);
   double x_cost = 0;
   auto evaluate_full = [&]() -> dvs_status {
     DVS_TRY(enqueue_eval(h, 1 | 2, true));
-    DVS_HIP(hipMemcpyAsync(Hpp.data(), h->d_Hpp, Hpp.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    DVS_HIP(hipMemcpyAsync(Hll.data(), h->d_Hll, Hll.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    DVS_HIP(hipMemcpyAsync(W.data(), h->d_W, W.size() * 8, hipMemcpyDeviceToHost, h->stream));  // camera-sorted order
-    DVS_HIP(hipMemcpyAsync(g.data(), h->d_g, g.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    DVS_HIP(hipMemcpyAsync(&x_cost, h->d_cost, 8, hipMemcpyDeviceToHost, h->stream));
+    DVS_HIP(hipMemcpyAsync(Hpp.data(), dev.Hpp, Hpp.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    DVS_HIP(hipMemcpyAsync(Hll.data(), dev.Hll, Hll.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    DVS_HIP(hipMemcpyAsync(W.data(), dev.W, W.size() * 8, hipMemcpyDeviceToHost, h->stream));  // camera-sorted order
+    DVS_HIP(hipMemcpyAsync(g.data(), dev.g, g.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    DVS_HIP(hipMemcpyAsync(&x_cost, dev.cost, 8, hipMemcpyDeviceToHost, h->stream));
     DVS_HIP(hipStreamSynchronize(h->stream));
     return DVS_OK;
   };
@@ -1619,13 +1661,11 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
   summary->initial_cost = x_cost;
   double min_cost = x_cost;
 
-  std::vector<unsigned char> lmUsed(L, 0), camUsed(K, 0), active(NT, 0);
-  for (int p = 0; p < R; p++) { lmUsed[h->lm[p]] = 1; camUsed[h->cam[p]] = 1; }
+  const FreeBlocks fb = free_blocks(h);
+  const std::vector<unsigned char>& active = fb.active;
+  const int nc = (int)fb.slotCam.size(), n = 6 * nc;
   std::vector<int> camSlot(K, -1);
-  int nc = 0;
-  for (int c = 0; c < K; c++) if (!h->pose_fixed[c] && camUsed[c]) { camSlot[c] = nc++; for (int a = 0; a < 6; a++) active[6 * c + a] = 1; }
-  for (int l = 0; l < L; l++) if (!h->lm_fixed[l] && lmUsed[l]) for (int a = 0; a < 3; a++) active[6 * K + 3 * l + a] = 1;
-  const int n = 6 * nc;
+  for (int s = 0; s < nc; s++) camSlot[fb.slotCam[s]] = s;
   std::vector<double> scale(NT, 1.0), diagonal(NT, 0.0), step(NT, 0.0), Vinv((size_t)L * 9), Sm, rhs;
   for (int c = 0; c < K; c++) for (int a = 0; a < 6; a++) scale[6 * c + a] = 1.0 / (1.0 + sqrt(Hpp[36 * (size_t)c + 7 * a]));
   for (int l = 0; l < L; l++) for (int a = 0; a < 3; a++) scale[6 * K + 3 * l + a] = 1.0 / (1.0 + sqrt(Hll[9 * (size_t)l + 4 * a]));
@@ -1649,20 +1689,14 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
     return sqrt(s);
   };
 
-  double radius = 1e4, decrease_factor = 2.0, gmax = grad_max_norm();
-  bool reuse_diagonal = false;
-  int iteration = 0, invalid = 0;
-  summary->termination = 1;
-  while (true) {
-    if (iteration >= max_iterations) { summary->termination = 1; break; }
-    if (gmax <= gtol) { summary->termination = 0; break; }
-    if (radius < 1e-32) { summary->termination = 0; break; }
-    iteration++;
-    if (!reuse_diagonal) {
+  double gmax = grad_max_norm();
+  TrustRegion tr;
+  while (tr.next(max_iterations, gmax, gtol, summary)) {
+    const double radius = tr.radius;
+    if (!tr.reuse_diagonal) {
       for (int c = 0; c < K; c++) for (int a = 0; a < 6; a++) { const int j = 6 * c + a; diagonal[j] = std::min(std::max(Hpp[36 * (size_t)c + 7 * a] * scale[j] * scale[j], 1e-6), 1e32); }
       for (int l = 0; l < L; l++) for (int a = 0; a < 3; a++) { const int j = 6 * K + 3 * l + a; diagonal[j] = std::min(std::max(Hll[9 * (size_t)l + 4 * a] * scale[j] * scale[j], 1e-6), 1e32); }
     }
-    reuse_diagonal = true;
     // reduced camera system S = (H_pp + D) - sum_l Wl (H_ll + D)^-1 Wl^T, on the Jacobi-scaled blocks
     Sm.assign((size_t)n * n, 0.0); rhs.assign(n, 0.0);
     for (int c = 0; c < K; c++) if (camSlot[c] >= 0) {
@@ -1738,11 +1772,9 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
     }
     if (!valid) {
       h->log(radius, 0, 0, model_cost_change, 0, 0);
-      if (++invalid >= 5) { summary->termination = 2; break; }
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = false;
+      if (tr.invalid_step()) { summary->termination = 2; break; }
       continue;
     }
-    invalid = 0;
     std::vector<double> cq = q, ct = t, cX = X;
     for (int c = 0; c < K; c++) if (camSlot[c] >= 0) {
       const double d[3] = {step[6 * c] * scale[6 * c], step[6 * c + 1] * scale[6 * c + 1], step[6 * c + 2] * scale[6 * c + 2]};
@@ -1753,7 +1785,7 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
     DVS_TRY(upload_params(h, cq, ct, cX));
     DVS_TRY(enqueue_eval(h, 0, false));  // cost only
     double cand_cost = 0;
-    DVS_HIP(hipMemcpyAsync(&cand_cost, h->d_cost, 8, hipMemcpyDeviceToHost, h->stream));
+    DVS_HIP(hipMemcpyAsync(&cand_cost, dev.cost, 8, hipMemcpyDeviceToHost, h->stream));
     DVS_HIP(hipStreamSynchronize(h->stream));
     double sn = 0;
     for (int c = 0; c < K; c++) if (camSlot[c] >= 0) { for (int i = 0; i < 4; i++) sn += (q[4 * c + i] - cq[4 * c + i]) * (q[4 * c + i] - cq[4 * c + i]); for (int i = 0; i < 3; i++) sn += (t[3 * c + i] - ct[3 * c + i]) * (t[3 * c + i] - ct[3 * c + i]); }
@@ -1762,21 +1794,20 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
     const double cost_change = x_cost - cand_cost;
     if (fabs(cost_change) <= ftol * x_cost) { h->log(radius, 4, cost_change, model_cost_change, 0, cand_cost); summary->termination = 0; break; }
     const double rel = cost_change / model_cost_change;
-    h->log(radius, rel > 1e-3 ? 1 : 2, cost_change, model_cost_change, rel, cand_cost);
-    if (rel > 1e-3) {
+    const bool accept = rel > TrustRegion::kMinRelativeDecrease;
+    h->log(radius, accept ? 1 : 2, cost_change, model_cost_change, rel, cand_cost);
+    if (accept) {
       q = cq; t = ct; X = cX;
       DVS_TRY(evaluate_full());  // parameters on the device already are the candidate
       gmax = grad_max_norm();
       summary->num_successful_steps++;
       min_cost = std::min(min_cost, x_cost);
-      radius = radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
-      radius = std::min(1e16, radius);
-      decrease_factor = 2.0; reuse_diagonal = false;
+      tr.accepted(rel);
     } else {
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
+      tr.rejected();
     }
   }
-  summary->num_iterations = iteration;
+  summary->num_iterations = tr.iteration;
   summary->final_cost = min_cost;
   h->q = q; h->t = t; h->X = X;
   DVS_TRY(upload_params(h, q, t, X));
@@ -1794,15 +1825,13 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
   DVS_HIP(hipSetDevice(h->device));
   const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
   if (R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
-  // active blocks, camera slots, observation table: fixed for the life of the handle (the observation structure and the fixed flags
-  // are set at creation), built and uploaded by the first solve
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  LmView& w = h->work;
+  // active blocks, camera slots, observation table: fixed for the life of a problem, built and uploaded by its first solve
   if (!h->lm_ready) {
-    std::vector<unsigned char> lmUsed(L, 0), camUsed(K, 0), active(NT, 0);
-    for (int p = 0; p < R; p++) { lmUsed[h->lm[p]] = 1; camUsed[h->cam[p]] = 1; }
-    std::vector<int> slotCam;
-    for (int c = 0; c < K; c++) if (!h->pose_fixed[c] && camUsed[c]) { slotCam.push_back(c); for (int a = 0; a < 6; a++) active[6 * c + a] = 1; }
-    for (int l = 0; l < L; l++) if (!h->lm_fixed[l] && lmUsed[l]) for (int a = 0; a < 3; a++) active[6 * K + 3 * l + a] = 1;
-    const int nc = (int)slotCam.size();
+    const FreeBlocks fb = free_blocks(h);
+    const int nc = (int)fb.slotCam.size();
     if (K > 64 || nc > h->device_window || nc == 0) {
       set_error("dvs_ba_solve_device handles sliding windows (<= 64 cameras, 1..%d of them free); this problem has %d / %d", h->device_window, K, nc);
       return DVS_ERR_UNSUPPORTED;
@@ -1815,63 +1844,32 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
         if (slot >= 0) { set_error("landmark %d is observed twice in camera %d: use dvs_ba_solve", l, h->cam[p]); return DVS_ERR_UNSUPPORTED; }
         slot = p;
       }
-    hipStream_t st = h->stream;
-    {
-      const size_t n = 6 * (size_t)nc;
-      ArenaPlan pl;
-      const size_t Rz = std::max(R, 1), Kz = std::max(K, 1), Lz = std::max(L, 1);
-      const size_t o_obsOf = pl.take(obsOf.size() * 4 + 4), o_slot = pl.take(64 * 4), o_active = pl.take((size_t)NT + 1);
-      const size_t uploadBytes = pl.used;
-      const size_t o_q0 = pl.take(Kz * 32), o_t0 = pl.take(Kz * 24), o_X0 = pl.take(Lz * 24), o_scale = pl.take((size_t)NT * 8), o_diag = pl.take((size_t)NT * 8),
-                   o_step = pl.take((size_t)NT * 8), o_Vinv = pl.take(Lz * 72), o_Ws = pl.take(Rz * 144), o_Y = pl.take(Rz * 144),
-                   o_S = pl.take((size_t)(1 + kSchurSplit) * n * n * 8), o_rhs = pl.take((size_t)(1 + kSchurSplit) * n * 8),
-                   o_A = pl.take(nc > 16 ? (size_t)(n + 1) * n * 8 : 0), o_lmPart = pl.take(Lz * 16),
-                   o_normPart = pl.take((size_t)((K + L + 255) / 256 + 1) * 16), o_status = pl.take(sizeof(LmStatus));
-      DVS_TRY(arena_fit(h->lm_arena, pl.used));
-      if (uploadBytes > h->h_stage_cap) {
-        DVS_HIP(hipStreamSynchronize(st));   // an upload of dvs_ba_set_problem may still be reading the block
-        if (h->h_stage) DVS_HIP(hipHostFree(h->h_stage));
-        h->h_stage = nullptr; h->h_stage_cap = 0;
-        DVS_HIP(hipHostMalloc((void**)&h->h_stage, uploadBytes + uploadBytes / 4));
-        h->h_stage_cap = uploadBytes + uploadBytes / 4;
-      }
-      uint8_t* B = h->lm_arena.base;
-      h->d_obsOf = (int*)(B + o_obsOf); h->d_slotCam = (int*)(B + o_slot); h->d_active = B + o_active;
-      h->d_q0 = (double*)(B + o_q0); h->d_t0 = (double*)(B + o_t0); h->d_X0 = (double*)(B + o_X0); h->d_scale = (double*)(B + o_scale);
-      h->d_diag = (double*)(B + o_diag); h->d_step = (double*)(B + o_step); h->d_Vinv = (double*)(B + o_Vinv); h->d_Ws = (double*)(B + o_Ws); h->d_Y = (double*)(B + o_Y);
-      h->d_S = (double*)(B + o_S); h->d_rhs = (double*)(B + o_rhs); h->d_A = (double*)(B + o_A); h->d_lmPart = (double*)(B + o_lmPart); h->d_normPart = (double*)(B + o_normPart);
-      h->d_status = (LmStatus*)(B + o_status);
-      if (!h->h_status) {
-        DVS_HIP(hipHostMalloc((void**)&h->h_status, 2 * sizeof(LmStatus)));   // [0]: the trial's record (k_lm_norms), [1]: the point's (k_lm_gmax)
-        DVS_HIP(hipFuncSetAttribute((const void*)k_lm_chol, hipFuncAttributeMaxDynamicSharedMemorySize, 97 * 96 * 8));
-        DVS_TRY(tiled_kernels_prepare());
-      }
-      const size_t outBytes = ((size_t)7 * Kz + 3 * Lz) * 8;
-      if (outBytes > h->h_out_cap) {
-        if (h->h_out) DVS_HIP(hipHostFree(h->h_out));
-        h->h_out = nullptr; h->h_out_cap = 0;
-        DVS_HIP(hipHostMalloc((void**)&h->h_out, outBytes + outBytes / 4));
-        h->h_out_cap = outBytes + outBytes / 4;
-      }
-      DVS_HIP(hipStreamSynchronize(st));     // the staging block is free (dvs_ba_set_problem's upload has completed)
-      memcpy(h->h_stage + o_obsOf, obsOf.data(), obsOf.size() * 4);
-      memcpy(h->h_stage + o_slot, slotCam.data(), (size_t)nc * 4);
-      memcpy(h->h_stage + o_active, active.data(), (size_t)NT);
-      DVS_HIP(hipMemcpyAsync(B, h->h_stage, uploadBytes, hipMemcpyHostToDevice, st));
+    w.carve(nullptr, K, L, R, nc);
+    DVS_TRY(grow(h->work_arena, h->work_cap, w.bytes));
+    DVS_HIP(hipStreamSynchronize(st));     // the staging block is free (dvs_ba_set_problem's upload has completed)
+    DVS_TRY(grow(h->stage, h->stage_cap, w.uploadBytes));
+    if (!h->status()) {
+      DVS_TRY(h->status_buf.alloc(2 * sizeof(LmStatus)));
+      DVS_HIP(hipFuncSetAttribute((const void*)k_lm_chol, hipFuncAttributeMaxDynamicSharedMemorySize, 97 * 96 * 8));
+      DVS_TRY(tiled_kernels_prepare());
     }
+    DVS_TRY(grow(h->out_buf, h->out_cap, ((size_t)7 * std::max(K, 1) + 3 * (size_t)std::max(L, 1)) * 8));
+    uint8_t* B = h->work_arena.get();
+    w.carve(B, K, L, R, nc);
+    stage_table(h->stage.get(), B, w.obsOf, obsOf); stage_table(h->stage.get(), B, w.slotCam, fb.slotCam); stage_table(h->stage.get(), B, w.active, fb.active);
+    DVS_HIP(hipMemcpyAsync(B, h->stage.get(), w.uploadBytes, hipMemcpyHostToDevice, st));
     h->lm_nc = nc;
     h->lm_ready = true;
   }
   const int nc = h->lm_nc, n = 6 * nc;
   h->trace.clear();
-  hipStream_t st = h->stream;
   DVS_TRY(upload_params(h, h->q, h->t, h->X));
   const dim3 copyGrid((std::max(4 * K, 3 * L) + 255) / 256);   // one launch instead of three copy commands
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, h->d_q, h->d_t, h->d_X, h->d_q0, h->d_t0, h->d_X0, nullptr);
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
   // two host records: the gated k_lm_gmax of an accepted step runs while the host may still be reading the trial's numbers, so it
   // must not publish over them
-  LmStatus* S = h->h_status;
-  LmStatus* SP = h->h_status + 1;
+  LmStatus* S = h->status();
+  LmStatus* SP = S + 1;
   // the last kernel enqueued wrote the record into the pinned host copy (lm_publish): poll its sequence number — a bounded spin,
   // then the stream wait — instead of sleeping in hipStreamSynchronize (a wake-up per trial step and per accepted step)
   int expect_seq = 0;
@@ -1896,11 +1894,8 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
   // accept: the evaluation buffers hold a candidate that becomes the point of the next iteration (stored by extra workgroups of
   // the evaluation kernel)
   auto enqueue_full = [&](const int* gate, bool accept) -> dvs_status {
-    h->eval_gate = gate; h->eval_accept = accept;
-    const dvs_status e = enqueue_eval(h, 1 | 2, true);
-    h->eval_gate = nullptr; h->eval_accept = false;
-    DVS_TRY(e);
-    hipLaunchKernelGGL(k_lm_gmax, dim3(1), dim3(256), 0, st, K, L, h->d_q0, h->d_g, h->d_active, h->d_cost, h->d_status, SP, gate);
+    DVS_TRY(enqueue_eval(h, 1 | 2, true, gate, accept));
+    hipLaunchKernelGGL(k_lm_gmax, dim3(1), dim3(256), 0, st, K, L, w.q0, dev.g, w.active, dev.cost, w.status, SP, gate);
     return DVS_OK;
   };
   auto evaluate_full = [&](bool accept) -> dvs_status { DVS_TRY(enqueue_full(nullptr, accept)); return fetch_status(SP); };
@@ -1908,44 +1903,37 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
   // behind the trial, gated on the verdict k_lm_norms leaves in the status record, so that they are ready when the trial ends; the
   // host takes the same decision from the same numbers.  Should the two ever differ (a last-bit difference between the host's and the
   // device's sqrt / pow in a tolerance test), the DEVICE's verdict stands — it has already been applied to the buffers.
-  const int* verdict = &h->d_status->accept;
+  const int* verdict = &w.status->accept;
   const bool speculate = h->lm_speculate;
-  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, h->d_status);
+  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
   DVS_TRY(evaluate_full(false));
   double x_cost = SP->x_cost, gmax = SP->gmax;
   summary->initial_cost = x_cost;
   double min_cost = x_cost;
-  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, h->d_Hpp, h->d_Hll, h->d_scale);
+  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
 
-  double radius = 1e4, decrease_factor = 2.0;
-  bool reuse_diagonal = false;
-  int iteration = 0, invalid = 0;
   const int nparts = (K + L + 255) / 256;
-  summary->termination = 1;
-  while (true) {
-    if (iteration >= max_iterations) { summary->termination = 1; break; }
-    if (gmax <= gtol) { summary->termination = 0; break; }
-    if (radius < 1e-32) { summary->termination = 0; break; }
-    iteration++;
-    hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, h->d_Hpp, h->d_Hll, h->d_W, h->d_cam, h->d_lm,
-                       h->d_lmStart, h->d_lmObs, h->d_scale, h->d_diag, h->d_active, radius, reuse_diagonal ? 0 : 1, h->d_Vinv, h->d_Ws, h->d_Y,
-                       h->d_status);
-    reuse_diagonal = true;
-    hipLaunchKernelGGL(k_lm_schur, dim3(nc, nc, kSchurSplit), dim3(256), 0, st, K, L, n, h->d_slotCam, h->d_obsOf, h->d_active, h->d_Hpp, h->d_g, h->d_scale,
-                       h->d_diag, radius, h->d_Ws, h->d_Y, h->d_S, h->d_rhs);
+  TrustRegion tr;
+  while (tr.next(max_iterations, gmax, gtol, summary)) {
+    const double radius = tr.radius;
+    hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
+                       dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, tr.reuse_diagonal ? 0 : 1, w.Vinv, w.Ws, w.Y,
+                       w.status);
+    hipLaunchKernelGGL(k_lm_schur, dim3(nc, nc, kSchurSplit), dim3(256), 0, st, K, L, n, w.slotCam, w.obsOf, w.active, dev.Hpp, dev.g, w.scale,
+                       w.diag, radius, w.Ws, w.Y, w.S, w.rhs);
     if (nc <= 16) {
-      hipLaunchKernelGGL(k_lm_chol, dim3(1), dim3(kCholThreads), (size_t)(n + 1) * n * 8, st, K, n, h->d_slotCam, h->d_S, h->d_rhs, h->d_step, h->d_status);
+      hipLaunchKernelGGL(k_lm_chol, dim3(1), dim3(kCholThreads), (size_t)(n + 1) * n * 8, st, K, n, w.slotCam, w.S, w.rhs, w.step, w.status);
     } else {
-      hipLaunchKernelGGL(k_lm_tile_assemble, dim3(n + 1), dim3(256), 0, st, K, n, h->d_S, h->d_rhs, h->d_A, h->d_step);
-      enqueue_tiled_factor(st, K, n, h->d_slotCam, h->d_A, h->d_step, h->d_status);
+      hipLaunchKernelGGL(k_lm_tile_assemble, dim3(n + 1), dim3(256), 0, st, K, n, w.S, w.rhs, w.A, w.step);
+      enqueue_tiled_factor(st, K, n, w.slotCam, w.A, w.step, w.status);
     }
-    hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, h->d_Hll, h->d_g, h->d_lmStart, h->d_lmObs, h->d_cam,
-                       h->d_scale, h->d_active, h->d_Vinv, h->d_Ws, h->d_step, h->d_lmPart, h->d_status);
-    hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, h->d_q0, h->d_t0, h->d_X0, h->d_step, h->d_scale, h->d_active,
-                       h->d_q, h->d_t, h->d_X, h->d_normPart);
+    hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, dev.Hll, dev.g, dev.lmStart, dev.lmObs, dev.cam,
+                       w.scale, w.active, w.Vinv, w.Ws, w.step, w.lmPart, w.status);
+    hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, w.step, w.scale, w.active,
+                       dev.q, dev.t, dev.X, w.normPart);
     DVS_TRY(enqueue_eval(h, 0, false));  // cost of the candidate
-    hipLaunchKernelGGL(k_lm_norms, dim3(1), dim3(256), 0, st, nparts, h->d_normPart, h->d_cost, K, L, h->d_Hpp, h->d_g, h->d_scale, h->d_step,
-                       h->d_lmPart, ptol, ftol, h->d_status, S);
+    hipLaunchKernelGGL(k_lm_norms, dim3(1), dim3(256), 0, st, nparts, w.normPart, dev.cost, K, L, dev.Hpp, dev.g, w.scale, w.step,
+                       w.lmPart, ptol, ftol, w.status, S);
     if (speculate) DVS_TRY(enqueue_full(verdict, true));
     DVS_HIP(hipGetLastError());
     DVS_TRY(fetch_status(S));
@@ -1953,18 +1941,16 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
     const bool dev_accept = speculate && S->accept != 0;   // the gated launches ran: the candidate IS the point of the next iteration
     if (!valid && !dev_accept) {
       h->log(radius, 0, 0, S->model_change, 0, 0);
-      if (++invalid >= 5) { summary->termination = 2; break; }
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = false;
+      if (tr.invalid_step()) { summary->termination = 2; break; }
       continue;
     }
-    invalid = 0;
     const double cost_change = x_cost - S->cand_cost;
     if (!dev_accept) {
       if (sqrt(S->sn) <= ptol * (sqrt(S->xn) + ptol)) { h->log(radius, 3, cost_change, S->model_change, 0, S->cand_cost); summary->termination = 0; break; }
       if (fabs(cost_change) <= ftol * x_cost) { h->log(radius, 4, cost_change, S->model_change, 0, S->cand_cost); summary->termination = 0; break; }
     }
     const double rel = cost_change / S->model_change;
-    const bool accept = speculate ? dev_accept : rel > 1e-3;
+    const bool accept = speculate ? dev_accept : rel > TrustRegion::kMinRelativeDecrease;
     h->log(radius, accept ? 1 : 2, cost_change, S->model_change, rel, S->cand_cost);
     if (accept) {
       if (speculate) {
@@ -1975,21 +1961,19 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
       x_cost = SP->x_cost; gmax = SP->gmax;
       summary->num_successful_steps++;
       min_cost = std::min(min_cost, x_cost);
-      radius = radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
-      radius = std::min(1e16, radius);
-      decrease_factor = 2.0; reuse_diagonal = false;
+      tr.accepted(rel);
     } else {
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
+      tr.rejected();
     }
   }
-  summary->num_iterations = iteration;
+  summary->num_iterations = tr.iteration;
   summary->final_cost = min_cost;
   // the accepted point becomes the problem's parameters (host mirror and evaluation buffers)
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, h->d_q0, h->d_t0, h->d_X0, h->d_q, h->d_t, h->d_X, nullptr);
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, dev.q, dev.t, dev.X, nullptr);
   // ... the host mirror through the handle's pinned block, written by a kernel: the three device-to-host copy commands this replaces
   // now and then blocked for 7 ms when enqueued (first solve after a warm-up, pageable or pinned destination alike)
-  double* ho = h->h_out;
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, h->d_q0, h->d_t0, h->d_X0, ho, ho + 4 * (size_t)K, ho + 7 * (size_t)K, nullptr);
+  double* ho = h->out();
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, ho, ho + 4 * (size_t)K, ho + 7 * (size_t)K, nullptr);
   DVS_HIP(hipStreamSynchronize(st));
   memcpy(h->q.data(), ho, (size_t)K * 32); memcpy(h->t.data(), ho + 4 * (size_t)K, (size_t)K * 24);
   memcpy(h->X.data(), ho + 7 * (size_t)K, (size_t)L * 24);
@@ -2007,35 +1991,29 @@ dvs_status dvs_ba_factor_probe(int32_t device, int32_t n, const double* S, const
   for (int i = 0; i < n; i++) for (int k = 0; k < n; k++) Ah[(size_t)i * n + k] = k <= i ? S[(size_t)i * n + k] : 0.0;
   std::vector<double> aug(Ah);
   aug.insert(aug.end(), rhs, rhs + n);
-  *ok_host = chol_solve(Ah, n, bh, &yh) ? 1 : 0;
+  *ok_dev = 0; *ok_host = chol_solve(Ah, n, bh, &yh) ? 1 : 0;
   memcpy(y_host, yh.data(), (size_t)n * 8); memcpy(x_host, bh.data(), (size_t)n * 8);
   const int K = n / 6;
   std::vector<int> slot(K);
   for (int c = 0; c < K; c++) slot[c] = c;
-  const size_t bytesA = (size_t)(n + 1) * n * 8;
-  uint8_t* d = nullptr;
-  DVS_HIP(hipMalloc((void**)&d, bytesA + (size_t)n * 8 + 256 + sizeof(LmStatus)));
-  double* dA = (double*)d; double* dStep = (double*)(d + bytesA); int* dSlot = (int*)(d + bytesA + (size_t)n * 8);
-  LmStatus* dSt = (LmStatus*)(d + bytesA + (size_t)n * 8 + 256);
+  double *dA, *dStep; int* dSlot; LmStatus* dSt;
+  auto layout = [&](uint8_t* base) { Carver c{base}; c.take(dA, (size_t)(n + 1) * n); c.take(dStep, n); c.take(dSlot, K); c.take(dSt, 1); return c.used; };
+  DeviceBuf<uint8_t> mem;
+  DVS_TRY(mem.alloc(layout(nullptr)));
+  layout(mem.get());
   LmStatus stat{};
-  dvs_status rc = DVS_OK;
-  auto run = [&]() -> dvs_status {
-    DVS_TRY(tiled_kernels_prepare());
-    DVS_HIP(hipMemcpy(dA, aug.data(), bytesA, hipMemcpyHostToDevice));
-    DVS_HIP(hipMemset(dStep, 0, (size_t)n * 8));
-    DVS_HIP(hipMemcpy(dSlot, slot.data(), (size_t)K * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, nullptr, dSt);
-    enqueue_tiled_factor(nullptr, K, n, dSlot, dA, dStep, dSt);
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipMemcpy(y_dev, dA + (size_t)n * n, (size_t)n * 8, hipMemcpyDeviceToHost));
-    DVS_HIP(hipMemcpy(x_dev, dStep, (size_t)n * 8, hipMemcpyDeviceToHost));
-    DVS_HIP(hipMemcpy(&stat, dSt, sizeof(stat), hipMemcpyDeviceToHost));
-    return DVS_OK;
-  };
-  rc = run();
-  (void)hipFree(d);
+  DVS_TRY(tiled_kernels_prepare());
+  DVS_HIP(hipMemcpy(dA, aug.data(), aug.size() * 8, hipMemcpyHostToDevice));
+  DVS_HIP(hipMemset(dStep, 0, (size_t)n * 8));
+  DVS_HIP(hipMemcpy(dSlot, slot.data(), (size_t)K * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, nullptr, dSt);
+  enqueue_tiled_factor(nullptr, K, n, dSlot, dA, dStep, dSt);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipMemcpy(y_dev, dA + (size_t)n * n, (size_t)n * 8, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(x_dev, dStep, (size_t)n * 8, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(&stat, dSt, sizeof(stat), hipMemcpyDeviceToHost));
   *ok_dev = stat.ok;
-  return rc;
+  return DVS_OK;
 }
 #endif  // DVS_TEST_HOOKS
 

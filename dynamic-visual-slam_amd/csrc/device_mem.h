@@ -35,6 +35,17 @@ class Buf {
 template <class T> using DeviceBuf = Buf<T, false>;
 template <class T> using PinnedBuf = Buf<T, true>;
 
+// A block that only grows: kept while `need` elements fit in its `cap`, else freed first and allocated with a quarter to spare.  After
+// a failed allocation it is empty with cap 0, so the next call allocates again and the owner still frees once.
+template <class T, bool Pinned>
+dvs_status grow(Buf<T, Pinned>& buf, size_t& cap, size_t need) {
+  if (need <= cap) return DVS_OK;
+  cap = 0;
+  DVS_TRY(buf.alloc(need + need / 4));
+  cap = need + need / 4;
+  return DVS_OK;
+}
+
 // Move-only owner of an event without timing.  Empty until create(): a handle can be built (and destroyed) without a device.
 class Event {
  public:

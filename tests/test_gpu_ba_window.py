@@ -246,3 +246,50 @@ def test_handle_reuse_replans_the_arena(gpu):
     b = _wide(small); b.set_device_window(16)                                     # the setting does not touch windows of <= 16 free cameras
     s3 = b.solve_device(ITERS)
     assert s3.final_cost == s.final_cost
+
+
+def _same_bits(name, got, want):
+    got = got if isinstance(got, (tuple, list)) else (got,)
+    want = want if isinstance(want, (tuple, list)) else (want,)
+    assert len(got) == len(want), name
+    for i, (x, y) in enumerate(zip(got, want)):
+        assert np.shape(x) == np.shape(y) and (_bits(x) == _bits(y)).all(), f"{name}[{i}] differs from a fresh handle's"
+
+
+def _summary(s):
+    return [s.termination, s.num_successful_steps, s.num_iterations, s.linear_solver, s.initial_cost, s.final_cost]
+
+
+def test_one_handle_through_every_entry_point_equals_fresh_handles(gpu):
+    """ONE handle through windows of growing and shrinking shape (10x400, 40x300, 3x60, 10x400) with the device window raised and
+    lowered in between: evaluate, normal_equations, evaluate_raw, solve and solve_device each give, bit for bit, what a fresh handle
+    gives for that window — outputs, summaries, traces and parameters.  (What a stale pointer into a re-planned arena, or a wrong
+    boundary between the uploaded, the zero-filled and the output part of an arena, would break.)"""
+    from dvslam_amd import BAProblem
+    steps = [(dict(K=10, L=400, seed=21), 16), (dict(K=40, L=300, seed=22), 63), (dict(K=3, L=60, seed=23), 63), (dict(K=10, L=400, seed=21), 16)]
+    h = None
+    for kw, window in steps:
+        P = synth.make_ba_problem(**kw)
+        if h is None:
+            h = BAProblem(P)
+        else:
+            h.set_device_window(window)
+            h.set_problem(P)
+        assert h.device_window() == window
+        f = BAProblem(P).set_device_window(window)
+        for call in ("evaluate", "normal_equations", "evaluate_raw", "evaluate"):     # the second evaluate: after evaluate_raw's buffer exists
+            _same_bits(f"{kw} {call}", getattr(h, call)(), getattr(f, call)())
+        sh = h.solve(ITERS); sf = f.solve(ITERS)
+        _same_bits(f"{kw} solve", _summary(sh) + [h.trace(), *h.parameters()], _summary(sf) + [f.trace(), *f.parameters()])
+        assert len(h.trace()) == sh.num_iterations >= 1
+        _same_bits(f"{kw} evaluate after solve", h.evaluate(), f.evaluate())
+        h.set_problem(P)                                                              # the same shape again: back to the initial point
+        f = BAProblem(P).set_device_window(window)
+        sh = h.solve_device(ITERS); sf = f.solve_device(ITERS)
+        _same_bits(f"{kw} solve_device", _summary(sh) + [h.trace(), *h.parameters()], _summary(sf) + [f.trace(), *f.parameters()])
+        assert sh.linear_solver == 1 and len(h.trace()) == sh.num_iterations >= 1
+        _same_bits(f"{kw} evaluate after solve_device", h.evaluate(), f.evaluate())
+    h.set_device_window(63)                                                           # a new limit alone plans the workspace again
+    f = BAProblem(P).set_device_window(63); f.solve_device(ITERS)
+    _same_bits("solve_device after a window change", _summary(h.solve_device(ITERS)) + [h.trace(), *h.parameters()],
+               _summary(f.solve_device(ITERS)) + [f.trace(), *f.parameters()])
