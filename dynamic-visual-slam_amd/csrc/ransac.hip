@@ -28,6 +28,7 @@
 #endif
 #include "io_pinned.h"
 #include "matcher.h"
+#include "ransac_device.h"
 
 namespace dvs {
 
@@ -39,9 +40,7 @@ __host__ __device__ __forceinline__ unsigned long long splitmix64(unsigned long 
   return z ^ (z >> 31);
 }
 
-// One RANSAC problem of a batch (blockIdx.y of every kernel below): its correspondences are rows [off, off + n) of the point arrays,
-// its hypotheses / counts / results slot `b` of the per-problem arrays.  The single-problem entry points are batches of one.
-struct RansacProb { int off, n; unsigned long long seed; };
+// RansacProb (ransac_device.h): one problem of a batch, blockIdx.y of every kernel below.
 
 // k distinct indices out of n (k <= 8), uniform without replacement, in draw order
 template <int KS>
@@ -1017,6 +1016,44 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
   }
 }
 
+// ---- the launch sequences, on device-resident problems: what the host-pointer entry points run behind their import and what the
+// device forms of ransac_device.h run directly.  n_bound >= every problem's n sizes the per-correspondence grid.
+static void launch_fm_own(hipStream_t st, int nprob, int n_bound, const RansacProb* d_probs, const float* d_p1, const float* d_p2, int H, double threshold,
+                          double confidence, double* d_F, int* d_valid, int* d_counts, int* d_sel, unsigned char* d_mask, double* d_Fb) {
+  hipLaunchKernelGGL(k_f_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_p1, d_p2, d_probs, H, d_F, d_valid);
+  hipLaunchKernelGGL(k_f_score, dim3(H, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, d_F, d_valid, threshold * threshold, d_counts, 0);
+  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H, d_probs, 8, confidence, 1, d_sel);
+  hipLaunchKernelGGL(k_f_mask, dim3((std::max(n_bound, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, d_F, d_sel, threshold * threshold, d_mask, d_Fb, 0);
+}
+// OpenCV's procedure: d_samples = the host-drawn 7-point samples of H iterations per problem (the seed field of a problem = how many have
+// one); lmeds: the 8..14-point form.  d_F / d_valid / d_counts hold 3 H models per problem.
+static void launch_fm_cv(hipStream_t st, int nprob, int n_bound, const RansacProb* d_probs, const float* d_p1, const float* d_p2, const int32_t* d_samples, int H,
+                         bool lmeds, double threshold, double confidence, int max_iters, double* d_F, int* d_valid, int* d_counts, int* d_sel,
+                         unsigned char* d_mask, double* d_Fb) {
+  const int H3 = 3 * H;
+  hipLaunchKernelGGL(k_f7_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_p1, d_p2, d_probs, d_samples, H, d_F, d_valid);
+  if (lmeds) {
+    hipLaunchKernelGGL(k_lmeds_select, dim3(nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, H, d_F, d_valid, d_sel, d_mask, d_Fb);
+  } else {
+    hipLaunchKernelGGL(k_f_score, dim3(H3, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H3, d_F, d_valid, threshold * threshold, d_counts, 1);
+    hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H3, d_probs, 7, confidence, 3, d_sel, 1, max_iters);
+    hipLaunchKernelGGL(k_f_mask, dim3((std::max(n_bound, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H3, d_F, d_sel, threshold * threshold, d_mask, d_Fb, 1);
+  }
+}
+static void launch_pnp_own(hipStream_t st, int nprob, const RansacProb* d_probs, const float* d_obj, const float* d_img, int H, const double* K4, double reproj_err,
+                           double confidence, double* d_poses, int* d_valid, int* d_counts, int* d_sel, int* d_inl, unsigned char* d_out) {
+  const int H4 = 4 * H;
+  const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3], thr2 = reproj_err * reproj_err;
+  hipLaunchKernelGGL(k_p3p_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_obj, d_img, d_probs, H, fx, fy, cx, cy, d_poses, d_valid);
+  hipLaunchKernelGGL(k_pnp_score, dim3(H4, nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H4, d_poses, d_valid, fx, fy, cx, cy, thr2, d_counts);
+  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H4, d_probs, 3, confidence, 4, d_sel);
+  hipLaunchKernelGGL(k_pnp_refine, dim3(nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H4, d_poses, d_sel, fx, fy, cx, cy, thr2, d_inl, d_out);
+}
+// the problem record of a device-resident single problem: the count comes from the device
+__global__ void k_ransac_prob(RansacProb* __restrict__ prob, const int* __restrict__ d_n, unsigned long long seed) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *prob = RansacProb{0, *d_n, seed};
+}
+
 // one pass over `nprob` problems with the models of the first H iterations; unfinished[b] = 1 where the loop wanted more than H
 // (lmeds: the problems are below 15 points — H = the fixed iteration count, k_lmeds_select instead of score / select / mask,
 //  unfinished[b] = 1 where the call FAILED, i.e. fewer than 7 inliers: OpenCV returns an empty matrix then, the mask stays as written)
@@ -1055,14 +1092,7 @@ static dvs_status fm_cv_pass(dvs_matcher* ctx, int32_t nprob, const int32_t* off
   }
   const int ndw_in = (int)(inb / 4);
   hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
-  hipLaunchKernelGGL(k_f7_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_p1, d_p2, d_probs, d_samples, H, d_F, d_valid);
-  if (lmeds) {
-    hipLaunchKernelGGL(k_lmeds_select, dim3(nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, H, d_F, d_valid, d_sel, d_mask, d_Fb);
-  } else {
-    hipLaunchKernelGGL(k_f_score, dim3(H3, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H3, d_F, d_valid, threshold * threshold, d_counts, 1);
-    hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H3, d_probs, 7, confidence, 3, d_sel, 1, max_iters);
-    hipLaunchKernelGGL(k_f_mask, dim3((std::max(maxn, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H3, d_F, d_sel, threshold * threshold, d_mask, d_Fb, 1);
-  }
+  launch_fm_cv(st, nprob, maxn, d_probs, d_p1, d_p2, d_samples, H, lmeds, threshold, confidence, max_iters, d_F, d_valid, d_counts, d_sel, d_mask, d_Fb);
   uint8_t* hout = hio + inb;
   if (outb <= 65536) {
     const int seq = ++*counter;
@@ -1142,6 +1172,130 @@ static void cv_subsets_nocheck(int n, int modelPoints, int iters, int32_t* idx_o
     }
 }
 
+static void launch_pnp_cv(hipStream_t st, int nprob, const RansacProb* d_probs, const float* d_obj, const float* d_img, const int* d_samples, int H, const double* K4,
+                          double reproj_err, double confidence, double* d_models, int* d_counts, int* d_sel, int* d_inl, unsigned char* d_out) {
+  const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3];
+  const float thr = (float)(reproj_err * reproj_err);
+  hipLaunchKernelGGL(k_epnp_hypotheses, dim3((H + kEpnpGroups - 1) / kEpnpGroups, nprob), dim3(64), 0, st, d_obj, d_img, d_probs, d_samples, H, fx, fy, cx, cy, d_models);
+  hipLaunchKernelGGL(k_pnpcv_score, dim3(H, nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H, d_models, fx, fy, cx, cy, thr, d_counts);
+  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H, d_probs, 5, confidence, 1, d_sel, 1, H);
+  hipLaunchKernelGGL(k_pnpcv_refit, dim3(nprob), dim3(64), 0, st, d_obj, d_img, d_probs, H, d_models, d_sel, fx, fy, cx, cy, thr, d_inl, d_out);
+}
+
+// ---- the device forms (ransac_device.h): one problem whose points already live on the device; argument rules as the host entry points'
+namespace dvs {
+
+dvs_status fm_own_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, const int* d_n, int n_bound, unsigned long long seed, double threshold,
+                         double confidence, int max_iters, unsigned char* d_mask) {
+  DVS_ARG(ctx && d_p1 && d_p2 && d_n && d_mask && n_bound >= 0 && max_iters >= 1 && max_iters <= 4096 && threshold > 0);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int H = max_iters;
+  const size_t fb = (size_t)H * 72, vb = (size_t)H * 4;
+  uint8_t* base;
+  DVS_TRY(matcher_scratch(ctx, 0, 16 + fb + 2 * vb + 16 + 72 + 64, (void**)&base));
+  RansacProb* d_prob = (RansacProb*)base;
+  double* d_F = (double*)(base + 16);
+  int* d_valid = (int*)(base + 16 + fb); int* d_counts = (int*)(base + 16 + fb + vb);
+  int* d_sel = (int*)(base + 16 + fb + 2 * vb); double* d_Fb = (double*)(base + 16 + fb + 2 * vb + 16);
+  hipLaunchKernelGGL(k_ransac_prob, dim3(1), dim3(1), 0, st, d_prob, d_n, seed);
+  launch_fm_own(st, 1, n_bound, d_prob, d_p1, d_p2, H, threshold, confidence, d_F, d_valid, d_counts, d_sel, d_mask, d_Fb);
+  DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+
+dvs_status pnp_own_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, const int* d_n, unsigned long long seed, const double* K4,
+                          int iterations, double reproj_err, double confidence, int* d_inl, unsigned char* d_out64) {
+  DVS_ARG(ctx && d_obj && d_img && d_n && K4 && d_inl && d_out64 && iterations >= 1 && iterations <= 1024 && reproj_err > 0);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int H = iterations, H4 = 4 * H;
+  const size_t posb = (size_t)H4 * 96, vb = (size_t)H4 * 4;
+  uint8_t* base;
+  DVS_TRY(matcher_scratch(ctx, 0, 16 + posb + 2 * vb + 16 + 64, (void**)&base));
+  RansacProb* d_prob = (RansacProb*)base;
+  double* d_poses = (double*)(base + 16);
+  int* d_valid = (int*)(base + 16 + posb); int* d_counts = (int*)(base + 16 + posb + vb);
+  int* d_sel = (int*)(base + 16 + posb + 2 * vb);
+  hipLaunchKernelGGL(k_ransac_prob, dim3(1), dim3(1), 0, st, d_prob, d_n, seed);
+  launch_pnp_own(st, 1, d_prob, d_obj, d_img, H, K4, reproj_err, confidence, d_poses, d_valid, d_counts, d_sel, d_inl, d_out64);
+  DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+
+dvs_status fm_cv_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, int n, double threshold, double confidence, int max_iters,
+                        unsigned char* d_mask) {
+  DVS_ARG(ctx && d_p1 && d_p2 && d_mask && n >= 8 && max_iters >= 1 && max_iters <= 4096);
+  if (threshold <= 0) threshold = 3;                                                 // as cv::findFundamentalMat
+  if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const bool lmeds = n < 15;
+  const int Hfull = lmeds ? std::max(ransac_update_iters_host(confidence, 0.45, 7, max_iters), 3) : max_iters;
+  const size_t pb = ((size_t)n * 8 + 15) & ~(size_t)15, sbmax = ((size_t)Hfull * 7 * 4 + 15) & ~(size_t)15;
+  uint8_t* hio; int *hseq, *counter;
+  DVS_TRY(matcher_pinned(ctx, 2 * pb + 16 + sbmax + 128, (void**)&hio, &hseq, &counter));
+  float* hp1 = (float*)hio; float* hp2 = (float*)(hio + pb);
+  uint8_t* hin = hio + 2 * pb;                 // [problem record | samples] of a pass
+  int* hsel = (int*)(hio + 2 * pb + 16 + sbmax);
+  DVS_HIP(hipMemcpyAsync(hp1, d_p1, (size_t)n * 8, hipMemcpyDeviceToHost, st));   // what the sampler's collinearity test reads
+  DVS_HIP(hipMemcpyAsync(hp2, d_p2, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  DVS_HIP(hipStreamSynchronize(st));
+  int H = lmeds ? Hfull : std::min<int>(max_iters, 96);   // RANSAC: the models of 96 iterations first, all of them only if the loop asks (dvs_find_fundamental_cv_batch)
+  for (;;) {
+    const int H3 = 3 * H;
+    const size_t sb = ((size_t)H * 7 * 4 + 15) & ~(size_t)15, inb = 16 + sb;
+    const size_t fb = (size_t)H3 * 72, vb = (size_t)H3 * 4;
+    uint8_t* base;
+    DVS_TRY(matcher_scratch(ctx, 0, inb + fb + 2 * vb + 16 + 72 + 64, (void**)&base));
+    int32_t* hs = (int32_t*)(hin + 16);
+    memset(hs, 0, sb);
+    const int found = cv_subsets(hp1, hp2, n, 7, H, hs, lmeds ? 1000 : 10000);
+    *(RansacProb*)hin = RansacProb{0, n, (unsigned long long)found};
+    double* d_F = (double*)(base + inb);
+    int* d_valid = (int*)(base + inb + fb); int* d_counts = (int*)(base + inb + fb + vb);
+    int* d_sel = (int*)(base + inb + fb + 2 * vb); double* d_Fb = (double*)(base + inb + fb + 2 * vb + 16);
+    const int ndw_in = (int)(inb / 4);
+    hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hin, (uint32_t*)base, ndw_in);
+    launch_fm_cv(st, 1, n, (const RansacProb*)base, d_p1, d_p2, (const int32_t*)(base + 16), H, lmeds, threshold, confidence, max_iters, d_F, d_valid, d_counts,
+                 d_sel, d_mask, d_Fb);
+    const int seq = ++*counter;
+    hipLaunchKernelGGL(k_io_export, dim3(1), dim3(256), 0, st, (const uint32_t*)d_sel, (uint32_t*)hsel, 4, hseq, seq);
+    DVS_HIP(hipGetLastError());
+    DVS_TRY(io_wait(hseq, seq, st));
+    if (lmeds || !hsel[3] || H >= max_iters) break;
+    H = max_iters;
+  }
+  return DVS_OK;
+}
+
+dvs_status pnp_cv_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, int n, const double* K4, int iterations, double reproj_err,
+                         double confidence, int* d_inl, unsigned char* d_out64, int* d_sel4) {
+  DVS_ARG(ctx && d_obj && d_img && K4 && d_inl && d_out64 && d_sel4 && n >= 6 && iterations >= 1 && iterations <= 1024 && reproj_err > 0 && confidence > 0 &&
+          confidence < 1);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int H = iterations;
+  const size_t sb = ((size_t)H * 5 * 4 + 15) & ~(size_t)15, inb = 16 + sb;
+  const size_t mb = (size_t)H * 18 * 8, vb = (size_t)H * 4;
+  uint8_t* base;
+  DVS_TRY(matcher_scratch(ctx, 0, inb + mb + vb + 64, (void**)&base));
+  uint8_t* hio; int *hseq, *counter;
+  DVS_TRY(matcher_pinned(ctx, inb, (void**)&hio, &hseq, &counter));
+  int32_t* hs = (int32_t*)(hio + 16);
+  memset(hs, 0, sb);
+  cv_subsets_nocheck(n, 5, H, hs);
+  *(RansacProb*)hio = RansacProb{0, n, (unsigned long long)H};
+  const int ndw_in = (int)(inb / 4);
+  hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
+  launch_pnp_cv(st, 1, (const RansacProb*)base, d_obj, d_img, (const int*)(base + 16), H, K4, reproj_err, confidence, (double*)(base + inb),
+                (int*)(base + inb + mb), d_sel4, d_inl, d_out64);
+  DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+
+}  // namespace dvs
+
 extern "C" {
 
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h)
@@ -1194,10 +1348,7 @@ dvs_status dvs_find_fundamental_ransac_batch(dvs_matcher* ctx, int32_t nprob, co
   memcpy(hio + hb, pts1, (size_t)total * 8); memcpy(hio + hb + pb, pts2, (size_t)total * 8);
   const int ndw_in = (int)(inb / 4);
   hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
-  hipLaunchKernelGGL(k_f_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_p1, d_p2, d_probs, H, d_F, d_valid);
-  hipLaunchKernelGGL(k_f_score, dim3(H, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, d_F, d_valid, threshold * threshold, d_counts, 0);
-  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H, d_probs, 8, confidence, 1, d_sel);
-  hipLaunchKernelGGL(k_f_mask, dim3((std::max(maxn, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, d_F, d_sel, threshold * threshold, d_mask, d_Fb, 0);
+  launch_fm_own(st, nprob, maxn, d_probs, d_p1, d_p2, H, threshold, confidence, d_F, d_valid, d_counts, d_sel, d_mask, d_Fb);
   uint8_t* hout = hio + inb;
   if (outb <= 65536) {   // small results leave through the export kernel + a polled sequence number (no copy command, no wake-up)
     const int seq = ++*counter;
@@ -1330,12 +1481,7 @@ dvs_status dvs_solve_pnp_ransac_cv_batch(dvs_matcher* ctx, int32_t nprob, const 
   memcpy(hio + hb, pts3d, (size_t)total * 12); memcpy(hio + hb + ob, pts2d, (size_t)total * 8);
   const int ndw_in = (int)(inb / 4);
   hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
-  const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3];
-  const float thr = (float)(reproj_err * reproj_err);
-  hipLaunchKernelGGL(k_epnp_hypotheses, dim3((H + kEpnpGroups - 1) / kEpnpGroups, nprob), dim3(64), 0, st, d_obj, d_img, d_probs, d_samples, H, fx, fy, cx, cy, d_models);
-  hipLaunchKernelGGL(k_pnpcv_score, dim3(H, nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H, d_models, fx, fy, cx, cy, thr, d_counts);
-  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H, d_probs, 5, confidence, 1, d_sel, 1, H);
-  hipLaunchKernelGGL(k_pnpcv_refit, dim3(nprob), dim3(64), 0, st, d_obj, d_img, d_probs, H, d_models, d_sel, fx, fy, cx, cy, thr, d_inl, d_out);
+  launch_pnp_cv(st, nprob, d_probs, d_obj, d_img, d_samples, H, K4, reproj_err, confidence, d_models, d_counts, d_sel, d_inl, d_out);
   uint8_t* hout = hio + inb;
   if (outb <= 65536) {
     const int seq = ++*counter;
@@ -1414,11 +1560,7 @@ dvs_status dvs_solve_pnp_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int
   memcpy(hio + hb, pts3d, (size_t)total * 12); memcpy(hio + hb + ob, pts2d, (size_t)total * 8);
   const int ndw_in = (int)(inb / 4);
   hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
-  const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3], thr2 = reproj_err * reproj_err;
-  hipLaunchKernelGGL(k_p3p_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_obj, d_img, d_probs, H, fx, fy, cx, cy, d_poses, d_valid);
-  hipLaunchKernelGGL(k_pnp_score, dim3(H4, nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H4, d_poses, d_valid, fx, fy, cx, cy, thr2, d_counts);
-  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H4, d_probs, 3, confidence, 4, d_sel);
-  hipLaunchKernelGGL(k_pnp_refine, dim3(nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H4, d_poses, d_sel, fx, fy, cx, cy, thr2, d_inl, d_out);
+  launch_pnp_own(st, nprob, d_probs, d_obj, d_img, H, K4, reproj_err, confidence, d_poses, d_valid, d_counts, d_sel, d_inl, d_out);
   uint8_t* hout = hio + inb;
   if (outb <= 65536) {
     const int seq = ++*counter;

@@ -1,0 +1,31 @@
+// ransac_device.h — the RANSAC stages of ransac.hip on inputs that already live on the device (used by tracker.hip).  The host-pointer
+// entry points of include/dvslam_hip.h import their points and then run the SAME launch sequences; these forms skip the import and leave
+// their results on the device.  `ctx` gives the stream and scratch slot 0 (hypotheses, counts, selection: gone with the next call).
+#pragma once
+#include "matcher.h"
+
+namespace dvs {
+
+// One RANSAC problem of a batch (blockIdx.y of every kernel of ransac.hip): its correspondences are rows [off, off + n) of the point
+// arrays, its hypotheses / counts / results slot `b` of the per-problem arrays.  The single-problem entry points are batches of one.
+struct RansacProb { int off, n; unsigned long long seed; };
+
+// dvs_find_fundamental_ransac on d_p1 / d_p2 (n x 2 float) with the count read from *d_n on the device (n_bound >= *d_n sizes the
+// grids): d_mask[0 .. *d_n) = the inlier mask.  Fewer than 8 correspondences give a mask of zeros.  Asynchronous.
+dvs_status fm_own_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, const int* d_n, int n_bound, unsigned long long seed, double threshold,
+                         double confidence, int max_iters, unsigned char* d_mask);
+// dvs_solve_pnp_ransac on d_obj (n x 3) / d_img (n x 2), count *d_n: d_out64 = the stage's 64-byte result record {int32 n_inliers,
+// int32 success, 8 bytes unused, double rvec[3], double tvec[3]}, d_inl = ascending inlier indices.  Asynchronous.
+dvs_status pnp_own_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, const int* d_n, unsigned long long seed, const double* K4,
+                          int iterations, double reproj_err, double confidence, int* d_inl, unsigned char* d_out64);
+// dvs_find_fundamental_cv: OpenCV's sample sequence is drawn on the host from the count AND the points (collinear samples are drawn again),
+// so the n (>= 8) correspondences are read back first; samples go up, the 16-byte selection record comes back (the 96-iteration pass may
+// ask for the full one).  The mask stays on the device.  Synchronises.
+dvs_status fm_cv_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, int n, double threshold, double confidence, int max_iters,
+                        unsigned char* d_mask);
+// dvs_solve_pnp_ransac_cv: its 5-point samples depend on the count alone (host `n` >= 6); samples go up, nothing comes back.  d_out64 as
+// above (rvec / tvec are meaningful when d_sel4[0] >= 0), d_sel4 = {best model or -1, iterations run, its inlier count, 0}.  Asynchronous.
+dvs_status pnp_cv_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, int n, const double* K4, int iterations, double reproj_err,
+                         double confidence, int* d_inl, unsigned char* d_out64, int* d_sel4);
+
+}  // namespace dvs

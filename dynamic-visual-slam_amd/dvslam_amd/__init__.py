@@ -11,3 +11,4 @@ from .matcher import BFMatcher  # noqa: F401
 from .ba import BAProblem, SlidingWindowBA  # noqa: F401
 from .glue import FrontendGlue  # noqa: F401
 from .cvorb import CvORB  # noqa: F401
+from .tracker import Tracker, TrackerParams, TrackResult  # noqa: F401

@@ -605,6 +605,77 @@ dvs_status dvs_cvorb_detect_and_compute(dvs_cvorb* h, const uint8_t* gray, int32
 /* parity introspection: level `level` of the last call's pyramid (blurred = 1: after the Gaussian), tight rows */
 dvs_status dvs_cvorb_get_level(dvs_cvorb* h, int32_t level, int32_t blurred, uint8_t* dst, int32_t cap_bytes, int32_t* w, int32_t* hgt);
 
+/* ============================ the tracking front end: one call per RGB-D frame ================================
+ * Frontend::syncCallback (frontend.cpp:1068-1324) as ONE handle and ONE call per frame (csrc/tracker.hip; INTEGRATION.md "Tracking
+ * front end"): gray -> extract -> filterDepth -> match against the previous frame -> distance < 50 -> fundamental-matrix gate ->
+ * feature culling -> estimateCameraPose (3D points from the PREVIOUS depth image, PnP, inverse motion, isMotionOutlier, pose
+ * products) -> isKeyframe -> Keyframe.msg CDR -> state update.  The image is copied up; the two depth images (current and previous)
+ * are kept in pinned host memory and the kernels read the pixels under the keypoints from there; keypoints, descriptors, matches, point
+ * lists and masks stay in HBM between the stages (with fm_mode = 1 the correspondences of a gate are read back for OpenCV's sampler).  The
+ * handle owns one extractor, one matcher context (on the extractor's stream) and the members syncCallback keeps: R_, t_, prev_kps_,
+ * prev_descriptors_, prev_frame_depth_, the last keyframe's features, frames_since_last_keyframe_, keyframe_id_.  Not thread-safe.
+ * With the library's own estimators frame t (counted from create / reset) seeds the gate against the previous frame with
+ * seed_base + 2t, PnP with seed_base + 2t + 1, the keyframe gate with seed_base + 2t + 1000003. */
+typedef struct dvs_tracker dvs_tracker;
+typedef struct dvs_tracker_params {
+  int32_t rows, cols;                  /* every frame's size */
+  double fx, fy, cx, cy;               /* rgb_fx_ .. rgb_cy_ */
+  dvs_orb_params orb;                  /* frontend.cpp:206: 1000, 1.2, 8, 20, 7; max_batch is ignored */
+  float min_depth, max_depth;          /* 0.3 / 3.0 (filterDepth, estimateCameraPose, publishKeyframe) */
+  int32_t max_hamming;                 /* 50: matches with distance < this (frontend.cpp:1127, 618) */
+  double fm_threshold, fm_confidence;  /* 2.0 px / 0.99 (frontend.cpp:1147, 636) */
+  int32_t fm_max_iters;                /* 1000, OpenCV's default */
+  int32_t cull_max_new;                /* MAX_NEW_FEATURES 200 (frontend.cpp:1205) */
+  float cull_min_response;             /* MIN_RESPONSE 50.0 (frontend.cpp:1206) */
+  int32_t pnp_iterations;              /* 100 (frontend.cpp:919-921) */
+  double pnp_reproj_err, pnp_confidence; /* 4.0 / 0.99 */
+  int32_t kf_min_matches;              /* a keyframe when fewer than 150 consistent matches with the last one (frontend.cpp:651) */
+  int32_t kf_max_frames;               /* ... or frames_since_last_keyframe_ > 30 (frontend.cpp:655) */
+  double max_translation, max_rotation; /* isMotionOutlier: 0.5 m / 0.2 rad (frontend.cpp:550-551) */
+  int32_t fm_mode, pnp_mode;           /* 0: dvs_find_fundamental_ransac / dvs_solve_pnp_ransac with the seeds above; 1: the _cv forms */
+  uint64_t seed_base;
+  int32_t gray_variant;                /* dvs_bgr_to_gray's variant for 3-channel input */
+  int32_t reserved;
+} dvs_tracker_params;
+enum {                                 /* dvs_track_result::kf_criterion (bits) */
+  DVS_KF_FIRST_FRAME = 1,              /* frontend.cpp:1295 */
+  DVS_KF_NO_REFERENCE = 2,             /* the first isKeyframe call: has_last_keyframe_ was false (frontend.cpp:603-606) */
+  DVS_KF_FEW_MATCHES = 4,              /* tracking_criterion (frontend.cpp:651) */
+  DVS_KF_MAX_FRAMES = 8                /* frames_since_last_keyframe_ > 30 (frontend.cpp:655) */
+};
+typedef struct dvs_track_result {
+  int64_t frame_index;                 /* t, counted from create / reset */
+  int64_t keyframe_id;                 /* Keyframe.frame_id of this frame's message, -1 if it is no keyframe */
+  int32_t n_extracted, n_filtered;     /* extractor output, after filterDepth */
+  int32_t n_matches, n_geometric;      /* distance-filtered, after the fundamental-matrix gate (= n_matches when it is skipped) */
+  int32_t n_pnp_points, n_pnp_inliers; /* 3D-2D correspondences built, inliers of the PnP model */
+  int32_t n_backend;                   /* culled feature set (what a keyframe carries) */
+  int32_t n_kf_matches, n_kf_geometric; /* the same two counts against the last keyframe; -1 where isKeyframe did not get there */
+  int32_t first_frame, tracking_reset, fm_skipped, pnp_skipped, pnp_failed, motion_outlier, pose_updated, is_keyframe, kf_criterion;
+  int32_t cdr_landmarks;               /* landmarks in the payload */
+  int32_t reserved;
+  uint64_t cdr_bytes;                  /* payload size (what cdr_out must hold); 0 if no keyframe or cdr_out is NULL */
+  double rvec[3], tvec[3];             /* this frame's PnP result (zeros when it did not run or failed) */
+  double R[9], t[3];                   /* R_ (row-major) and t_ after this frame */
+} dvs_track_result;
+void dvs_tracker_default_params(dvs_tracker_params* p);   /* the reference's constants; rows / cols / intrinsics stay zero */
+dvs_status dvs_tracker_create(const dvs_tracker_params* params, int32_t device, dvs_tracker** out);
+void dvs_tracker_destroy(dvs_tracker* h);
+/* back to the state after create: the next frame is a first frame, R_ = I, t_ = 0, keyframe_id_ = 0, t = 0.  Synchronises. */
+dvs_status dvs_tracker_reset(dvs_tracker* h);
+dvs_status dvs_tracker_set_stream(dvs_tracker* h, void* hip_stream);   /* extractor and matcher context move to it */
+dvs_status dvs_tracker_synchronize(dvs_tracker* h);
+/* One frame.  image: host, 8UC1 (channels 1) or BGR 8UC3 (channels 3), `step` bytes between rows; depth_u16: host 16UC1 in
+ * millimetres, depth_step bytes between rows.  When the frame is a keyframe and cdr_out is not NULL the Keyframe.msg payload
+ * (dvs_publish_keyframe_device's, header.frame_id "camera_link", header.stamp as given) is written there; if it needs more than
+ * cdr_cap bytes the call returns DVS_ERR_CAPACITY with out->cdr_bytes set — the frame has been processed and the state updated.
+ * Any other error leaves the frame half done: call dvs_tracker_reset before tracking on (dvs_tracker_get_backend_features gives 0 rows). */
+dvs_status dvs_tracker_track(dvs_tracker* h, const uint8_t* image, int32_t channels, size_t step, const uint16_t* depth_u16, size_t depth_step,
+                             int32_t stamp_sec, uint32_t stamp_nanosec, dvs_track_result* out, uint8_t* cdr_out, size_t cdr_cap);
+/* the last frame's culled feature set in order (kps / desc / sel_index — indices into the depth-filtered set — each nullable, `cap`
+ * rows); *n = rows available.  This read-back is the caller's choice, not part of the per-frame path. */
+dvs_status dvs_tracker_get_backend_features(dvs_tracker* h, dvs_keypoint* kps, uint8_t* desc, int32_t* sel_index, int32_t cap, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif
