@@ -15,6 +15,7 @@
 #include <vector>
 #include "io_pinned.h"
 #include "matcher.h"
+#include "associate_device.h"
 
 namespace dvs {
 
@@ -360,6 +361,39 @@ __global__ __launch_bounds__(256) void k_harris(const uint8_t* __restrict__ img,
 
 using namespace dvs;
 
+// ---- the launch sequence of dvs_associate* on device pointers (associate_device.h): the mapping backend keeps descriptors, pixels and
+// positions in HBM.  d_Rt = R (9, row-major) followed by t (3), on the device.
+namespace dvs {
+int associate_hamming_bound(double max_descriptor_distance) {
+  // (float)d < max_desc with integer d  <=>  d < ceil(max_desc)
+  return (int)std::min<double>(ceil(max_descriptor_distance), 257.0);
+}
+dvs_status associate_errors_device(dvs_matcher* ctx, const long long* d_offs, const int* d_pairs, long long total, const float* d_obs_px,
+                                   const float* d_lm_xyz, int nobs, const double* d_Rt, double fx, double fy, double cx, double cy,
+                                   double max_reprojection_distance, double* d_err, int* d_best) {
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(k_reproject_errors, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_pairs, total, d_obs_px, d_lm_xyz, d_Rt, fx, fy, cx, cy, d_err);
+  hipLaunchKernelGGL(k_assoc_argmin, dim3((nobs + 255) / 256), dim3(256), 0, st, d_offs, nobs, d_pairs, d_err, max_reprojection_distance, d_best);
+  DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+dvs_status associate_rows_device(dvs_matcher* ctx, const uint8_t* d_obs_desc, const float* d_obs_px, int nobs, const uint8_t* d_lm_desc,
+                                 const float* d_lm_xyz, int nlm, const double* d_Rt, double fx, double fy, double cx, double cy,
+                                 double max_descriptor_distance, double max_reprojection_distance, int* d_best, const long long** d_offs,
+                                 const int** d_pairs, long long* total) {
+  *total = 0; *d_offs = nullptr; *d_pairs = nullptr;
+  if (nobs == 0) return DVS_OK;
+  DVS_HIP(hipSetDevice(ctx->device));
+  DVS_HIP(hipMemsetAsync(d_best, 0xFF, (size_t)nobs * 4, ctx->stream));   // -1: no candidate
+  if (nlm == 0) return DVS_OK;
+  DVS_TRY(matcher_thresh_rows_device(ctx, d_obs_desc, nobs, d_lm_desc, nlm, associate_hamming_bound(max_descriptor_distance), d_offs, d_pairs, total));
+  if (*total == 0) return DVS_OK;
+  double* d_err;
+  DVS_TRY(matcher_scratch(ctx, 2, (size_t)*total * 8 + 64, (void**)&d_err));
+  return associate_errors_device(ctx, *d_offs, *d_pairs, *total, d_obs_px, d_lm_xyz, nobs, d_Rt, fx, fy, cx, cy, max_reprojection_distance, d_err, d_best);
+}
+}  // namespace dvs
+
 extern "C" {
 
 dvs_status dvs_bgr_to_gray_device(dvs_matcher* ctx, const uint8_t* d_bgr, int32_t nimg, int32_t rows, int32_t cols, size_t step,
@@ -522,8 +556,7 @@ static dvs_status associate_impl(dvs_matcher* ctx, const uint8_t* obs_desc, cons
   DVS_ARG(lm_desc && lm_xyz);
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  // (float)d < max_desc with integer d  <=>  d < ceil(max_desc)
-  const int thr = (int)std::min<double>(ceil(max_descriptor_distance), 257.0);
+  const int thr = associate_hamming_bound(max_descriptor_distance);
   const long long* d_offs; const int* d_pairs; long long total = 0;
   DVS_TRY(matcher_thresh_device(ctx, obs_desc, nobs, lm_desc, nlm, thr, &d_offs, &d_pairs, &total));
   if (n_cand) *n_cand = total;
@@ -539,9 +572,7 @@ static dvs_status associate_impl(dvs_matcher* ctx, const uint8_t* obs_desc, cons
   DVS_HIP(hipMemcpyAsync(d_px, obs_px, (size_t)nobs * 8, hipMemcpyHostToDevice, st));
   DVS_HIP(hipMemcpyAsync(d_lm, lm_xyz, (size_t)nlm * 12, hipMemcpyHostToDevice, st));
   DVS_HIP(hipMemcpyAsync(d_Rt, Rt, 96, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_reproject_errors, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_pairs, total, d_px, d_lm, d_Rt, fx, fy, cx, cy, d_err);
-  hipLaunchKernelGGL(k_assoc_argmin, dim3((nobs + 255) / 256), dim3(256), 0, st, d_offs, nobs, d_pairs, d_err, max_reprojection_distance, d_best);
-  DVS_HIP(hipGetLastError());
+  DVS_TRY(associate_errors_device(ctx, d_offs, d_pairs, total, d_px, d_lm, nobs, d_Rt, fx, fy, cx, cy, max_reprojection_distance, d_err, d_best));
   DVS_HIP(hipMemcpyAsync(best, d_best, (size_t)nobs * 4, hipMemcpyDeviceToHost, st));
   DVS_HIP(hipStreamSynchronize(st));
   if (cand_offsets) {

@@ -565,6 +565,10 @@ void launch_match_fp4(hipStream_t st, int k, int npairs, const uint8_t* q, const
   else launch_match_fp4_nq<2>(st, k, npairs, q, nq, qStrideRows, t, nt, tStrideRows, t0, nt0, idx, dist);
 }
 
+void launch_scan_counts(hipStream_t st, const int* counts, int n, long long* offs) {
+  hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, counts, n, offs);
+}
+
 dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out) {
   DVS_TRY(grow(&m->scratch[slot], &m->cscratch[slot], bytes));
   *out = m->scratch[slot];
@@ -582,18 +586,13 @@ dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq,
   return DVS_OK;
 }
 
-dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,
-                                 const int** d_pairs, long long* total) {
+dvs_status matcher_thresh_rows_device(dvs_matcher* m, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int max_dist, const long long** d_offs,
+                                      const int** d_pairs, long long* total) {
   DVS_HIP(hipSetDevice(m->device));
-  DVS_TRY(grow(&m->d_q, &m->cq, (size_t)nq * 32));
-  DVS_TRY(grow(&m->d_t, &m->ct, (size_t)nt * 32));
   DVS_TRY(grow(&m->d_counts, &m->ccounts, (size_t)nq * 4));
-  if (m->d_offs) { DVS_HIP(hipFree(m->d_offs)); m->d_offs = nullptr; }
-  DVS_HIP(hipMalloc(&m->d_offs, ((size_t)nq + 1) * 8));
-  DVS_HIP(hipMemcpyAsync(m->d_q, q, (size_t)nq * 32, hipMemcpyHostToDevice, m->stream));
-  DVS_HIP(hipMemcpyAsync(m->d_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, m->stream));
+  DVS_TRY(grow(&m->d_offs, &m->coffs, ((size_t)nq + 1) * 8));
   const dim3 grid((nq + 3) / 4);   // one wavefront per query
-  hipLaunchKernelGGL(k_thresh_count, grid, dim3(256), 0, m->stream, (const u64*)m->d_q, nq, (const u64*)m->d_t, nt, max_dist, (int*)m->d_counts);
+  hipLaunchKernelGGL(k_thresh_count, grid, dim3(256), 0, m->stream, (const u64*)d_q, nq, (const u64*)d_t, nt, max_dist, (int*)m->d_counts);
   hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, m->stream, (const int*)m->d_counts, nq, (long long*)m->d_offs);
   DVS_HIP(hipGetLastError());
   long long tot = 0;
@@ -601,13 +600,23 @@ dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const
   DVS_HIP(hipStreamSynchronize(m->stream));
   DVS_TRY(grow(&m->d_pairs, &m->cpairs, (size_t)std::max<long long>(tot, 1) * 12));
   if (tot) {
-    hipLaunchKernelGGL(k_thresh_write, grid, dim3(256), 0, m->stream, (const u64*)m->d_q, nq, (const u64*)m->d_t, nt, max_dist,
+    hipLaunchKernelGGL(k_thresh_write, grid, dim3(256), 0, m->stream, (const u64*)d_q, nq, (const u64*)d_t, nt, max_dist,
                        (const long long*)m->d_offs, (int*)m->d_pairs, tot);
     DVS_HIP(hipGetLastError());
     DVS_HIP(hipStreamSynchronize(m->stream));
   }
   *d_offs = (const long long*)m->d_offs; *d_pairs = (const int*)m->d_pairs; *total = tot;
   return DVS_OK;
+}
+
+dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,
+                                 const int** d_pairs, long long* total) {
+  DVS_HIP(hipSetDevice(m->device));
+  DVS_TRY(grow(&m->d_q, &m->cq, (size_t)nq * 32));
+  DVS_TRY(grow(&m->d_t, &m->ct, (size_t)nt * 32));
+  DVS_HIP(hipMemcpyAsync(m->d_q, q, (size_t)nq * 32, hipMemcpyHostToDevice, m->stream));
+  DVS_HIP(hipMemcpyAsync(m->d_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, m->stream));
+  return matcher_thresh_rows_device(m, (const uint8_t*)m->d_q, nq, (const uint8_t*)m->d_t, nt, max_dist, d_offs, d_pairs, total);
 }
 }  // namespace dvs
 

@@ -9,7 +9,7 @@ struct dvs_matcher {
   hipStream_t own_stream = nullptr, stream = nullptr;
   // grow-only staging for the host entry points
   void *d_q = nullptr, *d_t = nullptr, *d_idx = nullptr, *d_dist = nullptr, *d_counts = nullptr, *d_offs = nullptr, *d_pairs = nullptr;
-  size_t cq = 0, ct = 0, cidx = 0, ccounts = 0, cpairs = 0;
+  size_t cq = 0, ct = 0, cidx = 0, ccounts = 0, cpairs = 0, coffs = 0;
   void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};  // grow-only buffers of matcher_scratch
   size_t cscratch[4] = {0, 0, 0, 0};
   void* d_zero = nullptr;  // 64 zero bytes: the empty predecessor of dvs_match_hamming_sequence_device
@@ -44,6 +44,11 @@ dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq,
 // no scratch slot); synchronises once for the total
 dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,
                                  const int** d_pairs, long long* total);
+// enqueue k_scan_counts on st: single-workgroup exclusive scan of n int counts into 64-bit offsets, total at offs[n]
+void launch_scan_counts(hipStream_t st, const int* counts, int n, long long* offs);
+// the same on rows that already are on the device (16-byte aligned): nothing is copied
+dvs_status matcher_thresh_rows_device(dvs_matcher* m, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int max_dist, const long long** d_offs,
+                                      const int** d_pairs, long long* total);
 // enqueue k_match_fp4<NQ, k> (1 <= k <= 4) for npairs jobs on st: outputs k (idx, dist) slots per query; q / t / t0 16-byte aligned,
 // tStrideRows > 0; job 0 matches against t0 / nt0 when t0 is given
 void launch_match_fp4(hipStream_t st, int k, int npairs, const uint8_t* q, const int* nq, int qStrideRows, const uint8_t* t, const int* nt,

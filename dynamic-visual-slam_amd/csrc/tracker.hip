@@ -23,23 +23,11 @@
 #include "matcher.h"
 #include "orb_device_common.h"
 #include "ransac_device.h"
+#include "block_rank.h"
 
 namespace dvs {
 
 constexpr int kTrkMaxCap = 3072;   // k_cull sorts in LDS: 20 bytes per unmatched feature (keys, two rank scratches, sorted keys)
-
-// exclusive position of this thread's flag among the workgroup's 256 flags (thread order); total = how many are set.  s_w: 4 ints.
-__device__ __forceinline__ int block_rank256(bool flag, int* s_w, int& total) {
-  const unsigned long long b = __ballot(flag);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();                       // s_w may still be read from the trip before
-  if (lane == 0) s_w[w] = __popcll(b);
-  __syncthreads();
-  int base = 0;
-  for (int k = 0; k < w; k++) base += s_w[k];
-  total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  return base + __popcll(b & ((1ull << lane) - 1ull));
-}
 
 // frontend.cpp:1126-1142 (and :617-632 against the last keyframe): matches with distance < max_dist, in query order; p_train / p_query
 // are the .pt of the train (previous frame / last keyframe) and query (current frame) keypoints

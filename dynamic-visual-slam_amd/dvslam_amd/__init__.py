@@ -12,3 +12,4 @@ from .ba import BAProblem, SlidingWindowBA  # noqa: F401
 from .glue import FrontendGlue  # noqa: F401
 from .cvorb import CvORB  # noqa: F401
 from .tracker import Tracker, TrackerParams, TrackResult  # noqa: F401
+from .backend import MappingBackend  # noqa: F401

@@ -1,0 +1,212 @@
+"""ctypes mirror of the mapping backend (include/dvslam_hip.h, dvs_backend_*): Backend::syncCallback, the BA window, updateOptimizedResults
+and pruneLandmarks (backend.cpp) as one handle that keeps the landmark and observation tables on the device; one call per keyframe."""
+import ctypes as C
+import numpy as np
+from ._lib import lib, check, ptr, DvsError, KeyframeHeader
+
+MAX_FILTERED = 16
+
+
+class BackendParams(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("max_descriptor_distance", C.c_double),
+                ("max_reprojection_distance", C.c_double), ("window", C.c_int32), ("prune_min_observations", C.c_int32),
+                ("prune_max_age_sec", C.c_double), ("n_filtered", C.c_int32), ("filtered_class_ids", C.c_int32 * MAX_FILTERED),
+                ("initial_capacity", C.c_int32)]
+
+
+class Detection(C.Structure):
+    _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("w", C.c_double), ("h", C.c_double), ("class_id", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BackendResult(C.Structure):
+    _fields_ = [("n_kept", C.c_int32), ("n_filtered", C.c_int32), ("n_associated", C.c_int32), ("n_created", C.c_int32), ("n_moved", C.c_int32),
+                ("reserved", C.c_int32), ("first_observation_id", C.c_int64), ("first_landmark_id", C.c_int64)]
+    FIELDS = ("n_kept", "n_filtered", "n_associated", "n_created", "n_moved", "first_observation_id", "first_landmark_id")
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in self.FIELDS}
+
+
+class BackendCount(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_keyframes", "n_observations", "n_landmarks", "next_observation_id", "next_landmark_id")]
+
+
+def _bind(L):
+    vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
+    pi32, pi64 = C.POINTER(i32), C.POINTER(i64)
+    L.dvs_backend_default_params.argtypes = [C.POINTER(BackendParams)]; L.dvs_backend_default_params.restype = None
+    L.dvs_backend_create.argtypes = [C.POINTER(BackendParams), i32, C.POINTER(vp)]
+    L.dvs_backend_destroy.argtypes = [vp]; L.dvs_backend_destroy.restype = None
+    L.dvs_backend_reset.argtypes = [vp]
+    L.dvs_backend_add_keyframe.argtypes = [vp, C.POINTER(KeyframeHeader), i32, vp, vp, vp, vp, i32, C.POINTER(BackendResult)]
+    L.dvs_backend_add_keyframe_cdr.argtypes = [vp, vp, sz, vp, i32, C.POINTER(BackendResult)]
+    L.dvs_backend_counts.argtypes = [vp, C.POINTER(BackendCount)]
+    L.dvs_backend_get_window.argtypes = [vp, i32, i32, i32, vp, vp, vp, pi32, vp, vp, vp, vp, vp, pi32, vp, vp, vp, pi32]
+    L.dvs_backend_apply_optimized.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.dvs_backend_prune.argtypes = [vp, i32, C.c_uint32, pi32, pi32]
+    L.dvs_backend_get_landmarks.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, pi32, pi64]
+    L.dvs_backend_get_observations.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, pi32]
+    L.dvs_backend_get_keyframes.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, pi32, pi64]
+    return L
+
+
+def default_params(fx=0.0, fy=0.0, cx=0.0, cy=0.0, filtered_class_ids=(), **kw):
+    """dvs_backend_default_params (the reference's constants) with the intrinsics, the filtered class ids and any field overrides"""
+    p = BackendParams()
+    _bind(lib()).dvs_backend_default_params(C.byref(p))
+    p.fx, p.fy, p.cx, p.cy = fx, fy, cx, cy
+    ids = [int(c) for c in filtered_class_ids]
+    if len(ids) > MAX_FILTERED:
+        raise ValueError(f"at most {MAX_FILTERED} filtered classes")
+    p.n_filtered = len(ids)
+    for k, c in enumerate(ids):
+        p.filtered_class_ids[k] = c
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+class MappingBackend:
+    """mb = MappingBackend(fx, fy, cx, cy, filtered=("person",)); r = mb.add_keyframe_cdr(payload, [(cx, cy, w, h, "chair"), ...])
+
+    Class names are interned: 0 is "unlabeled", every other name gets the next id the first time it is seen."""
+
+    def __init__(self, fx, fy, cx, cy, filtered=("person",), device=0, **kw):
+        self._L = _bind(lib())
+        self._h = None
+        self._ba = None
+        self.fx, self.fy, self.cx, self.cy, self.device = fx, fy, cx, cy, device
+        self.class_names = ["unlabeled"]
+        self._class_id = {"unlabeled": 0}
+        self.params = default_params(fx, fy, cx, cy, [self.intern(c) for c in filtered], **kw)
+        h = C.c_void_p()
+        check(self._L.dvs_backend_create(C.byref(self.params), device, C.byref(h)))
+        self._h = h
+
+    def intern(self, name):
+        if name not in self._class_id:
+            self._class_id[name] = len(self.class_names); self.class_names.append(name)
+        return self._class_id[name]
+
+    def _detections(self, detections):
+        arr = (Detection * max(len(detections), 1))()
+        for k, (cx, cy, w, h, name) in enumerate(detections):
+            arr[k] = Detection(float(cx), float(cy), float(w), float(h), self.intern(name) if isinstance(name, str) else int(name), 0)
+        return arr, len(detections)
+
+    def add_keyframe(self, frame_id, stamp, translation, rotation_xyzw, landmark_xyz, obs_pixels, obs_desc, detections=()):
+        """syncCallback on flat arrays (landmark_xyz (n, 3) and obs_pixels (n, 2) float64, obs_desc (n, 32) uint8) -> result dict"""
+        from .glue import FrontendGlue
+        hdr = FrontendGlue._header(stamp, "camera_link", frame_id, translation, rotation_xyzw)
+        xyz = np.ascontiguousarray(landmark_xyz, np.float64).reshape(-1, 3); px = np.ascontiguousarray(obs_pixels, np.float64).reshape(-1, 2)
+        desc = np.ascontiguousarray(obs_desc, np.uint8).reshape(-1, 32)
+        if not len(xyz) == len(px) == len(desc):
+            raise ValueError("landmark_xyz, obs_pixels and obs_desc must have one row per observation")
+        det, nd = self._detections(detections)
+        r = BackendResult()
+        check(self._L.dvs_backend_add_keyframe(self._h, C.byref(hdr), len(px), ptr(xyz), ptr(px), ptr(desc), C.cast(det, C.c_void_p), nd, C.byref(r)))
+        return r.as_dict()
+
+    def add_keyframe_cdr(self, payload, detections=()):
+        """the same on the Keyframe.msg CDR payload of publish_keyframe / Tracker.track"""
+        buf = np.frombuffer(payload, np.uint8)
+        det, nd = self._detections(detections)
+        r = BackendResult()
+        check(self._L.dvs_backend_add_keyframe_cdr(self._h, buf.ctypes.data, len(buf), C.cast(det, C.c_void_p), nd, C.byref(r)))
+        return r.as_dict()
+
+    def counts(self):
+        c = BackendCount()
+        check(self._L.dvs_backend_counts(self._h, C.byref(c)))
+        return {k: int(getattr(c, k)) for k, _ in BackendCount._fields_}
+
+    def window(self):
+        """the BA window: dict of keyframes (frame_id, R, t), observations (px, landmark_id, class_id, frame_id, lm_index) and landmarks
+        (id, class_id, xyz) as arrays"""
+        c = self.counts()
+        ck, co, cl = max(int(self.params.window), 1), max(c["n_observations"], 1), max(c["n_landmarks"], 1)
+        kid = np.zeros(ck, np.uint64); R = np.zeros((ck, 3, 3)); t = np.zeros((ck, 3))
+        px = np.zeros((co, 2), np.float32); olm = np.zeros(co, np.uint64); ocl = np.zeros(co, np.int32); ofr = np.zeros(co, np.uint64); oix = np.zeros(co, np.int32)
+        lid = np.zeros(cl, np.uint64); lcl = np.zeros(cl, np.int32); xyz = np.zeros((cl, 3), np.float32)
+        nk, no, nl = C.c_int32(), C.c_int32(), C.c_int32()
+        check(self._L.dvs_backend_get_window(self._h, ck, co, cl, ptr(kid), ptr(R), ptr(t), C.byref(nk), ptr(px), ptr(olm), ptr(ocl), ptr(ofr), ptr(oix), C.byref(no),
+                                             ptr(lid), ptr(lcl), ptr(xyz), C.byref(nl)))
+        nk, no, nl = nk.value, no.value, nl.value
+        return dict(kf_frame_id=kid[:nk], kf_R=R[:nk], kf_t=t[:nk], obs_px=px[:no], obs_landmark_id=olm[:no], obs_class=ocl[:no], obs_frame_id=ofr[:no],
+                    obs_lm_index=oix[:no], lm_id=lid[:nl], lm_class=lcl[:nl], lm_xyz=xyz[:nl])
+
+    def apply_optimized(self, poses, landmarks):
+        """updateOptimizedResults: poses {frame_id: (R, t)}, landmarks {(id, class_id): xyz}"""
+        fid = np.array(list(poses.keys()), np.uint64)
+        R = np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses.values()], np.float64).reshape(-1, 9)
+        t = np.array([np.asarray(p[1], np.float64).reshape(3) for p in poses.values()], np.float64).reshape(-1, 3)
+        lid = np.array([k[0] for k in landmarks.keys()], np.uint64); lcl = np.array([k[1] for k in landmarks.keys()], np.int32)
+        xyz = np.array([np.asarray(v, np.float64).reshape(3) for v in landmarks.values()], np.float64).reshape(-1, 3)
+        check(self._L.dvs_backend_apply_optimized(self._h, len(fid), ptr(fid), ptr(R), ptr(t), len(lid), ptr(lid), ptr(lcl), ptr(xyz)))
+
+    def prune(self, now):
+        """pruneLandmarks at now = (sec, nanosec) -> (removed landmarks, removed observations)"""
+        a, b = C.c_int32(), C.c_int32()
+        check(self._L.dvs_backend_prune(self._h, int(now[0]), int(now[1]), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def bundle_adjust(self, now, max_iterations=20):
+        """bundleAdjustmentCallback: window -> SlidingWindowBA.optimize(..., 20) -> apply on success -> prune.  Returns (result dict, pruned)"""
+        from .ba import SlidingWindowBA
+        w = self.window()
+        kfs = [(int(f), w["kf_R"][k], w["kf_t"][k]) for k, f in enumerate(w["kf_frame_id"])]
+        lms = [(int(i), int(c), w["lm_xyz"][k].astype(np.float64), False) for k, (i, c) in enumerate(zip(w["lm_id"], w["lm_class"]))]
+        obs = [((float(p[0]), float(p[1])), int(l), int(c), int(f)) for p, l, c, f in zip(w["obs_px"], w["obs_landmark_id"], w["obs_class"], w["obs_frame_id"])]
+        if self._ba is None:
+            self._ba = SlidingWindowBA(self.fx, self.fy, self.cx, self.cy, device=self.device)
+        res = self._ba.optimize(kfs, lms, obs, max_iterations)
+        if res["success"]:
+            self.apply_optimized(res["optimized_poses"], res["optimized_landmarks"])
+        return res, self.prune(now)
+
+    def landmarks(self):
+        c = self.counts()
+        n, m = max(c["n_landmarks"], 1), max(c["n_observations"], 1)
+        lid = np.zeros(n, np.uint64); cl = np.zeros(n, np.int32); xyz = np.zeros((n, 3), np.float32); desc = np.zeros((n, 32), np.uint8)
+        cnt = np.zeros(n, np.int32); seen = np.zeros(n, np.int64); offs = np.zeros(n + 1, np.int64); oid = np.zeros(m, np.uint64)
+        nn, nm = C.c_int32(), C.c_int64()
+        check(self._L.dvs_backend_get_landmarks(self._h, n, m, ptr(lid), ptr(cl), ptr(xyz), ptr(desc), ptr(cnt), ptr(seen), ptr(offs), ptr(oid), C.byref(nn), C.byref(nm)))
+        n = nn.value
+        return dict(id=lid[:n], class_id=cl[:n], xyz=xyz[:n], desc=desc[:n], observation_count=cnt[:n], last_seen_ns=seen[:n], obs_offsets=offs[:n + 1],
+                    obs_ids=oid[:nm.value])
+
+    def observations(self):
+        n = max(self.counts()["n_observations"], 1)
+        oid = np.zeros(n, np.uint64); fr = np.zeros(n, np.uint64); px = np.zeros((n, 2), np.float32); desc = np.zeros((n, 32), np.uint8)
+        cl = np.zeros(n, np.int32); lm = np.zeros(n, np.uint64); nn = C.c_int32()
+        check(self._L.dvs_backend_get_observations(self._h, n, ptr(oid), ptr(fr), ptr(px), ptr(desc), ptr(cl), ptr(lm), C.byref(nn)))
+        n = nn.value
+        return dict(id=oid[:n], frame_id=fr[:n], px=px[:n], desc=desc[:n], class_id=cl[:n], landmark_id=lm[:n])
+
+    def keyframes(self):
+        c = self.counts()
+        n, m = max(c["n_keyframes"], 1), max(c["n_observations"], 1)
+        fid = np.zeros(n, np.uint64); st = np.zeros(n, np.int64); R = np.zeros((n, 3, 3)); t = np.zeros((n, 3)); offs = np.zeros(n + 1, np.int64)
+        oid = np.zeros(m, np.uint64); nn, nm = C.c_int32(), C.c_int64()
+        check(self._L.dvs_backend_get_keyframes(self._h, n, m, ptr(fid), ptr(st), ptr(R), ptr(t), ptr(offs), ptr(oid), C.byref(nn), C.byref(nm)))
+        n = nn.value
+        return dict(frame_id=fid[:n], stamp_ns=st[:n], R=R[:n], t=t[:n], obs_offsets=offs[:n + 1], obs_ids=oid[:nm.value])
+
+    def reset(self):
+        check(self._L.dvs_backend_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dvs_backend_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "default_params", "DvsError"]

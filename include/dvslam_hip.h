@@ -676,6 +676,85 @@ dvs_status dvs_tracker_track(dvs_tracker* h, const uint8_t* image, int32_t chann
  * rows); *n = rows available.  This read-back is the caller's choice, not part of the per-frame path. */
 dvs_status dvs_tracker_get_backend_features(dvs_tracker* h, dvs_keypoint* kps, uint8_t* desc, int32_t* sel_index, int32_t cap, int32_t* n);
 
+/* ============================ the mapping backend: one call per keyframe, the map kept on the device ==========================
+ * Backend::syncCallback (backend.cpp:709-832), the window selection of bundleAdjustmentCallback (:892-945), updateOptimizedResults
+ * (:1356-1392) and pruneLandmarks (:1249-1322) as ONE handle (csrc/backend.hip; INTEGRATION.md "Mapping backend").  The landmark table
+ * (id, class, position, descriptor, observation_count, last_seen), the observation table (all_observations_) and the keyframe poses
+ * live in HBM and grow by doubling; the id counters, the keyframe list (frame_id, stamp, observation_ids) and the sequential walk of
+ * the association loop stay on the host.  Categories are int32 class ids: 0 is "unlabeled", the adapters intern the strings.  The
+ * caller serialises the calls on a handle (the reference's timer and mutex are not part of it).
+ *
+ * One stated deviation: the reference walks std::unordered_map<uint64_t, LandmarkInfo>, whose iteration order decides which of two
+ * candidates with EXACTLY equal reprojection error wins (backend.cpp:1106, strict <).  The handle orders a class's landmarks by
+ * ascending id, so the lowest id wins; results are equal wherever no two candidates tie exactly.
+ * Unpinned: pruneLandmarks' age is read as (double)(now_ns - last_seen_ns) / 1e9 against a strict >, our reading of
+ * rclcpp::Duration::seconds(); no test against rclcpp itself backs it. */
+typedef struct dvs_backend dvs_backend;
+#define DVS_BACKEND_MAX_FILTERED 16
+typedef struct dvs_backend_params {
+  double fx, fy, cx, cy;               /* fx_ .. cy_ */
+  double max_descriptor_distance;      /* 50 (backend.cpp:1074) */
+  double max_reprojection_distance;    /* 5 (:1106) */
+  int32_t window;                      /* 5 (:895) */
+  int32_t prune_min_observations;      /* 2 (:1251) */
+  double prune_max_age_sec;            /* 20 (:1252) */
+  int32_t n_filtered;                  /* filtered_objects_ as class ids (:749) */
+  int32_t filtered_class_ids[DVS_BACKEND_MAX_FILTERED];
+  int32_t initial_capacity;            /* rows every table starts with (4096); tables double when full */
+} dvs_backend_params;
+typedef struct dvs_detection {         /* yolo_msgs Detection: bbox centre and size in pixels, the class as an interned id (> 0) */
+  double cx, cy, w, h;
+  int32_t class_id;
+  int32_t reserved;
+} dvs_detection;
+typedef struct dvs_backend_result {
+  int32_t n_kept, n_filtered;          /* observations stored / dropped by the filtered classes (:749-751) */
+  int32_t n_associated, n_created;     /* observations matched to an existing landmark / landmarks created (n_kept = sum) */
+  int32_t n_moved;                     /* distinct landmarks whose position this keyframe's triangulation replaced (:772) */
+  int32_t reserved;
+  int64_t first_observation_id;        /* next_observation_id_ / next_global_landmark_id_ before the keyframe: the ids assigned are */
+  int64_t first_landmark_id;           /* first .. first + n_kept - 1 and first .. first + n_created - 1 */
+} dvs_backend_result;
+typedef struct dvs_backend_count {
+  int64_t n_keyframes, n_observations, n_landmarks, next_observation_id, next_landmark_id;
+} dvs_backend_count;
+void dvs_backend_default_params(dvs_backend_params* p);   /* the reference's constants; the intrinsics stay zero, no class is filtered */
+dvs_status dvs_backend_create(const dvs_backend_params* params, int32_t device, dvs_backend** out);
+void dvs_backend_destroy(dvs_backend* h);
+dvs_status dvs_backend_reset(dvs_backend* h);             /* empty map, both id counters 0; the tables keep their size */
+/* syncCallback without the ROS and marker parts.  hdr: stamp, Keyframe.frame_id (hdr->keyframe_id; a repeat is DVS_ERR_ARG) and pose;
+ * n rows of landmark_xyz (3 doubles), obs_pixels (2 doubles) and obs_desc (32 bytes) in message order; detections in message order.
+ * An error leaves the map as it was before the call only if it is DVS_ERR_ARG; after any other, reset the handle. */
+dvs_status dvs_backend_add_keyframe(dvs_backend* h, const dvs_keyframe_header* hdr, int32_t n, const double* landmark_xyz, const double* obs_pixels,
+                                    const uint8_t* obs_desc, const dvs_detection* detections, int32_t ndet, dvs_backend_result* result);
+/* the same on the payload of dvs_publish_keyframe / dvs_tracker_track (through dvs_keyframe_unpack_cdr) */
+dvs_status dvs_backend_add_keyframe_cdr(dvs_backend* h, const uint8_t* payload, size_t len, const dvs_detection* detections, int32_t ndet,
+                                        dvs_backend_result* result);
+dvs_status dvs_backend_counts(dvs_backend* h, dvs_backend_count* out);
+/* The BA window as bundleAdjustmentCallback builds it: the last min(window, nkf) keyframes (frame_id, R 9 row-major, t 3), their
+ * observations in all_observations_ order (pixel 2 floats, landmark id, class, frame_id, and obs_lm_index = the landmark's row in the
+ * list that follows, -1 if the map does not hold it), and the distinct (landmark id, class) pairs in ascending id with their positions.
+ * Count-then-capacity: the three counts are always set; DVS_ERR_CAPACITY, nothing written, when one exceeds its capacity. */
+dvs_status dvs_backend_get_window(dvs_backend* h, int32_t cap_kf, int32_t cap_obs, int32_t cap_lm, uint64_t* kf_frame_id, double* kf_R, double* kf_t,
+                                  int32_t* n_kf, float* obs_px, uint64_t* obs_lm_id, int32_t* obs_class, uint64_t* obs_frame_id, int32_t* obs_lm_index,
+                                  int32_t* n_obs, uint64_t* lm_id, int32_t* lm_class, float* lm_xyz, int32_t* n_lm);
+/* updateOptimizedResults: poses by frame_id (R 9 row-major, t 3 each; unknown ids are skipped), landmark positions by (id, class)
+ * (3 doubles each, stored as float; a pair the map does not hold is skipped) */
+dvs_status dvs_backend_apply_optimized(dvs_backend* h, int32_t nposes, const uint64_t* frame_ids, const double* R, const double* t, int32_t nlm,
+                                       const uint64_t* lm_ids, const int32_t* lm_class, const double* lm_xyz);
+/* pruneLandmarks at time `now` with its cascade: landmarks with observation_count < prune_min_observations whose age exceeds
+ * prune_max_age_sec leave, with every observation in their lists or naming them; keyframes' observation_ids lose those ids */
+dvs_status dvs_backend_prune(dvs_backend* h, int32_t now_sec, uint32_t now_nanosec, int32_t* removed_landmarks, int32_t* removed_observations);
+/* Getters for tests and adapters (each output nullable, count-then-capacity as above).  Landmarks in ascending id; observation ids as
+ * CSR (obs_offsets: *n + 1 entries).  last_seen / stamps in nanoseconds. */
+dvs_status dvs_backend_get_landmarks(dvs_backend* h, int32_t cap, int64_t cap_obs_ids, uint64_t* id, int32_t* class_id, float* xyz, uint8_t* desc,
+                                     int32_t* observation_count, int64_t* last_seen_ns, int64_t* obs_offsets, uint64_t* obs_ids, int32_t* n,
+                                     int64_t* n_obs_ids);
+dvs_status dvs_backend_get_observations(dvs_backend* h, int32_t cap, uint64_t* id, uint64_t* frame_id, float* px, uint8_t* desc, int32_t* class_id,
+                                        uint64_t* landmark_id, int32_t* n);
+dvs_status dvs_backend_get_keyframes(dvs_backend* h, int32_t cap, int64_t cap_obs_ids, uint64_t* frame_id, int64_t* stamp_ns, double* R, double* t,
+                                     int64_t* obs_offsets, uint64_t* obs_ids, int32_t* n, int64_t* n_obs_ids);
+
 #ifdef __cplusplus
 }
 #endif
