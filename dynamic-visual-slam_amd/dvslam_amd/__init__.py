@@ -13,3 +13,4 @@ from .glue import FrontendGlue  # noqa: F401
 from .cvorb import CvORB  # noqa: F401
 from .tracker import Tracker, TrackerParams, TrackResult  # noqa: F401
 from .backend import MappingBackend  # noqa: F401
+from .bow import OrbVocabulary, OrbDatabase  # noqa: F401

@@ -157,6 +157,24 @@ def _bind(L):
         L.dvs_ba_get_trace.argtypes = [vp, vp, i32, C.POINTER(i32)]
         L.dvs_ba_pose_from_rt.argtypes = [vp, vp, vp, vp]
         L.dvs_ba_pose_to_rt.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "dvs_bow_vocab_info"):   # place recognition (dvslam_amd/bow.py)
+        pi32 = C.POINTER(i32)
+        L.dvs_bow_vocab_load_text.argtypes = [i32, vp, C.c_char_p, C.POINTER(vp)]
+        L.dvs_bow_vocab_from_arrays.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp)]
+        L.dvs_bow_vocab_destroy.argtypes = [vp]; L.dvs_bow_vocab_destroy.restype = None
+        L.dvs_bow_vocab_info.argtypes = [vp, pi32, pi32, pi32, pi32, pi32, pi32]
+        L.dvs_bow_vocab_synchronize.argtypes = [vp]
+        L.dvs_bow_transform.argtypes = [vp, vp, i32, i32, vp, vp, i32, pi32, vp, vp, vp, i32, pi32, vp, vp, vp]
+        L.dvs_bow_transform_batch_device.argtypes = [vp, vp, vp, i32, i32, i32] + [vp] * 10
+        L.dvs_bow_db_create.argtypes = [vp, C.POINTER(vp)]
+        L.dvs_bow_db_destroy.argtypes = [vp]; L.dvs_bow_db_destroy.restype = None
+        L.dvs_bow_db_clear.argtypes = [vp]
+        L.dvs_bow_db_size.argtypes = [vp]; L.dvs_bow_db_size.restype = i32
+        L.dvs_bow_db_add.argtypes = [vp, vp, i32, pi32]
+        L.dvs_bow_db_add_device.argtypes = [vp, vp, vp, i32, i32, pi32]
+        L.dvs_bow_db_query.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, pi32]
+        L.dvs_bow_db_query_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
+        L.dvs_bow_db_get_entry.argtypes = [vp, i32, vp, vp, i32, pi32]
 
 
 def _bind_hooks(L):

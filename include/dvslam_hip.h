@@ -755,6 +755,87 @@ dvs_status dvs_backend_get_observations(dvs_backend* h, int32_t cap, uint64_t* i
 dvs_status dvs_backend_get_keyframes(dvs_backend* h, int32_t cap, int64_t cap_obs_ids, uint64_t* frame_id, int64_t* stamp_ns, double* R, double* t,
                                      int64_t* obs_offsets, uint64_t* obs_ids, int32_t* n, int64_t* n_obs_ids);
 
+/* ======================= place recognition: DBoW2 vocabulary transform and keyframe database ===================================
+ * The other half of the reference's test/test_dbow2_integration.cpp (its README: "Loop Closure Ready: DBoW2 vocabulary integration";
+ * CMakeLists.txt:124-128 links DBoW2): OrbVocabulary (TemplatedVocabulary<FORB::TDescriptor, FORB>) and OrbDatabase
+ * (TemplatedDatabase) over 32-byte ORB descriptors, on the device (csrc/bow.hip; INTEGRATION.md "Place recognition").  PARITY UNPINNED:
+ * DBoW2 is not available to this project; the semantics are restated from the published sources (tests/bow_ref.py is the sequential
+ * restatement the kernels equal bit for bit), not proven against the library.
+ *
+ * Vocabulary: a tree, node 0 the root; every other node has a parent, a 32-byte descriptor, a double weight and an ordered child list;
+ * the leaves are the words, numbered 0, 1, ... in node-id order.  A feature descends from the root: at every node the child with the
+ * smallest Hamming distance wins, the FIRST such child on ties (DBoW2 compares with a strict <), until the winner is a leaf: that is
+ * its word, the leaf's weight its weight.  Its feature-vector node is the winner at level L - levelsup (the root, 0, when that is
+ * <= 0).  Deviation 1: where the descent ends at a leaf above that level DBoW2 leaves the node id uninitialised; here it is that leaf.
+ * A frame's BowVector: features whose weight is not > 0 contribute nothing; TF_IDF / TF: v[word] += weight in feature order (a repeated
+ * addition, ((w + w) + w) + ..., not count * w); IDF / BINARY: v[word] = weight; then every value is divided by the L1 norm, summed
+ * sequentially in ascending word id, if that is > 0.  Its FeatureVector: node id -> ascending feature indices, as CSR.
+ * Only scoring 0 (L1_NORM, DBoW2's and ORBvoc.txt's default) is built: any other is DVS_ERR_UNSUPPORTED.  Not built either:
+ * vocabulary.create() (test_dbow2_integration.cpp:158; k-means++ over DBoW2's own random source) and the direct index (use_di).
+ * A vocabulary handle enqueues on the caller's hipStream_t (NULL: the legacy default stream), as dvs_matcher_create_on_stream; it
+ * creates no stream.  A database borrows its vocabulary (stream and scratch): the vocabulary must outlive it, and the two are one
+ * handle as far as threads are concerned. */
+typedef struct dvs_bow_vocab dvs_bow_vocab;
+typedef struct dvs_bow_db dvs_bow_db;
+enum { DVS_BOW_L1_NORM = 0, DVS_BOW_L2_NORM = 1, DVS_BOW_CHI_SQUARE = 2, DVS_BOW_KL = 3, DVS_BOW_BHATTACHARYYA = 4, DVS_BOW_DOT_PRODUCT = 5 };
+enum { DVS_BOW_TF_IDF = 0, DVS_BOW_TF = 1, DVS_BOW_IDF = 2, DVS_BOW_BINARY = 3 };
+#define DVS_BOW_MAX_K 32
+#define DVS_BOW_MAX_L 10
+/* OrbVocabulary::loadFromTextFile (test_dbow2_integration.cpp:91), the text format of the ORB-SLAM flavour of DBoW2: first line
+ * "k L scoring weighting", then one line "parent_id is_leaf d0 ... d31 weight" per node; the node on the n-th such line has id n and is
+ * appended to its parent's child list.  k in 2..DVS_BOW_MAX_K, L in 1..DVS_BOW_MAX_L.  DVS_ERR_ARG: an unreadable file, a malformed
+ * line, a parent id that is not smaller than the node's own, a node with more than k children, a node marked as a leaf that has
+ * children or one not so marked that has none, a weight that is not finite.  Nodes with fewer than k children and leaves above depth L
+ * are fine.  The file is parsed and checked before the device is touched. */
+dvs_status dvs_bow_vocab_load_text(int32_t device, void* hip_stream, const char* path, dvs_bow_vocab** out);
+/* the same from arrays: row j (of n_nodes >= 0) describes node j + 1 — parent id, leaf flag, 32 descriptor bytes, weight */
+dvs_status dvs_bow_vocab_from_arrays(int32_t device, void* hip_stream, int32_t k, int32_t L, int32_t scoring, int32_t weighting, int32_t n_nodes,
+                                     const int32_t* parent, const uint8_t* is_leaf, const uint8_t* desc, const double* weight, dvs_bow_vocab** out);
+void dvs_bow_vocab_destroy(dvs_bow_vocab* voc);
+/* OrbVocabulary::size / empty / getBranchingFactor ... (test_dbow2_integration.cpp:94): any output may be NULL; n_nodes without the root */
+dvs_status dvs_bow_vocab_info(const dvs_bow_vocab* voc, int32_t* k, int32_t* L, int32_t* scoring, int32_t* weighting, int32_t* n_nodes,
+                              int32_t* n_words);
+dvs_status dvs_bow_vocab_synchronize(dvs_bow_vocab* voc);
+/* OrbVocabulary::transform(features, bow_vector, feature_vector, levelsup) (test_dbow2_integration.cpp:161 and, inside the database,
+ * :109, :117) for one frame of n host rows.  Outputs, each group nullable: word_ids / word_values (ascending word id; cap_words >= n
+ * entries) and *n_words; the FeatureVector as CSR — fv_nodes (ascending node id), fv_offsets (cap_fv + 1 entries), fv_features
+ * (cap_fv >= n entries) and *n_fv_nodes; feat_word / feat_node / feat_weight (n entries each): every feature's word, node and weight,
+ * weight-0 features included.  A capacity below n is DVS_ERR_CAPACITY before anything runs. */
+dvs_status dvs_bow_transform(dvs_bow_vocab* voc, const uint8_t* desc, int32_t n, int32_t levelsup, int32_t* word_ids, double* word_values,
+                             int32_t cap_words, int32_t* n_words, int32_t* fv_nodes, int32_t* fv_offsets, int32_t* fv_features, int32_t cap_fv,
+                             int32_t* n_fv_nodes, int32_t* feat_word, int32_t* feat_node, double* feat_weight);
+/* nframes device-resident frames in the layout of dvs_match_hamming_batch_device: frame f uses rows [0, d_n[f]) of d_desc +
+ * f*stride_rows*32 (16-byte aligned).  Outputs (each nullable) are [nframes][stride_rows] blocks — d_fv_offsets [nframes][stride_rows + 1] —
+ * with the per-frame counts d_n_words[nframes], d_n_fv_nodes[nframes].  Asynchronous on the vocabulary's stream. */
+dvs_status dvs_bow_transform_batch_device(dvs_bow_vocab* voc, const uint8_t* d_desc, const int32_t* d_n, int32_t stride_rows, int32_t nframes,
+                                          int32_t levelsup, int32_t* d_word_ids, double* d_word_values, int32_t* d_n_words, int32_t* d_fv_nodes,
+                                          int32_t* d_fv_offsets, int32_t* d_fv_features, int32_t* d_n_fv_nodes, int32_t* d_feat_word,
+                                          int32_t* d_feat_node, double* d_feat_weight);
+/* OrbDatabase(vocabulary) (test_dbow2_integration.cpp:103): entries kept on the device as a grow-only CSR of (word id, value) */
+dvs_status dvs_bow_db_create(dvs_bow_vocab* voc, dvs_bow_db** out);
+void dvs_bow_db_destroy(dvs_bow_db* db);
+dvs_status dvs_bow_db_clear(dvs_bow_db* db);          /* TemplatedDatabase::clear: no entries, the next id is 0 */
+int32_t dvs_bow_db_size(const dvs_bow_db* db);        /* TemplatedDatabase::size (:113); 0 for NULL */
+/* database.add(features) (:109): the frame's normalised BowVector becomes entry *entry_id = size() */
+dvs_status dvs_bow_db_add(dvs_bow_db* db, const uint8_t* desc, int32_t n, int32_t* entry_id);
+/* nframes device-resident frames (layout of dvs_bow_transform_batch_device) become entries *first_entry_id_out + f.  Asynchronous. */
+dvs_status dvs_bow_db_add_device(dvs_bow_db* db, const uint8_t* d_desc, const int32_t* d_n, int32_t stride_rows, int32_t nframes,
+                                 int32_t* first_entry_id_out);
+/* database.query(features, results, max_results, max_id) (:117) with L1 scoring: for every entry e (e < max_id unless max_id == -1) that
+ * shares a word with the query's vector q, raw = sum over the common words, in ascending word id, of |q_i - e_i| - |q_i| - |e_i|;
+ * entries without a common word do not appear.  Deviation 2: the results are ordered by ascending (raw, entry id) — the lowest id wins
+ * among equal raws, as everywhere in this library — where DBoW2 runs an unstable std::sort on raw alone; the two agree wherever no two
+ * raws tie exactly.  The first max_results (all if max_results <= 0) are written as ids / scores with score = -raw / 2.0; *n_results =
+ * their number.  cap below min(max_results or all, admissible entries) is DVS_ERR_CAPACITY before anything runs. */
+dvs_status dvs_bow_db_query(dvs_bow_db* db, const uint8_t* desc, int32_t n, int32_t max_results, int32_t max_id, int32_t* ids, double* scores,
+                            int32_t cap, int32_t* n_results);
+/* the same on device pointers: rows [0, *d_n) of d_desc (16-byte aligned, stride_rows rows allocated), results and count to device
+ * memory.  Asynchronous. */
+dvs_status dvs_bow_db_query_device(dvs_bow_db* db, const uint8_t* d_desc, const int32_t* d_n, int32_t stride_rows, int32_t max_results,
+                                   int32_t max_id, int32_t* d_ids, double* d_scores, int32_t cap, int32_t* d_n_results);
+/* read-back of entry `id` for tests and adapters: *n = its words (always set); DVS_ERR_CAPACITY, nothing written, if cap < *n */
+dvs_status dvs_bow_db_get_entry(dvs_bow_db* db, int32_t id, int32_t* word_ids, double* word_values, int32_t cap, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif
