@@ -16,6 +16,7 @@
 #include <vector>
 #include "common.h"
 #include "device_mem.h"
+#include "bow_internal.h"
 
 namespace {
 using namespace dvs;
@@ -23,15 +24,6 @@ using namespace dvs;
 constexpr int kGroup = 16;          // lanes per feature in the descent
 constexpr int kBlock = 256;
 constexpr int kQueryLdsRows = 4096; // a query of up to this many rows keeps its words in LDS (12 B each), a longer one reads them from memory
-
-struct VocabDev {
-  const uint4* desc;        // [nodes][2]: 32-byte rows, children of one node contiguous in child-list order
-  const int* child_begin;   // first child's row
-  const int* child_count;
-  const int* word_id;       // -1 for inner nodes
-  const int* orig_id;       // the node id callers see
-  const double* weight;
-};
 
 // One feature per 16-lane group.  The loop is uniform within a group (every lane of it follows the same winner), so the shuffles only
 // ever read lanes that run the same iteration.
@@ -267,13 +259,6 @@ __global__ __launch_bounds__(kBlock) void k_db_select(int n_entries, int limit, 
   if (e == 0) n_results[0] = limit > 0 ? min(*n_common_entries, limit) : *n_common_entries;
 }
 
-struct HostVocab {
-  int k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0;
-  std::vector<uint8_t> desc;   // rows in device order (row 0: the root, zeros)
-  std::vector<int> child_begin, child_count, word_id, orig_id;
-  std::vector<double> weight;
-};
-
 // checks, then renumbers breadth-first so that every node's children are contiguous in child-list order
 dvs_status build_vocab(int k, int L, int scoring, int weighting, int n, const int32_t* parent, const uint8_t* is_leaf, const uint8_t* desc,
                        const double* weight, HostVocab* H) {
@@ -389,24 +374,6 @@ dvs_status grow_keep(DeviceBuf<T>& buf, size_t& cap, size_t need, size_t used, h
 
 }  // namespace
 
-struct dvs_bow_vocab {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  HostVocab H;                 // the sizes; its arrays are released after the upload
-  DeviceBuf<uint8_t> desc;
-  DeviceBuf<int> child_begin, child_count, word_id, orig_id;
-  DeviceBuf<double> weight;
-  VocabDev V{};
-  // scratch and the handle's own outputs, [frames][rows] ([frames][rows + 1] for the two offset blocks), grown on demand
-  size_t cap_rows = 0, cap_frames = 0, cap_in = 0;
-  DeviceBuf<int> sw_word, sw_feat, sn_node, seg_start;
-  DeviceBuf<int> o_word_ids, o_fv_nodes, o_fv_offsets, o_fv_features, o_feat_word, o_feat_node, o_n_words, o_n_fv;
-  DeviceBuf<double> o_word_values, o_feat_weight;
-  DeviceBuf<uint8_t> in_desc;  // the host forms' staging: one frame's rows and its count
-  DeviceBuf<int> in_n;
-  PinnedBuf<int> h_n;
-};
-
 struct dvs_bow_db {
   dvs_bow_vocab* voc = nullptr;
   int n_entries = 0;
@@ -477,7 +444,7 @@ dvs_status stage_frame(dvs_bow_vocab* v, const uint8_t* desc, int n) {
   return DVS_OK;
 }
 
-dvs_status create_vocab(int device, void* hip_stream, HostVocab&& H, dvs_bow_vocab** out) {
+dvs_status create_vocab(int device, void* hip_stream, const HostVocab& H, dvs_bow_vocab** out) {
   DVS_TRY(check_device(device));
   dvs_bow_vocab* v = new dvs_bow_vocab();
   v->device = device; v->stream = (hipStream_t)hip_stream;
@@ -555,6 +522,23 @@ dvs_status db_query(dvs_bow_db* db, const uint8_t* d_desc, const int* d_n, int s
 
 }  // namespace
 
+// what bow_train.hip builds on (bow_internal.h)
+namespace dvs {
+dvs_status bow_build_vocab(int k, int L, int scoring, int weighting, int n, const int32_t* parent, const uint8_t* is_leaf, const uint8_t* desc,
+                           const double* weight, HostVocab* H) {
+  return build_vocab(k, L, scoring, weighting, n, parent, is_leaf, desc, weight, H);
+}
+dvs_status bow_create_vocab(int device, void* hip_stream, const HostVocab& H, dvs_bow_vocab** out) { return create_vocab(device, hip_stream, H, out); }
+dvs_status bow_enqueue_descend(const VocabDev& V, const uint8_t* d_desc, const int* d_n, int stride_rows, int nframes, int nid_level, int* feat_word,
+                               int* feat_node, double* feat_weight, hipStream_t s) {
+  if (nframes <= 0 || stride_rows <= 0) return DVS_OK;
+  const dim3 gd((stride_rows + kBlock / kGroup - 1) / (kBlock / kGroup), nframes);
+  hipLaunchKernelGGL(k_bow_descend, gd, dim3(kBlock), 0, s, V, d_desc, d_n, stride_rows, nid_level, feat_word, feat_node, feat_weight);
+  DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+}  // namespace dvs
+
 extern "C" {
 
 dvs_status dvs_bow_vocab_load_text(int32_t device, void* hip_stream, const char* path, dvs_bow_vocab** out) {
@@ -562,7 +546,7 @@ dvs_status dvs_bow_vocab_load_text(int32_t device, void* hip_stream, const char*
   *out = nullptr;
   HostVocab H;
   DVS_TRY(parse_text(path, &H));
-  return create_vocab(device, hip_stream, std::move(H), out);
+  return create_vocab(device, hip_stream, H, out);
 }
 
 dvs_status dvs_bow_vocab_from_arrays(int32_t device, void* hip_stream, int32_t k, int32_t L, int32_t scoring, int32_t weighting, int32_t n_nodes,
@@ -571,7 +555,7 @@ dvs_status dvs_bow_vocab_from_arrays(int32_t device, void* hip_stream, int32_t k
   *out = nullptr;
   HostVocab H;
   DVS_TRY(build_vocab(k, L, scoring, weighting, n_nodes, parent, is_leaf, desc, weight, &H));
-  return create_vocab(device, hip_stream, std::move(H), out);
+  return create_vocab(device, hip_stream, H, out);
 }
 
 void dvs_bow_vocab_destroy(dvs_bow_vocab* voc) {

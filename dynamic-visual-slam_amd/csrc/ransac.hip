@@ -29,16 +29,9 @@
 #include "io_pinned.h"
 #include "matcher.h"
 #include "ransac_device.h"
+#include "splitmix64.h"
 
 namespace dvs {
-
-__host__ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  unsigned long long z = x;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // RansacProb (ransac_device.h): one problem of a batch, blockIdx.y of every kernel below.
 

@@ -44,6 +44,15 @@ class BaSummary(C.Structure):
                 ("linear_solver", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double)]
 
 
+class VocTrainParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32), ("seed", C.c_uint64),
+                ("max_iterations", C.c_int32)]
+
+
+class VocTrainReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_words", "levels_run", "max_passes", "nodes_capped", "clusters_emptied", "nodes_short_seeded")]
+
+
 def build_library():
     """(re)build lib/libdvslam_hip.so with hipcc for gfx950 (cross-compiles without a GPU)."""
     subprocess.check_call(["make", "-s", "-j4", "-C", _PKG])
@@ -175,6 +184,13 @@ def _bind(L):
         L.dvs_bow_db_query.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, pi32]
         L.dvs_bow_db_query_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
         L.dvs_bow_db_get_entry.argtypes = [vp, i32, vp, vp, i32, pi32]
+    if hasattr(L, "dvs_voc_train"):   # vocabulary training (OrbVocabulary.create)
+        pi32 = C.POINTER(i32)
+        L.dvs_voc_train_default_params.argtypes = [C.POINTER(VocTrainParams)]
+        L.dvs_voc_train.argtypes = [i32, vp, C.POINTER(VocTrainParams), vp, vp, i32, C.POINTER(vp), C.POINTER(VocTrainReport)]
+        L.dvs_voc_train_device.argtypes = [i32, vp, C.POINTER(VocTrainParams), vp, vp, i32, i32, C.POINTER(vp), C.POINTER(VocTrainReport)]
+        L.dvs_voc_get_arrays.argtypes = [vp, i32, vp, vp, vp, vp, pi32]
+        L.dvs_voc_save_text.argtypes = [vp, C.c_char_p]
 
 
 def _bind_hooks(L):

@@ -1,8 +1,9 @@
 """Place recognition: thin mirrors of DBoW2's OrbVocabulary / OrbDatabase over dvs_bow_* (include/dvslam_hip.h, csrc/bow.hip), as the
-reference's test/test_dbow2_integration.cpp uses them.  No CPU fallback: creating a vocabulary needs the device."""
+reference's test/test_dbow2_integration.cpp uses them, and OrbVocabulary.create over dvs_voc_train (csrc/bow_train.hip).  No CPU fallback:
+creating a vocabulary needs the device."""
 import ctypes as C
 import numpy as np
-from ._lib import lib, check, ptr
+from ._lib import lib, check, ptr, VocTrainParams, VocTrainReport
 
 L1_NORM = 0
 TF_IDF, TF, IDF, BINARY = 0, 1, 2, 3
@@ -13,12 +14,14 @@ def _rows(features):
 
 
 class OrbVocabulary:
-    """OrbVocabulary: OrbVocabulary(path) / loadFromTextFile, or from_arrays(k, L, parent, is_leaf, desc, weight); size(), empty(),
-    transform().  stream: raw hipStream_t (int) to enqueue on; None = HIP's default stream (the handle creates none)."""
+    """OrbVocabulary: OrbVocabulary(path) / loadFromTextFile, from_arrays(k, L, parent, is_leaf, desc, weight), or create(training
+    features, k, L); size(), empty(), transform(), arrays(), save_text().  stream: raw hipStream_t (int) to enqueue on; None = HIP's
+    default stream (the handle creates none)."""
 
     def __init__(self, path=None, device=0, stream=None):
         self._L = lib()
         self._h = None
+        self.train_report = None          # dict of dvs_voc_train_report after create() / create_device()
         self._device, self._stream = device, stream
         if path is not None:
             self.loadFromTextFile(path)
@@ -35,6 +38,49 @@ class OrbVocabulary:
                                              C.byref(h)))
         v._h = h
         return v
+
+    def _train_params(self, k, L, weighting, seed, max_iterations, scoring):
+        return VocTrainParams(int(k), int(L), int(weighting), int(scoring), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations))
+
+    def _trained(self, h, rep):
+        self.close()
+        self._h = h
+        self.train_report = {n: getattr(rep, n) for n, _ in VocTrainReport._fields_}
+        return self
+
+    def create(self, training_features, k=10, L=5, weighting=TF_IDF, seed=0, max_iterations=100, scoring=L1_NORM):
+        """OrbVocabulary::create(training_features, k, L): training_features is a list of (n_i, 32) uint8 arrays, one per image.
+        Replaces this vocabulary (a database that borrows the old one must be gone).  Blocks: the stream is synchronised."""
+        images = [_rows(f) for f in training_features]
+        counts = np.array([len(f) for f in images], np.int32)
+        desc = np.ascontiguousarray(np.concatenate(images)) if images else np.zeros((0, 32), np.uint8)
+        prm = self._train_params(k, L, weighting, seed, max_iterations, scoring)
+        h, rep = C.c_void_p(), VocTrainReport()
+        check(self._L.dvs_voc_train(self._device, self._stream, C.byref(prm), ptr(desc) if len(desc) else None, ptr(counts) if len(counts) else None,
+                                    len(counts), C.byref(h), C.byref(rep)))
+        return self._trained(h, rep)
+
+    def create_device(self, d_desc, d_n, stride_rows, nframes, k=10, L=5, weighting=TF_IDF, seed=0, max_iterations=100, scoring=L1_NORM):
+        """the same on device-resident frames in the layout of transform_batch_device (frame f: rows [0, d_n[f]) of d_desc + f*stride_rows*32)"""
+        prm = self._train_params(k, L, weighting, seed, max_iterations, scoring)
+        h, rep = C.c_void_p(), VocTrainReport()
+        check(self._L.dvs_voc_train_device(self._device, self._stream, C.byref(prm), d_desc, d_n, stride_rows, nframes, C.byref(h), C.byref(rep)))
+        return self._trained(h, rep)
+
+    def arrays(self):
+        """dict: parent int32[n], is_leaf uint8[n], desc uint8[n, 32], weight float64[n] — what from_arrays takes (row j: node j + 1)"""
+        n = self.info()["n_nodes"] if self._h else 0
+        parent = np.zeros(n, np.int32); is_leaf = np.zeros(n, np.uint8); desc = np.zeros((n, 32), np.uint8); weight = np.zeros(n, np.float64)
+        got = C.c_int32()
+        if self._h:
+            check(self._L.dvs_voc_get_arrays(self._h, n, ptr(parent), ptr(is_leaf), ptr(desc), ptr(weight), C.byref(got)))
+        return dict(parent=parent, is_leaf=is_leaf, desc=desc, weight=weight)
+
+    def save_text(self, path):
+        """TemplatedVocabulary::saveToTextFile, the format loadFromTextFile reads"""
+        check(self._L.dvs_voc_save_text(self._h, str(path).encode()))
+
+    saveToTextFile = save_text
 
     def loadFromTextFile(self, path):
         self.close()

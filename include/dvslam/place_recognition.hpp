@@ -1,11 +1,12 @@
 // dvslam/place_recognition.hpp — header-only C++ adapter with the call surface of DBoW2's OrbVocabulary / OrbDatabase as the reference's
-// test/test_dbow2_integration.cpp:63-126 uses them, over dvs_bow_* of dvslam_hip.h.  A call site swaps the two typedefs (:7-8)
+// test/test_dbow2_integration.cpp:63-163 uses them, over dvs_bow_* and dvs_voc_* of dvslam_hip.h.  A call site swaps the two typedefs (:7-8)
 //   typedef dvslam::OrbVocabulary OrbVocabulary;   typedef dvslam::OrbDatabase OrbDatabase;
 // and DBoW2::EntryId / DBoW2::QueryResults for dvslam::EntryId / dvslam::QueryResults; the test body reads the same.
 //   plain layer    features as `const uint8_t* rows, int n` (n x 32 bytes) or std::vector<std::array<uint8_t, 32>>; needs only the C-ABI
 //   OpenCV layer   std::vector<cv::Mat> features (one 1 x 32 CV_8U row each), compiled only when DVSLAM_WITH_OPENCV is defined
-// Semantics, the two deviations (early-leaf node id, (raw, id) result order) and what is not built (create(), scorings other than L1,
-// the direct index): INTEGRATION.md "Place recognition".  Errors throw std::runtime_error, as DBoW2 throws on a file it cannot read.
+// Semantics, the deviations (early-leaf node id, (raw, id) result order; training: iteration cap, emptied cluster, the stated sampler)
+// and what is not built (scorings other than L1, the direct index): INTEGRATION.md "Place recognition".  Errors throw
+// std::runtime_error, as DBoW2 throws on a file it cannot read.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -27,6 +28,9 @@ typedef unsigned int NodeId;
 typedef std::vector<std::array<uint8_t, 32>> DescriptorVector;
 typedef std::map<WordId, double> BowVector;                       // DBoW2::BowVector is a std::map<WordId, WordValue>
 typedef std::map<NodeId, std::vector<unsigned int>> FeatureVector;
+
+enum WeightingType { TF_IDF = 0, TF = 1, IDF = 2, BINARY = 3 };                                  // DBoW2::WeightingType
+enum ScoringType { L1_NORM = 0, L2_NORM = 1, CHI_SQUARE = 2, KL = 3, BHATTACHARYYA = 4, DOT_PRODUCT = 5 };   // DBoW2::ScoringType
 
 struct Result {
   EntryId Id;
@@ -58,6 +62,10 @@ class OrbVocabulary {
   explicit OrbVocabulary(const std::string& filename, int device = 0, void* hip_stream = nullptr) : device_(device), stream_(hip_stream) {
     loadFromTextFile(filename);
   }
+  // TemplatedVocabulary(k, L, weighting, scoring): the parameters create(training_features) trains with (all four are required here:
+  // the two-argument form is (device, stream))
+  OrbVocabulary(int k, int L, WeightingType weighting, ScoringType scoring, int device = 0, void* hip_stream = nullptr)
+      : device_(device), stream_(hip_stream), k_(k), L_(L), weighting_(weighting), scoring_(scoring) {}
   ~OrbVocabulary() { dvs_bow_vocab_destroy(h_); }
   OrbVocabulary(const OrbVocabulary&) = delete;
   OrbVocabulary& operator=(const OrbVocabulary&) = delete;
@@ -69,6 +77,41 @@ class OrbVocabulary {
     h_ = h;
     return true;
   }
+  // TemplatedVocabulary::create: hierarchical k-means over all images' features (test_dbow2_integration.cpp:158).  Replaces the handle:
+  // a database that borrows the old one must be gone (DBoW2's database holds a copy instead).  Blocks until the vocabulary is trained.
+  void create(const uint8_t* rows, const int32_t* image_counts, int nimages) {
+    dvs_voc_train_params p;
+    detail::bow_check(dvs_voc_train_default_params(&p), "OrbVocabulary::create");
+    p.k = k_; p.L = L_; p.weighting = (int32_t)weighting_; p.scoring = (int32_t)scoring_; p.seed = seed_;
+    dvs_bow_vocab* h = nullptr;
+    detail::bow_check(dvs_voc_train(device_, stream_, &p, rows, image_counts, nimages, &h, &report_), "OrbVocabulary::create");
+    dvs_bow_vocab_destroy(h_);
+    h_ = h;
+  }
+  void create(const std::vector<DescriptorVector>& training_features) {
+    std::vector<int32_t> counts;
+    std::vector<uint8_t> rows;
+    for (const DescriptorVector& image : training_features) {
+      counts.push_back((int32_t)image.size());
+      for (const std::array<uint8_t, 32>& d : image) rows.insert(rows.end(), d.begin(), d.end());
+    }
+    create(rows.empty() ? nullptr : rows.data(), counts.empty() ? nullptr : counts.data(), (int)counts.size());
+  }
+  void create(const std::vector<DescriptorVector>& training_features, int k, int L) {
+    k_ = k; L_ = L;
+    create(training_features);
+  }
+  void create(const std::vector<DescriptorVector>& training_features, int k, int L, WeightingType weighting, ScoringType scoring) {
+    k_ = k; L_ = L; weighting_ = weighting; scoring_ = scoring;
+    create(training_features);
+  }
+  // TemplatedVocabulary::saveToTextFile, the format loadFromTextFile reads
+  void saveToTextFile(const std::string& filename) const {
+    if (!h_) throw std::runtime_error("OrbVocabulary::saveToTextFile: no vocabulary");
+    detail::bow_check(dvs_voc_save_text(h_, filename.c_str()), "OrbVocabulary::saveToTextFile");
+  }
+  void setSeed(uint64_t seed) { seed_ = seed; }              // the sampler's seed (DBoW2 seeds from the clock)
+  const dvs_voc_train_report& lastTrainReport() const { return report_; }
   // number of words
   unsigned int size() const {
     int32_t n = 0;
@@ -100,6 +143,24 @@ class OrbVocabulary {
     transform(rows.data(), (int)features.size(), v, fv, levelsup);
   }
   void transform(const std::vector<cv::Mat>& features, BowVector& v) const { FeatureVector fv; transform(features, v, fv, 0); }
+  void create(const std::vector<std::vector<cv::Mat>>& training_features) {
+    std::vector<int32_t> counts;
+    std::vector<uint8_t> rows;
+    for (const std::vector<cv::Mat>& image : training_features) {
+      const std::vector<uint8_t> r = detail::pack_rows(image);
+      counts.push_back((int32_t)image.size());
+      rows.insert(rows.end(), r.begin(), r.end());
+    }
+    create(rows.empty() ? nullptr : rows.data(), counts.empty() ? nullptr : counts.data(), (int)counts.size());
+  }
+  void create(const std::vector<std::vector<cv::Mat>>& training_features, int k, int L) {
+    k_ = k; L_ = L;
+    create(training_features);
+  }
+  void create(const std::vector<std::vector<cv::Mat>>& training_features, int k, int L, WeightingType weighting, ScoringType scoring) {
+    k_ = k; L_ = L; weighting_ = weighting; scoring_ = scoring;
+    create(training_features);
+  }
 #endif
   dvs_bow_vocab* handle() const { return h_; }
 
@@ -107,6 +168,11 @@ class OrbVocabulary {
   dvs_bow_vocab* h_ = nullptr;
   int device_;
   void* stream_;
+  int k_ = 10, L_ = 5;
+  WeightingType weighting_ = TF_IDF;
+  ScoringType scoring_ = L1_NORM;
+  uint64_t seed_ = 0;
+  dvs_voc_train_report report_ = dvs_voc_train_report();
 };
 
 // Borrows the vocabulary (DBoW2 copies it): the vocabulary must outlive the database.

@@ -770,8 +770,8 @@ dvs_status dvs_backend_get_keyframes(dvs_backend* h, int32_t cap, int64_t cap_ob
  * A frame's BowVector: features whose weight is not > 0 contribute nothing; TF_IDF / TF: v[word] += weight in feature order (a repeated
  * addition, ((w + w) + w) + ..., not count * w); IDF / BINARY: v[word] = weight; then every value is divided by the L1 norm, summed
  * sequentially in ascending word id, if that is > 0.  Its FeatureVector: node id -> ascending feature indices, as CSR.
- * Only scoring 0 (L1_NORM, DBoW2's and ORBvoc.txt's default) is built: any other is DVS_ERR_UNSUPPORTED.  Not built either:
- * vocabulary.create() (test_dbow2_integration.cpp:158; k-means++ over DBoW2's own random source) and the direct index (use_di).
+ * Only scoring 0 (L1_NORM, DBoW2's and ORBvoc.txt's default) is built: any other is DVS_ERR_UNSUPPORTED.  Not built either: the
+ * direct index (use_di).  vocabulary.create() (test_dbow2_integration.cpp:158) is dvs_voc_train below.
  * A vocabulary handle enqueues on the caller's hipStream_t (NULL: the legacy default stream), as dvs_matcher_create_on_stream; it
  * creates no stream.  A database borrows its vocabulary (stream and scratch): the vocabulary must outlive it, and the two are one
  * handle as far as threads are concerned. */
@@ -835,6 +835,58 @@ dvs_status dvs_bow_db_query_device(dvs_bow_db* db, const uint8_t* d_desc, const 
                                    int32_t max_id, int32_t* d_ids, double* d_scores, int32_t cap, int32_t* d_n_results);
 /* read-back of entry `id` for tests and adapters: *n = its words (always set); DVS_ERR_CAPACITY, nothing written, if cap < *n */
 dvs_status dvs_bow_db_get_entry(dvs_bow_db* db, int32_t id, int32_t* word_ids, double* word_values, int32_t cap, int32_t* n);
+
+/* ----------------------- vocabulary training: OrbVocabulary::create (test_dbow2_integration.cpp:138-163) --------------------------
+ * DBoW2's TemplatedVocabulary::create, HKmeansStep, initiateClustersKMpp, FORB::meanValue and setNodeWeights, restated from the
+ * published sources (PARITY UNPINNED, as above; tests/bow_train_ref.py is the recursive restatement csrc/bow_train.hip equals bit for
+ * bit).  The training set is nimages images, each an ordered list of 32-byte descriptors; `features` is all of them in image order.
+ *   create   the root is node 0; step(root, all features, level 1); the words are the leaves in ascending node id; then the weights.
+ *   step(parent, F, level)   nothing if F is empty.  |F| <= k: one cluster per feature in order (centre i = F[i], group i = {i}).
+ *     Otherwise k-means++ seeds, then passes: (1) from the second pass on every centre becomes the mean of its group, (2) every
+ *     feature joins the centre of smallest Hamming distance, the FIRST such centre on ties (strict <), (3) from the second pass on
+ *     stop when no association changed.  Groups keep their members in ascending position within F.  One node per cluster is appended
+ *     in cluster order (consecutive ids, descriptor = centre, parent = `parent`); then, if level < L, step(child i, group i, level + 1)
+ *     for i = 0, 1, ... where group i has more than one member.  So a node's children have contiguous ids and everything below child 0
+ *     precedes everything below child 1; a node above depth L whose group has at most one member is a leaf.
+ *   mean   bit b of the mean of N >= 1 descriptors is set iff at least N/2 + N%2 of them have it set.
+ *   seeding   the first centre is the feature at a drawn position; min_dist[i] = distance to the closest centre so far; while fewer
+ *     than k centres: S = sum(min_dist) (exact, 64 bits); S == 0 stops (fewer than k children: duplicate features); else with a drawn
+ *     cut in 1..S the next centre is the feature at the first position whose inclusive prefix sum of min_dist is >= cut.
+ *   sampler   DBoW2 seeds DUtils::Random from the clock, so there is nothing to reproduce; here every node has a key —
+ *     key(root) = splitmix64(seed), key(child c of a node with key K) = splitmix64(K ^ (c + 1)), c 0-based — and draw j of the node is
+ *     u_j = splitmix64(K + j * 0x9E3779B97F4A7C15): the first position is u_0 mod |F|, the j-th further centre uses cut = 1 + u_j mod S.
+ *     It does not depend on the order in which nodes are processed.
+ *   deviation 3 (iteration cap)   DBoW2's loop has none and could cycle; here a node runs at most max_iterations association passes
+ *     and keeps the centres and groups of its last pass (report: nodes_capped).
+ *   deviation 4 (emptied cluster)   DBoW2 would take the mean of an empty set; here the cluster keeps its previous centre and ends as a
+ *     childless node no training feature reaches: Ni = 0, weight 0 (report: clusters_emptied, counted over the final groups).
+ *   weights   TF / BINARY: 1.0 per word.  TF_IDF / IDF: every training feature is transformed with the finished tree; Ni[w] = images
+ *     with at least one feature on word w; weight = log((double)nimages / (double)Ni[w]) where Ni > 0, else 0.0, computed on the host
+ *     (glibc's log) from device-counted integers; inner nodes weigh 0.0.  ONE training image therefore gives all-zero weights (size() > 0,
+ *     every BowVector empty): that is DBoW2's behaviour.
+ * report: levels_run = the deepest level that got nodes; max_passes = the most association passes any node ran; nodes_short_seeded =
+ * nodes whose seeding stopped at S == 0.  The result is an ordinary dvs_bow_vocab bound to (device, hip_stream).
+ * DVS_ERR_ARG before any device work: k outside 2..DVS_BOW_MAX_K, L outside 1..DVS_BOW_MAX_L, a negative count, max_iterations < 1, a NULL
+ * array with a non-zero count, a weighting outside 0..3; DVS_ERR_UNSUPPORTED: a scoring other than L1_NORM.  No features at all: an empty
+ * vocabulary and DVS_OK.  The call runs on the caller's stream, creates none, and SYNCHRONISES that stream: convergence is read back
+ * (one word per few passes) and the tree's new nodes once per level.  No floating point on the device. */
+typedef struct { int32_t k, L, weighting, scoring; uint64_t seed; int32_t max_iterations; } dvs_voc_train_params;
+typedef struct { int32_t n_nodes, n_words, levels_run, max_passes, nodes_capped, clusters_emptied, nodes_short_seeded; } dvs_voc_train_report;
+/* k 10, L 5, TF_IDF, L1_NORM (DBoW2's constructor defaults), seed 0, max_iterations 100 */
+dvs_status dvs_voc_train_default_params(dvs_voc_train_params* params);
+/* host rows: desc = all images' rows concatenated, image_counts[nimages]; report may be NULL */
+dvs_status dvs_voc_train(int32_t device, void* hip_stream, const dvs_voc_train_params* params, const uint8_t* desc, const int32_t* image_counts,
+                         int32_t nimages, dvs_bow_vocab** out, dvs_voc_train_report* report);
+/* device-resident frames in the layout of dvs_bow_transform_batch_device (counts clamped to 0..stride_rows, at most 65535 frames): the
+ * extractor's or the tracker's blocks train it in place */
+dvs_status dvs_voc_train_device(int32_t device, void* hip_stream, const dvs_voc_train_params* params, const uint8_t* d_desc, const int32_t* d_n,
+                                int32_t stride_rows, int32_t nframes, dvs_bow_vocab** out, dvs_voc_train_report* report);
+/* any vocabulary back as dvs_bow_vocab_from_arrays takes it: *n_nodes always set; DVS_ERR_CAPACITY, nothing written, if cap < *n_nodes;
+ * each array may be NULL.  Synchronises the vocabulary's stream. */
+dvs_status dvs_voc_get_arrays(const dvs_bow_vocab* voc, int32_t cap, int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight,
+                              int32_t* n_nodes);
+/* TemplatedVocabulary::saveToTextFile in the format dvs_bow_vocab_load_text reads; weights with 17 significant digits (they round-trip) */
+dvs_status dvs_voc_save_text(const dvs_bow_vocab* voc, const char* path);
 
 #ifdef __cplusplus
 }
