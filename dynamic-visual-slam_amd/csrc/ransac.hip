@@ -11,7 +11,9 @@
 // solver: see k_f7_hypotheses below); dvs_find_fundamental_ransac and the PnP stage are the library's own estimators — the reference
 // only consumes the inlier SET (frontend.cpp:640-644, 1149-1153) and the refined pose — over a sampler stated here and in DESIGN.md: sample j of hypothesis h draws r = splitmix64(seed + 0x9E3779B97F4A7C15
 // * (h * 16 + j + 1)) mod (n - j) and takes the r-th index not drawn before (ascending), i.e. a uniform draw without
-// replacement; parity is a tolerance on the inlier set and the pose (tests/test_gpu_ransac.py), not bit equality.
+// replacement; parity of the whole estimator is a tolerance on the inlier set and the pose (tests/test_ransac.py), not bit equality;
+// each stage on its own (hypotheses, score, select, mask / inlier list, refinement) is held to a float64 reference in
+// tests/test_gpu_ransac_stages.py through the dvs_test_*_stages hooks at the end of this file.
 // Minimal solvers: normalised 8-point (null vector by complete-pivoting elimination, rank 2 enforced through the smallest
 // right singular vector) where OpenCV's kernel is the 7-point one; P3P (Grunert's quartic, all <= 4 poses scored) where
 // OpenCV's kernel is 5-point EPnP.  The final pose is refined on the inliers by Levenberg-Marquardt on the reprojection error,
@@ -25,6 +27,7 @@
 #include "common.h"
 #ifdef DVS_TEST_HOOKS
 #include "../../include/dvslam_hip_test.h"
+#include "device_mem.h"
 #endif
 #include "io_pinned.h"
 #include "matcher.h"
@@ -700,13 +703,34 @@ __host__ __device__ __forceinline__ int p3p_solve(const double P[3][3], const do
     roots[b + 1] = key;
   }
   for (int rI = 0; rI < nr && nsol < 4; rI++) {
-    const double v = roots[rI];
+    double v = roots[rI];
     if (!(v > 0) || !isfinite(v)) continue;
     if (rI > 0 && fabs(v - roots[rI - 1]) <= 1e-9 * fabs(v)) continue;   // a double root gives one pose
     const double den = 2 * (cg - v * ca);
     if (fabs(den) < 1e-12) continue;
-    const double u = ((-1 + q) * v * v - 2 * q * cb * v + 1 + q) / den;
+    double u = ((-1 + q) * v * v - 2 * q * cb * v + 1 + q) / den;
     if (!(u > 0) || !isfinite(u)) continue;
+    // (u, v) is a common root of the cosine laws of sides c and a, each divided by the one of side b:
+    //   f1 = 1 + u^2 - 2 u cg - (c2 / b2) m,   f2 = u^2 + v^2 - 2 u v ca - (a2 / b2) m,   m = 1 + v^2 - 2 v cb.
+    // The quartic's root carries the cancellations of its coefficients divided by the distance to the next root (roots 3e-4 apart
+    // left v 5e-10 off and the pose 4e-6 px off its own sample), and u the root's last digits divided by `den` (den = 1e-4 left u 5e-7
+    // off, the pose 2e-4 px).  The pair itself has no such cancellation: where it is not met to rounding, Newton steps on it, each
+    // kept only if it lowers the residual.  A pair that meets it is left as it is, bit for bit.
+    for (int k = 0; k < 3; k++) {
+      const double m = 1 + v * v - 2 * v * cb;
+      const double f1 = 1 + u * u - 2 * u * cg - c2 / b2 * m, f2 = u * u + v * v - 2 * u * v * ca - a2 / b2 * m;
+      const double res = fmax(fabs(f1), fabs(f2));
+      if (!(res > 1e-12 * (1 + u * u + v * v))) break;
+      const double f1u = 2 * (u - cg), f1v = -2 * c2 / b2 * (v - cb), f2u = 2 * (u - v * ca), f2v = 2 * (v - u * ca) - 2 * a2 / b2 * (v - cb);
+      const double det = f1u * f2v - f1v * f2u;
+      if (det == 0.0) break;
+      const double un = u - (f1 * f2v - f1v * f2) / det, vn = v - (f1u * f2 - f2u * f1) / det;
+      const double mn = 1 + vn * vn - 2 * vn * cb;
+      const double g1 = 1 + un * un - 2 * un * cg - c2 / b2 * mn, g2 = un * un + vn * vn - 2 * un * vn * ca - a2 / b2 * mn;
+      if (!(fmax(fabs(g1), fabs(g2)) < res)) break;
+      u = un; v = vn;
+    }
+    if (!(u > 0) || !(v > 0)) continue;
     const double dd = 1 + u * u - 2 * u * cg;
     if (!(dd > 1e-18)) continue;
     const double s1 = sqrt(c2 / dd), s2 = u * s1, s3 = v * s1;
@@ -803,6 +827,38 @@ __device__ __forceinline__ void exp_so3(const double* w, double* E) {
       for (int c = 0; c < 3; c++) kk += K[3 * a + c] * K[3 * c + b];
       E[3 * a + b] = (a == b ? 1.0 : 0.0) + A * K[3 * a + b] + B * kk;
     }
+}
+
+// rotation matrix -> Rodrigues vector, the principal one (|w| <= pi).  The antisymmetric part of R is 2 sin(theta) a and gives the axis a,
+// acos of the trace gives the angle — except where sin(theta) < 1e-4, next to 0 and next to pi.  There acos loses half the digits
+// (a rotation by 1e-9 has a trace of exactly 3 and came out as no rotation at all): the angle is atan2(sin, cos).  And next to pi the
+// antisymmetric part is too small to carry the axis (at pi - 1e-7 its rounding errors are 1e-9 of its length; at pi it is zero): the
+// axis comes from the symmetric part, (R + R^T) / 2 = cos I + (1 - cos) a a^T, whose row of the largest axis component k gives
+// every component WITH its sign relative to a_k; what is left of the antisymmetric part decides between a and -a.  Everywhere else
+// the operations are the ones k_pnp_refine always ran, bit for bit.
+__host__ __device__ __forceinline__ void rotation_to_rodrigues(const double* R, double* w) {
+  const double tr = R[0] + R[4] + R[8];
+  const double cth = fmax(-1.0, fmin(1.0, (tr - 1.0) / 2.0)), th = acos(cth);
+  w[0] = R[7] - R[5]; w[1] = R[2] - R[6]; w[2] = R[3] - R[1];
+  const double sn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) / 2.0;   // sin(theta)
+  const bool flat = sn < 1e-4;
+  if (flat && cth < 0) {
+    const double d[3] = {R[0] - cth, R[4] - cth, R[8] - cth};               // (1 - cos) a_i^2
+    int k = 0;
+    if (d[1] > d[k]) k = 1;
+    if (d[2] > d[k]) k = 2;
+    const double omc = 1.0 - cth, ak = sqrt(fmax(d[k], 0.0) / omc);
+    double a[3];
+    for (int i = 0; i < 3; i++) a[i] = i == k ? ak : (R[3 * k + i] + R[3 * i + k]) / 2.0 / (omc * ak);
+    const double sgn = w[0] * a[0] + w[1] * a[1] + w[2] * a[2] < 0 ? -1.0 : 1.0;
+    const double ang = atan2(sn, cth);
+    for (int i = 0; i < 3; i++) w[i] = sgn * ang * a[i];
+  } else if (sn > 1e-12) {
+    const double f = (flat ? atan2(sn, cth) : th) / (2.0 * sn);
+    for (int k = 0; k < 3; k++) w[k] *= f;
+  } else {   // theta = 0 to rounding
+    for (int k = 0; k < 3; k++) w[k] *= 0.5;
+  }
 }
 
 // inlier mask of the selected pose, then Levenberg-Marquardt on the reprojection error over the inliers (what
@@ -990,20 +1046,8 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
   }
   __syncthreads();
   if (tid == 0) {
-    // rotation matrix -> Rodrigues vector
-    const double tr = sR[0] + sR[4] + sR[8];
-    const double cth = fmax(-1.0, fmin(1.0, (tr - 1.0) / 2.0)), th = acos(cth);
-    double w[3] = {sR[7] - sR[5], sR[2] - sR[6], sR[3] - sR[1]};
-    const double sn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) / 2.0;   // sin(theta)
-    if (sn > 1e-12) {
-      const double f = th / (2.0 * sn);
-      for (int k = 0; k < 3; k++) w[k] *= f;
-    } else if (cth > 0) {
-      for (int k = 0; k < 3; k++) w[k] *= 0.5;
-    } else {  // theta = pi: axis from the diagonal
-      const double ax[3] = {sqrt(fmax((sR[0] + 1) / 2, 0.0)), sqrt(fmax((sR[4] + 1) / 2, 0.0)), sqrt(fmax((sR[8] + 1) / 2, 0.0))};
-      w[0] = th * ax[0]; w[1] = th * ax[1] * (sR[1] >= 0 ? 1 : -1); w[2] = th * ax[2] * (sR[2] >= 0 ? 1 : -1);
-    }
+    double w[3];
+    rotation_to_rodrigues(sR, w);
     for (int k = 0; k < 3; k++) { rt[k] = w[k]; rt[3 + k] = st[k]; }
     *success = m > 0 ? 1 : 0;
   }
@@ -1305,9 +1349,23 @@ int32_t dvs_test_p3p(const double* P9, const double* j9, double* poses48) {
 
 // ---- batches of independent RANSAC problems (one launch sequence for all of them; the single-problem entry points are batches of one) ----
 // problem b = correspondences [offsets[b], offsets[b + 1]) of the concatenated point arrays, sampler seed seeds[b]
-dvs_status dvs_find_fundamental_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
-                                             double confidence, int32_t max_iters, const uint64_t* seeds, double* F9, uint8_t* inlier_mask,
-                                             int32_t* n_inliers) {
+// (the body of dvs_find_fundamental_ransac_batch.  In the test library alone it has one more parameter, `dev`, which receives where the
+// stage arrays of the call lie in the handle's scratch block — all NULL where the call returned before any launch — for
+// dvs_test_fm_stages; the product library's translation unit does not see it)
+#ifdef DVS_TEST_HOOKS
+struct OwnStagesDev { const double* models; const int* valid; const int* counts; const int* sel; };
+#define DVS_STAGES_PARAM , OwnStagesDev* dev
+#define DVS_STAGES_NONE , nullptr
+#define DVS_STAGES_SET(...) do { if (dev) *dev = OwnStagesDev{__VA_ARGS__}; } while (0)
+#else
+#define DVS_STAGES_PARAM
+#define DVS_STAGES_NONE
+#define DVS_STAGES_SET(...) do { } while (0)
+#endif
+static dvs_status fm_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
+                               double confidence, int32_t max_iters, const uint64_t* seeds, double* F9, uint8_t* inlier_mask, int32_t* n_inliers
+                               DVS_STAGES_PARAM) {
+  DVS_STAGES_SET(nullptr, nullptr, nullptr, nullptr);
   DVS_ARG(ctx && nprob >= 0 && max_iters >= 1 && max_iters <= 4096 && threshold > 0);
   if (nprob == 0) return DVS_OK;
   DVS_ARG(offsets && seeds && offsets[0] == 0);
@@ -1342,6 +1400,7 @@ dvs_status dvs_find_fundamental_ransac_batch(dvs_matcher* ctx, int32_t nprob, co
   const int ndw_in = (int)(inb / 4);
   hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
   launch_fm_own(st, nprob, maxn, d_probs, d_p1, d_p2, H, threshold, confidence, d_F, d_valid, d_counts, d_sel, d_mask, d_Fb);
+  DVS_STAGES_SET(d_F, d_valid, d_counts, d_sel);
   uint8_t* hout = hio + inb;
   if (outb <= 65536) {   // small results leave through the export kernel + a polled sequence number (no copy command, no wake-up)
     const int seq = ++*counter;
@@ -1360,6 +1419,11 @@ dvs_status dvs_find_fundamental_ransac_batch(dvs_matcher* ctx, int32_t nprob, co
   }
   if (total) memcpy(inlier_mask, hout + (size_t)nprob * 88, (size_t)total);
   return DVS_OK;
+}
+dvs_status dvs_find_fundamental_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
+                                             double confidence, int32_t max_iters, const uint64_t* seeds, double* F9, uint8_t* inlier_mask,
+                                             int32_t* n_inliers) {
+  return fm_own_batch(ctx, nprob, offsets, pts1, pts2, threshold, confidence, max_iters, seeds, F9, inlier_mask, n_inliers DVS_STAGES_NONE);
 }
 
 // cv::findFundamentalMat(FM_RANSAC) the way OpenCV 4.x runs it (see k_f7_hypotheses): RANSAC from 15 correspondences on, LMedS for 8..14
@@ -1516,9 +1580,10 @@ dvs_status dvs_find_fundamental_ransac(dvs_matcher* ctx, const float* pts1, cons
 }
 
 // inliers: concatenated like the points (problem b's ascending inlier indices at inliers + offsets[b], n_inliers[b] of them)
-dvs_status dvs_solve_pnp_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
-                                      int32_t iterations, double reproj_err, double confidence, const uint64_t* seeds, double* rvec3, double* tvec3,
-                                      int32_t* inliers, int32_t* n_inliers, int32_t* success) {
+static dvs_status pnp_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
+                                int32_t iterations, double reproj_err, double confidence, const uint64_t* seeds, double* rvec3, double* tvec3,
+                                int32_t* inliers, int32_t* n_inliers, int32_t* success DVS_STAGES_PARAM) {   // `dev`: as fm_own_batch's
+  DVS_STAGES_SET(nullptr, nullptr, nullptr, nullptr);
   DVS_ARG(ctx && nprob >= 0 && iterations >= 1 && iterations <= 1024 && K4 && reproj_err > 0);
   if (nprob == 0) return DVS_OK;
   DVS_ARG(offsets && seeds && rvec3 && tvec3 && success && offsets[0] == 0);
@@ -1554,6 +1619,7 @@ dvs_status dvs_solve_pnp_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int
   const int ndw_in = (int)(inb / 4);
   hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
   launch_pnp_own(st, nprob, d_probs, d_obj, d_img, H, K4, reproj_err, confidence, d_poses, d_valid, d_counts, d_sel, d_inl, d_out);
+  DVS_STAGES_SET(d_poses, d_valid, d_counts, d_sel);
   uint8_t* hout = hio + inb;
   if (outb <= 65536) {
     const int seq = ++*counter;
@@ -1575,6 +1641,11 @@ dvs_status dvs_solve_pnp_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int
   }
   return DVS_OK;
 }
+dvs_status dvs_solve_pnp_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
+                                      int32_t iterations, double reproj_err, double confidence, const uint64_t* seeds, double* rvec3, double* tvec3,
+                                      int32_t* inliers, int32_t* n_inliers, int32_t* success) {
+  return pnp_own_batch(ctx, nprob, offsets, pts3d, pts2d, K4, iterations, reproj_err, confidence, seeds, rvec3, tvec3, inliers, n_inliers, success DVS_STAGES_NONE);
+}
 
 dvs_status dvs_solve_pnp_ransac(dvs_matcher* ctx, const float* pts3d, const float* pts2d, int32_t n, const double* K4, int32_t iterations,
                                 double reproj_err, double confidence, uint64_t seed, double* rvec3, double* tvec3, int32_t* inliers,
@@ -1583,5 +1654,87 @@ dvs_status dvs_solve_pnp_ransac(dvs_matcher* ctx, const float* pts3d, const floa
   const int32_t offsets[2] = {0, n};
   return dvs_solve_pnp_ransac_batch(ctx, 1, offsets, pts3d, pts2d, K4, iterations, reproj_err, confidence, &seed, rvec3, tvec3, inliers, n_inliers, success);
 }
+
+#ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h): the stages of the two own estimators, one by one
+// the product call (fm_own_batch: same import, same launches, same grids) and, beside its results, what each stage left on the device
+dvs_status dvs_test_fm_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold, double confidence,
+                              int32_t H, const uint64_t* seeds, double* F_all, int32_t* valid, int32_t* counts, int32_t* sel, uint8_t* mask, double* Fbest) {
+  DVS_ARG(ctx && nprob >= 1 && H >= 1 && offsets && F_all && valid && counts && sel && Fbest);
+  OwnStagesDev dev;
+  DVS_TRY(fm_own_batch(ctx, nprob, offsets, pts1, pts2, threshold, confidence, H, seeds, Fbest, mask, nullptr, &dev));
+  const size_t nh = (size_t)nprob * H;
+  if (!dev.models) {   // no problem had 8 points: nothing ran
+    memset(F_all, 0, nh * 72); memset(valid, 0, nh * 4); memset(counts, 0, nh * 4);
+    for (int b = 0; b < nprob; b++) { sel[4 * b] = -1; sel[4 * b + 1] = sel[4 * b + 2] = sel[4 * b + 3] = 0; }
+    return DVS_OK;
+  }
+  DVS_HIP(hipMemcpy(F_all, dev.models, nh * 72, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(valid, dev.valid, nh * 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(counts, dev.counts, nh * 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(sel, dev.sel, (size_t)nprob * 16, hipMemcpyDeviceToHost));
+  // k_f_hypotheses writes no model for a problem of fewer than 8 points (its `valid` says so): zeros, not what the scratch block held
+  for (int b = 0; b < nprob; b++) if (offsets[b + 1] - offsets[b] < 8) memset(F_all + 9 * (size_t)H * b, 0, (size_t)H * 72);
+  return DVS_OK;
+}
+
+dvs_status dvs_test_pnp_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4, double reproj_err,
+                               double confidence, int32_t H, const uint64_t* seeds, double* poses, int32_t* valid, int32_t* counts, int32_t* sel,
+                               int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
+  DVS_ARG(ctx && nprob >= 1 && H >= 1 && offsets && poses && valid && counts && sel && n_inliers && success && rvec3 && tvec3);
+  OwnStagesDev dev;
+  DVS_TRY(pnp_own_batch(ctx, nprob, offsets, pts3d, pts2d, K4, H, reproj_err, confidence, seeds, rvec3, tvec3, inliers, n_inliers, success, &dev));
+  const size_t nh = (size_t)nprob * 4 * H;
+  if (!dev.models) {   // no problem had 4 points: nothing ran
+    memset(poses, 0, nh * 96); memset(valid, 0, nh * 4); memset(counts, 0, nh * 4);
+    for (int b = 0; b < nprob; b++) { sel[4 * b] = -1; sel[4 * b + 1] = sel[4 * b + 2] = sel[4 * b + 3] = 0; }
+    return DVS_OK;
+  }
+  DVS_HIP(hipMemcpy(poses, dev.models, nh * 96, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(valid, dev.valid, nh * 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(counts, dev.counts, nh * 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(sel, dev.sel, (size_t)nprob * 16, hipMemcpyDeviceToHost));
+  return DVS_OK;
+}
+
+// k_ransac_select alone on counts of the caller's (H of them, H a multiple of `group`), in the own estimators' form
+dvs_status dvs_test_ransac_select(const int32_t* counts, int32_t H, int32_t n, int32_t model_points, double confidence, int32_t group, int32_t* sel4) {
+  DVS_ARG(counts && sel4 && H >= 1 && n >= 1 && model_points >= 1 && group >= 1 && H % group == 0);
+  DeviceBuf<int> dc, ds; DeviceBuf<RansacProb> dp;
+  DVS_TRY(dc.upload(std::vector<int>(counts, counts + H)));
+  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb{0, n, 0ull})));
+  DVS_TRY(ds.alloc(4));
+  hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(1), 0, 0, dc.get(), H, dp.get(), model_points, confidence, group, ds.get(), 0, 0);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipMemcpy(sel4, ds.get(), 16, hipMemcpyDeviceToHost));
+  return DVS_OK;
+}
+
+// k_pnp_refine alone on ONE problem with a pose of the caller's as the selected one (pose12 = R row-major, t; NULL: nothing selected,
+// sel[0] = -1), grid and block as launch_pnp_own's for one problem.  What launch_pnp_own cannot reach: select takes no pose with fewer
+// than 3 inliers, so the kernel's "fewer than 3 inliers: no LM step" path never runs through it.  inliers: room for n indices.
+dvs_status dvs_test_pnp_refine(const float* pts3d, const float* pts2d, int32_t n, const double* K4, const double* pose12, double reproj_err,
+                               int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
+  DVS_ARG(pts3d && pts2d && n >= 1 && K4 && reproj_err > 0 && inliers && n_inliers && success && rvec3 && tvec3);
+  DeviceBuf<float> dobj, dimg; DeviceBuf<RansacProb> dp; DeviceBuf<double> dpose; DeviceBuf<int> dsel, dinl; DeviceBuf<unsigned char> dres;
+  DVS_TRY(dobj.upload(std::vector<float>(pts3d, pts3d + 3 * (size_t)n)));
+  DVS_TRY(dimg.upload(std::vector<float>(pts2d, pts2d + 2 * (size_t)n)));
+  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb{0, n, 0ull})));
+  DVS_TRY(dpose.upload(pose12 ? std::vector<double>(pose12, pose12 + 12) : std::vector<double>(12, 0.0)));
+  DVS_TRY(dsel.upload(std::vector<int>{pose12 ? 0 : -1, 1, 0, 0}));
+  DVS_TRY(dinl.upload(std::vector<int>((size_t)n, -1)));
+  DVS_TRY(dres.alloc(64));
+  hipLaunchKernelGGL(k_pnp_refine, dim3(1), dim3(256), 0, 0, dobj.get(), dimg.get(), dp.get(), 1, dpose.get(), dsel.get(), K4[0], K4[1], K4[2], K4[3],
+                     reproj_err * reproj_err, dinl.get(), dres.get());
+  DVS_HIP(hipGetLastError());
+  unsigned char res[64];
+  DVS_HIP(hipMemcpy(res, dres.get(), 64, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(inliers, dinl.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
+  memcpy(n_inliers, res, 4); memcpy(success, res + 4, 4); memcpy(rvec3, res + 16, 24); memcpy(tvec3, res + 40, 24);
+  return DVS_OK;
+}
+
+// host only (no GPU): the conversion that ends k_pnp_refine
+void dvs_test_rotation_to_rodrigues(const double* R9, double* w3) { rotation_to_rodrigues(R9, w3); }
+#endif  // DVS_TEST_HOOKS
 
 }  // extern "C"

@@ -256,6 +256,11 @@ def test_lib():
     L.dvs_test_sort_nodes_device.argtypes = [vp, vp, i32, vp]; L.dvs_test_sort_nodes_device.restype = C.c_int
     L.dvs_test_quartic_roots.argtypes = [dbl, dbl, dbl, dbl, dbl, vp]
     L.dvs_test_p3p.argtypes = [vp, vp, vp]
+    L.dvs_test_rotation_to_rodrigues.argtypes = [vp, vp]; L.dvs_test_rotation_to_rodrigues.restype = None
+    L.dvs_test_fm_stages.argtypes = [vp, i32, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.dvs_test_pnp_stages.argtypes = [vp, i32, vp, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dvs_test_ransac_select.argtypes = [vp, i32, i32, i32, dbl, i32, vp]
+    L.dvs_test_pnp_refine.argtypes = [vp, vp, i32, vp, vp, dbl, vp, vp, vp, vp, vp]
     L.dvs_test_sincosf.argtypes = [C.c_float, vp, vp]; L.dvs_test_sincosf.restype = None
     L.dvs_test_geometry.argtypes = [C.POINTER(OrbParams), i32, i32, vp, vp, vp, vp, vp, vp]
     L.dvs_test_retain_best_host.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]; L.dvs_test_retain_best_host.restype = None

@@ -24,6 +24,30 @@ void dvs_test_sincosf(float a, float* s, float* c);
 /* the PnP stage's quartic (Ferrari + Newton) and P3P (Grunert) routines on the host: real roots (unordered) / up to 4 poses x 12 */
 int32_t dvs_test_quartic_roots(double a4, double a3, double a2, double a1, double a0, double* roots4);
 int32_t dvs_test_p3p(const double* P9, const double* j9, double* poses48);
+/* the conversion that ends the PnP stage's refinement kernel, on the host: rotation matrix (row-major) -> principal Rodrigues vector */
+void dvs_test_rotation_to_rodrigues(const double* R9, double* w3);
+/* (need a GPU) the library's own robust estimators stage by stage (csrc/ransac.hip; tests/test_gpu_ransac_stages.py).  Each runs the product
+ * call itself — dvs_find_fundamental_ransac_batch / dvs_solve_pnp_ransac_batch with max_iters / iterations = H: the same import, kernels
+ * and grids — and returns, beside its results, what every stage left on the device.  Per problem b of the batch (arguments as the
+ * product calls'):
+ *   fundamental: F_all[b][H][9] and valid[b][H] (hypotheses), counts[b][H] (score), sel[b][4] = {best hypothesis or -1, iterations used,
+ *     inliers of the best, 0} (select), mask[offsets[b] ..] and Fbest[b][9] (the product's outputs);
+ *   PnP: poses[b][4 H][12] (R row-major, t) and valid[b][4 H] (hypothesis 4 h + s = solution s of sample h), counts[b][4 H], sel[b][4],
+ *     and the product's outputs: inlier lists at inliers + offsets[b], n_inliers[b], success[b], rvec3[b][3], tvec3[b][3]. */
+dvs_status dvs_test_fm_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold, double confidence,
+                              int32_t H, const uint64_t* seeds, double* F_all, int32_t* valid, int32_t* counts, int32_t* sel, uint8_t* mask, double* Fbest);
+dvs_status dvs_test_pnp_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4, double reproj_err,
+                               double confidence, int32_t H, const uint64_t* seeds, double* poses, int32_t* valid, int32_t* counts, int32_t* sel,
+                               int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3);
+/* (needs a GPU) the select kernel alone — the sequential RANSAC loop replayed over `counts[H]` with `group` models per iteration, in
+ * the own estimators' form — for a problem of n correspondences: sel4 = {best, iterations used, best count, 0} */
+dvs_status dvs_test_ransac_select(const int32_t* counts, int32_t H, int32_t n, int32_t model_points, double confidence, int32_t group, int32_t* sel4);
+/* (needs a GPU) the PnP refinement kernel alone on one problem, with a pose of the caller's as the selected one (pose12 = R row-major, t;
+ * NULL: nothing selected): inlier scan under reproj_err, LM from 3 inliers on, rotation -> Rodrigues.  Reaches what the estimator cannot:
+ * its select never takes a pose with fewer than 3 inliers.  inliers: room for n indices (entries past n_inliers are -1).
+ * Note on dvs_test_fm_stages: F_all of a problem with fewer than 8 points is zeros (no hypothesis is computed for it). */
+dvs_status dvs_test_pnp_refine(const float* pts3d, const float* pts2d, int32_t n, const double* K4, const double* pose12, double reproj_err,
+                               int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3);
 /* (needs a GPU) hold `stream` for the given time with one idle wavefront (<= 200 000 us): lets a test delay an event */
 dvs_status dvs_test_stream_delay(void* stream, int32_t microseconds);
 /* KeyPointsFilter::retainBest on bare responses: perm[i] = original index of the i-th survivor.  _host: csrc/lsort.h's sequential

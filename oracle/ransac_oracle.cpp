@@ -346,13 +346,30 @@ int p3p(const double P[3][3], const double j[3][3], Pose* out) {
   std::sort(roots, roots + nr);   // canonical solution order (ascending v): ties between equally good poses resolve the same way everywhere
   int ns = 0;
   for (int r = 0; r < nr && ns < 4; r++) {
-    const double v = roots[r];
+    double v = roots[r];
     if (!(v > 0) || !std::isfinite(v)) continue;
     if (r > 0 && std::fabs(v - roots[r - 1]) <= 1e-9 * std::fabs(v)) continue;   // a double root gives one pose
     const double den = 2 * (cg - v * ca);
     if (std::fabs(den) < 1e-12) continue;
-    const double u = ((-1 + q) * v * v - 2 * q * cb * v + 1 + q) / den;
+    double u = ((-1 + q) * v * v - 2 * q * cb * v + 1 + q) / den;
     if (!(u > 0) || !std::isfinite(u)) continue;
+    // (u, v) against the two cosine laws it is the common root of (sides c and a, each divided by side b's): where they are not met to
+    // rounding — a root close to the next one, a small `den` — Newton steps on the pair, each kept only if it lowers the residual
+    for (int k = 0; k < 3; k++) {
+      const double m = 1 + v * v - 2 * v * cb;
+      const double f1 = 1 + u * u - 2 * u * cg - c2 / b2 * m, f2 = u * u + v * v - 2 * u * v * ca - a2 / b2 * m;
+      const double res = std::max(std::fabs(f1), std::fabs(f2));
+      if (!(res > 1e-12 * (1 + u * u + v * v))) break;
+      const double f1u = 2 * (u - cg), f1v = -2 * c2 / b2 * (v - cb), f2u = 2 * (u - v * ca), f2v = 2 * (v - u * ca) - 2 * a2 / b2 * (v - cb);
+      const double det = f1u * f2v - f1v * f2u;
+      if (det == 0.0) break;
+      const double un = u - (f1 * f2v - f1v * f2) / det, vn = v - (f1u * f2 - f2u * f1) / det;
+      const double mn = 1 + vn * vn - 2 * vn * cb;
+      const double g1 = 1 + un * un - 2 * un * cg - c2 / b2 * mn, g2 = un * un + vn * vn - 2 * un * vn * ca - a2 / b2 * mn;
+      if (!(std::max(std::fabs(g1), std::fabs(g2)) < res)) break;
+      u = un; v = vn;
+    }
+    if (!(u > 0) || !(v > 0)) continue;
     const double dd = 1 + u * u - 2 * u * cg;
     if (!(dd > 1e-18)) continue;
     const double s1 = std::sqrt(c2 / dd), s2 = u * s1, s3 = v * s1;
@@ -387,12 +404,25 @@ void rodrigues(const double* w, double* R) {   // cv::Rodrigues, vector -> matri
 void rodriguesInv(const double* R, double* w) {
   const double cth = std::min(1.0, std::max(-1.0, (R[0] + R[4] + R[8] - 1.0) / 2.0)), th = std::acos(cth);
   double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-  const double sn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) / 2.0;
-  if (sn > 1e-12) { for (int k = 0; k < 3; k++) w[k] = v[k] * th / (2.0 * sn); }
-  else if (cth > 0) { for (int k = 0; k < 3; k++) w[k] = v[k] * 0.5; }
-  else {
-    const double ax[3] = {std::sqrt(std::max((R[0] + 1) / 2, 0.0)), std::sqrt(std::max((R[4] + 1) / 2, 0.0)), std::sqrt(std::max((R[8] + 1) / 2, 0.0))};
-    w[0] = th * ax[0]; w[1] = th * ax[1] * (R[1] >= 0 ? 1 : -1); w[2] = th * ax[2] * (R[2] >= 0 ? 1 : -1);
+  const double sn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) / 2.0;   // sin(theta)
+  const bool flat = sn < 1e-4;   // next to 0 and to pi acos loses the angle: atan2(sin, cos)
+  if (flat && cth < 0) {
+    // next to pi the axis comes from the symmetric part, (R + R^T) / 2 = cos I + (1 - cos) a a^T: the row of the largest axis component
+    // gives every component with its sign relative to that one; what is left of the antisymmetric part decides between a and -a
+    const double d[3] = {R[0] - cth, R[4] - cth, R[8] - cth};
+    int k = 0;
+    if (d[1] > d[k]) k = 1;
+    if (d[2] > d[k]) k = 2;
+    const double omc = 1.0 - cth, ak = std::sqrt(std::max(d[k], 0.0) / omc);
+    double a[3];
+    for (int i = 0; i < 3; i++) a[i] = i == k ? ak : (R[3 * k + i] + R[3 * i + k]) / 2.0 / (omc * ak);
+    const double sgn = v[0] * a[0] + v[1] * a[1] + v[2] * a[2] < 0 ? -1.0 : 1.0, ang = std::atan2(sn, cth);
+    for (int i = 0; i < 3; i++) w[i] = sgn * ang * a[i];
+  } else if (sn > 1e-12) {
+    const double f = (flat ? std::atan2(sn, cth) : th) / (2.0 * sn);
+    for (int k = 0; k < 3; k++) w[k] = v[k] * f;
+  } else {
+    for (int k = 0; k < 3; k++) w[k] = v[k] * 0.5;
   }
 }
 
