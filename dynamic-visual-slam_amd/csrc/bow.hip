@@ -358,31 +358,7 @@ struct BowOut {
   int* feat_word; int* feat_node; double* feat_weight;
 };
 
-// a block that grows and keeps its contents (the copy is ordered on `s`, which is drained before the old block is freed)
-template <class T>
-dvs_status grow_keep(DeviceBuf<T>& buf, size_t& cap, size_t need, size_t used, hipStream_t s) {
-  if (need <= cap) return DVS_OK;
-  DeviceBuf<T> bigger;
-  const size_t ncap = need + need / 2;
-  DVS_TRY(bigger.alloc(ncap));
-  if (used) DVS_HIP(hipMemcpyAsync(bigger.get(), buf.get(), used * sizeof(T), hipMemcpyDeviceToDevice, s));
-  DVS_HIP(hipStreamSynchronize(s));
-  buf = std::move(bigger);
-  cap = ncap;
-  return DVS_OK;
-}
-
 }  // namespace
-
-struct dvs_bow_db {
-  dvs_bow_vocab* voc = nullptr;
-  int n_entries = 0;
-  long long nnz_bound = 0;     // no fewer than the words stored (device frames are counted by their rows until the count is read back)
-  size_t cap_off = 0, cap_nnz_w = 0, cap_nnz_v = 0, cap_raw = 0, cap_common = 0, cap_ids = 0, cap_scores = 0;
-  DeviceBuf<long long> off;
-  DeviceBuf<int> words, common, ids, counters;   // counters: [0] entries with a common word, [1] results
-  DeviceBuf<double> values, raw, scores;
-};
 
 namespace {
 
@@ -474,52 +450,6 @@ dvs_status db_reserve(dvs_bow_db* db, int more_entries, long long more_words) {
   return DVS_OK;
 }
 
-dvs_status db_append(dvs_bow_db* db, const uint8_t* d_desc, const int* d_n, int stride_rows, int nframes) {
-  dvs_bow_vocab* v = db->voc;
-  DVS_HIP(hipSetDevice(v->device));
-  DVS_TRY(ensure_scratch(v, nframes, stride_rows));
-  DVS_TRY(db_reserve(db, nframes, (long long)nframes * stride_rows));
-  const BowOut o = own_outputs(v);
-  DVS_TRY(enqueue_transform(v, d_desc, d_n, stride_rows, nframes, 0, o));
-  hipLaunchKernelGGL(k_db_append, dim3(nframes), dim3(kBlock), 0, v->stream, db->n_entries, stride_rows, o.word_ids, o.word_values, o.n_words, db->off.get(),
-                     db->words.get(), db->values.get());
-  DVS_HIP(hipGetLastError());
-  db->n_entries += nframes;
-  db->nnz_bound += (long long)nframes * stride_rows;
-  return DVS_OK;
-}
-
-int query_limit(const dvs_bow_db* db, int max_results, int max_id) {
-  const int admissible = max_id < 0 ? db->n_entries : std::min(max_id, db->n_entries);
-  return max_results > 0 ? std::min(max_results, admissible) : admissible;
-}
-
-// transform + query + selection; results and their count to device memory
-dvs_status db_query(dvs_bow_db* db, const uint8_t* d_desc, const int* d_n, int stride_rows, int max_results, int max_id, int* d_ids, double* d_scores,
-                    int* d_n_results) {
-  dvs_bow_vocab* v = db->voc;
-  hipStream_t s = v->stream;
-  DVS_HIP(hipSetDevice(v->device));
-  if (db->n_entries == 0) { DVS_HIP(hipMemsetAsync(d_n_results, 0, sizeof(int), s)); return DVS_OK; }
-  DVS_TRY(ensure_scratch(v, 1, stride_rows));
-  if ((size_t)db->n_entries > db->cap_raw) {
-    DVS_HIP(hipStreamSynchronize(s));
-    DVS_TRY(grow(db->raw, db->cap_raw, (size_t)db->n_entries));
-    DVS_TRY(grow(db->common, db->cap_common, (size_t)db->n_entries));
-  }
-  const BowOut o = own_outputs(v);
-  DVS_TRY(enqueue_transform(v, d_desc, d_n, stride_rows, 1, 0, o));
-  DVS_HIP(hipMemsetAsync(db->counters.get(), 0, 2 * sizeof(int), s));
-  const int use_lds = stride_rows <= kQueryLdsRows;
-  const int blocks = std::min((db->n_entries + kBlock / 64 - 1) / (kBlock / 64), 4096);
-  hipLaunchKernelGGL(k_db_query, dim3(blocks), dim3(kBlock), use_lds ? (size_t)stride_rows * 12 : 0, s, db->n_entries, max_id, db->off.get(),
-                     db->words.get(), db->values.get(), o.word_ids, o.word_values, o.n_words, use_lds, db->raw.get(), db->common.get(), db->counters.get());
-  hipLaunchKernelGGL(k_db_select, dim3((db->n_entries + kBlock - 1) / kBlock), dim3(kBlock), 0, s, db->n_entries, max_results > 0 ? max_results : 0,
-                     db->raw.get(), db->common.get(), db->counters.get(), d_ids, d_scores, d_n_results);
-  DVS_HIP(hipGetLastError());
-  return DVS_OK;
-}
-
 }  // namespace
 
 // what bow_train.hip builds on (bow_internal.h)
@@ -535,6 +465,97 @@ dvs_status bow_enqueue_descend(const VocabDev& V, const uint8_t* d_desc, const i
   const dim3 gd((stride_rows + kBlock / kGroup - 1) / (kBlock / kGroup), nframes);
   hipLaunchKernelGGL(k_bow_descend, gd, dim3(kBlock), 0, s, V, d_desc, d_n, stride_rows, nid_level, feat_word, feat_node, feat_weight);
   DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+
+dvs_status bow_db_init(dvs_bow_db* db, dvs_bow_vocab* voc) {
+  db->voc = voc;
+  DVS_TRY(db->off.alloc(1025));
+  DVS_TRY(db->counters.alloc(2));
+  DVS_HIP(hipMemsetAsync(db->off.get(), 0, sizeof(long long), voc->stream));
+  db->cap_off = 1025;
+  return DVS_OK;
+}
+
+dvs_status bow_stage_frame(dvs_bow_vocab* v, const uint8_t* desc, int n) { return stage_frame(v, desc, n); }
+
+dvs_status bow_transform_own(dvs_bow_vocab* v, const uint8_t* d_desc, const int* d_n, int stride_rows, int nframes, int levelsup) {
+  DVS_HIP(hipSetDevice(v->device));
+  DVS_TRY(ensure_scratch(v, nframes, stride_rows));
+  return enqueue_transform(v, d_desc, d_n, stride_rows, nframes, levelsup, own_outputs(v));
+}
+
+dvs_status bow_db_add_device(dvs_bow_db* db, const uint8_t* d_desc, const int* d_n, int stride_rows, int nframes, int levelsup) {
+  dvs_bow_vocab* v = db->voc;
+  DVS_HIP(hipSetDevice(v->device));
+  DVS_TRY(ensure_scratch(v, nframes, stride_rows));
+  DVS_TRY(db_reserve(db, nframes, (long long)nframes * stride_rows));
+  const BowOut o = own_outputs(v);
+  DVS_TRY(enqueue_transform(v, d_desc, d_n, stride_rows, nframes, levelsup, o));
+  hipLaunchKernelGGL(k_db_append, dim3(nframes), dim3(kBlock), 0, v->stream, db->n_entries, stride_rows, o.word_ids, o.word_values, o.n_words, db->off.get(),
+                     db->words.get(), db->values.get());
+  DVS_HIP(hipGetLastError());
+  db->n_entries += nframes;
+  db->nnz_bound += (long long)nframes * stride_rows;
+  return DVS_OK;
+}
+
+int bow_query_limit(const dvs_bow_db* db, int max_results, int max_id) {
+  const int admissible = max_id < 0 ? db->n_entries : std::min(max_id, db->n_entries);
+  return max_results > 0 ? std::min(max_results, admissible) : admissible;
+}
+
+// query + selection; results and their count to device memory
+dvs_status bow_db_query_own(dvs_bow_db* db, int stride_rows, int max_results, int max_id, int* d_ids, double* d_scores, int* d_n_results) {
+  dvs_bow_vocab* v = db->voc;
+  hipStream_t s = v->stream;
+  if (db->n_entries == 0) { DVS_HIP(hipMemsetAsync(d_n_results, 0, sizeof(int), s)); return DVS_OK; }
+  if ((size_t)db->n_entries > db->cap_raw) {
+    DVS_HIP(hipStreamSynchronize(s));
+    DVS_TRY(grow(db->raw, db->cap_raw, (size_t)db->n_entries));
+    DVS_TRY(grow(db->common, db->cap_common, (size_t)db->n_entries));
+  }
+  const BowOut o = own_outputs(v);
+  DVS_HIP(hipMemsetAsync(db->counters.get(), 0, 2 * sizeof(int), s));
+  const int use_lds = stride_rows <= kQueryLdsRows;
+  const int blocks = std::min((db->n_entries + kBlock / 64 - 1) / (kBlock / 64), 4096);
+  hipLaunchKernelGGL(k_db_query, dim3(blocks), dim3(kBlock), use_lds ? (size_t)stride_rows * 12 : 0, s, db->n_entries, max_id, db->off.get(),
+                     db->words.get(), db->values.get(), o.word_ids, o.word_values, o.n_words, use_lds, db->raw.get(), db->common.get(), db->counters.get());
+  hipLaunchKernelGGL(k_db_select, dim3((db->n_entries + kBlock - 1) / kBlock), dim3(kBlock), 0, s, db->n_entries, max_results > 0 ? max_results : 0,
+                     db->raw.get(), db->common.get(), db->counters.get(), d_ids, d_scores, d_n_results);
+  DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+
+dvs_status bow_db_query_host(dvs_bow_db* db, const uint8_t* desc, int n, int max_results, int max_id, int levelsup, int* ids, double* scores, int cap,
+                             int* n_results, const char* what) {
+  const int limit = bow_query_limit(db, max_results, max_id);
+  if (cap < limit || (limit > 0 && (!ids || !scores))) {
+    set_error("%s: up to %d results need ids / scores of that capacity (cap %d)", what, limit, cap);
+    return cap < limit ? DVS_ERR_CAPACITY : DVS_ERR_ARG;
+  }
+  *n_results = 0;
+  if (limit == 0) return DVS_OK;
+  dvs_bow_vocab* v = db->voc;
+  hipStream_t s = v->stream;
+  DVS_HIP(hipSetDevice(v->device));
+  if ((size_t)limit > db->cap_ids) {
+    DVS_HIP(hipStreamSynchronize(s));
+    DVS_TRY(grow(db->ids, db->cap_ids, (size_t)limit));
+    DVS_TRY(grow(db->scores, db->cap_scores, (size_t)limit));
+  }
+  DVS_TRY(stage_frame(v, desc, n));
+  DVS_TRY(bow_transform_own(v, v->in_desc.get(), v->in_n.get(), n, 1, levelsup));
+  DVS_TRY(bow_db_query_own(db, n, max_results, max_id, db->ids.get(), db->scores.get(), db->counters.get() + 1));
+  int nr = 0;
+  DVS_HIP(hipMemcpyAsync(&nr, db->counters.get() + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+  DVS_HIP(hipStreamSynchronize(s));
+  if (nr > 0) {
+    DVS_HIP(hipMemcpyAsync(ids, db->ids.get(), sizeof(int) * nr, hipMemcpyDeviceToHost, s));
+    DVS_HIP(hipMemcpyAsync(scores, db->scores.get(), sizeof(double) * nr, hipMemcpyDeviceToHost, s));
+    DVS_HIP(hipStreamSynchronize(s));
+  }
+  *n_results = nr;
   return DVS_OK;
 }
 }  // namespace dvs
@@ -655,12 +676,8 @@ dvs_status dvs_bow_db_create(dvs_bow_vocab* voc, dvs_bow_db** out) {
   *out = nullptr;
   DVS_HIP(hipSetDevice(voc->device));
   dvs_bow_db* db = new dvs_bow_db();
-  db->voc = voc;
-  dvs_status st = db->off.alloc(1025);
-  if (st == DVS_OK) st = db->counters.alloc(2);
-  if (st == DVS_OK && hipMemsetAsync(db->off.get(), 0, sizeof(long long), voc->stream) != hipSuccess) { set_error("dvs_bow_db_create: memset failed"); st = DVS_ERR_HIP; }
+  const dvs_status st = bow_db_init(db, voc);
   if (st != DVS_OK) { delete db; return st; }
-  db->cap_off = 1025;
   *out = db;
   return DVS_OK;
 }
@@ -688,7 +705,7 @@ dvs_status dvs_bow_db_add_device(dvs_bow_db* db, const uint8_t* d_desc, const in
   DVS_ARG((size_t)nframes * ((size_t)stride_rows + 1) < 0x7fffffffu && (long long)db->n_entries + nframes < 0x7fffffff);
   if (first_entry_id_out) *first_entry_id_out = db->n_entries;
   if (nframes == 0) return DVS_OK;
-  return db_append(db, d_desc, d_n, stride_rows, nframes);
+  return bow_db_add_device(db, d_desc, d_n, stride_rows, nframes, 0);
 }
 
 dvs_status dvs_bow_db_add(dvs_bow_db* db, const uint8_t* desc, int32_t n, int32_t* entry_id) {
@@ -697,7 +714,7 @@ dvs_status dvs_bow_db_add(dvs_bow_db* db, const uint8_t* desc, int32_t n, int32_
   DVS_HIP(hipSetDevice(v->device));
   DVS_TRY(stage_frame(v, desc, n));
   const int id = db->n_entries;
-  DVS_TRY(db_append(db, v->in_desc.get(), v->in_n.get(), n, 1));
+  DVS_TRY(bow_db_add_device(db, v->in_desc.get(), v->in_n.get(), n, 1, 0));
   DVS_HIP(hipStreamSynchronize(v->stream));
   if (entry_id) *entry_id = id;
   return DVS_OK;
@@ -707,44 +724,19 @@ dvs_status dvs_bow_db_query_device(dvs_bow_db* db, const uint8_t* d_desc, const 
                                    int32_t max_id, int32_t* d_ids, double* d_scores, int32_t cap, int32_t* d_n_results) {
   DVS_ARG(db && d_n && stride_rows >= 0 && (stride_rows == 0 || d_desc) && cap >= 0 && d_n_results && max_id >= -1);
   DVS_ARG(((uintptr_t)d_desc & 15) == 0);
-  const int limit = query_limit(db, max_results, max_id);
+  const int limit = bow_query_limit(db, max_results, max_id);
   if (cap < limit || (limit > 0 && (!d_ids || !d_scores))) {
     set_error("dvs_bow_db_query_device: up to %d results need ids / scores of that capacity (cap %d)", limit, cap);
     return cap < limit ? DVS_ERR_CAPACITY : DVS_ERR_ARG;
   }
-  return db_query(db, d_desc, d_n, stride_rows, max_results, max_id, d_ids, d_scores, d_n_results);
+  if (db->n_entries > 0) DVS_TRY(bow_transform_own(db->voc, d_desc, d_n, stride_rows, 1, 0));   // an empty database: the count alone
+  return bow_db_query_own(db, stride_rows, max_results, max_id, d_ids, d_scores, d_n_results);
 }
 
 dvs_status dvs_bow_db_query(dvs_bow_db* db, const uint8_t* desc, int32_t n, int32_t max_results, int32_t max_id, int32_t* ids, double* scores,
                             int32_t cap, int32_t* n_results) {
   DVS_ARG(db && n >= 0 && (n == 0 || desc) && cap >= 0 && n_results && max_id >= -1);
-  const int limit = query_limit(db, max_results, max_id);
-  if (cap < limit || (limit > 0 && (!ids || !scores))) {
-    set_error("dvs_bow_db_query: up to %d results need ids / scores of that capacity (cap %d)", limit, cap);
-    return cap < limit ? DVS_ERR_CAPACITY : DVS_ERR_ARG;
-  }
-  *n_results = 0;
-  if (limit == 0) return DVS_OK;
-  dvs_bow_vocab* v = db->voc;
-  hipStream_t s = v->stream;
-  DVS_HIP(hipSetDevice(v->device));
-  if ((size_t)limit > db->cap_ids) {
-    DVS_HIP(hipStreamSynchronize(s));
-    DVS_TRY(grow(db->ids, db->cap_ids, (size_t)limit));
-    DVS_TRY(grow(db->scores, db->cap_scores, (size_t)limit));
-  }
-  DVS_TRY(stage_frame(v, desc, n));
-  DVS_TRY(db_query(db, v->in_desc.get(), v->in_n.get(), n, max_results, max_id, db->ids.get(), db->scores.get(), db->counters.get() + 1));
-  int nr = 0;
-  DVS_HIP(hipMemcpyAsync(&nr, db->counters.get() + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-  DVS_HIP(hipStreamSynchronize(s));
-  if (nr > 0) {
-    DVS_HIP(hipMemcpyAsync(ids, db->ids.get(), sizeof(int) * nr, hipMemcpyDeviceToHost, s));
-    DVS_HIP(hipMemcpyAsync(scores, db->scores.get(), sizeof(double) * nr, hipMemcpyDeviceToHost, s));
-    DVS_HIP(hipStreamSynchronize(s));
-  }
-  *n_results = nr;
-  return DVS_OK;
+  return bow_db_query_host(db, desc, n, max_results, max_id, 0, ids, scores, cap, n_results, "dvs_bow_db_query");
 }
 
 dvs_status dvs_bow_db_get_entry(dvs_bow_db* db, int32_t id, int32_t* word_ids, double* word_values, int32_t cap, int32_t* n) {

@@ -14,3 +14,4 @@ from .cvorb import CvORB  # noqa: F401
 from .tracker import Tracker, TrackerParams, TrackResult  # noqa: F401
 from .backend import MappingBackend  # noqa: F401
 from .bow import OrbVocabulary, OrbDatabase  # noqa: F401
+from .loop import LoopDatabase  # noqa: F401

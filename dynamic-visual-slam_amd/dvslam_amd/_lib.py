@@ -49,6 +49,10 @@ class VocTrainParams(C.Structure):
                 ("max_iterations", C.c_int32)]
 
 
+class LoopMatchParams(C.Structure):
+    _fields_ = [("max_distance", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32)]
+
+
 class VocTrainReport(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_words", "levels_run", "max_passes", "nodes_capped", "clusters_emptied", "nodes_short_seeded")]
 
@@ -191,6 +195,24 @@ def _bind(L):
         L.dvs_voc_train_device.argtypes = [i32, vp, C.POINTER(VocTrainParams), vp, vp, i32, i32, C.POINTER(vp), C.POINTER(VocTrainReport)]
         L.dvs_voc_get_arrays.argtypes = [vp, i32, vp, vp, vp, vp, pi32]
         L.dvs_voc_save_text.argtypes = [vp, C.c_char_p]
+    if hasattr(L, "dvs_loop_db_create"):   # loop candidates (dvslam_amd/loop.py)
+        pi32, pp = C.POINTER(i32), C.POINTER(LoopMatchParams)
+        L.dvs_loop_match_default_params.argtypes = [pp]
+        L.dvs_loop_db_create.argtypes = [vp, i32, C.POINTER(vp)]
+        L.dvs_loop_db_destroy.argtypes = [vp]; L.dvs_loop_db_destroy.restype = None
+        L.dvs_loop_db_clear.argtypes = [vp]
+        L.dvs_loop_db_size.argtypes = [vp]; L.dvs_loop_db_size.restype = i32
+        L.dvs_loop_db_di_levels.argtypes = [vp]; L.dvs_loop_db_di_levels.restype = i32
+        L.dvs_loop_db_add.argtypes = [vp, vp, i32, pi32]
+        L.dvs_loop_db_add_device.argtypes = [vp, vp, vp, i32, i32, pi32]
+        L.dvs_loop_db_query.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, pi32]
+        L.dvs_loop_db_query_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
+        L.dvs_loop_db_get_features.argtypes = [vp, i32, vp, vp, vp, i32, i32, pi32, pi32]
+        L.dvs_loop_db_get_descriptors.argtypes = [vp, i32, vp, i32, pi32]
+        L.dvs_loop_db_match.argtypes = [vp, vp, i32, vp, i32, pp, vp, vp, vp]
+        L.dvs_loop_db_match_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, pp, vp, vp, vp]
+        L.dvs_loop_db_detect.argtypes = [vp, vp, i32, i32, i32, pp, vp, vp, vp, vp, vp, i32, pi32]
+        L.dvs_loop_db_detect_device.argtypes = [vp, vp, vp, i32, i32, i32, pp, vp, vp, vp, vp, vp, i32, vp]
 
 
 def _bind_hooks(L):

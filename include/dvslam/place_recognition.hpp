@@ -5,7 +5,8 @@
 //   plain layer    features as `const uint8_t* rows, int n` (n x 32 bytes) or std::vector<std::array<uint8_t, 32>>; needs only the C-ABI
 //   OpenCV layer   std::vector<cv::Mat> features (one 1 x 32 CV_8U row each), compiled only when DVSLAM_WITH_OPENCV is defined
 // Semantics, the deviations (early-leaf node id, (raw, id) result order; training: iteration cap, emptied cluster, the stated sampler)
-// and what is not built (scorings other than L1, the direct index): INTEGRATION.md "Place recognition".  Errors throw
+// and what is not built (scorings other than L1): INTEGRATION.md "Place recognition".  The direct index is dvslam::LoopDatabase
+// (loop_detection.hpp); OrbDatabase stays the database without one.  Errors throw
 // std::runtime_error, as DBoW2 throws on a file it cannot read.
 #pragma once
 #include <array>

@@ -770,8 +770,9 @@ dvs_status dvs_backend_get_keyframes(dvs_backend* h, int32_t cap, int64_t cap_ob
  * A frame's BowVector: features whose weight is not > 0 contribute nothing; TF_IDF / TF: v[word] += weight in feature order (a repeated
  * addition, ((w + w) + w) + ..., not count * w); IDF / BINARY: v[word] = weight; then every value is divided by the L1 norm, summed
  * sequentially in ascending word id, if that is > 0.  Its FeatureVector: node id -> ascending feature indices, as CSR.
- * Only scoring 0 (L1_NORM, DBoW2's and ORBvoc.txt's default) is built: any other is DVS_ERR_UNSUPPORTED.  Not built either: the
- * direct index (use_di).  vocabulary.create() (test_dbow2_integration.cpp:158) is dvs_voc_train below.
+ * Only scoring 0 (L1_NORM, DBoW2's and ORBvoc.txt's default) is built: any other is DVS_ERR_UNSUPPORTED.  The direct index
+ * (use_di) is the "loop candidates" block below, a handle of its own (dvs_loop_db).  vocabulary.create()
+ * (test_dbow2_integration.cpp:158) is dvs_voc_train below.
  * A vocabulary handle enqueues on the caller's hipStream_t (NULL: the legacy default stream), as dvs_matcher_create_on_stream; it
  * creates no stream.  A database borrows its vocabulary (stream and scratch): the vocabulary must outlive it, and the two are one
  * handle as far as threads are concerned. */
@@ -887,6 +888,86 @@ dvs_status dvs_voc_get_arrays(const dvs_bow_vocab* voc, int32_t cap, int32_t* pa
                               int32_t* n_nodes);
 /* TemplatedVocabulary::saveToTextFile in the format dvs_bow_vocab_load_text reads; weights with 17 significant digits (they round-trip) */
 dvs_status dvs_voc_save_text(const dvs_bow_vocab* voc, const char* path);
+
+/* ----------------------- loop candidates: a keyframe database with a direct index, and node-guided matching ----------------------
+ * What a loop detector does between database.query() and its robust estimators (dvs_find_fundamental_*, dvs_solve_pnp_ransac_*):
+ * correspondences between the new keyframe and each candidate, compared only inside the vocabulary node two features share
+ * (csrc/loop.hip; INTEGRATION.md "Loop candidates").  Neither DBoW2's direct index nor any loop detector is a reference interface this
+ * project can pin: the FeatureVector an entry keeps is DBoW2's (retrieveFeatures), the MATCHING RULE below is this library's own,
+ * stated in full and independent of any processing order, as the sampler of dvs_voc_train is.  Integers only: results are bit-exact
+ * (tests/loop_ref.py is the sequential restatement).
+ *
+ * Direct index.  A database is created over a vocabulary with di_levels >= 0.  add runs ONE transform of the frame at levelsup =
+ * di_levels; the BowVector does not depend on levelsup, so the stored entry and every query result are those of dvs_bow_db_add / query
+ * (the same kernels).  The entry also keeps its FeatureVector (node id -> ascending feature indices, exactly what dvs_bow_transform
+ * returns: features whose word weight is not > 0 are absent, deviation 1 applies, di_levels >= L puts every feature under node 0) and
+ * all n descriptor rows of the frame, so feature indices stay frame indices.  Everything stays on the device.
+ *
+ * Guided match of a query frame Q (n rows) against entry e with (max_distance, ratio_num, ratio_den): for every node present in both
+ * FeatureVectors (both at levelsup = di_levels) and every query feature i under it, over the entry's features j under the same node in
+ * ascending j: d1 = the smallest Hamming distance, j1 = the lowest j that attains it, d2 = the smallest distance among j != j1 (256
+ * when the node holds one entry feature).  i PROPOSES (j1, d1) iff d1 <= max_distance and d1 * ratio_den <= d2 * ratio_num.  Among the
+ * query features that propose the same j the one with the smallest (d1, i) keeps it, the others are unmatched.  (An entry feature lies
+ * under exactly one node, so conflicts never cross nodes.)  Output per candidate c and row i < stride_rows: train_idx = j or -1,
+ * dist = d1 or INT32_MAX; rows i >= n are written as unmatched; n_matches[c] = the candidate's count.  An entry id outside [0, size)
+ * gives n_matches[c] = -1 and all rows unmatched in the device forms, DVS_ERR_ARG before any device work in the host form.  The same
+ * id may appear twice in a candidate list: each occurrence gets the same answer.
+ * Parameters, not constants: the defaults are max_distance 50 and ratio 3/4, the values guided ORB matchers usually run with (quoted
+ * from memory, not pinned to any library).  DVS_ERR_ARG: max_distance outside 0..256, ratio_den outside 1..32767, ratio_num outside
+ * 0..32767.  A NULL params pointer means the defaults.  One call matches at most 65535 candidates (n_cand, cap_cand, or the most
+ * results detect's query can give: more is DVS_ERR_ARG), and candidates x max(rows of the frame, rows of the longest entry) must stay
+ * below 2^31.
+ *
+ * The handle borrows its vocabulary's stream and scratch as dvs_bow_db does: the vocabulary must outlive it, and the two are one handle
+ * as far as threads are concerned.  NULL handles are DVS_ERR_ARG, capacity checks come before any device work, and there is no CPU
+ * fallback (a vocabulary cannot be created without a device: DVS_ERR_NO_DEVICE). */
+typedef struct dvs_loop_db dvs_loop_db;
+typedef struct { int32_t max_distance, ratio_num, ratio_den; } dvs_loop_match_params;
+dvs_status dvs_loop_match_default_params(dvs_loop_match_params* p);   /* 50, 3, 4 */
+/* TemplatedDatabase(voc, use_di = true, di_levels) */
+dvs_status dvs_loop_db_create(dvs_bow_vocab* voc, int32_t di_levels, dvs_loop_db** out);
+void dvs_loop_db_destroy(dvs_loop_db* db);
+dvs_status dvs_loop_db_clear(dvs_loop_db* db);            /* no entries, the next id is 0; the blocks keep their size */
+int32_t dvs_loop_db_size(const dvs_loop_db* db);          /* 0 for NULL */
+int32_t dvs_loop_db_di_levels(const dvs_loop_db* db);     /* getDirectIndexLevels; -1 for NULL */
+/* database.add(features): entry *entry_id = size() with its BowVector, FeatureVector and rows.  Synchronises. */
+dvs_status dvs_loop_db_add(dvs_loop_db* db, const uint8_t* desc, int32_t n, int32_t* entry_id);
+/* nframes device-resident frames in the layout of dvs_bow_transform_batch_device become entries *first_entry_id + f.  The host does
+ * not know d_n: it reserves stride_rows rows per frame (the true counts are read back before a block grows).  Asynchronous. */
+dvs_status dvs_loop_db_add_device(dvs_loop_db* db, const uint8_t* d_desc, const int32_t* d_n, int32_t stride_rows, int32_t nframes,
+                                  int32_t* first_entry_id);
+/* dvs_bow_db_query / dvs_bow_db_query_device: the same arguments, the same results, the same kernels */
+dvs_status dvs_loop_db_query(dvs_loop_db* db, const uint8_t* desc, int32_t n, int32_t max_results, int32_t max_id, int32_t* ids, double* scores,
+                             int32_t cap, int32_t* n_results);
+dvs_status dvs_loop_db_query_device(dvs_loop_db* db, const uint8_t* d_desc, const int32_t* d_n, int32_t stride_rows, int32_t max_results,
+                                    int32_t max_id, int32_t* d_ids, double* d_scores, int32_t cap, int32_t* d_n_results);
+/* TemplatedDatabase::retrieveFeatures(id) as CSR: fv_nodes (ascending; cap_nodes entries), fv_offsets (cap_nodes + 1 entries),
+ * fv_features (cap_features entries), each nullable.  Count-then-capacity: *n_nodes and *n_features are always set; DVS_ERR_CAPACITY,
+ * nothing written, if one exceeds its capacity. */
+dvs_status dvs_loop_db_get_features(dvs_loop_db* db, int32_t id, int32_t* fv_nodes, int32_t* fv_offsets, int32_t* fv_features, int32_t cap_nodes,
+                                    int32_t cap_features, int32_t* n_nodes, int32_t* n_features);
+/* read-back of entry `id`'s rows for tests and adapters: *n always set; DVS_ERR_CAPACITY, nothing written, if cap_rows < *n */
+dvs_status dvs_loop_db_get_descriptors(dvs_loop_db* db, int32_t id, uint8_t* desc, int32_t cap_rows, int32_t* n);
+/* guided match of one host frame against n_cand entries (host ids): train_idx / dist are [n_cand][n], n_matches [n_cand].  Synchronises. */
+dvs_status dvs_loop_db_match(dvs_loop_db* db, const uint8_t* desc, int32_t n, const int32_t* entry_ids, int32_t n_cand,
+                             const dvs_loop_match_params* params, int32_t* train_idx, int32_t* dist, int32_t* n_matches);
+/* the same with everything on the device: rows [0, *d_n) of d_desc (16-byte aligned, stride_rows rows allocated), candidates
+ * d_entry_ids[0, *d_n_cand) with *d_n_cand clamped to 0..cap_cand — the ids / count dvs_loop_db_query_device wrote feed it with nothing
+ * crossing to the host.  Outputs d_train_idx / d_dist [cap_cand][stride_rows], d_n_matches [cap_cand]; blocks c >= *d_n_cand are
+ * written as unmatched with n_matches 0.  Asynchronous. */
+dvs_status dvs_loop_db_match_device(dvs_loop_db* db, const uint8_t* d_desc, const int32_t* d_n, int32_t stride_rows, const int32_t* d_entry_ids,
+                                    const int32_t* d_n_cand, int32_t cap_cand, const dvs_loop_match_params* params, int32_t* d_train_idx,
+                                    int32_t* d_dist, int32_t* d_n_matches);
+/* ONE transform of the frame, the query (max_results, max_id as in dvs_loop_db_query: max_id excludes recent keyframes), then the guided
+ * match of the results, all in one enqueue; one read-back returns ids / scores / n_matches [*n_results] and train_idx / dist
+ * [*n_results][n] (arrays of cap and cap * n entries; cap below the most results the query can give is DVS_ERR_CAPACITY). */
+dvs_status dvs_loop_db_detect(dvs_loop_db* db, const uint8_t* desc, int32_t n, int32_t max_results, int32_t max_id,
+                              const dvs_loop_match_params* params, int32_t* ids, double* scores, int32_t* n_matches, int32_t* train_idx,
+                              int32_t* dist, int32_t cap, int32_t* n_results);
+/* the same on device pointers: d_ids / d_scores / d_n_matches [cap], d_train_idx / d_dist [cap][stride_rows], *d_n_results.  Asynchronous. */
+dvs_status dvs_loop_db_detect_device(dvs_loop_db* db, const uint8_t* d_desc, const int32_t* d_n, int32_t stride_rows, int32_t max_results,
+                                     int32_t max_id, const dvs_loop_match_params* params, int32_t* d_ids, double* d_scores, int32_t* d_n_matches,
+                                     int32_t* d_train_idx, int32_t* d_dist, int32_t cap, int32_t* d_n_results);
 
 #ifdef __cplusplus
 }
