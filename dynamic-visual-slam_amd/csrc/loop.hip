@@ -8,12 +8,14 @@
 //                    are staged through LDS in tiles of kMatchTileRows rows; per query feature a running (d1, j1, d2); a proposal does
 //                    atomicMin(d1 << 32 | i) on its entry feature's slot
 //   k_loop_resolve   a proposal stays where its i won the slot; the candidate's count
+//   k_loop_set_points  an entry's 3D points (the block loop_verify.hip reads) copied from a batch in add_device's layout
 // The minimum of a set does not depend on the order of arrival, so the result is the same under any schedule.
 #include <limits.h>
 #include <vector>
 #include "common.h"
 #include "device_mem.h"
 #include "bow_internal.h"
+#include "loop_internal.h"
 
 namespace {
 using namespace dvs;
@@ -163,23 +165,17 @@ __global__ __launch_bounds__(kBlock) void k_loop_resolve(int n_entries, int stri
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&n_matches[c], __popcll(bal));
 }
 
-}  // namespace
+// frame f's points (rows f * stride_rows ... of d_xyz) become the points of entry first + f: no more rows than the entry has
+__global__ __launch_bounds__(kBlock) void k_loop_set_points(int first, int stride_rows, const float* __restrict__ d_xyz, const int* __restrict__ d_n,
+                                                            const long long* __restrict__ row_off, float* __restrict__ o_xyz) {
+  const int f = blockIdx.x;
+  const long long o = row_off[first + f], rows = row_off[first + f + 1] - o;
+  const size_t n3 = 3 * (size_t)min((long long)min(max(d_n[f], 0), stride_rows), rows);
+  const float* src = d_xyz + 3 * (size_t)f * stride_rows;
+  for (size_t r = threadIdx.x; r < n3; r += kBlock) o_xyz[3 * o + r] = src[r];
+}
 
-struct dvs_loop_db {
-  dvs_bow_db inv;              // the inverted part: bow.hip's, through bow_internal.h
-  int di_levels = 0;
-  long long rows_bound = 0;    // no fewer than the rows stored (device frames count as stride_rows until the count is read back)
-  int max_stride = 0;          // the longest frame ever reserved: the width of a candidate's winner column
-  size_t cap_e_off = 0, cap_e_nn = 0, cap_e_m = 0, cap_desc = 0, cap_nodes = 0, cap_start = 0, cap_feat = 0;
-  size_t cap_keys = 0, cap_cand_ids = 0, cap_out_t = 0, cap_out_d = 0, cap_out_n = 0;
-  DeviceBuf<long long> row_off;
-  DeviceBuf<int> e_nn, e_m, fv_nodes, fv_start, fv_feat;
-  DeviceBuf<uint4> desc;       // two per row
-  DeviceBuf<unsigned long long> keys;   // [candidates][max_stride]: the smallest (d1 << 32 | i) that proposed entry feature j
-  DeviceBuf<int> cand_ids;     // the host forms' candidate list: [0] the count, then the ids
-  DeviceBuf<int> out_train, out_dist, out_n;   // the host forms' outputs
-  std::vector<int> h_cand;
-};
+}  // namespace
 
 namespace {
 
@@ -198,7 +194,11 @@ dvs_status loop_reserve(dvs_loop_db* db, int more_entries, long long more_rows) 
     DVS_TRY(grow_keep(db->desc, db->cap_desc, 2 * want, 2 * (size_t)rows, s));
     DVS_TRY(grow_keep(db->fv_nodes, db->cap_nodes, want, (size_t)rows, s));
     DVS_TRY(grow_keep(db->fv_start, db->cap_start, want, (size_t)rows, s));
-    DVS_TRY(grow_keep(db->fv_feat, db->cap_feat, want, (size_t)rows, s));
+    const size_t xyz_before = db->cap_xyz;
+    DVS_TRY(grow_keep(db->xyz, db->cap_xyz, 3 * want, 3 * (size_t)rows, s));
+    if (db->cap_xyz != xyz_before)                // rows nobody gave points hold NaN (every byte 0xff)
+      DVS_HIP(hipMemsetAsync(db->xyz.get() + 3 * (size_t)rows, 0xff, (db->cap_xyz - 3 * (size_t)rows) * sizeof(float), s));
+    DVS_TRY(grow_keep(db->fv_feat, db->cap_feat, want, (size_t)rows, s));   // last: its capacity is the condition above
   }
   return DVS_OK;
 }
@@ -315,6 +315,10 @@ dvs_status dvs_loop_db_clear(dvs_loop_db* db) {
   db->inv.n_entries = 0;       // both offset blocks keep their leading 0
   db->inv.nnz_bound = 0;
   db->rows_bound = 0;
+  if (db->cap_xyz) {           // the points are forgotten with the entries: every row reads as "no point" again
+    DVS_HIP(hipSetDevice(db->inv.voc->device));
+    DVS_HIP(hipMemsetAsync(db->xyz.get(), 0xff, db->cap_xyz * sizeof(float), db->inv.voc->stream));
+  }
   return DVS_OK;
 }
 
@@ -401,6 +405,50 @@ dvs_status dvs_loop_db_get_descriptors(dvs_loop_db* db, int32_t id, uint8_t* des
   return DVS_OK;
 }
 
+dvs_status dvs_loopv_db_set_points(dvs_loop_db* db, int32_t entry_id, const float* xyz, int32_t n) {
+  DVS_ARG(db && n >= 0 && (n == 0 || xyz) && entry_id >= 0 && entry_id < db->inv.n_entries);
+  hipStream_t s = db->inv.voc->stream;
+  DVS_HIP(hipSetDevice(db->inv.voc->device));
+  long long be[2] = {0, 0};
+  DVS_HIP(hipMemcpyAsync(be, db->row_off.get() + entry_id, sizeof(be), hipMemcpyDeviceToHost, s));
+  DVS_HIP(hipStreamSynchronize(s));
+  if (be[1] - be[0] != n) {
+    set_error("dvs_loopv_db_set_points: entry %d has %lld rows, %d points given", entry_id, be[1] - be[0], n);
+    return DVS_ERR_ARG;
+  }
+  if (n > 0) DVS_HIP(hipMemcpyAsync(db->xyz.get() + 3 * be[0], xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  DVS_HIP(hipStreamSynchronize(s));
+  return DVS_OK;
+}
+
+dvs_status dvs_loopv_db_set_points_device(dvs_loop_db* db, int32_t first_entry_id, const float* d_xyz, const int32_t* d_n, int32_t stride_rows,
+                                         int32_t nframes) {
+  DVS_ARG(db && nframes >= 0 && stride_rows >= 0 && (nframes == 0 || d_n) && (nframes == 0 || stride_rows == 0 || d_xyz));
+  DVS_ARG(first_entry_id >= 0 && (long long)first_entry_id + nframes <= db->inv.n_entries);
+  DVS_ARG((size_t)nframes * ((size_t)stride_rows + 1) < 0x7fffffffu);
+  if (nframes == 0 || stride_rows == 0) return DVS_OK;
+  DVS_HIP(hipSetDevice(db->inv.voc->device));
+  hipLaunchKernelGGL(k_loop_set_points, dim3(nframes), dim3(kBlock), 0, db->inv.voc->stream, first_entry_id, stride_rows, d_xyz, d_n, db->row_off.get(),
+                     db->xyz.get());
+  DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+
+dvs_status dvs_loopv_db_get_points(dvs_loop_db* db, int32_t id, float* xyz, int32_t cap_rows, int32_t* n) {
+  DVS_ARG(db && n && cap_rows >= 0 && id >= 0 && id < db->inv.n_entries);
+  hipStream_t s = db->inv.voc->stream;
+  DVS_HIP(hipSetDevice(db->inv.voc->device));
+  long long be[2] = {0, 0};
+  DVS_HIP(hipMemcpyAsync(be, db->row_off.get() + id, sizeof(be), hipMemcpyDeviceToHost, s));
+  DVS_HIP(hipStreamSynchronize(s));
+  const long long cnt = be[1] - be[0];
+  *n = (int32_t)cnt;
+  if (cnt > cap_rows) { set_error("dvs_loopv_db_get_points: entry %d has %lld rows (cap %d)", id, cnt, cap_rows); return DVS_ERR_CAPACITY; }
+  if (cnt > 0 && xyz) DVS_HIP(hipMemcpyAsync(xyz, db->xyz.get() + 3 * be[0], (size_t)cnt * 12, hipMemcpyDeviceToHost, s));
+  DVS_HIP(hipStreamSynchronize(s));
+  return DVS_OK;
+}
+
 dvs_status dvs_loop_db_match_device(dvs_loop_db* db, const uint8_t* d_desc, const int32_t* d_n, int32_t stride_rows, const int32_t* d_entry_ids,
                                     const int32_t* d_n_cand, int32_t cap_cand, const dvs_loop_match_params* params, int32_t* d_train_idx,
                                     int32_t* d_dist, int32_t* d_n_matches) {
@@ -466,19 +514,23 @@ dvs_status dvs_loop_db_detect_device(dvs_loop_db* db, const uint8_t* d_desc, con
   return enqueue_match(db, d_desc, stride_rows, d_ids, d_n_results, limit, P, d_train_idx, d_dist, d_n_matches);
 }
 
-dvs_status dvs_loop_db_detect(dvs_loop_db* db, const uint8_t* desc, int32_t n, int32_t max_results, int32_t max_id,
-                              const dvs_loop_match_params* params, int32_t* ids, double* scores, int32_t* n_matches, int32_t* train_idx,
-                              int32_t* dist, int32_t cap, int32_t* n_results) {
+// dvs_loop_db_detect and dvs_loopv_db_detect_verify: one enqueue, one read-back; the verification (VP != NULL) reads the match where it
+// lies and adds its records and masks to the same read-back
+static dvs_status detect_host(dvs_loop_db* db, const uint8_t* desc, const float* xyz, int32_t n, int32_t max_results, int32_t max_id,
+                              const dvs_loop_match_params* params, const dvs_loop_verify_params* VP, int32_t* ids, double* scores, int32_t* n_matches,
+                              int32_t* train_idx, int32_t* dist, dvs_loop_verify_result* results, uint8_t* inlier_mask, int32_t cap, int32_t* n_results,
+                              const char* what) {
   DVS_ARG(db && n >= 0 && (n == 0 || desc) && cap >= 0 && n_results && max_id >= -1);
   dvs_loop_match_params P;
   DVS_TRY(check_params(params, &P));
   const int limit = bow_query_limit(&db->inv, max_results, max_id);
   if (cap < limit) {
-    set_error("dvs_loop_db_detect: up to %d results need outputs of that capacity (cap %d)", limit, cap);
+    set_error("%s: up to %d results need outputs of that capacity (cap %d)", what, limit, cap);
     return DVS_ERR_CAPACITY;
   }
   DVS_ARG(limit == 0 || (ids && scores && n_matches && (n == 0 || (train_idx && dist))));
   DVS_ARG((size_t)limit * std::max((size_t)n, (size_t)db->max_stride) < 0x7fffffffu && limit <= 65535);
+  if (VP) DVS_ARG(limit == 0 || (results && (n == 0 || (xyz && inlier_mask))));
   *n_results = 0;
   if (limit == 0) return DVS_OK;
   dvs_bow_db* inv = &db->inv;
@@ -486,6 +538,10 @@ dvs_status dvs_loop_db_detect(dvs_loop_db* db, const uint8_t* desc, int32_t n, i
   hipStream_t s = v->stream;
   DVS_HIP(hipSetDevice(v->device));
   DVS_TRY(host_outputs(db, (size_t)limit, (size_t)n));
+  if (VP) {
+    DVS_TRY(loop_verify_reserve(db, limit, n, VP->iterations));
+    DVS_TRY(loop_verify_host_blocks(db, (size_t)limit, (size_t)n, false));
+  }
   if ((size_t)limit > inv->cap_ids) {
     DVS_HIP(hipStreamSynchronize(s));
     DVS_TRY(grow(inv->ids, inv->cap_ids, (size_t)limit));
@@ -494,10 +550,14 @@ dvs_status dvs_loop_db_detect(dvs_loop_db* db, const uint8_t* desc, int32_t n, i
   DVS_HIP(hipMemsetAsync(inv->ids.get(), 0, sizeof(int) * limit, s));          // what lies past the result count reads as zeros
   DVS_HIP(hipMemsetAsync(inv->scores.get(), 0, sizeof(double) * limit, s));
   DVS_TRY(bow_stage_frame(v, desc, n));
+  if (VP && n > 0) DVS_HIP(hipMemcpyAsync(db->v_in_xyz.get(), xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
   DVS_TRY(bow_transform_own(v, v->in_desc.get(), v->in_n.get(), n, 1, db->di_levels));
   int* d_nr = inv->counters.get() + 1;
   DVS_TRY(bow_db_query_own(inv, n, max_results, max_id, inv->ids.get(), inv->scores.get(), d_nr));
   DVS_TRY(enqueue_match(db, v->in_desc.get(), n, inv->ids.get(), d_nr, limit, P, db->out_train.get(), db->out_dist.get(), db->out_n.get()));
+  if (VP)
+    DVS_TRY(loop_verify_enqueue(db, db->v_in_xyz.get(), v->in_n.get(), n, inv->ids.get(), d_nr, limit, db->out_train.get(), *VP, db->v_res.get(),
+                                db->v_mask.get()));
   int nr = 0;
   DVS_HIP(hipMemcpyAsync(&nr, d_nr, sizeof(int), hipMemcpyDeviceToHost, s));
   DVS_HIP(hipMemcpyAsync(ids, inv->ids.get(), sizeof(int) * limit, hipMemcpyDeviceToHost, s));
@@ -507,9 +567,29 @@ dvs_status dvs_loop_db_detect(dvs_loop_db* db, const uint8_t* desc, int32_t n, i
     DVS_HIP(hipMemcpyAsync(train_idx, db->out_train.get(), sizeof(int) * (size_t)limit * n, hipMemcpyDeviceToHost, s));
     DVS_HIP(hipMemcpyAsync(dist, db->out_dist.get(), sizeof(int) * (size_t)limit * n, hipMemcpyDeviceToHost, s));
   }
+  if (VP) {
+    DVS_HIP(hipMemcpyAsync(results, db->v_res.get(), sizeof(dvs_loop_verify_result) * limit, hipMemcpyDeviceToHost, s));
+    if (n > 0) DVS_HIP(hipMemcpyAsync(inlier_mask, db->v_mask.get(), (size_t)limit * n, hipMemcpyDeviceToHost, s));
+  }
   DVS_HIP(hipStreamSynchronize(s));
   *n_results = nr;
   return DVS_OK;
+}
+
+dvs_status dvs_loop_db_detect(dvs_loop_db* db, const uint8_t* desc, int32_t n, int32_t max_results, int32_t max_id,
+                              const dvs_loop_match_params* params, int32_t* ids, double* scores, int32_t* n_matches, int32_t* train_idx,
+                              int32_t* dist, int32_t cap, int32_t* n_results) {
+  return detect_host(db, desc, nullptr, n, max_results, max_id, params, nullptr, ids, scores, n_matches, train_idx, dist, nullptr, nullptr, cap, n_results,
+                     "dvs_loop_db_detect");
+}
+
+dvs_status dvs_loopv_db_detect_verify(dvs_loop_db* db, const uint8_t* desc, const float* xyz, int32_t n, int32_t max_results, int32_t max_id,
+                                     const dvs_loop_match_params* match_params, const dvs_loop_verify_params* verify_params, int32_t* ids,
+                                     double* scores, int32_t* n_matches, int32_t* train_idx, int32_t* dist, dvs_loop_verify_result* results,
+                                     uint8_t* inlier_mask, int32_t cap, int32_t* n_results) {
+  DVS_TRY(loop_verify_check_params(verify_params, "dvs_loopv_db_detect_verify"));
+  return detect_host(db, desc, xyz, n, max_results, max_id, match_params, verify_params, ids, scores, n_matches, train_idx, dist, results, inlier_mask, cap,
+                     n_results, "dvs_loopv_db_detect_verify");
 }
 
 }  // extern "C"

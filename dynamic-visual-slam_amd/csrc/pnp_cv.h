@@ -11,33 +11,13 @@
 // Every SVD is a cyclic Jacobi eigen-decomposition of the (symmetric) normal matrix; cv::findHomography's Levenberg-Marquardt polish of
 // the planar initialisation is not restated (the 20 CvLevMarq iterations that follow absorb it).
 #pragma once
+#include "jacobi_eig.h"   // jacobi_eig<N>: shared with loop_verify.hip
 
 namespace dvs {
 namespace pnpcv {
 
 // ---- small dense routines (per thread, arrays in private memory) ------------------------------------------------------------------
-// cyclic Jacobi on the symmetric N x N matrix A (row-major, destroyed); eigenvectors in the COLUMNS of V
-template <int N>
-__device__ inline void jacobi_eig(double* A, double* V) {
-  for (int i = 0; i < N * N; i++) V[i] = 0.0;
-  for (int i = 0; i < N; i++) V[i * N + i] = 1.0;
-  for (int sweep = 0; sweep < 64; sweep++) {
-    double off = 0.0, dg = 0.0;
-    for (int p = 0; p < N; p++) { dg += A[p * N + p] * A[p * N + p]; for (int q = p + 1; q < N; q++) off += A[p * N + q] * A[p * N + q]; }
-    if (!(off > 1e-28 * dg)) break;   // sums of squares: off-diagonal norm below 1e-14 of the diagonal's; Jacobi converges quadratically
-    for (int p = 0; p < N - 1; p++)
-      for (int q = p + 1; q < N; q++) {
-        const double apq = A[p * N + q];
-        if (apq == 0.0) continue;
-        const double theta = (A[q * N + q] - A[p * N + p]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < N; k++) { const double a = A[k * N + p], b = A[k * N + q]; A[k * N + p] = c * a - s * b; A[k * N + q] = s * a + c * b; }
-        for (int k = 0; k < N; k++) { const double a = A[p * N + k], b = A[q * N + k]; A[p * N + k] = c * a - s * b; A[q * N + k] = s * a + c * b; }
-        for (int k = 0; k < N; k++) { const double a = V[k * N + p], b = V[k * N + q]; V[k * N + p] = c * a - s * b; V[k * N + q] = s * a + c * b; }
-      }
-  }
-}
+// jacobi_eig<N> (one thread, private arrays) is jacobi_eig.h's.
 // The same decomposition by a GROUP of 16 lanes of one wavefront on matrices in LDS (N <= 16): lane k < N carries index k of the three
 // inner loops of a rotation (columns p, q of A; rows p, q of A; columns p, q of V) — the 66 rotations of a sweep stay sequential, each
 // costs three LDS round trips instead of 3 N.  Element for element the arithmetic of jacobi_eig: the same eigenvectors bit for bit.

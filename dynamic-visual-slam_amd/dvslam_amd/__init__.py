@@ -15,3 +15,4 @@ from .tracker import Tracker, TrackerParams, TrackResult  # noqa: F401
 from .backend import MappingBackend  # noqa: F401
 from .bow import OrbVocabulary, OrbDatabase  # noqa: F401
 from .loop import LoopDatabase  # noqa: F401
+from ._lib import LoopVerifyParams  # noqa: F401

@@ -53,6 +53,22 @@ class LoopMatchParams(C.Structure):
     _fields_ = [("max_distance", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32)]
 
 
+class LoopVerifyParams(C.Structure):
+    """dvs_loop_verify_params with the header's defaults; K4 = (fx, fy, cx, cy) has none"""
+    _fields_ = [("iterations", C.c_int32), ("min_correspondences", C.c_int32), ("min_inliers", C.c_int32), ("refine_rounds", C.c_int32),
+                ("reproj_err", C.c_double), ("confidence", C.c_double), ("seed", C.c_uint64), ("K4", C.c_double * 4)]
+
+    def __init__(self, K4=(0.0, 0.0, 0.0, 0.0), iterations=256, min_correspondences=12, min_inliers=12, refine_rounds=2, reproj_err=4.0,
+                 confidence=0.99, seed=0):
+        super().__init__(int(iterations), int(min_correspondences), int(min_inliers), int(refine_rounds), float(reproj_err), float(confidence),
+                         int(seed), (C.c_double * 4)(*[float(k) for k in K4]))
+
+
+# dvs_loop_verify_result as a numpy record (72 bytes, no padding)
+LOOP_VERIFY_RESULT = np.dtype([("n_corr", "<i4"), ("n_inliers", "<i4"), ("success", "<i4"), ("iterations", "<i4"), ("rvec", "<f8", 3),
+                               ("tvec", "<f8", 3), ("rms_px", "<f8")])
+
+
 class VocTrainReport(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_words", "levels_run", "max_passes", "nodes_capped", "clusters_emptied", "nodes_short_seeded")]
 
@@ -213,6 +229,15 @@ def _bind(L):
         L.dvs_loop_db_match_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, pp, vp, vp, vp]
         L.dvs_loop_db_detect.argtypes = [vp, vp, i32, i32, i32, pp, vp, vp, vp, vp, vp, i32, pi32]
         L.dvs_loop_db_detect_device.argtypes = [vp, vp, vp, i32, i32, i32, pp, vp, vp, vp, vp, vp, i32, vp]
+    if hasattr(L, "dvs_loopv_db_verify"):   # loop verification (dvslam_amd/loop.py)
+        pi32, pp, pv = C.POINTER(i32), C.POINTER(LoopMatchParams), C.POINTER(LoopVerifyParams)
+        L.dvs_loopv_default_params.argtypes = [pv]
+        L.dvs_loopv_db_set_points.argtypes = [vp, i32, vp, i32]
+        L.dvs_loopv_db_set_points_device.argtypes = [vp, i32, vp, vp, i32, i32]
+        L.dvs_loopv_db_get_points.argtypes = [vp, i32, vp, i32, pi32]
+        L.dvs_loopv_db_verify_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, pv, vp, vp]
+        L.dvs_loopv_db_verify.argtypes = [vp, vp, i32, vp, i32, vp, pv, vp, vp]
+        L.dvs_loopv_db_detect_verify.argtypes = [vp, vp, vp, i32, i32, i32, pp, pv, vp, vp, vp, vp, vp, vp, vp, i32, pi32]
 
 
 def _bind_hooks(L):
@@ -288,6 +313,7 @@ def test_lib():
     L.dvs_test_retain_best_host.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]; L.dvs_test_retain_best_host.restype = None
     L.dvs_test_retain_best_device.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]
     L.dvs_ba_factor_probe.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.dvs_test_loop_verify_stages.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, C.POINTER(LoopVerifyParams)] + [vp] * 12
     _test_lib = L
     return L
 

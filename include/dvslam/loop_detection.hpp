@@ -3,10 +3,15 @@
 // usingDirectIndex, getDirectIndexLevels, retrieveFeatures) and, beyond DBoW2, match / detect: node-guided, ratio-tested, one-to-one
 // correspondences between a frame and candidate entries.  The matching rule is this library's own (dvslam_hip.h, "loop candidates";
 // INTEGRATION.md "Loop candidates").  dvslam::OrbDatabase (place_recognition.hpp) stays the database without a direct index.
+// Loop verification (dvslam_hip.h, "loop verification"): setPoints / getPoints keep an entry's 3D points (its camera frame) beside its
+// descriptors; verify() and detectVerified() estimate, per candidate, the rigid motion x_query = R x_entry + t by a RANSAC over the
+// matched 3D points on the device and fill LoopCandidate::verified, R, t, inliers, rms.
 //   plain layer    features as `const uint8_t* rows, int n` (n x 32 bytes) or dvslam::DescriptorVector; needs only the C-ABI
 //   OpenCV layer   std::vector<cv::Mat> features (one 1 x 32 CV_8U row each), compiled only when DVSLAM_WITH_OPENCV is defined
 // Errors throw std::runtime_error.
 #pragma once
+#include <array>
+#include <cmath>
 #include "place_recognition.hpp"
 
 namespace dvslam {
@@ -18,6 +23,22 @@ struct LoopCandidate {
   EntryId Id;
   double Score;                   // the query's L1 score; 0 from match(), which runs no query
   std::vector<Match> matches;     // ascending query row
+  // filled by verify() / detectVerified(); as constructed by match() / detect()
+  bool verified = false;          // at least VerifyParams::min_inliers inliers
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // row-major; x_query = R x_entry + t
+  double t[3] = {0, 0, 0};
+  std::vector<int> inliers;       // query rows of the inlier correspondences, ascending
+  double rms = 0.0;               // square root of the mean inlier error, pixels
+  int correspondences = 0;        // matches with a valid 3D point on both sides (-1: no such entry)
+  int iterations = 0;             // RANSAC iterations run
+};
+typedef std::array<float, 3> Point3;
+typedef std::vector<Point3> PointVector;   // one per descriptor row; a row without depth is any invalid point (NaN)
+struct VerifyParams {
+  int iterations = 256, min_correspondences = 12, min_inliers = 12, refine_rounds = 2;
+  double reproj_err = 4.0, confidence = 0.99;
+  uint64_t seed = 0;
+  double fx = 0, fy = 0, cx = 0, cy = 0;   // no default: set them
 };
 struct MatchParams {
   int max_distance = 50, ratio_num = 3, ratio_den = 4;
@@ -112,6 +133,67 @@ class LoopDatabase {
   std::vector<LoopCandidate> detect(const DescriptorVector& features, int max_results = 4, int max_id = -1, const MatchParams& p = MatchParams()) const {
     return detect(data(features), (int)features.size(), max_results, max_id, p);
   }
+  // ---- loop verification ----
+  void setPoints(EntryId id, const float* xyz, int n) {
+    need();
+    detail::bow_check(dvs_loopv_db_set_points(h_, (int32_t)id, xyz, n), "LoopDatabase::setPoints");
+  }
+  void setPoints(EntryId id, const PointVector& points) { setPoints(id, points.empty() ? nullptr : points[0].data(), (int)points.size()); }
+  PointVector getPoints(EntryId id) const {
+    need();
+    int32_t n = 0;
+    const dvs_status st = dvs_loopv_db_get_points(h_, (int32_t)id, nullptr, 0, &n);
+    if (st != DVS_OK && st != DVS_ERR_CAPACITY) detail::bow_check(st, "LoopDatabase::getPoints");
+    PointVector out(n);
+    detail::bow_check(dvs_loopv_db_get_points(h_, (int32_t)id, n ? out[0].data() : nullptr, n, &n), "LoopDatabase::getPoints");
+    return out;
+  }
+  // the rigid 3D-3D verification of candidates that match() / detect() returned for the frame whose points these are (n rows)
+  void verify(const float* xyz, int n, std::vector<LoopCandidate>& candidates, const VerifyParams& p) const {
+    need();
+    const int c = (int)candidates.size();
+    std::vector<int32_t> ids(c + 1), train((size_t)c * n + 1, -1);
+    for (int x = 0; x < c; x++) {
+      ids[x] = (int32_t)candidates[x].Id;
+      for (const Match& m : candidates[x].matches)
+        if (m.query >= 0 && m.query < n) train[(size_t)x * n + m.query] = m.train;
+    }
+    std::vector<dvs_loop_verify_result> res(c + 1);
+    std::vector<uint8_t> mask((size_t)c * n + 1);
+    const dvs_loop_verify_params P = params(p);
+    detail::bow_check(dvs_loopv_db_verify(h_, xyz, n, ids.data(), c, train.data(), &P, res.data(), mask.data()), "LoopDatabase::verify");
+    for (int x = 0; x < c; x++) fill(candidates[x], res[x], &mask[(size_t)x * n], n);
+  }
+  void verify(const PointVector& points, std::vector<LoopCandidate>& candidates, const VerifyParams& p) const {
+    verify(points.empty() ? nullptr : points[0].data(), (int)points.size(), candidates, p);
+  }
+  // transform, query, guided match and verification in one enqueue and one read-back
+  std::vector<LoopCandidate> detectVerified(const uint8_t* rows, const float* xyz, int n, int max_results, int max_id, const VerifyParams& vp,
+                                            const MatchParams& p = MatchParams()) const {
+    need();
+    const int cap = capacity(max_results);
+    std::vector<int32_t> ids(cap + 1), nm(cap + 1), train((size_t)cap * n + 1), dist((size_t)cap * n + 1);
+    std::vector<double> scores(cap + 1);
+    std::vector<dvs_loop_verify_result> res(cap + 1);
+    std::vector<uint8_t> mask((size_t)cap * n + 1);
+    const dvs_loop_match_params P = {p.max_distance, p.ratio_num, p.ratio_den};
+    const dvs_loop_verify_params V = params(vp);
+    int32_t nr = 0;
+    detail::bow_check(dvs_loopv_db_detect_verify(h_, rows, xyz, n, max_results, max_id < 0 ? -1 : max_id, &P, &V, ids.data(), scores.data(), nm.data(),
+                                                train.data(), dist.data(), res.data(), mask.data(), cap, &nr), "LoopDatabase::detectVerified");
+    std::vector<LoopCandidate> out(nr);
+    for (int x = 0; x < nr; x++) {
+      out[x].Id = (EntryId)ids[x]; out[x].Score = scores[x];
+      collect(out[x], &train[(size_t)x * n], &dist[(size_t)x * n], n);
+      fill(out[x], res[x], &mask[(size_t)x * n], n);
+    }
+    return out;
+  }
+  std::vector<LoopCandidate> detectVerified(const DescriptorVector& descriptors, const PointVector& points, int max_results, int max_id,
+                                            const VerifyParams& vp, const MatchParams& p = MatchParams()) const {
+    if (points.size() != descriptors.size()) throw std::runtime_error("LoopDatabase::detectVerified: one point per descriptor row");
+    return detectVerified(data(descriptors), points.empty() ? nullptr : points[0].data(), (int)descriptors.size(), max_results, max_id, vp, p);
+  }
 #ifdef DVSLAM_WITH_OPENCV
   EntryId add(const std::vector<cv::Mat>& features) {
     const std::vector<uint8_t> rows = detail::pack_rows(features);
@@ -142,6 +224,32 @@ class LoopDatabase {
   static void collect(LoopCandidate& c, const int32_t* train, const int32_t* dist, int n) {
     for (int i = 0; i < n; i++)
       if (train[i] >= 0) c.matches.push_back(Match{i, (int)train[i], (int)dist[i]});
+  }
+  static dvs_loop_verify_params params(const VerifyParams& p) {
+    dvs_loop_verify_params P;
+    P.iterations = p.iterations; P.min_correspondences = p.min_correspondences; P.min_inliers = p.min_inliers; P.refine_rounds = p.refine_rounds;
+    P.reproj_err = p.reproj_err; P.confidence = p.confidence; P.seed = p.seed;
+    P.K4[0] = p.fx; P.K4[1] = p.fy; P.K4[2] = p.cx; P.K4[3] = p.cy;
+    return P;
+  }
+  // the record into the candidate: R from the Rodrigues vector (R = I + sin(a) K + (1 - cos(a)) K^2, K the unit axis' cross matrix)
+  static void fill(LoopCandidate& c, const dvs_loop_verify_result& r, const uint8_t* mask, int n) {
+    c.verified = r.success != 0; c.rms = r.rms_px; c.correspondences = r.n_corr; c.iterations = r.iterations;
+    for (int k = 0; k < 3; k++) c.t[k] = r.tvec[k];
+    const double a = std::sqrt(r.rvec[0] * r.rvec[0] + r.rvec[1] * r.rvec[1] + r.rvec[2] * r.rvec[2]);
+    const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int k = 0; k < 9; k++) c.R[k] = I[k];
+    if (a > 0) {
+      const double x = r.rvec[0] / a, y = r.rvec[1] / a, z = r.rvec[2] / a, K[9] = {0, -z, y, z, 0, -x, -y, x, 0};
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+          double kk = 0;
+          for (int m = 0; m < 3; m++) kk += K[3 * i + m] * K[3 * m + j];
+          c.R[3 * i + j] = I[3 * i + j] + std::sin(a) * K[3 * i + j] + (1.0 - std::cos(a)) * kk;
+        }
+    }
+    c.inliers.clear();
+    for (int i = 0; i < n; i++) if (mask[i]) c.inliers.push_back(i);
   }
   dvs_loop_db* h_ = nullptr;
 };

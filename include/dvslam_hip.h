@@ -969,6 +969,92 @@ dvs_status dvs_loop_db_detect_device(dvs_loop_db* db, const uint8_t* d_desc, con
                                      int32_t max_id, const dvs_loop_match_params* params, int32_t* d_ids, double* d_scores, int32_t* d_n_matches,
                                      int32_t* d_train_idx, int32_t* d_dist, int32_t cap, int32_t* d_n_results);
 
+/* ----------------------- loop verification: rigid 3D-3D RANSAC over the candidates of one detect, on the device -------------------
+ * The step after the guided match: for every candidate the rigid motion between the two keyframes' cameras, estimated from the metric
+ * 3D points both keyframes of an RGB-D system carry (csrc/loop_verify.hip; INTEGRATION.md "Loop candidates").  It reads train_idx where
+ * match / detect left it on the device and returns one small record per candidate.  No loop detector is a reference interface this
+ * project can pin, so the RULE is the library's own, stated here in full and restated sequentially in tests/loop_verify_ref.py: integer
+ * parts (gathered lists, samples, counts, selection, masks) are exact, float parts are FP64 on the float inputs and carry tolerances
+ * (tests/test_gpu_loop_verify.py states them).
+ *
+ * Points.  The direct index holds one more per-row block: xyz, three floats per descriptor row, in the entry keyframe's camera frame.
+ * add / add_device store no points: rows never given points hold NaN.  dvs_loopv_db_set_points* fill an entry's rows, dvs_loop_db_clear
+ * forgets them.  A point is VALID iff its three coordinates are finite and z > 0; a keypoint without depth is any invalid point.
+ *
+ * Model: x_q = R x_e + t, from the entry's camera frame to the query's, scale 1 (Sim(3) is out of scope).
+ * Per candidate c < clamp(*d_n_cand, 0, cap_cand), entry e = d_entry_ids[c]:
+ *  1 gather    the correspondence list: every query row i < clamp(*d_n, 0, stride_rows), in ascending i, with j = train_idx[c][i] in
+ *              [0, rows of e), query point i and entry point j both valid.  m entries; n_corr = m.  e outside [0, size): n_corr = -1
+ *              and the candidate fails.  m < min_correspondences: the candidate FAILS (success 0, n_inliers 0, iterations 0, pose and
+ *              rms zeros, mask zeros).
+ *  2 hypotheses  seed_c = splitmix64(seed ^ (uint64)e), so the answer does not depend on the candidate's position in the list.
+ *              Hypothesis h < iterations draws 3 distinct list positions with the sampler of dvs_solve_pnp_ransac (draw j of
+ *              hypothesis h is the r-th position not drawn before, r = splitmix64(seed_c + 0x9E3779B97F4A7C15 * (16 h + j + 1)) mod
+ *              (m - j)) and fits Horn's closed form (Horn 1987, "Closed-form solution of absolute orientation using unit
+ *              quaternions"): the centroids, the 3 x 3 cross-covariance S = sum (x_e - mean_e)(x_q - mean_q)^T of the centred triples,
+ *              the symmetric 4 x 4 matrix N of S, its eigenvector of the largest eigenvalue (cyclic Jacobi), sign q0 >= 0, R from
+ *              the unit quaternion, t = mean_q - R mean_e.  A hypothesis is DEGENERATE, with count 0, if anything is not finite or
+ *              (lambda1 - lambda2) <= 1e-9 |lambda1| for the two largest eigenvalues (collinear or coincident samples).
+ *  3 score     the error of correspondence k under (R, t) is the larger of two squared reprojection distances, with K4 = {fx, fy,
+ *              cx, cy}: in the query image between the projections of R x_e + t and x_q, in the entry image between the projections
+ *              of R^T (x_q - t) and x_e; +inf if either transformed depth is <= 0.  k is an inlier iff error <= reproj_err^2.
+ *  4 select    the sequential RANSAC loop replayed over the counts, as in dvs_solve_pnp_ransac: hypothesis h is iteration h, a count
+ *              above max(best, 2) becomes the best and shortens the loop by cv::RANSACUpdateNumIters(confidence, (m - count) / m, 3,
+ *              iterations).  `iterations` of the record = iterations run.  No hypothesis with more than 2 inliers: the candidate fails.
+ *  5 refine    S_0 = the inliers of the selected hypothesis.  For r = 1 .. refine_rounds: Horn on S_(r-1) (centroids first, then
+ *              the centred covariance; partial sums folded in a fixed order, no floating atomics: two identical calls give identical
+ *              bytes), S_r = the inliers of that fit; accepted iff the fit is not degenerate and |S_r| >= |S_(r-1)|, else the rounds
+ *              stop and round r-1's model and set stay.
+ *  6 result    n_inliers = |S|, rvec = the principal Rodrigues vector of R (the conversion dvs_solve_pnp_ransac ends in), tvec = t,
+ *              rms_px = sqrt(mean inlier error), success = n_inliers >= min_inliers (the pose, count and mask are reported either way);
+ *              inlier_mask[c][i] (uint8, query rows) = 1 exactly for the inlier correspondences' i, 0 for every other i < stride_rows.
+ * Slots c >= *d_n_cand are written as failed with n_corr 0.  The same id may appear twice: each occurrence gets the same record.
+ * Parameters, not constants: the defaults are 256 iterations, min_correspondences 12, min_inliers 12, refine_rounds 2, reproj_err 4.0
+ * px (the value the reference passes to solvePnPRansac, frontend.cpp:911-921), confidence 0.99, seed 0 — usual values, not pinned to
+ * any library; K4 has no default, so a NULL params pointer is DVS_ERR_ARG (dvs_loopv_default_params leaves K4 zeros: zeros are
+ * refused).  DVS_ERR_ARG: iterations outside 1..4096, min_correspondences < 3, min_inliers < 3, refine_rounds outside 0..8, reproj_err
+ * or a focal length not > 0, confidence outside (0, 1), anything not finite.  The limits of the match apply (65535 candidates,
+ * candidates x rows below 2^31) and candidates x iterations must stay below 2^31.  Scratch belongs to the handle and grows on demand;
+ * capacity checks come before any device work.
+ * Names: the functions carry the prefix dvs_loopv_ ("loop verification"), not dvs_loop_: tests/test_loop_cpu.py pins the exact set of
+ * dvs_loop_* symbols the library exports, and existing tests stay as they are.  They take the same dvs_loop_db handle. */
+typedef struct {
+  int32_t iterations, min_correspondences, min_inliers, refine_rounds;
+  double reproj_err, confidence;
+  uint64_t seed;
+  double K4[4];
+} dvs_loop_verify_params;
+typedef struct {
+  int32_t n_corr, n_inliers, success, iterations;
+  double rvec[3], tvec[3], rms_px;
+} dvs_loop_verify_result;
+dvs_status dvs_loopv_default_params(dvs_loop_verify_params* p);   /* 256, 12, 12, 2, 4.0, 0.99, 0, K4 zeros (to be set) */
+/* entry entry_id's points from the host: n must equal the entry's row count (DVS_ERR_ARG otherwise, and for an id outside [0, size)).
+ * Synchronises. */
+dvs_status dvs_loopv_db_set_points(dvs_loop_db* db, int32_t entry_id, const float* xyz, int32_t n);
+/* the points of entries first_entry_id + f, f < nframes, in the layout of dvs_loop_db_add_device: frame f's rows start at d_xyz + 3 * f *
+ * stride_rows; one kernel copies min(clamp(d_n[f], 0, stride_rows), rows of the entry) rows per entry.  Asynchronous. */
+dvs_status dvs_loopv_db_set_points_device(dvs_loop_db* db, int32_t first_entry_id, const float* d_xyz, const int32_t* d_n, int32_t stride_rows,
+                                         int32_t nframes);
+/* read-back of entry `id`'s points (NaN where none were set): *n always set; DVS_ERR_CAPACITY, nothing written, if cap_rows < *n */
+dvs_status dvs_loopv_db_get_points(dvs_loop_db* db, int32_t id, float* xyz, int32_t cap_rows, int32_t* n);
+/* the verification on exactly the buffers dvs_loop_db_detect_device / match_device wrote: d_xyz_query [stride_rows][3], d_train_idx
+ * [cap_cand][stride_rows]; outputs d_results [cap_cand], d_inlier_mask [cap_cand][stride_rows].  Nothing crosses to the host.
+ * Asynchronous. */
+dvs_status dvs_loopv_db_verify_device(dvs_loop_db* db, const float* d_xyz_query, const int32_t* d_n, int32_t stride_rows, const int32_t* d_entry_ids,
+                                     const int32_t* d_n_cand, int32_t cap_cand, const int32_t* d_train_idx, const dvs_loop_verify_params* params,
+                                     dvs_loop_verify_result* d_results, uint8_t* d_inlier_mask);
+/* host form: xyz [n][3], train_idx and inlier_mask [n_cand][n], results [n_cand]; an entry id outside [0, size) is DVS_ERR_ARG before any
+ * device work.  Synchronises. */
+dvs_status dvs_loopv_db_verify(dvs_loop_db* db, const float* xyz, int32_t n, const int32_t* entry_ids, int32_t n_cand, const int32_t* train_idx,
+                              const dvs_loop_verify_params* params, dvs_loop_verify_result* results, uint8_t* inlier_mask);
+/* dvs_loop_db_detect followed by the verification of its results: transform, query, guided match and verification in ONE enqueue with
+ * ONE read-back.  Outputs as dvs_loop_db_detect's plus results [cap] and inlier_mask [cap][n]. */
+dvs_status dvs_loopv_db_detect_verify(dvs_loop_db* db, const uint8_t* desc, const float* xyz, int32_t n, int32_t max_results, int32_t max_id,
+                                     const dvs_loop_match_params* match_params, const dvs_loop_verify_params* verify_params, int32_t* ids,
+                                     double* scores, int32_t* n_matches, int32_t* train_idx, int32_t* dist, dvs_loop_verify_result* results,
+                                     uint8_t* inlier_mask, int32_t cap, int32_t* n_results);
+
 #ifdef __cplusplus
 }
 #endif
