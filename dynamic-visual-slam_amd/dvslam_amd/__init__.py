@@ -16,3 +16,4 @@ from .backend import MappingBackend  # noqa: F401
 from .bow import OrbVocabulary, OrbDatabase  # noqa: F401
 from .loop import LoopDatabase  # noqa: F401
 from ._lib import LoopVerifyParams  # noqa: F401
+from .pose_graph import PoseGraph  # noqa: F401

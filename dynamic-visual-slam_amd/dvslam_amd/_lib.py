@@ -69,6 +69,17 @@ LOOP_VERIFY_RESULT = np.dtype([("n_corr", "<i4"), ("n_inliers", "<i4"), ("succes
                                ("tvec", "<f8", 3), ("rms_px", "<f8")])
 
 
+class PgoParams(C.Structure):
+    """dvs_pgo_params (fill it with dvs_pgo_default_params)"""
+    _fields_ = [("max_iterations", C.c_int32), ("max_pcg_iterations", C.c_int32), ("function_tolerance", C.c_double),
+                ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double), ("eta", C.c_double)]
+
+
+class PgoSummary(C.Structure):
+    _fields_ = [("termination", C.c_int32), ("num_successful_steps", C.c_int32), ("num_iterations", C.c_int32), ("pcg_iterations", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+
 class VocTrainReport(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_words", "levels_run", "max_passes", "nodes_capped", "clusters_emptied", "nodes_short_seeded")]
 
@@ -238,6 +249,20 @@ def _bind(L):
         L.dvs_loopv_db_verify_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, pv, vp, vp]
         L.dvs_loopv_db_verify.argtypes = [vp, vp, i32, vp, i32, vp, pv, vp, vp]
         L.dvs_loopv_db_detect_verify.argtypes = [vp, vp, vp, i32, i32, i32, pp, pv, vp, vp, vp, vp, vp, vp, vp, i32, pi32]
+    if hasattr(L, "dvs_pgo_create"):   # pose-graph optimisation (dvslam_amd/pose_graph.py)
+        L.dvs_pgo_default_params.argtypes = [C.POINTER(PgoParams)]
+        L.dvs_pgo_check_graph.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.dvs_pgo_create.argtypes = [i32, C.POINTER(vp)]
+        L.dvs_pgo_destroy.argtypes = [vp]; L.dvs_pgo_destroy.restype = None
+        L.dvs_pgo_synchronize.argtypes = [vp]
+        L.dvs_pgo_set_nodes.argtypes = [vp, i32, vp, vp, vp]
+        L.dvs_pgo_set_edges.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+        L.dvs_pgo_evaluate.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.dvs_pgo_solve.argtypes = [vp, C.POINTER(PgoParams), C.POINTER(PgoSummary)]
+        L.dvs_pgo_get_nodes.argtypes = [vp, vp, vp]
+        L.dvs_pgo_get_trace.argtypes = [vp, vp, i32, C.POINTER(i32)]
+        L.dvs_pgo_correct_points.argtypes = [vp, i32, vp, vp]
+        L.dvs_pgo_correct_points_device.argtypes = [vp, i32, vp, vp]
 
 
 def _bind_hooks(L):
@@ -314,6 +339,9 @@ def test_lib():
     L.dvs_test_retain_best_device.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]
     L.dvs_ba_factor_probe.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
     L.dvs_test_loop_verify_stages.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, C.POINTER(LoopVerifyParams)] + [vp] * 12
+    if hasattr(L, "dvs_test_pgo_apply"):
+        L.dvs_test_pgo_apply.argtypes = [vp, dbl, vp, vp]
+        L.dvs_test_pgo_pcg.argtypes = [vp, dbl, dbl, i32, vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(dbl)]
     _test_lib = L
     return L
 

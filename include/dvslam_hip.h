@@ -1055,6 +1055,90 @@ dvs_status dvs_loopv_db_detect_verify(dvs_loop_db* db, const uint8_t* desc, cons
                                      double* scores, int32_t* n_matches, int32_t* train_idx, int32_t* dist, dvs_loop_verify_result* results,
                                      uint8_t* inlier_mask, int32_t cap, int32_t* n_results);
 
+/* ======================================= Pose-graph optimisation ================================= */
+/* The consumer of a verified loop (csrc/pose_graph.hip): a sparse SE(3) least-squares solve over ALL keyframes, and the correction that
+ * moves the landmarks along with their keyframes.  The rule is the library's own (PARITY UNPINNED: stated here in full, restated
+ * sequentially in float64 in tests/pose_graph_ref.py; no g2o, GTSAM or Ceres is compared against).  FP64 throughout.
+ *  Nodes     N poses (R_i, t_i) with x_world = R_i x_i + t_i, given as R (9 doubles, row-major) and t — the layout dvs_backend_get_keyframes
+ *            returns, in the direction dvs_associate's reprojection reads it (x_cam = R^T (X - t)) — and a `fixed` flag per node.  The handle keeps the poses as given ("before") and the current ones.  The current
+ *            rotation is kept as a unit quaternion (w, x, y, z), made from R by Shepperd's rule (the largest of w, x, y, z first) and
+ *            normalised; dvs_pgo_get_nodes returns the R made from it (1 - 2(yy + zz), 2(xy - wz), ...), also before any solve.
+ *  Edges     E records (i, j, rvec, tvec, w_rot, w_trans).  The measurement Z = (R_z, t_z), R_z = cos(a) I + (1 - cos(a)) k k^T + sin(a) [k]x
+ *            for rvec = a k (the identity for the zero vector), means x_i = R_z x_j + t_z, that is Z ~ T_i^-1 T_j.  A verified loop is
+ *            the edge (query, entry, result.rvec, result.tvec) unchanged; odometry between consecutive keyframes has the same form.
+ *            Duplicate edges are allowed (each counts).
+ *  Residual  6 per edge: r = [ w_rot Log(R_z^T R_i^T R_j) ; w_trans R_z^T (R_i^T (t_j - t_i) - t_z) ], with Log(Q): v = vee(Q - Q^T) / 2,
+ *            s = |v|, c = (tr Q - 1) / 2, theta = atan2(s, c), omega = v theta / s if s > 1e-12, else v.  Rotation errors beyond about
+ *            3.1 rad are OUTSIDE THE DOMAIN (v vanishes at pi and the axis is lost).  Cost = 0.5 sum |r|^2.  There is no robust loss: the
+ *            RANSAC gate of the verification is the defence against false loops.
+ *  Update    delta_i = (omega, v): R_i <- R_i Exp(omega), t_i <- t_i + R_i v, both with the R_i before the step.  Jacobians are the exact
+ *            derivatives of r in delta_i, delta_j at delta = 0, two 6 x 6 blocks per edge (row = residual, column = delta), with
+ *            M = R_i^T R_j, Q = R_z^T M, p = R_i^T (t_j - t_i), Jr^-1 = I + [omega]x / 2 + c [omega]x^2, c = 1 / theta^2 - (1 + cos theta) /
+ *            (2 theta sin theta) (theta < 1e-2: 1/12 + theta^2 / 720 + theta^4 / 30240):
+ *              Ji = [ -w_rot Jr^-1 M^T, 0 ; w_trans R_z^T [p]x, -w_trans R_z^T ]      Jj = [ w_rot Jr^-1, 0 ; 0, w_trans Q ].
+ *            The block of a fixed node is zero, and its rows are not part of the linear system (gradient rows exactly 0).  The quaternion
+ *            is updated as q <- q * (cos(|omega| / 2), sin(|omega| / 2) omega / |omega|) and renormalised at every step.
+ *  Outer loop  Levenberg-Marquardt under the trust-region policy of dvs_ba_solve (csrc/ba.hip, struct TrustRegion, restated in
+ *            pose_graph.hip): initial radius 1e4; accepted when cost_change / model_cost_change > 1e-3; radius /= max(1/3, 1 - (2 rho - 1)^3)
+ *            on success (at most 1e16), /= 2, 4, 8 .. on failure; the LM diagonal D = clamp(diag(H), 1e-6, 1e32) (0 on fixed nodes) is kept
+ *            across a rejected step and rebuilt after any other; five invalid steps in a row (a step that is not finite, or a model
+ *            change that is not > 0) fail the solve.  model_cost_change = -(x.g + 0.5 |J x|^2).  Tolerances as there: max |g_k| over the
+ *            free coordinates <= gradient_tolerance at the loop head; |candidate - current| <= parameter_tolerance (|current| +
+ *            parameter_tolerance) over (q, t) of the free nodes, and |cost_change| <= function_tolerance cost, both on the candidate
+ *            before acceptance.  No Jacobi column scaling.
+ *  Linear solve  (H + D / radius) x = -g with H = J^T J never assembled: preconditioned conjugate gradients from x = 0; the preconditioner is
+ *            the inverse of the 6 x 6 diagonal blocks of H + D / radius (Cholesky; the inverse of its diagonal if a pivot is not positive).
+ *            It stops at the first iteration k >= 0 with |r_k|_2 <= eta |g|_2 (r_k the recurrence's residual) or at max_pcg_iterations
+ *            (0: max(100, 2 N)).  An isolated free node has a zero gradient and does not move.
+ *  Determinism  every sum folds in a fixed order — per node over its incident edges in ascending edge index, dot products as per-thread
+ *            strided partial sums folded by a fixed tree — and there are no floating-point atomics: two identical solves return
+ *            identical bytes.
+ * DVS_ERR_ARG, before any device work (dvs_pgo_check_graph makes the same checks without a handle or a device): no fixed node; i == j; an
+ * index outside [0, N); a weight not > 0; anything not finite; N outside 1..2^20 or E outside 1..2^22; edges set before nodes.  Setting
+ * nodes of another count drops the edges; setting the same count again keeps them (a second solve from the same start).
+ * Every N and E in range runs: a linear solve is ONE workgroup striding over nodes and edges, with its vectors in global memory.
+ * One small status record per trial step crosses to the host, as in dvs_ba_solve_device; nothing else does.  Calls on one handle are
+ * serial; the handle owns its stream. */
+typedef struct dvs_pgo dvs_pgo;
+typedef struct dvs_pgo_params {
+  int32_t max_iterations, max_pcg_iterations;     /* 50; 0 = max(100, 2 N) */
+  double function_tolerance, gradient_tolerance, parameter_tolerance;   /* 1e-6, 1e-10, 1e-8 */
+  double eta;                                     /* 0.1; in (0, 1) */
+} dvs_pgo_params;
+typedef struct dvs_pgo_summary {
+  int32_t termination;          /* 0 converged, 1 iteration limit, 2 failure */
+  int32_t num_successful_steps, num_iterations;
+  int32_t pcg_iterations;       /* over all trial steps */
+  double initial_cost, final_cost;
+} dvs_pgo_summary;
+dvs_status dvs_pgo_default_params(dvs_pgo_params* p);
+/* the argument checks of dvs_pgo_set_nodes and dvs_pgo_set_edges on their own: host code, no handle, no device */
+dvs_status dvs_pgo_check_graph(int32_t N, const double* R, const double* t, const uint8_t* fixed, int32_t E, const int32_t* i, const int32_t* j,
+                               const double* rvec, const double* tvec, const double* w_rot, const double* w_trans);
+dvs_status dvs_pgo_create(int32_t device, dvs_pgo** out);
+void dvs_pgo_destroy(dvs_pgo* h);
+dvs_status dvs_pgo_synchronize(dvs_pgo* h);
+/* R [N][9], t [N][3], fixed [N]: "before" and current both become these poses */
+dvs_status dvs_pgo_set_nodes(dvs_pgo* h, int32_t N, const double* R, const double* t, const uint8_t* fixed);
+/* i, j [E], rvec, tvec [E][3], w_rot, w_trans [E]; builds the node -> edge lists once */
+dvs_status dvs_pgo_set_edges(dvs_pgo* h, int32_t E, const int32_t* i, const int32_t* j, const double* rvec, const double* tvec, const double* w_rot,
+                             const double* w_trans);
+/* at the current poses: cost, residuals [E][6], Ji, Jj [E][36] (row-major), grad [6 N]; every output nullable.  The counterpart of
+ * dvs_ba_evaluate. */
+dvs_status dvs_pgo_evaluate(dvs_pgo* h, double* cost, double* residuals, double* Ji, double* Jj, double* grad);
+/* from the current poses; params NULL: the defaults.  Synchronises. */
+dvs_status dvs_pgo_solve(dvs_pgo* h, const dvs_pgo_params* params, dvs_pgo_summary* summary);
+dvs_status dvs_pgo_get_nodes(dvs_pgo* h, double* R, double* t);   /* the current poses; either may be NULL */
+/* as dvs_ba_get_trace, one row of 7 doubles per trial step: radius, kind (0 invalid, 1 accepted, 2 rejected, 3 parameter tolerance, 4
+ * function tolerance), cost_change, model_cost_change, rho, candidate cost, PCG iterations of the step */
+dvs_status dvs_pgo_get_trace(const dvs_pgo* h, double* rows, int32_t cap_rows, int32_t* n_rows);
+/* Map correction: for a = anchor[k] in [0, N): x' = R'_a (R_a^T (x - t_a)) + t'_a, unprimed "before", primed current — computed in FP64 in
+ * exactly that operation order (sums left to right) and rounded to float once, from the same R bytes dvs_pgo_get_nodes returns.  Any other
+ * anchor leaves the point untouched.  In place on xyz [n][3].  The host form synchronises; the device form is asynchronous on the
+ * handle's stream (dvs_pgo_synchronize). */
+dvs_status dvs_pgo_correct_points(dvs_pgo* h, int32_t n, float* xyz, const int32_t* anchor);
+dvs_status dvs_pgo_correct_points_device(dvs_pgo* h, int32_t n, float* d_xyz, const int32_t* d_anchor);
+
 #ifdef __cplusplus
 }
 #endif
