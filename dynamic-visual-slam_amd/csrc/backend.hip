@@ -33,32 +33,14 @@
 #include "common.h"
 #include "device_mem.h"
 #include "matcher.h"
+#include "backend_internal.h"
 #include "associate_device.h"
 #include "block_rank.h"
 #include "../../include/dvslam/association.hpp"   // reprojection_error: the device kernel's arithmetic on the host
 
 namespace dvs {
 
-typedef long long i64;
-
-struct LmView { i64* id; i64* seen; int* cls; int* cnt; float* xyz; uint8_t* desc; };
-struct ObView { i64* id; i64* frame; i64* lm; int* kf; int* cls; float* px; uint8_t* desc; };
-struct PairRec { i64 id; int j, slot, status; float xyz[3], tri[3]; int pad; };   // 48 bytes
-struct DetRec { double cx, cy, w, h; int cls, pad; };
-
-// row of landmark `key` in the ascending id column, -1 if the table does not hold it
-__device__ __forceinline__ int lm_find(const i64* __restrict__ id, int n, i64 key) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (id[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && id[lo] == key) ? lo : -1;
-}
-__device__ __forceinline__ void copy32(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src) {   // one descriptor row, 16-byte aligned
-  const uint4 a = reinterpret_cast<const uint4*>(src)[0], b = reinterpret_cast<const uint4*>(src)[1];
-  reinterpret_cast<uint4*>(dst)[0] = a; reinterpret_cast<uint4*>(dst)[1] = b;
-}
+// LmView / ObView, lm_find, copy32, the tables and the handle: backend_internal.h
 
 // categorizeObservation (:1011-1029): the first detection whose box holds the pixel — the float pixel promoted to double against
 // c -/+ size / 2 in double, inclusive on all four sides — else class 0.  code[i] = class, or -1 - class when the class is filtered (:749).
@@ -331,70 +313,13 @@ __global__ __launch_bounds__(256) void k_prune_compact(LmView lm, int nlm, const
   if (threadIdx.x == 0) { counts[0] = kl; counts[1] = ko; counts[2] = kr; }
 }
 
-struct LmTable {
-  DeviceBuf<i64> id, seen; DeviceBuf<int> cls, cnt; DeviceBuf<float> xyz; DeviceBuf<uint8_t> desc;
-  size_t cap = 0;
-  dvs_status alloc(size_t c) {
-    DVS_TRY(id.alloc(c)); DVS_TRY(seen.alloc(c)); DVS_TRY(cls.alloc(c)); DVS_TRY(cnt.alloc(c)); DVS_TRY(xyz.alloc(c * 3)); DVS_TRY(desc.alloc(c * 32));
-    cap = c;
-    return DVS_OK;
-  }
-  LmView view() const { return LmView{id.get(), seen.get(), cls.get(), cnt.get(), xyz.get(), desc.get()}; }
-};
-struct ObTable {
-  DeviceBuf<i64> id, frame, lm; DeviceBuf<int> kf, cls; DeviceBuf<float> px; DeviceBuf<uint8_t> desc;
-  size_t cap = 0;
-  dvs_status alloc(size_t c) {
-    DVS_TRY(id.alloc(c)); DVS_TRY(frame.alloc(c)); DVS_TRY(lm.alloc(c)); DVS_TRY(kf.alloc(c)); DVS_TRY(cls.alloc(c)); DVS_TRY(px.alloc(c * 2));
-    DVS_TRY(desc.alloc(c * 32));
-    cap = c;
-    return DVS_OK;
-  }
-  ObView view() const { return ObView{id.get(), frame.get(), lm.get(), kf.get(), cls.get(), px.get(), desc.get()}; }
-};
-
-struct KeyframeRec { uint64_t frame_id; i64 stamp; std::vector<uint64_t> obs_ids; double R[9], t[3]; };
-
 }  // namespace dvs
 
 using namespace dvs;
 
-struct dvs_backend {
-  dvs_backend_params P;
-  int device = 0;
-  dvs_matcher* ctx = nullptr;
-  // the map
-  LmTable lm, lm_spare; ObTable ob, ob_spare;          // the spare pair receives dvs_backend_prune's compaction
-  DeviceBuf<double> kf_R, kf_t;
-  size_t cap_kf = 0;
-  int nlm = 0, nob = 0;
-  std::vector<KeyframeRec> kfs;                      // keyframes_
-  std::unordered_map<uint64_t, int> kf_index;        // frame_id -> index
-  i64 next_obs = 0, next_lm = 0;                     // next_observation_id_, next_global_landmark_id_
-  // per-call staging and scratch (grow-only)
-  DeviceBuf<float> s_px, s_xyz, q_px, g_xyz, tri_xyz, view_px, w_px, w_lxyz;
-  DeviceBuf<uint8_t> s_desc, q_desc, g_desc;
-  DeviceBuf<int> s_code, s_order, s_small, g_slot, d_best, ob_slot, v_cnt, v_fill, v_obs, view_kf, tri_status, a_int, w_flag, w_pos, w_oi, w_slot, w_cls,
-      w_lmidx, w_lcls;
-  DeviceBuf<i64> view_offs, view_oid, a_i64, w_lm, w_frame, w_lid;
-  DeviceBuf<DetRec> s_det;
-  DeviceBuf<PairRec> p_rec;
-  DeviceBuf<int> p_flag, rem_kf;
-  DeviceBuf<i64> rem_id;
-  size_t c_pflag = 0, c_rem = 0;
-  DeviceBuf<double> d_Rt, a_dbl;
-  size_t c_n = 0, c_det = 0, c_glm = 0, c_vlm = 0, c_vob = 0, c_pair = 0, c_aint = 0, c_ai64 = 0, c_adbl = 0, c_wob = 0, c_wlm = 0;
-  // host staging that asynchronous copies read until the call's last synchronisation
-  std::vector<float> h_px, h_xyz;
-  std::vector<int> h_int;
-  std::vector<i64> h_i64;
-  std::vector<double> h_dbl;
-  std::vector<DetRec> h_det;
-};
-
 namespace {
 
-const int kSmall = 256;   // s_small: [0, 64) filtered ids, [64, 128) class list, [128, 192) class counts, [192, 196) counts, [196] marked landmarks
+const int kSmall = 256;   // s_small: [0, 64) filtered ids, [64, 128) class list, [128, 192) class counts, [192, 196) counts, [196] marked landmarks, [200, 208) loop_close.hip
 
 dvs_status backend_grow_tables(dvs_backend* h, size_t need_lm, size_t need_ob, size_t need_kf) {
   hipStream_t st = h->ctx->stream;
@@ -442,8 +367,22 @@ dvs_status backend_grow_tables(dvs_backend* h, size_t need_lm, size_t need_ob, s
   return DVS_OK;
 }
 
+void quat_to_R(const double* q_xyzw, double* R) {   // extractPoseFromTransform (:1194-1215)
+  double qx = q_xyzw[0], qy = q_xyzw[1], qz = q_xyzw[2], qw = q_xyzw[3];
+  const double norm = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+  qw /= norm; qx /= norm; qy /= norm; qz /= norm;
+  R[0] = 1 - 2 * (qy * qy + qz * qz); R[1] = 2 * (qx * qy - qw * qz); R[2] = 2 * (qx * qz + qw * qy);
+  R[3] = 2 * (qx * qy + qw * qz); R[4] = 1 - 2 * (qx * qx + qz * qz); R[5] = 2 * (qy * qz - qw * qx);
+  R[6] = 2 * (qx * qz - qw * qy); R[7] = 2 * (qy * qz + qw * qx); R[8] = 1 - 2 * (qx * qx + qy * qy);
+}
+
+template <class T>
+dvs_status grow_to(DeviceBuf<T>& b, size_t& cap, size_t need) { return grow(b, cap, need); }
+
+}  // namespace
+
 // landmark -> views CSR over the whole table into view_offs / view_kf / view_px / view_oid (nothing to do for an empty landmark table)
-dvs_status backend_views_build(dvs_backend* h) {
+dvs_status dvs::backend_views_build(dvs_backend* h) {
   hipStream_t st = h->ctx->stream;
   const int nlm = h->nlm, nob = h->nob;
   if (nlm == 0) return DVS_OK;
@@ -470,20 +409,6 @@ dvs_status backend_views_build(dvs_backend* h) {
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
-
-void quat_to_R(const double* q_xyzw, double* R) {   // extractPoseFromTransform (:1194-1215)
-  double qx = q_xyzw[0], qy = q_xyzw[1], qz = q_xyzw[2], qw = q_xyzw[3];
-  const double norm = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-  qw /= norm; qx /= norm; qy /= norm; qz /= norm;
-  R[0] = 1 - 2 * (qy * qy + qz * qz); R[1] = 2 * (qx * qy - qw * qz); R[2] = 2 * (qx * qz + qw * qy);
-  R[3] = 2 * (qx * qy + qw * qz); R[4] = 1 - 2 * (qx * qx + qz * qz); R[5] = 2 * (qy * qz - qw * qx);
-  R[6] = 2 * (qx * qz - qw * qy); R[7] = 2 * (qy * qz + qw * qx); R[8] = 1 - 2 * (qx * qx + qy * qy);
-}
-
-template <class T>
-dvs_status grow_to(DeviceBuf<T>& b, size_t& cap, size_t need) { return grow(b, cap, need); }
-
-}  // namespace
 
 extern "C" {
 

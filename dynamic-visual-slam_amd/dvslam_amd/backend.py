@@ -2,7 +2,7 @@
 and pruneLandmarks (backend.cpp) as one handle that keeps the landmark and observation tables on the device; one call per keyframe."""
 import ctypes as C
 import numpy as np
-from ._lib import lib, check, ptr, DvsError, KeyframeHeader
+from ._lib import lib, check, ptr, DvsError, KeyframeHeader, PgoParams, PgoSummary
 
 MAX_FILTERED = 16
 
@@ -31,6 +31,20 @@ class BackendCount(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n_keyframes", "n_observations", "n_landmarks", "next_observation_id", "next_landmark_id")]
 
 
+class FuseParams(C.Structure):
+    """dvs_fuse_params (fill it with dvs_fuse_default_params)"""
+    _fields_ = [("max_descriptor_distance", C.c_double), ("max_reprojection_distance", C.c_double), ("fuse_neighbours", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FuseResult(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_sources", "n_targets", "n_proposals", "n_fused")]
+
+
+class CloseLoopResult(C.Structure):
+    _fields_ = [("summary", PgoSummary), ("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("n_landmarks_moved", C.c_int32), ("reserved", C.c_int32),
+                ("fuse", FuseResult)]
+
+
 def _bind(L):
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
     pi32, pi64 = C.POINTER(i32), C.POINTER(i64)
@@ -47,7 +61,33 @@ def _bind(L):
     L.dvs_backend_get_landmarks.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, pi32, pi64]
     L.dvs_backend_get_observations.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, pi32]
     L.dvs_backend_get_keyframes.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, pi32, pi64]
+    dbl, u64 = C.c_double, C.c_uint64
+    L.dvs_fuse_default_params.argtypes = [C.POINTER(FuseParams)]
+    L.dvs_backend_get_anchors.argtypes = [vp, i32, vp, vp, pi32]
+    L.dvs_backend_build_pose_graph.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, pi32, pi32]
+    L.dvs_backend_close_loop.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, dbl, dbl, C.POINTER(PgoParams), C.POINTER(FuseParams), C.POINTER(CloseLoopResult)]
+    L.dvs_backend_fuse.argtypes = [vp, u64, vp, i32, C.POINTER(FuseParams), i32, C.POINTER(FuseResult), i32, vp, vp, vp, pi32]
     return L
+
+
+def fuse_params(**kw):
+    """dvs_fuse_default_params with field overrides"""
+    p = FuseParams()
+    check(_bind(lib()).dvs_fuse_default_params(C.byref(p)))
+    for k, v in kw.items():
+        if k not in dict(FuseParams._fields_) or k == "reserved":
+            raise TypeError(f"unknown parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _loop_arrays(loops):
+    """[(query frame id, entry frame id, rvec, tvec, w_rot, w_trans)] -> the six arrays of the C-ABI"""
+    q = np.array([l[0] for l in loops], np.uint64); e = np.array([l[1] for l in loops], np.uint64)
+    rv = np.array([np.asarray(l[2], np.float64).reshape(3) for l in loops], np.float64).reshape(-1, 3)
+    tv = np.array([np.asarray(l[3], np.float64).reshape(3) for l in loops], np.float64).reshape(-1, 3)
+    wr = np.array([l[4] for l in loops], np.float64); wt = np.array([l[5] for l in loops], np.float64)
+    return q, e, rv, tv, wr, wt
 
 
 def default_params(fx=0.0, fy=0.0, cx=0.0, cy=0.0, filtered_class_ids=(), **kw):
@@ -194,6 +234,61 @@ class MappingBackend:
         n = nn.value
         return dict(frame_id=fid[:n], stamp_ns=st[:n], R=R[:n], t=t[:n], obs_offsets=offs[:n + 1], obs_ids=oid[:nm.value])
 
+    # ---- loop closing on the map (include/dvslam_hip.h "Loop closing on the map")
+    def anchors(self):
+        """(landmark ids ascending, keyframe index of each landmark's lowest-id observation or -1)"""
+        n = max(self.counts()["n_landmarks"], 1)
+        lid = np.zeros(n, np.uint64); anc = np.zeros(n, np.int32); nn = C.c_int32()
+        check(self._L.dvs_backend_get_anchors(self._h, n, ptr(lid), ptr(anc), C.byref(nn)))
+        return lid[:nn.value], anc[:nn.value]
+
+    def build_pose_graph(self, loops, odo_w):
+        """loops: [(query frame id, entry frame id, rvec, tvec, w_rot, w_trans)], odo_w = (w_rot, w_trans) -> dict of the arrays
+        PoseGraph.set_nodes / set_edges take: R, t, fixed, ei, ej, rvec, tvec, w_rot, w_trans"""
+        q, e, rv, tv, wr, wt = _loop_arrays(loops)
+        cn = max(self.counts()["n_keyframes"], 1); ce = cn + len(loops)
+        R = np.zeros((cn, 3, 3)); t = np.zeros((cn, 3)); fixed = np.zeros(cn, np.uint8); ei = np.zeros(ce, np.int32); ej = np.zeros(ce, np.int32)
+        rvec = np.zeros((ce, 3)); tvec = np.zeros((ce, 3)); w_rot = np.zeros(ce); w_trans = np.zeros(ce); nn, ne = C.c_int32(), C.c_int32()
+        check(self._L.dvs_backend_build_pose_graph(self._h, len(loops), ptr(q), ptr(e), ptr(rv), ptr(tv), ptr(wr), ptr(wt), float(odo_w[0]), float(odo_w[1]), cn, ce,
+                                                   ptr(R), ptr(t), ptr(fixed), ptr(ei), ptr(ej), ptr(rvec), ptr(tvec), ptr(w_rot), ptr(w_trans), C.byref(nn), C.byref(ne)))
+        nn, ne = nn.value, ne.value
+        return dict(R=R[:nn], t=t[:nn], fixed=fixed[:nn], ei=ei[:ne], ej=ej[:ne], rvec=rvec[:ne], tvec=tvec[:ne], w_rot=w_rot[:ne], w_trans=w_trans[:ne])
+
+    def fuse(self, query, entries, apply=True, pairs=True, **params):
+        """dvs_backend_fuse: landmarks seen from the entry keyframes merged into the duplicates the query keyframe created -> dict of the four
+        counts and, unless pairs=False (the pair list then stays on the device), pairs = (survivor ids, removed ids, reprojection errors) in
+        ascending removed id"""
+        p = fuse_params(**params)
+        ent = np.array([int(f) for f in entries], np.uint64)
+        cap = max(self.counts()["n_landmarks"], 1) if pairs else 0
+        sv = np.zeros(cap, np.uint64); rm = np.zeros(cap, np.uint64); err = np.zeros(cap, np.float64); r = FuseResult(); n = C.c_int32()
+        check(self._L.dvs_backend_fuse(self._h, int(query), ptr(ent), len(ent), C.byref(p), 1 if apply else 0, C.byref(r), cap, ptr(sv) if pairs else None,
+                                       ptr(rm) if pairs else None, ptr(err) if pairs else None, C.byref(n)))
+        out = {k: int(getattr(r, k)) for k, _ in FuseResult._fields_}
+        if pairs:
+            out["pairs"] = (sv[:n.value], rm[:n.value], err[:n.value])
+        return out
+
+    def close_loop(self, pose_graph, loops, odo_w, pgo_params=None, fuse=None):
+        """dvs_backend_close_loop on a dvslam_amd.PoseGraph of the same device: pgo_params / fuse are dicts of field overrides (fuse=None: no
+        fusion, fuse={}: the defaults) -> dict(summary=PgoSummary, n_nodes, n_edges, n_landmarks_moved, n_sources, n_targets, n_proposals, n_fused)"""
+        q, e, rv, tv, wr, wt = _loop_arrays(loops)
+        pp = None
+        if pgo_params is not None:
+            pp = PgoParams()
+            check(self._L.dvs_pgo_default_params(C.byref(pp)))
+            for k, v in pgo_params.items():
+                if k not in dict(PgoParams._fields_):
+                    raise TypeError(f"unknown parameter {k}")
+                setattr(pp, k, v)
+        fp = fuse_params(**fuse) if fuse is not None else None
+        r = CloseLoopResult()
+        check(self._L.dvs_backend_close_loop(self._h, pose_graph._h, len(loops), ptr(q), ptr(e), ptr(rv), ptr(tv), ptr(wr), ptr(wt), float(odo_w[0]), float(odo_w[1]),
+                                             C.byref(pp) if pp is not None else None, C.byref(fp) if fp is not None else None, C.byref(r)))
+        out = dict(summary=r.summary, n_nodes=r.n_nodes, n_edges=r.n_edges, n_landmarks_moved=r.n_landmarks_moved)
+        out.update({k: int(getattr(r.fuse, k)) for k, _ in FuseResult._fields_})
+        return out
+
     def reset(self):
         check(self._L.dvs_backend_reset(self._h))
 
@@ -209,4 +304,4 @@ class MappingBackend:
             pass
 
 
-__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "default_params", "DvsError"]
+__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "default_params", "fuse_params", "DvsError"]

@@ -30,6 +30,22 @@ struct MapObservations {
 struct MapKeyframes {
   std::vector<uint64_t> frame_id, obs_ids; std::vector<int64_t> stamp_ns, obs_offsets; std::vector<double> R, t;
 };
+// dvslam_hip.h "Loop closing on the map": a loop as the pose graph takes it (x_query = R_z x_entry + t_z, rvec = Log(R_z)), the graph the
+// keyframes imply as the arrays of dvs_pgo_set_nodes / dvs_pgo_set_edges, the anchors, and the pairs a fusion kept
+struct MapLoop {
+  uint64_t query_frame_id, entry_frame_id;
+  double rvec[3], tvec[3], w_rot, w_trans;
+};
+struct MapPoseGraph {
+  std::vector<double> R, t, rvec, tvec, w_rot, w_trans; std::vector<uint8_t> fixed; std::vector<int32_t> ei, ej;
+};
+struct MapAnchors {
+  std::vector<uint64_t> id; std::vector<int32_t> keyframe;
+};
+struct MapFusion {
+  dvs_fuse_result counts;
+  std::vector<uint64_t> survivor_id, removed_id; std::vector<double> error;   // ascending removed id
+};
 
 class MappingBackend {
  public:
@@ -139,6 +155,44 @@ class MappingBackend {
                                     &nn, &nm), "dvs_backend_get_keyframes");
     K.obs_ids.resize((size_t)nm);
     return K;
+  }
+  // the keyframe index (row of keyframes()) of every landmark's lowest-id observation, -1 without one; landmarks in ascending id
+  MapAnchors anchors() const {
+    const size_t n = (size_t)counts().n_landmarks;
+    MapAnchors A;
+    A.id.resize(n); A.keyframe.resize(n);
+    int32_t nn = 0;
+    check(dvs_backend_get_anchors(h_, (int32_t)n, A.id.data(), A.keyframe.data(), &nn), "dvs_backend_get_anchors");
+    return A;
+  }
+  // all keyframes as nodes (node 0 fixed), odometry edges between consecutive keyframes, then the loops in the order given
+  MapPoseGraph buildPoseGraph(const std::vector<MapLoop>& loops, double odo_w_rot, double odo_w_trans) const {
+    std::vector<uint64_t> q, e; std::vector<double> rv, tv, wr, wt;
+    for (const MapLoop& l : loops) {
+      q.push_back(l.query_frame_id); e.push_back(l.entry_frame_id); rv.insert(rv.end(), l.rvec, l.rvec + 3); tv.insert(tv.end(), l.tvec, l.tvec + 3);
+      wr.push_back(l.w_rot); wt.push_back(l.w_trans);
+    }
+    const size_t cn = (size_t)counts().n_keyframes, ce = cn + loops.size();
+    MapPoseGraph G;
+    G.R.resize(cn * 9); G.t.resize(cn * 3); G.fixed.resize(cn); G.ei.resize(ce); G.ej.resize(ce); G.rvec.resize(ce * 3); G.tvec.resize(ce * 3); G.w_rot.resize(ce);
+    G.w_trans.resize(ce);
+    int32_t nn = 0, ne = 0;
+    check(dvs_backend_build_pose_graph(h_, (int32_t)loops.size(), q.data(), e.data(), rv.data(), tv.data(), wr.data(), wt.data(), odo_w_rot, odo_w_trans, (int32_t)cn,
+                                       (int32_t)ce, G.R.data(), G.t.data(), G.fixed.data(), G.ei.data(), G.ej.data(), G.rvec.data(), G.tvec.data(), G.w_rot.data(),
+                                       G.w_trans.data(), &nn, &ne), "dvs_backend_build_pose_graph");
+    G.ei.resize((size_t)ne); G.ej.resize((size_t)ne); G.rvec.resize((size_t)ne * 3); G.tvec.resize((size_t)ne * 3); G.w_rot.resize((size_t)ne); G.w_trans.resize((size_t)ne);
+    return G;
+  }
+  // landmarks seen from the entry keyframes merged into the duplicates the query keyframe created (apply = false: a dry run)
+  MapFusion fuse(uint64_t query_frame_id, const std::vector<uint64_t>& entry_frame_ids, const dvs_fuse_params* params = nullptr, bool apply = true) {
+    const size_t cap = (size_t)counts().n_landmarks;
+    MapFusion F;
+    F.survivor_id.resize(cap + 1); F.removed_id.resize(cap + 1); F.error.resize(cap + 1);
+    int32_t n = 0;
+    check(dvs_backend_fuse(h_, query_frame_id, entry_frame_ids.data(), (int32_t)entry_frame_ids.size(), params, apply ? 1 : 0, &F.counts, (int32_t)cap,
+                           F.survivor_id.data(), F.removed_id.data(), F.error.data(), &n), "dvs_backend_fuse");
+    F.survivor_id.resize((size_t)n); F.removed_id.resize((size_t)n); F.error.resize((size_t)n);
+    return F;
   }
   dvs_backend* handle() const { return h_; }
   const dvs_backend_params& params() const { return params_; }

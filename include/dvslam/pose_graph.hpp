@@ -16,10 +16,13 @@
 
 namespace dvslam {
 
+#ifndef DVSLAM_POSE_DEFINED   // sliding_window_ba.hpp defines the same struct: a translation unit may include both
+#define DVSLAM_POSE_DEFINED
 struct Pose {
   double R[9];   // row-major
   double t[3];
 };
+#endif
 
 class PoseGraph {
  public:

@@ -52,7 +52,10 @@ struct KeyframeData {
     std::memcpy(R, rotation, sizeof(R)); std::memcpy(t, translation, sizeof(t));
   }
 };
+#ifndef DVSLAM_POSE_DEFINED   // pose_graph.hpp defines the same struct: a translation unit may include both
+#define DVSLAM_POSE_DEFINED
 struct Pose { double R[9]; double t[3]; };
+#endif
 struct OptimizationResult {
   bool success = false;
   double final_cost = 0;

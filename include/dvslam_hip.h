@@ -1139,6 +1139,92 @@ dvs_status dvs_pgo_get_trace(const dvs_pgo* h, double* rows, int32_t cap_rows, i
 dvs_status dvs_pgo_correct_points(dvs_pgo* h, int32_t n, float* xyz, const int32_t* anchor);
 dvs_status dvs_pgo_correct_points_device(dvs_pgo* h, int32_t n, float* d_xyz, const int32_t* d_anchor);
 
+/* ======================================= Loop closing on the map ================================= */
+/* Verified loops applied to the map the mapping backend keeps on the device (csrc/loop_close.hip; INTEGRATION.md "Loop closure"): the
+ * step ORB-SLAM calls CorrectLoop (Mur-Artal, Montiel, Tardos 2015, section VII-C: pose-graph optimisation, then every map point moved
+ * with a keyframe that observes it) and the one it calls SearchAndFuse (duplicated map points merged), both as published ideas.  The
+ * reference has no loop closing, so there is no reference interface to pin: PARITY UNPINNED, the rule is the library's own, stated
+ * here in full and restated sequentially in tests/loop_closing_ref.py.
+ *  Anchors   The anchor of a landmark is the keyframe index (the row in dvs_backend_get_keyframes order) of its lowest-id observation
+ *            still in the observation table: the first view of its segment in the views CSR.  A landmark no observation names has -1.
+ *  Graph     Nodes: all keyframes in table order, R and t as dvs_backend_get_keyframes returns them (x_world = R x + t, unchanged); node
+ *            0 is fixed.  Edges k = 0 .. nkf - 2 are the odometry (k, k + 1) with R_z = R_a^T R_b and t_z = R_a^T (t_b - t_a) in double,
+ *            every product a left-to-right sum, rvec = Log(R_z) by the Log of the pose-graph residual above, weights odo_w_rot and
+ *            odo_w_trans.  Edges nkf - 1 .. are the loops in the order given: (index of the query frame, index of the entry frame, rvec,
+ *            tvec, w_rot, w_trans) unchanged — a verified dvs_loop_detect_verified result as it is.
+ *  Close     dvs_backend_close_loop builds that graph, solves it on the caller's dvs_pgo handle (same device; the backend owns none)
+ *            and, unless the solve FAILED (summary.termination == 2: the map stays byte for byte as it was and the call returns DVS_OK),
+ *            (1) makes the keyframe poses the bytes dvs_pgo_get_nodes returns, on the host copy and on the device, (2) runs
+ *            dvs_pgo_correct_points_device in place on the landmark table's position column with the device anchors — no position
+ *            crosses to the host — and (3), if fusion parameters are given, fuses once per loop in the order given with q = the query
+ *            keyframe and E = { k : |k - entry| <= fuse_neighbours, k != q } clipped to the table; each fusion sees the merges of the
+ *            one before.  The backend's stream is synchronised before its buffers go to the pose graph and the pose graph's before the
+ *            backend touches them again.
+ *  Fusion    For a query keyframe q and entry keyframes E (1 .. 64 distinct keyframes, q not among them):
+ *            TARGETS are the landmarks in the table named by at least one observation of q; SOURCES are the landmarks in the table named
+ *            by at least one observation of a keyframe of E and by none of q.  For a source A and an observation o of q whose landmark
+ *            B = o.landmark is in the table, (A, o) is a CANDIDATE iff all of
+ *              class(A) == class(o);
+ *              c2 > 0 for c = R_q^T (X_A - t_q): the landmark is in front of the camera (the (-1, -1) pixel dvs_associate gives a point
+ *                behind the camera never fuses anything);
+ *              e = |o.pixel - project(X_A)| < max_reprojection_distance, in the arithmetic of dvs_associate (include/dvslam/
+ *                association.hpp reprojection_error: double camera coordinates, float pixel, float difference, double norm);
+ *              hamming(desc(A), desc(o)) < max_descriptor_distance.  Both tests are strict.
+ *            Every source PROPOSES to the landmark B of its candidate with the smallest (e, o.id).  Every target KEEPS the proposal with
+ *            the smallest (e, A.id).  Sources and targets are disjoint and each is in at most one kept pair, so merges never chain.  Of a
+ *            kept pair the lower id is the SURVIVOR and the higher id is REMOVED: the survivor gets the sum of the two observation_counts
+ *            and the later last_seen and keeps its own position and descriptor; every observation naming the removed landmark names the
+ *            survivor instead; the removed row leaves the landmark table by an ordered compaction into the spare table, as in
+ *            dvs_backend_prune.  The observation table's other columns, the keyframes' observation_ids and both id counters are
+ *            untouched; two observations of one keyframe may then name one landmark, as the reference's association already allows.
+ *            Pairs are reported in ascending removed id with their e.  (e, id) is a total order and every minimum is an integer minimum
+ *            on the device: there is no tie deviation, and two identical calls on identical maps give identical bytes.
+ * Still out of scope: Sim(3), global BA, temporal consistency of candidates, re-triangulating the survivor, descriptor re-selection,
+ * several GPUs. */
+typedef struct dvs_fuse_params {
+  double max_descriptor_distance;      /* 50, the backend's */
+  double max_reprojection_distance;    /* 5, the backend's */
+  int32_t fuse_neighbours;             /* 2; read by dvs_backend_close_loop only; 0 .. 31 */
+  int32_t reserved;
+} dvs_fuse_params;
+typedef struct dvs_fuse_result {
+  int32_t n_sources, n_targets;        /* as defined above */
+  int32_t n_proposals, n_fused;        /* sources with a candidate / pairs kept */
+} dvs_fuse_result;
+typedef struct dvs_close_loop_result {
+  dvs_pgo_summary summary;
+  int32_t n_nodes, n_edges;
+  int32_t n_landmarks_moved;           /* landmarks with an anchor >= 0 */
+  int32_t reserved;
+  dvs_fuse_result fuse;                /* summed over the loops; zero without fusion */
+} dvs_close_loop_result;
+dvs_status dvs_fuse_default_params(dvs_fuse_params* p);
+/* Anchors of all landmarks in ascending id (count-then-capacity: *n is always set; either output may be NULL).  For tests and adapters:
+ * dvs_backend_close_loop uses the device array. */
+dvs_status dvs_backend_get_anchors(dvs_backend* h, int32_t cap, uint64_t* lm_id, int32_t* anchor_kf, int32_t* n);
+/* The graph stated above as the arrays dvs_pgo_set_nodes / dvs_pgo_set_edges take.  Host code only.  Loop arrays: n_loops rows (rvec and
+ * tvec 3 doubles each).  Count-then-capacity: *n_nodes = nkf and *n_edges = nkf - 1 + n_loops are set whenever the arguments are valid;
+ * every output may be NULL.  DVS_ERR_ARG before anything is written: fewer than 2 keyframes, an unknown frame id, query == entry, a
+ * weight not > 0, anything not finite. */
+dvs_status dvs_backend_build_pose_graph(dvs_backend* h, int32_t n_loops, const uint64_t* loop_query_frame_id, const uint64_t* loop_entry_frame_id,
+                                        const double* loop_rvec, const double* loop_tvec, const double* loop_w_rot, const double* loop_w_trans,
+                                        double odo_w_rot, double odo_w_trans, int32_t cap_nodes, int32_t cap_edges, double* R, double* t,
+                                        uint8_t* fixed, int32_t* ei, int32_t* ej, double* rvec, double* tvec, double* w_rot, double* w_trans,
+                                        int32_t* n_nodes, int32_t* n_edges);
+/* CorrectLoop as stated above ("Close").  pgo_params NULL: the defaults; fuse_params NULL: no fusion.  The argument errors of
+ * dvs_backend_build_pose_graph, and fusion thresholds that are not finite and > 0, are DVS_ERR_ARG before the map is touched. */
+dvs_status dvs_backend_close_loop(dvs_backend* h, dvs_pgo* pgo, int32_t n_loops, const uint64_t* loop_query_frame_id, const uint64_t* loop_entry_frame_id,
+                                  const double* loop_rvec, const double* loop_tvec, const double* loop_w_rot, const double* loop_w_trans,
+                                  double odo_w_rot, double odo_w_trans, const dvs_pgo_params* pgo_params, const dvs_fuse_params* fuse_params,
+                                  dvs_close_loop_result* out);
+/* SearchAndFuse as stated above ("Fusion").  params NULL: the defaults.  apply = 0 is a dry run: counts and pairs, the map not modified.
+ * survivor_id / removed_id / err: the kept pairs in ascending removed id, each nullable; *n_pairs (nullable) = their number.  If any of
+ * the three is given and cap_pairs is too small: DVS_ERR_CAPACITY, nothing applied.  DVS_ERR_ARG before any device work: an unknown frame
+ * id, q in the entry list, a repeated entry, n_entry outside 1 .. 64, thresholds not finite or not > 0. */
+dvs_status dvs_backend_fuse(dvs_backend* h, uint64_t query_frame_id, const uint64_t* entry_frame_ids, int32_t n_entry, const dvs_fuse_params* params,
+                            int32_t apply, dvs_fuse_result* out, int32_t cap_pairs, uint64_t* survivor_id, uint64_t* removed_id, double* err,
+                            int32_t* n_pairs);
+
 #ifdef __cplusplus
 }
 #endif
