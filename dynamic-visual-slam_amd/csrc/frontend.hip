@@ -333,7 +333,8 @@ __global__ __launch_bounds__(256) void k_harris(const uint8_t* __restrict__ img,
   const int lane = threadIdx.x & 63;
   const int r = blockSize / 2;
   const int x0 = xs[i], y0 = ys[i];
-  const bool inside = x0 - r - 1 >= 0 && y0 - r - 1 >= 0 && x0 - r + blockSize <= cols - 1 && y0 - r + blockSize <= rows - 1;
+  // x0 - r - 1 >= 0 && x0 - r + blockSize <= cols - 1 with the coordinate alone on its side: no x0, y0 can overflow the test
+  const bool inside = x0 >= r + 1 && y0 >= r + 1 && x0 <= cols - 1 - blockSize + r && y0 <= rows - 1 - blockSize + r;
   int a = 0, b = 0, c = 0;
   if (inside && lane < blockSize * blockSize) {
     const int wy = lane / blockSize, wx = lane - wy * blockSize;

@@ -1,6 +1,6 @@
 import ctypes as C
 import numpy as np
-from ._lib import lib, check, ptr, KP_DTYPE, KeyframeHeader
+from ._lib import lib, check, ptr, KP_DTYPE, KeyframeHeader, DvsError
 
 
 class FrontendGlue:
@@ -23,6 +23,14 @@ class FrontendGlue:
         L.dvs_keyframe_cdr_capacity.argtypes = [C.c_char_p, i32]; L.dvs_keyframe_cdr_capacity.restype = sz
         L.dvs_publish_keyframe.argtypes = [vp, C.POINTER(KeyframeHeader), vp, vp, i32, vp, i32, i32, sz, f32, f32, f32, f32, vp, vp, vp, sz,
                                            C.POINTER(sz), C.POINTER(i32)]
+        # the device forms (device pointers as integers) and the candidate-list form of the association
+        L.dvs_bgr_to_gray_device.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, sz, sz, i32]
+        L.dvs_filter_depth_batch_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, sz, sz, f32, f32, vp, vp, vp, vp]
+        L.dvs_publish_keyframe_device.argtypes = [vp, C.POINTER(KeyframeHeader), vp, vp, i32, vp, i32, i32, sz, f32, f32, f32, f32, vp, vp, vp, sz,
+                                                  vp, vp]
+        L.dvs_harris_responses_device.argtypes = [vp, vp, i32, i32, sz, vp, vp, i32, i32, f32, vp]
+        L.dvs_associate_candidates.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, dbl, dbl, dbl, dbl, dbl, dbl, vp, vp, vp, C.c_int64,
+                                               C.POINTER(C.c_int64)]
 
     def find_fundamental_ransac(self, pts1, pts2, threshold=2.0, confidence=0.99, max_iters=1000, seed=1):
         """cv::findFundamentalMat(pts1, pts2, mask, FM_RANSAC, threshold, confidence) -> (F 3x3, mask uint8[n], inliers of the model)"""
@@ -128,35 +136,63 @@ class FrontendGlue:
         except Exception:
             pass
 
-    def bgr_to_gray(self, bgr, variant=0):
+    def bgr_to_gray(self, bgr, variant=0, out=None):
+        """out: a caller's (rows, cols) uint8 array, rows possibly wider than cols (its row stride is the gray step)"""
         bgr = np.asarray(bgr); rows, cols, _ = bgr.shape
         assert bgr.dtype == np.uint8 and bgr.strides[2] == 1 and bgr.strides[1] == 3
-        gray = np.zeros((rows, cols), np.uint8)
-        check(self._L.dvs_bgr_to_gray(self._h, ptr(bgr), rows, cols, bgr.strides[0], ptr(gray), cols, variant))
+        gray = np.zeros((rows, cols), np.uint8) if out is None else out
+        assert gray.dtype == np.uint8 and gray.shape == (rows, cols) and gray.strides[1] == 1
+        check(self._L.dvs_bgr_to_gray(self._h, ptr(bgr), rows, cols, bgr.strides[0], ptr(gray), gray.strides[0], variant))
         return gray
 
-    def filter_depth(self, kps, desc, depth, min_depth=0.3, max_depth=3.0):
+    def filter_depth(self, kps, desc, depth, min_depth=0.3, max_depth=3.0, with_index=True, out=None):
+        """out: the caller's (keypoints, descriptors, indices) arrays of n rows to compact into (rows past the count stay untouched)"""
         kps = np.ascontiguousarray(kps, KP_DTYPE); n = len(kps)
         desc = np.ascontiguousarray(desc, np.uint8) if desc is not None else None
         depth = np.asarray(depth); assert depth.dtype == np.uint16 and depth.strides[1] == 2
-        ok = np.zeros(n, KP_DTYPE); od = np.zeros((n, 32), np.uint8); oi = np.zeros(n, np.int32); m = C.c_int32()
+        ok, od, oi = out if out is not None else (np.zeros(n, KP_DTYPE), np.zeros((n, 32), np.uint8), np.zeros(n, np.int32))
+        m = C.c_int32()
         check(self._L.dvs_filter_depth(self._h, ptr(kps), ptr(desc) if desc is not None else None, n, ptr(depth), depth.shape[0], depth.shape[1],
-                                       depth.strides[0], min_depth, max_depth, ptr(ok), ptr(od), ptr(oi), C.byref(m)))
+                                       depth.strides[0], min_depth, max_depth, ptr(ok), ptr(od), ptr(oi) if with_index else None, C.byref(m)))
         return ok[:m.value], od[:m.value], oi[:m.value]
 
-    def filter_matches(self, idx, dist, max_distance=50.0):
+    def filter_matches(self, idx, dist, max_distance=50.0, out=None):
         idx = np.ascontiguousarray(idx, np.int32); dist = np.ascontiguousarray(dist, np.int32); n = len(idx)
-        out = np.zeros((n, 3), np.int32); m = C.c_int32()
+        out = np.zeros((n, 3), np.int32) if out is None else out
+        m = C.c_int32()
         check(self._L.dvs_filter_matches(self._h, ptr(idx), ptr(dist), n, max_distance, ptr(out), C.byref(m)))
         return out[:m.value]
 
-    def backproject(self, kps, depth, fx, fy, cx, cy, R, t):
+    def backproject(self, kps, depth, fx, fy, cx, cy, R, t, out=None):
         kps = np.ascontiguousarray(kps, KP_DTYPE); n = len(kps)
         depth = np.asarray(depth); R = np.ascontiguousarray(R, np.float64); t = np.ascontiguousarray(t, np.float64).reshape(3)
-        w = np.zeros((n, 3), np.float64); oi = np.zeros(n, np.int32); m = C.c_int32()
+        w, oi = out if out is not None else (np.zeros((n, 3), np.float64), np.zeros(n, np.int32))
+        m = C.c_int32()
         check(self._L.dvs_backproject(self._h, ptr(kps), n, ptr(depth), depth.shape[0], depth.shape[1], depth.strides[0], fx, fy, cx, cy,
                                       ptr(R), ptr(t), ptr(w), ptr(oi), C.byref(m)))
         return w[:m.value], oi[:m.value]
+
+    # ---- device forms: device pointers (integers, e.g. DeviceBuffer.ptr), asynchronous on the handle's stream
+    def synchronize(self):
+        check(self._L.dvs_matcher_synchronize(self._h))
+
+    def bgr_to_gray_device(self, d_bgr, nimg, rows, cols, step, frame_stride, d_gray, gray_step, gray_frame_stride, variant=0):
+        check(self._L.dvs_bgr_to_gray_device(self._h, d_bgr, nimg, rows, cols, step, frame_stride, d_gray, gray_step, gray_frame_stride, variant))
+
+    def filter_depth_batch_device(self, d_kps, d_desc, d_n, stride_rows, nframes, d_depth, rows, cols, step_bytes, frame_stride_bytes,
+                                  d_out_kps, d_out_desc, d_out_index, d_n_out, min_depth=0.3, max_depth=3.0):
+        check(self._L.dvs_filter_depth_batch_device(self._h, d_kps, d_desc, d_n, stride_rows, nframes, d_depth, rows, cols, step_bytes,
+                                                    frame_stride_bytes, min_depth, max_depth, d_out_kps, d_out_desc, d_out_index, d_n_out))
+
+    def publish_keyframe_device(self, d_kps, d_desc, n, d_depth, rows, cols, step_bytes, fx, fy, cx, cy, R, t, d_out, cap, d_out_size, d_n_out,
+                                stamp=(0, 0), frame_id="camera_link", keyframe_id=0, q_xyzw=(0.0, 0.0, 0.0, 1.0)):
+        R = np.ascontiguousarray(R, np.float64); t = np.ascontiguousarray(t, np.float64).reshape(3)
+        hdr = self._header(stamp, frame_id, keyframe_id, t, q_xyzw)
+        check(self._L.dvs_publish_keyframe_device(self._h, C.byref(hdr), d_kps, d_desc, n, d_depth, rows, cols, step_bytes, fx, fy, cx, cy,
+                                                  ptr(R), ptr(t), d_out, cap, d_out_size, d_n_out))
+
+    def harris_responses_device(self, d_img, rows, cols, step, d_x, d_y, n, d_response, block_size=7, k=0.04):
+        check(self._L.dvs_harris_responses_device(self._h, d_img, rows, cols, step, d_x, d_y, n, block_size, k, d_response))
 
     def harris_responses(self, img, xs, ys, block_size=7, k=0.04):
         """cv::ORB's HARRIS_SCORE measure at integer pixel positions of one image (pyramid layer)"""
@@ -178,16 +214,22 @@ class FrontendGlue:
         return h
 
     def publish_keyframe(self, kps, desc, depth, fx, fy, cx, cy, R, t, stamp=(0, 0), frame_id="camera_link", keyframe_id=0,
-                         q_xyzw=(0.0, 0.0, 0.0, 1.0)):
-        """publishKeyframe (frontend.cpp:699-776) as the Keyframe.msg CDR payload: returns (bytes, n_landmarks)"""
+                         q_xyzw=(0.0, 0.0, 0.0, 1.0), cap=None):
+        """publishKeyframe (frontend.cpp:699-776) as the Keyframe.msg CDR payload: returns (bytes, n_landmarks); cap: the buffer's size
+        (default: dvs_keyframe_cdr_capacity)"""
         kps = np.ascontiguousarray(kps, KP_DTYPE); n = len(kps)
         desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         depth = np.asarray(depth); R = np.ascontiguousarray(R, np.float64); t = np.ascontiguousarray(t, np.float64).reshape(3)
         hdr = self._header(stamp, frame_id, keyframe_id, t, q_xyzw)
-        cap = self._L.dvs_keyframe_cdr_capacity(hdr.frame_id, n)
-        out = np.zeros(cap, np.uint8); size = C.c_size_t(); m = C.c_int32()
-        check(self._L.dvs_publish_keyframe(self._h, C.byref(hdr), ptr(kps), ptr(desc), n, ptr(depth), depth.shape[0], depth.shape[1],
-                                           depth.strides[0], fx, fy, cx, cy, ptr(R), ptr(t), ptr(out), cap, C.byref(size), C.byref(m)))
+        if cap is None:
+            cap = self._L.dvs_keyframe_cdr_capacity(hdr.frame_id, n)
+        out = np.zeros(max(cap, 1), np.uint8); size = C.c_size_t(); m = C.c_int32()
+        try:
+            check(self._L.dvs_publish_keyframe(self._h, C.byref(hdr), ptr(kps), ptr(desc), n, ptr(depth), depth.shape[0], depth.shape[1],
+                                               depth.strides[0], fx, fy, cx, cy, ptr(R), ptr(t), ptr(out), cap, C.byref(size), C.byref(m)))
+        except DvsError as e:
+            e.needed = size.value                                  # DVS_ERR_CAPACITY reports the size the payload needs
+            raise
         return out[:size.value].tobytes(), m.value
 
     def associate(self, obs_desc, obs_px, lm_desc, lm_xyz, R, t, fx, fy, cx, cy, max_desc=50.0, max_reproj=5.0):
@@ -198,6 +240,24 @@ class FrontendGlue:
         check(self._L.dvs_associate(self._h, ptr(obs_desc), ptr(obs_px), len(obs_desc), ptr(lm_desc), ptr(lm_xyz), len(lm_desc), ptr(R), ptr(t),
                                     fx, fy, cx, cy, max_desc, max_reproj, ptr(best)))
         return best
+
+    def associate_candidates(self, obs_desc, obs_px, lm_desc, lm_xyz, R, t, fx, fy, cx, cy, max_desc=50.0, max_reproj=5.0, cand_cap=None):
+        """dvs_associate_candidates -> (best, candidate offsets int64 (nobs + 1,), candidate landmarks int32); cand_cap: the list's
+        capacity (default nobs * nlm, which always suffices)"""
+        obs_desc = np.ascontiguousarray(obs_desc, np.uint8).reshape(-1, 32); obs_px = np.ascontiguousarray(obs_px, np.float32).reshape(-1, 2)
+        lm_desc = np.ascontiguousarray(lm_desc, np.uint8).reshape(-1, 32); lm_xyz = np.ascontiguousarray(lm_xyz, np.float32).reshape(-1, 3)
+        R = np.ascontiguousarray(R, np.float64); t = np.ascontiguousarray(t, np.float64).reshape(3)
+        nobs, nlm = len(obs_desc), len(lm_desc)
+        if cand_cap is None:
+            cand_cap = nobs * nlm
+        best = np.full(nobs, -1, np.int32); offs = np.zeros(nobs + 1, np.int64); cand = np.zeros(max(cand_cap, 1), np.int32); n = C.c_int64()
+        try:
+            check(self._L.dvs_associate_candidates(self._h, ptr(obs_desc), ptr(obs_px), nobs, ptr(lm_desc), ptr(lm_xyz), nlm, ptr(R), ptr(t),
+                                                   fx, fy, cx, cy, max_desc, max_reproj, ptr(best), ptr(offs), ptr(cand), cand_cap, C.byref(n)))
+        except DvsError as e:
+            e.n_cand = n.value                                     # DVS_ERR_CAPACITY reports the entries the list needs
+            raise
+        return best, offs, cand[:n.value]
 
     def triangulate_landmarks(self, R, t, fx, fy, cx, cy, view_offsets, view_kf, view_px, lm_xyz):
         """LandmarkInfo::triangulate (backend.cpp:439-613) for every landmark: R (nkf x 3 x 3, x_cam = R X + t), t (nkf x 3); landmark l's

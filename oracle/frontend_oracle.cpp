@@ -57,13 +57,16 @@ int orc_filter_matches(const int32_t* train_idx, const int32_t* dist, int n, flo
   return m;
 }
 
-// publishKeyframe: depth back-projection (float), range gate (double compare), world = R * p + t (double, row-major R)
-int orc_backproject(const orc_kp* kps, int n, const uint16_t* depth, size_t step_bytes, float fx, float fy, float cx, float cy,
+// publishKeyframe: depth back-projection (float), range gate (double compare), world = R * p + t (double, row-major R).
+// A keypoint whose rounded pixel lies outside the depth image is dropped, as include/dvslam_hip.h promises for every entry point
+// (frontend.cpp:737 indexes the image unchecked there: undefined behaviour, nothing to restate).
+int orc_backproject(const orc_kp* kps, int n, const uint16_t* depth, int rows, int cols, size_t step_bytes, float fx, float fy, float cx, float cy,
                     const double* R, const double* t, double* world_xyz, int32_t* out_index) {
   int m = 0;
   for (int i = 0; i < n; i++) {
     const float px = kps[i].x, py = kps[i].y;
     const int x = static_cast<int>(std::round(px)), y = static_cast<int>(std::round(py));
+    if (x < 0 || y < 0 || x >= cols || y >= rows) continue;
     const float pt_depth = *(const uint16_t*)((const uint8_t*)depth + (size_t)y * step_bytes + 2 * (size_t)x) * 0.001f;
     const float X = (px - cx) * pt_depth / fx, Y = (py - cy) * pt_depth / fy, Z = pt_depth;
     if (Z > 0.3 && Z < 3.0) {
@@ -144,13 +147,14 @@ extern "C" {
 // returns the payload size (written to out if it fits in cap); *n_lm = landmarks in the message
 size_t orc_publish_keyframe_cdr(int32_t sec, uint32_t nanosec, const char* header_frame_id, uint64_t keyframe_id, const double* trans,
                                 const double* rot_xyzw, const orc_kp* kps, const uint8_t* desc, int n, const uint16_t* depth,
-                                size_t step_bytes, float fx, float fy, float cx, float cy, const double* R, const double* t, uint8_t* out,
+                                int rows, int cols, size_t step_bytes, float fx, float fy, float cx, float cy, const double* R, const double* t, uint8_t* out,
                                 size_t cap, int32_t* n_lm) {
   std::vector<LandmarkMsg> landmarks;
   std::vector<ObservationMsg> observations;
   for (int i = 0; i < n; i++) {  // frontend.cpp:732-776
     const float px = kps[i].x, py = kps[i].y;
     const int x = static_cast<int>(std::round(px)), y = static_cast<int>(std::round(py));
+    if (x < 0 || y < 0 || x >= cols || y >= rows) continue;
     const float pt_depth = *(const uint16_t*)((const uint8_t*)depth + (size_t)y * step_bytes + 2 * (size_t)x) * 0.001f;
     const float X = (px - cx) * pt_depth / fx, Y = (py - cy) * pt_depth / fy, Z = pt_depth;
     if (Z > 0.3 && Z < 3.0) {

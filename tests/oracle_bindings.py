@@ -304,10 +304,10 @@ def _glue_lib():
     L.orc_bgr_to_gray.argtypes = [vp, i32, i32, sz, vp, sz, i32]
     L.orc_filter_depth.restype = i32; L.orc_filter_depth.argtypes = [vp, vp, i32, vp, i32, i32, sz, f32, f32, vp, vp, vp]
     L.orc_filter_matches.restype = i32; L.orc_filter_matches.argtypes = [vp, vp, i32, f32, vp]
-    L.orc_backproject.restype = i32; L.orc_backproject.argtypes = [vp, i32, vp, sz, f32, f32, f32, f32, vp, vp, vp, vp]
+    L.orc_backproject.restype = i32; L.orc_backproject.argtypes = [vp, i32, vp, i32, i32, sz, f32, f32, f32, f32, vp, vp, vp, vp]
     L.orc_associate.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, dbl, dbl, dbl, dbl, dbl, dbl, vp]
     L.orc_publish_keyframe_cdr.restype = sz
-    L.orc_publish_keyframe_cdr.argtypes = [i32, C.c_uint32, C.c_char_p, C.c_uint64, vp, vp, vp, vp, i32, vp, sz, f32, f32, f32, f32, vp, vp, vp, sz, vp]
+    L.orc_publish_keyframe_cdr.argtypes = [i32, C.c_uint32, C.c_char_p, C.c_uint64, vp, vp, vp, vp, i32, vp, i32, i32, sz, f32, f32, f32, f32, vp, vp, vp, sz, vp]
     L.orc_unpack_keyframe_cdr.restype = i32
     L.orc_unpack_keyframe_cdr.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
     return L
@@ -328,7 +328,7 @@ def publish_keyframe(kps, desc, depth, fx, fy, cx, cy, R, t, stamp=(0, 0), frame
     R = np.ascontiguousarray(R, np.float64); t = np.ascontiguousarray(t, np.float64).reshape(3); q = np.ascontiguousarray(q_xyzw, np.float64)
     n = len(kps); cap = 256 + 96 * (n + 1); out = np.zeros(cap, np.uint8); m = C.c_int32()
     size = _glue_lib().orc_publish_keyframe_cdr(int(stamp[0]), int(stamp[1]), frame_id.encode(), int(keyframe_id), _p(t), _p(q), _p(kps), _p(desc), n,
-                                                _p(depth), depth.shape[1] * 2, fx, fy, cx, cy, _p(R), _p(t), _p(out), cap, C.byref(m))
+                                                _p(depth), depth.shape[0], depth.shape[1], depth.shape[1] * 2, fx, fy, cx, cy, _p(R), _p(t), _p(out), cap, C.byref(m))
     assert size <= cap
     return out[:size].tobytes(), m.value
 
@@ -371,7 +371,7 @@ def backproject(kps, depth, fx, fy, cx, cy, R, t):
     kps = np.ascontiguousarray(kps, KP_DTYPE); depth = np.ascontiguousarray(depth, np.uint16)
     R = np.ascontiguousarray(R, np.float64); t = np.ascontiguousarray(t, np.float64)
     n = len(kps); w = np.zeros((n, 3)); oi = np.zeros(n, np.int32)
-    m = _glue_lib().orc_backproject(_p(kps), n, _p(depth), depth.shape[1] * 2, fx, fy, cx, cy, _p(R), _p(t), _p(w), _p(oi))
+    m = _glue_lib().orc_backproject(_p(kps), n, _p(depth), depth.shape[0], depth.shape[1], depth.shape[1] * 2, fx, fy, cx, cy, _p(R), _p(t), _p(w), _p(oi))
     return w[:m], oi[:m]
 
 

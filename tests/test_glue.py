@@ -3,6 +3,8 @@ CPU: known-answers of the oracle restatements; GPU: HIP entry points vs the orac
 doubles produced by identically ordered operations)."""
 import numpy as np
 import pytest
+import glue_ref
+from glue_ref import hand_cdr as _hand_cdr, harris as _harris_numpy   # independent statements: CDR rules; gradient maps + box sums
 from dvslam_amd import synth
 
 
@@ -28,9 +30,9 @@ def test_oracle_known_answers(oracle):
     assert oracle.bgr_to_gray(bgr, 1)[1, 1] == (10 * 1868 + 20 * 9617 + 30 * 4899 + 8192) >> 14
     kps, desc, depth = _scene()
     ok, od, oi = oracle.filter_depth(kps, desc, depth)
-    x = np.floor(np.abs(kps["x"]) + 0.5).astype(int); y = np.floor(np.abs(kps["y"]) + 0.5).astype(int)
-    inside = (x < 640) & (y < 480)
-    d = depth[np.minimum(y, 479), np.minimum(x, 639)].astype(np.float32) * np.float32(0.001)
+    x = glue_ref.round_px(kps["x"]); y = glue_ref.round_px(kps["y"])                       # std::round, exact (not float32 floor(|x| + 0.5))
+    inside = (x >= 0) & (y >= 0) & (x < 640) & (y < 480)
+    d = depth[np.clip(y, 0, 479), np.clip(x, 0, 639)].astype(np.float32) * np.float32(0.001)
     keep = inside & ~((d < np.float32(0.3)) | (d > np.float32(3.0)))
     assert (oi == np.nonzero(keep)[0]).all() and (od == desc[keep]).all() and ok.tobytes() == kps[keep].tobytes()
     idx = np.arange(6, dtype=np.int32)[::-1].copy(); dist = np.array([49, 50, 0, 256, 51, 12], np.int32)
@@ -89,32 +91,6 @@ def test_association_parity(gpu, oracle, nobs, nlm, seed):
 
 
 # ---------------------------------------------------------------- Keyframe.msg on the wire (row N3) ------------------------------
-def _hand_cdr(stamp, frame_id, kf_id, trans, rot, landmarks, observations):
-    """Third, independent statement of the layout, straight from the CDR rules: align every primitive to its size relative to
-    the byte after the 4-byte encapsulation header."""
-    import struct
-    b = bytearray()
-
-    def put(fmt, v):
-        size = struct.calcsize(fmt)
-        while len(b) % size:
-            b.append(0)
-        b.extend(struct.pack("<" + fmt, v))
-
-    put("i", stamp[0]); put("I", stamp[1])
-    put("I", len(frame_id) + 1); b.extend(frame_id.encode() + b"\0")
-    put("Q", kf_id)
-    for v in trans: put("d", v)
-    for v in rot: put("d", v)
-    put("I", len(landmarks))
-    for lid, x, y, z in landmarks:
-        put("Q", lid); put("d", x); put("d", y); put("d", z)
-    put("I", len(observations))
-    for lid, u, v, d in observations:
-        put("Q", lid); put("d", u); put("d", v); put("I", len(d)); b.extend(bytes(d))
-    return bytes([0, 1, 0, 0]) + bytes(b)
-
-
 def _kf_case(n, seed, all_invalid=False):
     kps, desc, depth = _scene(seed, max(n, 8))
     kps, desc = kps[:n], desc[:n]
@@ -182,26 +158,6 @@ def test_publish_keyframe_parity(gpu, oracle, n, seed, fid, all_invalid):
 
 
 # ---------------------------------------------------------------- Harris score (row N4) ---------------------------------------
-def _harris_numpy(img, xs, ys, bs=7, k=np.float32(0.04)):
-    """independent statement: whole-image integer gradient maps, box sums, float32 expression in the source's order"""
-    I = img.astype(np.int64)
-    Ix = np.zeros_like(I); Iy = np.zeros_like(I)
-    Ix[1:-1, 1:-1] = (I[1:-1, 2:] - I[1:-1, :-2]) * 2 + (I[:-2, 2:] - I[:-2, :-2]) + (I[2:, 2:] - I[2:, :-2])
-    Iy[1:-1, 1:-1] = (I[2:, 1:-1] - I[:-2, 1:-1]) * 2 + (I[2:, :-2] - I[:-2, :-2]) + (I[2:, 2:] - I[:-2, 2:])
-    r = bs // 2
-    out = np.zeros(len(xs), np.float32)
-    scale = np.float32(1.0) / (np.float32(4 * bs) * np.float32(255.0))
-    s4 = scale * scale * scale * scale
-    for i, (x, y) in enumerate(zip(xs, ys)):
-        if not (x - r - 1 >= 0 and y - r - 1 >= 0 and x - r + bs <= img.shape[1] - 1 and y - r + bs <= img.shape[0] - 1):
-            continue
-        wx = Ix[y - r:y - r + bs, x - r:x - r + bs]; wy = Iy[y - r:y - r + bs, x - r:x - r + bs]
-        a = np.float32(int((wx * wx).sum())); b = np.float32(int((wy * wy).sum())); c = np.float32(int((wx * wy).sum()))
-        s = a + b
-        out[i] = (a * b - c * c - (k * s) * s) * s4
-    return out
-
-
 def test_harris_oracle_known_answers(oracle):
     ramp = np.tile(np.arange(64, dtype=np.uint8), (48, 1))                 # I = x: Ix = 8, Iy = 0 everywhere
     r = oracle.harris_responses(ramp, [20, 30], [20, 10])
