@@ -1186,6 +1186,299 @@ __global__ __launch_bounds__(256) void k_lm_gmax(int K, int L, const double* __r
 
 __global__ void k_lm_reset(LmStatus* st) { st->ok = 1; st->finite = 1; st->model_change = 0; st->sn = 0; st->xn = 0; st->cand_cost = 0; st->seq = 0; st->accept = 0; }
 
+// =============================================================================================================================
+// Global BA (dvs_ba_solve_global): the camera steps of a trial step by preconditioned conjugate gradients on the reduced camera
+// system S, which is never formed (include/dvslam_hip.h, "Global BA", states the rule).  Around the linear solve the kernels above
+// run unchanged.  One PCG iteration is three plain launches — k_gba_lm (u_l = Vinv_l sum_f Ws_f^T p), k_gba_cam (per chunk
+// sum_e Ws_e u_l(e)), k_gba_update (q = S p, alpha, x, r, z, beta, p, stopping rule) — each of which returns at once when the
+// record says the solve has stopped, so the host enqueues them in batches and reads one small record per batch.
+// Every sum has a fixed order: a landmark's observations in lmStart / lmObs order, a chunk by a fixed shuffle tree, a camera's
+// chunks in chunk order, dot products by per-thread strides and block_sum_fixed.  No floating-point atomics.
+// =============================================================================================================================
+struct PcgState { double rz, bnorm2, rnorm2; int iter, done, ok, pad; };
+struct GbaDev {
+  int K, L;
+  const BaChunk* chunks;
+  const int *camChunkStart, *cam, *lm, *lmStart, *lmObs;
+  const unsigned char* active;
+  const double *Hpp, *g, *scale, *diag, *Vinv, *Ws, *Y;
+  double *Minv, *b, *x, *r, *z, *p, *u, *qpart, *qv;
+  PcgState* pcg;
+  LmStatus* st;
+};
+
+// M_c^-1 and b_c, a wavefront per camera: lane i sums the camera's observations i, i + 64, .. (Y_e Ws_e^T: 36 values, Y_e g_l: 6), the
+// wavefront's 42 totals by the transposing butterfly, then one lane inverts M_c = Hpp_c scaled + D_c / radius - sum by Cholesky (the
+// arithmetic of k_pgo_precond, pose_graph.hip: the inverse of the diagonal alone if a pivot is not positive).  Cameras that do not
+// move get zero blocks.
+__global__ __launch_bounds__(256) void k_gba_precond(GbaDev P, double radius) {
+  __shared__ double sm[4][48];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c = blockIdx.x * 4 + wv;
+  const bool camOn = c < P.K && P.active[6 * min(c, P.K - 1)] != 0;
+  double acc[36], rr[6];
+#pragma unroll
+  for (int k = 0; k < 36; k++) acc[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) rr[k] = 0.0;
+  if (camOn) {
+    const int c0 = P.camChunkStart[c], c1 = P.camChunkStart[c + 1];
+    if (c1 > c0) {
+      const int e0 = P.chunks[c0].start, e1 = P.chunks[c1 - 1].start + P.chunks[c1 - 1].count;
+      for (int e = e0 + lane; e < e1; e += 64) {
+        const int j0 = 6 * P.K + 3 * P.lm[e];
+        if (!P.active[j0]) continue;
+        const double* y = P.Y + 18 * (size_t)e;
+        const double* w = P.Ws + 18 * (size_t)e;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+          for (int b = 0; b < 6; b++) acc[6 * a + b] += y[3 * a] * w[3 * b] + y[3 * a + 1] * w[3 * b + 1] + y[3 * a + 2] * w[3 * b + 2];
+        const double gl0 = P.g[j0] * P.scale[j0], gl1 = P.g[j0 + 1] * P.scale[j0 + 1], gl2 = P.g[j0 + 2] * P.scale[j0 + 2];
+#pragma unroll
+        for (int a = 0; a < 6; a++) rr[a] += y[3 * a] * gl0 + y[3 * a + 1] * gl1 + y[3 * a + 2] * gl2;
+      }
+    }
+  }
+  {
+    double q[32];
+#pragma unroll
+    for (int k = 0; k < 32; k++) q[k] = acc[k];
+    const double t0 = wave_butterfly32(q, lane);
+#pragma unroll
+    for (int k = 0; k < 32; k++) q[k] = k < 4 ? acc[32 + k] : (k < 10 ? rr[k - 4] : 0.0);
+    const double t1 = wave_butterfly32(q, lane);
+    const int k = butterfly32_index(lane);
+    if ((lane & 1) == 0) { sm[wv][k] = t0; if (k < 10) sm[wv][32 + k] = t1; }
+  }
+  __syncthreads();
+  if (c >= P.K || lane != 0) return;
+  double* out = P.Minv + 36 * (size_t)c;
+  if (!camOn) {
+    for (int k = 0; k < 36; k++) out[k] = 0.0;
+    for (int a = 0; a < 6; a++) P.b[6 * c + a] = 0.0;
+    return;
+  }
+  double Lm[36], Li[36], dg[6];
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++) {
+      double v = P.Hpp[36 * (size_t)c + 6 * a + b] * P.scale[6 * c + a] * P.scale[6 * c + b];
+      if (a == b) v += P.diag[6 * c + a] / radius;
+      Lm[6 * a + b] = v - sm[wv][6 * a + b];
+      Li[6 * a + b] = 0.0;
+    }
+#pragma unroll
+  for (int a = 0; a < 6; a++) { dg[a] = Lm[7 * a]; P.b[6 * c + a] = P.g[6 * c + a] * P.scale[6 * c + a] - sm[wv][36 + a]; }
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    double d = Lm[7 * j];
+#pragma unroll
+    for (int k = 0; k < j; k++) d -= Lm[6 * j + k] * Lm[6 * j + k];
+    if (!(d > 0)) ok = false;
+    d = sqrt(d);
+    Lm[7 * j] = d;
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double s = Lm[6 * i + j];
+#pragma unroll
+      for (int k = 0; k < j; k++) s -= Lm[6 * i + k] * Lm[6 * j + k];
+      Lm[6 * i + j] = s / d;
+    }
+  }
+#pragma unroll
+  for (int cc = 0; cc < 6; cc++) {
+#pragma unroll
+    for (int i = cc; i < 6; i++) {
+      double s = (i == cc) ? 1.0 : 0.0;
+#pragma unroll
+      for (int k = cc; k < i; k++) s -= Lm[6 * i + k] * Li[6 * k + cc];
+      Li[6 * i + cc] = s / Lm[7 * i];
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++) {
+      double s = 0;
+#pragma unroll
+      for (int k = 0; k < 6; k++) if (k >= a && k >= b) s += Li[6 * k + a] * Li[6 * k + b];
+      out[6 * a + b] = ok ? s : (a == b ? 1.0 / dg[a] : 0.0);
+    }
+}
+
+// landmark pass, a quad of lanes per landmark as in k_lm_backsub: u_l = Vinv_l sum_{f of l, camera free} Ws_f^T p_cam(f)
+__global__ __launch_bounds__(256) void k_gba_lm(GbaDev P) {
+  if (P.pcg->done) return;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int l = t >> 2, m = t & 3;
+  const bool on = l < P.L && m < 3;
+  const int lc = min(l, P.L - 1), mc = min(m, 2);
+  const int j0 = 6 * P.K + 3 * lc;
+  const bool act = P.active[j0] != 0;
+  double tm = 0.0;
+  if (act) {
+    const int e0 = P.lmStart[lc], e1 = P.lmStart[lc + 1];
+    for (int e = e0; e < e1; e++) {
+      const int p = P.lmObs[e], c = P.cam[p];
+      if (!P.active[6 * c]) continue;
+      const double* w = P.Ws + 18 * (size_t)p + mc;
+      const double* pv = P.p + 6 * (size_t)c;
+#pragma unroll
+      for (int a = 0; a < 6; a++) tm += w[3 * a] * pv[a];
+    }
+  }
+  const int base = (int)(threadIdx.x & 63) & ~3;
+  const double t0 = __shfl(tm, base), t1 = __shfl(tm, base + 1), t2 = __shfl(tm, base + 2);
+  const double* Vi = P.Vinv + 9 * (size_t)lc;
+  const double um = act ? Vi[3 * mc] * t0 + Vi[3 * mc + 1] * t1 + Vi[3 * mc + 2] * t2 : 0.0;
+  if (on) P.u[3 * (size_t)l + m] = um;
+}
+
+// camera pass, a workgroup per chunk: sum_e Ws_e u_l(e) over the chunk's observations, each of the six values by a fixed tree (lane
+// bits 5 .. 0, then the four wavefronts in order); k_gba_update folds a camera's chunks in chunk order
+__global__ __launch_bounds__(256) void k_gba_cam(GbaDev P) {
+  if (P.pcg->done) return;
+  __shared__ double wred[4][6];
+  const BaChunk ch = P.chunks[blockIdx.x];
+  const int tid = threadIdx.x;
+  double v[6] = {0, 0, 0, 0, 0, 0};
+  if (tid < ch.count && P.active[6 * ch.cam]) {
+    const int e = ch.start + tid, l = P.lm[e];
+    if (P.active[6 * P.K + 3 * l]) {
+      const double u0 = P.u[3 * (size_t)l], u1 = P.u[3 * (size_t)l + 1], u2 = P.u[3 * (size_t)l + 2];
+      const double* w = P.Ws + 18 * (size_t)e;
+#pragma unroll
+      for (int a = 0; a < 6; a++) v[a] = w[3 * a] * u0 + w[3 * a + 1] * u1 + w[3 * a + 2] * u2;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v[a] += __shfl_xor(v[a], o);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int a = 0; a < 6; a++) wred[tid >> 6][a] = v[a];
+  }
+  __syncthreads();
+  if (tid < 6) P.qpart[6 * (size_t)blockIdx.x + tid] = ((wred[0][tid] + wred[1][tid]) + wred[2][tid]) + wred[3][tid];
+}
+
+__device__ __forceinline__ void pcg_publish(const PcgState* s, PcgState* host) {
+  host->rz = s->rz; host->bnorm2 = s->bnorm2; host->rnorm2 = s->rnorm2; host->iter = s->iter; host->done = s->done; host->ok = s->ok;
+  __threadfence_system();
+}
+
+// One workgroup; a thread owns the cameras tid, tid + 256, ..
+//   mode 0  start of a solve: x = 0, r = b, z = M^-1 r, p = z
+//   mode 1  one iteration: q = S p from the diagonal blocks and k_gba_cam's chunk sums, alpha = r.z / p.q, x += alpha p, r -= alpha q,
+//           z = M^-1 r, the stopping rule (|r| <= eta |b| or max_it iterations), else beta and p = z + beta p.  p.q <= 0 or not finite
+//           ends the solve; before the first iteration that makes the trial step invalid (st->ok = 0).
+//   mode 2  q = S p only (dvs_ba_schur_probe)
+// host: where to publish the record (mode 1, last launch of a batch), or null
+__global__ __launch_bounds__(256) void k_gba_update(GbaDev P, int mode, double radius, double eta, int max_it, PcgState* host) {
+  __shared__ double sm[256];
+  const int tid = threadIdx.x;
+  PcgState* S = P.pcg;
+  if (mode == 0) {
+    double rz = 0.0, bn = 0.0;
+    for (int c = tid; c < P.K; c += 256) {
+      double bv[6];
+#pragma unroll
+      for (int a = 0; a < 6; a++) bv[a] = P.b[6 * c + a];
+#pragma unroll
+      for (int a = 0; a < 6; a++) {
+        double z = 0.0;
+#pragma unroll
+        for (int b = 0; b < 6; b++) z += P.Minv[36 * (size_t)c + 6 * a + b] * bv[b];
+        P.x[6 * c + a] = 0.0; P.r[6 * c + a] = bv[a]; P.z[6 * c + a] = z; P.p[6 * c + a] = z;
+        rz += bv[a] * z; bn += bv[a] * bv[a];
+      }
+    }
+    rz = block_sum_fixed(rz, sm);
+    bn = block_sum_fixed(bn, sm);
+    if (tid == 0) { S->rz = rz; S->bnorm2 = bn; S->rnorm2 = bn; S->iter = 0; S->done = 0; S->ok = 1; }
+    return;
+  }
+  if (mode == 1 && S->done) {
+    if (host && tid == 0) pcg_publish(S, host);
+    return;
+  }
+  double pq = 0.0;
+  for (int c = tid; c < P.K; c += 256) {
+    double qv[6] = {0, 0, 0, 0, 0, 0};
+    if (P.active[6 * c]) {
+      double pv[6];
+#pragma unroll
+      for (int a = 0; a < 6; a++) pv[a] = P.p[6 * c + a];
+#pragma unroll
+      for (int a = 0; a < 6; a++) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < 6; b++) s += P.Hpp[36 * (size_t)c + 6 * a + b] * P.scale[6 * c + a] * P.scale[6 * c + b] * pv[b];
+        qv[a] = s + P.diag[6 * c + a] / radius * pv[a];
+      }
+      for (int k = P.camChunkStart[c]; k < P.camChunkStart[c + 1]; k++) {
+#pragma unroll
+        for (int a = 0; a < 6; a++) qv[a] -= P.qpart[6 * (size_t)k + a];
+      }
+#pragma unroll
+      for (int a = 0; a < 6; a++) pq += pv[a] * qv[a];
+    }
+#pragma unroll
+    for (int a = 0; a < 6; a++) P.qv[6 * c + a] = qv[a];
+  }
+  if (mode == 2) return;
+  pq = block_sum_fixed(pq, sm);
+  const double rz = S->rz, bn = S->bnorm2;
+  const int iter = S->iter;
+  if (!(pq > 0.0) || !isfinite(pq)) {
+    __syncthreads();
+    if (tid == 0) {
+      S->done = 1;
+      if (iter == 0) { S->ok = 0; P.st->ok = 0; }
+      if (host) pcg_publish(S, host);
+    }
+    return;
+  }
+  const double alpha = rz / pq;
+  double rzn = 0.0, rn = 0.0;
+  for (int c = tid; c < P.K; c += 256) {
+    double rv[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      P.x[6 * c + a] += alpha * P.p[6 * c + a];
+      rv[a] = P.r[6 * c + a] - alpha * P.qv[6 * c + a];
+      P.r[6 * c + a] = rv[a];
+    }
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      double z = 0.0;
+#pragma unroll
+      for (int b = 0; b < 6; b++) z += P.Minv[36 * (size_t)c + 6 * a + b] * rv[b];
+      P.z[6 * c + a] = z;
+      rzn += rv[a] * z; rn += rv[a] * rv[a];
+    }
+  }
+  rzn = block_sum_fixed(rzn, sm);
+  rn = block_sum_fixed(rn, sm);
+  const bool stop = sqrt(rn) <= eta * sqrt(bn) || iter + 1 >= max_it;
+  if (!stop) {
+    const double beta = rzn / rz;
+    for (int c = tid; c < P.K; c += 256)
+#pragma unroll
+      for (int a = 0; a < 6; a++) P.p[6 * c + a] = P.z[6 * c + a] + beta * P.p[6 * c + a];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    S->rz = rzn; S->rnorm2 = rn; S->iter = iter + 1; S->done = stop ? 1 : 0;
+    if (host) pcg_publish(S, host);
+  }
+}
+
 }  // namespace dvs
 
 using namespace dvs;
@@ -1246,6 +1539,28 @@ struct LmView {
   }
 };
 
+// The workspace of dvs_ba_solve_global: what LmView holds around the linear solve, and the PCG's vectors in place of the observation
+// table, the reduced system and its splits — nothing here grows with L x K or with the square of the free cameras.
+struct GbaView {
+  unsigned char* active;
+  double *q0, *t0, *X0, *scale, *diag, *step, *Vinv, *Ws, *Y, *lmPart, *normPart;
+  double *Minv, *b, *r, *z, *p, *qv, *u, *qpart;
+  LmStatus* status;
+  PcgState* pcg;
+  size_t uploadBytes, bytes;
+  void carve(uint8_t* base, int K, int L, int R, int nChunks) {
+    const size_t Rz = std::max(R, 1), Kz = std::max(K, 1), Lz = std::max(L, 1), Cz = std::max(nChunks, 1), NT = 6 * (size_t)K + 3 * (size_t)L;
+    Carver c{base};
+    c.take(active, NT + 1);
+    uploadBytes = c.used;
+    c.take(q0, Kz * 4); c.take(t0, Kz * 3); c.take(X0, Lz * 3); c.take(scale, NT); c.take(diag, NT); c.take(step, NT); c.take(Vinv, Lz * 9);
+    c.take(Ws, Rz * 18); c.take(Y, Rz * 18); c.take(lmPart, Lz * 2); c.take(normPart, (size_t)((K + L + 255) / 256 + 1) * 2);
+    c.take(Minv, Kz * 36); c.take(b, Kz * 6); c.take(r, Kz * 6); c.take(z, Kz * 6); c.take(p, Kz * 6); c.take(qv, Kz * 6); c.take(u, Lz * 3);
+    c.take(qpart, Cz * 6); c.take(status, 1); c.take(pcg, 1);
+    bytes = c.used;
+  }
+};
+
 }  // namespace
 
 struct dvs_ba {
@@ -1274,6 +1589,15 @@ struct dvs_ba {
   bool lm_ready = false;   // dvs_ba_solve_device: structure tables built and uploaded
   int lm_nc = 0;           // ... free cameras
   int device_window = 16;  // dvs_ba_set_device_window: most free cameras dvs_ba_solve_device takes; above 16 the tiled solver factors the system
+  // dvs_ba_solve_global: its own arena and view (the two device solvers may alternate on one problem), the pinned PCG record
+  DeviceBuf<uint8_t> gba_arena;
+  PinnedBuf<uint8_t> pcg_buf;
+  size_t gba_cap = 0;
+  GbaView gwork{};
+  bool gba_ready = false;
+  int gba_nc = 0;
+  std::vector<int> pcg_iters;         // dvs_ba_get_pcg_trace: one row per trial step of the last dvs_ba_solve_global
+  std::vector<double> pcg_rel;
   std::vector<double> trace;          // dvs_ba_get_trace: 6 doubles per trust-region iteration of the last solve
   void log(double radius, int kind, double dc, double dm, double rel, double cand) {
     const double row[6] = {radius, (double)kind, dc, dm, rel, cand};
@@ -1285,8 +1609,8 @@ namespace {
 
 // forget the current problem (the arenas and pinned blocks stay)
 void ba_reset(dvs_ba* h) {
-  h->prob = {}; h->work = {}; h->raw_buf = {};
-  h->lm_ready = false;
+  h->prob = {}; h->work = {}; h->raw_buf = {}; h->gwork = {};
+  h->lm_ready = false; h->gba_ready = false;
 }
 
 // copies a host table into the staging block S at the place its buffer `dev` has in the arena at B
@@ -1979,6 +2303,259 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
   memcpy(h->X.data(), ho + 7 * (size_t)K, (size_t)L * 24);
   return DVS_OK;
 }
+
+namespace {
+
+// The global solver's blocks: every camera that is not fixed moves (one that nobody observes is its damped diagonal block and stays
+// where it is); landmarks as in free_blocks.  Lays the workspace out and uploads the flags; once per problem.
+dvs_status gba_prepare(dvs_ba* h) {
+  if (h->gba_ready) return DVS_OK;
+  const int K = h->K, L = h->L, R = h->R;
+  if (R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
+  std::vector<unsigned char> lmUsed(L, 0), active(6 * (size_t)K + 3 * (size_t)L, 0);
+  for (int p = 0; p < R; p++) lmUsed[h->lm[p]] = 1;
+  int nc = 0;
+  for (int c = 0; c < K; c++) if (!h->pose_fixed[c]) { nc++; for (int a = 0; a < 6; a++) active[6 * (size_t)c + a] = 1; }
+  for (int l = 0; l < L; l++) if (!h->lm_fixed[l] && lmUsed[l]) for (int a = 0; a < 3; a++) active[6 * (size_t)K + 3 * (size_t)l + a] = 1;
+  if (nc == 0) { set_error("dvs_ba_solve_global: every camera is fixed"); return DVS_ERR_ARG; }
+  GbaView& w = h->gwork;
+  w.carve(nullptr, K, L, R, h->nChunks);
+  DVS_TRY(grow(h->gba_arena, h->gba_cap, w.bytes));
+  DVS_HIP(hipStreamSynchronize(h->stream));     // the staging block is free (dvs_ba_set_problem's upload has completed)
+  DVS_TRY(grow(h->stage, h->stage_cap, w.uploadBytes));
+  if (!h->pcg_buf.get()) DVS_TRY(h->pcg_buf.alloc(2 * sizeof(LmStatus) + sizeof(PcgState)));
+  DVS_TRY(grow(h->out_buf, h->out_cap, ((size_t)7 * std::max(K, 1) + 3 * (size_t)std::max(L, 1)) * 8));
+  uint8_t* B = h->gba_arena.get();
+  w.carve(B, K, L, R, h->nChunks);
+  stage_table(h->stage.get(), B, w.active, active);
+  DVS_HIP(hipMemcpyAsync(B, h->stage.get(), w.uploadBytes, hipMemcpyHostToDevice, h->stream));
+  DVS_HIP(hipStreamSynchronize(h->stream));
+  h->gba_nc = nc;
+  h->gba_ready = true;
+  return DVS_OK;
+}
+
+GbaDev gba_view(const dvs_ba* h) {
+  const ProbView& dev = h->prob;
+  const GbaView& w = h->gwork;
+  GbaDev G;
+  G.K = h->K; G.L = h->L;
+  G.chunks = dev.chunks; G.camChunkStart = dev.camChunkStart; G.cam = dev.cam; G.lm = dev.lm; G.lmStart = dev.lmStart; G.lmObs = dev.lmObs;
+  G.active = w.active; G.Hpp = dev.Hpp; G.g = dev.g; G.scale = w.scale; G.diag = w.diag; G.Vinv = w.Vinv; G.Ws = w.Ws; G.Y = w.Y;
+  G.Minv = w.Minv; G.b = w.b; G.x = w.step; G.r = w.r; G.z = w.z; G.p = w.p; G.u = w.u; G.qpart = w.qpart; G.qv = w.qv;
+  G.pcg = w.pcg; G.st = w.status;
+  return G;
+}
+
+// the launches of `count` PCG iterations; the last one publishes the record to `host`
+void enqueue_pcg(const dvs_ba* h, const GbaDev& G, int count, double radius, double eta, int max_it, PcgState* host) {
+  for (int i = 0; i < count; i++) {
+    hipLaunchKernelGGL(k_gba_lm, dim3((4 * h->L + 255) / 256), dim3(256), 0, h->stream, G);
+    hipLaunchKernelGGL(k_gba_cam, dim3(h->nChunks), dim3(256), 0, h->stream, G);
+    hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, h->stream, G, 1, radius, eta, max_it, i + 1 == count ? host : nullptr);
+  }
+}
+
+}  // namespace
+
+dvs_status dvs_ba_default_global_params(dvs_ba_global_params* p) {
+  DVS_ARG(p);
+  p->max_iterations = 50; p->max_pcg_iterations = 0;
+  p->function_tolerance = 1e-6; p->gradient_tolerance = 1e-10; p->parameter_tolerance = 1e-8; p->eta = 0.1;
+  return DVS_OK;
+}
+
+dvs_status dvs_ba_get_pcg_trace(const dvs_ba* h, int32_t* iterations, double* rel_residual, int32_t cap_rows, int32_t* n_rows) {
+  DVS_ARG(h && n_rows && cap_rows >= 0);
+  const int n = (int)h->pcg_iters.size();
+  *n_rows = n;
+  const size_t m = (size_t)std::min(n, cap_rows);
+  if (iterations && m) memcpy(iterations, h->pcg_iters.data(), m * sizeof(int32_t));
+  if (rel_residual && m) memcpy(rel_residual, h->pcg_rel.data(), m * sizeof(double));
+  return DVS_OK;
+}
+
+// The trust-region loop of dvs_ba_solve_device around an inexact linear solve: per trial step the host enqueues the observation
+// blocks, the preconditioner, the PCG iterations in batches (one small record read per batch), back-substitution, candidate, cost
+// evaluation, and reads ONE status record; after an accepted step the full evaluation.
+dvs_status dvs_ba_solve_global(dvs_ba* h, const dvs_ba_global_params* params, dvs_ba_global_summary* out) {
+  DVS_ARG(h && out);
+  dvs_ba_global_params prm;
+  dvs_ba_default_global_params(&prm);
+  if (params) prm = *params;
+  memset(out, 0, sizeof(*out));
+  dvs_ba_summary* summary = &out->ba;
+  summary->termination = 2;
+  summary->linear_solver = 3;   // matrix-free Schur PCG on the DEVICE
+  DVS_ARG(prm.max_iterations >= 0 && prm.max_pcg_iterations >= 0);
+  DVS_ARG(prm.eta > 0.0 && prm.eta < 1.0);
+  DVS_ARG(prm.function_tolerance >= 0.0 && prm.gradient_tolerance >= 0.0 && prm.parameter_tolerance >= 0.0);
+  DVS_HIP(hipSetDevice(h->device));
+  DVS_TRY(gba_prepare(h));
+  const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
+  const double ftol = prm.function_tolerance, gtol = prm.gradient_tolerance, ptol = prm.parameter_tolerance, eta = prm.eta;
+  const int max_pcg = prm.max_pcg_iterations > 0 ? prm.max_pcg_iterations : std::max(100, 12 * h->gba_nc);
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  GbaView& w = h->gwork;
+  const GbaDev G = gba_view(h);
+  h->trace.clear(); h->pcg_iters.clear(); h->pcg_rel.clear();
+  DVS_TRY(upload_params(h, h->q, h->t, h->X));
+  const dim3 copyGrid((std::max(4 * K, 3 * L) + 255) / 256);
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
+  LmStatus* S = (LmStatus*)h->pcg_buf.get();   // [0]: the trial's record (k_lm_norms), [1]: the point's (k_lm_gmax), then the PCG's
+  LmStatus* SP = S + 1;
+  PcgState* PH = (PcgState*)(S + 2);
+  // Jacobian blocks, gradient, cost of the point in the evaluation buffers; accept: they hold a candidate that becomes the point
+  auto evaluate_full = [&](bool accept) -> dvs_status {
+    if (accept) hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
+    DVS_TRY(enqueue_eval(h, 1 | 2, true));
+    hipLaunchKernelGGL(k_lm_gmax, dim3(1), dim3(256), 0, st, K, L, w.q0, dev.g, w.active, dev.cost, w.status, SP, nullptr);
+    DVS_HIP(hipGetLastError());
+    DVS_HIP(hipStreamSynchronize(st));
+    return DVS_OK;
+  };
+  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
+  DVS_TRY(evaluate_full(false));
+  double x_cost = SP->x_cost, gmax = SP->gmax;
+  summary->initial_cost = x_cost;
+  double min_cost = x_cost;
+  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
+
+  const int nparts = (K + L + 255) / 256;
+  TrustRegion tr;
+  while (tr.next(prm.max_iterations, gmax, gtol, summary)) {
+    const double radius = tr.radius;
+    hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
+                       dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, tr.reuse_diagonal ? 0 : 1, w.Vinv, w.Ws, w.Y,
+                       w.status);
+    hipLaunchKernelGGL(k_gba_precond, dim3((K + 3) / 4), dim3(256), 0, st, G, radius);
+    hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, st, G, 0, radius, eta, max_pcg, nullptr);
+    // batches of 4, 8, 16, 32, 32, .. iterations: the launches past the stopping iteration return at once
+    for (int batch = 4, enq = 0;; batch = std::min(2 * batch, 32)) {
+      enqueue_pcg(h, G, batch, radius, eta, max_pcg, PH);
+      enq += batch;
+      DVS_HIP(hipGetLastError());
+      DVS_HIP(hipStreamSynchronize(st));
+      if (PH->done) break;
+      if (enq > max_pcg + 32) { set_error("dvs_ba_solve_global: the PCG record never reported the end of the solve"); return DVS_ERR_HIP; }
+    }
+    out->pcg_iterations += PH->iter;
+    h->pcg_iters.push_back(PH->iter);
+    h->pcg_rel.push_back(PH->bnorm2 > 0.0 ? sqrt(PH->rnorm2) / sqrt(PH->bnorm2) : 0.0);
+    hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, dev.Hll, dev.g, dev.lmStart, dev.lmObs, dev.cam,
+                       w.scale, w.active, w.Vinv, w.Ws, w.step, w.lmPart, w.status);
+    hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, w.step, w.scale, w.active,
+                       dev.q, dev.t, dev.X, w.normPart);
+    DVS_TRY(enqueue_eval(h, 0, false));  // cost of the candidate
+    hipLaunchKernelGGL(k_lm_norms, dim3(1), dim3(256), 0, st, nparts, w.normPart, dev.cost, K, L, dev.Hpp, dev.g, w.scale, w.step,
+                       w.lmPart, ptol, ftol, w.status, S);
+    DVS_HIP(hipGetLastError());
+    DVS_HIP(hipStreamSynchronize(st));
+    const bool valid = S->ok && S->finite && S->model_change > 0.0;
+    if (!valid) {
+      h->log(radius, 0, 0, S->model_change, 0, 0);
+      if (tr.invalid_step()) { summary->termination = 2; break; }
+      continue;
+    }
+    const double cost_change = x_cost - S->cand_cost;
+    if (sqrt(S->sn) <= ptol * (sqrt(S->xn) + ptol)) { h->log(radius, 3, cost_change, S->model_change, 0, S->cand_cost); summary->termination = 0; break; }
+    if (fabs(cost_change) <= ftol * x_cost) { h->log(radius, 4, cost_change, S->model_change, 0, S->cand_cost); summary->termination = 0; break; }
+    const double rel = cost_change / S->model_change;
+    const bool accept = S->accept != 0;   // the device's verdict, from the same numbers (k_lm_norms)
+    h->log(radius, accept ? 1 : 2, cost_change, S->model_change, rel, S->cand_cost);
+    if (accept) {
+      DVS_TRY(evaluate_full(true));
+      x_cost = SP->x_cost; gmax = SP->gmax;
+      summary->num_successful_steps++;
+      min_cost = std::min(min_cost, x_cost);
+      tr.accepted(rel);
+    } else {
+      tr.rejected();
+    }
+  }
+  summary->num_iterations = tr.iteration;
+  summary->final_cost = min_cost;
+  // the accepted point becomes the problem's parameters (evaluation buffers and, through the pinned block, the host mirror)
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, dev.q, dev.t, dev.X, nullptr);
+  double* ho = h->out();
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, ho, ho + 4 * (size_t)K, ho + 7 * (size_t)K, nullptr);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipStreamSynchronize(st));
+  memcpy(h->q.data(), ho, (size_t)K * 32); memcpy(h->t.data(), ho + 4 * (size_t)K, (size_t)K * 24);
+  memcpy(h->X.data(), ho + 7 * (size_t)K, (size_t)L * 24);
+  return DVS_OK;
+}
+
+#ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test_ba.h)
+// S x, the preconditioner blocks and b of dvs_ba_solve_global's linear solve at the problem's current point and the given radius,
+// through the kernels the solve runs
+dvs_status dvs_ba_schur_probe(dvs_ba* h, double radius, const double* x_in, double* y_out, double* Minv_out, double* b_out) {
+  DVS_ARG(h && x_in && y_out && Minv_out && b_out && radius > 0.0);
+  DVS_HIP(hipSetDevice(h->device));
+  DVS_TRY(gba_prepare(h));
+  const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  GbaView& w = h->gwork;
+  const GbaDev G = gba_view(h);
+  DVS_TRY(upload_params(h, h->q, h->t, h->X));
+  std::vector<double> p(x_in, x_in + 6 * (size_t)K);
+  for (int c = 0; c < K; c++) if (h->pose_fixed[c]) for (int a = 0; a < 6; a++) p[6 * (size_t)c + a] = 0.0;
+  DVS_HIP(hipMemcpyAsync(w.p, p.data(), p.size() * 8, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
+  DVS_TRY(enqueue_eval(h, 1 | 2, true));
+  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
+  hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
+                     dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, 1, w.Vinv, w.Ws, w.Y, w.status);
+  hipLaunchKernelGGL(k_gba_precond, dim3((K + 3) / 4), dim3(256), 0, st, G, radius);
+  DVS_HIP(hipMemsetAsync(w.pcg, 0, sizeof(PcgState), st));   // done = 0: the passes run
+  hipLaunchKernelGGL(k_gba_lm, dim3((4 * L + 255) / 256), dim3(256), 0, st, G);
+  hipLaunchKernelGGL(k_gba_cam, dim3(h->nChunks), dim3(256), 0, st, G);
+  hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, st, G, 2, radius, 0.5, 1, nullptr);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipStreamSynchronize(st));
+  DVS_HIP(hipMemcpy(y_out, w.qv, (size_t)K * 6 * 8, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(Minv_out, w.Minv, (size_t)K * 36 * 8, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(b_out, w.b, (size_t)K * 6 * 8, hipMemcpyDeviceToHost));
+  return DVS_OK;
+}
+// one linear solve at the problem's current point, as a trial step of dvs_ba_solve_global enqueues it: the PCG's x (scaled, as solved),
+// the iterations run and the recurrence's |r| / |b|; *ok = 0 when the solve stopped before its first iteration
+dvs_status dvs_ba_pcg_probe(dvs_ba* h, double radius, double eta, int32_t max_pcg_iterations, double* x_out, int32_t* iterations,
+                            double* rel_residual, int32_t* ok) {
+  DVS_ARG(h && x_out && iterations && rel_residual && ok && radius > 0.0 && eta > 0.0 && eta < 1.0 && max_pcg_iterations >= 0);
+  DVS_HIP(hipSetDevice(h->device));
+  DVS_TRY(gba_prepare(h));
+  const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
+  const int max_pcg = max_pcg_iterations > 0 ? max_pcg_iterations : std::max(100, 12 * h->gba_nc);
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  GbaView& w = h->gwork;
+  const GbaDev G = gba_view(h);
+  PcgState* PH = (PcgState*)((LmStatus*)h->pcg_buf.get() + 2);
+  DVS_TRY(upload_params(h, h->q, h->t, h->X));
+  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
+  DVS_TRY(enqueue_eval(h, 1 | 2, true));
+  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
+  hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
+                     dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, 1, w.Vinv, w.Ws, w.Y, w.status);
+  hipLaunchKernelGGL(k_gba_precond, dim3((K + 3) / 4), dim3(256), 0, st, G, radius);
+  hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, st, G, 0, radius, eta, max_pcg, nullptr);
+  for (int batch = 4, enq = 0;; batch = std::min(2 * batch, 32)) {
+    enqueue_pcg(h, G, batch, radius, eta, max_pcg, PH);
+    enq += batch;
+    DVS_HIP(hipGetLastError());
+    DVS_HIP(hipStreamSynchronize(st));
+    if (PH->done) break;
+    if (enq > max_pcg + 32) { set_error("dvs_ba_pcg_probe: the PCG record never reported the end of the solve"); return DVS_ERR_HIP; }
+  }
+  *iterations = PH->iter; *ok = PH->ok;
+  *rel_residual = PH->bnorm2 > 0.0 ? sqrt(PH->rnorm2) / sqrt(PH->bnorm2) : 0.0;
+  DVS_HIP(hipMemcpy(x_out, w.step, (size_t)K * 6 * 8, hipMemcpyDeviceToHost));
+  return DVS_OK;
+}
+#endif  // DVS_TEST_HOOKS
 
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h)
 // one linear solve S x = rhs (S n x n row-major, its lower triangle is read; n a multiple of 6, 6..378) through the tiled solver's

@@ -572,4 +572,61 @@ dvs_status dvs_backend_close_loop(dvs_backend* h, dvs_pgo* pgo, int32_t n_loops,
   return DVS_OK;
 }
 
+// Global BA over the whole map ("Global BA of the map" in the header).  The problem is assembled on the host from the tables' columns
+// (one read-back per column, as the per-keyframe BA cycle's dvs_backend_get_window does); the solve is the caller's dvs_ba handle's.
+dvs_status dvs_backend_global_ba(dvs_backend* h, dvs_ba* ba, const dvs_ba_global_params* params, dvs_backend_gba_result* out) {
+  DVS_ARG(h && ba && out);
+  memset(out, 0, sizeof(*out));
+  const int nkf = (int)h->kfs.size(), nlm = h->nlm, nob = h->nob;
+  if (nkf < 2) { set_error("dvs_backend_global_ba: %d keyframes, at least 2 are needed", nkf); return DVS_ERR_ARG; }
+  std::vector<uint64_t> lm_id((size_t)std::max(nlm, 1)), ob_frame((size_t)std::max(nob, 1)), ob_lm((size_t)std::max(nob, 1));
+  std::vector<int32_t> lm_cls((size_t)std::max(nlm, 1));
+  std::vector<float> lm_xyz(3 * (size_t)std::max(nlm, 1)), ob_px(2 * (size_t)std::max(nob, 1));
+  int32_t n = 0;
+  DVS_TRY(dvs_backend_get_landmarks(h, nlm, 0, lm_id.data(), lm_cls.data(), lm_xyz.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &n, nullptr));
+  DVS_TRY(dvs_backend_get_observations(h, nob, nullptr, ob_frame.data(), ob_px.data(), nullptr, nullptr, ob_lm.data(), &n));
+  // observations whose landmark the table holds, then only those of landmarks with at least two of them
+  std::vector<int> row((size_t)nob, -1), cnt((size_t)nlm, 0), camOf((size_t)nob, -1);
+  for (int i = 0; i < nob; i++) {
+    const auto it = std::lower_bound(lm_id.begin(), lm_id.begin() + nlm, ob_lm[(size_t)i]);
+    const auto kf = h->kf_index.find(ob_frame[(size_t)i]);
+    if (it == lm_id.begin() + nlm || *it != ob_lm[(size_t)i] || kf == h->kf_index.end()) continue;
+    row[(size_t)i] = (int)(it - lm_id.begin()); camOf[(size_t)i] = kf->second;
+    cnt[(size_t)row[(size_t)i]]++;
+  }
+  std::vector<int32_t> cam, lmi;
+  std::vector<double> uv;
+  for (int i = 0; i < nob; i++) {
+    const int l = row[(size_t)i];
+    if (l < 0 || cnt[(size_t)l] < 2) continue;
+    cam.push_back(camOf[(size_t)i]); lmi.push_back(l);
+    uv.push_back((double)ob_px[2 * (size_t)i]); uv.push_back((double)ob_px[2 * (size_t)i + 1]);
+  }
+  const int R = (int)cam.size();
+  out->n_cameras = nkf; out->n_landmarks = nlm; out->n_observations = R; out->n_left_out = nob - R;
+  if (R == 0) { set_error("dvs_backend_global_ba: no landmark of the map has two observations"); return DVS_ERR_ARG; }
+  std::vector<double> q(4 * (size_t)nkf), t(3 * (size_t)nkf), X(3 * (size_t)nlm);
+  for (int k = 0; k < nkf; k++) DVS_TRY(dvs_ba_pose_from_rt(h->kfs[(size_t)k].R, h->kfs[(size_t)k].t, &q[4 * (size_t)k], &t[3 * (size_t)k]));
+  for (size_t i = 0; i < X.size(); i++) X[i] = (double)lm_xyz[i];
+  std::vector<uint8_t> pose_fixed((size_t)nkf, 0);
+  pose_fixed[0] = 1;                                   // the gauge, as SlidingWindowBA fixes its first keyframe
+  DVS_TRY(dvs_ba_set_problem(ba, nkf, q.data(), t.data(), nlm, X.data(), R, cam.data(), lmi.data(), uv.data(), pose_fixed.data(), nullptr, h->P.fx, h->P.fy,
+                             h->P.cx, h->P.cy, 1.0, 1.345));
+  DVS_TRY(dvs_ba_solve_global(ba, params, &out->summary));
+  if (out->summary.ba.termination != 0) return DVS_OK;   // the map stays as it was
+  DVS_TRY(dvs_ba_get_parameters(ba, q.data(), t.data(), X.data()));
+  std::vector<uint64_t> frames; std::vector<double> Rs, ts;
+  for (int k = 1; k < nkf; k++) {
+    double Rk[9], tk[3];
+    DVS_TRY(dvs_ba_pose_to_rt(&q[4 * (size_t)k], &t[3 * (size_t)k], Rk, tk));
+    frames.push_back(h->kfs[(size_t)k].frame_id); Rs.insert(Rs.end(), Rk, Rk + 9); ts.insert(ts.end(), tk, tk + 3);
+  }
+  std::vector<uint64_t> ids; std::vector<int32_t> cls; std::vector<double> xyz;
+  for (int l = 0; l < nlm; l++) {
+    if (cnt[(size_t)l] < 2) continue;                    // left without observations: keeps its position bytes
+    ids.push_back(lm_id[(size_t)l]); cls.push_back(lm_cls[(size_t)l]); xyz.insert(xyz.end(), &X[3 * (size_t)l], &X[3 * (size_t)l] + 3);
+  }
+  return dvs_backend_apply_optimized(h, (int32_t)frames.size(), frames.data(), Rs.data(), ts.data(), (int32_t)ids.size(), ids.data(), cls.data(), xyz.data());
+}
+
 }  // extern "C"

@@ -44,6 +44,15 @@ class BaSummary(C.Structure):
                 ("linear_solver", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double)]
 
 
+class BaGlobalParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_pcg_iterations", C.c_int32), ("function_tolerance", C.c_double),
+                ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double), ("eta", C.c_double)]
+
+
+class BaGlobalSummary(C.Structure):
+    _fields_ = [("ba", BaSummary), ("pcg_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
 class VocTrainParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32), ("seed", C.c_uint64),
                 ("max_iterations", C.c_int32)]
@@ -197,6 +206,10 @@ def _bind(L):
         L.dvs_ba_get_trace.argtypes = [vp, vp, i32, C.POINTER(i32)]
         L.dvs_ba_pose_from_rt.argtypes = [vp, vp, vp, vp]
         L.dvs_ba_pose_to_rt.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "dvs_ba_solve_global"):
+        L.dvs_ba_default_global_params.argtypes = [C.POINTER(BaGlobalParams)]
+        L.dvs_ba_solve_global.argtypes = [vp, C.POINTER(BaGlobalParams), C.POINTER(BaGlobalSummary)]
+        L.dvs_ba_get_pcg_trace.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
     if hasattr(L, "dvs_bow_vocab_info"):   # place recognition (dvslam_amd/bow.py)
         pi32 = C.POINTER(i32)
         L.dvs_bow_vocab_load_text.argtypes = [i32, vp, C.c_char_p, C.POINTER(vp)]
@@ -342,6 +355,9 @@ def test_lib():
     if hasattr(L, "dvs_test_pgo_apply"):
         L.dvs_test_pgo_apply.argtypes = [vp, dbl, vp, vp]
         L.dvs_test_pgo_pcg.argtypes = [vp, dbl, dbl, i32, vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(dbl)]
+    if hasattr(L, "dvs_ba_schur_probe"):
+        L.dvs_ba_schur_probe.argtypes = [vp, dbl, vp, vp, vp, vp]
+        L.dvs_ba_pcg_probe.argtypes = [vp, dbl, dbl, i32, vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i32)]
     _test_lib = L
     return L
 

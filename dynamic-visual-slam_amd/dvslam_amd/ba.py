@@ -1,6 +1,6 @@
 import ctypes as C
 import numpy as np
-from ._lib import lib, check, ptr, BaSummary, DvsError
+from ._lib import lib, test_lib, check, ptr, BaSummary, BaGlobalParams, BaGlobalSummary, DvsError
 
 TERMINATION = {0: "CONVERGENCE", 1: "NO_CONVERGENCE", 2: "FAILURE"}
 
@@ -8,12 +8,26 @@ TERMINATION = {0: "CONVERGENCE", 1: "NO_CONVERGENCE", 2: "FAILURE"}
 class BAProblem:
     """Direct driver of the dvs_ba_* C-ABI: problem in the optimiser's parameterisation (bundle_adjustment.hpp:92-165)."""
 
-    def __init__(self, prob, device=0):
-        self._L = lib()
+    def __init__(self, prob, device=0, hooks=False):
+        """hooks: make every call through the test-hook library (schur_probe / pcg_probe need it)"""
+        self._L = test_lib() if hooks else lib()
         h = C.c_void_p()
         check(self._L.dvs_ba_create(device, C.byref(h)))
         self._h = h
+        self._keep = []
         self.set_problem(prob)
+
+    @classmethod
+    def empty(cls, device=0, hooks=False):
+        """a handle without a problem yet (MappingBackend.global_bundle_adjust sets one on it)"""
+        self = cls.__new__(cls)
+        self._L = test_lib() if hooks else lib()
+        h = C.c_void_p()
+        check(self._L.dvs_ba_create(device, C.byref(h)))
+        self._h = h
+        self.K = self.L = self.R = 0
+        self._keep = []
+        return self
 
     def set_problem(self, prob):
         """a new window on the same handle (what SlidingWindowBA::optimize does per call): device memory is reused when it fits"""
@@ -82,6 +96,46 @@ class BAProblem:
         s = BaSummary()
         check(self._L.dvs_ba_solve_device(self._h, max_iterations, ftol, gtol, ptol, C.byref(s)))
         return s
+
+    def solve_global(self, **params):
+        """dvs_ba_solve_global: every keyframe on the device, the camera steps by matrix-free Schur PCG (no limit on K).  params: the
+        fields of dvs_ba_global_params (max_iterations 50, max_pcg_iterations 0 = max(100, 12 x free cameras), function_tolerance
+        1e-6, gradient_tolerance 1e-10, parameter_tolerance 1e-8, eta 0.1).  Returns the dvs_ba_global_summary (.ba is the summary
+        the other solvers return, .pcg_iterations the total over all trial steps)."""
+        p = BaGlobalParams()
+        check(self._L.dvs_ba_default_global_params(C.byref(p)))
+        names = {f[0] for f in BaGlobalParams._fields_}
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError(f"solve_global: unknown parameter {k!r}")
+            setattr(p, k, v)
+        s = BaGlobalSummary()
+        check(self._L.dvs_ba_solve_global(self._h, C.byref(p), C.byref(s)))
+        return s
+
+    def pcg_trace(self):
+        """dvs_ba_get_pcg_trace: (iterations int32 [n], |r| / |b| [n]), one entry per trial step of the last solve_global, beside
+        trace()"""
+        n = C.c_int32()
+        check(self._L.dvs_ba_get_pcg_trace(self._h, None, None, 0, C.byref(n)))
+        it = np.zeros(n.value, np.int32); rel = np.zeros(n.value)
+        check(self._L.dvs_ba_get_pcg_trace(self._h, ptr(it), ptr(rel), n.value, C.byref(n)))
+        return it, rel
+
+    def schur_probe(self, radius, x):
+        """dvs_ba_schur_probe (hooks=True): S x, the preconditioner blocks [K, 6, 6] and b of the global solver's linear solve at the
+        current point"""
+        x = np.ascontiguousarray(x, np.float64).reshape(6 * self.K)
+        y = np.zeros(6 * self.K); Minv = np.zeros((self.K, 6, 6)); b = np.zeros(6 * self.K)
+        check(self._L.dvs_ba_schur_probe(self._h, float(radius), ptr(x), ptr(y), ptr(Minv), ptr(b)))
+        return y, Minv, b
+
+    def pcg_probe(self, radius, eta, max_pcg_iterations=0):
+        """dvs_ba_pcg_probe (hooks=True): one linear solve at the current point -> (x [6K], iterations, |r| / |b|, ok)"""
+        x = np.zeros(6 * self.K); it = C.c_int32(); rel = C.c_double(); ok = C.c_int32()
+        check(self._L.dvs_ba_pcg_probe(self._h, float(radius), float(eta), int(max_pcg_iterations), ptr(x), C.byref(it), C.byref(rel),
+                                       C.byref(ok)))
+        return x, it.value, rel.value, ok.value
 
     def trace(self):
         """dvs_ba_get_trace: [iterations, 6] = radius, kind (0 invalid, 1 accepted, 2 rejected, 3 ptol, 4 ftol), cost change,

@@ -2,7 +2,7 @@
 and pruneLandmarks (backend.cpp) as one handle that keeps the landmark and observation tables on the device; one call per keyframe."""
 import ctypes as C
 import numpy as np
-from ._lib import lib, check, ptr, DvsError, KeyframeHeader, PgoParams, PgoSummary
+from ._lib import lib, check, ptr, DvsError, KeyframeHeader, PgoParams, PgoSummary, BaGlobalParams, BaGlobalSummary
 
 MAX_FILTERED = 16
 
@@ -45,6 +45,11 @@ class CloseLoopResult(C.Structure):
                 ("fuse", FuseResult)]
 
 
+class GlobalBaResult(C.Structure):
+    """dvs_backend_gba_result"""
+    _fields_ = [("summary", BaGlobalSummary), ("n_cameras", C.c_int32), ("n_landmarks", C.c_int32), ("n_observations", C.c_int32), ("n_left_out", C.c_int32)]
+
+
 def _bind(L):
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
     pi32, pi64 = C.POINTER(i32), C.POINTER(i64)
@@ -67,6 +72,7 @@ def _bind(L):
     L.dvs_backend_build_pose_graph.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, pi32, pi32]
     L.dvs_backend_close_loop.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, dbl, dbl, C.POINTER(PgoParams), C.POINTER(FuseParams), C.POINTER(CloseLoopResult)]
     L.dvs_backend_fuse.argtypes = [vp, u64, vp, i32, C.POINTER(FuseParams), i32, C.POINTER(FuseResult), i32, vp, vp, vp, pi32]
+    L.dvs_backend_global_ba.argtypes = [vp, vp, C.POINTER(BaGlobalParams), C.POINTER(GlobalBaResult)]
     return L
 
 
@@ -117,6 +123,7 @@ class MappingBackend:
         self._L = _bind(lib())
         self._h = None
         self._ba = None
+        self._gba = None
         self.fx, self.fy, self.cx, self.cy, self.device = fx, fy, cx, cy, device
         self.class_names = ["unlabeled"]
         self._class_id = {"unlabeled": 0}
@@ -289,6 +296,26 @@ class MappingBackend:
         out.update({k: int(getattr(r.fuse, k)) for k, _ in FuseResult._fields_})
         return out
 
+    def global_bundle_adjust(self, ba=None, **params):
+        """dvs_backend_global_ba: every keyframe and landmark of the map refined by BAProblem.solve_global (the step after close_loop), on
+        `ba` (a dvslam_amd.BAProblem of the same device; None: a handle this object creates once and keeps).  params: the fields of
+        dvs_ba_global_params.  The map changes only if the solve converged (summary.ba.termination == 0).
+        -> dict(summary=dvs_ba_global_summary, n_cameras, n_landmarks, n_observations, n_left_out)"""
+        from .ba import BAProblem
+        if ba is None:
+            if self._gba is None:
+                self._gba = BAProblem.empty(self.device)
+            ba = self._gba
+        p = BaGlobalParams()
+        check(self._L.dvs_ba_default_global_params(C.byref(p)))
+        for k, v in params.items():
+            if k not in dict(BaGlobalParams._fields_):
+                raise TypeError(f"unknown parameter {k}")
+            setattr(p, k, v)
+        r = GlobalBaResult()
+        check(self._L.dvs_backend_global_ba(self._h, ba._h, C.byref(p), C.byref(r)))
+        return dict(summary=r.summary, n_cameras=r.n_cameras, n_landmarks=r.n_landmarks, n_observations=r.n_observations, n_left_out=r.n_left_out)
+
     def reset(self):
         check(self._L.dvs_backend_reset(self._h))
 
@@ -304,4 +331,4 @@ class MappingBackend:
             pass
 
 
-__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "default_params", "fuse_params", "DvsError"]
+__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "default_params", "fuse_params", "DvsError"]

@@ -165,3 +165,16 @@ def make_ba_problem(K: int = 10, L: int = 2000, seed: int = 42, pixel_noise: flo
                 cam_idx=np.concatenate(cam_idx), lm_idx=np.concatenate(lm_idx), uv=np.ascontiguousarray(np.concatenate(uv)),
                 pose_fixed=pose_fixed, lm_fixed=np.zeros(L, np.uint8), fx=fx, fy=fy, cx=cx, cy=cy, sigma=1.0,
                 huber=1.345, gt_q=q_gt, gt_t=t_gt, gt_X=X)
+
+
+def make_ba_banded_problem(K: int = 96, L: int = 1200, seed: int = 96, half_span: int = 12, **kw):
+    """make_ba_problem(K, L, seed, **kw) with only the observations kept whose camera lies within half_span of the landmark's place
+    along the arc, |cam - (l * K) // L| <= half_span: the band structure of a long trajectory (a landmark is seen by the
+    2 half_span + 1 keyframes around it), for problems with many keyframes.  The random stream is make_ba_problem's."""
+    prob = make_ba_problem(K=K, L=L, seed=seed, **kw)
+    cam = prob["cam_idx"].astype(np.int64); lm = prob["lm_idx"].astype(np.int64)
+    keep = np.abs(cam - (lm * K) // L) <= half_span
+    prob["cam_idx"] = np.ascontiguousarray(prob["cam_idx"][keep])
+    prob["lm_idx"] = np.ascontiguousarray(prob["lm_idx"][keep])
+    prob["uv"] = np.ascontiguousarray(prob["uv"][keep])
+    return prob

@@ -518,7 +518,7 @@ typedef struct dvs_ba_summary {
   int32_t termination;          /* 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE (ceres::TerminationType order) */
   int32_t num_successful_steps; /* OptimizationResult::iterations_completed (bundle_adjustment.hpp:862) */
   int32_t num_iterations;
-  int32_t linear_solver;        /* who solved the normal equations: 1 = the device (dvs_ba_solve_device), 2 = the host (dvs_ba_solve) */
+  int32_t linear_solver;        /* who solved the normal equations: 1 = the device (dvs_ba_solve_device), 2 = the host (dvs_ba_solve), 3 = dvs_ba_solve_global */
   double initial_cost, final_cost;
 } dvs_ba_summary;
 
@@ -571,6 +571,50 @@ int32_t dvs_ba_get_device_window(const dvs_ba* h);
  * *n_rows = rows available; at most cap_rows are written (rows may be NULL). */
 dvs_status dvs_ba_get_trace(const dvs_ba* h, double* rows, int32_t cap_rows, int32_t* n_rows);
 dvs_status dvs_ba_get_parameters(dvs_ba* h, double* q_wxyz, double* t, double* X);
+/* ---- Global BA: every keyframe on the device, matrix-free Schur PCG -------------------------------------------------------------
+ * dvs_ba_solve_global runs the trust-region loop of dvs_ba_solve_device (same decisions, same tolerances, same 6-column log, one
+ * status record per trial step) around an INEXACT linear solve whose cost follows the number of observations: preconditioned
+ * conjugate gradients on the reduced camera system S, which is never formed.  No limit on K; no L x K or n x n array anywhere.  It
+ * takes every problem dvs_ba_set_problem takes that has at least one observation and one camera that is not fixed (DVS_ERR_ARG
+ * otherwise), a landmark observed twice in one camera included (two ordinary terms).
+ *
+ * The linear solve of one trial step at radius rho.  With the Jacobi scaling s_j = 1 / (1 + sqrt(H_jj)) fixed at the first Jacobian,
+ * D = clamp(diag(H scaled), 1e-6, 1e32), per active landmark l  Vinv_l = (Hll_l scaled + D_l / rho)^-1, and per observation e of
+ * camera cam(e) and landmark l(e)  Ws_e = the scaled 6 x 3 block W_e, Y_e = Ws_e Vinv_l(e), for each free camera c (not fixed):
+ *   (S p)_c = (Hpp_c scaled + D_c / rho) p_c - sum_{obs e of c} Ws_e Vinv_l(e) ( sum_{obs f of l(e), cam(f) free} Ws_f^T p_cam(f) )
+ *   b_c     = g_c scaled - sum_{obs e of c} Y_e g_l(e) scaled
+ * Fixed cameras and inactive landmarks (fixed, or observed by nobody) contribute nothing; a camera nobody observes is its damped
+ * diagonal block.  The step is stored as solved (camera part not negated), the sign back-substitution and candidate read.
+ *   Preconditioner  M_c^-1, M_c = Hpp_c scaled + D_c / rho - sum_{e of c} Y_e Ws_e^T (the 6 x 6 diagonal blocks of S, Ceres'
+ *                   SCHUR_JACOBI), inverted by Cholesky; the inverse of the block's diagonal alone if a pivot is not positive.
+ *   Iteration       x_0 = 0, r_0 = b, z = M^-1 r, p = z;  alpha = r.z / p.Sp, x += alpha p, r -= alpha S p, z = M^-1 r,
+ *                   beta = r.z new / r.z old, p = z + beta p.  Stops at the first k >= 1 with |r_k|_2 <= eta |b|_2 (r_k the
+ *                   recurrence's residual) or at max_pcg_iterations (0: max(100, 12 nc), nc = free cameras).
+ *   Breakdown       p.Sp <= 0 or not finite ends the solve: before the first iteration the trial step is invalid, later the
+ *                   current x is the step.
+ *   Determinism     the landmark-side sum runs over the landmark's observations in the order of the observation arrays grouped by
+ *                   camera; the camera-side sum per chunk of <= 256 observations by a fixed tree, chunks in order; dot products by
+ *                   fixed per-thread strides and a fixed tree.  No floating-point atomics: two identical solves return identical bytes.
+ * The model cost change is computed from the actual step, so it is right for an inexact one.  Launches: three plain kernels per PCG
+ * iteration that return at once after the stopping iteration; the host enqueues them in batches and reads one small record per
+ * batch — no grid-wide barrier, no persistent kernel. */
+typedef struct dvs_ba_global_params {
+  int32_t max_iterations;       /* 50 */
+  int32_t max_pcg_iterations;   /* 0 = max(100, 12 x free cameras) */
+  double function_tolerance, gradient_tolerance, parameter_tolerance;   /* 1e-6, 1e-10, 1e-8 */
+  double eta;                   /* 0.1; in (0, 1) */
+} dvs_ba_global_params;
+typedef struct dvs_ba_global_summary {
+  dvs_ba_summary ba;            /* ba.linear_solver = 3 */
+  int32_t pcg_iterations;       /* over all trial steps */
+  int32_t reserved;
+} dvs_ba_global_summary;
+dvs_status dvs_ba_default_global_params(dvs_ba_global_params* params);
+/* params NULL: the defaults.  eta outside (0, 1), a negative limit or tolerance: DVS_ERR_ARG. */
+dvs_status dvs_ba_solve_global(dvs_ba* h, const dvs_ba_global_params* params, dvs_ba_global_summary* out);
+/* beside dvs_ba_get_trace, one row per trial step of the last dvs_ba_solve_global: PCG iterations run and the recurrence's |r| / |b|
+ * at the end (either array may be NULL) */
+dvs_status dvs_ba_get_pcg_trace(const dvs_ba* h, int32_t* iterations, double* rel_residual, int32_t cap_rows, int32_t* n_rows);
 /* CameraPose::fromRt / toRt (bundle_adjustment.hpp:138-165, 192-212): caller-convention (R row-major 3x3, t) <->
  * optimiser (q_wxyz, translation).  Host arithmetic used by the SlidingWindowBA adapter. */
 dvs_status dvs_ba_pose_from_rt(const double* R, const double* t, double* q_wxyz, double* trans);
@@ -1179,7 +1223,7 @@ dvs_status dvs_pgo_correct_points_device(dvs_pgo* h, int32_t n, float* d_xyz, co
  *            untouched; two observations of one keyframe may then name one landmark, as the reference's association already allows.
  *            Pairs are reported in ascending removed id with their e.  (e, id) is a total order and every minimum is an integer minimum
  *            on the device: there is no tie deviation, and two identical calls on identical maps give identical bytes.
- * Still out of scope: Sim(3), global BA, temporal consistency of candidates, re-triangulating the survivor, descriptor re-selection,
+ * Still out of scope: Sim(3), temporal consistency of candidates, re-triangulating the survivor, descriptor re-selection,
  * several GPUs. */
 typedef struct dvs_fuse_params {
   double max_descriptor_distance;      /* 50, the backend's */
@@ -1224,6 +1268,30 @@ dvs_status dvs_backend_close_loop(dvs_backend* h, dvs_pgo* pgo, int32_t n_loops,
 dvs_status dvs_backend_fuse(dvs_backend* h, uint64_t query_frame_id, const uint64_t* entry_frame_ids, int32_t n_entry, const dvs_fuse_params* params,
                             int32_t apply, dvs_fuse_result* out, int32_t cap_pairs, uint64_t* survivor_id, uint64_t* removed_id, double* err,
                             int32_t* n_pairs);
+
+/* ---- Global BA of the map --------------------------------------------------------------------------------------------------------
+ * The step after CorrectLoop: every keyframe and every landmark of the map refined by dvs_ba_solve_global (B3 above) on the caller's
+ * dvs_ba handle (same device; the backend owns none, as dvs_backend_close_loop takes a dvs_pgo).  PARITY UNPINNED: the reference has no
+ * global BA; the rule is this library's own, restated over the getters' arrays in tests/global_ba_ref.py.
+ *   Cameras       all keyframes in table order, converted by dvs_ba_pose_from_rt; keyframe 0 is the fixed gauge, as SlidingWindowBA
+ *                 fixes its first.
+ *   Landmarks     all rows in ascending id, positions float -> double, none fixed.
+ *   Observations  all rows of the observation table, in table order, whose landmark is in the table (the obs_lm_index >= 0 rule of
+ *                 dvs_backend_get_window), pixels float -> double; the observations of a landmark with fewer than two such rows are left
+ *                 out.  Limitation: a landmark left without observations keeps its position bytes — nothing re-triangulates it.
+ *   Settings      the backend's fx .. cy, sigma 1.0, Huber 1.345.
+ *   Result        applied through dvs_backend_apply_optimized (keyframes 1 .., the landmarks with observations; positions rounded to
+ *                 float once) if and only if summary.ba.termination == 0.  Otherwise the map stays byte for byte as it was and the
+ *                 call still returns DVS_OK with the summary.  Fewer than 2 keyframes or no usable observation: DVS_ERR_ARG before
+ *                 the map is touched.
+ *   Data path     the problem is assembled on the HOST from one read-back per table column, as the per-keyframe BA cycle does through
+ *                 dvs_backend_get_window; handing the tables over on the device is not built.
+ * n_left_out counts the observation-table rows that are not in the problem. */
+typedef struct dvs_backend_gba_result {
+  dvs_ba_global_summary summary;
+  int32_t n_cameras, n_landmarks, n_observations, n_left_out;
+} dvs_backend_gba_result;
+dvs_status dvs_backend_global_ba(dvs_backend* h, dvs_ba* ba, const dvs_ba_global_params* params /* NULL: defaults */, dvs_backend_gba_result* out);
 
 #ifdef __cplusplus
 }

@@ -3,8 +3,8 @@
 checked against its own transcription in oracle/ba_oracle.cpp).
 
 Solves the synthetic windows 3x60, 5x200, 10x2000 and 24x300 (dvslam_amd.synth.make_ba_problem, the generator bench.py and the tests
-use) with scipy.optimize.least_squares(method="trf") to convergence and stores the optimum under
-tests/golden/ba_scipy_*.npz.  Nothing here shares code with csrc/ba.hip or oracle/ba_oracle.cpp:
+use) and the banded 80x400 problem (make_ba_banded_problem) with scipy.optimize.least_squares(method="trf") to convergence and
+stores the optimum under tests/golden/ba_scipy_*.npz.  Nothing here shares code with csrc/ba.hip or oracle/ba_oracle.cpp:
 
 * residual model written from bundle_adjustment.hpp:531-565 in numpy (rotation matrices, not the quaternion sandwich);
 * poses parameterised MINIMALLY as q = q_init (x) exp(omega), omega in R^3 (not Ceres' ambient quaternion + manifold);
@@ -37,7 +37,12 @@ HUBER = 1.345
 # (measured: 804.2 vs 1539.1 — the LM loop found the LOWER one); with >= 5 views the outliers cannot win and the basins coincide.
 CASES = [("3x60", dict(K=3, L=60, seed=9, outlier_frac=0.0)), ("5x200", dict(K=5, L=200, seed=7)), ("10x2000", dict(K=10, L=2000, seed=42)),
          # a window beyond 16 free keyframes with partial co-visibility (dvs_ba_set_device_window; tests/test_gpu_ba_window.py)
-         ("24x300", dict(K=24, L=300, seed=24, visibility=0.6))]
+         ("24x300", dict(K=24, L=300, seed=24, visibility=0.6)),
+         # a banded problem with more cameras than any window (dvs_ba_solve_global; tests/test_gpu_ba_global.py).  The third entry: the
+         # generator when it is not make_ba_problem, and exact=True for trf's dense SVD steps (tr_solver="exact") on a dense Jacobian:
+         # with lsmr steps this chain of 80 cameras creeps along the scale gauge's valley — 54689.68, 54689.55, 54689.48, 54689.42,
+         # 54689.39 after rounds of 300 evaluations — while the exact steps reach 54688.0787254513 in 61 evaluations and stay there.
+         ("80x400_banded", dict(K=80, L=400, seed=80, half_span=4), dict(generator="make_ba_banded_problem", exact=True))]
 
 
 def rot_from_quat(q):
@@ -133,14 +138,19 @@ class Window:
         return S.tocsr()
 
 
-def solve(P, verbose=0):
+def solve(P, verbose=0, exact=False):
     W = Window(P)
     x = W.x0()
     c0 = W.cost(x)
     best = None
+    if exact:
+        from scipy.optimize._numdiff import approx_derivative
+        sparsity = W.sparsity()
+        how = dict(jac=lambda x: approx_derivative(W.fun, x, method="3-point", sparsity=sparsity).toarray(), tr_solver="exact", max_nfev=100)
+    else:
+        how = dict(jac="3-point", jac_sparsity=W.sparsity(), max_nfev=300)
     for rnd in range(6):        # restart until the cost no longer moves: scipy's own stopping rules are not Ceres'
-        sol = least_squares(W.fun, x, jac="3-point", jac_sparsity=W.sparsity(), method="trf", loss="linear",
-                            xtol=1e-15, ftol=1e-15, gtol=1e-15, max_nfev=300, x_scale="jac", verbose=verbose)
+        sol = least_squares(W.fun, x, method="trf", loss="linear", xtol=1e-15, ftol=1e-15, gtol=1e-15, x_scale="jac", verbose=verbose, **how)
         x = sol.x
         c = W.cost(x)
         if best is not None and abs(best - c) <= 1e-10 * c:
@@ -157,15 +167,17 @@ def main():
     import json
     out_dir = os.path.join(ROOT, "tests", "golden")
     only = sys.argv[1:]
-    for name, kw in CASES:
+    for name, kw, *more in CASES:
         if only and name not in only:
             continue
-        P = synth.make_ba_problem(**kw)
+        opts = more[0] if more else {}
+        generator = opts.get("generator", "make_ba_problem")
+        P = getattr(synth, generator)(**kw)
         t0 = time.time()
-        c0, c, q, t, X = solve(P)
+        c0, c, q, t, X = solve(P, exact=opts.get("exact", False))
         print(f"{name}: initial cost {c0:.9g} -> optimum {c:.12g}  ({time.time() - t0:.1f} s)", flush=True)
         np.savez_compressed(os.path.join(out_dir, f"ba_scipy_{name}.npz"), make_ba_problem_kwargs=json.dumps(kw), initial_cost=c0,
-                            optimum_cost=c, q=q, t=t, X=X.astype(np.float64))
+                            optimum_cost=c, q=q, t=t, X=X.astype(np.float64), **({"generator": generator} if more else {}))
 
 
 if __name__ == "__main__":
