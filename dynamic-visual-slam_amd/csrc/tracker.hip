@@ -21,6 +21,7 @@
 #include "device_mem.h"
 #include "io_pinned.h"
 #include "matcher.h"
+#include "motion_internal.h"
 #include "orb_device_common.h"
 #include "ransac_device.h"
 #include "block_rank.h"
@@ -261,13 +262,55 @@ struct dvs_tracker {
   int since_kf = 0;                                // frames_since_last_keyframe_
   int64_t keyframe_id = 0, t = 0;                  // keyframe_id_; frames since create / reset
   double R[9], tt[3];                              // R_, t_
+  // the motion-mask opt-in (dvs_tracker_set_motion_mask); everything below is empty while it is off
+  struct MotionSlot { int64_t frame = -1; bool pose_updated = false; double R[9], t[3]; };
+  dvs_motion* mo = nullptr;
+  int mo_lag = 0;
+  DeviceBuf<uint16_t> mo_ring;                     // mo_lag + 1 depth images: frame f lives in slot f % (mo_lag + 1)
+  DeviceBuf<uint8_t> mo_mask;
+  MotionSlot mo_slot[17];
+  int mo_seq = 0;                                  // frames of the current sequence in the ring (it begins at a first frame / a tracking reset)
+  bool mo_after_reset = false;                     // the previous frame reset the tracking
+  int64_t mo_ref = -1;                             // the last frame's reference (-1: its extraction was unmasked)
+  double mo_R[9], mo_t[3];                         // ... and the relative pose its mask was made with
 };
+
+// the relative pose of dvs_tracker_set_motion_mask for frame t: constant-velocity prediction against slot `ref`.  Every product is a plain
+// row-by-column sum in index order (tests recompute it from the returned poses to 1e-12, not bit for bit).
+static void motion_relative_pose(const dvs_tracker* h, int64_t t, const dvs_tracker::MotionSlot& ref, double* R, double* tr) {
+  const int ns = h->mo_lag + 1;
+  const dvs_tracker::MotionSlot& a = h->mo_slot[(t - 1) % ns];   // T(t-1)
+  double Rp[9], tp[3];
+  memcpy(Rp, a.R, sizeof(Rp)); memcpy(tp, a.t, sizeof(tp));
+  if (a.pose_updated && h->mo_seq >= 2) {
+    const dvs_tracker::MotionSlot& b = h->mo_slot[(t - 2) % ns];   // T(t-2)
+    double Rrel[9], trel[3];                                      // T(t-2)^-1 o T(t-1)
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) Rrel[3 * i + j] = b.R[i] * a.R[j] + b.R[3 + i] * a.R[3 + j] + b.R[6 + i] * a.R[6 + j];
+      trel[i] = b.R[i] * (a.t[0] - b.t[0]) + b.R[3 + i] * (a.t[1] - b.t[1]) + b.R[6 + i] * (a.t[2] - b.t[2]);
+    }
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) Rp[3 * i + j] = a.R[3 * i] * Rrel[j] + a.R[3 * i + 1] * Rrel[3 + j] + a.R[3 * i + 2] * Rrel[6 + j];
+      tp[i] = a.R[3 * i] * trel[0] + a.R[3 * i + 1] * trel[1] + a.R[3 * i + 2] * trel[2] + a.t[i];
+    }
+  }
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) R[3 * i + j] = ref.R[i] * Rp[j] + ref.R[3 + i] * Rp[3 + j] + ref.R[6 + i] * Rp[6 + j];
+    tr[i] = ref.R[i] * (tp[0] - ref.t[0]) + ref.R[3 + i] * (tp[1] - ref.t[1]) + ref.R[6 + i] * (tp[2] - ref.t[2]);
+  }
+}
+
+static void motion_reset_state(dvs_tracker* h) {
+  h->mo_seq = 0; h->mo_after_reset = false; h->mo_ref = -1;
+  for (auto& s : h->mo_slot) s.frame = -1;
+}
 
 static void tracker_reset_state(dvs_tracker* h) {
   h->prev_valid = false; h->has_last_kf = false; h->p = 0; h->prev_n = 0; h->bkf = 0; h->kf_n = 0; h->blast = 0; h->last_n = 0;
   h->since_kf = 0; h->keyframe_id = 0; h->t = 0;
   for (int k = 0; k < 9; k++) h->R[k] = (k % 4 == 0) ? 1.0 : 0.0;
   h->tt[0] = h->tt[1] = h->tt[2] = 0.0;
+  motion_reset_state(h);
 }
 
 // the record block to the host: export kernel + polled sequence number (no copy command, no stream wait)
@@ -356,6 +399,7 @@ void dvs_tracker_destroy(dvs_tracker* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->ctx) (void)hipStreamSynchronize(h->ctx->stream);
+  if (h->mo) dvs_motion_destroy(h->mo);
   if (h->ctx) dvs_matcher_destroy(h->ctx);
   if (h->orb) dvs_orb_destroy(h->orb);
   delete h;
@@ -378,6 +422,7 @@ dvs_status dvs_tracker_set_stream(dvs_tracker* h, void* hip_stream) {
   DVS_ARG(h);
   DVS_TRY(dvs_tracker_synchronize(h));
   DVS_TRY(dvs_orb_set_stream(h->orb, hip_stream));
+  if (h->mo) DVS_TRY(dvs_motion_set_stream(h->mo, hip_stream));
   return dvs_matcher_set_stream(h->ctx, hip_stream);
 }
 
@@ -409,7 +454,28 @@ dvs_status dvs_tracker_track(dvs_tracker* h, const uint8_t* image, int32_t chann
     DVS_TRY(dvs_bgr_to_gray_device(h->ctx, h->d_img.get(), 1, rows, cols, (size_t)cols * 3, 0, h->d_gray.get(), cols, 0, P.gray_variant));
     d_gray = h->d_gray.get();
   }
-  DVS_TRY(dvs_orb_extract_batch_device(h->orb, d_gray, 1, rows, cols, cols, (size_t)rows * cols, (dvs_keypoint*)h->d_kraw.get(), h->d_draw.get(), cap, cnt + C_EXT));
+  const uint8_t* d_keep = nullptr;   // the motion mask of this frame (opt-in; NULL: the unmasked extraction, as ever)
+  if (h->mo) {
+    const int ns = h->mo_lag + 1;
+    const size_t px = (size_t)rows * cols;
+    uint16_t* d_cur = h->mo_ring.get() + (size_t)(t % ns) * px;
+    DVS_HIP(hipMemcpyAsync(d_cur, h->d_depth[p].get(), px * 2, hipMemcpyHostToDevice, st));
+    h->mo_ref = -1;
+    if (h->prev_valid && !h->mo_after_reset && h->mo_seq >= 1) {
+      const int64_t ref = t - std::min(h->mo_lag, h->mo_seq);
+      const dvs_tracker::MotionSlot& rs = h->mo_slot[ref % ns];
+      if (rs.frame == ref) {
+        motion_relative_pose(h, t, rs, h->mo_R, h->mo_t);
+        DVS_TRY(dvs_motion_segment_device(h->mo, h->mo_ring.get() + (size_t)(ref % ns) * px, (size_t)cols * 2, d_cur, (size_t)cols * 2, h->mo_R, h->mo_t,
+                                          h->mo_mask.get(), cols, nullptr));
+        h->mo_ref = ref;
+        d_keep = h->mo_mask.get();
+      }
+    }
+  }
+  if (d_keep) DVS_TRY(dvs_orb_extract_batch_device_masked(h->orb, d_gray, 1, rows, cols, cols, (size_t)rows * cols, d_keep, cols, 0, (dvs_keypoint*)h->d_kraw.get(),
+                                                          h->d_draw.get(), cap, cnt + C_EXT));
+  else DVS_TRY(dvs_orb_extract_batch_device(h->orb, d_gray, 1, rows, cols, cols, (size_t)rows * cols, (dvs_keypoint*)h->d_kraw.get(), h->d_draw.get(), cap, cnt + C_EXT));
   DVS_TRY(dvs_filter_depth_batch_device(h->ctx, (const dvs_keypoint*)h->d_kraw.get(), h->d_draw.get(), cnt + C_EXT, cap, 1, h->d_depth[p].get(), rows, cols,
                                         (size_t)cols * 2, 0, P.min_depth, P.max_depth, h->f_k[p].get(), h->f_d[p].get(), nullptr, cnt + C_F0 + p));
   const bool tracking = h->prev_valid && h->prev_n > 0;
@@ -423,7 +489,17 @@ dvs_status dvs_tracker_track(dvs_tracker* h, const uint8_t* image, int32_t chann
   out->n_extracted = n_ext; out->n_filtered = n_f;
   for (int k = 0; k < 9; k++) out->R[k] = h->R[k];
   for (int k = 0; k < 3; k++) out->t[k] = h->tt[k];
-  auto advance = [&]() { h->p = q; h->prev_n = n_f; h->prev_valid = true; h->t = t + 1; };   // :1258-1259, 1274-1275 / :1299-1312
+  auto advance = [&]() {   // :1258-1259, 1274-1275 / :1299-1312
+    if (h->mo) {           // this frame's pose beside its depth image in the ring; a first frame and a tracking reset begin a sequence
+      dvs_tracker::MotionSlot& s = h->mo_slot[t % (h->mo_lag + 1)];
+      s.frame = t; s.pose_updated = out->pose_updated != 0;
+      memcpy(s.R, h->R, sizeof(s.R)); memcpy(s.t, h->tt, sizeof(s.t));
+      const bool begins = out->first_frame || out->tracking_reset;
+      h->mo_seq = begins ? 1 : std::min(h->mo_seq + 1, h->mo_lag + 1);
+      h->mo_after_reset = out->tracking_reset != 0;
+    }
+    h->p = q; h->prev_n = n_f; h->prev_valid = true; h->t = t + 1;
+  };
   const int bw = 1 - h->bkf;                       // where this frame's backend set goes (the last keyframe's stays)
   int n_backend = 0;
   bool publish = false;
@@ -600,6 +676,56 @@ dvs_status dvs_tracker_get_backend_features(dvs_tracker* h, dvs_keypoint* kps, u
   if (desc) DVS_HIP(hipMemcpyAsync(desc, h->b_d[h->blast].get(), m * 32, hipMemcpyDeviceToHost, st));
   if (sel_index) DVS_HIP(hipMemcpyAsync(sel_index, h->b_sel.get(), m * 4, hipMemcpyDeviceToHost, st));
   DVS_HIP(hipStreamSynchronize(st));
+  return DVS_OK;
+}
+
+dvs_status dvs_tracker_set_motion_mask(dvs_tracker* h, const dvs_motion_params* p, int32_t lag) {
+  DVS_ARG(h);
+  dvs_motion_params mp;
+  if (p) {
+    DVS_ARG(lag >= 1 && lag <= 16);
+    mp = *p;
+    mp.rows = h->P.rows; mp.cols = h->P.cols; mp.fx = h->P.fx; mp.fy = h->P.fy; mp.cx = h->P.cx; mp.cy = h->P.cy;
+    DVS_TRY(motion_check_params(mp));
+  }
+  DVS_TRY(dvs_tracker_synchronize(h));
+  DVS_HIP(hipSetDevice(h->device));
+  if (h->mo) { dvs_motion_destroy(h->mo); h->mo = nullptr; }
+  h->mo_ring = DeviceBuf<uint16_t>(); h->mo_mask = DeviceBuf<uint8_t>();
+  h->mo_lag = 0;
+  motion_reset_state(h);
+  if (!p) return DVS_OK;
+  const size_t px = (size_t)h->P.rows * h->P.cols;
+  dvs_status s = dvs_motion_create(&mp, h->device, &h->mo);
+  if (s == DVS_OK) s = dvs_motion_set_stream(h->mo, h->ctx->stream);
+  if (s == DVS_OK) s = h->mo_ring.alloc(px * (size_t)(lag + 1));
+  if (s == DVS_OK) s = h->mo_mask.alloc(px);
+  if (s != DVS_OK) {
+    if (h->mo) { dvs_motion_destroy(h->mo); h->mo = nullptr; }
+    h->mo_ring = DeviceBuf<uint16_t>(); h->mo_mask = DeviceBuf<uint8_t>();
+    return s;
+  }
+  h->mo_lag = lag;
+  return DVS_OK;
+}
+
+dvs_status dvs_tracker_get_motion_mask(dvs_tracker* h, uint8_t* mask, size_t step, double* R9, double* t3, int64_t* ref_frame_index, dvs_motion_stats* stats) {
+  DVS_ARG(h && (!mask || step >= (size_t)h->P.cols));
+  const bool used = h->mo && h->mo_ref >= 0;
+  if (ref_frame_index) *ref_frame_index = used ? h->mo_ref : -1;
+  for (int k = 0; k < 9; k++) if (R9) R9[k] = used ? h->mo_R[k] : (k % 4 == 0 ? 1.0 : 0.0);
+  for (int k = 0; k < 3; k++) if (t3) t3[k] = used ? h->mo_t[k] : 0.0;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (!used) {
+    if (mask) for (int r = 0; r < h->P.rows; r++) memset(mask + (size_t)r * step, 255, (size_t)h->P.cols);
+    return DVS_OK;
+  }
+  DVS_HIP(hipSetDevice(h->device));
+  if (stats) DVS_TRY(motion_last_stats(h->mo, stats));
+  if (mask) {
+    DVS_HIP(hipMemcpy2DAsync(mask, step, h->mo_mask.get(), (size_t)h->P.cols, (size_t)h->P.cols, (size_t)h->P.rows, hipMemcpyDeviceToHost, h->ctx->stream));
+    DVS_HIP(hipStreamSynchronize(h->ctx->stream));
+  }
   return DVS_OK;
 }
 

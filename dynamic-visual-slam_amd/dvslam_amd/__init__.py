@@ -17,3 +17,4 @@ from .bow import OrbVocabulary, OrbDatabase  # noqa: F401
 from .loop import LoopDatabase  # noqa: F401
 from ._lib import LoopVerifyParams  # noqa: F401
 from .pose_graph import PoseGraph  # noqa: F401
+from .motion import MotionSegmenter, MotionParams, MotionStats  # noqa: F401

@@ -3,6 +3,7 @@ handle and one call per RGB-D frame, device-resident between the image upload an
 import ctypes as C
 import numpy as np
 from ._lib import lib, check, ptr, KP_DTYPE, OrbParams, DvsError
+from .motion import MotionParams, MotionStats
 
 KF_FIRST_FRAME, KF_NO_REFERENCE, KF_FEW_MATCHES, KF_MAX_FRAMES = 1, 2, 4, 8
 
@@ -45,6 +46,8 @@ def _bind(L):
     L.dvs_tracker_synchronize.argtypes = [vp]
     L.dvs_tracker_track.argtypes = [vp, vp, i32, sz, vp, sz, i32, C.c_uint32, C.POINTER(TrackResult), vp, sz]
     L.dvs_tracker_get_backend_features.argtypes = [vp, vp, vp, vp, i32, C.POINTER(i32)]
+    L.dvs_tracker_set_motion_mask.argtypes = [vp, C.POINTER(MotionParams), i32]
+    L.dvs_tracker_get_motion_mask.argtypes = [vp, vp, sz, vp, vp, C.POINTER(C.c_int64), C.POINTER(MotionStats)]
     L.dvs_keyframe_cdr_capacity.argtypes = [C.c_char_p, i32]; L.dvs_keyframe_cdr_capacity.restype = sz
     return L
 
@@ -114,6 +117,17 @@ class Tracker:
         k = np.zeros(self.capacity, KP_DTYPE); d = np.zeros((self.capacity, 32), np.uint8); s = np.zeros(self.capacity, np.int32); n = C.c_int32()
         check(self._L.dvs_tracker_get_backend_features(self._h, ptr(k), ptr(d), ptr(s), self.capacity, C.byref(n)))
         return k[:n.value].copy(), d[:n.value].copy(), s[:n.value].copy()
+
+    def set_motion_mask(self, params, lag=4):
+        """dvs_tracker_set_motion_mask: params a motion.MotionParams (its size and intrinsics are replaced by the tracker's) or None to
+        switch the motion mask off; lag in 1..16"""
+        check(self._L.dvs_tracker_set_motion_mask(self._h, C.byref(params) if params is not None else None, int(lag)))
+
+    def motion_mask(self):
+        """what the last frame's extraction used -> (mask uint8 (rows, cols), R (3, 3), t (3,), reference frame index or -1, stats dict)"""
+        mask = np.empty((self.rows, self.cols), np.uint8); R = np.empty(9); t = np.empty(3); ref = C.c_int64(); st = MotionStats()
+        check(self._L.dvs_tracker_get_motion_mask(self._h, ptr(mask), self.cols, ptr(R), ptr(t), C.byref(ref), C.byref(st)))
+        return mask, R.reshape(3, 3), t, int(ref.value), st.as_dict()
 
     def reset(self):
         check(self._L.dvs_tracker_reset(self._h))

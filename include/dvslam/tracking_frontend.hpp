@@ -62,6 +62,19 @@ class TrackingFrontend {
     if (sel) sel->resize((size_t)n);
     return n;
   }
+  // the motion-mask opt-in (dvs_tracker_set_motion_mask): p's size and intrinsics are replaced by the tracker's, lag in 1..16; nullptr: off
+  void setMotionMask(const dvs_motion_params* p, int lag = 4) {
+    if (dvs_tracker_set_motion_mask(h_, p, lag) != DVS_OK) throw std::runtime_error(std::string("dvs_tracker_set_motion_mask: ") + dvs_last_error());
+  }
+  // what the last frame's extraction used: the mask (rows x cols packed; all 255 when none), the relative pose, the statistics; returns
+  // the reference's frame index, -1 when the extraction was unmasked
+  int64_t motionMask(std::vector<uint8_t>& mask, double* R9 = nullptr, double* t3 = nullptr, dvs_motion_stats* stats = nullptr) {
+    mask.resize((size_t)params_.rows * (size_t)params_.cols);
+    int64_t ref = -1;
+    if (dvs_tracker_get_motion_mask(h_, mask.data(), (size_t)params_.cols, R9, t3, &ref, stats) != DVS_OK)
+      throw std::runtime_error(std::string("dvs_tracker_get_motion_mask: ") + dvs_last_error());
+    return ref;
+  }
   dvs_tracker* handle() const { return h_; }
   const dvs_tracker_params& params() const { return params_; }
 

@@ -720,6 +720,79 @@ dvs_status dvs_tracker_track(dvs_tracker* h, const uint8_t* image, int32_t chann
  * rows); *n = rows available.  This read-back is the caller's choice, not part of the per-frame path. */
 dvs_status dvs_tracker_get_backend_features(dvs_tracker* h, dvs_keypoint* kps, uint8_t* desc, int32_t* sel_index, int32_t cap, int32_t* n);
 
+/* ============================ motion segmentation from depth: keep masks for the extractor ====================
+ * Which pixels of the current depth image are moving, decided from two depth images, the relative pose between them and the intrinsics
+ * (csrc/motion_seg.hip; INTEGRATION.md "Motion segmentation"): a point that now occupies space an earlier frame saw as free has moved.
+ * The output is an 8-bit mask of the current frame, 255 = keep, 0 = moving, level-0 sized — exactly what dvs_orb_extract*_masked reads.
+ * The reference has no counterpart (it filters YOLO boxes, backend.cpp:746-751).  tests/motion_ref.py restates the rule in numpy and the
+ * GPU tests compare bit for bit.
+ *
+ * Inputs: D_ref, D_cur 16UC1 depth in millimetres (rows x cols); fx, fy, cx, cy; R[9] (row-major), t[3] with X_ref = R X_cur + t.
+ * Stage 1, seeds.  Every current pixel (u, v) on its own, FP64 throughout, no contraction, every expression evaluated left to right as
+ * written.  valid(d) := min_depth_mm < d && d <= max_depth_mm (integers).
+ *   d = D_cur[v][u]; invalid: no verdict
+ *   z = d * 0.001, x = (u - cx) * z / fx, y = (v - cy) * z / fy
+ *   xr = R[0]*x + R[1]*y + R[2]*z + t[0], yr and zr likewise (rows 1 and 2); zr <= 0: no verdict
+ *   ur = floor(fx * xr / zr + cx + 0.5), vr = floor(fy * yr / zr + cy + 0.5); a verdict needs 1 <= ur <= cols - 2 && 1 <= vr <= rows - 2,
+ *   compared as doubles before the conversion to integers
+ *   all nine D_ref values of the 3 x 3 window around (ur, vr) must be valid; m = their integer minimum   (n_valid counts who gets here)
+ *   tau = tau0_m + tau2_per_m * zr * zr;  SEED iff zr < m * 0.001 - tau, strictly
+ * i.e. the point lies nearer to the reference camera than anything that camera saw around that ray.  A point behind the reference surface
+ * is occluded, not moving: no seed.
+ * Stage 2, components.  Seeds are labelled by 8-connectivity: label[p] = the linear index y * cols + x of the component's smallest-index
+ * pixel, -1 off the seeds (so the labelling does not depend on any scheduling); area[root] = its pixel count (integer adds).  A seed is
+ * DYNAMIC iff its component has area >= min_area.
+ * Stage 3, mask.  mask[p] = 0 iff a dynamic pixel lies in the (2r+1) x (2r+1) square around p, r = dilate_radius; pixels outside the image
+ * count as not dynamic; every other pixel is 255.
+ * Known limit: an object displaced by less than its own width between the two frames still covers most of the space it covered before,
+ * and only its leading part is found (a third of its width: about 40 % of its pixels) — compare against a frame several frames back.
+ * The default tolerances are a starting point: they were NEVER fitted to a sensor. */
+typedef struct dvs_motion dvs_motion;
+typedef struct dvs_motion_params {
+  int32_t rows, cols;                       /* 1..4096 each */
+  double fx, fy, cx, cy;                    /* finite, fx, fy > 0 */
+  int32_t min_depth_mm, max_depth_mm;       /* 300 / 3000: the tracker's gates; 0 <= min < max <= 65535 */
+  double tau0_m, tau2_per_m;                /* 0.03 / 0.005; finite, >= 0 */
+  int32_t min_area;                         /* 200; >= 1 */
+  int32_t dilate_radius;                    /* 8; 0..31 */
+} dvs_motion_params;
+typedef struct dvs_motion_stats {           /* all exact */
+  int32_t n_valid;                          /* pixels that reached the depth compare */
+  int32_t n_seed;
+  int32_t n_components, n_components_kept;  /* all / those with area >= min_area */
+  int32_t n_dynamic;                        /* seeds of kept components */
+  int32_t n_masked;                         /* zeros in the mask */
+} dvs_motion_stats;
+void dvs_motion_default_params(dvs_motion_params* p);   /* the defaults above; rows / cols / intrinsics stay zero */
+/* DVS_ERR_ARG for parameters outside the ranges above, before any device work; then DVS_ERR_NO_DEVICE without a gfx950 (no CPU fallback).
+ * The handle works on HIP's legacy default stream until dvs_motion_set_stream. */
+dvs_status dvs_motion_create(const dvs_motion_params* params, int32_t device, dvs_motion** out);
+void dvs_motion_destroy(dvs_motion* h);
+dvs_status dvs_motion_set_stream(dvs_motion* h, void* hip_stream);   /* synchronises the old stream first */
+/* One mask.  d_ref / d_cur: device 16UC1 images, `*_step` bytes between rows (>= 2 cols, even); d_mask: device, mask_step >= cols.  R, t:
+ * host, must be finite.  A fixed sequence of launches on the handle's stream, nothing read back: with stats == NULL the call does not
+ * synchronise; otherwise it waits and fills *stats.  Nothing of an earlier call survives into the next.  Bad arguments: DVS_ERR_ARG
+ * before any device work. */
+dvs_status dvs_motion_segment_device(dvs_motion* h, const uint16_t* d_ref, size_t ref_step, const uint16_t* d_cur, size_t cur_step, const double* R9,
+                                     const double* t3, uint8_t* d_mask, size_t mask_step, dvs_motion_stats* stats);
+/* the same with host pointers; synchronises */
+dvs_status dvs_motion_segment(dvs_motion* h, const uint16_t* ref, size_t ref_step, const uint16_t* cur, size_t cur_step, const double* R9,
+                              const double* t3, uint8_t* mask, size_t mask_step, dvs_motion_stats* stats);
+/* ---- the tracker's opt-in (csrc/tracker.hip): dynamic regions out of the keypoint budget without outside help ----
+ * p != NULL switches it on: rows / cols / intrinsics of *p are replaced by the tracker's, lag in 1..16.  From then on every frame's depth
+ * image is also copied into a device ring of lag + 1 slots with the pose R_, t_ after that frame, and BEFORE the extraction of frame t the
+ * mask of frame t against frame t - min(lag, frames since the sequence began) is computed and the extraction goes through
+ * dvs_orb_extract_batch_device_masked.  A sequence begins at a first frame and at a frame that reset the tracking; the frame that begins
+ * one, the frame after a tracking reset, and any frame without a reference in the ring are extracted unmasked.  The current pose is
+ * predicted by constant velocity, T(t-1) o (T(t-2)^-1 o T(t-1)) — just T(t-1) when frame t-1 did not update the pose or t-2 is not in the
+ * sequence; R_, t_ are camera-to-world, so R = R_ref^T R_pred, t = R_ref^T (t_pred - t_ref).  dvs_tracker_reset empties the ring.
+ * p == NULL switches it off (the default): the tracker then allocates and launches nothing it did not before.  Synchronises. */
+dvs_status dvs_tracker_set_motion_mask(dvs_tracker* h, const dvs_motion_params* p /* NULL: off */, int32_t lag);
+/* what the last frame's extraction used, so that a caller can recompute it: the mask (host, step >= cols; all 255 when none was used), the
+ * relative pose it was made with, the reference's frame index (-1: none) and the statistics (zeros when none).  Any output may be NULL. */
+dvs_status dvs_tracker_get_motion_mask(dvs_tracker* h, uint8_t* mask, size_t step, double* R9, double* t3, int64_t* ref_frame_index,
+                                       dvs_motion_stats* stats);
+
 /* ============================ the mapping backend: one call per keyframe, the map kept on the device ==========================
  * Backend::syncCallback (backend.cpp:709-832), the window selection of bundleAdjustmentCallback (:892-945), updateOptimizedResults
  * (:1356-1392) and pruneLandmarks (:1249-1322) as ONE handle (csrc/backend.hip; INTEGRATION.md "Mapping backend").  The landmark table
