@@ -16,6 +16,7 @@
 #include <string.h>
 #include <new>
 #include <vector>
+#include "backend_internal.h"
 #include "common.h"
 #include "cull_order.h"
 #include "device_mem.h"
@@ -726,6 +727,35 @@ dvs_status dvs_tracker_get_motion_mask(dvs_tracker* h, uint8_t* mask, size_t ste
     DVS_HIP(hipMemcpy2DAsync(mask, step, h->mo_mask.get(), (size_t)h->P.cols, (size_t)h->P.cols, (size_t)h->P.rows, hipMemcpyDeviceToHost, h->ctx->stream));
     DVS_HIP(hipStreamSynchronize(h->ctx->stream));
   }
+  return DVS_OK;
+}
+
+// the last frame's depth-filtered set: dvs_tracker_track's advance() made it the "previous" one, f_*[1 - p] with prev_n rows
+dvs_status dvs_tracker_get_filtered_features(dvs_tracker* h, dvs_keypoint* kps, uint8_t* desc, int32_t cap, int32_t* n) {
+  DVS_ARG(h && n && cap >= 0);
+  const int m = h->prev_valid ? h->prev_n : 0;
+  *n = m;
+  if (m > cap) { set_error("dvs_tracker_get_filtered_features: %d rows, capacity %d", m, cap); return DVS_ERR_CAPACITY; }
+  if (m == 0) return DVS_OK;
+  DVS_HIP(hipSetDevice(h->device));
+  hipStream_t st = h->ctx->stream;
+  const int q = 1 - h->p;
+  if (kps) DVS_HIP(hipMemcpyAsync(kps, h->f_k[q].get(), (size_t)m * sizeof(dvs_keypoint), hipMemcpyDeviceToHost, st));
+  if (desc) DVS_HIP(hipMemcpyAsync(desc, h->f_d[q].get(), (size_t)m * 32, hipMemcpyDeviceToHost, st));
+  DVS_HIP(hipStreamSynchronize(st));
+  return DVS_OK;
+}
+
+// include/dvslam_hip.h "Tracking against the map": that set against the backend's landmark table, prior R_, t_; the tracker itself
+// launches nothing here
+dvs_status dvs_tracker_track_map(dvs_tracker* h, dvs_backend* backend, dvs_maptrack* mt, int32_t apply, dvs_maptrack_result* result) {
+  DVS_ARG(h && backend && mt && result && backend->device == h->device);
+  if (!h->prev_valid) { set_error("dvs_tracker_track_map: no frame has been tracked"); return DVS_ERR_EMPTY; }
+  DVS_HIP(hipSetDevice(h->device));
+  DVS_HIP(hipStreamSynchronize(h->ctx->stream));
+  const int q = 1 - h->p;
+  DVS_TRY(dvs_backend_track_frame(backend, mt, h->f_k[q].get(), h->f_d[q].get(), h->prev_n, h->R, h->tt, result));
+  if (apply && result->status == DVS_MAPTRACK_OK) { memcpy(h->R, result->R, sizeof(h->R)); memcpy(h->tt, result->t, sizeof(h->tt)); }
   return DVS_OK;
 }
 

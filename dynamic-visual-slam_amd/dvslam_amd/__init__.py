@@ -18,3 +18,4 @@ from .loop import LoopDatabase  # noqa: F401
 from ._lib import LoopVerifyParams  # noqa: F401
 from .pose_graph import PoseGraph  # noqa: F401
 from .motion import MotionSegmenter, MotionParams, MotionStats  # noqa: F401
+from .map_track import MapTracker, MapTrackParams, MapTrackResult  # noqa: F401

@@ -316,6 +316,16 @@ class MappingBackend:
         check(self._L.dvs_backend_global_ba(self._h, ba._h, C.byref(p), C.byref(r)))
         return dict(summary=r.summary, n_cameras=r.n_cameras, n_landmarks=r.n_landmarks, n_observations=r.n_observations, n_left_out=r.n_left_out)
 
+    def track_frame(self, map_tracker, d_kps, d_desc, n_kp, R, t):
+        """dvs_backend_track_frame: a frame's keypoints and descriptors (device pointers or DeviceBuffers) against the landmark table as it
+        stands, prior camera-to-world pose (R, t) -> map_track result dict; the map is not modified"""
+        from . import map_track as M
+        M._bind(self._L)
+        R = np.ascontiguousarray(R, np.float64).reshape(9); t = np.ascontiguousarray(t, np.float64).reshape(3)
+        r = M.MapTrackResult()
+        check(self._L.dvs_backend_track_frame(self._h, map_tracker.handle, M._raw(d_kps), M._raw(d_desc), int(n_kp), ptr(R), ptr(t), C.byref(r)))
+        return r.as_dict()
+
     def reset(self):
         check(self._L.dvs_backend_reset(self._h))
 

@@ -118,6 +118,23 @@ class Tracker:
         check(self._L.dvs_tracker_get_backend_features(self._h, ptr(k), ptr(d), ptr(s), self.capacity, C.byref(n)))
         return k[:n.value].copy(), d[:n.value].copy(), s[:n.value].copy()
 
+    def track_map(self, backend, map_tracker, apply=False):
+        """dvs_tracker_track_map: the last frame's depth-filtered features against the backend's landmark table, prior R_, t_ -> map_track
+        result dict; apply=True and status 0: the refined pose replaces R_, t_"""
+        from . import map_track as M
+        M._bind(self._L)
+        r = M.MapTrackResult()
+        check(self._L.dvs_tracker_track_map(self._h, backend._h, map_tracker.handle, 1 if apply else 0, C.byref(r)))
+        return r.as_dict()
+
+    def filtered_features(self):
+        """the last frame's depth-filtered set -> (keypoints, descriptors)"""
+        from . import map_track as M
+        M._bind(self._L)
+        k = np.zeros(self.capacity, KP_DTYPE); d = np.zeros((self.capacity, 32), np.uint8); n = C.c_int32()
+        check(self._L.dvs_tracker_get_filtered_features(self._h, ptr(k), ptr(d), self.capacity, C.byref(n)))
+        return k[:n.value].copy(), d[:n.value].copy()
+
     def set_motion_mask(self, params, lag=4):
         """dvs_tracker_set_motion_mask: params a motion.MotionParams (its size and intrinsics are replaced by the tracker's) or None to
         switch the motion mask off; lag in 1..16"""

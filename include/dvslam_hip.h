@@ -1366,6 +1366,116 @@ typedef struct dvs_backend_gba_result {
 } dvs_backend_gba_result;
 dvs_status dvs_backend_global_ba(dvs_backend* h, dvs_ba* ba, const dvs_ba_global_params* params /* NULL: defaults */, dvs_backend_gba_result* out);
 
+/* ======================================= Tracking against the map ================================= */
+/* A frame's keypoints matched against the landmarks of the map and its pose refined on those 3D-2D pairs (csrc/map_track.hip;
+ * INTEGRATION.md "Tracking against the map"): what ORB-SLAM calls TrackLocalMap — SearchByProjection, then PoseOptimization (Mur-Artal,
+ * Montiel, Tardos 2015, section V-D), as published ideas.  The reference's front end is odometry only, so there is no reference interface
+ * to pin: PARITY UNPINNED, the rule is the library's own, stated here in full and restated in numpy in tests/map_track_ref.py.  Integer
+ * outputs and the stage-1 doubles are compared bit for bit; the refinement calls sin / cos / sqrt and is compared through its inlier flags
+ * and its cost.
+ * Poses at the interface are camera-to-world as the tracker's and the backend's (X_w = R X_c + t, R 9 row-major doubles).  Inside,
+ * R_cw = R^T and t_cw[i] = -((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]).
+ *  Inputs    n_lm landmarks — float xyz[3], uint8 desc[32], int64 id in ascending order (a row index stands for the id where no id array
+ *            is given) —, n_kp keypoints — dvs_keypoint, uint8 desc[32] —, the prior pose, the parameters.
+ *  Stage 1   projection, one landmark on its own, FP64, only + - * /, every expression left to right as written, no contraction.
+ *            X = the float position widened; c[i] = ((R_cw[3i] * X0 + R_cw[3i + 1] * X1) + R_cw[3i + 2] * X2) + t_cw[i];
+ *            u = fx * c0 / c2 + cx, v = fy * c1 / c2 + cy.  VISIBLE iff min_z < c2 && c2 < max_z && 0 <= u && u < cols && 0 <= v &&
+ *            v < rows, compared as doubles.  A landmark that is not visible reports u = v = 0.
+ *  Stage 2   window search.  A keypoint is BINNED iff 0 <= x < cols && 0 <= y < rows (as floats) and 0 <= octave < n_levels; its cell
+ *            is ((int)x / cell, (int)y / cell) of a grid of ceil(cols / cell) x ceil(rows / cell) square cells, cells in row-major
+ *            order, the keypoints of a cell in ascending index (a stable counting sort).  A keypoint that is not binned is never
+ *            matched; the host-pointer form refuses it (DVS_ERR_ARG), the device-pointer forms count it in n_unbinned.
+ *            A binned keypoint k is a CANDIDATE of a visible landmark j iff |(double)x_k - u| <= radius && |(double)y_k - v| <= radius.
+ *            Only the cells that overlap the window are visited; the outcome does not depend on `cell`.  d = hamming(desc_j, desc_k);
+ *            best = the candidate with the smallest (d, k); d_second = the smallest d among the OTHER candidates (-1 if none).  The
+ *            landmark PROPOSES to best iff d_best < max_hamming (strict, as in the backend) and (there is no other candidate, or
+ *            ratio_pct <= 0, or d_best * 100 < ratio_pct * d_second — integers).
+ *  Stage 3   one-to-one.  Every keypoint KEEPS the proposal with the smallest (d, landmark row) — rows ascend with the id; an integer
+ *            minimum on the device, so there is no tie deviation.  A landmark that loses stays unmatched: there is no second round.
+ *  Stage 4   pose refinement on the kept pairs in keypoint order: X_i the landmark position widened, p_i = (x, y) of the keypoint widened,
+ *            s2_i = level_sigma2[octave].  With c = R_cw X_i + t_cw (as in stage 1): e_i = p_i - (fx c0 / c2 + cx, fy c1 / c2 + cy),
+ *            chi_i = (e_i . e_i) / s2_i; a pair with c2 <= 0 has chi_i = +infinity and adds nothing to any sum.  Parameters
+ *            delta = (omega, upsilon): R_cw <- Exp(omega) R_cw, t_cw <- Exp(omega) t_cw + upsilon, Exp by Rodrigues' formula
+ *            (|omega| < 1e-12: I + [omega]x); the camera point's Jacobian is [-[c]x | I].  Four rounds of ten Gauss-Newton steps
+ *            H delta = b, H = sum w_i J_i^T J_i / s2_i, b = sum w_i J_i^T e_i / s2_i, no step control.  Rounds 0 and 1: w_i =
+ *            sqrt(chi2_gate / chi_i) where chi_i > chi2_gate, else 1 (Huber with delta^2 = chi2_gate); rounds 2 and 3: w_i = 1.  The sums
+ *            run over the pairs currently flagged inlier — all of them before round 0 —; after every round ALL pairs are reclassified,
+ *            outliers included: inlier iff chi_i <= chi2_gate at the round's last pose.  The 6 x 6 system is solved by Cholesky in FP64
+ *            by one lane; the 27 sums and the cost are formed in one fixed order (pair i on lane i mod 256, the lanes added in a fixed order), so
+ *            two identical calls give identical bytes.  A pivot <= 1e-10 * max_diag(H), or anything not finite, ends the refinement.
+ *  Outcome   status 0 OK; 1 FEW_MATCHES: fewer than min_matches kept pairs, no refinement is run; 2 FEW_INLIERS: fewer than min_inliers
+ *            inliers after round 3; 3 DEGENERATE.  For every status but 0 the returned pose is the prior, byte for byte.  With status 0
+ *            it is R = R_cw^T, t[i] = -((R_cw[i] * t_cw[0] + R_cw[3 + i] * t_cw[1]) + R_cw[6 + i] * t_cw[2]), converted once at the end.
+ *            cost = sum of chi_i over the final inliers at the final pose (0 unless the four rounds ran).  Every status is DVS_OK.
+ * All four rounds run inside ONE kernel of one call; no host decision is taken between iterations; one 128-byte record comes back.
+ * Out of scope: predicted octave and viewing-angle gates, descriptor re-selection, relocalisation after a tracking reset, several GPUs. */
+typedef struct dvs_maptrack dvs_maptrack;
+#define DVS_MAPTRACK_MAX_LEVELS 16
+enum { DVS_MAPTRACK_OK = 0, DVS_MAPTRACK_FEW_MATCHES = 1, DVS_MAPTRACK_FEW_INLIERS = 2, DVS_MAPTRACK_DEGENERATE = 3 };
+typedef struct dvs_maptrack_params {
+  int32_t rows, cols;                  /* 1..16384 each */
+  double fx, fy, cx, cy;               /* finite, fx, fy > 0 */
+  double min_z, max_z;                 /* 0.05 / 20.0 metres; 0 <= min_z < max_z, finite */
+  double radius;                       /* 15.0 pixels; finite, >= 0 */
+  int32_t cell;                        /* 32; 1..16384, and at most 2^20 cells */
+  int32_t max_hamming;                 /* 50; 0..257 */
+  int32_t ratio_pct;                   /* 90; <= 0 switches the ratio test off; <= 100000 */
+  int32_t reserved0;
+  double chi2_gate;                    /* 5.991; finite, > 0 */
+  int32_t min_matches;                 /* 15; >= 3 */
+  int32_t min_inliers;                 /* 10; >= 0 */
+  int32_t n_levels;                    /* 8; 1..DVS_MAPTRACK_MAX_LEVELS */
+  int32_t reserved1;
+  double level_sigma2[DVS_MAPTRACK_MAX_LEVELS];   /* the extractor's sigma2 table (dvs_orb_get_tables) widened; the first n_levels finite, > 0 */
+} dvs_maptrack_params;
+typedef struct dvs_maptrack_result {   /* 128 bytes */
+  double R[9], t[3];                   /* the refined pose with status 0, else the prior's bytes */
+  double cost;
+  int32_t status;                      /* DVS_MAPTRACK_* */
+  int32_t n_visible, n_proposed;       /* landmarks visible / that proposed */
+  int32_t n_matches;                   /* kept pairs (refine_device: the correspondences given) */
+  int32_t n_inliers;                   /* inliers of the last classification (0 with FEW_MATCHES and DEGENERATE) */
+  int32_t n_unbinned;                  /* keypoints outside the image or the octave table (device-pointer forms) */
+} dvs_maptrack_result;
+/* the defaults above, level_sigma2 = the float table of scale factor 1.2 over 8 levels widened; rows / cols / intrinsics stay zero */
+void dvs_maptrack_default_params(dvs_maptrack_params* p);
+/* DVS_ERR_ARG for parameters outside the ranges above, before any device work; then DVS_ERR_NO_DEVICE without a gfx950 (no CPU fallback).
+ * The handle works on HIP's legacy default stream until dvs_maptrack_set_stream.  Not thread-safe; buffers grow with the largest call. */
+dvs_status dvs_maptrack_create(const dvs_maptrack_params* params, int32_t device, dvs_maptrack** out);
+void dvs_maptrack_destroy(dvs_maptrack* h);
+dvs_status dvs_maptrack_set_stream(dvs_maptrack* h, void* hip_stream);   /* synchronises the old stream first */
+/* Stages 1-3 on device arrays.  d_lm_id may be NULL (ids = rows); descriptor arrays 8-byte aligned; R9 / t3 host, finite.  result NULL: the
+ * call does not synchronise; otherwise it waits and fills the counts (pose = the prior, status 0, cost 0, n_inliers 0). */
+dvs_status dvs_maptrack_search_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                      const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3,
+                                      dvs_maptrack_result* result);
+/* Stage 4 alone — PoseOptimization on explicit correspondences: d_X n x 3 doubles, d_px n x 2 doubles, d_octave n int32 (an octave outside
+ * the table makes its pair a permanent outlier).  n_matches = n; fewer than min_matches is FEW_MATCHES.  Synchronises. */
+dvs_status dvs_maptrack_refine_device(dvs_maptrack* h, const double* d_X, const double* d_px, const int32_t* d_octave, int32_t n, const double* R9,
+                                      const double* t3, dvs_maptrack_result* result);
+/* Stages 1-4 in one call: the search's launches, then the one refinement kernel, which also gathers the kept pairs.  Synchronises. */
+dvs_status dvs_maptrack_track_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                     const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3,
+                                     dvs_maptrack_result* result);
+/* the same with host pointers (lm_id may be NULL); an unbinned keypoint and ids that do not ascend strictly are DVS_ERR_ARG */
+dvs_status dvs_maptrack_track(dvs_maptrack* h, const float* lm_xyz, const uint8_t* lm_desc, const int64_t* lm_id, int32_t n_lm, const dvs_keypoint* kps,
+                              const uint8_t* desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result);
+/* The last call's per-keypoint arrays (each nullable, count-then-capacity: *n = the last call's n_kp is always set): the landmark row kept
+ * (-1: none), its id, the distance (-1: none) and whether the pair ended as an inlier (all 0 unless status is 0 or 2).  After
+ * dvs_maptrack_refine_device the rows are the correspondences: lm_row[i] = lm_id[i] = i, dist 0. */
+dvs_status dvs_maptrack_get_matches(dvs_maptrack* h, int32_t cap, int32_t* lm_row, int64_t* lm_id, int32_t* dist, uint8_t* inlier, int32_t* n);
+/* dvs_maptrack_track_device with the backend's landmark table as it stands — position, descriptor and id columns handed over on the device,
+ * nothing of them crosses to the host; the map is not modified.  Same device for both handles; the backend's stream is synchronised first. */
+dvs_status dvs_backend_track_frame(dvs_backend* h, dvs_maptrack* mt, const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9,
+                                   const double* t3, dvs_maptrack_result* result);
+/* After a dvs_tracker_track: the last frame's depth-filtered keypoints and descriptors where the tracker left them in HBM, with the prior
+ * R_, t_, through dvs_backend_track_frame.  With apply != 0 and status 0 the refined pose replaces R_, t_, so the next frame's odometry
+ * composes on it (the motion mask's ring keeps the poses it recorded).  DVS_ERR_EMPTY before the first frame; the three handles
+ * are on one device, and mt's size and intrinsics are the caller's to make the tracker's.  Strictly opt-in: a tracker on which it is never called allocates and launches nothing it did not before. */
+dvs_status dvs_tracker_track_map(dvs_tracker* h, dvs_backend* backend, dvs_maptrack* mt, int32_t apply, dvs_maptrack_result* result);
+/* that set, for tests and adapters (kps / desc nullable, `cap` rows; *n = rows available) */
+dvs_status dvs_tracker_get_filtered_features(dvs_tracker* h, dvs_keypoint* kps, uint8_t* desc, int32_t cap, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif
