@@ -11,6 +11,8 @@
 //   k_mt_finalize  a keypoint per lane: the kept row, id and distance out of the key; the landmark's kept flag
 //   k_mt_refine    ONE workgroup: gathers the kept pairs in keypoint order, then runs the four rounds of ten Gauss-Newton steps itself —
 //                  per-lane strided partial sums, added through LDS in one fixed order, the 6 x 6 Cholesky on lane 0 — and writes the 128-byte record.  No host decision between iterations.
+//                  The schedule (first round, rounds, steps per round) is an argument, 0, 4, 10 in every product launch; the product's
+//                  instantiation has it as constants, the test hook's (dvs_test_maptrack_refine_steps: single steps compared) reads it.
 // Every launch is on the handle's stream; nothing is read back but the record.
 #include <math.h>
 #include <string.h>
@@ -179,13 +181,14 @@ struct MtGather {   // gather = 0: explicit mode
   const int* kp_lm; const float* xyz; const dvs_keypoint* kps; int n_kp, gather;
 };
 
-// chi and residual of pair i at (R, t); false (chi = +inf) where the point is not in front of the camera or its octave has no sigma
+// chi and residual of pair i at (R, t); false (chi = +inf) where the point is not in front of the camera or its octave has no sigma.
+// A position that is not finite gives no finite c2 (a row of R times it is never finite), so c2 < inf keeps such a pair out as well.
 __device__ __forceinline__ bool mt_residual(const dvs_maptrack_params& P, const double* R, const double* t, const double* X, const double* px, int oct,
                                             double* c, double& ex, double& ey, double& s2, double& chi) {
   if (oct < 0 || oct >= P.n_levels) return false;
 #pragma unroll
   for (int i = 0; i < 3; i++) c[i] = ((R[3 * i] * X[0] + R[3 * i + 1] * X[1]) + R[3 * i + 2] * X[2]) + t[i];
-  if (!(c[2] > 0.0)) return false;
+  if (!(c[2] > 0.0 && c[2] < (double)INFINITY)) return false;
   ex = px[0] - (P.fx * c[0] / c[2] + P.cx);
   ey = px[1] - (P.fy * c[1] / c[2] + P.cy);
   s2 = P.level_sigma2[oct];
@@ -267,9 +270,13 @@ __device__ bool mt_solve_update(const double* s, double* R, double* t) {
   return true;
 }
 
+// rounds first_round .. first_round + n_rounds - 1 of n_iters steps each; round r is robust iff r < 2.  The product's schedule is 0, 4, 10:
+// kAnySchedule = false compiles those in (reading them cost a track call 3 - 5 %: EXPERIMENTS.md "Map tracking"), true takes the arguments
+template <bool kAnySchedule>
 __global__ __launch_bounds__(kRefThreads) void k_mt_refine(dvs_maptrack_params P, MtPose T, MtGather G, MtCorr C, int n_explicit, uint8_t* kp_inl,
                                                            int* kp_lm_out, long long* kp_id_out, int* kp_dist_out, const int* counters,
-                                                           dvs_maptrack_result* out) {
+                                                           int first_round_arg, int n_rounds_arg, int n_iters_arg, dvs_maptrack_result* out) {
+  const int first_round = kAnySchedule ? first_round_arg : 0, n_rounds = kAnySchedule ? n_rounds_arg : 4, n_iters = kAnySchedule ? n_iters_arg : 10;
   __shared__ double s_red[27 * kRedStride];
   __shared__ double s_red8[kSums][8];
   __shared__ double s_tot[kSums];
@@ -307,9 +314,9 @@ __global__ __launch_bounds__(kRefThreads) void k_mt_refine(dvs_maptrack_params P
   if (n < P.min_matches) {
     status = DVS_MAPTRACK_FEW_MATCHES;
   } else {
-    for (int round = 0; round < 4 && status == DVS_MAPTRACK_OK; round++) {
+    for (int round = first_round; round < first_round + n_rounds && status == DVS_MAPTRACK_OK; round++) {
       const bool robust = round < 2;
-      for (int it = 0; it < 10; it++) {
+      for (int it = 0; it < n_iters; it++) {
         double R[9], t[3], acc[kSums];
         for (int k = 0; k < 9; k++) R[k] = s_R[k];
         for (int k = 0; k < 3; k++) t[k] = s_t[k];
@@ -526,6 +533,35 @@ static dvs_status mt_read_result(dvs_maptrack* h, dvs_maptrack_result* result) {
   return DVS_OK;
 }
 
+// stage 4 on explicit correspondences with a schedule: dvs_maptrack_refine_device's launch (0, 4, 10) and the test hook's
+static dvs_status mt_refine_explicit(dvs_maptrack* h, const double* d_X, const double* d_px, const int32_t* d_octave, int32_t n, const double* R9,
+                                     const double* t3, bool any_schedule, int first_round, int n_rounds, int n_iters, dvs_maptrack_result* result) {
+  DVS_ARG(h && result && n >= 0 && n <= (1 << 30) && (n == 0 || (d_X && d_px && d_octave)));
+  DVS_ARG(((uintptr_t)d_X & 7) == 0 && ((uintptr_t)d_px & 7) == 0 && ((uintptr_t)d_octave & 3) == 0);
+  MtPose T;
+  DVS_TRY(maptrack_pose(R9, t3, &T));
+  DVS_HIP(hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  h->last_n_kp = 0; h->last_n_lm = 0; h->last_search = false;
+  if ((size_t)n > h->c_kp || (size_t)n > h->c_corr) DVS_HIP(hipStreamSynchronize(st));
+  DVS_TRY(mt_grow_kp(h, (size_t)n));
+  DVS_TRY(mt_grow_corr(h, (size_t)n));
+  MtGather G; G.kp_lm = nullptr; G.xyz = nullptr; G.kps = nullptr; G.n_kp = 0; G.gather = 0;
+  MtCorr C; C.X = const_cast<double*>(d_X); C.px = const_cast<double*>(d_px); C.oct = const_cast<int*>(d_octave); C.kp = nullptr; C.inl = h->cinl.get();
+#ifdef DVS_TEST_HOOKS
+  if (any_schedule)
+    hipLaunchKernelGGL(k_mt_refine<true>, dim3(1), dim3(kRefThreads), 0, st, h->P, T, G, C, n, h->kp_inl.get(), h->kp_lm.get(), h->kp_id.get(), h->kp_dist.get(),
+                       (const int*)nullptr, first_round, n_rounds, n_iters, h->d_res.get());
+  else
+#endif
+    hipLaunchKernelGGL(k_mt_refine<false>, dim3(1), dim3(kRefThreads), 0, st, h->P, T, G, C, n, h->kp_inl.get(), h->kp_lm.get(), h->kp_id.get(), h->kp_dist.get(),
+                       (const int*)nullptr, 0, 4, 10, h->d_res.get());
+  (void)any_schedule; (void)first_round; (void)n_rounds; (void)n_iters;
+  DVS_HIP(hipGetLastError());
+  h->last_n_kp = n;
+  return mt_read_result(h, result);
+}
+
 extern "C" {
 
 void dvs_maptrack_default_params(dvs_maptrack_params* p) {
@@ -593,23 +629,7 @@ dvs_status dvs_maptrack_search_device(dvs_maptrack* h, const float* d_lm_xyz, co
 
 dvs_status dvs_maptrack_refine_device(dvs_maptrack* h, const double* d_X, const double* d_px, const int32_t* d_octave, int32_t n, const double* R9,
                                       const double* t3, dvs_maptrack_result* result) {
-  DVS_ARG(h && result && n >= 0 && n <= (1 << 30) && (n == 0 || (d_X && d_px && d_octave)));
-  DVS_ARG(((uintptr_t)d_X & 7) == 0 && ((uintptr_t)d_px & 7) == 0 && ((uintptr_t)d_octave & 3) == 0);
-  MtPose T;
-  DVS_TRY(maptrack_pose(R9, t3, &T));
-  DVS_HIP(hipSetDevice(h->device));
-  hipStream_t st = h->stream;
-  h->last_n_kp = 0; h->last_n_lm = 0; h->last_search = false;
-  if ((size_t)n > h->c_kp || (size_t)n > h->c_corr) DVS_HIP(hipStreamSynchronize(st));
-  DVS_TRY(mt_grow_kp(h, (size_t)n));
-  DVS_TRY(mt_grow_corr(h, (size_t)n));
-  MtGather G; G.kp_lm = nullptr; G.xyz = nullptr; G.kps = nullptr; G.n_kp = 0; G.gather = 0;
-  MtCorr C; C.X = const_cast<double*>(d_X); C.px = const_cast<double*>(d_px); C.oct = const_cast<int*>(d_octave); C.kp = nullptr; C.inl = h->cinl.get();
-  hipLaunchKernelGGL(k_mt_refine, dim3(1), dim3(kRefThreads), 0, st, h->P, T, G, C, n, h->kp_inl.get(), h->kp_lm.get(), h->kp_id.get(), h->kp_dist.get(),
-                     (const int*)nullptr, h->d_res.get());
-  DVS_HIP(hipGetLastError());
-  h->last_n_kp = n;
-  return mt_read_result(h, result);
+  return mt_refine_explicit(h, d_X, d_px, d_octave, n, R9, t3, false, 0, 4, 10, result);
 }
 
 dvs_status dvs_maptrack_track_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
@@ -625,8 +645,8 @@ dvs_status dvs_maptrack_track_device(dvs_maptrack* h, const float* d_lm_xyz, con
   DVS_TRY(mt_search(h, T, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp));
   MtGather G; G.kp_lm = h->kp_lm.get(); G.xyz = d_lm_xyz; G.kps = d_kps; G.n_kp = n_kp; G.gather = 1;
   MtCorr C; C.X = h->cX.get(); C.px = h->cpx.get(); C.oct = h->coct.get(); C.kp = h->ckp.get(); C.inl = h->cinl.get();
-  hipLaunchKernelGGL(k_mt_refine, dim3(1), dim3(kRefThreads), 0, h->stream, h->P, T, G, C, 0, h->kp_inl.get(), h->kp_lm.get(), h->kp_id.get(), h->kp_dist.get(),
-                     (const int*)mt_counters(h), h->d_res.get());
+  hipLaunchKernelGGL(k_mt_refine<false>, dim3(1), dim3(kRefThreads), 0, h->stream, h->P, T, G, C, 0, h->kp_inl.get(), h->kp_lm.get(), h->kp_id.get(), h->kp_dist.get(),
+                     (const int*)mt_counters(h), 0, 4, 10, h->d_res.get());
   DVS_HIP(hipGetLastError());
   return mt_read_result(h, result);
 }
@@ -727,6 +747,12 @@ dvs_status dvs_test_maptrack_cells(dvs_maptrack* h, int32_t cap_cells, int32_t c
   }
   if (order && nb > 0) DVS_HIP(hipMemcpy(order, h->order.get(), (size_t)nb * 4, hipMemcpyDeviceToHost));
   return DVS_OK;
+}
+
+dvs_status dvs_test_maptrack_refine_steps(dvs_maptrack* h, const double* d_X, const double* d_px, const int32_t* d_octave, int32_t n, const double* R9,
+                                          const double* t3, int32_t first_round, int32_t n_rounds, int32_t n_iters, dvs_maptrack_result* result) {
+  DVS_ARG(first_round >= 0 && n_rounds >= 1 && first_round <= 4 && n_rounds <= 4 && first_round + n_rounds <= 4 && n_iters >= 1 && n_iters <= 10);
+  return mt_refine_explicit(h, d_X, d_px, d_octave, n, R9, t3, true, first_round, n_rounds, n_iters, result);
 }
 #endif
 

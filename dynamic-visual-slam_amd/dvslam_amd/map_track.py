@@ -49,6 +49,7 @@ def _bind(L):
     if hasattr(L, "dvs_test_maptrack_landmarks"):
         L.dvs_test_maptrack_landmarks.argtypes = [vp, i32, vp, C.POINTER(i32)]
         L.dvs_test_maptrack_cells.argtypes = [vp, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+        L.dvs_test_maptrack_refine_steps.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, pr]
     return L
 
 
@@ -82,7 +83,7 @@ def _pose(R, t):
 class MapTracker:
     """mt = MapTracker(default_params(480, 640, f, f, cx, cy)); r = mt.track(xyz, ldesc, ids, kps, kdesc, R, t) -> result dict with the
     refined camera-to-world pose when r["status"] == OK.  hooks=True makes every call through lib/libdvslam_hip_test.so, which also has
-    landmark_records() and cells()."""
+    landmark_records(), cells() and refine_steps()."""
 
     def __init__(self, params, device=0, hooks=False):
         self._L = _bind(test_lib() if hooks else lib())
@@ -113,6 +114,14 @@ class MapTracker:
         R, t = _pose(R, t)
         r = MapTrackResult()
         check(self._L.dvs_maptrack_refine_device(self._h, _raw(d_X), _raw(d_px), _raw(d_octave), n, ptr(R), ptr(t), C.byref(r)))
+        return r.as_dict()
+
+    def refine_steps(self, d_X, d_px, d_octave, n, R, t, first_round=0, n_rounds=4, n_iters=10):
+        """(hooks) refine_device with a part of its schedule: rounds first_round .. first_round + n_rounds - 1 of n_iters steps each"""
+        R, t = _pose(R, t)
+        r = MapTrackResult()
+        check(self._L.dvs_test_maptrack_refine_steps(self._h, _raw(d_X), _raw(d_px), _raw(d_octave), n, ptr(R), ptr(t), first_round, n_rounds, n_iters,
+                                                     C.byref(r)))
         return r.as_dict()
 
     def track_device(self, d_xyz, d_ldesc, d_ids, n_lm, d_kps, d_kdesc, n_kp, R, t):

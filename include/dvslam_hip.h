@@ -1394,7 +1394,9 @@ dvs_status dvs_backend_global_ba(dvs_backend* h, dvs_ba* ba, const dvs_ba_global
  *            minimum on the device, so there is no tie deviation.  A landmark that loses stays unmatched: there is no second round.
  *  Stage 4   pose refinement on the kept pairs in keypoint order: X_i the landmark position widened, p_i = (x, y) of the keypoint widened,
  *            s2_i = level_sigma2[octave].  With c = R_cw X_i + t_cw (as in stage 1): e_i = p_i - (fx c0 / c2 + cx, fy c1 / c2 + cy),
- *            chi_i = (e_i . e_i) / s2_i; a pair with c2 <= 0 has chi_i = +infinity and adds nothing to any sum.  Parameters
+ *            chi_i = (e_i . e_i) / s2_i; a pair with c2 <= 0 has chi_i = +infinity and adds nothing to any sum.  A pair whose X_i is not
+ *            finite has no finite c2 and is treated the same way: a permanent outlier.  A pair whose p_i is not finite ends the
+ *            refinement as soon as it enters a sum: DEGENERATE, the prior's bytes, all flags 0.  Parameters
  *            delta = (omega, upsilon): R_cw <- Exp(omega) R_cw, t_cw <- Exp(omega) t_cw + upsilon, Exp by Rodrigues' formula
  *            (|omega| < 1e-12: I + [omega]x); the camera point's Jacobian is [-[c]x | I].  Four rounds of ten Gauss-Newton steps
  *            H delta = b, H = sum w_i J_i^T J_i / s2_i, b = sum w_i J_i^T e_i / s2_i, no step control.  Rounds 0 and 1: w_i =

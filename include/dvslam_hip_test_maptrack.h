@@ -25,6 +25,13 @@ dvs_status dvs_test_maptrack_landmarks(dvs_maptrack* h, int32_t cap, dvs_maptrac
  * in CSR order (order[*n_binned]); count-then-capacity on both, either output nullable */
 dvs_status dvs_test_maptrack_cells(dvs_maptrack* h, int32_t cap_cells, int32_t cap_kp, int32_t* cell_start, int32_t* order, int32_t* n_cells,
                                    int32_t* n_binned);
+/* (needs a GPU) dvs_maptrack_refine_device's launch with a part of its schedule, so that single Gauss-Newton steps can be compared: rounds
+ * first_round .. first_round + n_rounds - 1 of n_iters steps each (the product runs 0, 4, 10).  Round r is robust iff r < 2, r counted
+ * from first_round; every pair counts as an inlier before the first round that runs; all pairs are reclassified after every round that
+ * runs, and cost, flags, FEW_MATCHES, FEW_INLIERS and DEGENERATE are as in the product after the last of them.  DVS_ERR_ARG outside
+ * 0 <= first_round, 1 <= n_rounds, first_round + n_rounds <= 4, 1 <= n_iters <= 10. */
+dvs_status dvs_test_maptrack_refine_steps(dvs_maptrack* h, const double* d_X, const double* d_px, const int32_t* d_octave, int32_t n, const double* R9,
+                                          const double* t3, int32_t first_round, int32_t n_rounds, int32_t n_iters, dvs_maptrack_result* result);
 
 #ifdef __cplusplus
 }
