@@ -1588,6 +1588,7 @@ struct dvs_ba {
   bool lm_poll = true, lm_speculate = true;   // DVS_LM_POLL=0 / DVS_LM_SPECULATE=0 (read once in dvs_ba_create): A/B switches of dvs_ba_solve_device
   bool lm_ready = false;   // dvs_ba_solve_device: structure tables built and uploaded
   int lm_nc = 0;           // ... free cameras
+  bool lm_stepping = false;   // the step hook of the test library has run the prologue: its next call is the loop's next iteration
   int device_window = 16;  // dvs_ba_set_device_window: most free cameras dvs_ba_solve_device takes; above 16 the tiled solver factors the system
   // dvs_ba_solve_global: its own arena and view (the two device solvers may alternate on one problem), the pinned PCG record
   DeviceBuf<uint8_t> gba_arena;
@@ -1610,7 +1611,7 @@ namespace {
 // forget the current problem (the arenas and pinned blocks stay)
 void ba_reset(dvs_ba* h) {
   h->prob = {}; h->work = {}; h->raw_buf = {}; h->gwork = {};
-  h->lm_ready = false; h->gba_ready = false;
+  h->lm_ready = false; h->gba_ready = false; h->lm_stepping = false;
 }
 
 // copies a host table into the staging block S at the place its buffer `dev` has in the arena at B
@@ -1768,6 +1769,120 @@ void enqueue_tiled_factor(hipStream_t st, int K, int n, const int* slotCam, doub
 dvs_status tiled_kernels_prepare() {
   DVS_HIP(hipFuncSetAttribute((const void*)k_lm_tile_panel, hipFuncAttributeMaxDynamicSharedMemorySize, kTilePanelLds));
   DVS_HIP(hipFuncSetAttribute((const void*)k_lm_tile_backsolve, hipFuncAttributeMaxDynamicSharedMemorySize, kTileBackLds));
+  return DVS_OK;
+}
+
+// ---- the launches of dvs_ba_solve_device, in the pieces its loop is made of (the step hook of the test library enqueues the same) ----
+// active blocks, camera slots, observation table: fixed for the life of a problem, built and uploaded by its first solve
+dvs_status lm_plan(dvs_ba* h) {
+  if (h->lm_ready) return DVS_OK;
+  const int K = h->K, L = h->L, R = h->R;
+  hipStream_t st = h->stream;
+  LmView& w = h->work;
+  const FreeBlocks fb = free_blocks(h);
+  const int nc = (int)fb.slotCam.size();
+  if (K > 64 || nc > h->device_window || nc == 0) {
+    set_error("dvs_ba_solve_device handles sliding windows (<= 64 cameras, 1..%d of them free); this problem has %d / %d", h->device_window, K, nc);
+    return DVS_ERR_UNSUPPORTED;
+  }
+  std::vector<int> obsOf((size_t)L * K, -1);
+  for (int l = 0; l < L; l++)
+    for (int e = h->lmStart[l]; e < h->lmStart[l + 1]; e++) {
+      const int p = h->lmObs[e];
+      int& slot = obsOf[(size_t)l * K + h->cam[p]];
+      if (slot >= 0) { set_error("landmark %d is observed twice in camera %d: use dvs_ba_solve", l, h->cam[p]); return DVS_ERR_UNSUPPORTED; }
+      slot = p;
+    }
+  w.carve(nullptr, K, L, R, nc);
+  DVS_TRY(grow(h->work_arena, h->work_cap, w.bytes));
+  DVS_HIP(hipStreamSynchronize(st));     // the staging block is free (dvs_ba_set_problem's upload has completed)
+  DVS_TRY(grow(h->stage, h->stage_cap, w.uploadBytes));
+  if (!h->status()) {
+    DVS_TRY(h->status_buf.alloc(2 * sizeof(LmStatus)));
+    DVS_HIP(hipFuncSetAttribute((const void*)k_lm_chol, hipFuncAttributeMaxDynamicSharedMemorySize, 97 * 96 * 8));
+    DVS_TRY(tiled_kernels_prepare());
+  }
+  DVS_TRY(grow(h->out_buf, h->out_cap, ((size_t)7 * std::max(K, 1) + 3 * (size_t)std::max(L, 1)) * 8));
+  uint8_t* B = h->work_arena.get();
+  w.carve(B, K, L, R, nc);
+  stage_table(h->stage.get(), B, w.obsOf, obsOf); stage_table(h->stage.get(), B, w.slotCam, fb.slotCam); stage_table(h->stage.get(), B, w.active, fb.active);
+  DVS_HIP(hipMemcpyAsync(B, h->stage.get(), w.uploadBytes, hipMemcpyHostToDevice, st));
+  h->lm_nc = nc;
+  h->lm_ready = true;
+  return DVS_OK;
+}
+
+// the last kernel enqueued wrote the record into the pinned host copy (lm_publish): poll its sequence number — a bounded spin,
+// then the stream wait — instead of sleeping in hipStreamSynchronize (a wake-up per trial step and per accepted step)
+dvs_status lm_fetch_status(dvs_ba* h, const LmStatus* rec, int& expect_seq) {
+  expect_seq++;
+  if (h->lm_poll) {
+    const volatile int* seq = &rec->seq;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int spin = 1; *seq != expect_seq; spin++) {
+      __builtin_ia32_pause();
+      if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    if (*seq == expect_seq) return DVS_OK;
+  }
+  DVS_HIP(hipStreamSynchronize(h->stream));
+  return DVS_OK;
+}
+
+// Jacobian blocks, gradient, cost of the point in the evaluation buffers, then its record (gradient max-norm, cost) into the second
+// host record; `gate`: only if the device's verdict says so.  accept: the evaluation buffers hold a candidate that becomes the point
+// of the next iteration (stored by extra workgroups of the evaluation kernel)
+dvs_status lm_enqueue_full(dvs_ba* h, const int* gate, bool accept) {
+  DVS_TRY(enqueue_eval(h, 1 | 2, true, gate, accept));
+  const LmView& w = h->work;
+  hipLaunchKernelGGL(k_lm_gmax, dim3(1), dim3(256), 0, h->stream, h->K, h->L, w.q0, h->prob.g, w.active, h->prob.cost, w.status, h->status() + 1, gate);
+  return DVS_OK;
+}
+
+// what precedes the first trial step: the problem's parameters become the point, its blocks, cost and gradient norm (fetched into the
+// second host record), the Jacobi scaling from them
+dvs_status lm_prologue(dvs_ba* h, int& expect_seq) {
+  const int K = h->K, L = h->L, NT = 6 * K + 3 * L;
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  const LmView& w = h->work;
+  DVS_TRY(upload_params(h, h->q, h->t, h->X));
+  const dim3 copyGrid((std::max(4 * K, 3 * L) + 255) / 256);   // one launch instead of three copy commands
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
+  expect_seq = 0;
+  h->status()[0].seq = 0; h->status()[1].seq = 0;
+  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
+  DVS_TRY(lm_enqueue_full(h, nullptr, false));
+  DVS_TRY(lm_fetch_status(h, h->status() + 1, expect_seq));
+  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
+  return DVS_OK;
+}
+
+// one trial step at `radius`: system -> Cholesky -> back-substitution -> candidate -> its cost -> the record and the verdict into
+// the first host record.  refresh: rebuild the LM diagonal from the point's blocks (0: keep it, after a rejected step)
+dvs_status lm_enqueue_trial(dvs_ba* h, double radius, bool refresh, double ptol, double ftol) {
+  const int K = h->K, L = h->L, R = h->R, nc = h->lm_nc, n = 6 * nc, nparts = (K + L + 255) / 256;
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  const LmView& w = h->work;
+  hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
+                     dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, refresh ? 1 : 0, w.Vinv, w.Ws, w.Y, w.status);
+  hipLaunchKernelGGL(k_lm_schur, dim3(nc, nc, kSchurSplit), dim3(256), 0, st, K, L, n, w.slotCam, w.obsOf, w.active, dev.Hpp, dev.g, w.scale,
+                     w.diag, radius, w.Ws, w.Y, w.S, w.rhs);
+  if (nc <= 16) {
+    hipLaunchKernelGGL(k_lm_chol, dim3(1), dim3(kCholThreads), (size_t)(n + 1) * n * 8, st, K, n, w.slotCam, w.S, w.rhs, w.step, w.status);
+  } else {
+    hipLaunchKernelGGL(k_lm_tile_assemble, dim3(n + 1), dim3(256), 0, st, K, n, w.S, w.rhs, w.A, w.step);
+    enqueue_tiled_factor(st, K, n, w.slotCam, w.A, w.step, w.status);
+  }
+  hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, dev.Hll, dev.g, dev.lmStart, dev.lmObs, dev.cam,
+                     w.scale, w.active, w.Vinv, w.Ws, w.step, w.lmPart, w.status);
+  hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, w.step, w.scale, w.active,
+                     dev.q, dev.t, dev.X, w.normPart);
+  DVS_TRY(enqueue_eval(h, 0, false));  // cost of the candidate
+  hipLaunchKernelGGL(k_lm_norms, dim3(1), dim3(256), 0, st, nparts, w.normPart, dev.cost, K, L, dev.Hpp, dev.g, w.scale, w.step,
+                     w.lmPart, ptol, ftol, w.status, h->status());
   return DVS_OK;
 }
 
@@ -2147,120 +2262,38 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
   summary->termination = 2;
   summary->linear_solver = 1;   // linear algebra on the DEVICE
   DVS_HIP(hipSetDevice(h->device));
-  const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
+  const int K = h->K, L = h->L, R = h->R;
   if (R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
   hipStream_t st = h->stream;
   const ProbView& dev = h->prob;
   LmView& w = h->work;
-  // active blocks, camera slots, observation table: fixed for the life of a problem, built and uploaded by its first solve
-  if (!h->lm_ready) {
-    const FreeBlocks fb = free_blocks(h);
-    const int nc = (int)fb.slotCam.size();
-    if (K > 64 || nc > h->device_window || nc == 0) {
-      set_error("dvs_ba_solve_device handles sliding windows (<= 64 cameras, 1..%d of them free); this problem has %d / %d", h->device_window, K, nc);
-      return DVS_ERR_UNSUPPORTED;
-    }
-    std::vector<int> obsOf((size_t)L * K, -1);
-    for (int l = 0; l < L; l++)
-      for (int e = h->lmStart[l]; e < h->lmStart[l + 1]; e++) {
-        const int p = h->lmObs[e];
-        int& slot = obsOf[(size_t)l * K + h->cam[p]];
-        if (slot >= 0) { set_error("landmark %d is observed twice in camera %d: use dvs_ba_solve", l, h->cam[p]); return DVS_ERR_UNSUPPORTED; }
-        slot = p;
-      }
-    w.carve(nullptr, K, L, R, nc);
-    DVS_TRY(grow(h->work_arena, h->work_cap, w.bytes));
-    DVS_HIP(hipStreamSynchronize(st));     // the staging block is free (dvs_ba_set_problem's upload has completed)
-    DVS_TRY(grow(h->stage, h->stage_cap, w.uploadBytes));
-    if (!h->status()) {
-      DVS_TRY(h->status_buf.alloc(2 * sizeof(LmStatus)));
-      DVS_HIP(hipFuncSetAttribute((const void*)k_lm_chol, hipFuncAttributeMaxDynamicSharedMemorySize, 97 * 96 * 8));
-      DVS_TRY(tiled_kernels_prepare());
-    }
-    DVS_TRY(grow(h->out_buf, h->out_cap, ((size_t)7 * std::max(K, 1) + 3 * (size_t)std::max(L, 1)) * 8));
-    uint8_t* B = h->work_arena.get();
-    w.carve(B, K, L, R, nc);
-    stage_table(h->stage.get(), B, w.obsOf, obsOf); stage_table(h->stage.get(), B, w.slotCam, fb.slotCam); stage_table(h->stage.get(), B, w.active, fb.active);
-    DVS_HIP(hipMemcpyAsync(B, h->stage.get(), w.uploadBytes, hipMemcpyHostToDevice, st));
-    h->lm_nc = nc;
-    h->lm_ready = true;
-  }
-  const int nc = h->lm_nc, n = 6 * nc;
+  DVS_TRY(lm_plan(h));
+  h->lm_stepping = false;   // the step hook of the test library starts over from the problem's point
   h->trace.clear();
-  DVS_TRY(upload_params(h, h->q, h->t, h->X));
-  const dim3 copyGrid((std::max(4 * K, 3 * L) + 255) / 256);   // one launch instead of three copy commands
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
   // two host records: the gated k_lm_gmax of an accepted step runs while the host may still be reading the trial's numbers, so it
   // must not publish over them
   LmStatus* S = h->status();
   LmStatus* SP = S + 1;
-  // the last kernel enqueued wrote the record into the pinned host copy (lm_publish): poll its sequence number — a bounded spin,
-  // then the stream wait — instead of sleeping in hipStreamSynchronize (a wake-up per trial step and per accepted step)
   int expect_seq = 0;
-  S->seq = 0; SP->seq = 0;
-  const bool poll = h->lm_poll;
-  auto fetch_status = [&](const LmStatus* rec) -> dvs_status {
-    expect_seq++;
-    if (poll) {
-      const volatile int* seq = &rec->seq;
-      const auto t0 = std::chrono::steady_clock::now();
-      for (int spin = 1; *seq != expect_seq; spin++) {
-        __builtin_ia32_pause();
-        if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-      if (*seq == expect_seq) return DVS_OK;
-    }
-    DVS_HIP(hipStreamSynchronize(st));
-    return DVS_OK;
-  };
-  // Jacobian blocks, gradient, cost of the point in the evaluation buffers; `gate`: only if the device's verdict says so
-  // accept: the evaluation buffers hold a candidate that becomes the point of the next iteration (stored by extra workgroups of
-  // the evaluation kernel)
-  auto enqueue_full = [&](const int* gate, bool accept) -> dvs_status {
-    DVS_TRY(enqueue_eval(h, 1 | 2, true, gate, accept));
-    hipLaunchKernelGGL(k_lm_gmax, dim3(1), dim3(256), 0, st, K, L, w.q0, dev.g, w.active, dev.cost, w.status, SP, gate);
-    return DVS_OK;
-  };
-  auto evaluate_full = [&](bool accept) -> dvs_status { DVS_TRY(enqueue_full(nullptr, accept)); return fetch_status(SP); };
   // The launches that follow an accepted step (accept, full evaluation, gradient norm: ~27 us of host launch time) are enqueued right
   // behind the trial, gated on the verdict k_lm_norms leaves in the status record, so that they are ready when the trial ends; the
   // host takes the same decision from the same numbers.  Should the two ever differ (a last-bit difference between the host's and the
   // device's sqrt / pow in a tolerance test), the DEVICE's verdict stands — it has already been applied to the buffers.
   const int* verdict = &w.status->accept;
   const bool speculate = h->lm_speculate;
-  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
-  DVS_TRY(evaluate_full(false));
+  DVS_TRY(lm_prologue(h, expect_seq));
   double x_cost = SP->x_cost, gmax = SP->gmax;
   summary->initial_cost = x_cost;
   double min_cost = x_cost;
-  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
+  const dim3 copyGrid((std::max(4 * K, 3 * L) + 255) / 256);
 
-  const int nparts = (K + L + 255) / 256;
   TrustRegion tr;
   while (tr.next(max_iterations, gmax, gtol, summary)) {
     const double radius = tr.radius;
-    hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
-                       dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, tr.reuse_diagonal ? 0 : 1, w.Vinv, w.Ws, w.Y,
-                       w.status);
-    hipLaunchKernelGGL(k_lm_schur, dim3(nc, nc, kSchurSplit), dim3(256), 0, st, K, L, n, w.slotCam, w.obsOf, w.active, dev.Hpp, dev.g, w.scale,
-                       w.diag, radius, w.Ws, w.Y, w.S, w.rhs);
-    if (nc <= 16) {
-      hipLaunchKernelGGL(k_lm_chol, dim3(1), dim3(kCholThreads), (size_t)(n + 1) * n * 8, st, K, n, w.slotCam, w.S, w.rhs, w.step, w.status);
-    } else {
-      hipLaunchKernelGGL(k_lm_tile_assemble, dim3(n + 1), dim3(256), 0, st, K, n, w.S, w.rhs, w.A, w.step);
-      enqueue_tiled_factor(st, K, n, w.slotCam, w.A, w.step, w.status);
-    }
-    hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, dev.Hll, dev.g, dev.lmStart, dev.lmObs, dev.cam,
-                       w.scale, w.active, w.Vinv, w.Ws, w.step, w.lmPart, w.status);
-    hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, w.step, w.scale, w.active,
-                       dev.q, dev.t, dev.X, w.normPart);
-    DVS_TRY(enqueue_eval(h, 0, false));  // cost of the candidate
-    hipLaunchKernelGGL(k_lm_norms, dim3(1), dim3(256), 0, st, nparts, w.normPart, dev.cost, K, L, dev.Hpp, dev.g, w.scale, w.step,
-                       w.lmPart, ptol, ftol, w.status, S);
-    if (speculate) DVS_TRY(enqueue_full(verdict, true));
+    DVS_TRY(lm_enqueue_trial(h, radius, !tr.reuse_diagonal, ptol, ftol));
+    if (speculate) DVS_TRY(lm_enqueue_full(h, verdict, true));
     DVS_HIP(hipGetLastError());
-    DVS_TRY(fetch_status(S));
+    DVS_TRY(lm_fetch_status(h, S, expect_seq));
     const bool valid = S->ok && S->finite && S->model_change > 0.0;
     const bool dev_accept = speculate && S->accept != 0;   // the gated launches ran: the candidate IS the point of the next iteration
     if (!valid && !dev_accept) {
@@ -2278,9 +2311,10 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
     h->log(radius, accept ? 1 : 2, cost_change, S->model_change, rel, S->cand_cost);
     if (accept) {
       if (speculate) {
-        DVS_TRY(fetch_status(SP));       // the gated launches ran: wait for k_lm_gmax's record
+        DVS_TRY(lm_fetch_status(h, SP, expect_seq));       // the gated launches ran: wait for k_lm_gmax's record
       } else {
-        DVS_TRY(evaluate_full(true));
+        DVS_TRY(lm_enqueue_full(h, nullptr, true));
+        DVS_TRY(lm_fetch_status(h, SP, expect_seq));
       }
       x_cost = SP->x_cost; gmax = SP->gmax;
       summary->num_successful_steps++;
@@ -2553,6 +2587,78 @@ dvs_status dvs_ba_pcg_probe(dvs_ba* h, double radius, double eta, int32_t max_pc
   *iterations = PH->iter; *ok = PH->ok;
   *rel_residual = PH->bnorm2 > 0.0 ? sqrt(PH->rnorm2) / sqrt(PH->bnorm2) : 0.0;
   DVS_HIP(hipMemcpy(x_out, w.step, (size_t)K * 6 * 8, hipMemcpyDeviceToHost));
+  return DVS_OK;
+}
+// one trial step of dvs_ba_solve_device at the caller's radius, through lm_prologue / lm_enqueue_trial / lm_enqueue_full as the loop
+// enqueues them, and what it left in the workspace
+dvs_status dvs_ba_step_probe(dvs_ba* h, double radius, int32_t refresh, int32_t commit, double ftol, double ptol, double* scale_out,
+                             double* diag_out, double* Vinv_out, double* S_out, double* rhs_out, double* step_out, double* cand_q,
+                             double* cand_t, double* cand_X, dvs_ba_step_record* rec) {
+  DVS_ARG(h && radius > 0.0);
+  DVS_HIP(hipSetDevice(h->device));
+  const int K = h->K, L = h->L, NT = 6 * K + 3 * L;
+  if (h->R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
+  if (!h->lm_ready) h->lm_stepping = false;
+  DVS_TRY(lm_plan(h));
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  const LmView& w = h->work;
+  if (!h->lm_stepping) {
+    int seq = 0;
+    DVS_TRY(lm_prologue(h, seq));
+    h->lm_stepping = true;
+  }
+  DVS_TRY(lm_enqueue_trial(h, radius, refresh != 0, ptol, ftol));
+  if (commit) DVS_TRY(lm_enqueue_full(h, &w.status->accept, true));
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipStreamSynchronize(st));
+  const int nc = h->lm_nc, n = 6 * nc;
+  const FreeBlocks fb = free_blocks(h);
+  std::vector<double> sc(NT);
+  DVS_HIP(hipMemcpy(sc.data(), w.scale, (size_t)NT * 8, hipMemcpyDeviceToHost));
+  if (scale_out) memcpy(scale_out, sc.data(), (size_t)NT * 8);
+  if (diag_out) DVS_HIP(hipMemcpy(diag_out, w.diag, (size_t)NT * 8, hipMemcpyDeviceToHost));
+  if (Vinv_out) {
+    DVS_HIP(hipMemcpy(Vinv_out, w.Vinv, (size_t)L * 72, hipMemcpyDeviceToHost));
+    for (int l = 0; l < L; l++) if (!fb.active[6 * K + 3 * l]) memset(Vinv_out + 9 * (size_t)l, 0, 72);   // never written
+  }
+  if (S_out) {   // k_lm_chol's / k_lm_tile_assemble's sum of k_lm_schur's pieces
+    std::vector<double> P((size_t)(1 + kSchurSplit) * n * n);
+    DVS_HIP(hipMemcpy(P.data(), w.S, P.size() * 8, hipMemcpyDeviceToHost));
+    for (int r = 0; r < n; r++)
+      for (int c = 0; c < n; c++) {
+        const size_t i = (size_t)r * n + c;
+        double v = 0.0;
+        if (c < 6 * (r / 6) + 6) {
+          double tot = P[(size_t)n * n + i];
+          for (int sp = 1; sp < kSchurSplit; sp++) tot += P[(size_t)(sp + 1) * n * n + i];
+          v = P[i] - tot;
+        }
+        S_out[i] = v;
+      }
+  }
+  if (rhs_out) {
+    std::vector<double> P((size_t)(1 + kSchurSplit) * n);
+    DVS_HIP(hipMemcpy(P.data(), w.rhs, P.size() * 8, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) {
+      double tot = P[n + i];
+      for (int sp = 1; sp < kSchurSplit; sp++) tot += P[(size_t)(sp + 1) * n + i];
+      rhs_out[i] = P[i] - tot;
+    }
+  }
+  if (step_out) {   // as k_lm_candidate applies it
+    DVS_HIP(hipMemcpy(step_out, w.step, (size_t)NT * 8, hipMemcpyDeviceToHost));
+    for (int j = 0; j < NT; j++) step_out[j] = j < 6 * K ? -step_out[j] * sc[j] : step_out[j] * sc[j];
+  }
+  if (cand_q) DVS_HIP(hipMemcpy(cand_q, dev.q, (size_t)K * 32, hipMemcpyDeviceToHost));
+  if (cand_t) DVS_HIP(hipMemcpy(cand_t, dev.t, (size_t)K * 24, hipMemcpyDeviceToHost));
+  if (cand_X) DVS_HIP(hipMemcpy(cand_X, dev.X, (size_t)L * 24, hipMemcpyDeviceToHost));
+  if (rec) {
+    const LmStatus* S = h->status();
+    rec->ok = S->ok; rec->finite = S->finite; rec->accept = S->accept; rec->reserved = 0;
+    rec->model_change = S->model_change; rec->sn = S->sn; rec->xn = S->xn; rec->cand_cost = S->cand_cost;
+    rec->gmax = S->gmax; rec->x_cost = S->x_cost;
+  }
   return DVS_OK;
 }
 #endif  // DVS_TEST_HOOKS

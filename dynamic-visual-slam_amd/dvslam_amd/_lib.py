@@ -44,6 +44,12 @@ class BaSummary(C.Structure):
                 ("linear_solver", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double)]
 
 
+class BaStepRecord(C.Structure):
+    """dvs_ba_step_record (include/dvslam_hip_test_ba.h)"""
+    _fields_ = [("ok", C.c_int32), ("finite", C.c_int32), ("accept", C.c_int32), ("reserved", C.c_int32), ("model_change", C.c_double),
+                ("sn", C.c_double), ("xn", C.c_double), ("cand_cost", C.c_double), ("gmax", C.c_double), ("x_cost", C.c_double)]
+
+
 class BaGlobalParams(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("max_pcg_iterations", C.c_int32), ("function_tolerance", C.c_double),
                 ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double), ("eta", C.c_double)]
@@ -358,6 +364,7 @@ def test_lib():
     if hasattr(L, "dvs_ba_schur_probe"):
         L.dvs_ba_schur_probe.argtypes = [vp, dbl, vp, vp, vp, vp]
         L.dvs_ba_pcg_probe.argtypes = [vp, dbl, dbl, i32, vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i32)]
+    L.dvs_ba_step_probe.argtypes = [vp, dbl, i32, i32, dbl, dbl] + [vp] * 9 + [C.POINTER(BaStepRecord)]
     _test_lib = L
     return L
 

@@ -9,7 +9,7 @@ class BAProblem:
     """Direct driver of the dvs_ba_* C-ABI: problem in the optimiser's parameterisation (bundle_adjustment.hpp:92-165)."""
 
     def __init__(self, prob, device=0, hooks=False):
-        """hooks: make every call through the test-hook library (schur_probe / pcg_probe need it)"""
+        """hooks: make every call through the test-hook library (schur_probe / pcg_probe / step_probe need it)"""
         self._L = test_lib() if hooks else lib()
         h = C.c_void_p()
         check(self._L.dvs_ba_create(device, C.byref(h)))
@@ -136,6 +136,26 @@ class BAProblem:
         check(self._L.dvs_ba_pcg_probe(self._h, float(radius), float(eta), int(max_pcg_iterations), ptr(x), C.byref(it), C.byref(rel),
                                        C.byref(ok)))
         return x, it.value, rel.value, ok.value
+
+    def step_probe(self, radius, refresh=True, commit=False, ftol=1e-6, ptol=1e-8):
+        """dvs_ba_step_probe (hooks=True): one trial step of solve_device at `radius` through the loop's own launches.  The first call
+        on a problem runs the loop's prologue; later calls keep point and scaling.  Returns a dict: scale, diag [6K + 3L], Vinv [L, 3, 3],
+        S [n, n] (block lower triangle), rhs [n], step [6K + 3L] (parameter units, as applied), q, t, X (the candidate) and the
+        status record's fields ok, finite, accept, model_change, sn, xn, cand_cost, gmax, x_cost."""
+        from ._lib import BaStepRecord
+        K, L = self.K, self.L
+        N = 6 * K + 3 * L
+        pf, lf, cam, lm = self._keep[6], self._keep[7], self._keep[3], self._keep[4]
+        n = 6 * int(((pf == 0) & np.isin(np.arange(K), cam)).sum())
+        o = dict(scale=np.zeros(N), diag=np.zeros(N), Vinv=np.zeros((L, 3, 3)), S=np.zeros((n, n)), rhs=np.zeros(n), step=np.zeros(N),
+                 q=np.zeros((K, 4)), t=np.zeros((K, 3)), X=np.zeros((L, 3)))
+        rec = BaStepRecord()
+        check(self._L.dvs_ba_step_probe(self._h, float(radius), int(bool(refresh)), int(bool(commit)), float(ftol), float(ptol),
+                                        *[ptr(o[k]) for k in ("scale", "diag", "Vinv", "S", "rhs", "step", "q", "t", "X")], C.byref(rec)))
+        for k, _ in BaStepRecord._fields_:
+            if k != "reserved":
+                o[k] = getattr(rec, k)
+        return o
 
     def trace(self):
         """dvs_ba_get_trace: [iterations, 6] = radius, kind (0 invalid, 1 accepted, 2 rejected, 3 ptol, 4 ftol), cost change,

@@ -1,6 +1,6 @@
 /*
- * dvslam_hip_test_ba.h — the test hooks of the global bundle-adjustment solver (csrc/ba.hip, dvs_ba_solve_global): exported by
- * libdvslam_hip_test.so (-DDVS_TEST_HOOKS) only, never by the product library.  A header of its own for the reason
+ * dvslam_hip_test_ba.h — the test hooks of the global bundle-adjustment solver (csrc/ba.hip, dvs_ba_solve_global) and the step
+ * hook of the sliding-window solver (dvs_ba_solve_device): exported by libdvslam_hip_test.so (-DDVS_TEST_HOOKS) only, never by the product library.  A header of its own for the reason
  * dvslam_hip_test_pgo.h gives.
  */
 #ifndef DVSLAM_HIP_TEST_BA_H
@@ -19,6 +19,32 @@ dvs_status dvs_ba_schur_probe(dvs_ba* h, double radius, const double* x_in, doub
  * stopped before its first iteration.  max_pcg_iterations 0: max(100, 12 x free cameras). */
 dvs_status dvs_ba_pcg_probe(dvs_ba* h, double radius, double eta, int32_t max_pcg_iterations, double* x_out, int32_t* iterations,
                             double* rel_residual, int32_t* ok);
+
+/* (needs a GPU) ONE trial step of dvs_ba_solve_device (the sliding-window solver; dvs_ba_set_device_window's rule decides between the
+ * in-LDS and the tiled factorisation) at `radius`, through the functions that solver's loop itself calls to enqueue its launches.
+ * The first call after dvs_ba_set_problem (or after a dvs_ba_solve_device / dvs_ba_set_device_window on the handle) first runs the
+ * loop's prologue at the problem's parameters: upload, the point, its blocks, cost and gradient norm, the Jacobi scaling.  Later
+ * calls keep the scaling and the point, as later iterations of the loop do.
+ *   refresh  the loop's "rebuild the LM diagonal" flag (0 after a rejected step: the diagonal of the call before is reused)
+ *   commit   non-zero: if the device's verdict accepts, the candidate becomes the point as in the loop (gated full evaluation and
+ *            gradient norm behind the trial); the next call is then the loop's next iteration
+ *   function_tolerance, parameter_tolerance   as dvs_ba_solve_device takes them (they enter the verdict)
+ * Outputs, each may be NULL.  N = 6 K + 3 L, n = 6 x (free cameras with an observation), slots in camera order:
+ *   scale, diag [N]   Jacobi scaling and LM diagonal (of the scaled system)
+ *   Vinv [L][9]       per active landmark (zero rows otherwise)
+ *   S [n][n], rhs [n] the reduced system as the factorisation assembles it: the H_pp part minus the four split sums in split order;
+ *                     the block lower triangle (6 x 6 blocks, diagonal blocks whole), zero above it
+ *   step [N]          the step as the candidate applies it: in parameter units (scaled back), camera rows negated
+ *   cand_q [K][4], cand_t [K][3], cand_X [L][3]   the candidate point
+ *   rec               the trial's status record; gmax and x_cost are those of the point the step was taken from
+ * The handle's parameters (dvs_ba_get_parameters) stay those of dvs_ba_set_problem. */
+typedef struct dvs_ba_step_record {
+  int32_t ok, finite, accept, reserved;
+  double model_change, sn, xn, cand_cost, gmax, x_cost;
+} dvs_ba_step_record;
+dvs_status dvs_ba_step_probe(dvs_ba* h, double radius, int32_t refresh, int32_t commit, double function_tolerance,
+                             double parameter_tolerance, double* scale, double* diag, double* Vinv, double* S, double* rhs, double* step,
+                             double* cand_q, double* cand_t, double* cand_X, dvs_ba_step_record* rec);
 
 #ifdef __cplusplus
 }

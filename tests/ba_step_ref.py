@@ -1,0 +1,427 @@
+"""Dense reference of ONE Levenberg-Marquardt trial step of the sliding-window bundle adjustment (dvs_ba_solve / dvs_ba_solve_device;
+the rules are include/dvslam_hip.h's: Jacobi scaling s_j = 1 / (1 + sqrt(H_jj)) fixed at the first Jacobian, LM diagonal
+D = clamp(diag(H_s), 1e-6, 1e32), the step solves (H_s + D / radius) delta = -g_s over the active blocks), and the windows the step
+tests use.  numpy only.
+
+Nothing here follows the kernels or dvs_ba_solve.  Inputs are the Gauss-Newton blocks H_pp [K,6,6], H_ll [L,3,3], W [R,6,3] (the
+caller's observation order) and g [6K + 3L] as normal_equations() returns them, the fixed flags, the point, a radius, and optionally a
+frozen scale and diagonal.  The full (6K + 3L) system is assembled densely in numpy.longdouble and solved DIRECTLY — no Schur
+complement: a float64 inverse gives the first solution, which is then refined against the longdouble residual until it stops
+moving.  The reduced system S, rhs and the per-landmark inverses exist only so that a failure can be localised.
+
+schur_f64() is a second solve of the same step, in plain float64, by eliminating the landmarks (batched numpy.linalg.inv, a dense
+S, numpy.linalg.solve).  It is what STEP_MEASURED is measured on: how far a straightforward float64 Schur solve is from solving the
+full system, in the distance Step.residual() states.  tests/test_ba_step_ref_cpu.py measures it over every case below and asserts
+that it does not exceed the constant; the GPU tests hold the device's step to 10 x the constant.
+
+An "active" block is one the solve moves: a camera that is not fixed and has an observation, a landmark that is not fixed and has
+an observation.  Rows and columns of every other block are left out of the system; their step is zero."""
+import functools
+import numpy as np
+
+LD = np.longdouble
+EPS = float(np.finfo(np.float64).eps)
+
+# The largest Step.residual(schur_f64()) over CASES, per radius (tests/test_ba_step_ref_cpu.py::test_measured_constants, which fails
+# if a re-measurement exceeds these).  Per radius, not one number: the damping D / radius sets the conditioning of the 3 x 3 landmark
+# blocks, and an explicit inverse (which a Schur solve forms, here as in the product and in Ceres) leaves a residual of about
+# cond(V) x 1e-16 in that landmark's rows.  The windows with a landmark of a single observation (V singular up to the damping) set
+# the values at 1e4 and 1e10; the largest over all radii, the one constant a coarser test would use, is the entry at 1e10.
+STEP_MEASURED = {
+    1e-2: 6.0e-16,      # measured 4.91e-16 ("16 free of 20")
+    1e4: 9.0e-13,       # measured 7.37e-13 ("edges 8x150"; 4.2e-14 without that window)
+    1e10: 3.6e-7,       # measured 2.87e-07 ("edges 8x150"; "16 free of 20" 9.7e-08, "live 5x200" 3.6e-15)
+}
+
+
+# ------------------------------------------------------------------------------------------------------------ the windows
+def _trim(P, keep):
+    for k in ("cam_idx", "lm_idx", "uv"):
+        P[k] = np.ascontiguousarray(P[k][keep])
+
+
+def _trim_landmark(P, l, cams):
+    """landmark l keeps only its observations in `cams`"""
+    _trim(P, (P["lm_idx"] != l) | np.isin(P["cam_idx"], cams))
+
+
+LDS_TRIMS = {3: [1], 10: [0, 1, 2, 3], 11: [0, 1, 2, 3, 4], 50: list(range(16)), 51: list(range(17))}   # landmark -> its cameras
+
+
+def _lds_window(fixed):
+    """K = 20, full visibility, L = 120: every landmark has 20 observations except five trimmed to exactly 1, 4, 5, 16 and 17"""
+    from dvslam_amd import synth
+    P = synth.make_ba_problem(K=20, L=120, seed=20)
+    P["pose_fixed"][:] = 0
+    P["pose_fixed"][fixed] = 1
+    for l, cams in LDS_TRIMS.items():
+        _trim_landmark(P, l, cams)
+    return P
+
+
+EDGES = dict(fixed_cams=(0, 5), unobserved_lm=5, single_lm=9, fixed_only_lm=13, empty_cam=3)
+
+
+def _edges_window():
+    from dvslam_amd import synth
+    P = synth.make_ba_problem(K=8, L=150, seed=8)
+    P["pose_fixed"][list(EDGES["fixed_cams"])] = 1
+    P["lm_fixed"][::7] = 1
+    _trim(P, P["lm_idx"] != EDGES["unobserved_lm"])
+    _trim_landmark(P, EDGES["single_lm"], [2])
+    _trim_landmark(P, EDGES["fixed_only_lm"], list(EDGES["fixed_cams"]))
+    _trim(P, P["cam_idx"] != EDGES["empty_cam"])
+    P["q"] = np.ascontiguousarray(P["q"] * np.linspace(0.5, 2.0, 8)[:, None])
+    assert not P["lm_fixed"][[EDGES["unobserved_lm"], EDGES["single_lm"], EDGES["fixed_only_lm"]]].any()
+    return P
+
+
+def _plain(**kw):
+    from dvslam_amd import synth
+    return synth.make_ba_problem(**kw)
+
+
+RADII3 = (1e4, 1e-2, 1e10)
+# name -> (builder, device window, radii)
+CASES = {
+    "live 5x200": (lambda: _plain(K=5, L=200, seed=7), 16, RADII3),
+    "one free camera 2x60": (lambda: _plain(K=2, L=60, seed=2), 16, (1e4,)),
+    "16 free of 20": (lambda: _lds_window([0, 7, 8, 19]), 16, RADII3),
+    "15 free of 20": (lambda: _lds_window([0, 7, 8, 12, 19]), 16, (1e4,)),
+    "tiled 17 free": (lambda: _plain(K=18, L=150, seed=18), 63, (1e4,)),
+    "tiled 63 free": (lambda: _plain(K=64, L=100, seed=64, visibility=0.6), 63, (1e4,)),
+    # the tiled route's own sum of the four Schur splits: split s holds landmarks 256 s .. 256 s + 255 (mod 1024), so only a window of
+    # more than 768 landmarks puts anything into the last one (the windows above leave splits 1 .. 3 of k_lm_tile_assemble empty)
+    "tiled 17 free, 800 landmarks": (lambda: _plain(K=18, L=800, seed=81, visibility=0.5), 63, (1e4,)),
+    "edges 8x150": (_edges_window, 16, RADII3),
+}
+# k_lm_schur's landmark stride (256 x 4), k_lm_backsub's 64 landmarks per workgroup, 256 blocks per partial sum (K + L = 255, 256, 257)
+STRIDE_L = (63, 64, 65, 252, 253, 254, 255, 256, 257, 1023, 1024, 1025)
+for _L in STRIDE_L:
+    CASES[f"3x{_L}"] = (functools.partial(_plain, K=3, L=_L, seed=300 + _L % 7), 16, (1e4,))
+REPLAY = ("live 5x200", "16 free of 20", "tiled 17 free")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    return CASES[name][0]()
+
+
+def case(name):
+    """a fresh copy of the window"""
+    return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in _case(name).items()}
+
+
+def active_blocks(P):
+    """-> (cameras [K] bool, landmarks [L] bool, slot table: the active cameras in order)"""
+    K, L = int(P["K"]), int(P["L"])
+    cu = np.zeros(K, bool); cu[np.asarray(P["cam_idx"], np.int64)] = True
+    lu = np.zeros(L, bool); lu[np.asarray(P["lm_idx"], np.int64)] = True
+    ca = cu & (np.asarray(P["pose_fixed"]) == 0); la = lu & (np.asarray(P["lm_fixed"]) == 0)
+    return ca, la, np.nonzero(ca)[0]
+
+
+def case_premises(name):
+    """what the case was chosen for, asserted from the window alone (the CPU test runs this for every case): a case cannot
+    silently stop reaching its branch"""
+    P = case(name)
+    K, L = int(P["K"]), int(P["L"])
+    ca, la, slots = active_blocks(P)
+    nobs = np.bincount(P["lm_idx"], minlength=L)
+    pairs = set(zip(P["cam_idx"].tolist(), P["lm_idx"].tolist()))
+    assert len(pairs) == len(P["cam_idx"]), "a landmark at most once per camera"
+    window = CASES[name][1]
+    assert 1 <= len(slots) <= window and K <= 64
+    if name == "live 5x200":
+        assert (K, L, len(slots)) == (5, 200, 4)
+    elif name.startswith("one free"):
+        assert K == 2 and len(slots) == 1
+    elif name in ("16 free of 20", "15 free of 20"):
+        nfree = 16 if name.startswith("16") else 15
+        assert K == 20 and L == 120 and len(slots) == nfree and (slots != np.arange(nfree)).any(), "a slot table that is not the identity"
+        assert sorted(nobs[list(LDS_TRIMS)].tolist()) == [1, 4, 5, 16, 17]
+        rest = np.ones(L, bool); rest[list(LDS_TRIMS)] = False
+        assert (nobs[rest] == 20).all(), "more than 16 observations: k_lm_backsub's plain loops"
+        assert la.all()
+    elif name == "tiled 17 free":
+        assert len(slots) == 17 and (nobs == 18).all()
+    elif name.startswith("tiled 17 free, 800"):
+        assert len(slots) == 17 and L > 768 and la[768:].sum() >= 16 and nobs.min() >= 1
+    elif name == "tiled 63 free":
+        assert len(slots) == 63 and nobs.min() >= 1 and nobs.max() > 16 and nobs.min() < nobs.max()
+    elif name == "edges 8x150":
+        E = EDGES
+        assert (K, L) == (8, 150) and P["pose_fixed"].sum() == 2 and P["lm_fixed"].sum() == 22
+        assert nobs[E["unobserved_lm"]] == 0 and not la[E["unobserved_lm"]]
+        assert nobs[E["single_lm"]] == 1 and la[E["single_lm"]]
+        assert set(P["cam_idx"][P["lm_idx"] == E["fixed_only_lm"]].tolist()) == set(E["fixed_cams"]) and la[E["fixed_only_lm"]]
+        assert not ca[E["empty_cam"]] and not P["pose_fixed"][E["empty_cam"]] and E["empty_cam"] not in P["cam_idx"]
+        assert len(slots) == 5 and (slots != np.arange(5)).any()
+        n2 = np.einsum("ki,ki->k", P["q"], P["q"])
+        assert abs(n2[0] - 0.25) < 1e-12 and abs(n2[-1] - 4.0) < 1e-12
+    else:
+        assert K == 3 and L in STRIDE_L and len(slots) == 2 and (nobs == 3).all()
+    return P
+
+
+# ------------------------------------------------------------------------------------------------------------ the step
+def quat_plus(x, d):
+    """ceres::EigenQuaternionManifold::Plus on the four stored numbers x read as Eigen's (x, y, z, w): exp(d) * x, not normalised.
+    x [.., 4], d [.., 3], any float type"""
+    x = np.asarray(x); d = np.asarray(d)
+    nd = np.sqrt((d * d).sum(-1, keepdims=True))
+    safe = np.where(nd == 0, 1, nd)
+    dv = np.where(nd == 0, 0 * d, np.sin(safe) / safe * d); dw = np.cos(nd)
+    xv, xw = x[..., :3], x[..., 3:]
+    ov = dw * xv + xw * dv + np.cross(dv, xv)
+    ow = dw * xw - (dv * xv).sum(-1, keepdims=True)
+    out = np.concatenate([ov, ow], -1)
+    return np.where(nd == 0, x, out)
+
+
+def quat_plus_magnitude(x, d):
+    """per output component, the sum of the absolute values of the four products quat_plus adds up"""
+    x = np.abs(np.asarray(x, LD)); d = np.asarray(d, LD)
+    nd = np.sqrt((d * d).sum(-1, keepdims=True))
+    safe = np.where(nd == 0, 1, nd)
+    dv = np.abs(np.sin(safe) / safe * d); dw = np.abs(np.cos(nd))
+    xv, xw = x[..., :3], x[..., 3:]
+    cr = np.stack([dv[..., 1] * xv[..., 2] + dv[..., 2] * xv[..., 1], dv[..., 2] * xv[..., 0] + dv[..., 0] * xv[..., 2],
+                   dv[..., 0] * xv[..., 1] + dv[..., 1] * xv[..., 0]], -1)
+    return np.concatenate([dw * xv + xw * dv + cr, dw * xw + (dv * xv).sum(-1, keepdims=True)], -1).astype(np.float64)
+
+
+def jacobi_scale(hpp, hll):
+    """s_j = 1 / (1 + sqrt(H_jj)) for every coordinate, longdouble"""
+    d = np.concatenate([np.einsum("caa->ca", hpp).reshape(-1), np.einsum("laa->la", hll).reshape(-1)]).astype(LD)
+    return 1 / (1 + np.sqrt(d))
+
+
+def lm_diagonal(hpp, hll, scale):
+    """D = clamp(diag(H_s), 1e-6, 1e32) for every coordinate, longdouble"""
+    d = np.concatenate([np.einsum("caa->ca", hpp).reshape(-1), np.einsum("laa->la", hll).reshape(-1)]).astype(LD)
+    s = np.asarray(scale, LD)
+    return np.clip(d * s * s, LD(1e-6), LD(1e32))
+
+
+def _inv3(V):
+    """batched inverse of 3 x 3 matrices in the type of V (Gauss-Jordan with partial pivoting; numpy.linalg has no longdouble)"""
+    V = np.array(V, copy=True)
+    n = len(V)
+    M = np.concatenate([V, np.broadcast_to(np.eye(3, dtype=V.dtype), (n, 3, 3))], axis=2)
+    rows = np.arange(n)
+    for j in range(3):
+        p = j + np.abs(M[:, j:, j]).argmax(1)
+        tmp = M[rows, j].copy(); M[rows, j] = M[rows, p]; M[rows, p] = tmp
+        M[:, j] = M[:, j] / M[:, j, j][:, None]
+        for i in range(3):
+            if i != j:
+                M[:, i] = M[:, i] - M[:, i, j][:, None] * M[:, j]
+    return M[:, :, 3:]
+
+
+def inv3_rounding(V):
+    """what float64 rounding may do to a 3 x 3 inverse formed as adjugate / determinant, V [n, 3, 3] longdouble ->
+    (tau [n], G [n, 3, 3]): G = (sum of the absolute values of the two products of each cofactor) / |det|, transposed like the
+    adjugate (G >= |V^-1| element-wise), tau = (the same for the determinant's expansion along the first row) / |det| >= 1."""
+    n = len(V)
+    C = np.zeros((n, 3, 3), LD); Cm = np.zeros((n, 3, 3), LD)
+    for i in range(3):
+        for j in range(3):
+            i1, i2, j1, j2 = (i + 1) % 3, (i + 2) % 3, (j + 1) % 3, (j + 2) % 3
+            C[:, i, j] = V[:, i1, j1] * V[:, i2, j2] - V[:, i1, j2] * V[:, i2, j1]
+            Cm[:, i, j] = np.abs(V[:, i1, j1] * V[:, i2, j2]) + np.abs(V[:, i1, j2] * V[:, i2, j1])
+    det = (V[:, 0, :] * C[:, 0, :]).sum(1)
+    detm = (np.abs(V[:, 0, :]) * Cm[:, 0, :]).sum(1)
+    return detm / np.abs(det), np.swapaxes(Cm, 1, 2) / np.abs(det)[:, None, None]
+
+
+class Step:
+    """one trial step at `radius` from the point (q, t, X) whose blocks are hpp, hll, w, g.  scale / diag: frozen values (the loop
+    keeps the scaling of its first Jacobian, and the diagonal across a rejected step); by default both are made from the blocks."""
+
+    def __init__(self, P, hpp, hll, w, g, q, t, X, radius, scale=None, diag=None):
+        K, L = int(P["K"]), int(P["L"])
+        self.P, self.K, self.L, self.N, self.radius = P, K, L, 6 * K + 3 * L, radius
+        self.cam = np.asarray(P["cam_idx"], np.int64); self.lm = np.asarray(P["lm_idx"], np.int64)
+        self.ca, self.la, self.slots = active_blocks(P)
+        self.act = np.concatenate([np.repeat(self.ca, 6), np.repeat(self.la, 3)])
+        self.idx = np.nonzero(self.act)[0]
+        self.hpp, self.hll, self.w = np.asarray(hpp), np.asarray(hll), np.asarray(w)
+        self.q, self.t, self.X = (np.array(a, np.float64) for a in (q, t, X))
+        self.scale = jacobi_scale(hpp, hll) if scale is None else np.asarray(scale, LD)
+        self.diag = lm_diagonal(hpp, hll, self.scale) if diag is None else np.asarray(diag, LD)
+        self.g = np.asarray(g, np.float64)
+        self.gs = np.where(self.act, np.asarray(g, LD) * self.scale, LD(0))
+        # the dense Gauss-Newton matrix: float64 holds the blocks exactly; observations of one (camera, landmark) pair add up
+        H = np.zeros((self.N, self.N))
+        for c in range(K):
+            H[6 * c:6 * c + 6, 6 * c:6 * c + 6] = hpp[c]
+        for l in range(L):
+            H[6 * K + 3 * l:6 * K + 3 * l + 3, 6 * K + 3 * l:6 * K + 3 * l + 3] = hll[l]
+        Wd = np.zeros((K, 6, L, 3), LD)
+        np.add.at(Wd, (self.cam, slice(None), self.lm), np.asarray(w, LD))
+        self.Wd = Wd
+        Wf = Wd.reshape(6 * K, 3 * L)
+        i = self.idx
+        Hs = H[np.ix_(i, i)].astype(LD)
+        ic, il = i[i < 6 * K], i[i >= 6 * K] - 6 * K
+        Hs[:len(ic), len(ic):] = Wf[np.ix_(ic, il)]
+        Hs[len(ic):, :len(ic)] = Wf[np.ix_(ic, il)].T
+        s = self.scale[i]
+        self.Hs = Hs * s[:, None] * s[None, :]                  # active x active
+        self.A = self.Hs.copy()
+        self.A[np.arange(len(i)), np.arange(len(i))] += self.diag[i] / LD(radius)
+        self.Ainv = np.linalg.inv(self.A.astype(np.float64))
+        x = np.zeros(len(i), LD)
+        for _ in range(6):                                       # refinement against the longdouble residual
+            r = -(self.gs[i] + self.A @ x)
+            dx = (self.Ainv @ r.astype(np.float64)).astype(LD)
+            x = x + dx
+            if np.abs(dx).max() <= 1e-19 * np.abs(x).max():
+                break
+        self.refine_last = float(np.abs(dx).max() / max(float(np.abs(x).max()), 1e-300))
+        self.delta_s = self._full(x)                             # scaled units
+        self.delta = self.delta_s * self.scale                   # parameter units, as the update applies it
+
+    def _full(self, x):
+        out = np.zeros(self.N, LD); out[self.idx] = x
+        return out
+
+    def scaled(self, delta):
+        """a step in parameter units -> scaled units, longdouble"""
+        return np.asarray(delta, LD) / self.scale
+
+    def magnitude(self, delta):
+        """(|H_s| + D / radius) |delta_s| + |g_s| per active row: what the residual's terms add up to before they cancel"""
+        d = np.abs(self.scaled(delta)[self.idx])
+        return np.abs(self.Hs) @ d + self.diag[self.idx] / LD(self.radius) * d + np.abs(self.gs[self.idx])
+
+    def residual_rows(self, delta):
+        d = self.scaled(delta)[self.idx]
+        return np.abs(self.A @ d + self.gs[self.idx]) / self.magnitude(delta)
+
+    def residual(self, delta):
+        """the distance STEP_MEASURED is stated in: max over the active rows of |(H_s + D / radius) delta_s + g_s| relative to
+        magnitude()"""
+        return float(self.residual_rows(delta).max())
+
+    def model_change(self, delta):
+        """-(delta.g_s + delta^T H_s delta / 2), without the damping (Ceres), and the sum of the absolute values of its terms"""
+        d = self.scaled(delta)[self.idx]
+        gs = self.gs[self.idx]
+        val = -(d @ gs + d @ (self.Hs @ d) / 2)
+        mag = np.abs(d) @ np.abs(gs) + np.abs(d) @ (np.abs(self.Hs) @ np.abs(d)) / 2
+        return val, mag
+
+    def model_change_slack(self, delta, rho):
+        """how far model_change(delta) may be from model_change(the exact step) when delta's residual is within rho x magnitude:
+        with e = delta - exact, A e = residual, so |e| <= |A^-1| rho magnitude row by row, and (g = -A exact)
+        model_change(delta) - model_change(exact) = e^T (D / radius) exact - e^T H_s e / 2"""
+        e = (np.abs(self.Ainv) @ (rho * self.magnitude(delta)).astype(np.float64)).astype(LD)
+        ex = np.abs(self.delta_s[self.idx]) * self.diag[self.idx] / LD(self.radius)
+        return float(e @ ex + e @ (np.abs(self.Hs) @ e) / 2)
+
+    def reduced(self):
+        """the reduced camera system in slot order, longdouble -> dict S, rhs, their un-cancelled magnitudes Smag, rhsmag, and per
+        landmark V = H_ll scaled + D / radius, Vinv (zero where inactive)"""
+        K, L = self.K, self.L
+        sp = self.scale[:6 * K].reshape(K, 6); sl = self.scale[6 * K:].reshape(L, 3)
+        V = np.asarray(self.hll, LD) * sl[:, :, None] * sl[:, None, :]
+        V[:, np.arange(3), np.arange(3)] += self.diag[6 * K:].reshape(L, 3) / LD(self.radius)
+        Vinv = np.zeros((L, 3, 3), LD); Vinv[self.la] = _inv3(V[self.la])
+        Ws = self.Wd * sp[:, :, None, None] * sl[None, None, :, :] * self.la[None, None, :, None]     # [K, 6, L, 3]
+        Ws = Ws[self.slots]
+        nc = len(self.slots)
+        Y = np.einsum("kalb,lbc->kalc", Ws, Vinv)
+        U = np.zeros((nc, 6, nc, 6), LD)
+        for k, c in enumerate(self.slots):
+            U[k, :, k, :] = np.asarray(self.hpp[c], LD) * sp[c][:, None] * sp[c][None, :] + np.diag(self.diag[6 * c:6 * c + 6] / LD(self.radius))
+        gl = self.gs[6 * K:].reshape(L, 3)
+        gp = self.gs[:6 * K].reshape(K, 6)[self.slots]
+        S = U - np.einsum("kalc,mblc->kamb", Y, Ws)
+        Smag = np.abs(U) + np.einsum("kalc,mblc->kamb", np.einsum("kalb,lbc->kalc", np.abs(Ws), np.abs(Vinv)), np.abs(Ws))
+        rhs = gp - np.einsum("kalc,lc->ka", Y, gl)
+        rhsmag = np.abs(gp) + np.einsum("kalc,lc->ka", np.einsum("kalb,lbc->kalc", np.abs(Ws), np.abs(Vinv)), np.abs(gl))
+        n = 6 * nc
+        return dict(S=S.reshape(n, n), Smag=Smag.reshape(n, n), rhs=rhs.reshape(n), rhsmag=rhsmag.reshape(n), V=V, Vinv=Vinv, Ws=Ws)
+
+    def landmark_part(self, delta, red=None, Vinv=None):
+        """the landmark rows that follow from delta's camera rows: delta_l = -Vinv_l (g_l + sum_c W_cl^T delta_c) -> (delta_l [L, 3],
+        the sum of the absolute values of its terms [L, 3]), both in PARAMETER units.  Vinv: the inverses to use (the reference's own
+        by default)"""
+        red = red or self.reduced()
+        K, L = self.K, self.L
+        Vinv = red["Vinv"] if Vinv is None else np.asarray(Vinv, LD) * self.la[:, None, None]
+        dc = self.scaled(delta)[:6 * K].reshape(K, 6)[self.slots]
+        b = self.gs[6 * K:].reshape(L, 3) + np.einsum("kalb,ka->lb", red["Ws"], dc)
+        bm = np.abs(self.gs[6 * K:].reshape(L, 3)) + np.einsum("kalb,ka->lb", np.abs(red["Ws"]), np.abs(dc))
+        sl = self.scale[6 * K:].reshape(L, 3)
+        return -np.einsum("lab,lb->la", Vinv, b) * sl, np.einsum("lab,lb->la", np.abs(Vinv), bm) * sl
+
+    def candidate(self, delta):
+        """the point the update reaches with `delta` (parameter units): quat_plus on the cameras, plain sums elsewhere; evaluated in
+        longdouble, returned in float64.  Inactive blocks keep their values."""
+        K = self.K
+        d = np.asarray(delta, LD)
+        dc = d[:6 * K].reshape(K, 6); dl = d[6 * K:].reshape(self.L, 3)
+        q = np.where(self.ca[:, None], quat_plus(self.q.astype(LD), dc[:, :3]), self.q.astype(LD))
+        t = np.where(self.ca[:, None], self.t.astype(LD) + dc[:, 3:], self.t.astype(LD))
+        X = np.where(self.la[:, None], self.X.astype(LD) + dl, self.X.astype(LD))
+        return q.astype(np.float64), t.astype(np.float64), X.astype(np.float64)
+
+    def norms(self, cq, ct, cX):
+        """|x - cand|^2 and |x|^2 over the active blocks, longdouble"""
+        sn = xn = LD(0)
+        for a, b, m in ((self.q, cq, self.ca), (self.t, ct, self.ca), (self.X, cX, self.la)):
+            a = a.astype(LD)[m]; b = np.asarray(b, LD)[m]
+            sn = sn + ((a - b) ** 2).sum(); xn = xn + (a * a).sum()
+        return sn, xn
+
+    def gmax(self):
+        """Ceres' gradient max-norm |x - Plus(x, -g)|_inf over the active blocks (g unscaled)"""
+        K = self.K
+        g = np.asarray(self.g, LD)
+        gc = g[:6 * K].reshape(K, 6)[self.ca]; gl = g[6 * K:].reshape(self.L, 3)[self.la]
+        qa = self.q.astype(LD)[self.ca]
+        m = [np.abs(qa - quat_plus(qa, -gc[:, :3])).max(initial=0), np.abs(gc[:, 3:]).max(initial=0), np.abs(gl).max(initial=0)]
+        return float(max(m))
+
+    def schur_f64(self):
+        """the same step by a plain float64 Schur solve (landmarks eliminated) -> delta [N], parameter units.  Any straightforward
+        float64 implementation: batched inverses, dense products, numpy.linalg.solve."""
+        K, L = self.K, self.L
+        s = self.scale.astype(np.float64); D = self.diag.astype(np.float64) / self.radius
+        sp = s[:6 * K].reshape(K, 6); sl = s[6 * K:].reshape(L, 3)
+        slots = self.slots; nc = len(slots); la = self.la
+        gs = self.g * s
+        V = self.hll * sl[:, :, None] * sl[:, None, :] + np.einsum("la,ab->lab", D[6 * K:].reshape(L, 3), np.eye(3))
+        Vinv = np.zeros((L, 3, 3)); Vinv[la] = np.linalg.inv(V[la])
+        Ws = (self.Wd.astype(np.float64) * sp[:, :, None, None] * sl[None, None, :, :])[slots][:, :, la, :]       # [nc, 6, La, 3]
+        Wm = Ws.reshape(6 * nc, -1)
+        La = int(la.sum())
+        Y = np.einsum("kalb,lbc->kalc", Ws, Vinv[la]).reshape(6 * nc, 3 * La)
+        U = np.zeros((6 * nc, 6 * nc))
+        for k, c in enumerate(slots):
+            U[6 * k:6 * k + 6, 6 * k:6 * k + 6] = self.hpp[c] * sp[c][:, None] * sp[c][None, :] + np.diag(D[6 * c:6 * c + 6])
+        gl = gs[6 * K:].reshape(L, 3)[la].reshape(-1)
+        gp = gs[:6 * K].reshape(K, 6)[slots].reshape(-1)
+        dc = np.linalg.solve(U - Y @ Wm.T, -(gp - Y @ gl))
+        dl = -np.einsum("lab,lb->la", Vinv[la], (gl + Wm.T @ dc).reshape(La, 3))
+        out = np.zeros(self.N)
+        out[:6 * K].reshape(K, 6)[slots] = dc.reshape(nc, 6)
+        out[6 * K:].reshape(L, 3)[la] = dl
+        return out * s
+
+
+def accept_rule(rec, ftol, ptol):
+    """dvs_ba_solve_device's verdict on a trial step from its status record's own numbers (a dict with ok, finite, model_change, sn,
+    xn, cand_cost, x_cost): valid, not within the parameter or the function tolerance, relative decrease above 1e-3"""
+    if not (rec["ok"] and rec["finite"] and rec["model_change"] > 0.0):
+        return 0
+    if np.sqrt(rec["sn"]) <= ptol * (np.sqrt(rec["xn"]) + ptol):
+        return 0
+    cc = rec["x_cost"] - rec["cand_cost"]
+    if abs(cc) <= ftol * rec["x_cost"]:
+        return 0
+    return 1 if cc / rec["model_change"] > 1e-3 else 0
