@@ -319,7 +319,7 @@ using namespace dvs;
 
 namespace {
 
-const int kSmall = 256;   // s_small: [0, 64) filtered ids, [64, 128) class list, [128, 192) class counts, [192, 196) counts, [196] marked landmarks, [200, 208) loop_close.hip
+const int kSmall = 256;   // s_small: [0, 64) filtered ids, [64, 128) class list, [128, 192) class counts, [192, 196) counts, [196] marked landmarks, [200, 208) loop_close.hip, [208] covisibility.hip
 
 dvs_status backend_grow_tables(dvs_backend* h, size_t need_lm, size_t need_ob, size_t need_kf) {
   hipStream_t st = h->ctx->stream;

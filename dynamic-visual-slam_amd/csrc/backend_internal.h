@@ -96,10 +96,28 @@ struct dvs_backend {
   dvs::DeviceBuf<unsigned long long> f_prope, f_beste;
   dvs::DeviceBuf<double> f_pe;
   size_t c_flm = 0, c_frow = 0, c_fob = 0, c_fq = 0;   // anchors; fusion per landmark row / per observation / per query observation
+  // covisibility (covisibility.hip), all grow-only: per view / per keyframe / per landmark row / per observation / per requested row x keyframe
+  dvs::DeviceBuf<int> cv_kf, cv_tmp, cv_list;                                    // per view: the keyframe where the view counts, keyframe -> landmarks CSR
+  dvs::DeviceBuf<int> cv_cnt, cv_fill, cv_role, cv_f, cv_blk;                    // per keyframe (cv_blk: per 256-row block of a table)
+  dvs::DeviceBuf<dvs::i64> cv_offs, cv_nboffs, cv_blkoffs;
+  dvs::DeviceBuf<int> cv_lflag, cv_lpos, cv_uslot, cv_ucls;                      // per landmark row: in U, row in U; U's columns
+  dvs::DeviceBuf<dvs::i64> cv_uid;
+  dvs::DeviceBuf<float> cv_uxyz;
+  dvs::DeviceBuf<uint8_t> cv_udesc;
+  dvs::DeviceBuf<int> cv_oflag, cv_ocls, cv_olmidx;                              // per observation: in the window; the window's columns
+  dvs::DeviceBuf<dvs::i64> cv_olm, cv_oframe;
+  dvs::DeviceBuf<float> cv_opx;
+  dvs::DeviceBuf<int> cv_w, cv_nbt, cv_nbi, cv_nbw, cv_nbc, cv_pki, cv_pkw;      // weights and neighbour lists, rows x keyframes; packed CSR
+  size_t c_cvv = 0, c_cvk = 0, c_cvl = 0, c_cvo = 0, c_cvw = 0, c_cvb = 0;
 };
 
 namespace dvs {
 // landmark -> views CSR over the whole table into view_offs / view_kf / view_px / view_oid, segments in observation order, on the
 // handle's stream (backend.hip); nothing to do for an empty landmark table
 dvs_status backend_views_build(dvs_backend* h);
+// the local map of keyframe ref_frame_id ("Covisibility" in the header; covisibility.hip): U's positions, descriptors and ids compacted in
+// ascending id into the handle's scratch, device pointers valid until the handle's next call; the stream has been synchronised.  The
+// argument errors of the section are returned before any device work.
+dvs_status backend_local_map(dvs_backend* h, uint64_t ref_frame_id, const dvs_covis_params* params, const float** d_xyz, const uint8_t** d_desc,
+                             const i64** d_id, int* n);
 }  // namespace dvs

@@ -719,6 +719,19 @@ dvs_status dvs_backend_track_frame(dvs_backend* h, dvs_maptrack* mt, const dvs_k
   return dvs_maptrack_track_device(mt, h->lm.xyz.get(), h->lm.desc.get(), (const int64_t*)h->lm.id.get(), h->nlm, d_kps, d_desc, n_kp, R9, t3, result);
 }
 
+// the same against the local map of one keyframe ("Covisibility" in the header): covisibility.hip compacts U's columns on the device
+dvs_status dvs_backend_track_frame_local(dvs_backend* h, dvs_maptrack* mt, uint64_t ref_frame_id, const dvs_covis_params* params, const dvs_keypoint* d_kps,
+                                         const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result) {
+  DVS_ARG(h && mt && result && h->device == mt->device);
+  DVS_TRY(mt_check_search_args(mt, h->lm.xyz.get(), h->lm.desc.get(), h->nlm, d_kps, d_desc, n_kp));
+  MtPose T;
+  DVS_TRY(maptrack_pose(R9, t3, &T));
+  const float* xyz = nullptr; const uint8_t* desc = nullptr; const dvs::i64* id = nullptr;
+  int n = 0;
+  DVS_TRY(dvs::backend_local_map(h, ref_frame_id, params, &xyz, &desc, &id, &n));   // returns with the backend's stream synchronised
+  return dvs_maptrack_track_device(mt, xyz, desc, (const int64_t*)id, n, d_kps, d_desc, n_kp, R9, t3, result);
+}
+
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test_maptrack.h)
 dvs_status dvs_test_maptrack_landmarks(dvs_maptrack* h, int32_t cap, dvs_maptrack_lm_record* rec, int32_t* n) {
   DVS_ARG(h && n && cap >= 0);

@@ -2,7 +2,7 @@
 and pruneLandmarks (backend.cpp) as one handle that keeps the landmark and observation tables on the device; one call per keyframe."""
 import ctypes as C
 import numpy as np
-from ._lib import lib, check, ptr, DvsError, KeyframeHeader, PgoParams, PgoSummary, BaGlobalParams, BaGlobalSummary
+from ._lib import lib, check, ptr, DvsError, KeyframeHeader, PgoParams, PgoSummary, BaGlobalParams, BaGlobalSummary, BaSummary
 
 MAX_FILTERED = 16
 
@@ -50,6 +50,17 @@ class GlobalBaResult(C.Structure):
     _fields_ = [("summary", BaGlobalSummary), ("n_cameras", C.c_int32), ("n_landmarks", C.c_int32), ("n_observations", C.c_int32), ("n_left_out", C.c_int32)]
 
 
+class CovisParams(C.Structure):
+    """dvs_covis_params (fill it with dvs_covis_default_params)"""
+    _fields_ = [("min_weight", C.c_int32), ("max_neighbours", C.c_int32), ("max_fixed", C.c_int32), ("ba_max_iterations", C.c_int32)]
+
+
+class LocalBaResult(C.Structure):
+    """dvs_backend_lba_result"""
+    _fields_ = [("summary", BaSummary), ("n_cameras", C.c_int32), ("n_fixed", C.c_int32), ("n_landmarks", C.c_int32), ("n_observations", C.c_int32),
+                ("n_left_out", C.c_int32), ("n_dropped", C.c_int32)]
+
+
 def _bind(L):
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
     pi32, pi64 = C.POINTER(i32), C.POINTER(i64)
@@ -73,6 +84,11 @@ def _bind(L):
     L.dvs_backend_close_loop.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, dbl, dbl, C.POINTER(PgoParams), C.POINTER(FuseParams), C.POINTER(CloseLoopResult)]
     L.dvs_backend_fuse.argtypes = [vp, u64, vp, i32, C.POINTER(FuseParams), i32, C.POINTER(FuseResult), i32, vp, vp, vp, pi32]
     L.dvs_backend_global_ba.argtypes = [vp, vp, C.POINTER(BaGlobalParams), C.POINTER(GlobalBaResult)]
+    pcv = C.POINTER(CovisParams)
+    L.dvs_covis_default_params.argtypes = [pcv]; L.dvs_covis_default_params.restype = None
+    L.dvs_backend_covisibility.argtypes = [vp, i32, i32, i64, vp, vp, vp, vp, pi32, pi64]
+    L.dvs_backend_get_local_window.argtypes = [vp, u64, pcv, i32, i32, i32, vp, vp, vp, vp, vp, pi32, vp, vp, vp, vp, vp, pi32, vp, vp, vp, pi32, pi32]
+    L.dvs_backend_local_ba.argtypes = [vp, vp, u64, pcv, C.POINTER(LocalBaResult)]
     return L
 
 
@@ -82,6 +98,17 @@ def fuse_params(**kw):
     check(_bind(lib()).dvs_fuse_default_params(C.byref(p)))
     for k, v in kw.items():
         if k not in dict(FuseParams._fields_) or k == "reserved":
+            raise TypeError(f"unknown parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def covis_params(**kw):
+    """dvs_covis_default_params with field overrides"""
+    p = CovisParams()
+    _bind(lib()).dvs_covis_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(CovisParams._fields_):
             raise TypeError(f"unknown parameter {k}")
         setattr(p, k, v)
     return p
@@ -326,6 +353,64 @@ class MappingBackend:
         check(self._L.dvs_backend_track_frame(self._h, map_tracker.handle, M._raw(d_kps), M._raw(d_desc), int(n_kp), ptr(R), ptr(t), C.byref(r)))
         return r.as_dict()
 
+    # ---- covisibility (include/dvslam_hip.h "Covisibility")
+    def covisibility(self, min_weight=15, weights=True):
+        """dvs_backend_covisibility: the whole graph -> dict(weights (n, n) int32 or None, nb_offsets (n + 1) int64, nb_index, nb_weight): the
+        neighbour lists of every keyframe at min_weight as CSR, each ordered by (weight descending, index ascending)"""
+        nk, nn = C.c_int32(), C.c_int64()
+        check(self._L.dvs_backend_covisibility(self._h, int(min_weight), 0, 0, None, None, None, None, C.byref(nk), C.byref(nn)))
+        n, m = nk.value, nn.value
+        W = np.zeros((n, n), np.int32) if weights else None
+        offs = np.zeros(n + 1, np.int64); idx = np.zeros(max(m, 1), np.int32); wt = np.zeros(max(m, 1), np.int32)
+        check(self._L.dvs_backend_covisibility(self._h, int(min_weight), n, m, ptr(W) if weights else None, ptr(offs), ptr(idx), ptr(wt), C.byref(nk), C.byref(nn)))
+        return dict(weights=W, nb_offsets=offs, nb_index=idx[:m], nb_weight=wt[:m])
+
+    def local_window(self, ref_frame_id, **params):
+        """dvs_backend_get_local_window of keyframe ref_frame_id (params: the fields of dvs_covis_params): window()'s dict plus kf_fixed,
+        kf_weight and n_left_out"""
+        p = covis_params(**params)
+        nk, no, nl, left = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        none = [None] * 5
+        check(self._L.dvs_backend_get_local_window(self._h, int(ref_frame_id), C.byref(p), 0, 0, 0, *none, C.byref(nk), *none, C.byref(no), None, None, None,
+                                                   C.byref(nl), C.byref(left)))
+        ck, co, cl = max(nk.value, 1), max(no.value, 1), max(nl.value, 1)
+        kid = np.zeros(ck, np.uint64); R = np.zeros((ck, 3, 3)); t = np.zeros((ck, 3)); fixed = np.zeros(ck, np.uint8); kw = np.zeros(ck, np.int32)
+        px = np.zeros((co, 2), np.float32); olm = np.zeros(co, np.uint64); ocl = np.zeros(co, np.int32); ofr = np.zeros(co, np.uint64); oix = np.zeros(co, np.int32)
+        lid = np.zeros(cl, np.uint64); lcl = np.zeros(cl, np.int32); xyz = np.zeros((cl, 3), np.float32)
+        check(self._L.dvs_backend_get_local_window(self._h, int(ref_frame_id), C.byref(p), ck, co, cl, ptr(kid), ptr(R), ptr(t), ptr(fixed), ptr(kw), C.byref(nk),
+                                                   ptr(px), ptr(olm), ptr(ocl), ptr(ofr), ptr(oix), C.byref(no), ptr(lid), ptr(lcl), ptr(xyz), C.byref(nl), C.byref(left)))
+        nk, no, nl = nk.value, no.value, nl.value
+        return dict(kf_frame_id=kid[:nk], kf_R=R[:nk], kf_t=t[:nk], kf_fixed=fixed[:nk], kf_weight=kw[:nk], obs_px=px[:no], obs_landmark_id=olm[:no],
+                    obs_class=ocl[:no], obs_frame_id=ofr[:no], obs_lm_index=oix[:no], lm_id=lid[:nl], lm_class=lcl[:nl], lm_xyz=xyz[:nl], n_left_out=left.value)
+
+    def local_bundle_adjust(self, ref_frame_id, ba=None, **params):
+        """dvs_backend_local_ba: the local window of keyframe ref_frame_id refined by BAProblem.solve_device on `ba` (a dvslam_amd.BAProblem of
+        the same device; None: a handle this object creates once and keeps).  The map changes only if the solve converged
+        (summary.termination == 0).  -> dict(summary=dvs_ba_summary, n_cameras, n_fixed, n_landmarks, n_observations, n_left_out, n_dropped)"""
+        from .ba import BAProblem
+        if ba is None:
+            if self._gba is None:
+                self._gba = BAProblem.empty(self.device)
+            ba = self._gba
+        p = covis_params(**params)
+        r = LocalBaResult()
+        check(self._L.dvs_backend_local_ba(self._h, ba._h, int(ref_frame_id), C.byref(p), C.byref(r)))
+        out = {k: int(getattr(r, k)) for k, _ in LocalBaResult._fields_ if k != "summary"}
+        out["summary"] = r.summary
+        return out
+
+    def track_frame_local(self, map_tracker, ref_frame_id, d_kps, d_desc, n_kp, R, t, **params):
+        """dvs_backend_track_frame_local: track_frame against the local map of keyframe ref_frame_id only; map_tracker.matches() then reports
+        rows of that local map, and the ids identify them"""
+        from . import map_track as M
+        M._bind(self._L)
+        p = covis_params(**params)
+        R = np.ascontiguousarray(R, np.float64).reshape(9); t = np.ascontiguousarray(t, np.float64).reshape(3)
+        r = M.MapTrackResult()
+        check(self._L.dvs_backend_track_frame_local(self._h, map_tracker.handle, int(ref_frame_id), C.byref(p), M._raw(d_kps), M._raw(d_desc), int(n_kp), ptr(R), ptr(t),
+                                                    C.byref(r)))
+        return r.as_dict()
+
     def reset(self):
         check(self._L.dvs_backend_reset(self._h))
 
@@ -341,4 +426,4 @@ class MappingBackend:
             pass
 
 
-__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "default_params", "fuse_params", "DvsError"]
+__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "CovisParams", "LocalBaResult", "covis_params", "default_params", "fuse_params", "DvsError"]

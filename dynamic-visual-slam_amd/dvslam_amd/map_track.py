@@ -44,6 +44,7 @@ def _bind(L):
     L.dvs_maptrack_track.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, pr]
     L.dvs_maptrack_get_matches.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(i32)]
     L.dvs_backend_track_frame.argtypes = [vp, vp, vp, vp, i32, vp, vp, pr]
+    L.dvs_backend_track_frame_local.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, i32, vp, vp, pr]
     L.dvs_tracker_track_map.argtypes = [vp, vp, vp, i32, pr]
     L.dvs_tracker_get_filtered_features.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
     if hasattr(L, "dvs_test_maptrack_landmarks"):

@@ -1478,6 +1478,81 @@ dvs_status dvs_tracker_track_map(dvs_tracker* h, dvs_backend* backend, dvs_maptr
 /* that set, for tests and adapters (kps / desc nullable, `cap` rows; *n = rows available) */
 dvs_status dvs_tracker_get_filtered_features(dvs_tracker* h, dvs_keypoint* kps, uint8_t* desc, int32_t cap, int32_t* n);
 
+/* ======================================= Covisibility ================================= */
+/* The covisibility graph of the map the backend keeps on the device (csrc/covisibility.hip; INTEGRATION.md "Covisibility"): keyframes as
+ * nodes, the number of landmarks two keyframes both observe as the edge weight — what ORB-SLAM organises its local map and its local BA
+ * around (Mur-Artal, Montiel, Tardos 2015, sections III-D and VI-D), as published ideas.  PARITY UNPINNED: the reference has no counterpart;
+ * the rule is the library's own, defined over the tables as the getters return them, stated here in full and restated with Python sets in
+ * tests/covisibility_ref.py.
+ *  Observes   Keyframe k (index in table order) observes landmark L iff the landmark table holds L and at least one observation row has
+ *             kf == k (its frame_id is keyframe k's) and landmark_id == L.  S_k is the set of those landmarks.  Two rows of one keyframe
+ *             naming one landmark count once (this happens after fusion, and the reference's association allows it); a row naming a
+ *             landmark the table does not hold counts nowhere.
+ *  Weights    W[a][b] = |S_a n S_b| for a != b, W[a][a] = |S_a|; int32, symmetric by construction.
+ *  Neighbours N(a; theta) = the keyframes b != a with W[a][b] >= theta, ordered by weight descending, then index ascending; theta >= 1.
+ *  Local set  of a reference keyframe r with (theta, max_neighbours): the FREE keyframes are r and the first max_neighbours of
+ *             N(r; theta); the LOCAL LANDMARKS U are the union of S_k over the free keyframes, in ascending id.
+ *  Fixed      (BA only) the keyframes c that are not free and have f_c = |S_c n U| >= 1, ordered by (f_c descending, index ascending),
+ *             the first max_fixed of them.  If that leaves no fixed keyframe, the free keyframe of lowest index is marked fixed: the
+ *             gauge, as SlidingWindowBA fixes its first.
+ *  Window     keyframes (free and fixed) in ascending table index, each with a `fixed` byte and its weight to r (W[r][k]; for r itself
+ *             W[r][r]); landmarks U; observations = the rows of the observation table, in table order, whose keyframe is in the window,
+ *             whose landmark is in U and that are the FIRST row in table order of their (keyframe, landmark) pair — dvs_ba_solve_device
+ *             takes a landmark at most once per camera.  The later rows of such pairs are counted in n_left_out.  obs_lm_index is the
+ *             landmark's row in U and is never -1.
+ * Every quantity is an integer and every order is total: there is no tie deviation, two identical calls on identical maps give identical
+ * bytes, and no call but dvs_backend_local_ba modifies the map.
+ * Limit: the row kernel keeps one 4-byte counter per keyframe in LDS, 32 KiB at most (four workgroups per compute unit); a map of more
+ * than DVS_COVIS_MAX_KEYFRAMES keyframes is refused with DVS_ERR_CAPACITY by every call of this section.
+ * DVS_ERR_ARG before any device work: min_weight < 1, max_neighbours outside 0..62, max_fixed outside 0..63, max_neighbours + 1 +
+ * max_fixed > 64 (the device solver's camera limit), ba_max_iterations < 1, an unknown ref_frame_id.
+ * Out of scope: covisibility edges in the pose graph, keyframe culling, a cached graph, scale and viewing-angle conditions, several GPUs. */
+#define DVS_COVIS_MAX_KEYFRAMES 8192
+typedef struct dvs_covis_params {
+  int32_t min_weight;          /* 15: theta */
+  int32_t max_neighbours;      /* 10: with r, 11 free cameras — inside the in-LDS solver's default window of 16 */
+  int32_t max_fixed;           /* 32 */
+  int32_t ba_max_iterations;   /* 20 (SlidingWindowBA's); read by dvs_backend_local_ba only */
+} dvs_covis_params;
+void dvs_covis_default_params(dvs_covis_params* p);
+/* The whole graph, count-then-capacity: *n_kf and *n_nb (the total length of all neighbour lists at min_weight) are always set.
+ * weights: n_kf x n_kf row-major, nullable.  Neighbour lists as CSR, each array nullable: nb_offsets n_kf + 1, nb_index / nb_weight
+ * *n_nb entries.  DVS_ERR_CAPACITY if an array is given and cap_kf < *n_kf (weights, nb_offsets) or cap_nb < *n_nb (nb_index, nb_weight). */
+dvs_status dvs_backend_covisibility(dvs_backend* h, int32_t min_weight, int32_t cap_kf, int64_t cap_nb, int32_t* weights, int64_t* nb_offsets,
+                                    int32_t* nb_index, int32_t* nb_weight, int32_t* n_kf, int64_t* n_nb);
+/* The local window of keyframe ref_frame_id: dvs_backend_get_window's outputs (each nullable, count-then-capacity: the three counts are
+ * always set) plus kf_fixed, kf_weight and *n_left_out (nullable).  params NULL: the defaults. */
+dvs_status dvs_backend_get_local_window(dvs_backend* h, uint64_t ref_frame_id, const dvs_covis_params* params, int32_t cap_kf, int32_t cap_obs,
+                                        int32_t cap_lm, uint64_t* kf_frame_id, double* kf_R, double* kf_t, uint8_t* kf_fixed, int32_t* kf_weight,
+                                        int32_t* n_kf, float* obs_px, uint64_t* obs_lm_id, int32_t* obs_class, uint64_t* obs_frame_id,
+                                        int32_t* obs_lm_index, int32_t* n_obs, uint64_t* lm_id, int32_t* lm_class, float* lm_xyz, int32_t* n_lm,
+                                        int32_t* n_left_out);
+/* Local BA: the local window refined on the caller's dvs_ba handle (same device), as dvs_backend_global_ba refines the whole map.
+ *   Cameras       the window's keyframes in its order through dvs_ba_pose_from_rt, pose_fixed = the window's fixed bytes.
+ *   Landmarks     the rows of U that keep at least two of the window's observations, in ascending id, float -> double, none fixed.
+ *   Observations  the window's, in its order, pixels float -> double, without those of a landmark with fewer than two of them
+ *                 (counted in n_dropped), as global BA drops them.
+ *   Settings      the backend's fx .. cy, sigma 1.0, Huber 1.345; dvs_ba_solve_device with ba_max_iterations and SlidingWindowBA's
+ *                 tolerances 1e-6 / 1e-10 / 1e-8.  dvs_ba_set_device_window is never called: a caller who raises max_neighbours above
+ *                 15 raises the window on their own handle; DVS_ERR_UNSUPPORTED from the solver is passed on.
+ *   Result        applied through dvs_backend_apply_optimized — the keyframes that are not fixed and the problem's landmarks, positions
+ *                 rounded to float once — if and only if summary.termination == 0.  Otherwise the map stays byte for byte as it was and
+ *                 the call still returns DVS_OK with the summary.  No camera that is not fixed, or no observation left: DVS_ERR_ARG
+ *                 before the map is touched. */
+typedef struct dvs_backend_lba_result {
+  dvs_ba_summary summary;
+  int32_t n_cameras, n_fixed, n_landmarks, n_observations, n_left_out, n_dropped;
+} dvs_backend_lba_result;
+dvs_status dvs_backend_local_ba(dvs_backend* h, dvs_ba* ba, uint64_t ref_frame_id, const dvs_covis_params* params /* NULL: defaults */,
+                                dvs_backend_lba_result* out);
+/* dvs_backend_track_frame against the local map of keyframe ref_frame_id: U's position, descriptor and id columns are compacted on the
+ * device in ascending id into the backend's scratch and handed to dvs_maptrack_track_device as dvs_backend_track_frame hands over the whole
+ * table; nothing of the map crosses to the host.  dvs_maptrack_get_matches then reports rows of U, and the ids identify them.  max_fixed
+ * and ba_max_iterations are checked and not used. */
+dvs_status dvs_backend_track_frame_local(dvs_backend* h, dvs_maptrack* mt, uint64_t ref_frame_id, const dvs_covis_params* params /* NULL: defaults */,
+                                         const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3,
+                                         dvs_maptrack_result* result);
+
 #ifdef __cplusplus
 }
 #endif
