@@ -14,6 +14,7 @@
 // TrustRegion below RESTATES the policy of csrc/ba.hip (struct TrustRegion there): that one writes into a dvs_ba_summary and lives in
 // ba.hip's anonymous namespace; lifting it would have touched the BA translation unit, whose results must not change by a byte.
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -638,6 +639,27 @@ void enqueue_linearize(dvs_pgo* h) {
   h->lin_valid = true;
 }
 
+// the launches of ONE trial step at `radius`, from the current linearisation: the LM diagonal (kept when the step before was rejected),
+// the preconditioner, the linear solve, the candidate and its record.  dvs_pgo_solve's loop and dvs_test_pgo_trial_step both enqueue a
+// trial through this function; given_x (the hook only) leaves the linear solve out and takes the step that is already in P.x.
+void enqueue_trial(dvs_pgo* h, double radius, double eta, int max_pcg, bool reuse_diagonal, bool given_x = false) {
+  const PgoDev P = dev_view(h);
+  const int N = h->N, E = h->E;
+  hipStream_t st = h->stream;
+  if (!reuse_diagonal) hipLaunchKernelGGL(k_pgo_lm_diag, grid_for(6 * N), dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_pgo_precond, grid_for(N), dim3(256), 0, st, P, radius);
+  if (!given_x) hipLaunchKernelGGL(k_pgo_pcg, dim3(1), dim3(kPcgThreads), 0, st, P, radius, eta, max_pcg);
+  hipLaunchKernelGGL(k_pgo_candidate, grid_for(N), dim3(256), 0, st, P, h->q_cur, h->t_cur, h->R_cur, h->q_cand, h->t_cand, h->R_cand);
+  hipLaunchKernelGGL(k_pgo_trial_edges, grid_for(E), dim3(256), 0, st, P, h->R_cand, h->t_cand);
+  hipLaunchKernelGGL(k_pgo_trial_reduce, dim3(1), dim3(kPcgThreads), 0, st, P);
+}
+
+// an accepted step: the candidate becomes the point (the two sets of buffers change roles) and is linearised
+void commit_candidate(dvs_pgo* h) {
+  std::swap(h->q_cur, h->q_cand); std::swap(h->t_cur, h->t_cand); std::swap(h->R_cur, h->R_cand);
+  enqueue_linearize(h);
+}
+
 dvs_status read_status(dvs_pgo* h, PgoStatus* out) {
   DVS_HIP(hipGetLastError());
   DVS_HIP(hipMemcpyAsync(h->hstatus.get(), h->dstatus.get(), sizeof(PgoStatus), hipMemcpyDeviceToHost, h->stream));
@@ -768,8 +790,7 @@ dvs_status dvs_pgo_solve(dvs_pgo* h, const dvs_pgo_params* params, dvs_pgo_summa
   memset(summary, 0, sizeof(*summary));
   summary->termination = 2;
   DVS_TRY(prepare(h, true));
-  const int N = h->N, E = h->E;
-  const int max_pcg = prm.max_pcg_iterations > 0 ? prm.max_pcg_iterations : std::max(100, 2 * N);
+  const int max_pcg = prm.max_pcg_iterations > 0 ? prm.max_pcg_iterations : std::max(100, 2 * h->N);
   hipStream_t st = h->stream;
   h->trace.clear();
   enqueue_linearize(h);
@@ -781,14 +802,8 @@ dvs_status dvs_pgo_solve(dvs_pgo* h, const dvs_pgo_params* params, dvs_pgo_summa
   for (;;) {
     if (tr.iteration >= prm.max_iterations) { summary->termination = 1; break; }
     if (tr.radius < 1e-32) { summary->termination = 0; break; }
-    const PgoDev P = dev_view(h);
     const double radius = tr.radius;
-    if (!tr.reuse_diagonal) hipLaunchKernelGGL(k_pgo_lm_diag, grid_for(6 * N), dim3(256), 0, st, P);
-    hipLaunchKernelGGL(k_pgo_precond, grid_for(N), dim3(256), 0, st, P, radius);
-    hipLaunchKernelGGL(k_pgo_pcg, dim3(1), dim3(kPcgThreads), 0, st, P, radius, prm.eta, max_pcg);
-    hipLaunchKernelGGL(k_pgo_candidate, grid_for(N), dim3(256), 0, st, P, h->q_cur, h->t_cur, h->R_cur, h->q_cand, h->t_cand, h->R_cand);
-    hipLaunchKernelGGL(k_pgo_trial_edges, grid_for(E), dim3(256), 0, st, P, h->R_cand, h->t_cand);
-    hipLaunchKernelGGL(k_pgo_trial_reduce, dim3(1), dim3(kPcgThreads), 0, st, P);
+    enqueue_trial(h, radius, prm.eta, max_pcg, tr.reuse_diagonal);
     DVS_TRY(read_status(h, &s));
     // the gradient test of the loop head, on the record this read brought along: the trial enqueued above is dropped, uncounted
     if (s.gmax <= prm.gradient_tolerance) { summary->termination = 0; break; }
@@ -811,8 +826,7 @@ dvs_status dvs_pgo_solve(dvs_pgo* h, const dvs_pgo_params* params, dvs_pgo_summa
     const bool accept = rel > TrustRegion::kMinRelativeDecrease;
     h->log(radius, accept ? 1 : 2, cost_change, model_cost_change, rel, cand_cost, s.pcg_iterations);
     if (accept) {
-      std::swap(h->q_cur, h->q_cand); std::swap(h->t_cur, h->t_cand); std::swap(h->R_cur, h->R_cand);
-      enqueue_linearize(h);   // its cost and max |g| arrive with the next trial's record
+      commit_candidate(h);    // its cost and max |g| arrive with the next trial's record
       x_cost = cand_cost;
       summary->num_successful_steps++;
       tr.accepted(rel);
@@ -897,6 +911,39 @@ DVS_HOOK dvs_status dvs_test_pgo_pcg(dvs_pgo* h, double radius, double eta, int3
   if (iterations) *iterations = s.pcg_iterations;
   if (rnorm) *rnorm = s.rnorm;
   if (gnorm) *gnorm = s.gnorm;
+  return DVS_OK;
+}
+
+// ONE trial step through enqueue_trial / read_status / commit_candidate, the three functions dvs_pgo_solve's loop is made of
+DVS_HOOK dvs_status dvs_test_pgo_trial_step(dvs_pgo* h, double radius, double eta, int32_t max_pcg_iterations, int32_t reuse_diagonal, int32_t commit,
+                                            const double* x_in, double* cur_q, double* cur_t, double* x, double* D, double* cand_q, double* cand_t,
+                                            dvs_pgo_step_record* rec) {
+  static_assert(sizeof(dvs_pgo_step_record) == sizeof(PgoStatus), "the hook's record is the status record");
+  DVS_ARG(h && radius > 0 && eta > 0 && eta < 1 && max_pcg_iterations >= 0);
+  DVS_TRY(prepare(h, true));
+  if (!h->lin_valid) enqueue_linearize(h);
+  const PgoDev P = dev_view(h);
+  const size_t N = h->N;
+  const int max_pcg = max_pcg_iterations > 0 ? max_pcg_iterations : std::max(100, 2 * h->N);
+  if (x_in) {   // the linear solve's part of the record is not written by this trial: zero, not what an earlier call left
+    DVS_HIP(hipMemcpyAsync(P.x, x_in, 6 * N * 8, hipMemcpyHostToDevice, h->stream));
+    DVS_HIP(hipMemsetAsync(&P.status->rnorm, 0, sizeof(PgoStatus) - offsetof(PgoStatus, rnorm), h->stream));
+  }
+  enqueue_trial(h, radius, eta, max_pcg, reuse_diagonal != 0, x_in != nullptr);
+  PgoStatus s;
+  DVS_TRY(read_status(h, &s));
+  if (cur_q) DVS_HIP(hipMemcpy(cur_q, h->q_cur, 4 * N * 8, hipMemcpyDeviceToHost));
+  if (cur_t) DVS_HIP(hipMemcpy(cur_t, h->t_cur, 3 * N * 8, hipMemcpyDeviceToHost));
+  if (x) DVS_HIP(hipMemcpy(x, P.x, 6 * N * 8, hipMemcpyDeviceToHost));
+  if (D) DVS_HIP(hipMemcpy(D, P.D, 6 * N * 8, hipMemcpyDeviceToHost));
+  if (cand_q) DVS_HIP(hipMemcpy(cand_q, h->q_cand, 4 * N * 8, hipMemcpyDeviceToHost));
+  if (cand_t) DVS_HIP(hipMemcpy(cand_t, h->t_cand, 3 * N * 8, hipMemcpyDeviceToHost));
+  if (rec) memcpy(rec, &s, sizeof(s));
+  if (commit) {
+    commit_candidate(h);
+    DVS_HIP(hipStreamSynchronize(h->stream));
+    DVS_HIP(hipGetLastError());
+  }
   return DVS_OK;
 }
 #endif  // DVS_TEST_HOOKS

@@ -90,6 +90,12 @@ class PgoParams(C.Structure):
                 ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double), ("eta", C.c_double)]
 
 
+class PgoStepRecord(C.Structure):
+    """dvs_pgo_step_record (include/dvslam_hip_test_pgo.h)"""
+    _fields_ = [(k, C.c_double) for k in ("cur_cost", "gmax", "cand_cost", "model_cost_change", "step2", "x2", "rnorm", "gnorm")] + \
+               [(k, C.c_int32) for k in ("pcg_iterations", "finite", "breakdown", "reserved")]
+
+
 class PgoSummary(C.Structure):
     _fields_ = [("termination", C.c_int32), ("num_successful_steps", C.c_int32), ("num_iterations", C.c_int32), ("pcg_iterations", C.c_int32),
                 ("initial_cost", C.c_double), ("final_cost", C.c_double)]
@@ -361,6 +367,8 @@ def test_lib():
     if hasattr(L, "dvs_test_pgo_apply"):
         L.dvs_test_pgo_apply.argtypes = [vp, dbl, vp, vp]
         L.dvs_test_pgo_pcg.argtypes = [vp, dbl, dbl, i32, vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(dbl)]
+    if hasattr(L, "dvs_test_pgo_trial_step"):
+        L.dvs_test_pgo_trial_step.argtypes = [vp, dbl, dbl, i32, i32, i32] + [vp] * 7 + [C.POINTER(PgoStepRecord)]
     if hasattr(L, "dvs_ba_schur_probe"):
         L.dvs_ba_schur_probe.argtypes = [vp, dbl, vp, vp, vp, vp]
         L.dvs_ba_pcg_probe.argtypes = [vp, dbl, dbl, i32, vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i32)]

@@ -1,12 +1,12 @@
 import ctypes as C
 import numpy as np
-from ._lib import lib, test_lib, check, ptr, PgoParams, PgoSummary
+from ._lib import lib, test_lib, check, ptr, PgoParams, PgoSummary, PgoStepRecord
 
 
 class PoseGraph:
     """Driver of the dvs_pgo_* C-ABI (include/dvslam_hip.h "Pose-graph optimisation"): nodes (R, t, fixed), edges (i, j, rvec, tvec, w_rot,
     w_trans) with x_i = R_z x_j + t_z, a Levenberg-Marquardt solve on the device, and the map correction.  hooks=True makes every call
-    through lib/libdvslam_hip_test.so, which also has the operator and linear-solve hooks (apply, pcg)."""
+    through lib/libdvslam_hip_test.so, which also has the operator, linear-solve and trial-step hooks (apply, pcg, trial_step)."""
 
     def __init__(self, device=0, hooks=False):
         self._L = test_lib() if hooks else lib()
@@ -104,3 +104,18 @@ class PoseGraph:
         x = np.zeros(6 * self.N); it = C.c_int32(); rn = C.c_double(); gn = C.c_double()
         check(self._L.dvs_test_pgo_pcg(self._h, float(radius), float(eta), int(max_it), ptr(x), C.byref(it), C.byref(rn), C.byref(gn)))
         return x, it.value, rn.value, gn.value
+
+    def trial_step(self, radius, eta=0.1, max_pcg_iterations=0, reuse_diagonal=False, commit=False, x_in=None):
+        """ONE trial step of the solve (dvs_test_pgo_trial_step): a dict of the point it was taken from (q, t), the step x, the LM diagonal D,
+        the candidate (cand_q, cand_t) and the fields of the status record.  x_in: a step to take in place of the linear solve's."""
+        N = self.N
+        if x_in is not None:
+            x_in = np.ascontiguousarray(x_in, np.float64)
+            assert x_in.size == 6 * N
+        o = dict(q=np.zeros((N, 4)), t=np.zeros((N, 3)), x=np.zeros(6 * N), D=np.zeros(6 * N), cand_q=np.zeros((N, 4)), cand_t=np.zeros((N, 3)))
+        rec = PgoStepRecord()
+        check(self._L.dvs_test_pgo_trial_step(self._h, float(radius), float(eta), int(max_pcg_iterations), int(bool(reuse_diagonal)), int(bool(commit)),
+                                              ptr(x_in) if x_in is not None else None, ptr(o["q"]), ptr(o["t"]), ptr(o["x"]), ptr(o["D"]),
+                                              ptr(o["cand_q"]), ptr(o["cand_t"]), C.byref(rec)))
+        o.update({k: getattr(rec, k) for k, _ in PgoStepRecord._fields_ if k != "reserved"})
+        return o

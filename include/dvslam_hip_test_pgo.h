@@ -19,6 +19,25 @@ dvs_status dvs_test_pgo_apply(dvs_pgo* h, double radius, const double* p, double
 /* one linear solve (preconditioner build, then the PCG kernel): x [6 N], the iterations run, and the recurrence's |r| and |g| at the end */
 dvs_status dvs_test_pgo_pcg(dvs_pgo* h, double radius, double eta, int32_t max_it, double* x, int32_t* iterations, double* rnorm, double* gnorm);
 
+/* (needs a GPU) ONE Levenberg-Marquardt trial step of dvs_pgo_solve at `radius`, through the functions that solver's loop itself calls:
+ * the enqueue of a trial (LM diagonal, preconditioner, linear solve, candidate, candidate cost and model term, the record), the read of
+ * the record, and the commit of an accepted step.  The first call after dvs_pgo_set_nodes / dvs_pgo_set_edges linearises at the handle's
+ * poses, as the solver's prologue does; later calls work at the linearisation the handle holds, as later iterations of the loop do.
+ *   max_pcg_iterations  0: max(100, 2 N), as dvs_pgo_params has it
+ *   reuse_diagonal      non-zero: the LM diagonal of the call before is kept (the loop does so after a rejected step)
+ *   commit              non-zero: the candidate becomes the point and is linearised (the loop's accept path); the verdict is the caller's
+ *   x_in                NULL, or a step [6 N] to take in place of the linear solve's: the PCG kernel is not launched, and the record's
+ *                       rnorm, gnorm, pcg_iterations and breakdown are zero
+ * Outputs, each may be NULL: cur_q [N][4] (w, x, y, z), cur_t [N][3] the point the step was taken from; x [6 N] the step; D [6 N] the LM
+ * diagonal; cand_q, cand_t the candidate; rec the status record (cur_cost and gmax are those of the point the step was taken from). */
+typedef struct dvs_pgo_step_record {
+  double cur_cost, gmax, cand_cost, model_cost_change, step2, x2, rnorm, gnorm;
+  int32_t pcg_iterations, finite, breakdown, reserved;
+} dvs_pgo_step_record;
+dvs_status dvs_test_pgo_trial_step(dvs_pgo* h, double radius, double eta, int32_t max_pcg_iterations, int32_t reuse_diagonal, int32_t commit,
+                                   const double* x_in, double* cur_q, double* cur_t, double* x, double* D, double* cand_q, double* cand_t,
+                                   dvs_pgo_step_record* rec);
+
 #ifdef __cplusplus
 }
 #endif

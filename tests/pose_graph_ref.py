@@ -15,6 +15,11 @@ import numpy as np
 LIN_MEASURED = 6.0e-16          # measured 5.67e-16
 EXACT_POSE_MEASURED = 2.0e-14   # measured 1.91e-14
 PCG_X_MEASURED = 8.0e-11        # measured 7.55e-11
+# the step tests' constants (tests/test_pose_graph_steps_cpu.py measures them and asserts they are not exceeded):
+#   TRIAL_MEASURED     trial_step() in float64 against longdouble at the same poses and step, in trial_distance(), over every replayed step
+#   PCG_STEP_MEASURED  the float64 PCG against pcg_k() in longdouble on the same system at the same iteration, |x - x_ld| / |x_ld|, per graph
+TRIAL_MEASURED = 9.0e-16        # measured 8.55e-16
+PCG_STEP_MEASURED = {"ring24_far": 2.0e-14, "ring24_far2": 3.0e-15, "chain515": 2.0e-15, "hub300": 3.0e-14}   # measured 1.72e-14, 2.51e-15, 1.92e-15, 2.79e-14
 
 # costs below this are zero to rounding (residuals of w eps |t|, about 1e-13, squared): the relative brackets add it as an absolute floor
 ZERO_COST = 1e-20
@@ -25,6 +30,16 @@ SCIPY_COST = {"ring24": 5.519908971873887, "hub300": 205.07267987146153, "exact2
 # the systems the linear-solve hook test solves: (graph, radius), at the graph's initial linearisation
 PCG_CASES = (("ring24", 1e4), ("ring24", 1.0), ("hub300", 1e4))
 PCG_TIGHT_MAX_IT = 2000
+# the same on the graph whose 515 nodes and 517 edges take the single-workgroup loops (512 threads) through a second trip.  The long chain
+# is worse conditioned at radius 1e4 (1350 iterations): its systems have PCG_X_MEASURED's of their own, measured in the same way
+SECOND_TRIP_GRAPHS = ("chain515", "chain515_fixed")
+SECOND_TRIP_PCG_CASES = (("chain515", 1e4), ("chain515", 1.0))
+PCG_X_MEASURED_SECOND_TRIP = {("chain515", 1e4): 1.2e-9, ("chain515", 1.0): 4.0e-12}   # measured 1.11e-09, 3.54e-12
+
+
+def pcg_x_measured(name, radius):
+    return PCG_X_MEASURED_SECOND_TRIP.get((name, radius), PCG_X_MEASURED)
+
 
 DEFAULTS = dict(max_iterations=50, function_tolerance=1e-6, gradient_tolerance=1e-10, parameter_tolerance=1e-8, eta=0.1, max_pcg_iterations=0)
 # what the solve tests pass: the function tolerance of the default would stop within 1e-6 of the minimum, which IS the tests' bracket
@@ -193,8 +208,9 @@ def lm_diagonal(H, fixed):
     return D * np.repeat(1 - np.asarray(fixed, dtype=np.float64), 6)
 
 
-def pcg(H, D, radius, gvec, fixed, eta, max_it):
-    """(x, iterations, |r|, |g|): block-Jacobi preconditioned CG on (H + D / radius) x = -g, zero start, over the free rows"""
+def pcg(H, D, radius, gvec, fixed, eta, max_it, hist=None):
+    """(x, iterations, |r|, |g|): block-Jacobi preconditioned CG on (H + D / radius) x = -g, zero start, over the free rows.  hist, a list,
+    receives |r| / (eta |g|) of the start and of every iteration: how far each stopping test was from its threshold."""
     n = len(gvec)
     free = np.repeat(np.asarray(fixed) == 0, 6)
     Am = H + np.diag(D / radius)
@@ -206,6 +222,8 @@ def pcg(H, D, radius, gvec, fixed, eta, max_it):
     r = np.where(free, -gvec, 0.0)
     gnorm = math.sqrt(r @ r)
     rnorm, it = gnorm, 0
+    if hist is not None:
+        hist.append(rnorm / (eta * gnorm) if gnorm > 0 else 0.0)
     if rnorm <= eta * gnorm or max_it <= 0:
         return x, it, rnorm, gnorm
     z = Minv @ r
@@ -221,6 +239,8 @@ def pcg(H, D, radius, gvec, fixed, eta, max_it):
         r = r - a * y
         rnorm = math.sqrt(r @ r)
         it += 1
+        if hist is not None:
+            hist.append(rnorm / (eta * gnorm))
         if rnorm <= eta * gnorm or it >= max_it:
             break
         z = Minv @ r
@@ -242,9 +262,10 @@ def apply_step(g, q, t, x):
     return q2, t2
 
 
-def solve(g, params=None):
+def solve(g, params=None, steps=None, n_steps=None):
     """the outer loop: Levenberg-Marquardt under the trust-region policy of csrc/ba.hip.  Returns a dict with R, t, the summary fields and
-    the trace rows (radius, kind, cost_change, model_cost_change, rho, candidate cost, pcg iterations)."""
+    the trace rows (radius, kind, cost_change, model_cost_change, rho, candidate cost, pcg iterations).  steps, a list, receives one dict
+    per trial step (what replay() documents); n_steps ends the loop after that many trial steps (termination 1)."""
     P = dict(DEFAULTS, **(params or {}))
     max_pcg = P["max_pcg_iterations"] or max(100, 2 * g.N)
     q = np.array([quat_from_R(R) for R in g.R]); t = g.t.copy()
@@ -255,7 +276,7 @@ def solve(g, params=None):
     radius, decrease, reuse, iteration, invalid = 1e4, 2.0, False, 0, 0
     D = None
     while True:
-        if iteration >= P["max_iterations"]:
+        if iteration >= P["max_iterations"] or (n_steps is not None and iteration >= n_steps):
             out["termination"] = 1; break
         if np.abs(grad[free]).max(initial=0.0) <= P["gradient_tolerance"] or radius < 1e-32:
             out["termination"] = 0; break
@@ -263,10 +284,15 @@ def solve(g, params=None):
         J = dense_jacobian(g, A, B); H = J.T @ J
         if not reuse:
             D = lm_diagonal(H, g.fixed)
-        x, its, _, _ = pcg(H, D, radius, grad, g.fixed, P["eta"], max_pcg)
+        hist = []
+        x, its, _, _ = pcg(H, D, radius, grad, g.fixed, P["eta"], max_pcg, hist)
         out["pcg_iterations"] += its
         Jx = J @ x
         model = -(x @ grad + 0.5 * (Jx @ Jx))
+        rec = dict(radius=radius, reuse=reuse, pcg_iterations=its, kind=0, rho=0.0, q=q, t=t, x=x, D=D, A=A, B=B, grad=grad, cost=cost,
+                   pcg_margin=min(abs(h - 1) for h in hist[-2:]), rho_margin=np.inf, ftol_margin=np.inf, ptol_margin=np.inf)
+        if steps is not None:
+            steps.append(rec)
         if not (model > 0) or not np.isfinite(x).all():
             out["trace"].append((radius, 0, 0, model, 0, 0, its))
             invalid += 1
@@ -280,12 +306,18 @@ def solve(g, params=None):
         step_norm = math.sqrt(((cq - q)[fr] ** 2).sum() + ((ct - t)[fr] ** 2).sum())
         x_norm = math.sqrt((q[fr] ** 2).sum() + (t[fr] ** 2).sum())
         change = cost - cand[0]
-        if step_norm <= P["parameter_tolerance"] * (x_norm + P["parameter_tolerance"]):
+        p_lim, f_lim = P["parameter_tolerance"] * (x_norm + P["parameter_tolerance"]), P["function_tolerance"] * cost
+        rec["ptol_margin"] = abs(step_norm / p_lim - 1) if p_lim > 0 else np.inf
+        if step_norm <= p_lim:
+            rec["kind"] = 3
             out["trace"].append((radius, 3, change, model, 0, cand[0], its)); out["termination"] = 0; break
-        if abs(change) <= P["function_tolerance"] * cost:
+        rec["ftol_margin"] = abs(abs(change) / f_lim - 1) if f_lim > 0 else np.inf
+        if abs(change) <= f_lim:
+            rec["kind"] = 4
             out["trace"].append((radius, 4, change, model, 0, cand[0], its)); out["termination"] = 0; break
         rho = change / model
         accept = rho > 1e-3
+        rec.update(kind=1 if accept else 2, rho=rho, rho_margin=abs(rho - 1e-3) / abs(rho))
         out["trace"].append((radius, 1 if accept else 2, change, model, rho, cand[0], its))
         if accept:
             q, t = cq, ct
@@ -299,6 +331,154 @@ def solve(g, params=None):
             radius /= decrease; decrease *= 2; reuse = True
     out.update(num_iterations=iteration, final_cost=cost, R=Rs(q), t=t)
     return out
+
+
+def replay(g, params, n_steps):
+    """the first n_steps trial steps of solve(g, params), one dict each: the restatement's radius, reuse (the LM diagonal is kept), pcg_iterations,
+    kind and rho; what the step started from (q, t, cost, the blocks A, B, grad, the diagonal D) and its step x; and how far each decision
+    was from its threshold: pcg_margin, the smaller |rnorm / (eta gnorm) - 1| of the stopping PCG iteration and the one before it;
+    rho_margin |rho - 1e-3| / |rho|; ftol_margin and ptol_margin, |lhs / rhs - 1| of the two tolerance comparisons (inf where a
+    comparison was not reached)."""
+    steps = []
+    solve(g, params, steps=steps, n_steps=n_steps)
+    return steps
+
+
+def _edge_product(g, A, B, v):
+    """u_e = A_e v_i + B_e v_j, [E][6]"""
+    v = v.reshape(-1, 6)
+    return np.einsum("eab,eb->ea", A, v[g.ei]) + np.einsum("eab,eb->ea", B, v[g.ej])
+
+
+def _inv6(M):
+    """inverses of [n][6][6] blocks by Gauss-Jordan without pivoting (the blocks are positive definite), in the blocks' number type"""
+    n = len(M)
+    W = np.concatenate([M.copy(), np.broadcast_to(np.eye(6, dtype=M.dtype), (n, 6, 6)).copy()], axis=2)
+    for c in range(6):
+        W[:, c, :] = W[:, c, :] / W[:, c, c][:, None]
+        for r in range(6):
+            if r != c:
+                W[:, r, :] = W[:, r, :] - W[:, r, c][:, None] * W[:, c, :]
+    return W[:, :, 6:]
+
+
+def pcg_k(g, A, B, D, radius, gvec, k, dtype=np.longdouble):
+    """x after exactly k iterations of pcg()'s recurrence on (J^T J + D / radius) x = -g, in `dtype` and without the dense matrices: J p
+    per edge, J^T of that per node.  What the step tests hold a float64 PCG stopped at iteration k against."""
+    A, B, D, gvec = (np.asarray(a, dtype) for a in (A, B, D, gvec))
+    N = g.N
+    free = np.repeat(g.fixed == 0, 6)
+
+    def scatter(U, out):     # out_n += sum over the edges at n of (A_e or B_e)^T U_e
+        np.add.at(out, g.ei, np.einsum("eab,ea->eb", A, U))
+        np.add.at(out, g.ej, np.einsum("eab,ea->eb", B, U))
+        return out
+
+    def op(p):
+        y = scatter(_edge_product(g, A, B, p), np.zeros((N, 6), dtype)).ravel() + (D / dtype(radius)) * p
+        return np.where(free, y, 0)
+    Hd = np.zeros((N, 6, 6), dtype)
+    np.add.at(Hd, g.ei, np.einsum("eab,eac->ebc", A, A))
+    np.add.at(Hd, g.ej, np.einsum("eab,eac->ebc", B, B))
+    Hd = Hd + (D / dtype(radius)).reshape(N, 6)[:, :, None] * np.eye(6, dtype=dtype)
+    fixed = g.fixed != 0
+    Hd[fixed] = np.eye(6, dtype=dtype)
+    Minv = _inv6(Hd)
+    Minv[fixed] = 0
+    pre = lambda r: np.einsum("nab,nb->na", Minv, r.reshape(N, 6)).ravel()
+    x = np.zeros(6 * N, dtype)
+    r = np.where(free, -gvec, 0)
+    if k <= 0:
+        return x
+    z = pre(r); p = z.copy(); rz = r @ z
+    for it in range(k):
+        y = op(p)
+        a = rz / (p @ y)
+        x = x + a * p
+        r = r - a * y
+        if it + 1 < k:
+            z = pre(r); rz2 = r @ z
+            p = z + (rz2 / rz) * p
+            rz = rz2
+    return x
+
+
+def pcg_distance(x, want):
+    want = np.asarray(want, np.longdouble)
+    return float(np.sqrt(((np.asarray(x, np.longdouble) - want) ** 2).sum()) / np.sqrt((want ** 2).sum()))
+
+
+def trial_step(g, q, t, x, lin=None, dtype=np.longdouble):
+    """what ONE trial produces from a given step x at the poses (q [N][4], t [N][3]), in `dtype`: the candidate poses (cand_q, cand_t), the
+    candidate's cost, x.g (xg), |J x|^2 / 2 (half_m), the model cost change -(x.g + |J x|^2 / 2), step2 = |candidate - point|^2 and
+    x2 = |point|^2 over the free nodes.  lin: linearize()'s tuple at the poses, made here when not given.  A step entry on a fixed node
+    is not read."""
+    q = np.asarray(q, dtype); t = np.asarray(t, dtype); x = np.asarray(x, dtype)
+    Rs = lambda qq: np.array([R_from_quat(v) for v in qq])
+    if lin is None:
+        lin = linearize(g, Rs(q), t, dtype=dtype)
+    _, _, A, B, grad = (np.asarray(a, dtype) for a in lin)
+    cq, ct = q.copy(), t.copy()
+    step2 = x2 = dtype(0)
+    half = dtype(1) / 2
+    xf = x.reshape(-1, 6) * (g.fixed == 0)[:, None].astype(dtype)
+    for n in range(g.N):
+        if g.fixed[n]:
+            continue
+        w, v = xf[n, :3], xf[n, 3:]
+        th = np.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2])
+        if th == 0:
+            e = np.array([1, 0, 0, 0], dtype)
+        else:
+            s = np.sin(th * half) / th
+            e = np.array([np.cos(th * half), s * w[0], s * w[1], s * w[2]], dtype)
+        qq = quat_mul(q[n], e)
+        cq[n] = qq / np.sqrt(qq @ qq)
+        ct[n] = t[n] + R_from_quat(q[n]) @ v
+        step2 = step2 + ((cq[n] - q[n]) ** 2).sum() + ((ct[n] - t[n]) ** 2).sum()
+        x2 = x2 + (q[n] ** 2).sum() + (t[n] ** 2).sum()
+    cand_cost = linearize(g, Rs(cq), ct, dtype=dtype)[0]
+    u = _edge_product(g, A, B, xf.ravel())
+    xg, half_m = xf.ravel() @ grad, (u * u).sum() * half
+    return dict(cand_q=cq, cand_t=ct, cand_cost=cand_cost, xg=xg, half_m=half_m, model_cost_change=-(xg + half_m), step2=step2, x2=x2)
+
+
+def trial_distance(g, got, want):
+    """the distance TRIAL_MEASURED is stated in, per quantity, the largest of them.  `want`: trial_step() in longdouble; `got`: a dict with
+    cand_q, cand_t, cand_cost, model_cost_change, step2, x2.  Candidate poses: absolute, against 1 and max(1, |t|_max).  The candidate's
+    cost: against lin_distance's scale for a cost.  The model change: against |x.g| + |J x|^2 / 2, the terms that cancel in it.
+    step2 and x2: against their own values."""
+    L = np.longdouble
+    s_r = float(max(g.w_rot.max(), g.w_trans.max()) * max(1.0, np.abs(want["cand_t"]).max()))
+    d = dict(cand_q=np.abs(np.asarray(got["cand_q"], L) - want["cand_q"]).max(),
+             cand_t=np.abs(np.asarray(got["cand_t"], L) - want["cand_t"]).max() / max(1.0, float(np.abs(want["cand_t"]).max())),
+             cand_cost=abs(L(got["cand_cost"]) - want["cand_cost"]) / max(float(want["cand_cost"]), s_r * s_r),
+             model=abs(L(got["model_cost_change"]) - want["model_cost_change"]) / (abs(want["xg"]) + want["half_m"]),
+             step2=abs(L(got["step2"]) - want["step2"]) / want["step2"], x2=abs(L(got["x2"]) - want["x2"]) / want["x2"])
+    return max(float(v) for v in d.values()), {k: float(v) for k, v in d.items()}
+
+
+def verdict(rec, x_cost, params):
+    """the host's rule of dvs_pgo_solve on one status record: (kind, cost change, relative decrease) — kind 0 invalid, 1 accepted,
+    2 rejected, 3 parameter tolerance, 4 function tolerance; x_cost is the cost of the point the step was taken from"""
+    P = dict(DEFAULTS, **(params or {}))
+    if not rec["finite"] or not (rec["model_cost_change"] > 0.0):
+        return 0, 0.0, 0.0
+    change = x_cost - rec["cand_cost"]
+    if math.sqrt(rec["step2"]) <= P["parameter_tolerance"] * (math.sqrt(rec["x2"]) + P["parameter_tolerance"]):
+        return 3, change, 0.0
+    if abs(change) <= P["function_tolerance"] * x_cost:
+        return 4, change, 0.0
+    rho = change / rec["model_cost_change"]
+    return (1 if rho > 1e-3 else 2), change, rho
+
+
+def trace_row(rec, radius, x_cost, params):
+    """the row dvs_pgo_solve logs for the record"""
+    kind, change, rho = verdict(rec, x_cost, params)
+    if kind == 0:
+        return [radius, 0.0, 0.0, rec["model_cost_change"], 0.0, 0.0, float(rec["pcg_iterations"])]
+    return [radius, float(kind), change, rec["model_cost_change"], rho, rec["cand_cost"], float(rec["pcg_iterations"])]
 
 
 def correct_points(xyz, anchor, R0, t0, R1, t1):
@@ -426,7 +606,62 @@ def graph(name):
         return make_graph(24, [(23, 0), (22, 1), (12, 0)], seed=1, noise=False)
     if name == "hub300":
         return make_graph(300, [(299, 0), (150, 1)], _hub_extra(), seed=2)
+    if name == "ring24_far":
+        return _far(1.0, 2.0, 3)
+    if name == "ring24_far2":
+        return _far(2.0, 5.0, 4)
+    if name == "chain515":
+        return make_graph(515, [(514, 0), (257, 1), (400, 100)], seed=3)
+    if name == "chain515_fixed":
+        g = make_graph(515, [(514, 0), (257, 1), (400, 100)], seed=3)
+        g.fixed[513] = 1
+        return g
     return edge_case(name)
+
+
+def _far(s_rot, s_trans, seed):
+    """ring24 started far from its minimum: nodes 1 .. 23 moved by R_n <- R_n Exp(N(0, s_rot)^3), t_n += N(0, s_trans)^3, node after node"""
+    g = graph("ring24")
+    rng = np.random.default_rng(seed)
+    R, t = g.R.copy(), g.t.copy()
+    for n in range(1, g.N):
+        R[n] = R[n] @ rodrigues(rng.normal(0, s_rot, 3)); t[n] = t[n] + rng.normal(0, s_trans, 3)
+    return Graph(R, t, g.fixed, g.ei, g.ej, g.rvec, g.tvec, g.w_rot, g.w_trans, planted=g.planted)
+
+
+# The graphs of the step tests (tests/test_pose_graph_steps_cpu.py asserts every statement here on the restatement):
+#   ring24_far   kinds of the first twelve trial steps under TIGHT: FAR_KINDS — four rejections in a row (the radius divided by 2, 4, 8, 16,
+#                the LM diagonal kept, a second, third .. trial from one linearisation) and a later single one
+#   ring24_far2  a rejection directly after the first accepted step; the run meets the iteration limit (termination 1)
+#   chain515     N = 515, E = 517: the single-workgroup loops (512 threads) make a second trip of 3 nodes and 5 edges
+#   chain515_fixed  the same with a fixed node inside the second trip
+#   ring24 under PTOL ends by the parameter tolerance (kind 3); overflow6 (weights 1e150) fails after five invalid steps (kind 0)
+FAR_KINDS = (1, 1, 1, 1, 2, 2, 2, 2, 1, 1, 2, 1)
+FAR2_KINDS = (1, 2, 2, 2, 2, 1)
+PTOL = dict(TIGHT, parameter_tolerance=1e-3, function_tolerance=1e-14)
+OVERFLOW_RADII = (1e4, 5e3, 1250.0, 156.25, 9.765625)
+# (graph, parameters, replayed trial steps): the hook is driven through these steps one at a time
+REPLAY_CASES = {"ring24_far": ("ring24_far", TIGHT, 15), "ring24_far2": ("ring24_far2", TIGHT, 8), "chain515": ("chain515", TIGHT, 3),
+                "hub300": ("hub300", TIGHT, 3)}
+# whole solves: (graph, parameters)
+SOLVE_CASES = {"ring24_far": ("ring24_far", TIGHT), "ring24_far2": ("ring24_far2", TIGHT), "chain515": ("chain515", TIGHT), "ring24_ptol": ("ring24", PTOL)}
+PREMISE = 1e-6
+
+
+@functools.lru_cache(maxsize=None)
+def replay_case(name):
+    gname, params, n = REPLAY_CASES[name]
+    return replay(graph(gname), params, n)
+
+
+@functools.lru_cache(maxsize=None)
+def solve_case(name):
+    """the restatement's whole solve of a SOLVE_CASES entry, with its per-step records under "steps" """
+    gname, params = SOLVE_CASES[name]
+    steps = []
+    out = solve(graph(gname), params, steps=steps)
+    out["steps"] = steps
+    return out
 
 
 SOLVE_GRAPHS = ("ring24", "hub300", "exact24")
@@ -457,6 +692,8 @@ def edge_case(name):
         ei.append(1); ej.append(3); rv.append(w); tv.append(R[1].T @ (t[3] - t[1])); wr.append(300.0); wt.append(200.0)
     elif name == "two_fixed":
         fixed[3] = 1
+    elif name == "overflow6":             # every weight 1e150: cost (4.47e298) and gradient are finite, the gradient's squared norm is not
+        wr = [1e150] * len(wr); wt = [1e150] * len(wt)
     else:
         raise KeyError(name)
     return Graph(R, t, fixed, ei, ej, rv, tv, wr, wt, planted=None)
