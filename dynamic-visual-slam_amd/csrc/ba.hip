@@ -23,6 +23,7 @@
 #include <new>
 #include <chrono>
 #include <vector>
+#include "block_ops.h"
 #include "common.h"
 #include "device_mem.h"
 
@@ -369,13 +370,8 @@ __device__ __forceinline__ void ba_reduce_body(const int bid, const int nReduce,
     double sacc = 0;
     const int per = (K + 255) / 256;
     for (int i = tid * per; i < min(K, (tid + 1) * per); i++) sacc += __hip_atomic_load(&costCam[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_red[tid] = sacc;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {  // fixed-shape tree: deterministic
-      if (tid < o) s_red[tid] += s_red[tid + o];
-      __syncthreads();
-    }
-    if (tid == 0) { *cost = s_red[0]; __hip_atomic_store(ticketCounter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    sacc = block_sum<256>(sacc, s_red);  // fixed-shape tree: deterministic
+    if (tid == 0) { *cost = sacc; __hip_atomic_store(ticketCounter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   }
 }
 
@@ -399,21 +395,10 @@ __global__ __launch_bounds__(256) void k_ba_reduce(BaDev P, int K, int L, int nC
 // =============================================================================================================================
 struct LmStatus { int ok, finite; double model_change, sn, xn, cand_cost, gmax, x_cost; int seq, accept; };   // seq: number of this publication; accept: the trial step's verdict (k_lm_norms)
 
-__device__ __forceinline__ double block_sum_fixed(double v, double* sm) {  // 256 threads, fixed tree
-  const int tid = threadIdx.x;
-  __syncthreads();
-  sm[tid] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) sm[tid] += sm[tid + s];
-    __syncthreads();
-  }
-  return sm[0];
-}
-
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
-__device__ __forceinline__ void quat_plus_dev(const double* x, const double* d, double* o) {  // EigenQuaternionManifold::Plus
+// ceres::EigenQuaternionManifold::Plus on the raw (w,x,y,z) memory read as Eigen (x,y,z,w); the kernels and the host solver share it
+__host__ __device__ __forceinline__ void quat_plus(const double* x, const double* d, double* o) {
   const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
   if (nd == 0.0) { for (int i = 0; i < 4; i++) o[i] = x[i]; return; }
   const double sn = sin(nd) / nd;
@@ -1059,7 +1044,7 @@ __global__ __launch_bounds__(256) void k_lm_candidate(int K, int L, const double
     if (active[6 * c]) {
       // the camera steps are stored as k_lm_chol solved them (not negated: k_lm_backsub reads them so); the landmarks' are negated
       const double d[3] = {-step[6 * c] * scale[6 * c], -step[6 * c + 1] * scale[6 * c + 1], -step[6 * c + 2] * scale[6 * c + 2]};
-      quat_plus_dev(q0 + 4 * c, d, cq);
+      quat_plus(q0 + 4 * c, d, cq);
       for (int k = 0; k < 3; k++) ct[k] = t0[3 * c + k] + -step[6 * c + 3 + k] * scale[6 * c + 3 + k];
       for (int k = 0; k < 4; k++) { sn += (q0[4 * c + k] - cq[k]) * (q0[4 * c + k] - cq[k]); xn += q0[4 * c + k] * q0[4 * c + k]; }
       for (int k = 0; k < 3; k++) { sn += (t0[3 * c + k] - ct[k]) * (t0[3 * c + k] - ct[k]); xn += t0[3 * c + k] * t0[3 * c + k]; }
@@ -1077,16 +1062,11 @@ __global__ __launch_bounds__(256) void k_lm_candidate(int K, int L, const double
       X[3 * l + k] = v;
     }
   }
-  // both sums through one tree (block_sum_fixed's association for each)
+  // both sums through one tree
   __shared__ double sm2[2][256];
-  const int tid = threadIdx.x;
-  sm2[0][tid] = sn; sm2[1][tid] = xn;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) { sm2[0][tid] += sm2[0][tid + s]; sm2[1][tid] += sm2[1][tid + s]; }
-    __syncthreads();
-  }
-  if (tid == 0) { part[2 * blockIdx.x] = sm2[0][0]; part[2 * blockIdx.x + 1] = sm2[1][0]; }
+  double v[2] = {sn, xn};
+  block_sums<256, 2>(v, &sm2[0][0]);
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = v[0]; part[2 * blockIdx.x + 1] = v[1]; }
 }
 
 // publish the status record to the host's pinned copy (read after the stream synchronises: no D2H copy command), and — last kernel of
@@ -1120,18 +1100,11 @@ __global__ __launch_bounds__(256) void k_lm_norms(int nparts, const double* __re
     for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++)
       sHs += -step[6 * c + a] * scale[6 * c + a] * Hpp[36 * (size_t)c + 6 * a + b] * scale[6 * c + b] * -step[6 * c + b];
   for (int l = tid; l < L; l += 256) { sg += lmPart[2 * (size_t)l]; sHs += lmPart[2 * (size_t)l + 1]; }
-  // the five sums through ONE tree (block_sum_fixed's association for each; five passes of it were 45 barriers)
+  // the five sums through ONE tree (five one-wide passes were 45 barriers)
   __shared__ double sm5[5][256];
-  sm5[0][tid] = sn; sm5[1][tid] = xn; sm5[2][tid] = sg; sm5[3][tid] = sHs; sm5[4][tid] = fin;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) {
-#pragma unroll
-      for (int k = 0; k < 5; k++) sm5[k][tid] += sm5[k][tid + s];
-    }
-    __syncthreads();
-  }
-  const double a = sm5[0][0], b = sm5[1][0], tg = sm5[2][0], th = sm5[3][0], tf = sm5[4][0];
+  double v[5] = {sn, xn, sg, sHs, fin};
+  block_sums<256, 5>(v, &sm5[0][0]);
+  const double a = v[0], b = v[1], tg = v[2], th = v[3], tf = v[4];
   if (tid == 0) {
     if (tf > 0.0) st->finite = 0;
     st->model_change = -(tg + 0.5 * th);
@@ -1171,7 +1144,7 @@ __global__ __launch_bounds__(256) void k_lm_gmax(int K, int L, const double* __r
   for (int c = tid; c < K; c += 256) if (active[6 * c]) {
     const double d[3] = {-g[6 * c], -g[6 * c + 1], -g[6 * c + 2]};
     double qp[4];
-    quat_plus_dev(q0 + 4 * c, d, qp);
+    quat_plus(q0 + 4 * c, d, qp);
     for (int i = 0; i < 4; i++) m = fmax(m, fabs(q0[4 * c + i] - qp[i]));
     for (int i = 0; i < 3; i++) m = fmax(m, fabs(g[6 * c + 3 + i]));
   }
@@ -1193,7 +1166,7 @@ __global__ void k_lm_reset(LmStatus* st) { st->ok = 1; st->finite = 1; st->model
 // sum_e Ws_e u_l(e)), k_gba_update (q = S p, alpha, x, r, z, beta, p, stopping rule) — each of which returns at once when the
 // record says the solve has stopped, so the host enqueues them in batches and reads one small record per batch.
 // Every sum has a fixed order: a landmark's observations in lmStart / lmObs order, a chunk by a fixed shuffle tree, a camera's
-// chunks in chunk order, dot products by per-thread strides and block_sum_fixed.  No floating-point atomics.
+// chunks in chunk order, dot products by per-thread strides and block_ops.h's fixed tree.  No floating-point atomics.
 // =============================================================================================================================
 struct PcgState { double rz, bnorm2, rnorm2; int iter, done, ok, pad; };
 struct GbaDev {
@@ -1380,7 +1353,7 @@ __device__ __forceinline__ void pcg_publish(const PcgState* s, PcgState* host) {
 //   mode 2  q = S p only (dvs_ba_schur_probe)
 // host: where to publish the record (mode 1, last launch of a batch), or null
 __global__ __launch_bounds__(256) void k_gba_update(GbaDev P, int mode, double radius, double eta, int max_it, PcgState* host) {
-  __shared__ double sm[256];
+  __shared__ double sm[2][256];
   const int tid = threadIdx.x;
   PcgState* S = P.pcg;
   if (mode == 0) {
@@ -1398,9 +1371,9 @@ __global__ __launch_bounds__(256) void k_gba_update(GbaDev P, int mode, double r
         rz += bv[a] * z; bn += bv[a] * bv[a];
       }
     }
-    rz = block_sum_fixed(rz, sm);
-    bn = block_sum_fixed(bn, sm);
-    if (tid == 0) { S->rz = rz; S->bnorm2 = bn; S->rnorm2 = bn; S->iter = 0; S->done = 0; S->ok = 1; }
+    double v[2] = {rz, bn};
+    block_sums<256, 2>(v, &sm[0][0]);
+    if (tid == 0) { S->rz = v[0]; S->bnorm2 = v[1]; S->rnorm2 = v[1]; S->iter = 0; S->done = 0; S->ok = 1; }
     return;
   }
   if (mode == 1 && S->done) {
@@ -1432,7 +1405,7 @@ __global__ __launch_bounds__(256) void k_gba_update(GbaDev P, int mode, double r
     for (int a = 0; a < 6; a++) P.qv[6 * c + a] = qv[a];
   }
   if (mode == 2) return;
-  pq = block_sum_fixed(pq, sm);
+  pq = block_sum<256>(pq, &sm[0][0]);
   const double rz = S->rz, bn = S->bnorm2;
   const int iter = S->iter;
   if (!(pq > 0.0) || !isfinite(pq)) {
@@ -1463,8 +1436,9 @@ __global__ __launch_bounds__(256) void k_gba_update(GbaDev P, int mode, double r
       rzn += rv[a] * z; rn += rv[a] * rv[a];
     }
   }
-  rzn = block_sum_fixed(rzn, sm);
-  rn = block_sum_fixed(rn, sm);
+  double v[2] = {rzn, rn};
+  block_sums<256, 2>(v, &sm[0][0]);
+  rzn = v[0]; rn = v[1];
   const bool stop = sqrt(rn) <= eta * sqrt(bn) || iter + 1 >= max_it;
   if (!stop) {
     const double beta = rzn / rz;
@@ -1711,18 +1685,6 @@ struct TrustRegion {
  private:
   void shrink(bool reuse) { radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = reuse; }
 };
-
-// ceres::EigenQuaternionManifold::Plus on the raw (w,x,y,z) memory read as Eigen (x,y,z,w)
-void quat_plus(const double* x, const double* d, double* o) {
-  const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-  if (nd == 0.0) { for (int i = 0; i < 4; i++) o[i] = x[i]; return; }
-  const double sn = sin(nd) / nd;
-  const double dx = sn * d[0], dy = sn * d[1], dz = sn * d[2], dw = cos(nd);
-  o[3] = dw * x[3] - dx * x[0] - dy * x[1] - dz * x[2];
-  o[0] = dw * x[0] + dx * x[3] + dy * x[2] - dz * x[1];
-  o[1] = dw * x[1] + dy * x[3] + dz * x[0] - dx * x[2];
-  o[2] = dw * x[2] + dz * x[3] + dx * x[1] - dy * x[0];
-}
 
 bool chol_solve(std::vector<double>& A, int n, std::vector<double>& b, std::vector<double>* y = nullptr) {   // y: b after the forward substitution
   for (int j = 0; j < n; j++) {

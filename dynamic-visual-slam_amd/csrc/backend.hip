@@ -15,7 +15,7 @@
 //   k_window_gather    the window's observations, the distinct landmarks in id order, indices into that list                (:916-945)
 //   k_apply            optimised positions and poses                                                                        (:1356-1392)
 //   k_prune_mark / k_prune_compact   mark, then compact both tables in order and list the removed observations              (:1249-1322)
-// Compactions are one workgroup of four wavefronts walking the table in trips of 256 (block_rank.h), as tracker.hip does it.
+// Compactions are one workgroup of four wavefronts walking the table in trips of 256 (block_ops.h), as tracker.hip does it.
 //
 // Triangulation: LandmarkInfo::triangulate at :772 reads the views stored BEFORE this keyframe and the landmark's position at the start of
 // the keyframe only (include/dvslam/triangulation.hpp states why), so it runs once per keyframe over the whole table, before the classes.
@@ -35,7 +35,7 @@
 #include "matcher.h"
 #include "backend_internal.h"
 #include "associate_device.h"
-#include "block_rank.h"
+#include "block_ops.h"
 #include "../../include/dvslam/association.hpp"   // reprojection_error: the device kernel's arithmetic on the host
 
 namespace dvs {

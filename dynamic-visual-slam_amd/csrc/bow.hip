@@ -14,6 +14,7 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include "block_ops.h"
 #include "common.h"
 #include "device_mem.h"
 #include "bow_internal.h"
@@ -99,20 +100,6 @@ __global__ __launch_bounds__(kBlock) void k_bow_rank(const int* __restrict__ d_n
   }
 }
 
-// exclusive block scan of a flag; *total = the block's sum.  Every thread of the block calls it.
-__device__ int block_scan_flag(bool flag, int* s_wave, int* total) {
-  const unsigned long long bal = __ballot(flag);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int excl = __popcll(bal & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) s_wave[wave] = __popcll(bal);
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int w = 0; w < kBlock / 64; w++) { before += w < wave ? s_wave[w] : 0; all += s_wave[w]; }
-  *total = all;
-  return before + excl;
-}
-
 // heads of the runs of equal keys in sorted[0, m): keys[s] = the run's key, starts[s] = its first position, starts[count] = m
 __device__ int segment_heads(const int* __restrict__ sorted, int m, int* __restrict__ keys, int* __restrict__ starts, int* s_wave) {
   int count = 0;
@@ -120,7 +107,7 @@ __device__ int segment_heads(const int* __restrict__ sorted, int m, int* __restr
     const int r = t + threadIdx.x;
     const bool head = r < m && (r == 0 || sorted[r] != sorted[r - 1]);
     int total;
-    const int s = count + block_scan_flag(head, s_wave, &total);
+    const int s = count + block_rank256(head, s_wave, total);
     if (head) { keys[s] = sorted[r]; starts[s] = r; }
     count += total;
   }

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+#include "block_ops.h"
 #include "common.h"
 #include "device_mem.h"
 #include "bow_internal.h"
@@ -78,13 +79,8 @@ __global__ __launch_bounds__(kBlock) void k_scan_partial(const int* __restrict__
   const int base = blockIdx.x * kScanChunk + threadIdx.x * 4;
   long long s = 0;
   for (int i = 0; i < 4; i++) if (base + i < P) s += vals[base + i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = kBlock / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) bsum[blockIdx.x] = sh[0];
+  s = block_sum<kBlock>(s, sh);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = s;
 }
 
 // inclusive scan of one value per thread of the workgroup

@@ -27,7 +27,7 @@
 #include "device_mem.h"
 #include "matcher.h"
 #include "backend_internal.h"
-#include "block_rank.h"
+#include "block_ops.h"
 
 namespace dvs {
 

@@ -16,23 +16,9 @@
 #include "io_pinned.h"
 #include "matcher.h"
 #include "associate_device.h"
+#include "block_ops.h"
 
 namespace dvs {
-
-__device__ __forceinline__ int blk_excl_scan(int v, int* wsum, int& total) {  // 256 threads
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { int t = __shfl_up(incl, o); if ((int)(threadIdx.x & 63) >= o) incl += t; }
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 63) wsum[w] = incl;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) { const int s = wsum[i]; if (i < w) base += s; }
-  total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  return base + incl - v;
-}
 
 // 4 pixels per thread; coefficients of OpenCV's RGB2Gray<uchar> (variant 0: 15-bit, 4.x; variant 1: 14-bit, older releases)
 __global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t* __restrict__ bgr, uint64_t step, uint64_t fstride, int rows, int cols,
@@ -70,7 +56,7 @@ __global__ __launch_bounds__(256) void k_filter_depth(const dvs_keypoint* __rest
                                                       int cols, float dmin, float dmax, dvs_keypoint* __restrict__ okps,
                                                       uint8_t* __restrict__ odesc, int* __restrict__ oindex, int* __restrict__ nOut,
                                                       int* __restrict__ hseq, int seq) {
-  __shared__ int wsum[5];
+  __shared__ int wsum[4];
   const int f = blockIdx.x, tid = threadIdx.x;
   const int n = nArr ? min(max(nArr[f], 0), strideRows) : nConst;  // a stale / corrupt count must not walk past the frame's block (as k_match)
   const dvs_keypoint* kp = kps + (size_t)f * strideRows;
@@ -113,7 +99,7 @@ __global__ __launch_bounds__(256) void k_filter_depth(const dvs_keypoint* __rest
       if (b + 256 * u >= n) break;
       const int i = b + 256 * u + tid;
       int tot;
-      const int pos = carry + blk_excl_scan(keep[u] ? 1 : 0, wsum, tot);
+      const int pos = carry + block_rank256(keep[u], wsum, tot);
       if (keep[u]) {
         okps[(size_t)f * strideRows + pos] = k[u];
         if (oindex) oindex[(size_t)f * strideRows + pos] = i;
@@ -135,7 +121,7 @@ __global__ __launch_bounds__(256) void k_filter_depth(const dvs_keypoint* __rest
 
 __global__ __launch_bounds__(256) void k_filter_matches(const int* __restrict__ idx, const int* __restrict__ dist, const int* __restrict__ nArr,
                                                         int nConst, int strideRows, float maxd, int* __restrict__ out, int* __restrict__ nOut) {
-  __shared__ int wsum[5];
+  __shared__ int wsum[4];
   const int f = blockIdx.x, tid = threadIdx.x;
   const int n = nArr ? min(max(nArr[f], 0), strideRows) : nConst;  // a stale / corrupt count must not walk past the frame's block (as k_match)
   int carry = 0;
@@ -143,7 +129,7 @@ __global__ __launch_bounds__(256) void k_filter_matches(const int* __restrict__ 
     const int i = b + tid;
     const bool keep = i < n && (float)dist[(size_t)f * strideRows + i] < maxd;
     int tot;
-    const int pos = carry + blk_excl_scan(keep ? 1 : 0, wsum, tot);
+    const int pos = carry + block_rank256(keep, wsum, tot);
     if (keep) {
       int* o = out + 3 * ((size_t)f * strideRows + pos);
       o[0] = i; o[1] = idx[(size_t)f * strideRows + i]; o[2] = dist[(size_t)f * strideRows + i];
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(256) void k_filter_matches(const int* __restrict__ 
 __global__ __launch_bounds__(256) void k_backproject(const dvs_keypoint* __restrict__ kps, int n, const uint16_t* __restrict__ depth,
                                                      int rows, int cols, uint64_t dstep, float fx, float fy, float cx, float cy, const double* __restrict__ Rt,
                                                      double* __restrict__ world, int* __restrict__ oindex, int* __restrict__ nOut) {
-  __shared__ int wsum[5];
+  __shared__ int wsum[4];
   const int tid = threadIdx.x;
   int carry = 0;
   for (int b = 0; b < n; b += 256) {
@@ -175,7 +161,7 @@ __global__ __launch_bounds__(256) void k_backproject(const dvs_keypoint* __restr
       keep = (double)Z > 0.3 && (double)Z < 3.0;
     }
     int tot;
-    const int pos = carry + blk_excl_scan(keep ? 1 : 0, wsum, tot);
+    const int pos = carry + block_rank256(keep, wsum, tot);
     if (keep) {
       const double v0 = X, v1 = Y, v2 = Z;
 #pragma unroll
@@ -245,8 +231,7 @@ __global__ __launch_bounds__(256) void k_publish_keyframe(KfHead H, const dvs_ke
                                                           float cx, float cy, const double* __restrict__ Rt, uint8_t* __restrict__ out,
                                                           unsigned long long cap, unsigned long long* __restrict__ outSize,
                                                           int* __restrict__ nOut) {
-  __shared__ int wsum[5];
-  __shared__ int s_m;
+  __shared__ int wsum[4], s_sum[256];
   const int tid = threadIdx.x;
   uint8_t* P = out + 4;
   const uint32_t o2 = H.o1 + 64;
@@ -258,11 +243,7 @@ __global__ __launch_bounds__(256) void k_publish_keyframe(KfHead H, const dvs_ke
     const float Z = inb ? __fmul_rn((float)*(const uint16_t*)((const uint8_t*)depth + (uint64_t)y * dstep + 2 * (uint64_t)x), 0.001f) : 0.f;
     cnt += ((double)Z > 0.3 && (double)Z < 3.0) ? 1 : 0;
   }
-  int tot;
-  (void)blk_excl_scan(cnt, wsum, tot);
-  if (tid == 0) s_m = tot;
-  __syncthreads();
-  const int m = s_m;
+  const int m = block_sum<256>(cnt, s_sum);
   const unsigned long long total = 4ull + (m == 0 ? o2 + 8ull : o2 + 8ull + 32ull * m + 8ull + 64ull * (m - 1) + 60ull);
   if (tid == 0) { *outSize = total; *nOut = m; }
   if (total > cap) return;  // the host reports DVS_ERR_CAPACITY from outSize
@@ -299,7 +280,7 @@ __global__ __launch_bounds__(256) void k_publish_keyframe(KfHead H, const dvs_ke
       keep = (double)Z > 0.3 && (double)Z < 3.0;
     }
     int t2;
-    const int pos = carry + blk_excl_scan(keep ? 1 : 0, wsum, t2);
+    const int pos = carry + block_rank256(keep, wsum, t2);
     if (keep) {
       const double v0 = X, v1 = Y, v2 = Z;
       uint8_t* L = P + lm0 + 32 * (size_t)pos;

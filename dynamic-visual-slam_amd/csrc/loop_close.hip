@@ -7,7 +7,7 @@
 //   k_anchors        per landmark the keyframe of the first view of its segment in the views CSR (backend_views_build), -1 without one
 //   k_fuse_mark      per observation: its landmark's row, and the landmark flagged target (named by the query keyframe q) or entry-side
 //                    (named by a keyframe of E) with an integer atomic OR; the observation that sets a target's flag first counts it
-//   k_fuse_lists     one workgroup, trips of 256 (block_rank.h): q's observations — one run of the table, found by binary search — packed
+//   k_fuse_lists     one workgroup, trips of 256 (block_ops.h): q's observations — one run of the table, found by binary search — packed
 //                    in table order (pixel, class, id, target row, descriptor), and the source rows (entry-side and not target) in ascending id
 //   k_fuse_propose   one lane per source, 256 per workgroup: camera point and float pixel once, the descriptor in eight registers; q's
 //                    packed observations stream through LDS in tiles of 256 (14 KB; every lane reads the same row, a broadcast), eight
@@ -31,7 +31,7 @@
 #include "device_mem.h"
 #include "matcher.h"
 #include "backend_internal.h"
-#include "block_rank.h"
+#include "block_ops.h"
 
 namespace dvs {
 

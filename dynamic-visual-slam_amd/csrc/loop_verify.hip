@@ -14,6 +14,7 @@
 #include <math.h>
 #include <string.h>
 #include <vector>
+#include "block_ops.h"
 #include "common.h"
 #include "device_mem.h"
 #include "loop_internal.h"
@@ -122,20 +123,14 @@ __global__ __launch_bounds__(kBlock) void k_lv_gather(const long long* __restric
         take = point_valid(qx, qy, qz) && point_valid(ex, ey, ez);
       }
     }
-    const unsigned long long bal = __ballot(take);
-    const int lane = tid & 63, w = tid >> 6;
-    __syncthreads();                                  // the totals of the chunk before have been read
-    if (lane == 0) s_wave[w] = __popcll(bal);
-    __syncthreads();
-    int before = m;
-    for (int k = 0; k < w; k++) before += s_wave[k];
+    int total;
+    const int pos = m + block_rank256(take, s_wave, total);   // pos <= i < stride_rows
     if (take) {
-      const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));   // pos <= i < stride_rows
       list_i[base + pos] = i;
       plane[pos] = ex; plane[(size_t)stride_rows + pos] = ey; plane[2 * (size_t)stride_rows + pos] = ez;
       plane[3 * (size_t)stride_rows + pos] = qx; plane[4 * (size_t)stride_rows + pos] = qy; plane[5 * (size_t)stride_rows + pos] = qz;
     }
-    m += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    m += total;
   }
   if (tid == 0) {
     // a list shorter than min_correspondences runs no later stage: its RansacProb is empty
@@ -186,15 +181,6 @@ __global__ __launch_bounds__(64) void k_lv_hypotheses(const RansacProb* __restri
   if (dbg_gap) dbg_gap[o] = gap;
 }
 
-// number of threads of the 256-thread block with pred; s_cnt: 4 ints of LDS
-__device__ __forceinline__ int block_count(bool pred, int* s_cnt) {
-  const unsigned long long b = __ballot(pred);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
-  return s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
 // grid (H, cap_cand), 256 threads: thread k of a chunk reads position k of each plane — consecutive floats
 __global__ __launch_bounds__(kBlock) void k_lv_score(const RansacProb* __restrict__ probs, const float* __restrict__ pts, int stride_rows, int H,
                                                      const double* __restrict__ models, const int* __restrict__ valid, Cam K, double thr2,
@@ -215,27 +201,12 @@ __global__ __launch_bounds__(kBlock) void k_lv_score(const RansacProb* __restric
     if (k < n)
       in = lv_error(R, t, K, plane[k], plane[(size_t)stride_rows + k], plane[2 * (size_t)stride_rows + k], plane[3 * (size_t)stride_rows + k],
                     plane[4 * (size_t)stride_rows + k], plane[5 * (size_t)stride_rows + k]) <= thr2;
-    total += block_count(in, s_cnt);
+    total += block_count256(in, s_cnt);
   }
   if (threadIdx.x == 0) counts[o] = total;
 }
 
-// the NV sums of a 256-thread block in a fixed order: thread t's partial sums (its positions t, t + 256, ... in ascending order) are
-// folded pairwise, t with t + 128, then + 64, ... — the same tree whatever the schedule.  Every thread gets the totals.
-template <int NV>
-__device__ __forceinline__ void block_sums(double* v, double* s_red /* [NV][256] */) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  for (int k = 0; k < NV; k++) s_red[k * kBlock + tid] = v[k];
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if (tid < s)
-      for (int k = 0; k < NV; k++) s_red[k * kBlock + tid] += s_red[k * kBlock + tid + s];
-    __syncthreads();
-  }
-  for (int k = 0; k < NV; k++) v[k] = s_red[k * kBlock];
-}
-
+// the sums of k_lv_refine: thread t's partial sums (its positions t, t + 256, ... in ascending order) folded by block_ops.h's fixed tree
 // grid (cap_cand), 256 threads
 __global__ __launch_bounds__(kBlock) void k_lv_refine(const RansacProb* __restrict__ probs, const float* __restrict__ pts, const int* __restrict__ list_i,
                                                       int stride_rows, int H, const double* __restrict__ models, const int* __restrict__ sel, Cam K,
@@ -260,7 +231,7 @@ __global__ __launch_bounds__(kBlock) void k_lv_refine(const RansacProb* __restri
     for (int k0 = 0; k0 < n; k0 += kBlock) {
       const int k = k0 + tid;
       const bool in = k < n && lv_error(Rm, tm, K, pex[k], pey[k], pez[k], pqx[k], pqy[k], pqz[k]) <= thr2;
-      total += block_count(in, s_cnt);
+      total += block_count256(in, s_cnt);
     }
     return total;
   };
@@ -274,7 +245,7 @@ __global__ __launch_bounds__(kBlock) void k_lv_refine(const RansacProb* __restri
       if (lv_error(R, t, K, pex[k], pey[k], pez[k], pqx[k], pqy[k], pqz[k]) <= thr2) {
         v[0] += pex[k]; v[1] += pey[k]; v[2] += pez[k]; v[3] += pqx[k]; v[4] += pqy[k]; v[5] += pqz[k];
       }
-    block_sums<6>(v, s_red);
+    block_sums<kBlock, 6>(v, s_red);
     const double me[3] = {v[0] / size, v[1] / size, v[2] / size}, mq[3] = {v[3] / size, v[4] / size, v[5] / size};
     // pass 2: the centred cross-covariance
     for (int k = 0; k < 9; k++) v[k] = 0.0;
@@ -283,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void k_lv_refine(const RansacProb* __restri
         const double e[3] = {pex[k] - me[0], pey[k] - me[1], pez[k] - me[2]}, q[3] = {pqx[k] - mq[0], pqy[k] - mq[1], pqz[k] - mq[2]};
         for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) v[3 * a + b] += e[a] * q[b];
       }
-    block_sums<9>(v, s_red);
+    block_sums<kBlock, 9>(v, s_red);
     if (tid == 0) {
       double Rn[9], tn[3], gap;
       const bool ok = horn_fit(me, mq, v, Rn, tn, &gap);
@@ -311,19 +282,19 @@ __global__ __launch_bounds__(kBlock) void k_lv_refine(const RansacProb* __restri
     size = nsize;
   }
   // the mask over query rows and the mean inlier error
-  double es[1] = {0.0};
+  double es = 0.0;
   for (int k = tid; k < n; k += kBlock) {
     const double e = lv_error(R, t, K, pex[k], pey[k], pez[k], pqx[k], pqy[k], pqz[k]);
-    if (e <= thr2) { es[0] += e; mask[(size_t)c * stride_rows + list_i[(size_t)c * stride_rows + k]] = 1; }
+    if (e <= thr2) { es += e; mask[(size_t)c * stride_rows + list_i[(size_t)c * stride_rows + k]] = 1; }
   }
-  block_sums<1>(es, s_red);
+  es = block_sum<kBlock>(es, s_red);
   if (tid == 0) {
     dvs_loop_verify_result* res = &results[c];
     res->n_inliers = size; res->success = size >= min_inliers ? 1 : 0; res->iterations = sel[4 * c + 1];
     double w[3];
     rotation_to_rodrigues(R, w);
     for (int k = 0; k < 3; k++) { res->rvec[k] = w[k]; res->tvec[k] = t[k]; }
-    res->rms_px = sqrt(es[0] / size);
+    res->rms_px = sqrt(es / size);
   }
 }
 

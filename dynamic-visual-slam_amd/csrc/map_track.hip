@@ -20,7 +20,7 @@
 #include <vector>
 #include "common.h"
 #include "device_mem.h"
-#include "block_rank.h"
+#include "block_ops.h"
 #include "backend_internal.h"
 
 namespace dvs {

@@ -11,7 +11,9 @@
 // Every SVD is a cyclic Jacobi eigen-decomposition of the (symmetric) normal matrix; cv::findHomography's Levenberg-Marquardt polish of
 // the planar initialisation is not restated (the 20 CvLevMarq iterations that follow absorb it).
 #pragma once
+#include "block_ops.h"
 #include "jacobi_eig.h"   // jacobi_eig<N>: shared with loop_verify.hip
+#include "ransac_device.h"   // RansacProb
 
 namespace dvs {
 namespace pnpcv {
@@ -498,12 +500,13 @@ __global__ __launch_bounds__(256) void k_pnpcv_score(const float* __restrict__ o
   double R[9], t[3];
   for (int k = 0; k < 9; k++) R[k] = m[6 + k];
   for (int k = 0; k < 3; k++) t[k] = m[3 + k];
+  __shared__ int s_w[4];
   int total = 0;
   for (int i0 = 0; i0 < n; i0 += 256) {
     const int i = i0 + threadIdx.x;
     bool in = false;
     if (i < n) in = pnpcv::proj_err_f(R, t, fx, fy, cx, cy, obj + 3 * i, img + 2 * i) <= thr;
-    total += block_count256(in);
+    total += block_count256(in, s_w);
   }
   if (threadIdx.x == 0) counts[h] = total;
 }
@@ -541,7 +544,7 @@ __global__ __launch_bounds__(64) void k_pnpcv_refit(const float* __restrict__ ob
     const int i = i0 + lane;
     const bool in = i < n && proj_err_f(R, t, fx, fy, cx, cy, obj + 3 * i, img + 2 * i) <= thr;
     const unsigned long long b = __ballot(in);
-    if (in) inl[count + __popcll(b & ((1ull << lane) - 1ull))] = i;
+    if (in) inl[count + lanes_below(b)] = i;
     count += __popcll(b);
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

@@ -18,6 +18,7 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
+#include "block_ops.h"
 #include "common.h"
 #include "device_mem.h"
 #ifdef DVS_TEST_HOOKS
@@ -83,31 +84,6 @@ __device__ inline void edge_residual(const double* Ri, const double* ti, const d
   const double e0 = p[0] - tz[0], e1 = p[1] - tz[1], e2 = p[2] - tz[2];
 #pragma unroll
   for (int a = 0; a < 3; a++) { r[a] = wr * om[a]; r[3 + a] = wt * (Rz[a] * e0 + Rz[3 + a] * e1 + Rz[6 + a] * e2); }
-}
-
-__device__ inline double block_sum(double v, double* sh) {   // the same value in every thread; a fixed tree
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int s = kPcgThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) sh[tid] += sh[tid + s];
-    __syncthreads();
-  }
-  const double out = sh[0];
-  __syncthreads();
-  return out;
-}
-__device__ inline double block_max(double v, double* sh) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int s = kPcgThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) sh[tid] = fmax(sh[tid], sh[tid + s]);
-    __syncthreads();
-  }
-  const double out = sh[0];
-  __syncthreads();
-  return out;
 }
 
 // u_e = A_e p_i + B_e p_j
@@ -242,8 +218,8 @@ __global__ __launch_bounds__(kPcgThreads) void k_pgo_state_reduce(PgoDev P) {
   for (int n = threadIdx.x; n < P.N; n += kPcgThreads)
     if (!P.fixed[n])
       for (int a = 0; a < 6; a++) m = fmax(m, fabs(P.g[6 * (size_t)n + a]));
-  c = block_sum(c, sh);
-  m = block_max(m, sh);
+  c = block_sum<kPcgThreads>(c, sh);
+  m = block_max<kPcgThreads>(m, sh);
   if (threadIdx.x == 0) { P.status->cur_cost = 0.5 * c; P.status->gmax = m; }
 }
 
@@ -334,7 +310,7 @@ __global__ __launch_bounds__(kPcgThreads) void k_pgo_pcg(PgoDev P, double radius
       P.r[k] = v; P.x[k] = 0; P.p[k] = 0;
       part += v * v;
     }
-  const double gnorm = sqrt(block_sum(part, sh));
+  const double gnorm = sqrt(block_sum<kPcgThreads>(part, sh));
   double rnorm = gnorm;
   int it = 0, breakdown = 0;
   if (!(rnorm <= eta * gnorm) && max_it > 0) {
@@ -343,7 +319,7 @@ __global__ __launch_bounds__(kPcgThreads) void k_pgo_pcg(PgoDev P, double radius
       part += precond_row_dot(P, n, P.r, P.z);
       for (int c = 0; c < 6; c++) P.p[6 * (size_t)n + c] = P.z[6 * (size_t)n + c];
     }
-    double rz = block_sum(part, sh);
+    double rz = block_sum<kPcgThreads>(part, sh);
     for (;;) {
       __syncthreads();   // p of every node is written
       for (int e = tid; e < P.E; e += kPcgThreads) edge_product(P, e, P.p);
@@ -354,7 +330,7 @@ __global__ __launch_bounds__(kPcgThreads) void k_pgo_pcg(PgoDev P, double radius
         node_gather(P, n, radius, P.p, y);
         for (int c = 0; c < 6; c++) { P.y[6 * (size_t)n + c] = y[c]; part += P.p[6 * (size_t)n + c] * y[c]; }
       }
-      const double pAp = block_sum(part, sh);
+      const double pAp = block_sum<kPcgThreads>(part, sh);
       if (!(pAp > 0) || !isfinite(pAp)) { breakdown = 1; break; }
       const double alpha = rz / pAp;
       part = 0;
@@ -366,12 +342,12 @@ __global__ __launch_bounds__(kPcgThreads) void k_pgo_pcg(PgoDev P, double radius
           P.r[k] = rv;
           part += rv * rv;
         }
-      rnorm = sqrt(block_sum(part, sh));
+      rnorm = sqrt(block_sum<kPcgThreads>(part, sh));
       it++;
       if (rnorm <= eta * gnorm || it >= max_it) break;
       part = 0;
       for (int n = tid; n < P.N; n += kPcgThreads) part += precond_row_dot(P, n, P.r, P.z);
-      const double rz2 = block_sum(part, sh);
+      const double rz2 = block_sum<kPcgThreads>(part, sh);
       const double beta = rz2 / rz;
       rz = rz2;
       for (int n = tid; n < P.N; n += kPcgThreads)
@@ -440,7 +416,7 @@ __global__ __launch_bounds__(256) void k_pgo_trial_edges(PgoDev P, const double*
 }
 
 __global__ __launch_bounds__(kPcgThreads) void k_pgo_trial_reduce(PgoDev P) {
-  __shared__ double sh[kPcgThreads];
+  __shared__ double sh[6 * kPcgThreads];   // 24 KB: the six sums through one tree
   double c = 0, m = 0, xg = 0, s2 = 0, x2 = 0;
   int finite = 1;
   for (int e = threadIdx.x; e < P.E; e += kPcgThreads) { c += P.ecost[e]; m += P.emodel[e]; }
@@ -448,11 +424,11 @@ __global__ __launch_bounds__(kPcgThreads) void k_pgo_trial_reduce(PgoDev P) {
     for (int a = 0; a < 6; a++) { const double xv = P.x[6 * (size_t)n + a]; xg += xv * P.g[6 * (size_t)n + a]; if (!isfinite(xv)) finite = 0; }
     s2 += P.nodePart[2 * (size_t)n]; x2 += P.nodePart[2 * (size_t)n + 1];
   }
-  c = block_sum(c, sh); m = block_sum(m, sh); xg = block_sum(xg, sh); s2 = block_sum(s2, sh); x2 = block_sum(x2, sh);
-  const double bad = block_sum(finite ? 0.0 : 1.0, sh);
+  double v[6] = {c, m, xg, s2, x2, finite ? 0.0 : 1.0};
+  block_sums<kPcgThreads, 6>(v, sh);
   if (threadIdx.x == 0) {
-    P.status->cand_cost = 0.5 * c; P.status->model_cost_change = -(xg + 0.5 * m); P.status->step2 = s2; P.status->x2 = x2;
-    P.status->finite = bad == 0.0 ? 1 : 0;
+    P.status->cand_cost = 0.5 * v[0]; P.status->model_cost_change = -(v[2] + 0.5 * v[1]); P.status->step2 = v[3]; P.status->x2 = v[4];
+    P.status->finite = v[5] == 0.0 ? 1 : 0;
   }
 }
 

@@ -24,6 +24,7 @@
 #include <string.h>
 #include <chrono>
 #include <vector>
+#include "block_ops.h"
 #include "common.h"
 #ifdef DVS_TEST_HOOKS
 #include "../../include/dvslam_hip_test.h"
@@ -31,6 +32,7 @@
 #endif
 #include "io_pinned.h"
 #include "matcher.h"
+#include "pnp_cv.h"   // cv::solvePnPRansac by OpenCV's procedure: EPnP hypotheses, float scoring, solvePnP(ITERATIVE) refit
 #include "ransac_device.h"
 #include "ransac_shared.h"
 #include "splitmix64.h"
@@ -203,15 +205,6 @@ __device__ __forceinline__ double epi_err(const double* F, double x1, double y1,
   return fmax(d1 * d1 * s1, d2 * d2 * s2);
 }
 
-__device__ __forceinline__ int block_count256(bool pred) {  // number of threads of the 256-thread block with pred
-  __shared__ int wcnt[4];
-  const unsigned long long b = __ballot(pred);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
-  return wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-}
-
 // one workgroup per hypothesis: inlier count over all correspondences
 __global__ __launch_bounds__(256) void k_f_score(const float* __restrict__ p1, const float* __restrict__ p2, const RansacProb* __restrict__ probs, int H,
                                                  const double* __restrict__ Fall, const int* __restrict__ valid, double thr2, int* __restrict__ counts, int fcmp) {
@@ -223,6 +216,7 @@ __global__ __launch_bounds__(256) void k_f_score(const float* __restrict__ p1, c
   if (!valid[h]) { if (threadIdx.x == 0) counts[h] = 0; return; }
   double F[9];
   for (int k = 0; k < 9; k++) F[k] = Fall[9 * (size_t)h + k];
+  __shared__ int s_w[4];
   int total = 0;
   for (int i0 = 0; i0 < n; i0 += 256) {
     const int i = i0 + threadIdx.x;
@@ -231,7 +225,7 @@ __global__ __launch_bounds__(256) void k_f_score(const float* __restrict__ p1, c
       const double e = epi_err(F, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]);
       in = fcmp ? (float)e <= (float)thr2 : e <= thr2;   // OpenCV stores the error and the squared threshold as floats (findInliers)
     }
-    total += block_count256(in);
+    total += block_count256(in, s_w);
   }
   if (threadIdx.x == 0) counts[h] = total;
 }
@@ -528,14 +522,8 @@ __global__ __launch_bounds__(256) void k_lmeds_select(const float* __restrict__ 
     const unsigned long long key = ((unsigned long long)__float_as_uint(med) << 32) | (unsigned)m;
     best = key < best ? key : best;
   }
-  s_best[tid] = best;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) s_best[tid] = s_best[tid + s] < s_best[tid] ? s_best[tid + s] : s_best[tid];
-    __syncthreads();
-  }
+  best = block_min<256>(best, s_best);
   if (tid != 0) return;
-  best = s_best[0];
   sel[1] = iters;
   if (best == ~0ull) { sel[0] = -1; sel[2] = 0; sel[3] = 0; for (int i = 0; i < n; i++) mask[i] = 0; for (int k = 0; k < 9; k++) Fbest[k] = 0.0; return; }
   const int bm = (int)(unsigned)best;
@@ -743,25 +731,15 @@ __global__ __launch_bounds__(256) void k_pnp_score(const float* __restrict__ obj
   if (!valid[h]) { if (threadIdx.x == 0) counts[h] = 0; return; }
   double Rt[12];
   for (int k = 0; k < 12; k++) Rt[k] = poses[12 * (size_t)h + k];
+  __shared__ int s_w[4];
   int total = 0;
   for (int i0 = 0; i0 < n; i0 += 256) {
     const int i = i0 + threadIdx.x;
     bool in = false;
     if (i < n) in = reproj_err2(Rt, Rt + 9, fx, fy, cx, cy, obj + 3 * i, img + 2 * i) <= thr2;
-    total += block_count256(in);
+    total += block_count256(in, s_w);
   }
   if (threadIdx.x == 0) counts[h] = total;
-}
-
-__device__ __forceinline__ double block_sum256(double v, double* sm) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  sm[tid] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] += sm[tid + s]; __syncthreads(); }
-  const double r = sm[0];
-  __syncthreads();
-  return r;
 }
 
 __device__ __forceinline__ void exp_so3(const double* w, double* E) {
@@ -792,7 +770,7 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
   __shared__ double sm[256];
   __shared__ double sm27[27][256];   // 54 KB: all normal-equation sums of an iteration in one reduction tree
   __shared__ double sR[9], st[3], sRn[9], stn[3], sH[36], sg[6], sd[6];
-  __shared__ int s_cnt, s_wsum[5];
+  __shared__ int s_w[4];
   __shared__ double s_lambda;
   __shared__ int s_stop;
   const int tid = threadIdx.x;
@@ -800,40 +778,32 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
   if (best < 0) { if (tid == 0) { *nin = 0; *success = 0; for (int k = 0; k < 6; k++) rt[k] = 0; } return; }
   if (tid < 9) sR[tid] = poses[12 * (size_t)best + tid];
   if (tid < 3) st[tid] = poses[12 * (size_t)best + 9 + tid];
-  if (tid == 0) { s_cnt = 0; s_lambda = 1e-3; s_stop = 0; }
+  if (tid == 0) { s_lambda = 1e-3; s_stop = 0; }
   __syncthreads();
-  // ordered inlier list (ascending index): block scans over chunks of 256
+  // ordered inlier list (ascending index): trips of 256
+  int m = 0;
   for (int i0 = 0; i0 < n; i0 += 256) {
     const int i = i0 + tid;
     const bool in = i < n && reproj_err2(sR, st, fx, fy, cx, cy, obj + 3 * i, img + 2 * i) <= thr2;
-    int incl = in ? 1 : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int tt = __shfl_up(incl, o); if ((tid & 63) >= o) incl += tt; }
-    __syncthreads();
-    if ((tid & 63) == 63) s_wsum[tid >> 6] = incl;
-    __syncthreads();
-    int base = s_cnt;
-    for (int w = 0; w < (tid >> 6); w++) base += s_wsum[w];
-    if (in) inliers[base + incl - 1] = i;
-    __syncthreads();
-    if (tid == 0) s_cnt += s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
-    __syncthreads();
+    int total;
+    const int pos = m + block_rank256(in, s_w, total);
+    if (in) inliers[pos] = i;
+    m += total;
   }
-  const int m = s_cnt;
   if (tid == 0) *nin = m;
   auto cost_of = [&](const double* R, const double* t) -> double {
     double c = 0;
     for (int e = tid; e < m; e += 256) { const int i = inliers[e]; c += fmin(reproj_err2(R, t, fx, fy, cx, cy, obj + 3 * i, img + 2 * i), 1e12); }
-    return block_sum256(c, sm);
+    return block_sum<256>(c, sm);
   };
   __threadfence_block();
   __syncthreads();
   double cost = cost_of(sR, st);
   for (int iter = 0; iter < 20 && m >= 3; iter++) {
     // normal equations of the current pose: left perturbation R <- exp(w) R, t <- t + dt
-    double H[21], g[6];
-    for (int k = 0; k < 21; k++) H[k] = 0;
-    for (int k = 0; k < 6; k++) g[k] = 0;
+    double Hg[27];   // the upper triangle of H, then g
+    double *H = Hg, *g = Hg + 21;
+    for (int k = 0; k < 27; k++) Hg[k] = 0;
     for (int e = tid; e < m; e += 256) {
       const int i = inliers[e];
       const float* X = obj + 3 * i;
@@ -856,28 +826,13 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
         g[a] += Ju[a] * du + Jv[a] * dv;
       }
     }
-    {
-      // the 27 sums through ONE tree (block_sum256's association for each, so the same bits; 27 passes of it were ~250 barriers per
-      // iteration and most of this kernel's 165 us)
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 21; k++) sm27[k][tid] = H[k];
-#pragma unroll
-      for (int a = 0; a < 6; a++) sm27[21 + a][tid] = g[a];
-      __syncthreads();
-      for (int sft = 128; sft > 0; sft >>= 1) {
-        if (tid < sft) {
-#pragma unroll
-          for (int k = 0; k < 27; k++) sm27[k][tid] += sm27[k][tid + sft];
-        }
-        __syncthreads();
-      }
-      if (tid == 0) {
-        int k = 0;
-        for (int a = 0; a < 6; a++)
-          for (int b = a; b < 6; b++) { const double v = sm27[k++][0]; sH[6 * a + b] = v; sH[6 * b + a] = v; }
-        for (int a = 0; a < 6; a++) sg[a] = sm27[21 + a][0];
-      }
+    // the 27 sums through ONE tree (27 one-wide passes were ~250 barriers per iteration and most of this kernel's 165 us)
+    block_sums<256, 27>(Hg, &sm27[0][0]);
+    if (tid == 0) {
+      int k = 0;
+      for (int a = 0; a < 6; a++)
+        for (int b = a; b < 6; b++) { const double v = H[k++]; sH[6 * a + b] = v; sH[6 * b + a] = v; }
+      for (int a = 0; a < 6; a++) sg[a] = g[a];
     }
     __syncthreads();
     bool accepted = false;
@@ -1101,10 +1056,7 @@ struct FmSubset {
   }
 };
 
-
 }  // namespace dvs
-
-#include "pnp_cv.h"   // cv::solvePnPRansac by OpenCV's procedure: EPnP hypotheses, float scoring, solvePnP(ITERATIVE) refit (needs RansacProb, block_count256)
 
 using namespace dvs;
 

@@ -25,7 +25,7 @@
 #include "motion_internal.h"
 #include "orb_device_common.h"
 #include "ransac_device.h"
-#include "block_rank.h"
+#include "block_ops.h"
 
 namespace dvs {
 

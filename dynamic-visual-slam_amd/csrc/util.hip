@@ -4,6 +4,8 @@
 #include "common.h"
 #ifdef DVS_TEST_HOOKS
 #include "../../include/dvslam_hip_test.h"
+#include "block_ops.h"
+#include "device_mem.h"
 #endif
 
 extern "C" char** environ;   // (POSIX)
@@ -124,6 +126,49 @@ StageTimer::~StageTimer() { for (int i = 0; i < npool; i++) hipEventDestroy(pool
 __global__ void k_test_spin(unsigned long long ticks) {
   const unsigned long long t0 = wall_clock64();
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
+}
+
+// test hook for block_ops.h (dvs_test_block_ops): one workgroup runs the header's functions on per-thread inputs and stores what every thread got.
+// Two trips of block_rank256 and then two of block_count256 through ONE s_w, no barrier of the kernel's own between them.
+__global__ __launch_bounds__(256) void k_test_block_rank(const uint8_t* __restrict__ flags /* [2][256] */, int* __restrict__ out /* [2][256][3] */) {
+  __shared__ int s_w[4];
+  const int tid = threadIdx.x;
+  int rank[2], total[2], count[2];
+  for (int trip = 0; trip < 2; trip++) rank[trip] = dvs::block_rank256(flags[256 * trip + tid] != 0, s_w, total[trip]);
+  for (int trip = 0; trip < 2; trip++) count[trip] = dvs::block_count256(flags[256 * trip + tid] != 0, s_w);
+  for (int trip = 0; trip < 2; trip++) {
+    int* o = out + 3 * (256 * trip + tid);
+    o[0] = rank[trip]; o[1] = total[trip]; o[2] = count[trip];
+  }
+}
+// how the second reduction's inputs depend on the first one's result
+__device__ __forceinline__ double test_mix(double a, double r) { return a + r; }
+__device__ __forceinline__ unsigned long long test_mix(unsigned long long a, unsigned long long r) { return a ^ r; }
+// out[0][k][t] = thread t's copy of the reduction of in[k][.]; out[1][k][t] = the same of test_mix(in[k][.], that result), on the same scratch
+template <int NT, int NV, typename T, typename Op>
+__global__ __launch_bounds__(NT) void k_test_block_reduce(const T* __restrict__ in /* [NV][NT] */, T* __restrict__ out /* [2][NV][NT] */) {
+  __shared__ T sm[NV * NT];
+  const int tid = threadIdx.x;
+  T v[NV];
+  for (int k = 0; k < NV; k++) v[k] = in[k * NT + tid];
+  dvs::block_reduce<NT, NV>(v, sm, Op());
+  for (int k = 0; k < NV; k++) { out[k * NT + tid] = v[k]; v[k] = test_mix(in[k * NT + tid], v[k]); }
+  dvs::block_reduce<NT, NV>(v, sm, Op());
+  for (int k = 0; k < NV; k++) out[(NV + k) * NT + tid] = v[k];
+}
+template <int NT, int NV>
+static bool launch_test_block_reduce(int op, const void* in, void* out) {
+  typedef unsigned long long u64;
+  if (op == 0) hipLaunchKernelGGL((k_test_block_reduce<NT, NV, double, dvs::OpSum>), dim3(1), dim3(NT), 0, nullptr, (const double*)in, (double*)out);
+  else if (op == 1) hipLaunchKernelGGL((k_test_block_reduce<NT, NV, double, dvs::OpFmax>), dim3(1), dim3(NT), 0, nullptr, (const double*)in, (double*)out);
+  else if (op == 2) hipLaunchKernelGGL((k_test_block_reduce<NT, NV, u64, dvs::OpMin>), dim3(1), dim3(NT), 0, nullptr, (const u64*)in, (u64*)out);
+  else return false;
+  return true;
+}
+template <int NT>
+static bool launch_test_block_reduce(int nv, int op, const void* in, void* out) {
+  return nv == 1 ? launch_test_block_reduce<NT, 1>(op, in, out) : nv == 5 ? launch_test_block_reduce<NT, 5>(op, in, out)
+       : nv == 27 ? launch_test_block_reduce<NT, 27>(op, in, out) : false;
 }
 #endif
 
@@ -258,6 +303,29 @@ dvs_status dvs_test_stream_delay(void* stream, int32_t microseconds) {
   DVS_ARG(microseconds >= 0 && microseconds <= 200000);   // bounded: 0.2 s
   hipLaunchKernelGGL(k_test_spin, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long)microseconds * 100ull);
   DVS_HIP(hipGetLastError());
+  return DVS_OK;
+}
+dvs_status dvs_test_block_ops(int32_t op, int32_t nt, int32_t nv, const void* in, void* out) {
+  DVS_ARG(in && out);
+  if (op == 3) {
+    dvs::DeviceBuf<uint8_t> din; dvs::DeviceBuf<int> dout;
+    DVS_TRY(din.upload(std::vector<uint8_t>((const uint8_t*)in, (const uint8_t*)in + 512)));
+    DVS_TRY(dout.alloc(2 * 256 * 3));
+    hipLaunchKernelGGL(k_test_block_rank, dim3(1), dim3(256), 0, nullptr, din.get(), dout.get());
+    DVS_HIP(hipGetLastError());
+    DVS_HIP(hipMemcpy(out, dout.get(), 2 * 256 * 3 * sizeof(int), hipMemcpyDeviceToHost));
+    return DVS_OK;
+  }
+  DVS_ARG((nt == 256 || nt == 512) && (nv == 1 || nv == 5 || nv == 27) && op >= 0 && op <= 2);
+  const size_t n = (size_t)nv * nt;
+  dvs::DeviceBuf<uint64_t> din, dout;
+  DVS_TRY(din.upload(std::vector<uint64_t>((const uint64_t*)in, (const uint64_t*)in + n)));
+  DVS_TRY(dout.alloc(2 * n));
+  const bool known = nt == 256 ? launch_test_block_reduce<256>(nv, op, din.get(), dout.get())
+                   : nt == 512 ? launch_test_block_reduce<512>(nv, op, din.get(), dout.get()) : false;
+  DVS_ARG(known);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipMemcpy(out, dout.get(), 2 * n * 8, hipMemcpyDeviceToHost));
   return DVS_OK;
 }
 #endif

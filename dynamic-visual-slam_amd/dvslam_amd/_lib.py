@@ -348,6 +348,8 @@ def test_lib():
     _bind_hooks(L)
     vp, i32, dbl = C.c_void_p, C.c_int32, C.c_double
     L.dvs_test_stream_delay.argtypes = [vp, i32]
+    if hasattr(L, "dvs_test_block_ops"):                # (an A/B run may load a library built before csrc/block_ops.h)
+        L.dvs_test_block_ops.argtypes = [i32, i32, i32, vp, vp]
     L.dvs_test_sort_nodes.argtypes = [vp, vp, i32, vp]; L.dvs_test_sort_nodes.restype = None
     L.dvs_test_sort_nodes_ranked.argtypes = [vp, vp, i32, vp]; L.dvs_test_sort_nodes_ranked.restype = None
     L.dvs_test_sort_nodes_device.argtypes = [vp, vp, i32, vp]; L.dvs_test_sort_nodes_device.restype = C.c_int

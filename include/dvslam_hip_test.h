@@ -55,6 +55,13 @@ dvs_status dvs_test_pnp_refine(const float* pts3d, const float* pts2d, int32_t n
                                int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3);
 /* (needs a GPU) hold `stream` for the given time with one idle wavefront (<= 200 000 us): lets a test delay an event */
 dvs_status dvs_test_stream_delay(void* stream, int32_t microseconds);
+/* (needs a GPU) csrc/block_ops.h on its own, one workgroup, every thread's results.
+ * op 0 = double +, 1 = double fmax, 2 = uint64 min: block_reduce<nt, nv> (nt 256 or 512; nv 1, 5 or 27) on in[nv][nt];
+ *   out[0][nv][nt] = every thread's copy of the results, out[1][nv][nt] = a second reduction on the same scratch whose inputs are
+ *   in + result (doubles) or in ^ result (uint64).
+ * op 3 (nt, nv unused): in = uint8 flags[2][256] -> out = int32 [2][256][3] = {rank, total, count}: block_rank256 on trip 0 and on
+ *   trip 1, then block_count256 on both, all four through one scratch with nothing in between. */
+dvs_status dvs_test_block_ops(int32_t op, int32_t nt, int32_t nv, const void* in, void* out);
 /* KeyPointsFilter::retainBest on bare responses: perm[i] = original index of the i-th survivor.  _host: csrc/lsort.h's sequential
  * restatement of std::nth_element + std::partition (no GPU); _device: the wavefront routine the cv::ORB kernels run */
 void dvs_test_retain_best_host(const float* responses, int32_t n, int32_t n_points, int32_t* perm, int32_t* n_kept);
