@@ -15,7 +15,7 @@
 // Every reduction has a fixed order, so cost / gradient are bit-reproducible run to run.
 // dvs_ba_solve: host LM around the two launches (reduced camera system <= 6K x 6K); dvs_ba_solve_device: the k_lm_* kernels.
 // Host side: the handle owns two device arenas and three pinned blocks (device_mem.h) and reaches them through ProbView / LmView, each
-// laid out by one carve(); both solvers follow one TrustRegion.
+// laid out by one carve(); the three solvers here and the pose graph's follow trust_region.h (policy and verdict on a trial step).
 #include <float.h>
 #include <math.h>
 #include <string.h>
@@ -26,6 +26,7 @@
 #include "block_ops.h"
 #include "common.h"
 #include "device_mem.h"
+#include "trust_region.h"
 
 namespace dvs {
 
@@ -1109,14 +1110,10 @@ __global__ __launch_bounds__(256) void k_lm_norms(int nparts, const double* __re
     if (tf > 0.0) st->finite = 0;
     st->model_change = -(tg + 0.5 * th);
     st->sn = a; st->xn = b; st->cand_cost = *cost;
-    // the verdict of dvs_ba_solve_device's loop, in its order and arithmetic (IEEE sqrt / divide on both sides): the launches that
-    // follow an accepted step are already enqueued behind this kernel and read it
-    int acc = 0;
-    if (st->ok && st->finite && st->model_change > 0.0 && !(sqrt(a) <= ptol * (sqrt(b) + ptol))) {
-      const double cost_change = st->x_cost - st->cand_cost;
-      if (!(fabs(cost_change) <= ftol * st->x_cost)) acc = cost_change / st->model_change > 1e-3 ? 1 : 0;
-    }
-    st->accept = acc;
+    // the verdict the host loops take from the same record (trust_region.h): the launches that follow an accepted step are already
+    // enqueued behind this kernel and read it
+    const TrialRecord rec = {st->ok && st->finite, st->model_change, st->cand_cost, a, b};
+    st->accept = trial_verdict(rec, st->x_cost, ptol, ftol).kind == kStepAccepted ? 1 : 0;
     lm_publish(st, host);
     st->ok = 1; st->finite = 1; st->model_change = 0; st->sn = 0; st->xn = 0; st->cand_cost = 0;
   }
@@ -1493,13 +1490,20 @@ struct ProbView {
   }
 };
 
-// The workspace of dvs_ba_solve_device: [tables uploaded from the host | accepted point, scaling, LM diagonal, step, per-landmark
-// inverses, scaled W, Y = W V^-1, reduced system, the tiled solver's augmented system (n + 1) x n, partial sums, status record]
-struct LmView {
-  int *obsOf, *slotCam;   // observation of (landmark, camera); camera of a slot of the reduced system
+// What both device workspaces hold around the linear solve, and what the launches the two solvers share take (lm_enqueue_trial_tail,
+// lm_epilogue): active flags, accepted point, scaling, LM diagonal, step, per-landmark inverses, scaled W, Y = W V^-1, partial sums,
+// status record.  Each workspace carves them in its own order.
+struct LmCore {
   unsigned char* active;
-  double *q0, *t0, *X0, *scale, *diag, *step, *Vinv, *Ws, *Y, *S, *rhs, *A, *lmPart, *normPart;
+  double *q0, *t0, *X0, *scale, *diag, *step, *Vinv, *Ws, *Y, *lmPart, *normPart;
   LmStatus* status;
+};
+
+// The workspace of dvs_ba_solve_device: [tables uploaded from the host | LmCore's buffers, and among them the reduced system and the
+// tiled solver's augmented system (n + 1) x n]
+struct LmView : LmCore {
+  int *obsOf, *slotCam;   // observation of (landmark, camera); camera of a slot of the reduced system
+  double *S, *rhs, *A;
   size_t uploadBytes, bytes;
   void carve(uint8_t* base, int K, int L, int R, int nc) {
     const size_t Rz = std::max(R, 1), Kz = std::max(K, 1), Lz = std::max(L, 1), NT = 6 * (size_t)K + 3 * (size_t)L, n = 6 * (size_t)nc;
@@ -1513,13 +1517,10 @@ struct LmView {
   }
 };
 
-// The workspace of dvs_ba_solve_global: what LmView holds around the linear solve, and the PCG's vectors in place of the observation
-// table, the reduced system and its splits — nothing here grows with L x K or with the square of the free cameras.
-struct GbaView {
-  unsigned char* active;
-  double *q0, *t0, *X0, *scale, *diag, *step, *Vinv, *Ws, *Y, *lmPart, *normPart;
+// The workspace of dvs_ba_solve_global: LmCore's buffers, and the PCG's vectors in place of the observation table, the reduced system
+// and its splits — nothing here grows with L x K or with the square of the free cameras.
+struct GbaView : LmCore {
   double *Minv, *b, *r, *z, *p, *qv, *u, *qpart;
-  LmStatus* status;
   PcgState* pcg;
   size_t uploadBytes, bytes;
   void carve(uint8_t* base, int K, int L, int R, int nChunks) {
@@ -1574,8 +1575,8 @@ struct dvs_ba {
   std::vector<int> pcg_iters;         // dvs_ba_get_pcg_trace: one row per trial step of the last dvs_ba_solve_global
   std::vector<double> pcg_rel;
   std::vector<double> trace;          // dvs_ba_get_trace: 6 doubles per trust-region iteration of the last solve
-  void log(double radius, int kind, double dc, double dm, double rel, double cand) {
-    const double row[6] = {radius, (double)kind, dc, dm, rel, cand};
+  void log(double radius, const StepVerdict& v, const TrialRecord& r) {
+    const double row[6] = {radius, (double)v.kind, v.cost_change, r.model_change, v.rel, v.kind == kStepInvalid ? 0.0 : r.cand_cost};
     trace.insert(trace.end(), row, row + 6);
   }
 };
@@ -1654,37 +1655,6 @@ FreeBlocks free_blocks(const dvs_ba* h) {
   for (int l = 0; l < L; l++) if (!h->lm_fixed[l] && lmUsed[l]) for (int a = 0; a < 3; a++) f.active[6 * K + 3 * l + a] = 1;
   return f;
 }
-
-// The trust-region policy both solvers follow, ceres::Solver defaults (trust_region_minimizer.cc / levenberg_marquardt_strategy.cc,
-// Ceres 2.x): initial radius 1e4; a step is accepted when its relative decrease exceeds 1e-3; radius /= max(1/3, 1 - (2 rho - 1)^3)
-// on success, /= 2, 4, 8 .. on failure; the LM diagonal is kept across a rejected step and rebuilt after any other.
-struct TrustRegion {
-  static constexpr double kMinRelativeDecrease = 1e-3;
-  double radius = 1e4, decrease_factor = 2.0;
-  bool reuse_diagonal = false;
-  int iteration = 0, invalid = 0;
-  // loop head: counts the iteration, or ends the solve (false) with summary->termination set
-  bool next(int max_iterations, double gmax, double gtol, dvs_ba_summary* summary) {
-    if (iteration >= max_iterations) { summary->termination = 1; return false; }
-    if (gmax <= gtol || radius < 1e-32) { summary->termination = 0; return false; }
-    iteration++;
-    return true;
-  }
-  bool invalid_step() {   // true: the fifth in a row, the solve has failed
-    if (++invalid >= 5) return true;
-    shrink(false);
-    return false;
-  }
-  void accepted(double rel) {
-    invalid = 0;
-    radius = radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
-    radius = std::min(1e16, radius);
-    decrease_factor = 2.0; reuse_diagonal = false;
-  }
-  void rejected() { invalid = 0; shrink(true); }
- private:
-  void shrink(bool reuse) { radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = reuse; }
-};
 
 bool chol_solve(std::vector<double>& A, int n, std::vector<double>& b, std::vector<double>* y = nullptr) {   // y: b after the forward substitution
   for (int j = 0; j < n; j++) {
@@ -1821,10 +1791,46 @@ dvs_status lm_prologue(dvs_ba* h, int& expect_seq) {
   return DVS_OK;
 }
 
-// one trial step at `radius`: system -> Cholesky -> back-substitution -> candidate -> its cost -> the record and the verdict into
-// the first host record.  refresh: rebuild the LM diagonal from the point's blocks (0: keep it, after a rejected step)
+// ---- what the two device solvers share: the end of a trial step (its camera steps are in w.step), its record, the end of a solve ----
+// back-substitution -> candidate -> its cost -> the record and the device's verdict into `host`
+dvs_status lm_enqueue_trial_tail(dvs_ba* h, const LmCore& w, double ptol, double ftol, LmStatus* host) {
+  const int K = h->K, L = h->L, nparts = (K + L + 255) / 256;
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, dev.Hll, dev.g, dev.lmStart, dev.lmObs, dev.cam,
+                     w.scale, w.active, w.Vinv, w.Ws, w.step, w.lmPart, w.status);
+  hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, w.step, w.scale, w.active,
+                     dev.q, dev.t, dev.X, w.normPart);
+  DVS_TRY(enqueue_eval(h, 0, false));  // cost of the candidate
+  hipLaunchKernelGGL(k_lm_norms, dim3(1), dim3(256), 0, st, nparts, w.normPart, dev.cost, K, L, dev.Hpp, dev.g, w.scale, w.step,
+                     w.lmPart, ptol, ftol, w.status, host);
+  return DVS_OK;
+}
+
+TrialRecord trial_record(const LmStatus& s) { return {s.ok && s.finite, s.model_change, s.cand_cost, s.sn, s.xn}; }
+
+// the accepted point becomes the problem's parameters (evaluation buffers and host mirror)
+dvs_status lm_epilogue(dvs_ba* h, const LmCore& w) {
+  const int K = h->K, L = h->L;
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob;
+  const dim3 copyGrid((std::max(4 * K, 3 * L) + 255) / 256);
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, dev.q, dev.t, dev.X, nullptr);
+  // ... the host mirror through the handle's pinned block, written by a kernel: the three device-to-host copy commands this replaces
+  // now and then blocked for 7 ms when enqueued (first solve after a warm-up, pageable or pinned destination alike)
+  double* ho = h->out();
+  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, ho, ho + 4 * (size_t)K, ho + 7 * (size_t)K, nullptr);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipStreamSynchronize(st));
+  memcpy(h->q.data(), ho, (size_t)K * 32); memcpy(h->t.data(), ho + 4 * (size_t)K, (size_t)K * 24);
+  memcpy(h->X.data(), ho + 7 * (size_t)K, (size_t)L * 24);
+  return DVS_OK;
+}
+
+// one trial step at `radius`: system -> Cholesky -> the tail above, into the first host record.  refresh: rebuild the LM diagonal from
+// the point's blocks (0: keep it, after a rejected step)
 dvs_status lm_enqueue_trial(dvs_ba* h, double radius, bool refresh, double ptol, double ftol) {
-  const int K = h->K, L = h->L, R = h->R, nc = h->lm_nc, n = 6 * nc, nparts = (K + L + 255) / 256;
+  const int K = h->K, L = h->L, R = h->R, nc = h->lm_nc, n = 6 * nc;
   hipStream_t st = h->stream;
   const ProbView& dev = h->prob;
   const LmView& w = h->work;
@@ -1838,14 +1844,7 @@ dvs_status lm_enqueue_trial(dvs_ba* h, double radius, bool refresh, double ptol,
     hipLaunchKernelGGL(k_lm_tile_assemble, dim3(n + 1), dim3(256), 0, st, K, n, w.S, w.rhs, w.A, w.step);
     enqueue_tiled_factor(st, K, n, w.slotCam, w.A, w.step, w.status);
   }
-  hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, dev.Hll, dev.g, dev.lmStart, dev.lmObs, dev.cam,
-                     w.scale, w.active, w.Vinv, w.Ws, w.step, w.lmPart, w.status);
-  hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, w.step, w.scale, w.active,
-                     dev.q, dev.t, dev.X, w.normPart);
-  DVS_TRY(enqueue_eval(h, 0, false));  // cost of the candidate
-  hipLaunchKernelGGL(k_lm_norms, dim3(1), dim3(256), 0, st, nparts, w.normPart, dev.cost, K, L, dev.Hpp, dev.g, w.scale, w.step,
-                     w.lmPart, ptol, ftol, w.status, h->status());
-  return DVS_OK;
+  return lm_enqueue_trial_tail(h, w, ptol, ftol, h->status());
 }
 
 }  // namespace
@@ -2083,16 +2082,16 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
     for (int l = 0; l < L; l++) if (active[6 * K + 3 * l]) for (int i = 0; i < 3; i++) m = std::max(m, fabs(g[6 * K + 3 * l + i]));
     return m;
   };
-  auto x_norm = [&]() {
+  auto x_norm2 = [&]() {
     double s = 0;
     for (int c = 0; c < K; c++) if (camSlot[c] >= 0) { for (int i = 0; i < 4; i++) s += q[4 * c + i] * q[4 * c + i]; for (int i = 0; i < 3; i++) s += t[3 * c + i] * t[3 * c + i]; }
     for (int l = 0; l < L; l++) if (active[6 * K + 3 * l]) for (int i = 0; i < 3; i++) s += X[3 * l + i] * X[3 * l + i];
-    return sqrt(s);
+    return s;
   };
 
   double gmax = grad_max_norm();
   TrustRegion tr;
-  while (tr.next(max_iterations, gmax, gtol, summary)) {
+  while (go_on(tr.next(max_iterations, gmax, gtol), &summary->termination)) {
     const double radius = tr.radius;
     if (!tr.reuse_diagonal) {
       for (int c = 0; c < K; c++) for (int a = 0; a < 6; a++) { const int j = 6 * c + a; diagonal[j] = std::min(std::max(Hpp[36 * (size_t)c + 7 * a] * scale[j] * scale[j], 1e-6), 1e32); }
@@ -2168,48 +2167,39 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
         for (int l = 0; l < L; l++) { const int j0 = 6 * K + 3 * l; for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) sHs += step[j0 + a] * scale[j0 + a] * Hll[9 * (size_t)l + 3 * a + b] * scale[j0 + b] * step[j0 + b]; }
         for (int p = 0; p < R; p++) { const int c = h->cam[p], j0 = 6 * K + 3 * h->lm[p]; for (int a = 0; a < 6; a++) for (int b = 0; b < 3; b++) sHs += 2.0 * step[6 * c + a] * scale[6 * c + a] * W[18 * (size_t)p + 3 * a + b] * scale[j0 + b] * step[j0 + b]; }
         model_cost_change = -(sg + 0.5 * sHs);
-        if (model_cost_change <= 0.0) valid = false;
+        if (!(model_cost_change > 0.0)) valid = false;
       }
     }
-    if (!valid) {
-      h->log(radius, 0, 0, model_cost_change, 0, 0);
-      if (tr.invalid_step()) { summary->termination = 2; break; }
-      continue;
+    TrialRecord rec = {valid, model_cost_change, 0.0, 0.0, 0.0};
+    std::vector<double> cq, ct, cX;
+    if (valid) {   // the candidate, its cost and the step's norm
+      cq = q; ct = t; cX = X;
+      for (int c = 0; c < K; c++) if (camSlot[c] >= 0) {
+        const double d[3] = {step[6 * c] * scale[6 * c], step[6 * c + 1] * scale[6 * c + 1], step[6 * c + 2] * scale[6 * c + 2]};
+        quat_plus(&q[4 * c], d, &cq[4 * c]);
+        for (int i = 0; i < 3; i++) ct[3 * c + i] = t[3 * c + i] + step[6 * c + 3 + i] * scale[6 * c + 3 + i];
+      }
+      for (int l = 0; l < L; l++) if (active[6 * K + 3 * l]) for (int i = 0; i < 3; i++) cX[3 * l + i] = X[3 * l + i] + step[6 * K + 3 * l + i] * scale[6 * K + 3 * l + i];
+      DVS_TRY(upload_params(h, cq, ct, cX));
+      DVS_TRY(enqueue_eval(h, 0, false));  // cost only
+      DVS_HIP(hipMemcpyAsync(&rec.cand_cost, dev.cost, 8, hipMemcpyDeviceToHost, h->stream));
+      DVS_HIP(hipStreamSynchronize(h->stream));
+      double& sn = rec.sn;
+      for (int c = 0; c < K; c++) if (camSlot[c] >= 0) { for (int i = 0; i < 4; i++) sn += (q[4 * c + i] - cq[4 * c + i]) * (q[4 * c + i] - cq[4 * c + i]); for (int i = 0; i < 3; i++) sn += (t[3 * c + i] - ct[3 * c + i]) * (t[3 * c + i] - ct[3 * c + i]); }
+      for (int l = 0; l < L; l++) if (active[6 * K + 3 * l]) for (int i = 0; i < 3; i++) sn += (X[3 * l + i] - cX[3 * l + i]) * (X[3 * l + i] - cX[3 * l + i]);
+      rec.xn = x_norm2();
     }
-    std::vector<double> cq = q, ct = t, cX = X;
-    for (int c = 0; c < K; c++) if (camSlot[c] >= 0) {
-      const double d[3] = {step[6 * c] * scale[6 * c], step[6 * c + 1] * scale[6 * c + 1], step[6 * c + 2] * scale[6 * c + 2]};
-      quat_plus(&q[4 * c], d, &cq[4 * c]);
-      for (int i = 0; i < 3; i++) ct[3 * c + i] = t[3 * c + i] + step[6 * c + 3 + i] * scale[6 * c + 3 + i];
-    }
-    for (int l = 0; l < L; l++) if (active[6 * K + 3 * l]) for (int i = 0; i < 3; i++) cX[3 * l + i] = X[3 * l + i] + step[6 * K + 3 * l + i] * scale[6 * K + 3 * l + i];
-    DVS_TRY(upload_params(h, cq, ct, cX));
-    DVS_TRY(enqueue_eval(h, 0, false));  // cost only
-    double cand_cost = 0;
-    DVS_HIP(hipMemcpyAsync(&cand_cost, dev.cost, 8, hipMemcpyDeviceToHost, h->stream));
-    DVS_HIP(hipStreamSynchronize(h->stream));
-    double sn = 0;
-    for (int c = 0; c < K; c++) if (camSlot[c] >= 0) { for (int i = 0; i < 4; i++) sn += (q[4 * c + i] - cq[4 * c + i]) * (q[4 * c + i] - cq[4 * c + i]); for (int i = 0; i < 3; i++) sn += (t[3 * c + i] - ct[3 * c + i]) * (t[3 * c + i] - ct[3 * c + i]); }
-    for (int l = 0; l < L; l++) if (active[6 * K + 3 * l]) for (int i = 0; i < 3; i++) sn += (X[3 * l + i] - cX[3 * l + i]) * (X[3 * l + i] - cX[3 * l + i]);
-    if (sqrt(sn) <= ptol * (x_norm() + ptol)) { h->log(radius, 3, x_cost - cand_cost, model_cost_change, 0, cand_cost); summary->termination = 0; break; }
-    const double cost_change = x_cost - cand_cost;
-    if (fabs(cost_change) <= ftol * x_cost) { h->log(radius, 4, cost_change, model_cost_change, 0, cand_cost); summary->termination = 0; break; }
-    const double rel = cost_change / model_cost_change;
-    const bool accept = rel > TrustRegion::kMinRelativeDecrease;
-    h->log(radius, accept ? 1 : 2, cost_change, model_cost_change, rel, cand_cost);
-    if (accept) {
+    const StepVerdict v = verdict_host_decides(rec, x_cost, ptol, ftol);
+    h->log(radius, v, rec);
+    if (!go_on(tr.update(v), &summary->termination)) break;
+    if (v.kind == kStepAccepted) {
       q = cq; t = ct; X = cX;
       DVS_TRY(evaluate_full());  // parameters on the device already are the candidate
       gmax = grad_max_norm();
-      summary->num_successful_steps++;
-      min_cost = std::min(min_cost, x_cost);
-      tr.accepted(rel);
-    } else {
-      tr.rejected();
+      summary->num_successful_steps++; min_cost = std::min(min_cost, x_cost);
     }
   }
-  summary->num_iterations = tr.iteration;
-  summary->final_cost = min_cost;
+  summary->num_iterations = tr.iteration; summary->final_cost = min_cost;
   h->q = q; h->t = t; h->X = X;
   DVS_TRY(upload_params(h, q, t, X));
   DVS_HIP(hipStreamSynchronize(h->stream));
@@ -2224,80 +2214,46 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
   summary->termination = 2;
   summary->linear_solver = 1;   // linear algebra on the DEVICE
   DVS_HIP(hipSetDevice(h->device));
-  const int K = h->K, L = h->L, R = h->R;
-  if (R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
-  hipStream_t st = h->stream;
-  const ProbView& dev = h->prob;
-  LmView& w = h->work;
+  if (h->R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
   DVS_TRY(lm_plan(h));
   h->lm_stepping = false;   // the step hook of the test library starts over from the problem's point
   h->trace.clear();
   // two host records: the gated k_lm_gmax of an accepted step runs while the host may still be reading the trial's numbers, so it
   // must not publish over them
-  LmStatus* S = h->status();
-  LmStatus* SP = S + 1;
+  LmStatus *S = h->status(), *SP = S + 1;
   int expect_seq = 0;
   // The launches that follow an accepted step (accept, full evaluation, gradient norm: ~27 us of host launch time) are enqueued right
   // behind the trial, gated on the verdict k_lm_norms leaves in the status record, so that they are ready when the trial ends; the
-  // host takes the same decision from the same numbers.  Should the two ever differ (a last-bit difference between the host's and the
-  // device's sqrt / pow in a tolerance test), the DEVICE's verdict stands — it has already been applied to the buffers.
-  const int* verdict = &w.status->accept;
+  // host takes the same decision from the same numbers, and where it would not, the device's stands (verdict_device_accept_applied).
+  const int* verdict = &h->work.status->accept;
   const bool speculate = h->lm_speculate;
   DVS_TRY(lm_prologue(h, expect_seq));
   double x_cost = SP->x_cost, gmax = SP->gmax;
   summary->initial_cost = x_cost;
   double min_cost = x_cost;
-  const dim3 copyGrid((std::max(4 * K, 3 * L) + 255) / 256);
 
   TrustRegion tr;
-  while (tr.next(max_iterations, gmax, gtol, summary)) {
+  while (go_on(tr.next(max_iterations, gmax, gtol), &summary->termination)) {
     const double radius = tr.radius;
     DVS_TRY(lm_enqueue_trial(h, radius, !tr.reuse_diagonal, ptol, ftol));
     if (speculate) DVS_TRY(lm_enqueue_full(h, verdict, true));
     DVS_HIP(hipGetLastError());
     DVS_TRY(lm_fetch_status(h, S, expect_seq));
-    const bool valid = S->ok && S->finite && S->model_change > 0.0;
-    const bool dev_accept = speculate && S->accept != 0;   // the gated launches ran: the candidate IS the point of the next iteration
-    if (!valid && !dev_accept) {
-      h->log(radius, 0, 0, S->model_change, 0, 0);
-      if (tr.invalid_step()) { summary->termination = 2; break; }
-      continue;
-    }
-    const double cost_change = x_cost - S->cand_cost;
-    if (!dev_accept) {
-      if (sqrt(S->sn) <= ptol * (sqrt(S->xn) + ptol)) { h->log(radius, 3, cost_change, S->model_change, 0, S->cand_cost); summary->termination = 0; break; }
-      if (fabs(cost_change) <= ftol * x_cost) { h->log(radius, 4, cost_change, S->model_change, 0, S->cand_cost); summary->termination = 0; break; }
-    }
-    const double rel = cost_change / S->model_change;
-    const bool accept = speculate ? dev_accept : rel > TrustRegion::kMinRelativeDecrease;
-    h->log(radius, accept ? 1 : 2, cost_change, S->model_change, rel, S->cand_cost);
-    if (accept) {
-      if (speculate) {
-        DVS_TRY(lm_fetch_status(h, SP, expect_seq));       // the gated launches ran: wait for k_lm_gmax's record
-      } else {
-        DVS_TRY(lm_enqueue_full(h, nullptr, true));
-        DVS_TRY(lm_fetch_status(h, SP, expect_seq));
-      }
+    const TrialRecord rec = trial_record(*S);
+    // speculating, the gated launches ran on the device's accept: the candidate IS the point of the next iteration
+    const StepVerdict v = speculate ? verdict_device_accept_applied(rec, S->accept != 0, x_cost, ptol, ftol)
+                                    : verdict_host_decides(rec, x_cost, ptol, ftol);
+    h->log(radius, v, rec);
+    if (!go_on(tr.update(v), &summary->termination)) break;
+    if (v.kind == kStepAccepted) {
+      if (!speculate) DVS_TRY(lm_enqueue_full(h, nullptr, true));
+      DVS_TRY(lm_fetch_status(h, SP, expect_seq));       // k_lm_gmax's record
       x_cost = SP->x_cost; gmax = SP->gmax;
-      summary->num_successful_steps++;
-      min_cost = std::min(min_cost, x_cost);
-      tr.accepted(rel);
-    } else {
-      tr.rejected();
+      summary->num_successful_steps++; min_cost = std::min(min_cost, x_cost);
     }
   }
-  summary->num_iterations = tr.iteration;
-  summary->final_cost = min_cost;
-  // the accepted point becomes the problem's parameters (host mirror and evaluation buffers)
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, dev.q, dev.t, dev.X, nullptr);
-  // ... the host mirror through the handle's pinned block, written by a kernel: the three device-to-host copy commands this replaces
-  // now and then blocked for 7 ms when enqueued (first solve after a warm-up, pageable or pinned destination alike)
-  double* ho = h->out();
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, ho, ho + 4 * (size_t)K, ho + 7 * (size_t)K, nullptr);
-  DVS_HIP(hipStreamSynchronize(st));
-  memcpy(h->q.data(), ho, (size_t)K * 32); memcpy(h->t.data(), ho + 4 * (size_t)K, (size_t)K * 24);
-  memcpy(h->X.data(), ho + 7 * (size_t)K, (size_t)L * 24);
-  return DVS_OK;
+  summary->num_iterations = tr.iteration; summary->final_cost = min_cost;
+  return lm_epilogue(h, h->work);
 }
 
 namespace {
@@ -2332,8 +2288,7 @@ dvs_status gba_prepare(dvs_ba* h) {
 }
 
 GbaDev gba_view(const dvs_ba* h) {
-  const ProbView& dev = h->prob;
-  const GbaView& w = h->gwork;
+  const ProbView& dev = h->prob; const GbaView& w = h->gwork;
   GbaDev G;
   G.K = h->K; G.L = h->L;
   G.chunks = dev.chunks; G.camChunkStart = dev.camChunkStart; G.cam = dev.cam; G.lm = dev.lm; G.lmStart = dev.lmStart; G.lmObs = dev.lmObs;
@@ -2343,14 +2298,71 @@ GbaDev gba_view(const dvs_ba* h) {
   return G;
 }
 
-// the launches of `count` PCG iterations; the last one publishes the record to `host`
-void enqueue_pcg(const dvs_ba* h, const GbaDev& G, int count, double radius, double eta, int max_it, PcgState* host) {
-  for (int i = 0; i < count; i++) {
-    hipLaunchKernelGGL(k_gba_lm, dim3((4 * h->L + 255) / 256), dim3(256), 0, h->stream, G);
-    hipLaunchKernelGGL(k_gba_cam, dim3(h->nChunks), dim3(256), 0, h->stream, G);
-    hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, h->stream, G, 1, radius, eta, max_it, i + 1 == count ? host : nullptr);
-  }
+// the pinned records: [0] the trial's (k_lm_norms), [1] the point's (k_lm_gmax), then the PCG's
+LmStatus* gba_status(const dvs_ba* h) { return (LmStatus*)h->pcg_buf.get(); }
+PcgState* gba_pcg_record(const dvs_ba* h) { return (PcgState*)(gba_status(h) + 2); }
+int gba_max_pcg(const dvs_ba* h, int asked) { return asked > 0 ? asked : std::max(100, 12 * h->gba_nc); }
+
+// ---- the launches of dvs_ba_solve_global, in the pieces its loop is made of (the hooks of the test library call the same) ----
+// Jacobian blocks, gradient, cost of the point in the evaluation buffers, its record (gradient max-norm, cost) read into the second
+// host record; accept: the buffers hold a candidate that becomes the point
+dvs_status gba_evaluate_full(dvs_ba* h, bool accept) {
+  const int K = h->K, L = h->L;
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob; const GbaView& w = h->gwork;
+  if (accept) hipLaunchKernelGGL(k_lm_accept, dim3((std::max(4 * K, 3 * L) + 255) / 256), dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
+  DVS_TRY(enqueue_eval(h, 1 | 2, true));
+  hipLaunchKernelGGL(k_lm_gmax, dim3(1), dim3(256), 0, st, K, L, w.q0, dev.g, w.active, dev.cost, w.status, gba_status(h) + 1, nullptr);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipStreamSynchronize(st));
+  return DVS_OK;
 }
+
+// what precedes the first trial step: the problem's parameters become the point, its blocks, cost and gradient norm, the Jacobi scaling
+dvs_status gba_prologue(dvs_ba* h) {
+  const int K = h->K, L = h->L, NT = 6 * K + 3 * L;
+  hipStream_t st = h->stream;
+  const ProbView& dev = h->prob; const GbaView& w = h->gwork;
+  DVS_TRY(upload_params(h, h->q, h->t, h->X));
+  hipLaunchKernelGGL(k_lm_accept, dim3((std::max(4 * K, 3 * L) + 255) / 256), dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
+  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
+  DVS_TRY(gba_evaluate_full(h, false));
+  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
+  return DVS_OK;
+}
+
+// the system of a trial step at `radius`: observation blocks and preconditioner.  refresh: as lm_enqueue_trial's
+void gba_enqueue_system(dvs_ba* h, const GbaDev& G, double radius, bool refresh) {
+  const int K = h->K, L = h->L, R = h->R;
+  const ProbView& dev = h->prob; const GbaView& w = h->gwork;
+  hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, h->stream, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam,
+                     dev.lm, dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, refresh ? 1 : 0, w.Vinv, w.Ws, w.Y, w.status);
+  hipLaunchKernelGGL(k_gba_precond, dim3((K + 3) / 4), dim3(256), 0, h->stream, G, radius);
+}
+
+// the linear solve of a trial step, the camera steps into w.step: the system, the PCG's first residual, then its iterations (three
+// launches each) in batches of 4, 8, 16, 32, 32, ..; the launches past the stopping iteration return at once.  *end: the PCG's record
+dvs_status gba_linear_solve(dvs_ba* h, const GbaDev& G, double radius, bool refresh, double eta, int max_pcg, PcgState* end) {
+  hipStream_t st = h->stream;
+  PcgState* host = gba_pcg_record(h);
+  gba_enqueue_system(h, G, radius, refresh);
+  hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, st, G, 0, radius, eta, max_pcg, nullptr);
+  for (int batch = 4, enq = 0;; batch = std::min(2 * batch, 32)) {
+    for (int i = 0; i < batch; i++) {   // the last one publishes the record
+      hipLaunchKernelGGL(k_gba_lm, dim3((4 * h->L + 255) / 256), dim3(256), 0, st, G);
+      hipLaunchKernelGGL(k_gba_cam, dim3(h->nChunks), dim3(256), 0, st, G);
+      hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, st, G, 1, radius, eta, max_pcg, i + 1 == batch ? host : nullptr);
+    }
+    enq += batch;
+    DVS_HIP(hipGetLastError());
+    DVS_HIP(hipStreamSynchronize(st));
+    if (host->done) break;
+    if (enq > max_pcg + 32) { set_error("global BA: the PCG record never reported the end of the solve"); return DVS_ERR_HIP; }
+  }
+  *end = *host;
+  return DVS_OK;
+}
+double pcg_rel_residual(const PcgState& s) { return s.bnorm2 > 0.0 ? sqrt(s.rnorm2) / sqrt(s.bnorm2) : 0.0; }
 
 }  // namespace
 
@@ -2388,123 +2400,58 @@ dvs_status dvs_ba_solve_global(dvs_ba* h, const dvs_ba_global_params* params, dv
   DVS_ARG(prm.function_tolerance >= 0.0 && prm.gradient_tolerance >= 0.0 && prm.parameter_tolerance >= 0.0);
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(gba_prepare(h));
-  const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
   const double ftol = prm.function_tolerance, gtol = prm.gradient_tolerance, ptol = prm.parameter_tolerance, eta = prm.eta;
-  const int max_pcg = prm.max_pcg_iterations > 0 ? prm.max_pcg_iterations : std::max(100, 12 * h->gba_nc);
-  hipStream_t st = h->stream;
-  const ProbView& dev = h->prob;
-  GbaView& w = h->gwork;
+  const int max_pcg = gba_max_pcg(h, prm.max_pcg_iterations);
   const GbaDev G = gba_view(h);
+  LmStatus *S = gba_status(h), *SP = S + 1;
   h->trace.clear(); h->pcg_iters.clear(); h->pcg_rel.clear();
-  DVS_TRY(upload_params(h, h->q, h->t, h->X));
-  const dim3 copyGrid((std::max(4 * K, 3 * L) + 255) / 256);
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
-  LmStatus* S = (LmStatus*)h->pcg_buf.get();   // [0]: the trial's record (k_lm_norms), [1]: the point's (k_lm_gmax), then the PCG's
-  LmStatus* SP = S + 1;
-  PcgState* PH = (PcgState*)(S + 2);
-  // Jacobian blocks, gradient, cost of the point in the evaluation buffers; accept: they hold a candidate that becomes the point
-  auto evaluate_full = [&](bool accept) -> dvs_status {
-    if (accept) hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, dev.q, dev.t, dev.X, w.q0, w.t0, w.X0, nullptr);
-    DVS_TRY(enqueue_eval(h, 1 | 2, true));
-    hipLaunchKernelGGL(k_lm_gmax, dim3(1), dim3(256), 0, st, K, L, w.q0, dev.g, w.active, dev.cost, w.status, SP, nullptr);
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipStreamSynchronize(st));
-    return DVS_OK;
-  };
-  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
-  DVS_TRY(evaluate_full(false));
+  DVS_TRY(gba_prologue(h));
   double x_cost = SP->x_cost, gmax = SP->gmax;
   summary->initial_cost = x_cost;
   double min_cost = x_cost;
-  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
 
-  const int nparts = (K + L + 255) / 256;
   TrustRegion tr;
-  while (tr.next(prm.max_iterations, gmax, gtol, summary)) {
+  while (go_on(tr.next(prm.max_iterations, gmax, gtol), &summary->termination)) {
     const double radius = tr.radius;
-    hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
-                       dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, tr.reuse_diagonal ? 0 : 1, w.Vinv, w.Ws, w.Y,
-                       w.status);
-    hipLaunchKernelGGL(k_gba_precond, dim3((K + 3) / 4), dim3(256), 0, st, G, radius);
-    hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, st, G, 0, radius, eta, max_pcg, nullptr);
-    // batches of 4, 8, 16, 32, 32, .. iterations: the launches past the stopping iteration return at once
-    for (int batch = 4, enq = 0;; batch = std::min(2 * batch, 32)) {
-      enqueue_pcg(h, G, batch, radius, eta, max_pcg, PH);
-      enq += batch;
-      DVS_HIP(hipGetLastError());
-      DVS_HIP(hipStreamSynchronize(st));
-      if (PH->done) break;
-      if (enq > max_pcg + 32) { set_error("dvs_ba_solve_global: the PCG record never reported the end of the solve"); return DVS_ERR_HIP; }
-    }
-    out->pcg_iterations += PH->iter;
-    h->pcg_iters.push_back(PH->iter);
-    h->pcg_rel.push_back(PH->bnorm2 > 0.0 ? sqrt(PH->rnorm2) / sqrt(PH->bnorm2) : 0.0);
-    hipLaunchKernelGGL(k_lm_backsub, dim3((4 * L + 255) / 256), dim3(256), 0, st, K, L, dev.Hll, dev.g, dev.lmStart, dev.lmObs, dev.cam,
-                       w.scale, w.active, w.Vinv, w.Ws, w.step, w.lmPart, w.status);
-    hipLaunchKernelGGL(k_lm_candidate, dim3(nparts), dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, w.step, w.scale, w.active,
-                       dev.q, dev.t, dev.X, w.normPart);
-    DVS_TRY(enqueue_eval(h, 0, false));  // cost of the candidate
-    hipLaunchKernelGGL(k_lm_norms, dim3(1), dim3(256), 0, st, nparts, w.normPart, dev.cost, K, L, dev.Hpp, dev.g, w.scale, w.step,
-                       w.lmPart, ptol, ftol, w.status, S);
+    PcgState pcg;
+    DVS_TRY(gba_linear_solve(h, G, radius, !tr.reuse_diagonal, eta, max_pcg, &pcg));
+    out->pcg_iterations += pcg.iter;
+    h->pcg_iters.push_back(pcg.iter);
+    h->pcg_rel.push_back(pcg_rel_residual(pcg));
+    DVS_TRY(lm_enqueue_trial_tail(h, h->gwork, ptol, ftol, S));
     DVS_HIP(hipGetLastError());
-    DVS_HIP(hipStreamSynchronize(st));
-    const bool valid = S->ok && S->finite && S->model_change > 0.0;
-    if (!valid) {
-      h->log(radius, 0, 0, S->model_change, 0, 0);
-      if (tr.invalid_step()) { summary->termination = 2; break; }
-      continue;
-    }
-    const double cost_change = x_cost - S->cand_cost;
-    if (sqrt(S->sn) <= ptol * (sqrt(S->xn) + ptol)) { h->log(radius, 3, cost_change, S->model_change, 0, S->cand_cost); summary->termination = 0; break; }
-    if (fabs(cost_change) <= ftol * x_cost) { h->log(radius, 4, cost_change, S->model_change, 0, S->cand_cost); summary->termination = 0; break; }
-    const double rel = cost_change / S->model_change;
-    const bool accept = S->accept != 0;   // the device's verdict, from the same numbers (k_lm_norms)
-    h->log(radius, accept ? 1 : 2, cost_change, S->model_change, rel, S->cand_cost);
-    if (accept) {
-      DVS_TRY(evaluate_full(true));
+    DVS_HIP(hipStreamSynchronize(h->stream));
+    const TrialRecord rec = trial_record(*S);
+    // the host's own validity and tolerance tests, then the device's verdict (k_lm_norms, the same numbers) for the relative decrease
+    const StepVerdict v = verdict_device_decides_decrease(rec, S->accept != 0, x_cost, ptol, ftol);
+    h->log(radius, v, rec);
+    if (!go_on(tr.update(v), &summary->termination)) break;
+    if (v.kind == kStepAccepted) {
+      DVS_TRY(gba_evaluate_full(h, true));
       x_cost = SP->x_cost; gmax = SP->gmax;
-      summary->num_successful_steps++;
-      min_cost = std::min(min_cost, x_cost);
-      tr.accepted(rel);
-    } else {
-      tr.rejected();
+      summary->num_successful_steps++; min_cost = std::min(min_cost, x_cost);
     }
   }
-  summary->num_iterations = tr.iteration;
-  summary->final_cost = min_cost;
-  // the accepted point becomes the problem's parameters (evaluation buffers and, through the pinned block, the host mirror)
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, dev.q, dev.t, dev.X, nullptr);
-  double* ho = h->out();
-  hipLaunchKernelGGL(k_lm_accept, copyGrid, dim3(256), 0, st, K, L, w.q0, w.t0, w.X0, ho, ho + 4 * (size_t)K, ho + 7 * (size_t)K, nullptr);
-  DVS_HIP(hipGetLastError());
-  DVS_HIP(hipStreamSynchronize(st));
-  memcpy(h->q.data(), ho, (size_t)K * 32); memcpy(h->t.data(), ho + 4 * (size_t)K, (size_t)K * 24);
-  memcpy(h->X.data(), ho + 7 * (size_t)K, (size_t)L * 24);
-  return DVS_OK;
+  summary->num_iterations = tr.iteration; summary->final_cost = min_cost;
+  return lm_epilogue(h, h->gwork);
 }
 
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test_ba.h)
 // S x, the preconditioner blocks and b of dvs_ba_solve_global's linear solve at the problem's current point and the given radius,
-// through the kernels the solve runs
+// through gba_prologue / gba_enqueue_system and the kernels of one PCG iteration
 dvs_status dvs_ba_schur_probe(dvs_ba* h, double radius, const double* x_in, double* y_out, double* Minv_out, double* b_out) {
   DVS_ARG(h && x_in && y_out && Minv_out && b_out && radius > 0.0);
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(gba_prepare(h));
-  const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
+  const int K = h->K, L = h->L;
   hipStream_t st = h->stream;
-  const ProbView& dev = h->prob;
-  GbaView& w = h->gwork;
+  const GbaView& w = h->gwork;
   const GbaDev G = gba_view(h);
-  DVS_TRY(upload_params(h, h->q, h->t, h->X));
   std::vector<double> p(x_in, x_in + 6 * (size_t)K);
   for (int c = 0; c < K; c++) if (h->pose_fixed[c]) for (int a = 0; a < 6; a++) p[6 * (size_t)c + a] = 0.0;
+  DVS_TRY(gba_prologue(h));
+  gba_enqueue_system(h, G, radius, true);
   DVS_HIP(hipMemcpyAsync(w.p, p.data(), p.size() * 8, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
-  DVS_TRY(enqueue_eval(h, 1 | 2, true));
-  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
-  hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
-                     dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, 1, w.Vinv, w.Ws, w.Y, w.status);
-  hipLaunchKernelGGL(k_gba_precond, dim3((K + 3) / 4), dim3(256), 0, st, G, radius);
   DVS_HIP(hipMemsetAsync(w.pcg, 0, sizeof(PcgState), st));   // done = 0: the passes run
   hipLaunchKernelGGL(k_gba_lm, dim3((4 * L + 255) / 256), dim3(256), 0, st, G);
   hipLaunchKernelGGL(k_gba_cam, dim3(h->nChunks), dim3(256), 0, st, G);
@@ -2516,41 +2463,22 @@ dvs_status dvs_ba_schur_probe(dvs_ba* h, double radius, const double* x_in, doub
   DVS_HIP(hipMemcpy(b_out, w.b, (size_t)K * 6 * 8, hipMemcpyDeviceToHost));
   return DVS_OK;
 }
-// one linear solve at the problem's current point, as a trial step of dvs_ba_solve_global enqueues it: the PCG's x (scaled, as solved),
-// the iterations run and the recurrence's |r| / |b|; *ok = 0 when the solve stopped before its first iteration
+// one linear solve at the problem's current point, through gba_prologue / gba_linear_solve as a trial step of dvs_ba_solve_global
+// runs them: the PCG's x (scaled, as solved), the iterations run and the recurrence's |r| / |b|; *ok = 0 when the solve stopped before
+// its first iteration
 dvs_status dvs_ba_pcg_probe(dvs_ba* h, double radius, double eta, int32_t max_pcg_iterations, double* x_out, int32_t* iterations,
                             double* rel_residual, int32_t* ok) {
   DVS_ARG(h && x_out && iterations && rel_residual && ok && radius > 0.0 && eta > 0.0 && eta < 1.0 && max_pcg_iterations >= 0);
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(gba_prepare(h));
-  const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
-  const int max_pcg = max_pcg_iterations > 0 ? max_pcg_iterations : std::max(100, 12 * h->gba_nc);
-  hipStream_t st = h->stream;
-  const ProbView& dev = h->prob;
-  GbaView& w = h->gwork;
-  const GbaDev G = gba_view(h);
-  PcgState* PH = (PcgState*)((LmStatus*)h->pcg_buf.get() + 2);
-  DVS_TRY(upload_params(h, h->q, h->t, h->X));
-  hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, st, w.status);
-  DVS_TRY(enqueue_eval(h, 1 | 2, true));
-  hipLaunchKernelGGL(k_lm_scale, dim3((NT + 255) / 256), dim3(256), 0, st, K, L, dev.Hpp, dev.Hll, w.scale);
-  hipLaunchKernelGGL(k_lm_observations, dim3((R + L + K + 255) / 256), dim3(256), 0, st, K, L, R, dev.Hpp, dev.Hll, dev.W, dev.cam, dev.lm,
-                     dev.lmStart, dev.lmObs, w.scale, w.diag, w.active, radius, 1, w.Vinv, w.Ws, w.Y, w.status);
-  hipLaunchKernelGGL(k_gba_precond, dim3((K + 3) / 4), dim3(256), 0, st, G, radius);
-  hipLaunchKernelGGL(k_gba_update, dim3(1), dim3(256), 0, st, G, 0, radius, eta, max_pcg, nullptr);
-  for (int batch = 4, enq = 0;; batch = std::min(2 * batch, 32)) {
-    enqueue_pcg(h, G, batch, radius, eta, max_pcg, PH);
-    enq += batch;
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipStreamSynchronize(st));
-    if (PH->done) break;
-    if (enq > max_pcg + 32) { set_error("dvs_ba_pcg_probe: the PCG record never reported the end of the solve"); return DVS_ERR_HIP; }
-  }
-  *iterations = PH->iter; *ok = PH->ok;
-  *rel_residual = PH->bnorm2 > 0.0 ? sqrt(PH->rnorm2) / sqrt(PH->bnorm2) : 0.0;
-  DVS_HIP(hipMemcpy(x_out, w.step, (size_t)K * 6 * 8, hipMemcpyDeviceToHost));
+  DVS_TRY(gba_prologue(h));
+  PcgState pcg;
+  DVS_TRY(gba_linear_solve(h, gba_view(h), radius, true, eta, gba_max_pcg(h, max_pcg_iterations), &pcg));
+  *iterations = pcg.iter; *ok = pcg.ok; *rel_residual = pcg_rel_residual(pcg);
+  DVS_HIP(hipMemcpy(x_out, h->gwork.step, (size_t)h->K * 6 * 8, hipMemcpyDeviceToHost));
   return DVS_OK;
 }
+
 // one trial step of dvs_ba_solve_device at the caller's radius, through lm_prologue / lm_enqueue_trial / lm_enqueue_full as the loop
 // enqueues them, and what it left in the workspace
 dvs_status dvs_ba_step_probe(dvs_ba* h, double radius, int32_t refresh, int32_t commit, double ftol, double ptol, double* scale_out,
@@ -2626,6 +2554,27 @@ dvs_status dvs_ba_step_probe(dvs_ba* h, double radius, int32_t refresh, int32_t 
 #endif  // DVS_TEST_HOOKS
 
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h)
+// trust_region.h driven as the solvers' loops drive it, over a script of trial records: head, verdict (by `mode`'s rule), update, and
+// on an accepted step the candidate's cost becomes the point's.  The script's length is the iteration limit; the gradient never ends it.
+dvs_status dvs_test_trust_region(int32_t mode, const dvs_test_tr_trial* trials, int32_t n, double x_cost, double ftol, double ptol,
+                                 dvs_test_tr_step* steps, int32_t* n_steps, int32_t* termination) {
+  DVS_ARG(mode >= 0 && mode <= 2 && n >= 0 && (trials || n == 0) && (steps || n == 0) && n_steps && termination);
+  TrustRegion tr;
+  for (*n_steps = 0; go_on(tr.next(n, 1.0, 0.0), termination);) {
+    const dvs_test_tr_trial& t = trials[*n_steps];
+    const TrialRecord rec = {t.valid, t.model_change, t.cand_cost, t.sn, t.xn};
+    const StepVerdict v = mode == 0   ? verdict_host_decides(rec, x_cost, ptol, ftol)
+                          : mode == 1 ? verdict_device_decides_decrease(rec, t.accept != 0, x_cost, ptol, ftol)
+                                      : verdict_device_accept_applied(rec, t.accept != 0, x_cost, ptol, ftol);
+    dvs_test_tr_step& s = steps[(*n_steps)++];
+    const double before = tr.radius;
+    const bool more = go_on(tr.update(v), termination);
+    s = {before, v.cost_change, v.rel, tr.radius, tr.decrease_factor, v.kind, tr.reuse_diagonal ? 1 : 0, tr.invalid, 0};
+    if (!more) break;
+    if (v.kind == kStepAccepted) x_cost = t.cand_cost;
+  }
+  return DVS_OK;
+}
 // one linear solve S x = rhs (S n x n row-major, its lower triangle is read; n a multiple of 6, 6..378) through the tiled solver's
 // launches and through chol_solve: the forward-substituted y and the solution of each, and whether every pivot was positive
 dvs_status dvs_ba_factor_probe(int32_t device, int32_t n, const double* S, const double* rhs, double* y_dev, double* x_dev, double* y_host,

@@ -11,8 +11,7 @@
 //   k_pgo_trial_reduce the sums, folded in a fixed order, into the ONE status record the host reads per trial step
 // and after an accepted step k_pgo_linearize (one thread per edge), k_pgo_nodes (gradient and diagonal blocks: a node's incident edges
 // in ascending edge index) and k_pgo_state_reduce (cost, max |g|), whose record the NEXT trial's read brings along.
-// TrustRegion below RESTATES the policy of csrc/ba.hip (struct TrustRegion there): that one writes into a dvs_ba_summary and lives in
-// ba.hip's anonymous namespace; lifting it would have touched the BA translation unit, whose results must not change by a byte.
+// The trust-region policy and the verdict on a trial step are trust_region.h's, shared with the bundle adjustment's solvers.
 #include <math.h>
 #include <stddef.h>
 #include <string.h>
@@ -21,6 +20,7 @@
 #include "block_ops.h"
 #include "common.h"
 #include "device_mem.h"
+#include "trust_region.h"
 #ifdef DVS_TEST_HOOKS
 #include "../../include/dvslam_hip_test.h"
 #endif
@@ -451,30 +451,6 @@ __global__ __launch_bounds__(256) void k_pgo_correct_points(int N, int n, const 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// The trust-region policy of csrc/ba.hip (struct TrustRegion there; ceres::Solver defaults), restated: initial radius 1e4; a step is
-// accepted when its relative decrease exceeds 1e-3; radius /= max(1/3, 1 - (2 rho - 1)^3) on success, /= 2, 4, 8 .. on failure; the LM
-// diagonal is kept across a rejected step and rebuilt after any other.
-struct TrustRegion {
-  static constexpr double kMinRelativeDecrease = 1e-3;
-  double radius = 1e4, decrease_factor = 2.0;
-  bool reuse_diagonal = false;
-  int iteration = 0, invalid = 0;
-  bool invalid_step() {   // true: the fifth in a row, the solve has failed
-    if (++invalid >= 5) return true;
-    shrink(false);
-    return false;
-  }
-  void accepted(double rel) {
-    invalid = 0;
-    radius = radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
-    radius = std::min(1e16, radius);
-    decrease_factor = 2.0; reuse_diagonal = false;
-  }
-  void rejected() { invalid = 0; shrink(true); }
- private:
-  void shrink(bool reuse) { radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = reuse; }
-};
-
 void rodrigues_to_R(const double* w, double* R) {   // cos I + (1 - cos) k k^T + sin [k]x; the identity for the zero vector
   const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   if (th == 0) { for (int k = 0; k < 9; k++) R[k] = (k % 4 == 0) ? 1.0 : 0.0; return; }
@@ -551,8 +527,8 @@ struct dvs_pgo {
   DeviceBuf<float> pts; DeviceBuf<int32_t> anchors; size_t pts_cap = 0, anchors_cap = 0;
   double *q_cur = nullptr, *t_cur = nullptr, *R_cur = nullptr, *q_cand = nullptr, *t_cand = nullptr, *R_cand = nullptr;
   std::vector<double> trace;   // 7 per row
-  void log(double radius, int kind, double cost_change, double model_change, double rel, double cost, int pcg) {
-    const double row[7] = {radius, (double)kind, cost_change, model_change, rel, cost, (double)pcg};
+  void log(double radius, const StepVerdict& v, const TrialRecord& r, int pcg) {
+    const double row[7] = {radius, (double)v.kind, v.cost_change, r.model_change, v.rel, v.kind == kStepInvalid ? 0.0 : r.cand_cost, (double)pcg};
     trace.insert(trace.end(), row, row + 7);
   }
 };
@@ -775,39 +751,21 @@ dvs_status dvs_pgo_solve(dvs_pgo* h, const dvs_pgo_params* params, dvs_pgo_summa
   double x_cost = s.cur_cost;
   summary->initial_cost = x_cost;
   TrustRegion tr;
-  for (;;) {
-    if (tr.iteration >= prm.max_iterations) { summary->termination = 1; break; }
-    if (tr.radius < 1e-32) { summary->termination = 0; break; }
+  while (go_on(tr.before_trial(prm.max_iterations), &summary->termination)) {
     const double radius = tr.radius;
     enqueue_trial(h, radius, prm.eta, max_pcg, tr.reuse_diagonal);
     DVS_TRY(read_status(h, &s));
     // the gradient test of the loop head, on the record this read brought along: the trial enqueued above is dropped, uncounted
-    if (s.gmax <= prm.gradient_tolerance) { summary->termination = 0; break; }
-    tr.iteration++;
+    if (!go_on(tr.count_trial(s.gmax, prm.gradient_tolerance), &summary->termination)) break;
     summary->pcg_iterations += s.pcg_iterations;
-    const double model_cost_change = s.model_cost_change;
-    if (!s.finite || !(model_cost_change > 0.0)) {
-      h->log(radius, 0, 0, model_cost_change, 0, 0, s.pcg_iterations);
-      if (tr.invalid_step()) { summary->termination = 2; break; }
-      continue;
-    }
-    const double cand_cost = s.cand_cost, cost_change = x_cost - cand_cost;
-    if (sqrt(s.step2) <= prm.parameter_tolerance * (sqrt(s.x2) + prm.parameter_tolerance)) {
-      h->log(radius, 3, cost_change, model_cost_change, 0, cand_cost, s.pcg_iterations); summary->termination = 0; break;
-    }
-    if (fabs(cost_change) <= prm.function_tolerance * x_cost) {
-      h->log(radius, 4, cost_change, model_cost_change, 0, cand_cost, s.pcg_iterations); summary->termination = 0; break;
-    }
-    const double rel = cost_change / model_cost_change;
-    const bool accept = rel > TrustRegion::kMinRelativeDecrease;
-    h->log(radius, accept ? 1 : 2, cost_change, model_cost_change, rel, cand_cost, s.pcg_iterations);
-    if (accept) {
+    const TrialRecord rec = {s.finite, s.model_cost_change, s.cand_cost, s.step2, s.x2};
+    const StepVerdict v = verdict_host_decides(rec, x_cost, prm.parameter_tolerance, prm.function_tolerance);
+    h->log(radius, v, rec, s.pcg_iterations);
+    if (!go_on(tr.update(v), &summary->termination)) break;
+    if (v.kind == kStepAccepted) {
       commit_candidate(h);    // its cost and max |g| arrive with the next trial's record
-      x_cost = cand_cost;
+      x_cost = rec.cand_cost;
       summary->num_successful_steps++;
-      tr.accepted(rel);
-    } else {
-      tr.rejected();
     }
   }
   summary->num_iterations = tr.iteration;

@@ -26,6 +26,21 @@ void dvs_test_sort_nodes_ranked(const int32_t* count, const int32_t* ulx, int32_
 /* ... and through the kernel's workgroup sort itself (needs a GPU; n <= 1500) */
 dvs_status dvs_test_sort_nodes_device(const int32_t* count, const int32_t* ulx, int32_t n, int32_t* perm);
 void dvs_test_sincosf(float a, float* s, float* c);
+/* csrc/trust_region.h on its own, driven as the four Levenberg-Marquardt loops drive it, over a script of n trial records starting from
+ * a point of cost x_cost: loop head (the script's length is the iteration limit, the gradient test never fires), verdict, policy update;
+ * an accepted step makes its cand_cost the next x_cost.  sn, xn: squared norms of the step and the point.  mode says who decides:
+ * 0 the host (dvs_ba_solve, dvs_pgo_solve, dvs_ba_solve_device without speculation; `accept` unused), 1 the device's `accept` in place
+ * of the relative-decrease test after the host's validity and tolerance tests (dvs_ba_solve_global), 2 the device's accept has been
+ * applied and overrides every test (speculating dvs_ba_solve_device).  Per step run: the radius it was tried at, the verdict (kind
+ * 0 invalid, 1 accepted, 2 rejected, 3 parameter tolerance, 4 function tolerance), and the policy's state after it.  *termination:
+ * 0 converged (tolerance, or radius below 1e-32), 1 script exhausted, 2 five invalid steps in a row. */
+typedef struct dvs_test_tr_trial { int32_t valid, accept; double model_change, cand_cost, sn, xn; } dvs_test_tr_trial;
+typedef struct dvs_test_tr_step {
+  double radius_before, cost_change, rel, radius, decrease_factor;
+  int32_t kind, reuse_diagonal, invalid, reserved;
+} dvs_test_tr_step;
+dvs_status dvs_test_trust_region(int32_t mode, const dvs_test_tr_trial* trials, int32_t n, double x_cost, double ftol, double ptol,
+                                 dvs_test_tr_step* steps, int32_t* n_steps, int32_t* termination);
 /* the PnP stage's quartic (Ferrari + Newton) and P3P (Grunert) routines on the host: real roots (unordered) / up to 4 poses x 12 */
 int32_t dvs_test_quartic_roots(double a4, double a3, double a2, double a1, double a0, double* roots4);
 int32_t dvs_test_p3p(const double* P9, const double* j9, double* poses48);
