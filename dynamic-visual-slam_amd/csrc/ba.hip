@@ -21,11 +21,11 @@
 #include <string.h>
 #include <algorithm>
 #include <new>
-#include <chrono>
 #include <vector>
 #include "block_ops.h"
 #include "common.h"
 #include "device_mem.h"
+#include "io_host.h"
 #include "trust_region.h"
 
 namespace dvs {
@@ -1456,17 +1456,6 @@ using namespace dvs;
 
 namespace {
 
-// Lays the buffers of an arena out: run over a null base for the size, then over the arena for the pointers.  256-byte aligned, never
-// a zero-byte block.
-struct Carver {
-  uint8_t* base;
-  size_t used = 0;
-  template <class T> void take(T*& p, size_t count) {
-    p = base ? (T*)(base + used) : nullptr;
-    used += (std::max<size_t>(count * sizeof(T), 1) + 255) & ~(size_t)255;
-  }
-};
-
 // A problem's device memory (dvs_ba_set_problem): [tables uploaded from the host | buffers that start at zero | evaluation outputs]
 struct ProbView {
   double *q, *t, *X, *uv;
@@ -1540,7 +1529,8 @@ struct GbaView : LmCore {
 
 struct dvs_ba {
   int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+  Stream own_stream;               // declared before the blocks: it outlives them
+  hipStream_t stream = nullptr;    // own_stream or the caller's (dvs_ba_set_stream)
   int K = 0, L = 0, R = 0, nChunks = 0, lmBlocks = 0;
   double fx = 0, fy = 0, cx = 0, cy = 0, sigma = 1, huber = 1.345;
   std::vector<double> q, t, X;            // host mirror of the parameters
@@ -1748,16 +1738,7 @@ dvs_status lm_plan(dvs_ba* h) {
 // then the stream wait — instead of sleeping in hipStreamSynchronize (a wake-up per trial step and per accepted step)
 dvs_status lm_fetch_status(dvs_ba* h, const LmStatus* rec, int& expect_seq) {
   expect_seq++;
-  if (h->lm_poll) {
-    const volatile int* seq = &rec->seq;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int spin = 1; *seq != expect_seq; spin++) {
-      __builtin_ia32_pause();
-      if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    if (*seq == expect_seq) return DVS_OK;
-  }
+  if (h->lm_poll) return io_wait(&rec->seq, expect_seq, h->stream, 2);
   DVS_HIP(hipStreamSynchronize(h->stream));
   return DVS_OK;
 }
@@ -1858,7 +1839,7 @@ dvs_status dvs_ba_create(int32_t device, dvs_ba** out) {
   dvs_ba* h = new (std::nothrow) dvs_ba();
   if (!h) { set_error("out of host memory"); return DVS_ERR_HIP; }
   h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+  const hipError_t e = h->own_stream.create();
   if (e != hipSuccess) { delete h; set_error("hipStreamCreate: %s", hipGetErrorString(e)); return DVS_ERR_HIP; }
   h->stream = h->own_stream;
   h->lm_poll = dvs::env_switch("DVS_LM_POLL", 1) != 0;
@@ -1871,7 +1852,6 @@ void dvs_ba_destroy(dvs_ba* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
 }
 

@@ -386,7 +386,7 @@ using namespace dvs;
 struct dvs_cvorb {
   dvs_cvorb_params prm;
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;   // declared before the workspace: it outlives it
   int rows = 0, cols = 0, capacity = 0;
   CvGeom G;
   uint64_t blockBytes = 0;
@@ -507,7 +507,7 @@ dvs_status dvs_cvorb_create(const dvs_cvorb_params* p, int32_t device, dvs_cvorb
   dvs_cvorb* h = new (std::nothrow) dvs_cvorb();
   if (!h) { set_error("out of host memory"); return DVS_ERR_HIP; }
   h->prm = *p; h->device = device;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; set_error("hipStreamCreate failed"); return DVS_ERR_HIP; }
+  if (h->stream.create() != hipSuccess) { delete h; set_error("hipStreamCreate failed"); return DVS_ERR_HIP; }
   *out = h;
   return DVS_OK;
 }
@@ -516,7 +516,6 @@ void dvs_cvorb_destroy(dvs_cvorb* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  (void)hipStreamDestroy(h->stream);
   delete h;   // (frees the workspace)
 }
 

@@ -1,6 +1,7 @@
-// device_mem.h — owners of what a handle holds on the device: hipMalloc / hipHostMalloc blocks, events, and the rings of buffer sets a
-// pipelined caller's batches rotate through.  Internal to the library; nothing here is exported.  Each resource is freed exactly once
-// because its owner cannot be copied: a handle's "free everything" is the assignment of an empty struct of these.
+// device_mem.h — owners of what a handle holds on the device: hipMalloc / hipHostMalloc blocks, streams, events, and the rings of buffer
+// sets a pipelined caller's batches rotate through; and the Carver that lays sub-buffers out in one block.  Internal to the library;
+// nothing here is exported.  Each resource is freed exactly once because its owner cannot be copied: a handle's "free everything" is the
+// assignment of an empty struct of these.  A handle declares its own stream BEFORE its buffers, so that the stream outlives them.
 #pragma once
 #include <algorithm>
 #include <memory>
@@ -59,6 +60,37 @@ class Event {
  private:
   struct Destroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
   std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Destroy> e_;
+};
+
+// Move-only owner of a non-blocking stream.  Empty until create(); every HIP stream is a hardware queue, so a handle creates one only
+// when it is used.  priority_class > 0 / < 0: the device's highest / lowest dispatch priority (as dvs_stream_create).
+class Stream {
+ public:
+  hipError_t create(int priority_class = 0) {
+    hipStream_t s = nullptr;
+    int lo = 0, hi = 0;
+    if (priority_class) (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+    const hipError_t r = priority_class ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority_class > 0 ? hi : lo)
+                                        : hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    s_.reset(s);
+    return r;
+  }
+  operator hipStream_t() const { return s_.get(); }
+ private:
+  struct Destroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+  std::unique_ptr<std::remove_pointer_t<hipStream_t>, Destroy> s_;
+};
+
+// Lays the buffers of a block out: run over a null base for the size, then over the block for the pointers.  Every buffer starts on a
+// multiple of `align` bytes (a power of two) behind the base, and an empty one still takes one unit: no two buffers share an address.
+struct Carver {
+  uint8_t* base;
+  size_t align = 256;
+  size_t used = 0;
+  template <class T> void take(T*& p, size_t count) {
+    p = base ? (T*)(base + used) : nullptr;
+    used += (std::max<size_t>(count * sizeof(T), 1) + align - 1) & ~(align - 1);
+  }
 };
 
 // Four slots of which the first `depth` (3 or 4) are used in turn.  A slot is a small struct of owners; its user allocates a slot when

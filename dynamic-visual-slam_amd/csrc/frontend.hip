@@ -13,7 +13,6 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
-#include "io_pinned.h"
 #include "matcher.h"
 #include "associate_device.h"
 #include "block_ops.h"
@@ -434,8 +433,9 @@ dvs_status dvs_filter_depth(dvs_matcher* ctx, const dvs_keypoint* kps, const uin
   // image only the n pixels under the keypoints): no copy commands, and the host polls the sequence number the kernel publishes.
   const size_t kb = ((size_t)n * sizeof(dvs_keypoint) + 15) & ~(size_t)15, db = (size_t)n * 32, ib = ((size_t)n * 4 + 16 + 15) & ~(size_t)15;
   const size_t zb = (size_t)rows * cols * 2;
-  uint8_t* hio; int *hseq, *counter;
-  DVS_TRY(matcher_pinned(ctx, 2 * kb + 2 * db + ib + zb, (void**)&hio, &hseq, &counter));
+  PinnedIo* io;
+  DVS_TRY(matcher_pinned(ctx, 2 * kb + 2 * db + ib + zb, &io));
+  uint8_t* hio = io->h();
   dvs_keypoint* p_k = (dvs_keypoint*)hio; dvs_keypoint* p_ok = (dvs_keypoint*)(hio + kb);
   uint8_t* p_d = hio + 2 * kb; uint8_t* p_od = p_d + db;
   int* p_oi = (int*)(p_od + db); int* p_no = p_oi + n;
@@ -444,11 +444,11 @@ dvs_status dvs_filter_depth(dvs_matcher* ctx, const dvs_keypoint* kps, const uin
   if (desc) memcpy(p_d, desc, db);
   if (step_bytes == (size_t)cols * 2) memcpy(p_dep, depth, zb);
   else for (int r = 0; r < rows; r++) memcpy((uint8_t*)p_dep + (size_t)r * cols * 2, (const uint8_t*)depth + (size_t)r * step_bytes, (size_t)cols * 2);
-  const int seq = ++*counter;
+  const int seq = io->next_seq();   // the kernel publishes it itself
   hipLaunchKernelGGL(k_filter_depth, dim3(1), dim3(256), 0, st, p_k, desc ? p_d : nullptr, (const int*)nullptr, n, n, p_dep, (uint64_t)cols * 2,
-                     (uint64_t)0, rows, cols, min_depth, max_depth, p_ok, p_od, p_oi, p_no, hseq, seq);
+                     (uint64_t)0, rows, cols, min_depth, max_depth, p_ok, p_od, p_oi, p_no, io->seq_word.get(), seq);
   DVS_HIP(hipGetLastError());
-  DVS_TRY(io_wait(hseq, seq, st));
+  DVS_TRY(io->wait(st, seq));
   const int m = *p_no;
   if (m) {
     memcpy(out_kps, p_ok, (size_t)m * sizeof(dvs_keypoint));

@@ -501,15 +501,6 @@ __global__ __launch_bounds__(1024) void k_scan_counts(const int* __restrict__ co
 using namespace dvs;
 
 namespace {
-dvs_status grow(void** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return DVS_OK;
-  if (*p) DVS_HIP(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  DVS_HIP(hipMalloc(p, need ? need : 1));
-  *cap = need;
-  return DVS_OK;
-}
-
 template <int NQ>
 void launch_match_fp4_nq(hipStream_t st, int k, int npairs, const uint8_t* q, const int* nq, int qs, const uint8_t* t, const int* nt, int ts,
                          const uint8_t* t0, const int* nt0, int* idx, int* dist) {
@@ -545,7 +536,7 @@ dvs_status create_matcher(int device, bool own_stream, hipStream_t stream, dvs_m
   if (!m) { set_error("out of host memory"); return DVS_ERR_HIP; }
   m->device = device;
   if (own_stream) {
-    hipError_t e = hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking);
+    const hipError_t e = m->own_stream.create();
     if (e != hipSuccess) { delete m; set_error("hipStreamCreate: %s", hipGetErrorString(e)); return DVS_ERR_HIP; }
     stream = m->own_stream;
   }
@@ -570,53 +561,42 @@ void launch_scan_counts(hipStream_t st, const int* counts, int n, long long* off
 }
 
 dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out) {
-  DVS_TRY(grow(&m->scratch[slot], &m->cscratch[slot], bytes));
-  *out = m->scratch[slot];
-  return DVS_OK;
-}
-dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq, int** counter) {
-  if (bytes > m->cio || !m->h_io) {
-    if (m->h_io) { DVS_HIP(hipStreamSynchronize(m->stream)); DVS_HIP(hipHostFree(m->h_io)); m->h_io = nullptr; m->cio = 0; }
-    const size_t cap = std::max<size_t>(bytes + bytes / 2, 65536);
-    DVS_HIP(hipHostMalloc(&m->h_io, cap));
-    m->cio = cap;
-  }
-  if (!m->h_seq) { DVS_HIP(hipHostMalloc((void**)&m->h_seq, 64)); *m->h_seq = 0; m->io_seq = 0; }
-  *out = m->h_io; *h_seq = m->h_seq; *counter = &m->io_seq;
+  DVS_TRY(grow(m->scratch[slot], m->cscratch[slot], std::max<size_t>(bytes, 1)));
+  *out = m->scratch[slot].get();
   return DVS_OK;
 }
 
 dvs_status matcher_thresh_rows_device(dvs_matcher* m, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int max_dist, const long long** d_offs,
                                       const int** d_pairs, long long* total) {
   DVS_HIP(hipSetDevice(m->device));
-  DVS_TRY(grow(&m->d_counts, &m->ccounts, (size_t)nq * 4));
-  DVS_TRY(grow(&m->d_offs, &m->coffs, ((size_t)nq + 1) * 8));
+  DVS_TRY(grow(m->d_counts, m->ccounts, std::max<size_t>(nq, 1)));
+  DVS_TRY(grow(m->d_offs, m->coffs, (size_t)nq + 1));
   const dim3 grid((nq + 3) / 4);   // one wavefront per query
-  hipLaunchKernelGGL(k_thresh_count, grid, dim3(256), 0, m->stream, (const u64*)d_q, nq, (const u64*)d_t, nt, max_dist, (int*)m->d_counts);
-  hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, m->stream, (const int*)m->d_counts, nq, (long long*)m->d_offs);
+  hipLaunchKernelGGL(k_thresh_count, grid, dim3(256), 0, m->stream, (const u64*)d_q, nq, (const u64*)d_t, nt, max_dist, m->d_counts.get());
+  hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, m->stream, (const int*)m->d_counts.get(), nq, m->d_offs.get());
   DVS_HIP(hipGetLastError());
   long long tot = 0;
-  DVS_HIP(hipMemcpyAsync(&tot, (long long*)m->d_offs + nq, 8, hipMemcpyDeviceToHost, m->stream));
+  DVS_HIP(hipMemcpyAsync(&tot, m->d_offs.get() + nq, 8, hipMemcpyDeviceToHost, m->stream));
   DVS_HIP(hipStreamSynchronize(m->stream));
-  DVS_TRY(grow(&m->d_pairs, &m->cpairs, (size_t)std::max<long long>(tot, 1) * 12));
+  DVS_TRY(grow(m->d_pairs, m->cpairs, (size_t)std::max<long long>(tot, 1) * 3));
   if (tot) {
     hipLaunchKernelGGL(k_thresh_write, grid, dim3(256), 0, m->stream, (const u64*)d_q, nq, (const u64*)d_t, nt, max_dist,
-                       (const long long*)m->d_offs, (int*)m->d_pairs, tot);
+                       (const long long*)m->d_offs.get(), m->d_pairs.get(), tot);
     DVS_HIP(hipGetLastError());
     DVS_HIP(hipStreamSynchronize(m->stream));
   }
-  *d_offs = (const long long*)m->d_offs; *d_pairs = (const int*)m->d_pairs; *total = tot;
+  *d_offs = m->d_offs.get(); *d_pairs = m->d_pairs.get(); *total = tot;
   return DVS_OK;
 }
 
 dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,
                                  const int** d_pairs, long long* total) {
   DVS_HIP(hipSetDevice(m->device));
-  DVS_TRY(grow(&m->d_q, &m->cq, (size_t)nq * 32));
-  DVS_TRY(grow(&m->d_t, &m->ct, (size_t)nt * 32));
-  DVS_HIP(hipMemcpyAsync(m->d_q, q, (size_t)nq * 32, hipMemcpyHostToDevice, m->stream));
-  DVS_HIP(hipMemcpyAsync(m->d_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, m->stream));
-  return matcher_thresh_rows_device(m, (const uint8_t*)m->d_q, nq, (const uint8_t*)m->d_t, nt, max_dist, d_offs, d_pairs, total);
+  DVS_TRY(grow(m->d_q, m->cq, std::max<size_t>((size_t)nq * 32, 1)));
+  DVS_TRY(grow(m->d_t, m->ct, std::max<size_t>((size_t)nt * 32, 1)));
+  DVS_HIP(hipMemcpyAsync(m->d_q.get(), q, (size_t)nq * 32, hipMemcpyHostToDevice, m->stream));
+  DVS_HIP(hipMemcpyAsync(m->d_t.get(), t, (size_t)nt * 32, hipMemcpyHostToDevice, m->stream));
+  return matcher_thresh_rows_device(m, m->d_q.get(), nq, m->d_t.get(), nt, max_dist, d_offs, d_pairs, total);
 }
 }  // namespace dvs
 
@@ -633,12 +613,7 @@ void dvs_matcher_destroy(dvs_matcher* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   (void)hipStreamSynchronize(m->stream);
-  void* ptrs[] = {m->d_q, m->d_t, m->d_idx, m->d_dist, m->d_counts, m->d_offs, m->d_pairs, m->scratch[0], m->scratch[1], m->scratch[2], m->scratch[3], m->d_zero};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (m->h_io) (void)hipHostFree(m->h_io);
-  if (m->h_seq) (void)hipHostFree(m->h_seq);
-  if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
-  delete m;
+  delete m;   // (its blocks, then its own stream)
 }
 
 dvs_status dvs_matcher_set_stream(dvs_matcher* m, void* s) {
@@ -652,7 +627,7 @@ DVS_HOOK dvs_status dvs_matcher_use_own_stream(dvs_matcher* m) {
   DVS_ARG(m);
   DVS_HIP(hipSetDevice(m->device));
   DVS_HIP(hipStreamSynchronize(m->stream));
-  if (!m->own_stream) DVS_HIP(hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking));
+  if (!m->own_stream) DVS_HIP(m->own_stream.create());
   m->stream = m->own_stream;
   return DVS_OK;
 }
@@ -684,13 +659,13 @@ dvs_status dvs_match_hamming_sequence_device(dvs_matcher* m, const uint8_t* d_de
   if (nframes == 0) return DVS_OK;
   DVS_HIP(hipSetDevice(m->device));
   if (!d_prev_desc) {  // no predecessor: frame 0 matches against nothing (train_idx -1, dist INT32_MAX)
-    if (!m->d_zero) {
-      DVS_HIP(hipMalloc((void**)&m->d_zero, 64));
+    if (!m->d_zero.get()) {
+      DVS_TRY(m->d_zero.alloc(16));
       // on the matcher's own (non-blocking) stream, i.e. ordered before the kernel below: a hipMemset on the null stream is not,
       // and the kernel then read an uninitialised row count (intermittent GPU fault in tests/test_gpu_match.py)
-      DVS_HIP(hipMemsetAsync(m->d_zero, 0, 64, m->stream));
+      DVS_HIP(hipMemsetAsync(m->d_zero.get(), 0, 64, m->stream));
     }
-    d_prev_desc = (const uint8_t*)m->d_zero; d_prev_n = (const int32_t*)m->d_zero;
+    d_prev_desc = (const uint8_t*)m->d_zero.get(); d_prev_n = m->d_zero.get();
   }
   // the matrix cores from 7 frames of 2 000 descriptors on (the four-stream schedule's match stream; up to 6 frames a lane matches from
   // LDS, k_match_lds): with the operands built in the kernel the matrix-core match needs no second launch and wins earlier than rounds
@@ -711,37 +686,35 @@ dvs_status dvs_match_hamming(dvs_matcher* m, const uint8_t* q, int32_t nq, const
   DVS_ARG(q && train_idx && dist && (t || nt == 0));
   DVS_ARG(nt < (1 << 23));  // k_match packs the train index into 23 bits
   DVS_HIP(hipSetDevice(m->device));
-  DVS_TRY(grow(&m->d_q, &m->cq, (size_t)nq * 32));
-  DVS_TRY(grow(&m->d_t, &m->ct, (size_t)std::max(nt, 1) * 32));
-  DVS_TRY(grow(&m->d_idx, &m->cidx, (size_t)nq * 8));
-  int* d_idx = (int*)m->d_idx;
+  const size_t qb = (size_t)nq * 32, tb = (size_t)nt * 32;
+  DVS_TRY(grow(m->d_q, m->cq, qb));
+  DVS_TRY(grow(m->d_t, m->ct, std::max<size_t>(tb, 32)));
+  DVS_TRY(grow(m->d_idx, m->cidx, (size_t)nq * 2));
+  const u64* d_q = (const u64*)m->d_q.get(); const u64* d_t = (const u64*)m->d_t.get();
+  int* d_idx = m->d_idx.get();
   int* d_dist = d_idx + nq;
   // frame-sized sets go through the pinned block (import / export kernels, polled sequence number): no copy commands, no stream wait
   const bool pinned_io = nq <= 16384 && nt <= 16384;
-  uint8_t* hio = nullptr; int *hseq = nullptr, *counter = nullptr;
+  PinnedIo* io = nullptr;
   if (pinned_io) {
-    DVS_TRY(matcher_pinned(m, (size_t)(nq + nt) * 32 + (size_t)nq * 8, (void**)&hio, &hseq, &counter));
-    memcpy(hio, q, (size_t)nq * 32);
-    if (nt) memcpy(hio + (size_t)nq * 32, t, (size_t)nt * 32);
-    hipLaunchKernelGGL(k_io_import, dim3((nq * 8 + 255) / 256), dim3(256), 0, m->stream, (const uint32_t*)hio, (uint32_t*)m->d_q, nq * 8);
-    if (nt) hipLaunchKernelGGL(k_io_import, dim3((nt * 8 + 255) / 256), dim3(256), 0, m->stream, (const uint32_t*)(hio + (size_t)nq * 32), (uint32_t*)m->d_t, nt * 8);
+    DVS_TRY(matcher_pinned(m, qb + tb + (size_t)nq * 8, &io));   // [query rows | train rows | idx | dist]
+    memcpy(io->h(), q, qb);
+    if (nt) memcpy(io->h() + qb, t, tb);
+    io->import(m->stream, m->d_q.get(), qb);
+    if (nt) io->import(m->stream, m->d_t.get(), tb, qb);
   } else {
-    DVS_HIP(hipMemcpyAsync(m->d_q, q, (size_t)nq * 32, hipMemcpyHostToDevice, m->stream));
-    if (nt) DVS_HIP(hipMemcpyAsync(m->d_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, m->stream));
+    DVS_HIP(hipMemcpyAsync(m->d_q.get(), q, qb, hipMemcpyHostToDevice, m->stream));
+    if (nt) DVS_HIP(hipMemcpyAsync(m->d_t.get(), t, tb, hipMemcpyHostToDevice, m->stream));
   }
   if (nq <= 16384)
-    launch_match_few(m->stream, dim3((nq + 63) / 64, 1), (const u64*)m->d_q, (const int*)nullptr, nq, nq, (const u64*)m->d_t, (const int*)nullptr, nt, nt,
-                     d_idx, d_dist, nt);
+    launch_match_few(m->stream, dim3((nq + 63) / 64, 1), d_q, (const int*)nullptr, nq, nq, d_t, (const int*)nullptr, nt, nt, d_idx, d_dist, nt);
   else
-    hipLaunchKernelGGL((k_match<8, 2>), dim3((nq + 127) / 128, 1), dim3(512), 0, m->stream, (const u64*)m->d_q, (const int*)nullptr, nq, nq,
-                     (const u64*)m->d_t, (const int*)nullptr, nt, nt, d_idx, d_dist);
+    hipLaunchKernelGGL((k_match<8, 2>), dim3((nq + 127) / 128, 1), dim3(512), 0, m->stream, d_q, (const int*)nullptr, nq, nq, d_t, (const int*)nullptr,
+                       nt, nt, d_idx, d_dist);
   DVS_HIP(hipGetLastError());
   if (pinned_io) {
-    uint8_t* hout = hio + (size_t)(nq + nt) * 32;
-    const int seq = ++*counter;
-    hipLaunchKernelGGL(k_io_export, dim3(1), dim3(256), 0, m->stream, (const uint32_t*)d_idx, (uint32_t*)hout, nq * 2, hseq, seq);
-    DVS_HIP(hipGetLastError());
-    DVS_TRY(io_wait(hseq, seq, m->stream));
+    uint8_t* hout = io->h() + qb + tb;
+    DVS_TRY(io->fetch(m->stream, d_idx, hout, (size_t)nq * 8, 16384 * 8));   // every frame-sized result leaves through the export kernel
     memcpy(train_idx, hout, (size_t)nq * 4); memcpy(dist, hout + (size_t)nq * 4, (size_t)nq * 4);
     return DVS_OK;
   }

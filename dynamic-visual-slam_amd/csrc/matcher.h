@@ -3,21 +3,25 @@
 // its grow-only device scratch and its pinned in / out block.
 #pragma once
 #include "common.h"
+#include "device_mem.h"
+#include "io_host.h"
 
 struct dvs_matcher {
   int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  // grow-only staging for the host entry points
-  void *d_q = nullptr, *d_t = nullptr, *d_idx = nullptr, *d_dist = nullptr, *d_counts = nullptr, *d_offs = nullptr, *d_pairs = nullptr;
-  size_t cq = 0, ct = 0, cidx = 0, ccounts = 0, cpairs = 0, coffs = 0;
-  void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};  // grow-only buffers of matcher_scratch
+  dvs::Stream own_stream;          // declared before the blocks: it outlives them
+  hipStream_t stream = nullptr;    // own_stream or the caller's (dvs_matcher_create_on_stream, dvs_matcher_set_stream)
+  // grow-only staging for the host entry points (dvs::grow): rows of 32 descriptor bytes, (idx | dist), the threshold match's passes
+  dvs::DeviceBuf<uint8_t> d_q, d_t;
+  dvs::DeviceBuf<int> d_idx, d_counts, d_pairs;
+  dvs::DeviceBuf<long long> d_offs;
+  size_t cq = 0, ct = 0, cidx = 0, ccounts = 0, cpairs = 0, coffs = 0;   // capacities in elements
+  dvs::DeviceBuf<uint8_t> scratch[4];  // grow-only buffers of matcher_scratch
   size_t cscratch[4] = {0, 0, 0, 0};
-  void* d_zero = nullptr;  // 64 zero bytes: the empty predecessor of dvs_match_hamming_sequence_device
-  int use_mfma = 1;        // DVS_MATCH_MFMA=0 keeps every job on the popcount kernels
-  // pinned in / out block of the small host entry points (RANSAC stages): inputs are placed here and imported by a kernel, results
-  // are exported by a kernel that publishes a sequence number the host polls — no copy commands, no stream wait
-  void* h_io = nullptr; size_t cio = 0;
-  int* h_seq = nullptr; int io_seq = 0;
+  dvs::DeviceBuf<int> d_zero;      // 64 zero bytes: the empty predecessor of dvs_match_hamming_sequence_device
+  int use_mfma = 1;                // DVS_MATCH_MFMA=0 keeps every job on the popcount kernels
+  // pinned in / out block of the small host entry points: inputs are placed here and imported by a kernel, results are exported by a
+  // kernel that publishes a sequence number the host polls — no copy commands, no stream wait
+  dvs::PinnedIo io;
 };
 
 namespace dvs {
@@ -38,8 +42,12 @@ __device__ __forceinline__ int hamming256(const u64* a, const u64* b) {
 //   3  dvs_publish_keyframe_device's pose; the reverse arg-min of dvs_match_hamming_cross_batch_device; dvs_match_hamming_radius's sort;
 //      the At rows of dvs_triangulate_landmarks* for landmarks with more than eight views
 dvs_status matcher_scratch(dvs_matcher* m, int slot, size_t bytes, void** out);
-// the pinned in / out block (at least `bytes`), its published sequence number and the host-side counter of the last one issued
-dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, void** out, int** h_seq, int** counter);
+// the pinned in / out block, at least `bytes` long (PinnedIo::reserve on the handle's stream)
+inline dvs_status matcher_pinned(dvs_matcher* m, size_t bytes, PinnedIo** out) {
+  DVS_TRY(m->io.reserve(m->stream, bytes));
+  *out = &m->io;
+  return DVS_OK;
+}
 // candidate pairs (Hamming < max_dist) as (q, t, dist) triplets in (q, t) order + per-query offsets, left on the device (own staging,
 // no scratch slot); synchronises once for the total
 dvs_status matcher_thresh_device(dvs_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int max_dist, const long long** d_offs,

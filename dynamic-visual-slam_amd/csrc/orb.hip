@@ -7,11 +7,11 @@
 #include <string.h>
 #include <algorithm>
 #include <new>
-#include <chrono>
 #include <vector>
 #include "common.h"
 #include "cv_round.h"
 #include "device_mem.h"
+#include "io_host.h"
 #ifdef DVS_TEST_HOOKS
 #include "../../include/dvslam_hip_test.h"
 #endif
@@ -140,9 +140,10 @@ enum {
 struct dvs_orb {
   dvs_orb_params prm;
   int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  hipStream_t pf_stream = nullptr;         // highest priority: the NEXT batch's level chain (dvs_orb_hint_next_batch_device)
-  hipStream_t aux_stream = nullptr;        // lowest priority: in-step level chain, blur, a deferred descriptor stage
+  Stream own_stream;                       // the three owned streams are declared before everything they serve: they outlive it
+  Stream pf_stream;                        // highest priority: the NEXT batch's level chain (dvs_orb_hint_next_batch_device)
+  Stream aux_stream;                       // lowest priority: in-step level chain, blur, a deferred descriptor stage
+  hipStream_t stream = nullptr;            // own_stream or the caller's
   Event ev[kEvCount];
   int pf_idx = 0;
   Event ev_level[DVS_MAX_LEVELS];          // level l of the pyramid is complete (in-step chain beside FAST)
@@ -1105,7 +1106,7 @@ static dvs_status orb_create(const dvs_orb_params* params, int32_t device, bool 
   if (on_stream) {   // the caller's stream for good: no stream of its own is ever created
     h->stream = ext;
   } else {
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+    const hipError_t e = h->own_stream.create();
     if (e != hipSuccess) { delete h; set_error("hipStreamCreate: %s", hipGetErrorString(e)); return DVS_ERR_HIP; }
     h->stream = h->own_stream;
   }
@@ -1124,14 +1125,11 @@ static dvs_status orb_create(const dvs_orb_params* params, int32_t device, bool 
   // 36-pixel interior is always 9 column groups = 7 rows per trip of the rejection loop (aligned origin: 9 or 10 groups by the
   // cell's phase, 6 rows per trip for the latter).  FAST alone 0.295 -> 0.287 ms per 64 frames.
   h->fast_byte_dma = probe_byte_dma(device, h->stream) && env_int("DVS_FAST_BYTE_DMA", 1);
-  int prio_lo = 0, prio_hi = 0;
-  (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
   // the auxiliary stream carries the blur (and a deferred descriptor stage): LOWEST dispatch priority, so that the quad-tree
   // workgroups launched at the same moment on the main stream all become resident first — with the blur's workgroups dispatched
   // ahead of them some quad-tree workgroups started 90 us late and the kernel took 170 us instead of 110 (64 frames per step:
   // 0.628 -> 0.592 ms, neutral below 64)
-  bool ok = single_stream || (hipStreamCreateWithPriority(&h->aux_stream, hipStreamNonBlocking, prio_lo) == hipSuccess &&
-                              hipStreamCreateWithPriority(&h->pf_stream, hipStreamNonBlocking, prio_hi) == hipSuccess);
+  bool ok = single_stream || (h->aux_stream.create(-1) == hipSuccess && h->pf_stream.create(1) == hipSuccess);
   for (Event& e : h->ev) ok = ok && e.create() == hipSuccess;
   for (Event& e : h->ev_outs.slot) ok = ok && e.create() == hipSuccess;
   for (int l = 1; l < params->nlevels; l++) ok = ok && h->ev_level[l].create() == hipSuccess;
@@ -1152,10 +1150,7 @@ void dvs_orb_destroy(dvs_orb* h) {
   (void)quiesce(h);
   h->timer.resolve();
   free_workspace(h);
-  if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
-  if (h->pf_stream) (void)hipStreamDestroy(h->pf_stream);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;   // (its events and the export ticket go with it)
+  delete h;   // (its events, the export ticket and its streams go with it)
 }
 
 int32_t dvs_orb_max_keypoints(const dvs_orb* h) { return h ? h->prm.nfeatures + 3 * h->prm.nlevels : 0; }
@@ -1387,14 +1382,7 @@ dvs_status dvs_orb_extract_batch_masked(dvs_orb* h, const uint8_t* const* imgs, 
       hipLaunchKernelGGL(k_export_host, dim3(4, nb), dim3(256), 0, h->stream, nb, cap, (const uint32_t*)W.d_kps.get(), (const uint32_t*)W.d_desc.get(),
                          W.d_nout.get(), (uint32_t*)W.h_kps.get(), (uint32_t*)W.h_desc.get(), W.h_nout.get(), h->d_ticket.get(), h->h_seq.get(), seq);
       DVS_HIP(hipGetLastError());
-      const volatile int* ps = h->h_seq.get();
-      const auto t0 = std::chrono::steady_clock::now();
-      for (int spin = 1; *ps != seq; spin++) {
-        __builtin_ia32_pause();
-        if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-      if (*ps != seq) DVS_HIP(hipStreamSynchronize(h->stream));
+      DVS_TRY(io_wait(h->h_seq.get(), seq, h->stream));
     } else {
       DVS_HIP(hipMemcpyAsync(W.h_nout.get(), W.d_nout.get(), nb * 4, hipMemcpyDeviceToHost, h->stream));
       DVS_HIP(hipMemcpyAsync(W.h_kps.get(), W.d_kps.get(), (size_t)nb * cap * sizeof(dvs_keypoint), hipMemcpyDeviceToHost, h->stream));

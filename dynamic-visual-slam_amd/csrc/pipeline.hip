@@ -21,6 +21,7 @@
 // waits for the matches of batches i and i + 1 (the readers of set i).
 #include <vector>
 #include "common.h"
+#include "device_mem.h"
 
 using namespace dvs;
 
@@ -35,14 +36,16 @@ struct dvs_pipeline {
   std::vector<dvs_matcher*> mats;
   dvs_comm* comm = nullptr;
   hipStream_t T = nullptr, M = nullptr;   // lane 0's main stream; match stream (= T for the serial and the lane schedule)
-  bool own_M = false;
-  hipStream_t lane4 = nullptr;            // the fourth lane's stream (highest dispatch priority), owned here
-  uint8_t* arena = nullptr;               // all output sets in one allocation
+  // What the handle owns, released by dvs_pipeline_destroy in this order: matchers, match stream, extractors (all three in its body),
+  // then — with the handle, in reverse declaration order — events, lane-4 stream, arena.
+  DeviceBuf<uint8_t> arena;               // all output sets in one allocation
+  Stream lane4;                           // the fourth lane's stream (highest dispatch priority)
+  Stream own_M;                           // the match stream of the two-stream schedule (M, when it is not T)
+  std::vector<Event> ev_ext, ev_match;
+  Event ev_fast;
   std::vector<dvs_keypoint*> kps;
   std::vector<uint8_t*> desc;
   std::vector<int32_t*> n, idx, dist;
-  std::vector<hipEvent_t> ev_ext, ev_match;
-  hipEvent_t ev_fast = nullptr;
   int64_t i = 0;
   int64_t matched = -1;                   // pipelined schedule: the last batch whose match has been enqueued (a flush enqueues it early)
 };
@@ -139,10 +142,8 @@ dvs_status dvs_pipeline_create(const dvs_pipeline_params* prm, int32_t device, d
     // same priority shares a queue with another lane (0.088 against 0.057 ms per 1-frame step), on a stream of ANOTHER priority it has a
     // queue to itself (0.040 ms).  A fifth lane of any priority collapses all of them (0.074-0.097 ms): four queues run at a time.
     if (lanes >= 2 && l == 3) {
-      void* s4 = nullptr;
-      if ((st = dvs_stream_create(device, 1, &s4)) != DVS_OK) return fail(st);
-      p->lane4 = (hipStream_t)s4;
-      if ((st = dvs_orb_create_on_stream(&op, device, s4, &o)) != DVS_OK) return fail(st);
+      if (hipSetDevice(device) != hipSuccess || p->lane4.create(1) != hipSuccess) { set_error("dvs_pipeline_create: hipStreamCreate failed (lane 4)"); return fail(DVS_ERR_HIP); }
+      if ((st = dvs_orb_create_on_stream(&op, device, (hipStream_t)p->lane4, &o)) != DVS_OK) return fail(st);
     } else if ((st = lanes >= 2 ? dvs_orb_create_single_stream(&op, device, &o) : dvs_orb_create(&op, device, &o)) != DVS_OK) {
       return fail(st);
     }
@@ -156,9 +157,8 @@ dvs_status dvs_pipeline_create(const dvs_pipeline_params* prm, int32_t device, d
   p->T = (hipStream_t)dvs_orb_get_stream(p->orb);
   p->M = p->T;
   if (p->pipelined && lanes == 1) {
-    void* s = nullptr;
-    if ((st = dvs_stream_create(device, 0, &s)) != DVS_OK) return fail(st);
-    p->M = (hipStream_t)s; p->own_M = true;
+    if (hipSetDevice(device) != hipSuccess || p->own_M.create() != hipSuccess) { set_error("dvs_pipeline_create: hipStreamCreate failed (match stream)"); return fail(DVS_ERR_HIP); }
+    p->M = p->own_M;
   }
   for (int l = 0; l < lanes; l++) {
     dvs_matcher* m = nullptr;
@@ -169,21 +169,20 @@ dvs_status dvs_pipeline_create(const dvs_pipeline_params* prm, int32_t device, d
   const size_t B = p->B, cap = p->cap;
   const size_t b_kps = up256(B * cap * sizeof(dvs_keypoint)), b_desc = up256(B * cap * 32), b_n = up256(B * 4), b_idx = up256(B * cap * 4);
   const size_t per_set = b_kps + b_desc + b_n + 2 * b_idx;
-  if (hipMalloc((void**)&p->arena, per_set * nsets) != hipSuccess) { set_error("dvs_pipeline_create: %zu bytes of output sets", per_set * nsets); return fail(DVS_ERR_HIP); }
+  if (p->arena.alloc(per_set * nsets) != DVS_OK) { set_error("dvs_pipeline_create: %zu bytes of output sets", per_set * nsets); return fail(DVS_ERR_HIP); }
   // counts and descriptor rows start at zero: the match of a set that was never extracted (or a row past a frame's count) reads zeros
-  if (hipMemset(p->arena, 0, per_set * nsets) != hipSuccess) return fail(DVS_ERR_HIP);
+  if (hipMemset(p->arena.get(), 0, per_set * nsets) != hipSuccess) return fail(DVS_ERR_HIP);
+  p->ev_ext = std::vector<Event>(nsets); p->ev_match = std::vector<Event>(nsets);   // batch's outputs complete (recorded by the extractor) / batch's match complete
   for (int s = 0; s < nsets; s++) {
-    uint8_t* q = p->arena + per_set * s;
+    uint8_t* q = p->arena.get() + per_set * s;
     p->kps.push_back((dvs_keypoint*)q); q += b_kps;
     p->desc.push_back(q); q += b_desc;
     p->n.push_back((int32_t*)q); q += b_n;
     p->idx.push_back((int32_t*)q); q += b_idx;
     p->dist.push_back((int32_t*)q);
-    hipEvent_t e1 = nullptr, e2 = nullptr;
-    if (hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&e2, hipEventDisableTiming) != hipSuccess) return fail(DVS_ERR_HIP);
-    p->ev_ext.push_back(e1); p->ev_match.push_back(e2);   // batch's outputs complete (recorded by the extractor) / batch's match complete
+    if (p->ev_ext[s].create() != hipSuccess || p->ev_match[s].create() != hipSuccess) return fail(DVS_ERR_HIP);
   }
-  if (hipEventCreateWithFlags(&p->ev_fast, hipEventDisableTiming) != hipSuccess) return fail(DVS_ERR_HIP);
+  if (p->ev_fast.create() != hipSuccess) return fail(DVS_ERR_HIP);
   if (p->pipelined && lanes == 1) {
     if ((st = dvs_orb_set_after_fast_event(p->orb, p->ev_fast)) != DVS_OK) return fail(st);
   }
@@ -211,15 +210,11 @@ void dvs_pipeline_destroy(dvs_pipeline* p) {
     (void)dvs_orb_set_defer_outputs(o, 0);
     (void)dvs_orb_set_after_fast_event(o, nullptr);
   }
-  for (hipEvent_t e : p->ev_ext) (void)hipEventDestroy(e);
-  for (hipEvent_t e : p->ev_match) (void)hipEventDestroy(e);
-  if (p->ev_fast) (void)hipEventDestroy(p->ev_fast);
+  // in this order: the matchers before their stream, the extractors before the lane-4 stream one of them runs on
   for (dvs_matcher* m : p->mats) dvs_matcher_destroy(m);
-  if (p->own_M && p->M) (void)dvs_stream_destroy(p->M);
+  p->own_M = Stream();
   for (dvs_orb* o : p->orbs) dvs_orb_destroy(o);
-  if (p->lane4) (void)dvs_stream_destroy(p->lane4);
-  if (p->arena) (void)hipFree(p->arena);
-  delete p;
+  delete p;   // (the events, the lane-4 stream, then the arena)
 }
 
 dvs_status dvs_pipeline_attach_comm(dvs_pipeline* p, dvs_comm* comm) {

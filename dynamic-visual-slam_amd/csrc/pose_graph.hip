@@ -510,7 +510,7 @@ dvs_status check_edges(int32_t N, int32_t E, const int32_t* i, const int32_t* j,
 
 struct dvs_pgo {
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;   // declared before the blocks: it outlives them
   int N = 0, E = 0;
   // host copies
   std::vector<double> R0, t0, q, t;          // "before" as given; the current quaternion and translation
@@ -656,7 +656,7 @@ dvs_status dvs_pgo_create(int32_t device, dvs_pgo** out) {
   dvs_pgo* h = new (std::nothrow) dvs_pgo();
   if (!h) { set_error("out of host memory"); return DVS_ERR_HIP; }
   h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  const hipError_t e = h->stream.create();
   if (e != hipSuccess) { delete h; set_error("hipStreamCreate: %s", hipGetErrorString(e)); return DVS_ERR_HIP; }
   *out = h;
   return DVS_OK;
@@ -666,7 +666,6 @@ void dvs_pgo_destroy(dvs_pgo* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  (void)hipStreamDestroy(h->stream);
   delete h;
 }
 

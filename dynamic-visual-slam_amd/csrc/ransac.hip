@@ -961,6 +961,79 @@ __global__ void k_ransac_prob(RansacProb* __restrict__ prob, const int* __restri
   if (threadIdx.x == 0 && blockIdx.x == 0) *prob = RansacProb{0, *d_n, seed};
 }
 
+// Results up to this size leave through the export kernel and a polled sequence number (no copy command, no wake-up), larger ones
+// by a copy command and the stream wait.
+constexpr size_t kExportMax = 65536;
+
+// A batch of F problems in scratch slot 0 and, without the work region, in the pinned block — one definition for the device carve,
+// the host placement and the host unpack.
+//   in   [problem records | pts1 | pts2 | samples 7 x nsamples (cv form)], blocks of 16 bytes: placed by the host, imported
+//   work [models 72 x nmodels | valid | counts], device only (nmodels = 0: none)
+//   out  [sel 16 x nprob | F 72 x nprob | mask total], whole dwords: fetched
+struct FmIo {
+  RansacProb* probs; float *p1, *p2; int32_t* samples;
+  double* models; int *valid, *counts;
+  int* sel; double* F; uint8_t* mask;
+  size_t sampb, inb, outb, bytes;   // the samples block, in, out, everything
+  FmIo(uint8_t* base, int nprob, int total, size_t nsamples, size_t nmodels) {
+    Carver c{base, 16};
+    c.take(probs, nprob); c.take(p1, 2 * (size_t)total); c.take(p2, 2 * (size_t)total);
+    samples = nullptr; sampb = c.used;
+    if (nsamples) c.take(samples, 7 * nsamples);
+    inb = c.used; sampb = inb - sampb;
+    c.align = 4;
+    models = nullptr; valid = counts = nullptr;
+    if (nmodels) { c.take(models, 9 * nmodels); c.take(valid, nmodels); c.take(counts, nmodels); }
+    const size_t out0 = c.used;
+    c.take(sel, 4 * (size_t)nprob); c.take(F, 9 * (size_t)nprob); c.take(mask, total);
+    outb = c.used - out0; bytes = c.used;
+  }
+  // out of the fetched region: inlier counts (0 where nothing was selected), models, masks
+  void unpack(int nprob, int total, double* F9, uint8_t* inlier_mask, int32_t* n_inliers) const {
+    for (int b = 0; b < nprob; b++)
+      if (n_inliers) n_inliers[b] = sel[4 * b] >= 0 ? sel[4 * b + 2] : 0;
+    if (F9) memcpy(F9, F, (size_t)nprob * 72);
+    if (total) memcpy(inlier_mask, mask, (size_t)total);
+  }
+};
+
+// The same for a batch of PnP problems; the work region differs between the two estimators and is carved by the caller at `work`.
+//   in   [problem records | object points 12 x total | image points 8 x total | samples 5 x nsamples (cv form)], blocks of 16 bytes
+//   work workb bytes, device only
+//   out  [result records 64 x nprob | inlier lists 4 x total | select records 16 x nprob (cv form: sel_tail)]
+struct PnpIo {
+  RansacProb* probs; float *obj, *img; int32_t* samples;
+  uint8_t *work, *rec; int *inl, *sel;
+  size_t sampb, inb, outb, bytes;
+  PnpIo(uint8_t* base, int nprob, int total, size_t nsamples, size_t workb, bool sel_tail) {
+    Carver c{base, 16};
+    c.take(probs, nprob); c.take(obj, 3 * (size_t)total); c.take(img, 2 * (size_t)total);
+    samples = nullptr; sampb = c.used;
+    if (nsamples) c.take(samples, 5 * nsamples);
+    inb = c.used; sampb = inb - sampb;
+    c.align = 4;
+    work = nullptr;
+    if (workb) c.take(work, workb);
+    const size_t out0 = c.used;
+    c.take(rec, 64 * (size_t)nprob); c.take(inl, total);
+    sel = nullptr;
+    if (sel_tail) c.take(sel, 4 * (size_t)nprob);
+    outb = c.used - out0; bytes = c.used;
+  }
+  // out of the fetched region; a pose is written where the estimator succeeded, or (by_sel: the cv form) wherever a model was selected
+  void unpack(int nprob, const int32_t* offsets, bool by_sel, double* rvec3, double* tvec3, int32_t* inliers, int32_t* n_inliers, int32_t* success) const {
+    for (int b = 0; b < nprob; b++) {
+      const uint8_t* r = rec + 64 * (size_t)b;
+      int nin = 0, succ = 0;
+      memcpy(&nin, r, 4); memcpy(&succ, r + 4, 4);
+      if (n_inliers) n_inliers[b] = nin;
+      success[b] = succ;
+      if (by_sel ? sel[4 * b] >= 0 : succ != 0) { memcpy(rvec3 + 3 * (size_t)b, r + 16, 24); memcpy(tvec3 + 3 * (size_t)b, r + 40, 24); }
+      if (inliers && nin > 0) memcpy(inliers + offsets[b], inl + offsets[b], (size_t)nin * 4);
+    }
+  }
+};
+
 // one pass over `nprob` problems with the models of the first H iterations; unfinished[b] = 1 where the loop wanted more than H
 // (lmeds: the problems are below 15 points — H = the fixed iteration count, k_lmeds_select instead of score / select / mask,
 //  unfinished[b] = 1 where the call FAILED, i.e. fewer than 7 inliers: OpenCV returns an empty matrix then, the mask stays as written)
@@ -971,57 +1044,29 @@ static dvs_status fm_cv_pass(dvs_matcher* ctx, int32_t nprob, const int32_t* off
   for (int b = 0; b < nprob; b++) maxn = std::max(maxn, offsets[b + 1] - offsets[b]);
   const int total = offsets[nprob];
   hipStream_t st = ctx->stream;
-  const int H3 = 3 * H;
-  const size_t hb = ((size_t)nprob * sizeof(RansacProb) + 15) & ~(size_t)15, pb = ((size_t)total * 8 + 15) & ~(size_t)15;
-  const size_t sb = ((size_t)nprob * H * 7 * 4 + 15) & ~(size_t)15;
-  const size_t inb = hb + 2 * pb + sb;
-  const size_t fb = (size_t)nprob * H3 * 72, vb = (size_t)nprob * H3 * 4;
-  const size_t outb = ((size_t)nprob * (16 + 72) + (size_t)total + 3) & ~(size_t)3;
+  const size_t nsamples = (size_t)nprob * H, nmodels = 3 * nsamples;
   uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, inb + fb + 2 * vb + outb + 64, (void**)&base));
-  const RansacProb* d_probs = (const RansacProb*)base;
-  float* d_p1 = (float*)(base + hb); float* d_p2 = (float*)(base + hb + pb);
-  const int32_t* d_samples = (const int32_t*)(base + hb + 2 * pb);
-  double* d_F = (double*)(base + inb);
-  int* d_valid = (int*)(base + inb + fb); int* d_counts = (int*)(base + inb + fb + vb);
-  uint8_t* d_out = base + inb + fb + 2 * vb;
-  int* d_sel = (int*)d_out; double* d_Fb = (double*)(d_out + (size_t)nprob * 16); unsigned char* d_mask = d_out + (size_t)nprob * 88;
-  uint8_t* hio; int *hseq, *counter;
-  DVS_TRY(matcher_pinned(ctx, inb + outb, (void**)&hio, &hseq, &counter));
-  RansacProb* hp = (RansacProb*)hio;
-  memcpy(hio + hb, pts1, (size_t)total * 8); memcpy(hio + hb + pb, pts2, (size_t)total * 8);
-  int32_t* hs = (int32_t*)(hio + hb + 2 * pb);
-  memset(hs, 0, sb);
+  DVS_TRY(matcher_scratch(ctx, 0, FmIo(nullptr, nprob, total, nsamples, nmodels).bytes + 64, (void**)&base));
+  const FmIo d(base, nprob, total, nsamples, nmodels);
+  PinnedIo* io;
+  DVS_TRY(matcher_pinned(ctx, d.inb + d.outb, &io));
+  const FmIo h(io->h(), nprob, total, nsamples, 0);
+  memcpy(h.p1, pts1, (size_t)total * 8); memcpy(h.p2, pts2, (size_t)total * 8);
+  memset(h.samples, 0, h.sampb);
   for (int b = 0; b < nprob; b++) {
     const int n = offsets[b + 1] - offsets[b];
-    const int found = cv_subsets(pts1 + 2 * (size_t)offsets[b], pts2 + 2 * (size_t)offsets[b], n, 7, H, hs + (size_t)b * H * 7, lmeds ? 1000 : 10000);
-    hp[b] = RansacProb{offsets[b], n, (unsigned long long)found};   // the seed field carries the iterations that have a sample
+    const int found = cv_subsets(pts1 + 2 * (size_t)offsets[b], pts2 + 2 * (size_t)offsets[b], n, 7, H, h.samples + (size_t)b * H * 7, lmeds ? 1000 : 10000);
+    h.probs[b] = RansacProb{offsets[b], n, (unsigned long long)found};   // the seed field carries the iterations that have a sample
   }
-  const int ndw_in = (int)(inb / 4);
-  hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
-  launch_fm_cv(st, nprob, maxn, d_probs, d_p1, d_p2, d_samples, H, lmeds, threshold, confidence, max_iters, d_F, d_valid, d_counts, d_sel, d_mask, d_Fb);
-  uint8_t* hout = hio + inb;
-  if (outb <= 65536) {
-    const int seq = ++*counter;
-    hipLaunchKernelGGL(k_io_export, dim3(1), dim3(256), 0, st, (const uint32_t*)d_out, (uint32_t*)hout, (int)(outb / 4), hseq, seq);
-    DVS_HIP(hipGetLastError());
-    DVS_TRY(io_wait(hseq, seq, st));
-  } else {
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipMemcpyAsync(hout, d_out, outb, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipStreamSynchronize(st));
-  }
-  const int* sel = (const int*)hout;
+  io->import(st, base, d.inb);
+  launch_fm_cv(st, nprob, maxn, d.probs, d.p1, d.p2, d.samples, H, lmeds, threshold, confidence, max_iters, d.models, d.valid, d.counts, d.sel, d.mask, d.F);
+  DVS_TRY(io->fetch(st, d.sel, h.sel, d.outb, kExportMax));
+  h.unpack(nprob, total, F9, inlier_mask, n_inliers);
   for (int b = 0; b < nprob; b++) {
-    if (n_inliers) n_inliers[b] = sel[4 * b] >= 0 ? sel[4 * b + 2] : 0;
-    if (iterations) iterations[b] = sel[4 * b + 1];
-    unfinished[b] = lmeds ? (uint8_t)(sel[4 * b + 3] ? 0 : 1) : (uint8_t)sel[4 * b + 3];
-    if (F9) {
-      if (lmeds && !sel[4 * b + 3]) memset(F9 + 9 * (size_t)b, 0, 72);
-      else memcpy(F9 + 9 * (size_t)b, hout + (size_t)nprob * 16 + 72 * (size_t)b, 72);
-    }
+    if (iterations) iterations[b] = h.sel[4 * b + 1];
+    unfinished[b] = lmeds ? (uint8_t)(h.sel[4 * b + 3] ? 0 : 1) : (uint8_t)h.sel[4 * b + 3];
+    if (F9 && lmeds && !h.sel[4 * b + 3]) memset(F9 + 9 * (size_t)b, 0, 72);   // the call failed: OpenCV returns an empty matrix
   }
-  memcpy(inlier_mask, hout + (size_t)nprob * 88, (size_t)total);
   return DVS_OK;
 }
 
@@ -1137,8 +1182,9 @@ dvs_status fm_cv_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, 
   const bool lmeds = n < 15;
   const int Hfull = lmeds ? std::max(ransac_update_iters_host(confidence, 0.45, 7, max_iters), 3) : max_iters;
   const size_t pb = ((size_t)n * 8 + 15) & ~(size_t)15, sbmax = ((size_t)Hfull * 7 * 4 + 15) & ~(size_t)15;
-  uint8_t* hio; int *hseq, *counter;
-  DVS_TRY(matcher_pinned(ctx, 2 * pb + 16 + sbmax + 128, (void**)&hio, &hseq, &counter));
+  PinnedIo* io;
+  DVS_TRY(matcher_pinned(ctx, 2 * pb + 16 + sbmax + 128, &io));
+  uint8_t* hio = io->h();
   float* hp1 = (float*)hio; float* hp2 = (float*)(hio + pb);
   uint8_t* hin = hio + 2 * pb;                 // [problem record | samples] of a pass
   int* hsel = (int*)(hio + 2 * pb + 16 + sbmax);
@@ -1159,14 +1205,10 @@ dvs_status fm_cv_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, 
     double* d_F = (double*)(base + inb);
     int* d_valid = (int*)(base + inb + fb); int* d_counts = (int*)(base + inb + fb + vb);
     int* d_sel = (int*)(base + inb + fb + 2 * vb); double* d_Fb = (double*)(base + inb + fb + 2 * vb + 16);
-    const int ndw_in = (int)(inb / 4);
-    hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hin, (uint32_t*)base, ndw_in);
+    io->import(st, base, inb, 2 * pb);
     launch_fm_cv(st, 1, n, (const RansacProb*)base, d_p1, d_p2, (const int32_t*)(base + 16), H, lmeds, threshold, confidence, max_iters, d_F, d_valid, d_counts,
                  d_sel, d_mask, d_Fb);
-    const int seq = ++*counter;
-    hipLaunchKernelGGL(k_io_export, dim3(1), dim3(256), 0, st, (const uint32_t*)d_sel, (uint32_t*)hsel, 4, hseq, seq);
-    DVS_HIP(hipGetLastError());
-    DVS_TRY(io_wait(hseq, seq, st));
+    DVS_TRY(io->fetch(st, d_sel, hsel, 16, 16));   // the select record alone: the mask stays on the device
     if (lmeds || !hsel[3] || H >= max_iters) break;
     H = max_iters;
   }
@@ -1184,14 +1226,13 @@ dvs_status pnp_cv_device(dvs_matcher* ctx, const float* d_obj, const float* d_im
   const size_t mb = (size_t)H * 18 * 8, vb = (size_t)H * 4;
   uint8_t* base;
   DVS_TRY(matcher_scratch(ctx, 0, inb + mb + vb + 64, (void**)&base));
-  uint8_t* hio; int *hseq, *counter;
-  DVS_TRY(matcher_pinned(ctx, inb, (void**)&hio, &hseq, &counter));
-  int32_t* hs = (int32_t*)(hio + 16);
+  PinnedIo* io;
+  DVS_TRY(matcher_pinned(ctx, inb, &io));
+  int32_t* hs = (int32_t*)(io->h() + 16);
   memset(hs, 0, sb);
   cv_subsets_nocheck(n, 5, H, hs);
-  *(RansacProb*)hio = RansacProb{0, n, (unsigned long long)H};
-  const int ndw_in = (int)(inb / 4);
-  hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
+  *(RansacProb*)io->h() = RansacProb{0, n, (unsigned long long)H};
+  io->import(st, base, inb);   // (returns with the import still reading the block: PinnedIo::reserve waits before it releases one)
   launch_pnp_cv(st, 1, (const RansacProb*)base, d_obj, d_img, (const int*)(base + 16), H, K4, reproj_err, confidence, (double*)(base + inb),
                 (int*)(base + inb + mb), d_sel4, d_inl, d_out64);
   DVS_HIP(hipGetLastError());
@@ -1247,44 +1288,20 @@ static dvs_status fm_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* o
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int H = max_iters;
-  const size_t hb = ((size_t)nprob * sizeof(RansacProb) + 15) & ~(size_t)15, pb = ((size_t)total * 8 + 15) & ~(size_t)15;
-  const size_t inb = hb + 2 * pb;
-  const size_t fb = (size_t)nprob * H * 72, vb = (size_t)nprob * H * 4;
-  const size_t outb = ((size_t)nprob * (16 + 72) + (size_t)total + 3) & ~(size_t)3;
+  const size_t nmodels = (size_t)nprob * H;
   uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, inb + fb + 2 * vb + outb + 64, (void**)&base));
-  const RansacProb* d_probs = (const RansacProb*)base;
-  float* d_p1 = (float*)(base + hb); float* d_p2 = (float*)(base + hb + pb);
-  double* d_F = (double*)(base + inb);
-  int* d_valid = (int*)(base + inb + fb); int* d_counts = (int*)(base + inb + fb + vb);
-  uint8_t* d_out = base + inb + fb + 2 * vb;                       // [sel 16 x nprob | Fb 72 x nprob | mask total]: the pinned block's layout
-  int* d_sel = (int*)d_out; double* d_Fb = (double*)(d_out + (size_t)nprob * 16); unsigned char* d_mask = d_out + (size_t)nprob * 88;
-  uint8_t* hio; int *hseq, *counter;
-  DVS_TRY(matcher_pinned(ctx, inb + outb, (void**)&hio, &hseq, &counter));
-  RansacProb* hp = (RansacProb*)hio;
-  for (int b = 0; b < nprob; b++) hp[b] = RansacProb{offsets[b], offsets[b + 1] - offsets[b], (unsigned long long)seeds[b]};
-  memcpy(hio + hb, pts1, (size_t)total * 8); memcpy(hio + hb + pb, pts2, (size_t)total * 8);
-  const int ndw_in = (int)(inb / 4);
-  hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
-  launch_fm_own(st, nprob, maxn, d_probs, d_p1, d_p2, H, threshold, confidence, d_F, d_valid, d_counts, d_sel, d_mask, d_Fb);
-  DVS_STAGES_SET(d_F, d_valid, d_counts, d_sel);
-  uint8_t* hout = hio + inb;
-  if (outb <= 65536) {   // small results leave through the export kernel + a polled sequence number (no copy command, no wake-up)
-    const int seq = ++*counter;
-    hipLaunchKernelGGL(k_io_export, dim3(1), dim3(256), 0, st, (const uint32_t*)d_out, (uint32_t*)hout, (int)(outb / 4), hseq, seq);
-    DVS_HIP(hipGetLastError());
-    DVS_TRY(io_wait(hseq, seq, st));
-  } else {
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipMemcpyAsync(hout, d_out, outb, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipStreamSynchronize(st));
-  }
-  const int* sel = (const int*)hout;
-  for (int b = 0; b < nprob; b++) {
-    if (n_inliers) n_inliers[b] = sel[4 * b] >= 0 ? sel[4 * b + 2] : 0;
-    if (F9) memcpy(F9 + 9 * (size_t)b, hout + (size_t)nprob * 16 + 72 * (size_t)b, 72);
-  }
-  if (total) memcpy(inlier_mask, hout + (size_t)nprob * 88, (size_t)total);
+  DVS_TRY(matcher_scratch(ctx, 0, FmIo(nullptr, nprob, total, 0, nmodels).bytes + 64, (void**)&base));
+  const FmIo d(base, nprob, total, 0, nmodels);
+  PinnedIo* io;
+  DVS_TRY(matcher_pinned(ctx, d.inb + d.outb, &io));
+  const FmIo h(io->h(), nprob, total, 0, 0);
+  for (int b = 0; b < nprob; b++) h.probs[b] = RansacProb{offsets[b], offsets[b + 1] - offsets[b], (unsigned long long)seeds[b]};
+  memcpy(h.p1, pts1, (size_t)total * 8); memcpy(h.p2, pts2, (size_t)total * 8);
+  io->import(st, base, d.inb);
+  launch_fm_own(st, nprob, maxn, d.probs, d.p1, d.p2, H, threshold, confidence, d.models, d.valid, d.counts, d.sel, d.mask, d.F);
+  DVS_STAGES_SET(d.models, d.valid, d.counts, d.sel);
+  DVS_TRY(io->fetch(st, d.sel, h.sel, d.outb, kExportMax));
+  h.unpack(nprob, total, F9, inlier_mask, n_inliers);
   return DVS_OK;
 }
 dvs_status dvs_find_fundamental_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
@@ -1376,57 +1393,30 @@ dvs_status dvs_solve_pnp_ransac_cv_batch(dvs_matcher* ctx, int32_t nprob, const 
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int H = iterations;
-  const size_t hb = ((size_t)nprob * sizeof(RansacProb) + 15) & ~(size_t)15, ob = ((size_t)total * 12 + 15) & ~(size_t)15, ib = ((size_t)total * 8 + 15) & ~(size_t)15;
-  const size_t sb = ((size_t)nprob * H * 5 * 4 + 15) & ~(size_t)15;
-  const size_t inb = hb + ob + ib + sb;
-  const size_t mb = (size_t)nprob * H * 18 * 8, vb = (size_t)nprob * H * 4, selb = (size_t)nprob * 16;
-  const size_t outb = (size_t)nprob * 64 + (size_t)total * 4 + selb;      // [result records 64 x nprob | inlier lists 4 x total | select records]
+  const size_t nh = (size_t)nprob * H;
+  const size_t workb = nh * (144 + 4);                                    // [models 144 x nh | counts 4 x nh]
   uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, inb + mb + vb + outb + 64, (void**)&base));
-  const RansacProb* d_probs = (const RansacProb*)base;
-  float* d_obj = (float*)(base + hb); float* d_img = (float*)(base + hb + ob);
-  const int* d_samples = (const int*)(base + hb + ob + ib);
-  double* d_models = (double*)(base + inb);
-  int* d_counts = (int*)(base + inb + mb);
-  uint8_t* d_out = base + inb + mb + vb;
-  int* d_inl = (int*)(d_out + (size_t)nprob * 64);
-  int* d_sel = (int*)(d_out + (size_t)nprob * 64 + (size_t)total * 4);
-  uint8_t* hio; int *hseq, *counter;
-  DVS_TRY(matcher_pinned(ctx, inb + outb, (void**)&hio, &hseq, &counter));
-  RansacProb* hp = (RansacProb*)hio;
-  int32_t* hs = (int32_t*)(hio + hb + ob + ib);
-  memset(hs, 0, sb);
+  DVS_TRY(matcher_scratch(ctx, 0, PnpIo(nullptr, nprob, total, nh, workb, true).bytes + 64, (void**)&base));
+  const PnpIo d(base, nprob, total, nh, workb, true);
+  double* d_models; int* d_counts;
+  Carver w{d.work, 4};
+  w.take(d_models, 18 * nh); w.take(d_counts, nh);
+  PinnedIo* io;
+  DVS_TRY(matcher_pinned(ctx, d.inb + d.outb, &io));
+  const PnpIo h(io->h(), nprob, total, nh, 0, true);
+  memset(h.samples, 0, h.sampb);
   for (int b = 0; b < nprob; b++) {
     const int n = offsets[b + 1] - offsets[b];
     const bool run = n >= 6;     // (n == 5 would be solvePnP on all points, n == 4 the P3P kernel: not what the reference can reach)
-    if (run) cv_subsets_nocheck(n, 5, H, hs + (size_t)b * H * 5);
-    hp[b] = RansacProb{offsets[b], n, (unsigned long long)(run ? H : 0)};   // the seed field: iterations that have a sample
+    if (run) cv_subsets_nocheck(n, 5, H, h.samples + (size_t)b * H * 5);
+    h.probs[b] = RansacProb{offsets[b], n, (unsigned long long)(run ? H : 0)};   // the seed field: iterations that have a sample
   }
-  memcpy(hio + hb, pts3d, (size_t)total * 12); memcpy(hio + hb + ob, pts2d, (size_t)total * 8);
-  const int ndw_in = (int)(inb / 4);
-  hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
-  launch_pnp_cv(st, nprob, d_probs, d_obj, d_img, d_samples, H, K4, reproj_err, confidence, d_models, d_counts, d_sel, d_inl, d_out);
-  uint8_t* hout = hio + inb;
-  if (outb <= 65536) {
-    const int seq = ++*counter;
-    hipLaunchKernelGGL(k_io_export, dim3(1), dim3(256), 0, st, (const uint32_t*)d_out, (uint32_t*)hout, (int)(outb / 4), hseq, seq);
-    DVS_HIP(hipGetLastError());
-    DVS_TRY(io_wait(hseq, seq, st));
-  } else {
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipMemcpyAsync(hout, d_out, outb, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipStreamSynchronize(st));
-  }
-  const int* hsel = (const int*)(hout + (size_t)nprob * 64 + (size_t)total * 4);
-  for (int b = 0; b < nprob; b++) {
-    int nin = 0, succ = 0;
-    memcpy(&nin, hout + 64 * (size_t)b, 4); memcpy(&succ, hout + 64 * (size_t)b + 4, 4);
-    if (n_inliers) n_inliers[b] = nin;
-    if (iterations_run) iterations_run[b] = hsel[4 * b + 1];
-    success[b] = succ;
-    if (hsel[4 * b] >= 0) { memcpy(rvec3 + 3 * (size_t)b, hout + 64 * (size_t)b + 16, 24); memcpy(tvec3 + 3 * (size_t)b, hout + 64 * (size_t)b + 40, 24); }
-    if (inliers && nin > 0) memcpy(inliers + offsets[b], hout + (size_t)nprob * 64 + 4 * (size_t)offsets[b], (size_t)nin * 4);
-  }
+  memcpy(h.obj, pts3d, (size_t)total * 12); memcpy(h.img, pts2d, (size_t)total * 8);
+  io->import(st, base, d.inb);
+  launch_pnp_cv(st, nprob, d.probs, d.obj, d.img, d.samples, H, K4, reproj_err, confidence, d_models, d_counts, d.sel, d.inl, d.rec);
+  DVS_TRY(io->fetch(st, d.rec, h.rec, d.outb, kExportMax));
+  h.unpack(nprob, offsets, true, rvec3, tvec3, inliers, n_inliers, success);
+  if (iterations_run) for (int b = 0; b < nprob; b++) iterations_run[b] = h.sel[4 * b + 1];
   return DVS_OK;
 }
 
@@ -1464,48 +1454,25 @@ static dvs_status pnp_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* 
   if (maxn < 4) return DVS_OK;   // cv::solvePnPRansac: "npoints >= 4"
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int H = iterations, H4 = 4 * H;
-  const size_t hb = ((size_t)nprob * sizeof(RansacProb) + 15) & ~(size_t)15, ob = ((size_t)total * 12 + 15) & ~(size_t)15, ib = ((size_t)total * 8 + 15) & ~(size_t)15;
-  const size_t inb = hb + ob + ib;
-  const size_t posb = (size_t)nprob * H4 * 96, vb = (size_t)nprob * H4 * 4, selb = (size_t)nprob * 16;
-  const size_t outb = (size_t)nprob * 64 + (size_t)total * 4;      // [result records 64 x nprob | inlier lists 4 x total]
+  const int H = iterations;
+  const size_t nh4 = (size_t)nprob * 4 * H;
+  const size_t workb = nh4 * (96 + 4 + 4) + (size_t)nprob * 16;   // [poses 96 x nh4 | valid | counts | select records 16 x nprob]
   uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, inb + posb + 2 * vb + selb + outb + 64, (void**)&base));
-  const RansacProb* d_probs = (const RansacProb*)base;
-  float* d_obj = (float*)(base + hb); float* d_img = (float*)(base + hb + ob);
-  double* d_poses = (double*)(base + inb);
-  int* d_valid = (int*)(base + inb + posb); int* d_counts = (int*)(base + inb + posb + vb);
-  int* d_sel = (int*)(base + inb + posb + 2 * vb);
-  uint8_t* d_out = base + inb + posb + 2 * vb + selb;
-  int* d_inl = (int*)(d_out + (size_t)nprob * 64);
-  uint8_t* hio; int *hseq, *counter;
-  DVS_TRY(matcher_pinned(ctx, inb + outb, (void**)&hio, &hseq, &counter));
-  RansacProb* hp = (RansacProb*)hio;
-  for (int b = 0; b < nprob; b++) hp[b] = RansacProb{offsets[b], offsets[b + 1] - offsets[b], (unsigned long long)seeds[b]};
-  memcpy(hio + hb, pts3d, (size_t)total * 12); memcpy(hio + hb + ob, pts2d, (size_t)total * 8);
-  const int ndw_in = (int)(inb / 4);
-  hipLaunchKernelGGL(k_io_import, dim3((ndw_in + 255) / 256), dim3(256), 0, st, (const uint32_t*)hio, (uint32_t*)base, ndw_in);
-  launch_pnp_own(st, nprob, d_probs, d_obj, d_img, H, K4, reproj_err, confidence, d_poses, d_valid, d_counts, d_sel, d_inl, d_out);
+  DVS_TRY(matcher_scratch(ctx, 0, PnpIo(nullptr, nprob, total, 0, workb, false).bytes + 64, (void**)&base));
+  const PnpIo d(base, nprob, total, 0, workb, false);
+  double* d_poses; int *d_valid, *d_counts, *d_sel;
+  Carver w{d.work, 4};
+  w.take(d_poses, 12 * nh4); w.take(d_valid, nh4); w.take(d_counts, nh4); w.take(d_sel, 4 * (size_t)nprob);
+  PinnedIo* io;
+  DVS_TRY(matcher_pinned(ctx, d.inb + d.outb, &io));
+  const PnpIo h(io->h(), nprob, total, 0, 0, false);
+  for (int b = 0; b < nprob; b++) h.probs[b] = RansacProb{offsets[b], offsets[b + 1] - offsets[b], (unsigned long long)seeds[b]};
+  memcpy(h.obj, pts3d, (size_t)total * 12); memcpy(h.img, pts2d, (size_t)total * 8);
+  io->import(st, base, d.inb);
+  launch_pnp_own(st, nprob, d.probs, d.obj, d.img, H, K4, reproj_err, confidence, d_poses, d_valid, d_counts, d_sel, d.inl, d.rec);
   DVS_STAGES_SET(d_poses, d_valid, d_counts, d_sel);
-  uint8_t* hout = hio + inb;
-  if (outb <= 65536) {
-    const int seq = ++*counter;
-    hipLaunchKernelGGL(k_io_export, dim3(1), dim3(256), 0, st, (const uint32_t*)d_out, (uint32_t*)hout, (int)(outb / 4), hseq, seq);
-    DVS_HIP(hipGetLastError());
-    DVS_TRY(io_wait(hseq, seq, st));
-  } else {
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipMemcpyAsync(hout, d_out, outb, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipStreamSynchronize(st));
-  }
-  for (int b = 0; b < nprob; b++) {
-    int nin = 0, succ = 0;
-    memcpy(&nin, hout + 64 * (size_t)b, 4); memcpy(&succ, hout + 64 * (size_t)b + 4, 4);
-    if (n_inliers) n_inliers[b] = nin;
-    success[b] = succ;
-    if (succ) { memcpy(rvec3 + 3 * (size_t)b, hout + 64 * (size_t)b + 16, 24); memcpy(tvec3 + 3 * (size_t)b, hout + 64 * (size_t)b + 40, 24); }
-    if (inliers && nin > 0) memcpy(inliers + offsets[b], hout + (size_t)nprob * 64 + 4 * (size_t)offsets[b], (size_t)nin * 4);
-  }
+  DVS_TRY(io->fetch(st, d.rec, h.rec, d.outb, kExportMax));
+  h.unpack(nprob, offsets, false, rvec3, tvec3, inliers, n_inliers, success);
   return DVS_OK;
 }
 dvs_status dvs_solve_pnp_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,

@@ -316,11 +316,7 @@ static void tracker_reset_state(dvs_tracker* h) {
 
 // the record block to the host: export kernel + polled sequence number (no copy command, no stream wait)
 static dvs_status tracker_export(dvs_tracker* h) {
-  hipStream_t st = h->ctx->stream;
-  const int seq = ++h->seq;
-  hipLaunchKernelGGL(k_io_export, dim3(1), dim3(256), 0, st, (const uint32_t*)h->d_rec.get(), (uint32_t*)h->h_rec.get(), (int)(kRecBytes / 4), h->h_seq.get(), seq);
-  DVS_HIP(hipGetLastError());
-  return io_wait(h->h_seq.get(), seq, st);
+  return io_export_wait(h->ctx->stream, h->d_rec.get(), h->h_rec.get(), kRecBytes, h->h_seq.get(), ++h->seq);
 }
 
 static dvs_status tracker_fm(dvs_tracker* h, const float* p1, const float* p2, const int* d_n, int n, unsigned long long seed, unsigned char* mask) {
