@@ -1343,7 +1343,7 @@ __device__ __forceinline__ void pcg_publish(const PcgState* s, PcgState* host) {
 }
 
 // One workgroup; a thread owns the cameras tid, tid + 256, ..
-//   mode 0  start of a solve: x = 0, r = b, z = M^-1 r, p = z
+//   mode 0  start of a solve: x = 0, r = b, z = M^-1 r, p = z; |b| = 0 ends it there (x = 0 solves it: zero iterations, a valid step)
 //   mode 1  one iteration: q = S p from the diagonal blocks and k_gba_cam's chunk sums, alpha = r.z / p.q, x += alpha p, r -= alpha q,
 //           z = M^-1 r, the stopping rule (|r| <= eta |b| or max_it iterations), else beta and p = z + beta p.  p.q <= 0 or not finite
 //           ends the solve; before the first iteration that makes the trial step invalid (st->ok = 0).
@@ -1370,7 +1370,8 @@ __global__ __launch_bounds__(256) void k_gba_update(GbaDev P, int mode, double r
     }
     double v[2] = {rz, bn};
     block_sums<256, 2>(v, &sm[0][0]);
-    if (tid == 0) { S->rz = v[0]; S->bnorm2 = v[1]; S->rnorm2 = v[1]; S->iter = 0; S->done = 0; S->ok = 1; }
+    // |b| = 0: x = 0 is the solution, the solve is over before its first iteration and the step is valid
+    if (tid == 0) { S->rz = v[0]; S->bnorm2 = v[1]; S->rnorm2 = v[1]; S->iter = 0; S->done = v[1] == 0.0 ? 1 : 0; S->ok = 1; }
     return;
   }
   if (mode == 1 && S->done) {
@@ -1562,6 +1563,7 @@ struct dvs_ba {
   GbaView gwork{};
   bool gba_ready = false;
   int gba_nc = 0;
+  bool gba_stepping = false;   // the global step hook of the test library has run the prologue (as lm_stepping)
   std::vector<int> pcg_iters;         // dvs_ba_get_pcg_trace: one row per trial step of the last dvs_ba_solve_global
   std::vector<double> pcg_rel;
   std::vector<double> trace;          // dvs_ba_get_trace: 6 doubles per trust-region iteration of the last solve
@@ -1576,7 +1578,7 @@ namespace {
 // forget the current problem (the arenas and pinned blocks stay)
 void ba_reset(dvs_ba* h) {
   h->prob = {}; h->work = {}; h->raw_buf = {}; h->gwork = {};
-  h->lm_ready = false; h->gba_ready = false; h->lm_stepping = false;
+  h->lm_ready = false; h->gba_ready = false; h->lm_stepping = false; h->gba_stepping = false;
 }
 
 // copies a host table into the staging block S at the place its buffer `dev` has in the arena at B
@@ -2021,6 +2023,7 @@ dvs_status dvs_ba_solve(dvs_ba* h, int32_t max_iterations, double ftol, double g
   DVS_HIP(hipSetDevice(h->device));
   const int K = h->K, L = h->L, R = h->R, NT = 6 * K + 3 * L;
   if (R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
+  h->lm_stepping = false; h->gba_stepping = false;   // the step hooks of the test library start over from the problem's point
   const ProbView& dev = h->prob;
   std::vector<double> Hpp((size_t)K * 36), Hll((size_t)L * 9), W((size_t)R * 18), g(NT);
   double x_cost = 0;
@@ -2196,7 +2199,7 @@ dvs_status dvs_ba_solve_device(dvs_ba* h, int32_t max_iterations, double ftol, d
   DVS_HIP(hipSetDevice(h->device));
   if (h->R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
   DVS_TRY(lm_plan(h));
-  h->lm_stepping = false;   // the step hook of the test library starts over from the problem's point
+  h->lm_stepping = false; h->gba_stepping = false;   // the step hooks of the test library start over from the problem's point
   h->trace.clear();
   // two host records: the gated k_lm_gmax of an accepted step runs while the host may still be reading the trial's numbers, so it
   // must not publish over them
@@ -2344,6 +2347,28 @@ dvs_status gba_linear_solve(dvs_ba* h, const GbaDev& G, double radius, bool refr
 }
 double pcg_rel_residual(const PcgState& s) { return s.bnorm2 > 0.0 ? sqrt(s.rnorm2) / sqrt(s.bnorm2) : 0.0; }
 
+// ONE trial step of dvs_ba_solve_global's loop at `radius` from the point whose cost is x_cost (the step hook of the test library
+// calls the same), in two halves.  gba_trial_finish, from the camera steps in w.step on: the tail the two device solvers share, ONE
+// status record read, the verdict — the host's own validity and tolerance tests, then the device's (k_lm_norms, the same numbers)
+// for the relative decrease — and, if `commit` and the verdict accepts, the candidate becomes the point (full evaluation, its record
+// in the second host record).  gba_trial_step: the linear solve, then that.
+struct GbaTrial { PcgState pcg; TrialRecord rec; StepVerdict v; };
+dvs_status gba_trial_finish(dvs_ba* h, double ptol, double ftol, double x_cost, bool commit, GbaTrial* o) {
+  LmStatus* S = gba_status(h);
+  DVS_TRY(lm_enqueue_trial_tail(h, h->gwork, ptol, ftol, S));
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipStreamSynchronize(h->stream));
+  o->rec = trial_record(*S);
+  o->v = verdict_device_decides_decrease(o->rec, S->accept != 0, x_cost, ptol, ftol);
+  if (commit && o->v.kind == kStepAccepted) DVS_TRY(gba_evaluate_full(h, true));
+  return DVS_OK;
+}
+dvs_status gba_trial_step(dvs_ba* h, const GbaDev& G, double radius, bool refresh, double eta, int max_pcg, double ptol, double ftol,
+                          double x_cost, bool commit, GbaTrial* o) {
+  DVS_TRY(gba_linear_solve(h, G, radius, refresh, eta, max_pcg, &o->pcg));
+  return gba_trial_finish(h, ptol, ftol, x_cost, commit, o);
+}
+
 }  // namespace
 
 dvs_status dvs_ba_default_global_params(dvs_ba_global_params* p) {
@@ -2383,7 +2408,8 @@ dvs_status dvs_ba_solve_global(dvs_ba* h, const dvs_ba_global_params* params, dv
   const double ftol = prm.function_tolerance, gtol = prm.gradient_tolerance, ptol = prm.parameter_tolerance, eta = prm.eta;
   const int max_pcg = gba_max_pcg(h, prm.max_pcg_iterations);
   const GbaDev G = gba_view(h);
-  LmStatus *S = gba_status(h), *SP = S + 1;
+  const LmStatus* SP = gba_status(h) + 1;
+  h->lm_stepping = false; h->gba_stepping = false;   // the step hooks of the test library start over from the problem's point
   h->trace.clear(); h->pcg_iters.clear(); h->pcg_rel.clear();
   DVS_TRY(gba_prologue(h));
   double x_cost = SP->x_cost, gmax = SP->gmax;
@@ -2393,21 +2419,14 @@ dvs_status dvs_ba_solve_global(dvs_ba* h, const dvs_ba_global_params* params, dv
   TrustRegion tr;
   while (go_on(tr.next(prm.max_iterations, gmax, gtol), &summary->termination)) {
     const double radius = tr.radius;
-    PcgState pcg;
-    DVS_TRY(gba_linear_solve(h, G, radius, !tr.reuse_diagonal, eta, max_pcg, &pcg));
-    out->pcg_iterations += pcg.iter;
-    h->pcg_iters.push_back(pcg.iter);
-    h->pcg_rel.push_back(pcg_rel_residual(pcg));
-    DVS_TRY(lm_enqueue_trial_tail(h, h->gwork, ptol, ftol, S));
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipStreamSynchronize(h->stream));
-    const TrialRecord rec = trial_record(*S);
-    // the host's own validity and tolerance tests, then the device's verdict (k_lm_norms, the same numbers) for the relative decrease
-    const StepVerdict v = verdict_device_decides_decrease(rec, S->accept != 0, x_cost, ptol, ftol);
-    h->log(radius, v, rec);
-    if (!go_on(tr.update(v), &summary->termination)) break;
-    if (v.kind == kStepAccepted) {
-      DVS_TRY(gba_evaluate_full(h, true));
+    GbaTrial T;
+    DVS_TRY(gba_trial_step(h, G, radius, !tr.reuse_diagonal, eta, max_pcg, ptol, ftol, x_cost, true, &T));
+    out->pcg_iterations += T.pcg.iter;
+    h->pcg_iters.push_back(T.pcg.iter);
+    h->pcg_rel.push_back(pcg_rel_residual(T.pcg));
+    h->log(radius, T.v, T.rec);
+    if (!go_on(tr.update(T.v), &summary->termination)) break;
+    if (T.v.kind == kStepAccepted) {   // the trial step has made the candidate the point
       x_cost = SP->x_cost; gmax = SP->gmax;
       summary->num_successful_steps++; min_cost = std::min(min_cost, x_cost);
     }
@@ -2423,6 +2442,7 @@ dvs_status dvs_ba_schur_probe(dvs_ba* h, double radius, const double* x_in, doub
   DVS_ARG(h && x_in && y_out && Minv_out && b_out && radius > 0.0);
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(gba_prepare(h));
+  h->lm_stepping = false; h->gba_stepping = false;
   const int K = h->K, L = h->L;
   hipStream_t st = h->stream;
   const GbaView& w = h->gwork;
@@ -2444,18 +2464,81 @@ dvs_status dvs_ba_schur_probe(dvs_ba* h, double radius, const double* x_in, doub
   return DVS_OK;
 }
 // one linear solve at the problem's current point, through gba_prologue / gba_linear_solve as a trial step of dvs_ba_solve_global
-// runs them: the PCG's x (scaled, as solved), the iterations run and the recurrence's |r| / |b|; *ok = 0 when the solve stopped before
-// its first iteration
+// runs them: the PCG's x (scaled, as solved), the iterations run and the recurrence's |r| / |b|; *ok = 0 when the solve stopped by
+// breakdown before its first iteration
 dvs_status dvs_ba_pcg_probe(dvs_ba* h, double radius, double eta, int32_t max_pcg_iterations, double* x_out, int32_t* iterations,
                             double* rel_residual, int32_t* ok) {
   DVS_ARG(h && x_out && iterations && rel_residual && ok && radius > 0.0 && eta > 0.0 && eta < 1.0 && max_pcg_iterations >= 0);
   DVS_HIP(hipSetDevice(h->device));
   DVS_TRY(gba_prepare(h));
+  h->lm_stepping = false; h->gba_stepping = false;
   DVS_TRY(gba_prologue(h));
   PcgState pcg;
   DVS_TRY(gba_linear_solve(h, gba_view(h), radius, true, eta, gba_max_pcg(h, max_pcg_iterations), &pcg));
   *iterations = pcg.iter; *ok = pcg.ok; *rel_residual = pcg_rel_residual(pcg);
   DVS_HIP(hipMemcpy(x_out, h->gwork.step, (size_t)h->K * 6 * 8, hipMemcpyDeviceToHost));
+  return DVS_OK;
+}
+
+// one trial step of dvs_ba_solve_global at the caller's radius, through gba_prologue / gba_trial_step as the loop calls them, and what
+// it left in the workspace.  x_in: camera rows that take the place of the linear solve's (the system's launches, then
+// gba_trial_finish): the only way to a step that is no PCG iterate
+dvs_status dvs_ba_global_step_probe(dvs_ba* h, double radius, int32_t refresh, int32_t commit, double eta, int32_t max_pcg_iterations,
+                                    double ftol, double ptol, const double* x_in, double* scale_out, double* diag_out, double* Vinv_out,
+                                    double* x_out, double* step_out, double* cand_q, double* cand_t, double* cand_X,
+                                    int32_t* pcg_iterations, double* pcg_rel, int32_t* pcg_ok, dvs_ba_step_record* rec) {
+  DVS_ARG(h && radius > 0.0 && eta > 0.0 && eta < 1.0 && max_pcg_iterations >= 0 && ftol >= 0.0 && ptol >= 0.0);
+  DVS_HIP(hipSetDevice(h->device));
+  if (!h->gba_ready) h->gba_stepping = false;
+  DVS_TRY(gba_prepare(h));
+  h->lm_stepping = false;   // the window solver's hook starts over: this one evaluates into the same buffers
+  const int K = h->K, L = h->L, NT = 6 * K + 3 * L;
+  const ProbView& dev = h->prob;
+  const GbaView& w = h->gwork;
+  if (!h->gba_stepping) {
+    DVS_TRY(gba_prologue(h));
+    h->gba_stepping = true;
+  }
+  const double x_cost = gba_status(h)[1].x_cost;
+  GbaTrial T;
+  if (x_in) {
+    std::vector<double> x(x_in, x_in + 6 * (size_t)K);
+    for (int c = 0; c < K; c++) if (h->pose_fixed[c]) for (int a = 0; a < 6; a++) x[6 * (size_t)c + a] = 0.0;
+    gba_enqueue_system(h, gba_view(h), radius, refresh != 0);
+    DVS_HIP(hipMemcpyAsync(w.step, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
+    DVS_HIP(hipStreamSynchronize(h->stream));   // x leaves scope
+    T.pcg = PcgState{}; T.pcg.ok = 1;
+    DVS_TRY(gba_trial_finish(h, ptol, ftol, x_cost, commit != 0, &T));
+  } else {
+    DVS_TRY(gba_trial_step(h, gba_view(h), radius, refresh != 0, eta, gba_max_pcg(h, max_pcg_iterations), ptol, ftol, x_cost, commit != 0, &T));
+  }
+  // a committed accept evaluates the candidate where it lies and copies it to the point: the step, the candidate in the evaluation
+  // buffers and the first host record are still the trial's
+  const LmStatus S = *gba_status(h);
+  std::vector<double> sc(NT), stp(NT);
+  DVS_HIP(hipMemcpy(sc.data(), w.scale, (size_t)NT * 8, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(stp.data(), w.step, (size_t)NT * 8, hipMemcpyDeviceToHost));
+  if (scale_out) memcpy(scale_out, sc.data(), (size_t)NT * 8);
+  if (diag_out) DVS_HIP(hipMemcpy(diag_out, w.diag, (size_t)NT * 8, hipMemcpyDeviceToHost));
+  if (Vinv_out) {
+    std::vector<unsigned char> act(NT);
+    DVS_HIP(hipMemcpy(act.data(), w.active, (size_t)NT, hipMemcpyDeviceToHost));
+    DVS_HIP(hipMemcpy(Vinv_out, w.Vinv, (size_t)L * 72, hipMemcpyDeviceToHost));
+    for (int l = 0; l < L; l++) if (!act[6 * (size_t)K + 3 * (size_t)l]) memset(Vinv_out + 9 * (size_t)l, 0, 72);   // never written
+  }
+  if (x_out) memcpy(x_out, stp.data(), (size_t)K * 48);
+  if (step_out) for (int j = 0; j < NT; j++) step_out[j] = j < 6 * K ? -stp[j] * sc[j] : stp[j] * sc[j];   // as k_lm_candidate applies it
+  if (cand_q) DVS_HIP(hipMemcpy(cand_q, dev.q, (size_t)K * 32, hipMemcpyDeviceToHost));
+  if (cand_t) DVS_HIP(hipMemcpy(cand_t, dev.t, (size_t)K * 24, hipMemcpyDeviceToHost));
+  if (cand_X) DVS_HIP(hipMemcpy(cand_X, dev.X, (size_t)L * 24, hipMemcpyDeviceToHost));
+  if (pcg_iterations) *pcg_iterations = T.pcg.iter;
+  if (pcg_rel) *pcg_rel = pcg_rel_residual(T.pcg);
+  if (pcg_ok) *pcg_ok = T.pcg.ok;
+  if (rec) {
+    rec->ok = S.ok; rec->finite = S.finite; rec->accept = S.accept; rec->reserved = 0;
+    rec->model_change = S.model_change; rec->sn = S.sn; rec->xn = S.xn; rec->cand_cost = S.cand_cost;
+    rec->gmax = S.gmax; rec->x_cost = S.x_cost;
+  }
   return DVS_OK;
 }
 
@@ -2469,6 +2552,7 @@ dvs_status dvs_ba_step_probe(dvs_ba* h, double radius, int32_t refresh, int32_t 
   const int K = h->K, L = h->L, NT = 6 * K + 3 * L;
   if (h->R == 0) { set_error("no observations"); return DVS_ERR_ARG; }
   if (!h->lm_ready) h->lm_stepping = false;
+  h->gba_stepping = false;
   DVS_TRY(lm_plan(h));
   hipStream_t st = h->stream;
   const ProbView& dev = h->prob;

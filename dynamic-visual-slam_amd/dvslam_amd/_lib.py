@@ -375,6 +375,8 @@ def test_lib():
         L.dvs_ba_schur_probe.argtypes = [vp, dbl, vp, vp, vp, vp]
         L.dvs_ba_pcg_probe.argtypes = [vp, dbl, dbl, i32, vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i32)]
     L.dvs_ba_step_probe.argtypes = [vp, dbl, i32, i32, dbl, dbl] + [vp] * 9 + [C.POINTER(BaStepRecord)]
+    L.dvs_ba_global_step_probe.argtypes = ([vp, dbl, i32, i32, dbl, i32, dbl, dbl] + [vp] * 9
+                                           + [C.POINTER(i32), C.POINTER(dbl), C.POINTER(i32), C.POINTER(BaStepRecord)])
     _test_lib = L
     return L
 

@@ -9,7 +9,8 @@ class BAProblem:
     """Direct driver of the dvs_ba_* C-ABI: problem in the optimiser's parameterisation (bundle_adjustment.hpp:92-165)."""
 
     def __init__(self, prob, device=0, hooks=False):
-        """hooks: make every call through the test-hook library (schur_probe / pcg_probe / step_probe need it)"""
+        """hooks: make every call through the test-hook library (schur_probe / pcg_probe / step_probe / global_step_probe
+        need it)"""
         self._L = test_lib() if hooks else lib()
         h = C.c_void_p()
         check(self._L.dvs_ba_create(device, C.byref(h)))
@@ -152,6 +153,29 @@ class BAProblem:
         rec = BaStepRecord()
         check(self._L.dvs_ba_step_probe(self._h, float(radius), int(bool(refresh)), int(bool(commit)), float(ftol), float(ptol),
                                         *[ptr(o[k]) for k in ("scale", "diag", "Vinv", "S", "rhs", "step", "q", "t", "X")], C.byref(rec)))
+        for k, _ in BaStepRecord._fields_:
+            if k != "reserved":
+                o[k] = getattr(rec, k)
+        return o
+
+    def global_step_probe(self, radius, refresh=True, commit=False, eta=0.1, max_pcg_iterations=0, ftol=1e-6, ptol=1e-8, x_in=None):
+        """dvs_ba_global_step_probe (hooks=True): one trial step of solve_global at `radius` through the loop's own trial-step
+        function.  The first call on a problem (or after a solve or another probe) runs the loop's prologue; later calls keep point
+        and scaling.  x_in [6K]: camera rows (scaled, as solved) to use in place of the linear solve's.  Returns a dict: scale, diag [6K + 3L], Vinv [L, 3, 3], x [6K] (the PCG's camera rows, scaled, as solved), step
+        [6K + 3L] (parameter units, as applied), q, t, X (the candidate), pcg_iterations, pcg_rel_residual, pcg_ok and the status
+        record's fields ok, finite, accept, model_change, sn, xn, cand_cost, gmax, x_cost."""
+        from ._lib import BaStepRecord
+        K, L = self.K, self.L
+        N = 6 * K + 3 * L
+        o = dict(scale=np.zeros(N), diag=np.zeros(N), Vinv=np.zeros((L, 3, 3)), x=np.zeros(6 * K), step=np.zeros(N),
+                 q=np.zeros((K, 4)), t=np.zeros((K, 3)), X=np.zeros((L, 3)))
+        rec = BaStepRecord(); it = C.c_int32(); rel = C.c_double(); ok = C.c_int32()
+        xin = None if x_in is None else np.ascontiguousarray(x_in, np.float64).reshape(6 * K)
+        check(self._L.dvs_ba_global_step_probe(self._h, float(radius), int(bool(refresh)), int(bool(commit)), float(eta),
+                                               int(max_pcg_iterations), float(ftol), float(ptol), None if xin is None else ptr(xin),
+                                               *[ptr(o[k]) for k in ("scale", "diag", "Vinv", "x", "step", "q", "t", "X")],
+                                               C.byref(it), C.byref(rel), C.byref(ok), C.byref(rec)))
+        o["pcg_iterations"], o["pcg_rel_residual"], o["pcg_ok"] = it.value, rel.value, ok.value
         for k, _ in BaStepRecord._fields_:
             if k != "reserved":
                 o[k] = getattr(rec, k)

@@ -585,13 +585,19 @@ dvs_status dvs_ba_get_parameters(dvs_ba* h, double* q_wxyz, double* t, double* X
  *   b_c     = g_c scaled - sum_{obs e of c} Y_e g_l(e) scaled
  * Fixed cameras and inactive landmarks (fixed, or observed by nobody) contribute nothing; a camera nobody observes is its damped
  * diagonal block.  The step is stored as solved (camera part not negated), the sign back-substitution and candidate read.
+ *   Active set      every camera that is not fixed is active, whether or not anyone observes it (dvs_ba_solve_device also asks for
+ *                   an observation); landmarks as there: not fixed and observed.  A free camera nobody observes has b_c = 0, so its
+ *                   step is zero and it keeps its bytes, but as an active block its |x_c|^2 counts in the squared norm of the point
+ *                   that the parameter-tolerance test reads — in dvs_ba_solve_device it does not.
  *   Preconditioner  M_c^-1, M_c = Hpp_c scaled + D_c / rho - sum_{e of c} Y_e Ws_e^T (the 6 x 6 diagonal blocks of S, Ceres'
  *                   SCHUR_JACOBI), inverted by Cholesky; the inverse of the block's diagonal alone if a pivot is not positive.
  *   Iteration       x_0 = 0, r_0 = b, z = M^-1 r, p = z;  alpha = r.z / p.Sp, x += alpha p, r -= alpha S p, z = M^-1 r,
  *                   beta = r.z new / r.z old, p = z + beta p.  Stops at the first k >= 1 with |r_k|_2 <= eta |b|_2 (r_k the
- *                   recurrence's residual) or at max_pcg_iterations (0: max(100, 12 nc), nc = free cameras).
- *   Breakdown       p.Sp <= 0 or not finite ends the solve: before the first iteration the trial step is invalid, later the
- *                   current x is the step.
+ *                   recurrence's residual) or at max_pcg_iterations (0: max(100, 12 nc), nc = free cameras).  |b|_2 = 0 (no free
+ *                   camera is coupled to an active landmark with a gradient): x = 0 is the solution, the solve ends with zero
+ *                   iterations and the trial step is valid — the landmarks still take their own steps -Vinv_l g_l.
+ *   Breakdown       p.Sp <= 0 or not finite, with |b|_2 > 0, ends the solve: before the first iteration the trial step is invalid,
+ *                   later the current x is the step.
  *   Determinism     the landmark-side sum runs over the landmark's observations in the order of the observation arrays grouped by
  *                   camera; the camera-side sum per chunk of <= 256 observations by a fixed tree, chunks in order; dot products by
  *                   fixed per-thread strides and a fixed tree.  No floating-point atomics: two identical solves return identical bytes.

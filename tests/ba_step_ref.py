@@ -15,7 +15,8 @@ full system, in the distance Step.residual() states.  tests/test_ba_step_ref_cpu
 that it does not exceed the constant; the GPU tests hold the device's step to 10 x the constant.
 
 An "active" block is one the solve moves: a camera that is not fixed and has an observation, a landmark that is not fixed and has
-an observation.  Rows and columns of every other block are left out of the system; their step is zero."""
+an observation.  Rows and columns of every other block are left out of the system; their step is zero.  dvs_ba_solve_global has
+another rule for cameras (global_active_blocks; Step takes either)."""
 import functools
 import numpy as np
 
@@ -118,6 +119,14 @@ def active_blocks(P):
     cu = np.zeros(K, bool); cu[np.asarray(P["cam_idx"], np.int64)] = True
     lu = np.zeros(L, bool); lu[np.asarray(P["lm_idx"], np.int64)] = True
     ca = cu & (np.asarray(P["pose_fixed"]) == 0); la = lu & (np.asarray(P["lm_fixed"]) == 0)
+    return ca, la, np.nonzero(ca)[0]
+
+
+def global_active_blocks(P):
+    """the active set of dvs_ba_solve_global (include/dvslam_hip.h, "Global BA"): every camera that is not fixed, observed or not;
+    landmarks as in active_blocks"""
+    _, la, _ = active_blocks(P)
+    ca = np.asarray(P["pose_fixed"]) == 0
     return ca, la, np.nonzero(ca)[0]
 
 
@@ -240,11 +249,12 @@ class Step:
     """one trial step at `radius` from the point (q, t, X) whose blocks are hpp, hll, w, g.  scale / diag: frozen values (the loop
     keeps the scaling of its first Jacobian, and the diagonal across a rejected step); by default both are made from the blocks."""
 
-    def __init__(self, P, hpp, hll, w, g, q, t, X, radius, scale=None, diag=None):
+    def __init__(self, P, hpp, hll, w, g, q, t, X, radius, scale=None, diag=None, active=active_blocks):
+        """active: the rule that names the active blocks, active_blocks or global_active_blocks"""
         K, L = int(P["K"]), int(P["L"])
         self.P, self.K, self.L, self.N, self.radius = P, K, L, 6 * K + 3 * L, radius
         self.cam = np.asarray(P["cam_idx"], np.int64); self.lm = np.asarray(P["lm_idx"], np.int64)
-        self.ca, self.la, self.slots = active_blocks(P)
+        self.ca, self.la, self.slots = active(P)
         self.act = np.concatenate([np.repeat(self.ca, 6), np.repeat(self.la, 3)])
         self.idx = np.nonzero(self.act)[0]
         self.hpp, self.hll, self.w = np.asarray(hpp), np.asarray(hll), np.asarray(w)
@@ -298,8 +308,10 @@ class Step:
         return np.abs(self.Hs) @ d + self.diag[self.idx] / LD(self.radius) * d + np.abs(self.gs[self.idx])
 
     def residual_rows(self, delta):
+        """a row without any term (a free camera nobody observes, at a zero step) has residual 0"""
         d = self.scaled(delta)[self.idx]
-        return np.abs(self.A @ d + self.gs[self.idx]) / self.magnitude(delta)
+        r = np.abs(self.A @ d + self.gs[self.idx]); m = self.magnitude(delta)
+        return np.where(m > 0, r / np.where(m > 0, m, 1), np.where(r > 0, np.inf, 0))
 
     def residual(self, delta):
         """the distance STEP_MEASURED is stated in: max over the active rows of |(H_s + D / radius) delta_s + g_s| relative to
@@ -322,16 +334,24 @@ class Step:
         ex = np.abs(self.delta_s[self.idx]) * self.diag[self.idx] / LD(self.radius)
         return float(e @ ex + e @ (np.abs(self.Hs) @ e) / 2)
 
-    def reduced(self):
-        """the reduced camera system in slot order, longdouble -> dict S, rhs, their un-cancelled magnitudes Smag, rhsmag, and per
-        landmark V = H_ll scaled + D / radius, Vinv (zero where inactive)"""
+    def landmark_blocks(self):
+        """longdouble -> dict of, per landmark, V = H_ll scaled + D / radius and Vinv (zero where inactive), and Ws [slots, 6, L, 3],
+        the scaled W blocks of the active cameras in slot order (zero for inactive landmarks): all landmark_part needs"""
         K, L = self.K, self.L
         sp = self.scale[:6 * K].reshape(K, 6); sl = self.scale[6 * K:].reshape(L, 3)
         V = np.asarray(self.hll, LD) * sl[:, :, None] * sl[:, None, :]
         V[:, np.arange(3), np.arange(3)] += self.diag[6 * K:].reshape(L, 3) / LD(self.radius)
         Vinv = np.zeros((L, 3, 3), LD); Vinv[self.la] = _inv3(V[self.la])
         Ws = self.Wd * sp[:, :, None, None] * sl[None, None, :, :] * self.la[None, None, :, None]     # [K, 6, L, 3]
-        Ws = Ws[self.slots]
+        return dict(V=V, Vinv=Vinv, Ws=Ws[self.slots])
+
+    def reduced(self):
+        """the reduced camera system in slot order, longdouble -> landmark_blocks() and S, rhs, their un-cancelled magnitudes Smag,
+        rhsmag"""
+        K, L = self.K, self.L
+        sp = self.scale[:6 * K].reshape(K, 6)
+        lb = self.landmark_blocks()
+        V, Vinv, Ws = lb["V"], lb["Vinv"], lb["Ws"]
         nc = len(self.slots)
         Y = np.einsum("kalb,lbc->kalc", Ws, Vinv)
         U = np.zeros((nc, 6, nc, 6), LD)
@@ -348,9 +368,9 @@ class Step:
 
     def landmark_part(self, delta, red=None, Vinv=None):
         """the landmark rows that follow from delta's camera rows: delta_l = -Vinv_l (g_l + sum_c W_cl^T delta_c) -> (delta_l [L, 3],
-        the sum of the absolute values of its terms [L, 3]), both in PARAMETER units.  Vinv: the inverses to use (the reference's own
-        by default)"""
-        red = red or self.reduced()
+        the sum of the absolute values of its terms [L, 3]), both in PARAMETER units.  red: reduced() or landmark_blocks().  Vinv: the
+        inverses to use (the reference's own by default)"""
+        red = red or self.landmark_blocks()
         K, L = self.K, self.L
         Vinv = red["Vinv"] if Vinv is None else np.asarray(Vinv, LD) * self.la[:, None, None]
         dc = self.scaled(delta)[:6 * K].reshape(K, 6)[self.slots]

@@ -37,7 +37,8 @@ class SchurSystem:
         free = ~pf
         used = np.zeros(L, bool); used[lm] = True
         act = ~lf & used
-        self.K, self.free, self.nc = K, free, int(free.sum())
+        self.K, self.L, self.free, self.act, self.nc = K, L, free, act, int(free.sum())
+        self.cam, self.lm = cam, lm
         sp = 1.0 / (1.0 + np.sqrt(np.einsum("caa->ca", hpp)))            # [K, 6]
         sl = 1.0 / (1.0 + np.sqrt(np.einsum("laa->la", hll)))            # [L, 3]
         U = hpp * sp[:, :, None] * sp[:, None, :]
@@ -59,6 +60,7 @@ class SchurSystem:
             Vd[3 * l:3 * l + 3, 3 * l:3 * l + 3] = Vinv[l]
         gp = (g[:6 * K].reshape(K, 6) * sp * free[:, None]).reshape(-1)
         gl = (g[6 * K:].reshape(L, 3) * sl * act[:, None]).reshape(-1)
+        self.sp, self.sl, self.Vinv, self.Ws, self.gl = sp, sl, Vinv, Ws, gl.reshape(L, 3)
         self.S = Ud - Wd @ Vd @ Wd.T
         self.b = gp - Wd @ Vd @ gl
         self.Smag = np.abs(Ud) + Wa @ np.abs(Vd) @ Wa.T
@@ -81,13 +83,25 @@ class SchurSystem:
     def precond(self, r):
         return np.einsum("cab,cb->ca", self.Minv, r.reshape(self.K, 6)).reshape(-1)
 
+    def back_substitute(self, x):
+        """the whole step that follows from the camera rows x of S x = b, plain float64: delta_c = -x,
+        delta_l = -Vinv_l (g_l + sum_e Ws_e^T delta_cam(e)), scaled back -> [6K + 3L] in parameter units"""
+        dc = -np.asarray(x).reshape(self.K, 6)
+        tl = self.gl.copy()
+        np.add.at(tl, self.lm, np.einsum("eab,ea->eb", self.Ws, dc[self.cam]))
+        dl = -np.einsum("lab,lb->la", self.Vinv, tl)
+        return np.concatenate([(dc * self.sp).reshape(-1), (dl * self.sl).reshape(-1)])
+
     def pcg(self, eta, max_it=0):
-        """-> x, iterations, |r| / |b| of the recurrence, ok (0: stopped before the first iteration)"""
+        """-> x, iterations, |r| / |b| of the recurrence, ok (0: stopped by breakdown before the first iteration).  |b| = 0: x = 0
+        solves the system, zero iterations, ok"""
         cap = max_it if max_it > 0 else default_cap(self.nc)
         b = self.b
         x = np.zeros_like(b); r = b.copy(); z = self.precond(r); p = z.copy()
         rz = r @ z; bn = np.sqrt(b @ b)
         k = 0
+        if bn == 0:
+            return x, 0, 0.0, 1
         while True:
             q = self.S @ p
             pq = p @ q
@@ -104,9 +118,12 @@ class SchurSystem:
             rz = rzn
 
 
-# the four systems of the tests (include/dvslam_hip.h "Global BA"; the smallest shapes that reach every branch of the kernels):
+# the four systems of the tests (include/dvslam_hip.h "Global BA"):
 # (a) 95 free cameras (> 64), 162..313 observations per camera (two chunks), 13..25 per landmark (crosses k_lm_backsub's 16)
 # (b) 25..45 observations per camera, 5..9 per landmark   (c) the full 20 x 200 window   (d) (c) with large noise
+# They do NOT reach every branch of the kernels: at most 96 cameras (the loops that stride the cameras by 256 take one trip), every K
+# a multiple of 4 (k_gba_precond's last workgroup is full), no camera with exactly 63, 64, 65, 256 or 257 observations or with three
+# chunks.  Those shapes are tests/gba_step_ref.py's "259 cameras" and "chunk edges" (tests/test_gpu_ba_global_steps.py).
 LARGE_NOISE = dict(pose_noise=(0.2, np.deg2rad(8)), lm_noise=0.3, outlier_frac=0.1)
 
 

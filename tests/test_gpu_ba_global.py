@@ -1,7 +1,9 @@
 """GPU: dvs_ba_solve_global (csrc/ba.hip) — the camera steps by matrix-free Schur PCG, any number of keyframes — against the dense
 numpy restatement of its linear solve (tests/schur_pcg_ref.py), the two existing solvers, and an independent scipy optimum.
-The four systems (a)..(d) are schur_pcg_ref.system_problem's: the smallest shapes that reach every branch (more than 64 cameras,
-two chunks per camera, landmarks on both sides of k_lm_backsub's 16-observation path)."""
+The four systems (a)..(d) are schur_pcg_ref.system_problem's: more than 64 cameras, two chunks per camera, landmarks on both sides of
+k_lm_backsub's 16-observation path.  The second trip of the loops that stride the cameras by 256, a K that is no multiple of 4 and
+the chunk edges (63 / 64 / 65, 256 / 257 observations, three chunks) are tests/test_gpu_ba_global_steps.py's, one trial step at a
+time."""
 import numpy as np
 import pytest
 import schur_pcg_ref as ref

@@ -35,17 +35,15 @@ Bounds, per probe (eps = 2^-52):
 import numpy as np
 import pytest
 import ba_step_ref as bs
+import ba_step_checks as ck
+from ba_step_checks import FTOL, PTOL, GTOL, check_scale_and_diag
 
 pytestmark = pytest.mark.gpu
 EPS = bs.EPS
 LD = bs.LD
 MARGIN = 10
-FTOL, PTOL, GTOL = 1e-6, 1e-8, 1e-10
 ALL = [(n, r) for n, (_, _, radii) in bs.CASES.items() for r in radii]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+_bits, _at, _cost_of = ck.bits, ck.at, ck.cost_of
 
 
 def _handle(P, name, hooks=True):
@@ -54,11 +52,6 @@ def _handle(P, name, hooks=True):
     if bs.CASES[name][1] != 16:
         g.set_device_window(bs.CASES[name][1])
     return g
-
-
-def _at(P, q, t, X):
-    Q = dict(P); Q["q"], Q["t"], Q["X"] = (np.ascontiguousarray(a) for a in (q, t, X))
-    return Q
 
 
 _BLOCKS = {}
@@ -88,23 +81,10 @@ def reference(name, radius, o):
     return s
 
 
-def check_scale_and_diag(B, o, scale_from=None):
-    hpp, hll = B[0], B[1]
-    if scale_from is None:
-        want = bs.jacobi_scale(hpp, hll)
-        assert (np.abs(o["scale"] - want) <= 1e-11 * want).all()
-    else:
-        assert (_bits(o["scale"]) == _bits(scale_from)).all(), "the scaling is fixed at the first Jacobian"
-    want = bs.lm_diagonal(hpp, hll, o["scale"])
-    assert (np.abs(o["diag"] - want) <= 1e-11 * want).all()
-    assert (o["diag"] >= 1e-6).all() and (o["diag"] <= 1e32).all()
-
-
 def check_probe(tag, s, o, B, cost_of):
     """every assertion of the module docstring on one probe `o` against the reference `s` (built from o's scale and diag);
-    cost_of(q, t, X): a fresh handle's evaluate() cost.  Returns the distances, in units of their bounds where they have one."""
-    K, L, N = s.K, s.L, s.N
-    radius = s.radius
+    cost_of(q, t, X): a fresh handle's evaluate() cost.  The pieces the global solver's step tests share are ba_step_checks'.
+    Returns the distances, in units of their bounds where they have one."""
     dist = {}
     assert o["ok"] == 1 and o["finite"] == 1
     # ---- reduced system
@@ -118,68 +98,19 @@ def check_probe(tag, s, o, B, cost_of):
     dist["S"], dist["rhs"] = float(eS.max()), float(er.max())
     assert dist["S"] <= 1e-11, f"{tag}: S off by {dist['S']:.2e} of the un-cancelled magnitude"
     assert dist["rhs"] <= 1e-11, f"{tag}: rhs off by {dist['rhs']:.2e} of the un-cancelled magnitude"
-    # ---- Vinv
-    la = s.la
-    assert not o["Vinv"][~la].any()
-    V = red["V"][la]
-    tau, G = bs.inv3_rounding(V)
-    Rm = np.abs(np.einsum("lab,lbc->lac", V, o["Vinv"][la].astype(LD)) - np.eye(3))
-    lim = 16 * EPS * (np.einsum("lab,lbc->lac", np.abs(V), G) + tau[:, None, None] * np.eye(3))
-    worst = int((Rm / lim).max(axis=(1, 2)).argmax())
-    dist["Vinv"] = float((Rm / lim).max())
-    cond = np.linalg.cond(V.astype(np.float64))
-    assert (Rm <= lim).all(), f"{tag}: |V Vinv - I| = {float(Rm[worst].max()):.2e} at cond(V) = {cond[worst]:.2e}"
+    ck.check_vinv(tag, s, o, red, dist)
     # ---- the step
-    step = o["step"]
-    assert not step[~s.act].any(), "rows of inactive blocks are exactly zero"
-    assert np.isfinite(step).all()
-    dist["step"] = s.residual(step)
-    rho = MARGIN * bs.STEP_MEASURED[radius]
-    assert dist["step"] <= rho, f"{tag}: full-system residual {dist['step']:.2e} > {rho:.1e}"
-    dl, mag = s.landmark_part(step, red, Vinv=o["Vinv"])
-    el = np.abs(dl - step[6 * K:].reshape(L, 3))
-    dist["landmark part"] = float((el[la] / mag[la]).max())
-    assert (el <= 1e-11 * mag).all(), f"{tag}: landmark rows off by {dist['landmark part']:.2e} of their absolute terms"
+    rho = MARGIN * bs.STEP_MEASURED[s.radius]
+    ck.check_step_residual(tag, s, o, rho, dist)
+    ck.check_landmark_rows(tag, s, o, red, dist)
     # ---- model cost change
-    mc, mmag = s.model_change(step)
-    dist["model change"] = float(abs(o["model_change"] - mc) / mmag)
-    assert dist["model change"] <= 1e-11, f"{tag}: model change {o['model_change']!r}, reference formula on the device's step {float(mc)!r}"
+    mmag = ck.check_model_change(tag, s, o, dist)
     mc_ref, _ = s.model_change(s.delta)
-    assert abs(o["model_change"] - mc_ref) <= s.model_change_slack(step, rho) + 1e-11 * mmag
-    # ---- candidate
-    dc = step[:6 * K].reshape(K, 6); dX = step[6 * K:].reshape(L, 3)
-    want_q = bs.quat_plus(s.q.astype(LD), dc[:, :3].astype(LD))
-    nd = np.sqrt((dc[:, :3] ** 2).sum(1))
-    qlim = (8 + 2 * nd)[:, None] * EPS * bs.quat_plus_magnitude(s.q, dc[:, :3])
-    eq = np.abs(o["q"] - want_q)[s.ca]
-    dist["candidate q (ulp of its terms)"] = float((eq / (EPS * bs.quat_plus_magnitude(s.q, dc[:, :3])[s.ca])).max())
-    assert (eq <= qlim[s.ca]).all(), f"{tag}: candidate quaternion {dist['candidate q (ulp of its terms)']:.1f} ulp off"
-    assert (_bits(o["t"][s.ca]) == _bits(s.t[s.ca] + dc[s.ca, 3:])).all()
-    assert (_bits(o["X"][la]) == _bits(s.X[la] + dX[la])).all()
-    assert (_bits(o["q"][~s.ca]) == _bits(s.q[~s.ca])).all() and (_bits(o["t"][~s.ca]) == _bits(s.t[~s.ca])).all()
-    assert (_bits(o["X"][~la]) == _bits(s.X[~la])).all()
-    # ---- norms, costs, verdict
-    sn, xn = s.norms(o["q"], o["t"], o["X"])
-    dist["sn"], dist["xn"] = float(abs(o["sn"] - sn) / sn), float(abs(o["xn"] - xn) / xn)
-    assert dist["sn"] <= 1e-13 and dist["xn"] <= 1e-13
-    cc = cost_of(o["q"], o["t"], o["X"])
-    dist["cand_cost"] = abs(o["cand_cost"] - cc) / cc
-    assert dist["cand_cost"] <= 1e-12
-    assert _bits(o["x_cost"]) == _bits(B[4])
-    g = s.g[:6 * K].reshape(K, 6)
-    glim = ((8 + 2 * np.sqrt((g[:, :3] ** 2).sum(1)))[:, None] * EPS * bs.quat_plus_magnitude(s.q, -g[:, :3]))[s.ca].max()
-    assert abs(o["gmax"] - s.gmax()) <= glim, (o["gmax"], s.gmax())
-    assert o["accept"] == bs.accept_rule(o, FTOL, PTOL)
-    print(f"{tag}: " + "  ".join(f"{k} {v:.2e}" for k, v in dist.items()) + f"  accept {o['accept']}")
+    assert abs(o["model_change"] - mc_ref) <= s.model_change_slack(o["step"], rho) + 1e-11 * mmag
+    ck.check_candidate(tag, s, o, dist)
+    ck.check_record(tag, s, o, B, cost_of, dist)
+    ck.report(tag, dist, o)
     return dist
-
-
-def _cost_of(P):
-    from dvslam_amd import BAProblem
-
-    def f(q, t, X):
-        return BAProblem(_at(P, q, t, X)).evaluate()[0]
-    return f
 
 
 @pytest.mark.parametrize("name,radius", ALL, ids=[f"{n} r={r:g}" for n, r in ALL])
@@ -258,38 +189,8 @@ def test_committed_step_is_the_next_iteration(gpu, hooks, name):
 
 
 def _replay(g, P, iters):
-    """dvs_ba_solve_device's loop around the hook, with the trust-region schedule tests/ba_bracket.py states: -> (trace rows, q, t, X)"""
-    radius, factor, reuse = 1e4, 2.0, False
-    q, t, X = P["q"], P["t"], P["X"]
-    rows = []
-    invalid = 0
-    for _ in range(iters):
-        o = g.step_probe(radius, refresh=not reuse, commit=True, ftol=FTOL, ptol=PTOL)
-        assert o["gmax"] > GTOL and radius >= 1e-32, "the replay does not model the gradient-tolerance exit"
-        valid = o["ok"] and o["finite"] and o["model_change"] > 0.0
-        if not valid and not o["accept"]:
-            rows.append([radius, 0, 0, o["model_change"], 0, 0])
-            invalid += 1
-            if invalid >= 5:
-                break
-            radius /= factor; factor *= 2; reuse = False
-            continue
-        cc = o["x_cost"] - o["cand_cost"]
-        if not o["accept"]:
-            if np.sqrt(o["sn"]) <= PTOL * (np.sqrt(o["xn"]) + PTOL):
-                rows.append([radius, 3, cc, o["model_change"], 0, o["cand_cost"]]); break
-            if abs(cc) <= FTOL * o["x_cost"]:
-                rows.append([radius, 4, cc, o["model_change"], 0, o["cand_cost"]]); break
-        rel = cc / o["model_change"]
-        rows.append([radius, 1 if o["accept"] else 2, cc, o["model_change"], rel, o["cand_cost"]])
-        invalid = 0
-        if o["accept"]:
-            q, t, X = o["q"], o["t"], o["X"]
-            radius = min(1e16, radius / max(1.0 / 3.0, 1.0 - (2.0 * rel - 1.0) ** 3))
-            factor, reuse = 2.0, False
-        else:
-            radius /= factor; factor *= 2; reuse = True
-    return np.array(rows), q, t, X
+    """dvs_ba_solve_device's loop around the hook (ba_step_checks.replay): -> (trace rows, q, t, X)"""
+    return ck.replay(lambda radius, refresh, commit: g.step_probe(radius, refresh=refresh, commit=commit, ftol=FTOL, ptol=PTOL), P, iters)[:4]
 
 
 @pytest.mark.parametrize("name", bs.REPLAY + ("hard 5x200",))
