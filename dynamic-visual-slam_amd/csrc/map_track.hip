@@ -22,6 +22,7 @@
 #include "device_mem.h"
 #include "block_ops.h"
 #include "backend_internal.h"
+#include "maptrack_internal.h"
 
 namespace dvs {
 
@@ -464,6 +465,11 @@ struct dvs_maptrack {
   int last_n_kp = 0, last_n_lm = 0;
   bool last_search = false;
 };
+
+namespace dvs {   // maptrack_internal.h
+const dvs_maptrack_params& maptrack_params(const dvs_maptrack* h) { return h->P; }
+int maptrack_device(const dvs_maptrack* h) { return h->device; }
+}  // namespace dvs
 
 static int* mt_cnt(dvs_maptrack* h) { return h->cells.get(); }
 static int* mt_fill(dvs_maptrack* h) { return h->cells.get() + h->ncell; }

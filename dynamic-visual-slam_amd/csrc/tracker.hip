@@ -755,6 +755,19 @@ dvs_status dvs_tracker_track_map(dvs_tracker* h, dvs_backend* backend, dvs_maptr
   return DVS_OK;
 }
 
+// include/dvslam_hip.h "Relocalisation": that set against the backend's landmark table with no prior; the tracker itself launches nothing here.
+// After a frame with tracking_reset the set may be empty: FEW_PAIRS, not an error
+dvs_status dvs_tracker_relocalize(dvs_tracker* h, dvs_backend* backend, dvs_reloc* reloc, dvs_maptrack* mt, int32_t apply, dvs_reloc_result* result) {
+  DVS_ARG(h && backend && reloc && mt && result && backend->device == h->device);
+  if (!h->prev_valid) { set_error("dvs_tracker_relocalize: no frame has been tracked"); return DVS_ERR_EMPTY; }
+  DVS_HIP(hipSetDevice(h->device));
+  DVS_HIP(hipStreamSynchronize(h->ctx->stream));
+  const int q = 1 - h->p;
+  DVS_TRY(dvs_backend_relocalize_frame(backend, reloc, mt, h->f_k[q].get(), h->f_d[q].get(), h->prev_n, result));
+  if (apply && result->status == DVS_RELOC_OK) { memcpy(h->R, result->R, sizeof(h->R)); memcpy(h->tt, result->t, sizeof(h->tt)); }
+  return DVS_OK;
+}
+
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h)
 // the same order through k_cull itself (needs a GPU): keypoints that carry the responses, the matched indices as the match list
 dvs_status dvs_test_cull_order_device(const float* response, const uint8_t* matched, int32_t n, int32_t max_new, float min_response, int32_t* order,

@@ -19,3 +19,4 @@ from ._lib import LoopVerifyParams  # noqa: F401
 from .pose_graph import PoseGraph  # noqa: F401
 from .motion import MotionSegmenter, MotionParams, MotionStats  # noqa: F401
 from .map_track import MapTracker, MapTrackParams, MapTrackResult  # noqa: F401
+from .reloc import Relocalizer, RelocParams, RelocResult  # noqa: F401

@@ -353,6 +353,15 @@ class MappingBackend:
         check(self._L.dvs_backend_track_frame(self._h, map_tracker.handle, M._raw(d_kps), M._raw(d_desc), int(n_kp), ptr(R), ptr(t), C.byref(r)))
         return r.as_dict()
 
+    def relocalize_frame(self, relocalizer, map_tracker, d_kps, d_desc, n_kp):
+        """dvs_backend_relocalize_frame: a frame's keypoints and descriptors (device pointers or DeviceBuffers) against the landmark table as
+        it stands, no prior pose -> reloc result dict; the map is not modified"""
+        from . import map_track as M, reloc as RL
+        RL._bind(self._L)
+        r = RL.RelocResult()
+        check(self._L.dvs_backend_relocalize_frame(self._h, relocalizer.handle, map_tracker.handle, M._raw(d_kps), M._raw(d_desc), int(n_kp), C.byref(r)))
+        return r.as_dict()
+
     # ---- covisibility (include/dvslam_hip.h "Covisibility")
     def covisibility(self, min_weight=15, weights=True):
         """dvs_backend_covisibility: the whole graph -> dict(weights (n, n) int32 or None, nb_offsets (n + 1) int64, nb_index, nb_weight): the

@@ -127,6 +127,15 @@ class Tracker:
         check(self._L.dvs_tracker_track_map(self._h, backend._h, map_tracker.handle, 1 if apply else 0, C.byref(r)))
         return r.as_dict()
 
+    def relocalize(self, backend, relocalizer, map_tracker, apply=False):
+        """dvs_tracker_relocalize: the last frame's depth-filtered features against the backend's landmark table with no prior -> reloc result
+        dict; apply=True and status 0: the found pose replaces R_, t_"""
+        from . import reloc as RL
+        RL._bind(self._L)
+        r = RL.RelocResult()
+        check(self._L.dvs_tracker_relocalize(self._h, backend._h, relocalizer.handle, map_tracker.handle, 1 if apply else 0, C.byref(r)))
+        return r.as_dict()
+
     def filtered_features(self):
         """the last frame's depth-filtered set -> (keypoints, descriptors)"""
         from . import map_track as M

@@ -1416,7 +1416,8 @@ dvs_status dvs_backend_global_ba(dvs_backend* h, dvs_ba* ba, const dvs_ba_global
  *            it is R = R_cw^T, t[i] = -((R_cw[i] * t_cw[0] + R_cw[3 + i] * t_cw[1]) + R_cw[6 + i] * t_cw[2]), converted once at the end.
  *            cost = sum of chi_i over the final inliers at the final pose (0 unless the four rounds ran).  Every status is DVS_OK.
  * All four rounds run inside ONE kernel of one call; no host decision is taken between iterations; one 128-byte record comes back.
- * Out of scope: predicted octave and viewing-angle gates, descriptor re-selection, relocalisation after a tracking reset, several GPUs. */
+ * Out of scope: predicted octave and viewing-angle gates, descriptor re-selection, several GPUs.  (A frame whose prior is not within `radius`
+ * of the truth is what "Relocalisation" below is for.) */
 typedef struct dvs_maptrack dvs_maptrack;
 #define DVS_MAPTRACK_MAX_LEVELS 16
 enum { DVS_MAPTRACK_OK = 0, DVS_MAPTRACK_FEW_MATCHES = 1, DVS_MAPTRACK_FEW_INLIERS = 2, DVS_MAPTRACK_DEGENERATE = 3 };
@@ -1558,6 +1559,100 @@ dvs_status dvs_backend_local_ba(dvs_backend* h, dvs_ba* ba, uint64_t ref_frame_i
 dvs_status dvs_backend_track_frame_local(dvs_backend* h, dvs_maptrack* mt, uint64_t ref_frame_id, const dvs_covis_params* params /* NULL: defaults */,
                                          const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3,
                                          dvs_maptrack_result* result);
+
+/* ======================================= Relocalisation ================================= */
+/* A frame's pose in the map WITHOUT a prior (csrc/reloc.hip; INTEGRATION.md "Relocalisation"): what recovers a tracker after a tracking
+ * reset, when R_, t_ are stale and the window search of "Tracking against the map" finds nothing.  It is what ORB-SLAM's Relocalization
+ * does after candidate selection (Mur-Artal, Montiel, Tardos 2015, section V-C: matches, PnP RANSAC, a guided search and a pose
+ * optimisation that must keep enough inliers), as published ideas, with the candidate stage replaced by a search of the WHOLE landmark
+ * table: one frame against a map is one Hamming contraction, which the matrix-core matcher runs with the landmarks as its query rows.
+ * PARITY UNPINNED: the reference has no counterpart; the rule is the library's own, stated here in full and restated in numpy in
+ * tests/reloc_ref.py.  Stages 1-3 are integers and are compared bit for bit; stage 4 is dvs_solve_pnp_ransac's procedure and is compared
+ * byte for byte with that call; the host's Rodrigues conversion calls sin / cos and carries a tolerance.
+ *  Inputs    n_lm landmarks — float xyz[3], uint8 desc[32], int64 id in ascending order (optional: a row index stands for the id) —,
+ *            n_kp keypoints — dvs_keypoint, uint8 desc[32] —, the parameters.  No prior pose enters.
+ *  Stage 1   global search, one landmark on its own, integers only.  Landmark row j with three finite coordinates is compared with every
+ *            keypoint k < n_kp: d = hamming(desc_j, desc_k); best = the keypoint with the smallest (d, k); d_second = the smallest d among
+ *            the OTHER keypoints (-1 if n_kp == 1).  The landmark PROPOSES to best iff d_best < max_hamming (strict) and (d_second < 0, or
+ *            ratio_pct <= 0, or d_best * 100 < ratio_pct * d_second).  A landmark whose position is not finite is never compared and never
+ *            proposes; with n_kp == 0 nothing is compared.
+ *  Stage 2   one-to-one, as map tracking's stage 3.  Every keypoint KEEPS the proposal with the smallest (d, landmark row): one 64-bit
+ *            integer minimum per proposal, so there is no tie deviation.  A landmark that loses stays unmatched.
+ *  Stage 3   the list.  The kept pairs in ascending keypoint index, m of them: obj = the landmark's three floats, img = the keypoint's
+ *            (x, y) floats.  m < min_pairs: status FEW_PAIRS, nothing is solved.
+ *  Stage 4   pose from the list: dvs_solve_pnp_ransac's procedure, unchanged, on (obj, img, m, K4, pnp_iterations, pnp_reproj_err,
+ *            pnp_confidence, seed), where the list lies.  One small record comes back: the call's first wait.  success == 0, or
+ *            n_inliers < min_pnp_inliers, or an rvec / tvec that is not finite: status NO_POSE.  Otherwise the camera-to-world pose is
+ *            formed on the host in FP64, every expression left to right as written: with w = rvec, th2 = (w0 w0 + w1 w1) + w2 w2,
+ *            th = sqrt(th2), K = [w]x; th < 1e-12: R_cw = I + K; else A = sin(th) / th, B = (1 - cos(th)) / th2,
+ *            R_cw[3i + j] = ((i == j) + A K[3i + j]) + B K2[3i + j], K2[3i + j] = (K[3i] K[j] + K[3i + 1] K[3 + j]) + K[3i + 2] K[6 + j];
+ *            pnp_R = R_cw^T, pnp_t[i] = -((R_cw[i] * tvec0 + R_cw[3 + i] * tvec1) + R_cw[6 + i] * tvec2).
+ *  Stage 5   confirmation: dvs_maptrack_track_device on the caller's dvs_maptrack handle with the same arrays and (pnp_R, pnp_t) as the
+ *            prior; its record is embedded in the result.  Status OK iff track.status == DVS_MAPTRACK_OK and track.n_inliers >=
+ *            min_confirmed, else NOT_CONFIRMED.
+ *  Outcome   status 0 OK, 1 FEW_PAIRS, 2 NO_POSE, 3 NOT_CONFIRMED.  R, t = track.R, track.t with status 0, identity and zero otherwise;
+ *            pnp_inliers, pnp_success, pnp_R, pnp_t and track are zeros with status 1 (and pnp_R, pnp_t, track with status 2).  Every status is DVS_OK.
+ *            Two identical calls give identical bytes.
+ * The defaults are usual values (ORB-SLAM's 50 / 0.75-style descriptor gates, OpenCV's 4 px and 0.99), never fitted to a sensor.
+ * The handle owns a matcher context of its own, the top-2 arrays [n_lm][2], the per-keypoint keys and the list, all grow-only; it shares
+ * nothing with the dvs_maptrack handle but the pose that crosses the host.  A program that never creates one allocates and launches
+ * nothing it did not before.
+ * Out of scope: candidate keyframes by votes or by the vocabulary, a depth-consistency gate on the pairs, a policy that calls it
+ * automatically after a reset, octave and viewing-angle gates, several GPUs. */
+typedef struct dvs_reloc dvs_reloc;
+enum { DVS_RELOC_OK = 0, DVS_RELOC_FEW_PAIRS = 1, DVS_RELOC_NO_POSE = 2, DVS_RELOC_NOT_CONFIRMED = 3 };
+typedef struct dvs_reloc_params {      /* 80 bytes */
+  double K4[4];                        /* fx, fy, cx, cy: no default, zeros are refused (finite, fx, fy > 0) */
+  int32_t max_hamming;                 /* 50; 0..257 */
+  int32_t ratio_pct;                   /* 75; <= 0 switches the ratio test off; <= 100000 */
+  int32_t min_pairs;                   /* 20; >= 4 */
+  int32_t pnp_iterations;              /* 512; 1..1024 */
+  double pnp_reproj_err;               /* 4.0 pixels; finite, > 0 */
+  double pnp_confidence;               /* 0.99; inside (0, 1) */
+  int32_t min_pnp_inliers;             /* 15; >= 0 */
+  int32_t min_confirmed;               /* 30; >= 0 */
+  uint64_t seed;                       /* 0: RANSAC's sampler seed */
+} dvs_reloc_params;
+typedef struct dvs_reloc_result {      /* 344 bytes */
+  int32_t status;                      /* DVS_RELOC_* */
+  int32_t n_proposed, n_pairs;         /* landmarks that proposed; kept pairs (m) */
+  int32_t pnp_inliers, pnp_success;
+  int32_t reserved;
+  double pnp_R[9], pnp_t[3];           /* stage 4's pose, camera-to-world */
+  dvs_maptrack_result track;           /* stage 5's record */
+  double R[9], t[3];                   /* the confirmed pose with status 0, else identity and zero */
+} dvs_reloc_result;
+/* the defaults above; K4 stays zero */
+void dvs_reloc_default_params(dvs_reloc_params* p);
+/* DVS_ERR_ARG for parameters outside the ranges above, before any device work; then DVS_ERR_NO_DEVICE without a gfx950 (no CPU fallback).
+ * The handle works on HIP's legacy default stream until dvs_reloc_set_stream.  Not thread-safe; buffers grow with the largest call. */
+dvs_status dvs_reloc_create(const dvs_reloc_params* params, int32_t device, dvs_reloc** out);
+void dvs_reloc_destroy(dvs_reloc* h);
+dvs_status dvs_reloc_set_stream(dvs_reloc* h, void* hip_stream);   /* synchronises the old stream first */
+/* Stages 1-5 on device arrays; mt confirms (same device; its image size and intrinsics are the caller's to make the frame's).  d_lm_id may
+ * be NULL; descriptor arrays 16-byte aligned; n_lm * 2 and n_kp stay below 2^31.  Synchronises. */
+dvs_status dvs_reloc_locate_device(dvs_reloc* h, dvs_maptrack* mt, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id /* may be NULL */,
+                                   int32_t n_lm, const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, dvs_reloc_result* result);
+/* the same with host pointers; a keypoint mt would not bin and ids that do not ascend strictly are DVS_ERR_ARG, as in dvs_maptrack_track */
+dvs_status dvs_reloc_locate(dvs_reloc* h, dvs_maptrack* mt, const float* lm_xyz, const uint8_t* lm_desc, const int64_t* lm_id, int32_t n_lm,
+                            const dvs_keypoint* kps, const uint8_t* desc, int32_t n_kp, dvs_reloc_result* result);
+/* The last call's stage-3 list (each array nullable, count-then-capacity: *n = m is always set): the landmark row, the keypoint, the
+ * distance and whether RANSAC ended with the pair as an inlier (all 0 with status 1). */
+dvs_status dvs_reloc_get_pairs(dvs_reloc* h, int32_t cap, int32_t* lm_row, int32_t* kp_index, int32_t* dist, uint8_t* pnp_inlier, int32_t* n);
+/* measurement (tools/reloc_timing.py; results are unaffected): with timing on, every locate call records four events on the handle's
+ * stream — created by the first dvs_reloc_set_timing(h, 1), never otherwise — and ms3 = {stage 1, stages 2-3, stage 4 up to the export of
+ * the record} of the last call; DVS_ERR_EMPTY without one. */
+dvs_status dvs_reloc_set_timing(dvs_reloc* h, int32_t on);
+dvs_status dvs_reloc_get_stage_ms(dvs_reloc* h, double* ms3);
+/* dvs_reloc_locate_device with the backend's landmark table as it stands — position, descriptor and id columns handed over on the device;
+ * the map is not modified.  Same device for the three handles; the backend's stream is synchronised first. */
+dvs_status dvs_backend_relocalize_frame(dvs_backend* backend, dvs_reloc* h, dvs_maptrack* mt, const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp,
+                                        dvs_reloc_result* result);
+/* After a dvs_tracker_track: the last frame's depth-filtered keypoints and descriptors where the tracker left them in HBM, through
+ * dvs_backend_relocalize_frame.  With apply != 0 and status 0, R, t replace R_, t_, so the next frame's odometry composes on them, as
+ * dvs_tracker_track_map does.  DVS_ERR_EMPTY before the first frame; after a frame with tracking_reset the set may be empty, which is
+ * status FEW_PAIRS, not an error.  Strictly opt-in: nothing calls it after a reset but the caller. */
+dvs_status dvs_tracker_relocalize(dvs_tracker* tracker, dvs_backend* backend, dvs_reloc* h, dvs_maptrack* mt, int32_t apply, dvs_reloc_result* result);
 
 #ifdef __cplusplus
 }
