@@ -523,15 +523,28 @@ __device__ __forceinline__ double wave_allsum(double v) {
 // projection Jacobian.  Sums over the inliers are lane-strided partial sums folded by a butterfly (every lane then holds the same
 // total and runs the same small dense arithmetic: no broadcasts).  out record per problem (64 B): {int nInliers, int success, pad,
 // double rvec[3], tvec[3]}.
+// In the test library alone (-DDVS_TEST_HOOKS) the kernel has one more parameter, `dbg` (may be NULL): 8 doubles per problem — the
+// initialisation handed to the LM (rvec, tvec), the path taken (0 no initialisation, 1 planar, 2 DLT), the LM's iteration count — for
+// dvs_test_pnpcv_refit; the product library's kernel does not have it.
+#ifdef DVS_TEST_HOOKS
+#define DVS_REFIT_DBG_PARAM , double* __restrict__ dbg
+#define DVS_REFIT_DBG_NONE , nullptr
+#define DVS_REFIT_DBG(...) do { if (dbg && lane == 0) { __VA_ARGS__; } } while (0)
+#else
+#define DVS_REFIT_DBG_PARAM
+#define DVS_REFIT_DBG_NONE
+#define DVS_REFIT_DBG(...) do { } while (0)
+#endif
 __global__ __launch_bounds__(64) void k_pnpcv_refit(const float* __restrict__ obj, const float* __restrict__ img, const RansacProb* __restrict__ probs, int H,
                                                     const double* __restrict__ models, const int* __restrict__ sel, double fx, double fy, double cx,
-                                                    double cy, float thr, int* __restrict__ inl, unsigned char* __restrict__ out) {
+                                                    double cy, float thr, int* __restrict__ inl, unsigned char* __restrict__ out DVS_REFIT_DBG_PARAM) {
   using namespace pnpcv;
   __shared__ double wsA[145], wsV[145], wsOut[16];   // the 9 x 9 / 12 x 12 eigen-decompositions of the initialisation: lane 0, in LDS
   const RansacProb pb = probs[blockIdx.x];
   const int n = pb.n, lane = threadIdx.x;
   obj += 3 * (size_t)pb.off; img += 2 * (size_t)pb.off; inl += pb.off;
   out += 64 * (size_t)blockIdx.x;
+  DVS_REFIT_DBG(dbg += 8 * (size_t)blockIdx.x; for (int k = 0; k < 8; k++) dbg[k] = 0.0);
   const int best = sel[4 * blockIdx.x];
   if (best < 0) { if (lane < 16) ((int*)out)[lane] = 0; return; }
   const double* bm = models + 18 * ((size_t)H * blockIdx.x + best);
@@ -574,7 +587,9 @@ __global__ __launch_bounds__(64) void k_pnpcv_refit(const float* __restrict__ ob
   }
   const double W1 = MM[4 * o3[1]], W2 = MM[4 * o3[2]];
   bool init_ok = count >= 4;
+  [[maybe_unused]] int path = 0;   // (reported through `dbg` only)
   if (init_ok && W2 / W1 < 1e-3) {
+    path = 1;
     // planar structure: homography between the plane's coordinates and the normalised image points
     double Rt[9];   // rows = right singular vectors
     for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) Rt[3 * a + b] = Vm[3 * b + o3[a]];
@@ -636,6 +651,7 @@ __global__ __launch_bounds__(64) void k_pnpcv_refit(const float* __restrict__ ob
     }
   } else if (init_ok) {
     init_ok = count >= 6;   // "DLT algorithm needs at least 6 points"
+    path = 2;
     if (init_ok) {
       double LL[144];
       for (int k = 0; k < 144; k++) LL[k] = 0.0;
@@ -676,6 +692,7 @@ __global__ __launch_bounds__(64) void k_pnpcv_refit(const float* __restrict__ ob
   // ---- CvLevMarq through update(): J^T J / J^T e / |e| over the inliers by the wavefront, the 6 x 6 step in every lane ----
   if (init_ok) {
     double param[6] = {r[0], r[1], r[2], tt[0], tt[1], tt[2]}, prevParam[6], JtJ[36], JtErr[6];
+    DVS_REFIT_DBG(for (int k = 0; k < 6; k++) dbg[k] = param[k]; dbg[6] = path);
     double prevErrNorm = 1.7976931348623157e308, errNorm = 0.0;
     int lambdaLg10 = -3, iters = 0, state = 0;   // 0 STARTED, 1 CALC_J, 2 CHECK_ERR, 3 DONE
     // residuals (and normal equations) at `param`
@@ -746,6 +763,7 @@ __global__ __launch_bounds__(64) void k_pnpcv_refit(const float* __restrict__ ob
       }
     }
     for (int k = 0; k < 3; k++) { r[k] = param[k]; tt[k] = param[3 + k]; }
+    DVS_REFIT_DBG(dbg[7] = iters);
     success = 1;
   }
   if (lane == 0) {

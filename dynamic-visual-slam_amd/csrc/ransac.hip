@@ -14,6 +14,8 @@
 // replacement; parity of the whole estimator is a tolerance on the inlier set and the pose (tests/test_ransac.py), not bit equality;
 // each stage on its own (hypotheses, score, select, mask / inlier list, refinement) is held to a float64 reference in
 // tests/test_gpu_ransac_stages.py through the dvs_test_*_stages hooks at the end of this file.
+// The OpenCV-procedure forms (dvs_find_fundamental_cv*, dvs_solve_pnp_ransac_cv*) likewise: tests/test_gpu_ransac_cv_stages.py through the
+// hooks of include/dvslam_hip_test_ransac_cv.h.
 // Minimal solvers: normalised 8-point (null vector by complete-pivoting elimination, rank 2 enforced through the smallest
 // right singular vector) where OpenCV's kernel is the 7-point one; P3P (Grunert's quartic, all <= 4 poses scored) where
 // OpenCV's kernel is 5-point EPnP.  The final pose is refined on the inliers by Levenberg-Marquardt on the reprojection error,
@@ -1034,12 +1036,27 @@ struct PnpIo {
   }
 };
 
+// In the test library alone the batch bodies below have one more parameter, `dev`, which receives where the stage arrays of the call lie
+// in the handle's scratch block — all NULL where the call returned before any launch — for the dvs_test_*_stages hooks at the end of
+// this file; the product library's translation unit does not see it.  (samples, probs, best: the OpenCV-procedure forms only.)
+#ifdef DVS_TEST_HOOKS
+struct StagesDev { const double* models; const int* valid; const int* counts; const int* sel; const int32_t* samples; const RansacProb* probs; const double* best; };
+#define DVS_STAGES_PARAM , StagesDev* dev
+#define DVS_STAGES_NONE , nullptr
+#define DVS_STAGES_SET(...) do { if (dev) *dev = StagesDev{__VA_ARGS__}; } while (0)
+#else
+#define DVS_STAGES_PARAM
+#define DVS_STAGES_NONE
+#define DVS_STAGES_SET(...) do { } while (0)
+#endif
+
 // one pass over `nprob` problems with the models of the first H iterations; unfinished[b] = 1 where the loop wanted more than H
 // (lmeds: the problems are below 15 points — H = the fixed iteration count, k_lmeds_select instead of score / select / mask,
 //  unfinished[b] = 1 where the call FAILED, i.e. fewer than 7 inliers: OpenCV returns an empty matrix then, the mask stays as written)
 static dvs_status fm_cv_pass(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold, double confidence,
-                             int32_t max_iters, int32_t H, double* F9, uint8_t* inlier_mask, int32_t* n_inliers, int32_t* iterations, uint8_t* unfinished,
-                             bool lmeds = false) {
+                             int32_t max_iters, int32_t H, double* F9, uint8_t* inlier_mask, int32_t* n_inliers, int32_t* iterations, uint8_t* unfinished
+                             DVS_STAGES_PARAM, bool lmeds = false) {
+  DVS_STAGES_SET(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   int maxn = 0;
   for (int b = 0; b < nprob; b++) maxn = std::max(maxn, offsets[b + 1] - offsets[b]);
   const int total = offsets[nprob];
@@ -1060,6 +1077,7 @@ static dvs_status fm_cv_pass(dvs_matcher* ctx, int32_t nprob, const int32_t* off
   }
   io->import(st, base, d.inb);
   launch_fm_cv(st, nprob, maxn, d.probs, d.p1, d.p2, d.samples, H, lmeds, threshold, confidence, max_iters, d.models, d.valid, d.counts, d.sel, d.mask, d.F);
+  DVS_STAGES_SET(d.models, d.valid, d.counts, d.sel, d.samples, d.probs, d.F);
   DVS_TRY(io->fetch(st, d.sel, h.sel, d.outb, kExportMax));
   h.unpack(nprob, total, F9, inlier_mask, n_inliers);
   for (int b = 0; b < nprob; b++) {
@@ -1128,7 +1146,7 @@ static void launch_pnp_cv(hipStream_t st, int nprob, const RansacProb* d_probs, 
   hipLaunchKernelGGL(k_epnp_hypotheses, dim3((H + kEpnpGroups - 1) / kEpnpGroups, nprob), dim3(64), 0, st, d_obj, d_img, d_probs, d_samples, H, fx, fy, cx, cy, d_models);
   hipLaunchKernelGGL(k_pnpcv_score, dim3(H, nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H, d_models, fx, fy, cx, cy, thr, d_counts);
   hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H, d_probs, 5, confidence, 1, d_sel, 1, H);
-  hipLaunchKernelGGL(k_pnpcv_refit, dim3(nprob), dim3(64), 0, st, d_obj, d_img, d_probs, H, d_models, d_sel, fx, fy, cx, cy, thr, d_inl, d_out);
+  hipLaunchKernelGGL(k_pnpcv_refit, dim3(nprob), dim3(64), 0, st, d_obj, d_img, d_probs, H, d_models, d_sel, fx, fy, cx, cy, thr, d_inl, d_out DVS_REFIT_DBG_NONE);
 }
 
 // ---- the device forms (ransac_device.h): one problem whose points already live on the device; argument rules as the host entry points'
@@ -1257,19 +1275,7 @@ int32_t dvs_test_p3p(const double* P9, const double* j9, double* poses48) {
 
 // ---- batches of independent RANSAC problems (one launch sequence for all of them; the single-problem entry points are batches of one) ----
 // problem b = correspondences [offsets[b], offsets[b + 1]) of the concatenated point arrays, sampler seed seeds[b]
-// (the body of dvs_find_fundamental_ransac_batch.  In the test library alone it has one more parameter, `dev`, which receives where the
-// stage arrays of the call lie in the handle's scratch block — all NULL where the call returned before any launch — for
-// dvs_test_fm_stages; the product library's translation unit does not see it)
-#ifdef DVS_TEST_HOOKS
-struct OwnStagesDev { const double* models; const int* valid; const int* counts; const int* sel; };
-#define DVS_STAGES_PARAM , OwnStagesDev* dev
-#define DVS_STAGES_NONE , nullptr
-#define DVS_STAGES_SET(...) do { if (dev) *dev = OwnStagesDev{__VA_ARGS__}; } while (0)
-#else
-#define DVS_STAGES_PARAM
-#define DVS_STAGES_NONE
-#define DVS_STAGES_SET(...) do { } while (0)
-#endif
+// (the body of dvs_find_fundamental_ransac_batch; `dev`: DVS_STAGES_PARAM above, for dvs_test_fm_stages)
 static dvs_status fm_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
                                double confidence, int32_t max_iters, const uint64_t* seeds, double* F9, uint8_t* inlier_mask, int32_t* n_inliers
                                DVS_STAGES_PARAM) {
@@ -1335,7 +1341,7 @@ dvs_status dvs_find_fundamental_cv_batch(dvs_matcher* ctx, int32_t nprob, const 
     A.gather(big, offsets, pts1, pts2);
     const int H1 = std::min<int>(max_iters, 96);
     DVS_TRY(fm_cv_pass(ctx, (int)big.size(), A.off.data(), A.q1.data(), A.q2.data(), threshold, confidence, max_iters, H1, A.F.data(), A.mask.data(), A.nin.data(),
-                       A.its.data(), A.flag.data()));
+                       A.its.data(), A.flag.data() DVS_STAGES_NONE));
     A.scatter(offsets, F9, inlier_mask, n_inliers, iterations);
     std::vector<int> again;
     for (size_t i = 0; i < big.size(); i++) if (A.flag[i]) again.push_back(big[i]);
@@ -1343,7 +1349,7 @@ dvs_status dvs_find_fundamental_cv_batch(dvs_matcher* ctx, int32_t nprob, const 
       FmSubset B;
       B.gather(again, offsets, pts1, pts2);
       DVS_TRY(fm_cv_pass(ctx, (int)again.size(), B.off.data(), B.q1.data(), B.q2.data(), threshold, confidence, max_iters, max_iters, B.F.data(), B.mask.data(),
-                         B.nin.data(), B.its.data(), B.flag.data()));
+                         B.nin.data(), B.its.data(), B.flag.data() DVS_STAGES_NONE));
       B.scatter(offsets, F9, inlier_mask, n_inliers, iterations);
     }
   }
@@ -1353,7 +1359,7 @@ dvs_status dvs_find_fundamental_cv_batch(dvs_matcher* ctx, int32_t nprob, const 
     FmSubset C;
     C.gather(small, offsets, pts1, pts2);
     DVS_TRY(fm_cv_pass(ctx, (int)small.size(), C.off.data(), C.q1.data(), C.q2.data(), threshold, confidence, max_iters, niters, C.F.data(), C.mask.data(), C.nin.data(),
-                       C.its.data(), C.flag.data(), true));
+                       C.its.data(), C.flag.data() DVS_STAGES_NONE, true));
     C.scatter(offsets, F9, inlier_mask, n_inliers, iterations);
   }
   return DVS_OK;
@@ -1377,9 +1383,11 @@ dvs_status dvs_cv_ransac_subsets(const float* pts1, const float* pts2, int32_t n
 // cv::solvePnPRansac(obj, img, K, no distortion, rvec, tvec, false, iterations, reproj_err, confidence, inliers) as OpenCV 4.x runs it with
 // its default flags (csrc/pnp_cv.h).  Problems with fewer than 6 points are refused per problem (success 0; the reference returns before
 // the call, frontend.cpp:900).  iterations_run[b] = iterations the adaptive loop used (may be NULL).
-dvs_status dvs_solve_pnp_ransac_cv_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
-                                         int32_t iterations, double reproj_err, double confidence, double* rvec3, double* tvec3, int32_t* inliers,
-                                         int32_t* n_inliers, int32_t* success, int32_t* iterations_run) {
+// (the body of dvs_solve_pnp_ransac_cv_batch; `dev`: DVS_STAGES_PARAM above, for dvs_test_pnp_cv_stages — no `valid` array in this form)
+static dvs_status pnp_cv_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
+                               int32_t iterations, double reproj_err, double confidence, double* rvec3, double* tvec3, int32_t* inliers,
+                               int32_t* n_inliers, int32_t* success, int32_t* iterations_run DVS_STAGES_PARAM) {
+  DVS_STAGES_SET(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   DVS_ARG(ctx && nprob >= 0 && iterations >= 1 && iterations <= 1024 && K4 && reproj_err > 0 && confidence > 0 && confidence < 1);
   if (nprob == 0) return DVS_OK;
   DVS_ARG(offsets && rvec3 && tvec3 && success && offsets[0] == 0);
@@ -1414,10 +1422,17 @@ dvs_status dvs_solve_pnp_ransac_cv_batch(dvs_matcher* ctx, int32_t nprob, const 
   memcpy(h.obj, pts3d, (size_t)total * 12); memcpy(h.img, pts2d, (size_t)total * 8);
   io->import(st, base, d.inb);
   launch_pnp_cv(st, nprob, d.probs, d.obj, d.img, d.samples, H, K4, reproj_err, confidence, d_models, d_counts, d.sel, d.inl, d.rec);
+  DVS_STAGES_SET(d_models, nullptr, d_counts, d.sel, d.samples, d.probs, nullptr);
   DVS_TRY(io->fetch(st, d.rec, h.rec, d.outb, kExportMax));
   h.unpack(nprob, offsets, true, rvec3, tvec3, inliers, n_inliers, success);
   if (iterations_run) for (int b = 0; b < nprob; b++) iterations_run[b] = h.sel[4 * b + 1];
   return DVS_OK;
+}
+dvs_status dvs_solve_pnp_ransac_cv_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
+                                         int32_t iterations, double reproj_err, double confidence, double* rvec3, double* tvec3, int32_t* inliers,
+                                         int32_t* n_inliers, int32_t* success, int32_t* iterations_run) {
+  return pnp_cv_batch(ctx, nprob, offsets, pts3d, pts2d, K4, iterations, reproj_err, confidence, rvec3, tvec3, inliers, n_inliers, success,
+                      iterations_run DVS_STAGES_NONE);
 }
 
 dvs_status dvs_solve_pnp_ransac_cv(dvs_matcher* ctx, const float* pts3d, const float* pts2d, int32_t n, const double* K4, int32_t iterations,
@@ -1494,7 +1509,7 @@ dvs_status dvs_solve_pnp_ransac(dvs_matcher* ctx, const float* pts3d, const floa
 dvs_status dvs_test_fm_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold, double confidence,
                               int32_t H, const uint64_t* seeds, double* F_all, int32_t* valid, int32_t* counts, int32_t* sel, uint8_t* mask, double* Fbest) {
   DVS_ARG(ctx && nprob >= 1 && H >= 1 && offsets && F_all && valid && counts && sel && Fbest);
-  OwnStagesDev dev;
+  StagesDev dev;
   DVS_TRY(fm_own_batch(ctx, nprob, offsets, pts1, pts2, threshold, confidence, H, seeds, Fbest, mask, nullptr, &dev));
   const size_t nh = (size_t)nprob * H;
   if (!dev.models) {   // no problem had 8 points: nothing ran
@@ -1515,7 +1530,7 @@ dvs_status dvs_test_pnp_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* o
                                double confidence, int32_t H, const uint64_t* seeds, double* poses, int32_t* valid, int32_t* counts, int32_t* sel,
                                int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
   DVS_ARG(ctx && nprob >= 1 && H >= 1 && offsets && poses && valid && counts && sel && n_inliers && success && rvec3 && tvec3);
-  OwnStagesDev dev;
+  StagesDev dev;
   DVS_TRY(pnp_own_batch(ctx, nprob, offsets, pts3d, pts2d, K4, H, reproj_err, confidence, seeds, rvec3, tvec3, inliers, n_inliers, success, &dev));
   const size_t nh = (size_t)nprob * 4 * H;
   if (!dev.models) {   // no problem had 4 points: nothing ran
@@ -1569,6 +1584,113 @@ dvs_status dvs_test_pnp_refine(const float* pts3d, const float* pts2d, int32_t n
 
 // host only (no GPU): the conversion that ends k_pnp_refine
 void dvs_test_rotation_to_rodrigues(const double* R9, double* w3) { rotation_to_rodrigues(R9, w3); }
+
+// ---- the OpenCV-procedure forms (include/dvslam_hip_test_ransac_cv.h; tests/test_gpu_ransac_cv_stages.py)
+// ONE fm_cv_pass with the models of H iterations (the product's passes: H = min(max_iters, 96), then max_iters where the loop asked; LMedS:
+// the fixed count) and, beside its results, what every stage left on the device.  A batch is of one kind — all problems >= 15 points
+// (RANSAC) or all 8 .. 14 (LMedS: no counts, zeros) — as the product's passes are.
+dvs_status dvs_test_fm_cv_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
+                                 double confidence, int32_t max_iters, int32_t H, int32_t* samples, int32_t* found, double* F_all, int32_t* valid,
+                                 int32_t* counts, int32_t* sel, uint8_t* mask, double* Fbest) {
+  DVS_ARG(ctx && nprob >= 1 && H >= 1 && max_iters >= 1 && offsets && offsets[0] == 0 && pts1 && pts2 && threshold > 0 && samples && found && F_all && valid &&
+          counts && sel && mask && Fbest);
+  int nsmall = 0;
+  for (int b = 0; b < nprob; b++) {
+    const int n = offsets[b + 1] - offsets[b];
+    DVS_ARG(n >= 8);
+    nsmall += n < 15 ? 1 : 0;
+  }
+  DVS_ARG(nsmall == 0 || nsmall == nprob);
+  const bool lmeds = nsmall != 0;
+  DVS_HIP(hipSetDevice(ctx->device));
+  std::vector<uint8_t> flag(nprob);
+  StagesDev dev;
+  DVS_TRY(fm_cv_pass(ctx, nprob, offsets, pts1, pts2, threshold, confidence, max_iters, H, nullptr, mask, nullptr, nullptr, flag.data(), &dev, lmeds));
+  const size_t nh = (size_t)nprob * H;
+  std::vector<RansacProb> probs(nprob);
+  DVS_HIP(hipMemcpy(probs.data(), dev.probs, (size_t)nprob * sizeof(RansacProb), hipMemcpyDeviceToHost));
+  for (int b = 0; b < nprob; b++) found[b] = (int32_t)probs[b].seed;
+  DVS_HIP(hipMemcpy(samples, dev.samples, nh * 28, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(F_all, dev.models, nh * 216, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(valid, dev.valid, nh * 12, hipMemcpyDeviceToHost));
+  if (lmeds) memset(counts, 0, nh * 12);
+  else DVS_HIP(hipMemcpy(counts, dev.counts, nh * 12, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(sel, dev.sel, (size_t)nprob * 16, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(Fbest, dev.best, (size_t)nprob * 72, hipMemcpyDeviceToHost));
+  // k_f7_hypotheses writes no model into a slot it marks invalid (its `valid` says so): zeros, not what the scratch block held
+  for (size_t m = 0; m < 3 * nh; m++) if (!valid[m]) memset(F_all + 9 * m, 0, 72);
+  return DVS_OK;
+}
+
+// the body of dvs_solve_pnp_ransac_cv_batch with iterations = H and what every stage left on the device: models[b][H][18] (rvec, tvec, R,
+// pad), counts[b][H], sel[b][4], the samples the host drew (zeros for a refused problem)
+dvs_status dvs_test_pnp_cv_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
+                                  double reproj_err, double confidence, int32_t H, int32_t* samples, double* models, int32_t* counts, int32_t* sel,
+                                  int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
+  DVS_ARG(ctx && nprob >= 1 && H >= 1 && offsets && samples && models && counts && sel && n_inliers && success && rvec3 && tvec3);
+  StagesDev dev;
+  DVS_TRY(pnp_cv_batch(ctx, nprob, offsets, pts3d, pts2d, K4, H, reproj_err, confidence, rvec3, tvec3, inliers, n_inliers, success, nullptr, &dev));
+  DVS_ARG(dev.models != nullptr);
+  const size_t nh = (size_t)nprob * H;
+  DVS_HIP(hipMemcpy(samples, dev.samples, nh * 20, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(models, dev.models, nh * 144, hipMemcpyDeviceToHost));
+  for (size_t m = 0; m < nh; m++) models[18 * m + 15] = models[18 * m + 16] = models[18 * m + 17] = 0.0;   // the pad: no kernel writes it
+  DVS_HIP(hipMemcpy(counts, dev.counts, nh * 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(sel, dev.sel, (size_t)nprob * 16, hipMemcpyDeviceToHost));
+  return DVS_OK;
+}
+
+// k_ransac_select alone in the OpenCV-procedure form (capInSeed = 1): counts of H models, `group` per iteration (H a multiple of it), of a
+// loop of up to max_iters_true iterations of which getSubset found a sample for `found`
+dvs_status dvs_test_ransac_select_cv(const int32_t* counts, int32_t H, int32_t n, int32_t model_points, double confidence, int32_t group, int32_t found,
+                                     int32_t max_iters_true, int32_t* sel4) {
+  DVS_ARG(counts && sel4 && H >= 1 && n >= 1 && model_points >= 1 && group >= 1 && H % group == 0 && found >= 0 && max_iters_true >= 1);
+  DeviceBuf<int> dc, ds; DeviceBuf<RansacProb> dp;
+  DVS_TRY(dc.upload(std::vector<int>(counts, counts + H)));
+  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb{0, n, (unsigned long long)found})));
+  DVS_TRY(ds.alloc(4));
+  hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(1), 0, 0, dc.get(), H, dp.get(), model_points, confidence, group, ds.get(), 1, max_iters_true);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipMemcpy(sel4, ds.get(), 16, hipMemcpyDeviceToHost));
+  return DVS_OK;
+}
+
+// k_pnpcv_refit alone on ONE problem with a model of the caller's as the selected one (model6 = rvec, tvec — the rotation matrix the
+// hypothesis kernel stores beside it is made here, by the same routine; NULL: nothing selected, sel[0] = -1), grid and block as
+// launch_pnp_cv's for one problem.  inliers: room for n indices (-1 where none was written).  dbg8: see k_pnpcv_refit.
+static __global__ void k_test_pnpcv_model(const double* __restrict__ model6, double* __restrict__ m18) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double R[9];
+  const double rv[3] = {model6[0], model6[1], model6[2]};
+  pnpcv::rodrigues_vec(rv, R, nullptr);
+  for (int k = 0; k < 6; k++) m18[k] = model6[k];
+  for (int k = 0; k < 9; k++) m18[6 + k] = R[k];
+  for (int k = 15; k < 18; k++) m18[k] = 0.0;
+}
+dvs_status dvs_test_pnpcv_refit(const float* pts3d, const float* pts2d, int32_t n, const double* K4, const double* model6, double reproj_err, int32_t* inliers,
+                                int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3, double* dbg8) {
+  DVS_ARG(pts3d && pts2d && n >= 1 && K4 && reproj_err > 0 && inliers && n_inliers && success && rvec3 && tvec3 && dbg8);
+  DeviceBuf<float> dobj, dimg; DeviceBuf<RansacProb> dp; DeviceBuf<double> dm6, dm18, ddbg; DeviceBuf<int> dsel, dinl; DeviceBuf<unsigned char> dres;
+  DVS_TRY(dobj.upload(std::vector<float>(pts3d, pts3d + 3 * (size_t)n)));
+  DVS_TRY(dimg.upload(std::vector<float>(pts2d, pts2d + 2 * (size_t)n)));
+  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb{0, n, 1ull})));
+  DVS_TRY(dm6.upload(model6 ? std::vector<double>(model6, model6 + 6) : std::vector<double>(6, 0.0)));
+  DVS_TRY(dm18.upload(std::vector<double>(18, 0.0)));
+  DVS_TRY(ddbg.upload(std::vector<double>(8, -1.0)));
+  DVS_TRY(dsel.upload(std::vector<int>{model6 ? 0 : -1, 1, 0, 0}));
+  DVS_TRY(dinl.upload(std::vector<int>((size_t)n, -1)));
+  DVS_TRY(dres.upload(std::vector<unsigned char>(64, 0xff)));
+  if (model6) hipLaunchKernelGGL(k_test_pnpcv_model, dim3(1), dim3(1), 0, 0, dm6.get(), dm18.get());
+  hipLaunchKernelGGL(k_pnpcv_refit, dim3(1), dim3(64), 0, 0, dobj.get(), dimg.get(), dp.get(), 1, dm18.get(), dsel.get(), K4[0], K4[1], K4[2], K4[3],
+                     (float)(reproj_err * reproj_err), dinl.get(), dres.get(), ddbg.get());
+  DVS_HIP(hipGetLastError());
+  unsigned char res[64];
+  DVS_HIP(hipMemcpy(res, dres.get(), 64, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(inliers, dinl.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(dbg8, ddbg.get(), 64, hipMemcpyDeviceToHost));
+  memcpy(n_inliers, res, 4); memcpy(success, res + 4, 4); memcpy(rvec3, res + 16, 24); memcpy(tvec3, res + 40, 24);
+  return DVS_OK;
+}
 #endif  // DVS_TEST_HOOKS
 
 }  // extern "C"

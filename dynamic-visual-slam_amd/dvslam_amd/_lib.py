@@ -360,6 +360,10 @@ def test_lib():
     L.dvs_test_pnp_stages.argtypes = [vp, i32, vp, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.dvs_test_ransac_select.argtypes = [vp, i32, i32, i32, dbl, i32, vp]
     L.dvs_test_pnp_refine.argtypes = [vp, vp, i32, vp, vp, dbl, vp, vp, vp, vp, vp]
+    L.dvs_test_fm_cv_stages.argtypes = [vp, i32, vp, vp, vp, dbl, dbl, i32, i32] + [vp] * 8      # include/dvslam_hip_test_ransac_cv.h
+    L.dvs_test_pnp_cv_stages.argtypes = [vp, i32, vp, vp, vp, vp, dbl, dbl, i32] + [vp] * 9
+    L.dvs_test_ransac_select_cv.argtypes = [vp, i32, i32, i32, dbl, i32, i32, i32, vp]
+    L.dvs_test_pnpcv_refit.argtypes = [vp, vp, i32, vp, vp, dbl] + [vp] * 6
     L.dvs_test_sincosf.argtypes = [C.c_float, vp, vp]; L.dvs_test_sincosf.restype = None
     L.dvs_test_geometry.argtypes = [C.POINTER(OrbParams), i32, i32, vp, vp, vp, vp, vp, vp]
     L.dvs_test_retain_best_host.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]; L.dvs_test_retain_best_host.restype = None

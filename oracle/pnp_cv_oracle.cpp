@@ -494,7 +494,8 @@ void projectJac(const double* M, int n, const double* rv, const double* tv, cons
 void solveSym6(const double* A, const double* b, double* x) { solveSvd(A, 6, 6, b, x); }
 
 // cvFindExtrinsicCameraParams2(objectPoints (double), imagePoints (double pixels), A, no distortion, useExtrinsicGuess = 0)
-bool findExtrinsics(const std::vector<double>& M, const std::vector<double>& m, const double* K4, double* rvec, double* tvec) {
+// init7 (may be null): the initialisation handed to the Levenberg-Marquardt loop (rvec, tvec) and the path taken (1 planar, 2 DLT)
+bool findExtrinsics(const std::vector<double>& M, const std::vector<double>& m, const double* K4, double* rvec, double* tvec, double* init7 = nullptr) {
   const int count = (int)M.size() / 3;
   std::vector<double> mn(2 * (size_t)count);
   const double ifx = 1. / K4[0], ify = 1. / K4[1];
@@ -595,6 +596,7 @@ bool findExtrinsics(const std::vector<double>& M, const std::vector<double>& m, 
   }
   // CvLevMarq(6, 2 count, (EPS + ITER, 20, FLT_EPSILON), completeSymm) driven through update(): see calibration.cpp
   double param[6] = {r[0], r[1], r[2], t[0], t[1], t[2]}, prevParam[6];
+  if (init7) { memcpy(init7, param, sizeof(param)); init7[6] = W[2] / W[1] < 1e-3 ? 1 : 2; }
   std::vector<double> J((size_t)2 * count * 6), err(2 * (size_t)count), proj(2 * (size_t)count);
   double JtJ[36], JtErr[6], prevErrNorm = DBL_MAX, errNorm = 0;
   int lambdaLg10 = -3, iters = 0;
@@ -668,6 +670,13 @@ void orc_epnp(const float* obj, const float* img, int m, const double* K4, doubl
 int orc_solve_pnp_iterative(const double* obj, const double* img, int n, const double* K4, double* rvec, double* tvec) {
   std::vector<double> M(obj, obj + 3 * (size_t)n), m(img, img + 2 * (size_t)n);
   return findExtrinsics(M, m, K4, rvec, tvec) ? 1 : 0;
+}
+
+// the same, and the initialisation it started from: init7 = {rvec, tvec, path (1 planar, 2 DLT)}, zeros where there was none
+int orc_solve_pnp_iterative_init(const double* obj, const double* img, int n, const double* K4, double* rvec, double* tvec, double* init7) {
+  std::vector<double> M(obj, obj + 3 * (size_t)n), m(img, img + 2 * (size_t)n);
+  memset(init7, 0, 7 * sizeof(double));
+  return findExtrinsics(M, m, K4, rvec, tvec, init7) ? 1 : 0;
 }
 
 // returns success.  sel3 = {iteration of the best model, iterations run, its inlier count}; model6 = the RANSAC stage's (rvec, tvec)

@@ -406,6 +406,7 @@ def _ransac_lib():
     L.orc_cv_subsets_nocheck.restype = i32; L.orc_cv_subsets_nocheck.argtypes = [i32, i32, i32, vp]
     L.orc_epnp.argtypes = [vp, vp, i32, vp, vp, vp]; L.orc_epnp.restype = None
     L.orc_solve_pnp_iterative.restype = i32; L.orc_solve_pnp_iterative.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.orc_solve_pnp_iterative_init.restype = i32; L.orc_solve_pnp_iterative_init.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     return L
 
 
@@ -497,6 +498,15 @@ def solve_pnp_iterative(obj, img, K4):
     r = np.zeros(3); t = np.zeros(3)
     ok = _ransac_lib().orc_solve_pnp_iterative(_p(obj), _p(img), len(obj), _p(np.ascontiguousarray(K4, np.float64)), _p(r), _p(t))
     return bool(ok), r, t
+
+
+def solve_pnp_iterative_init(obj, img, K4):
+    """solve_pnp_iterative and the initialisation its Levenberg-Marquardt loop started from -> (ok, rvec, tvec, path (0 none, 1 planar, 2 DLT),
+    rvec0, tvec0)"""
+    obj = np.ascontiguousarray(obj, np.float64).reshape(-1, 3); img = np.ascontiguousarray(img, np.float64).reshape(-1, 2)
+    r = np.zeros(3); t = np.zeros(3); init = np.zeros(7)
+    ok = _ransac_lib().orc_solve_pnp_iterative_init(_p(obj), _p(img), len(obj), _p(np.ascontiguousarray(K4, np.float64)), _p(r), _p(t), _p(init))
+    return bool(ok), r, t, int(init[6]), init[:3].copy(), init[3:6].copy()
 
 
 def solve_pnp_ransac(obj, img, K4, iterations=100, reproj_err=4.0, confidence=0.99, seed=1):

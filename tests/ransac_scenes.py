@@ -1,4 +1,5 @@
-"""Synthetic two-view / PnP scenes with known ground truth for the robust-estimation tests (tests/test_ransac.py)."""
+"""Synthetic two-view / PnP scenes with known ground truth for the robust-estimation tests (tests/test_ransac.py), and the inputs the
+stage tests cut out of them (tests/test_gpu_ransac_stages.py, tests/test_gpu_ransac_cv_stages.py and their CPU companions)."""
 import numpy as np
 
 
@@ -47,3 +48,41 @@ def iou(a, b):
     a = np.asarray(a, bool); b = np.asarray(b, bool)
     u = (a | b).sum()
     return 1.0 if u == 0 else (a & b).sum() / u
+
+
+# ------------------------------------------------------------------ the stage tests' inputs (EXPERIMENTS.md has what the gates leave out of them)
+def fm_scene(n, planar=False):
+    sc = two_view(n=600, outlier_frac=0.3, noise=0.5, seed=3 if planar else 0, planar=planar)
+    return sc["pts1"][:n].copy(), sc["pts2"][:n].copy()
+
+
+def pnp_scene(n, planar=False, noise=0.5, outliers=0.3):
+    """object points, their image in view 2, K4, indices moved BEHIND the camera, R, t.  A moved point is mirrored through the camera
+    centre of view 2: it projects onto the pixel it had, so only its depth tells it from an inlier."""
+    sc = two_view(n=600, outlier_frac=outliers, noise=noise, seed=4 if planar else 1, planar=planar)
+    X = sc["X"].astype(np.float64)
+    behind = np.array([i for i in range(2, 600, 20) if sc["truth"][i]])
+    Xc = X[behind] @ sc["R"].T + sc["t"]
+    X[behind] = (-Xc - sc["t"]) @ sc["R"]
+    return X.astype(np.float32)[:n].copy(), sc["pts2"][:n].copy(), sc["K4"], behind[behind < n], sc["R"], sc["t"]
+
+
+def planar_inlier_set(n, noise=0.5):
+    """n object points that all lie IN the plane of the planar PnP scene (the points pnp_scene moved behind the camera and the outliers
+    taken out), their image, K4, R, t: what the refit's planar branch is for"""
+    sc = two_view(n=600, outlier_frac=0.3, noise=noise, seed=4, planar=True)
+    keep = np.flatnonzero(sc["truth"])[:n]
+    assert len(keep) == n
+    return sc["X"][keep].copy(), sc["pts2"][keep].copy(), sc["K4"], sc["R"], sc["t"]
+
+
+def lmeds_scene(n):
+    """n < 15 correspondences without outliers (cv::findFundamentalMat runs LMedS there), as tests/test_ransac.py's LMedS tests make them"""
+    sc = two_view(n=n, outlier_frac=0.0, noise=0.3, seed=n)
+    return sc["pts1"], sc["pts2"]
+
+
+def loop_scene(outlier_frac):
+    """600 correspondences whose RANSAC loop wants many iterations (50 % outliers: about 587) or few (10 %)"""
+    sc = two_view(n=600, outlier_frac=outlier_frac, noise=0.5, seed=7)
+    return sc["pts1"], sc["pts2"]

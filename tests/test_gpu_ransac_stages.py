@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import ransac_scenes as rs
 import ransac_stage_ref as ref
+from ransac_scenes import fm_scene, pnp_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -43,22 +44,6 @@ SEED = 11
 
 
 # ------------------------------------------------------------------ inputs (made on the CPU; EXPERIMENTS.md has what the gates leave out of them)
-def fm_scene(n, planar=False):
-    sc = rs.two_view(n=600, outlier_frac=0.3, noise=0.5, seed=3 if planar else 0, planar=planar)
-    return sc["pts1"][:n].copy(), sc["pts2"][:n].copy()
-
-
-def pnp_scene(n, planar=False, noise=0.5, outliers=0.3):
-    """object points, their image in view 2, K4, indices moved BEHIND the camera, R, t.  A moved point is mirrored through the camera
-    centre of view 2: it projects onto the pixel it had, so only its depth tells it from an inlier."""
-    sc = rs.two_view(n=600, outlier_frac=outliers, noise=noise, seed=4 if planar else 1, planar=planar)
-    X = sc["X"].astype(np.float64)
-    behind = np.array([i for i in range(2, 600, 20) if sc["truth"][i]])
-    Xc = X[behind] @ sc["R"].T + sc["t"]
-    X[behind] = (-Xc - sc["t"]) @ sc["R"]
-    return X.astype(np.float32)[:n].copy(), sc["pts2"][:n].copy(), sc["K4"], behind[behind < n], sc["R"], sc["t"]
-
-
 def fm_cases():
     cases = {f"n{n}": fm_scene(n) for n in F_SIZES}
     cases["planar257"] = fm_scene(257, planar=True)
