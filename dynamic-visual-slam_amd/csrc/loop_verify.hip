@@ -103,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_lv_gather(const long long* __restric
   const bool listed = c < clamp_count(d_n_cand, cap_cand);
   const int e = listed ? d_entry_ids[c] : -1;
   if (!listed || e < 0 || e >= n_entries) {
-    if (tid == 0) { probs[c] = RansacProb{0, 0, 0ull}; write_failed(&results[c], listed ? -1 : 0); }
+    if (tid == 0) { probs[c] = RansacProb::seeded(0, 0, 0ull); write_failed(&results[c], listed ? -1 : 0); }
     return;
   }
   const int n = clamp_count(d_n, stride_rows);
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(kBlock) void k_lv_gather(const long long* __restric
   }
   if (tid == 0) {
     // a list shorter than min_correspondences runs no later stage: its RansacProb is empty
-    probs[c] = RansacProb{0, m >= min_corr ? m : 0, splitmix64(seed ^ (unsigned long long)e)};
+    probs[c] = RansacProb::seeded(0, m >= min_corr ? m : 0, splitmix64(seed ^ (unsigned long long)e));
     write_failed(&results[c], m);                     // the refinement completes the record where the candidate gets that far
   }
 }

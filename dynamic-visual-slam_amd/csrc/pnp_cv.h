@@ -475,7 +475,7 @@ __global__ __launch_bounds__(64) void k_epnp_hypotheses(const float* __restrict_
   obj += 3 * (size_t)pb.off; img += 2 * (size_t)pb.off;
   samples += 5 * ((size_t)H * blockIdx.y + h);
   double* m = models + 18 * ((size_t)H * blockIdx.y + h);
-  if (h >= (int)pb.seed) { if (gl == 0) for (int k = 0; k < 18; k++) m[k] = 0.0; return; }   // (the seed field: iterations that have a sample)
+  if (h >= pb.sampled_iterations()) { if (gl == 0) for (int k = 0; k < 18; k++) m[k] = 0.0; return; }
   int idx[5];
   for (int k = 0; k < 5; k++) idx[k] = samples[k];
   double rv[3], tv[3], R[9];
@@ -496,7 +496,7 @@ __global__ __launch_bounds__(256) void k_pnpcv_score(const float* __restrict__ o
   obj += 3 * (size_t)pb.off; img += 2 * (size_t)pb.off;
   const double* m = models + 18 * ((size_t)H * blockIdx.y + h);
   counts += (size_t)H * blockIdx.y;
-  if (h >= (int)pb.seed) { if (threadIdx.x == 0) counts[h] = 0; return; }
+  if (h >= pb.sampled_iterations()) { if (threadIdx.x == 0) counts[h] = 0; return; }
   double R[9], t[3];
   for (int k = 0; k < 9; k++) R[k] = m[6 + k];
   for (int k = 0; k < 3; k++) t[k] = m[3 + k];

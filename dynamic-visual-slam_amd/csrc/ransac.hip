@@ -16,6 +16,8 @@
 // tests/test_gpu_ransac_stages.py through the dvs_test_*_stages hooks at the end of this file.
 // The OpenCV-procedure forms (dvs_find_fundamental_cv*, dvs_solve_pnp_ransac_cv*) likewise: tests/test_gpu_ransac_cv_stages.py through the
 // hooks of include/dvslam_hip_test_ransac_cv.h.
+// The file is kernels first, then the host side: one pass per estimator over a layout of ransac_layout.h, called by the host batch body
+// and by the device form of ransac_device.h (tests/test_gpu_ransac_device_forms.py: the same bytes from both), the entry points, the hooks.
 // Minimal solvers: normalised 8-point (null vector by complete-pivoting elimination, rank 2 enforced through the smallest
 // right singular vector) where OpenCV's kernel is the 7-point one; P3P (Grunert's quartic, all <= 4 poses scored) where
 // OpenCV's kernel is 5-point EPnP.  The final pose is refined on the inliers by Levenberg-Marquardt on the reprojection error,
@@ -30,18 +32,18 @@
 #include "common.h"
 #ifdef DVS_TEST_HOOKS
 #include "../../include/dvslam_hip_test.h"
-#include "device_mem.h"
 #endif
 #include "io_pinned.h"
 #include "matcher.h"
 #include "pnp_cv.h"   // cv::solvePnPRansac by OpenCV's procedure: EPnP hypotheses, float scoring, solvePnP(ITERATIVE) refit
 #include "ransac_device.h"
+#include "ransac_layout.h"
 #include "ransac_shared.h"
 #include "splitmix64.h"
 
 namespace dvs {
 
-// RansacProb (ransac_device.h): one problem of a batch, blockIdx.y of every kernel below.
+// RansacProb (ransac_layout.h): one problem of a batch, blockIdx.y of every kernel below.
 
 // eigenvector of the smallest eigenvalue of a symmetric 3x3 (cyclic Jacobi)
 __device__ __forceinline__ void smallest_eigvec3(const double* S, double* v) {
@@ -232,17 +234,6 @@ __global__ __launch_bounds__(256) void k_f_score(const float* __restrict__ p1, c
   if (threadIdx.x == 0) counts[h] = total;
 }
 
-static int ransac_update_iters_host(double p, double ep, int modelPoints, int maxIters) {   // the same on the host (LMedS' iteration count)
-  p = std::max(p, 0.0); p = std::min(p, 1.0);
-  ep = std::max(ep, 0.0); ep = std::min(ep, 1.0);
-  double num = std::max(1.0 - p, DBL_MIN);
-  double denom = 1.0 - std::pow(1.0 - ep, (double)modelPoints);
-  if (denom < DBL_MIN) return 0;
-  num = std::log(num);
-  denom = std::log(denom);
-  return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int)std::rint(num / denom);
-}
-
 __global__ __launch_bounds__(256) void k_f_mask(const float* __restrict__ p1, const float* __restrict__ p2, const RansacProb* __restrict__ probs, int H,
                                                 const double* __restrict__ Fall, const int* __restrict__ sel, double thr2, unsigned char* __restrict__ mask,
                                                 double* __restrict__ Fbest, int fcmp) {
@@ -299,7 +290,8 @@ static bool cv_have_collinear(const float* pts, const int* idx, int count) {   /
   return false;
 }
 
-// the samples of iterations 0 .. iters - 1 (modelPoints indices each); returns how many iterations found one
+// the samples of iterations 0 .. iters - 1 (modelPoints <= 16 indices each); returns how many iterations found one.  p1 = p2 = NULL: getSubset
+// without a checkSubset, the 5-point samples of cv::solvePnPRansac's RANSAC stage — every iteration finds one at its first attempt
 static int cv_subsets(const float* p1, const float* p2, int n, int modelPoints, int iters, int32_t* idx_out, int maxAttempts = 10000) {
   CvRng rng(~0ull);
   int idx[16];
@@ -316,7 +308,7 @@ static int cv_subsets(const float* p1, const float* p2, int n, int modelPoints, 
         } while (dup);
         idx[i] = v;
       }
-      found = !(cv_have_collinear(p1, idx, modelPoints) || cv_have_collinear(p2, idx, modelPoints));
+      found = !p1 || !(cv_have_collinear(p1, idx, modelPoints) || cv_have_collinear(p2, idx, modelPoints));
     }
     if (!found) return it;
     for (int i = 0; i < modelPoints; i++) idx_out[(size_t)it * modelPoints + i] = idx[i];
@@ -382,7 +374,7 @@ __global__ __launch_bounds__(64) void k_f7_hypotheses(const float* __restrict__ 
   p1 += 2 * (size_t)pb.off; p2 += 2 * (size_t)pb.off;
   Fout += 27 * (size_t)H * blockIdx.y; valid += 3 * (size_t)H * blockIdx.y; samples += 7 * (size_t)H * blockIdx.y;
   valid[3 * h] = valid[3 * h + 1] = valid[3 * h + 2] = 0;
-  if (h >= (int)pb.seed) return;   // iterations getSubset found no sample for
+  if (h >= pb.sampled_iterations()) return;   // iterations getSubset found no sample for
   double A[7][9];
 #pragma unroll
   for (int i = 0; i < 7; i++) {
@@ -503,7 +495,7 @@ __global__ __launch_bounds__(256) void k_lmeds_select(const float* __restrict__ 
   const int n = pb.n, tid = threadIdx.x;
   p1 += 2 * (size_t)pb.off; p2 += 2 * (size_t)pb.off; mask += pb.off;
   Fall += 27 * (size_t)H * blockIdx.x; valid += 3 * (size_t)H * blockIdx.x; sel += 4 * (size_t)blockIdx.x; Fbest += 9 * (size_t)blockIdx.x;
-  const int iters = min(min(niters, H), (int)pb.seed);
+  const int iters = min(min(niters, H), pb.sampled_iterations());
   __shared__ unsigned long long s_best[256];
   unsigned long long best = ~0ull;   // (median's float bits << 32) | model index: non-negative floats order as their bit patterns
   for (int m = tid; m < 3 * iters; m += 256) {
@@ -925,339 +917,352 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
   }
 }
 
-// ---- the launch sequences, on device-resident problems: what the host-pointer entry points run behind their import and what the
-// device forms of ransac_device.h run directly.  n_bound >= every problem's n sizes the per-correspondence grid.
-static void launch_fm_own(hipStream_t st, int nprob, int n_bound, const RansacProb* d_probs, const float* d_p1, const float* d_p2, int H, double threshold,
-                          double confidence, double* d_F, int* d_valid, int* d_counts, int* d_sel, unsigned char* d_mask, double* d_Fb) {
-  hipLaunchKernelGGL(k_f_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_p1, d_p2, d_probs, H, d_F, d_valid);
-  hipLaunchKernelGGL(k_f_score, dim3(H, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, d_F, d_valid, threshold * threshold, d_counts, 0);
-  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H, d_probs, 8, confidence, 1, d_sel);
-  hipLaunchKernelGGL(k_f_mask, dim3((std::max(n_bound, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, d_F, d_sel, threshold * threshold, d_mask, d_Fb, 0);
+// ---------------------------------------------------------------------------------------------------------------------------
+// The host side.  Each estimator has ONE pass — what runs on the stream once its device layout (ransac_layout.h) is carved — and two
+// callers of it: the host batch body (check, zero the outputs, lay out, place the points, run the pass, fetch, unpack) and the device
+// form of ransac_device.h (lay out, run the pass on the caller's pointers).  The points, the mask, the result records and the inlier
+// lists are the layout's own arrays in the first and the caller's in the second; n_bound >= every problem's n sizes the
+// per-correspondence grid.
+// ---------------------------------------------------------------------------------------------------------------------------
+static void fm_own_pass(hipStream_t st, const FmLayout& d, int nprob, int n_bound, const float* d_p1, const float* d_p2, unsigned char* d_mask, int H,
+                        double threshold, double confidence) {
+  hipLaunchKernelGGL(k_f_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_p1, d_p2, d.probs, H, d.models, d.valid);
+  hipLaunchKernelGGL(k_f_score, dim3(H, nprob), dim3(256), 0, st, d_p1, d_p2, d.probs, H, d.models, d.valid, threshold * threshold, d.counts, 0);
+  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d.counts, H, d.probs, 8, confidence, 1, d.sel);
+  hipLaunchKernelGGL(k_f_mask, dim3((std::max(n_bound, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d.probs, H, d.models, d.sel, threshold * threshold, d_mask, d.F, 0);
 }
-// OpenCV's procedure: d_samples = the host-drawn 7-point samples of H iterations per problem (the seed field of a problem = how many have
-// one); lmeds: the 8..14-point form.  d_F / d_valid / d_counts hold 3 H models per problem.
-static void launch_fm_cv(hipStream_t st, int nprob, int n_bound, const RansacProb* d_probs, const float* d_p1, const float* d_p2, const int32_t* d_samples, int H,
-                         bool lmeds, double threshold, double confidence, int max_iters, double* d_F, int* d_valid, int* d_counts, int* d_sel,
-                         unsigned char* d_mask, double* d_Fb) {
-  const int H3 = 3 * H;
-  hipLaunchKernelGGL(k_f7_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_p1, d_p2, d_probs, d_samples, H, d_F, d_valid);
+static void pnp_own_pass(hipStream_t st, const PnpLayout& d, int nprob, const float* d_obj, const float* d_img, int* d_inl, unsigned char* d_rec, int H,
+                         const double* K4, double reproj_err, double confidence) {
+  const int H4 = kP3pPoses * H;
+  const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3], thr2 = reproj_err * reproj_err;
+  hipLaunchKernelGGL(k_p3p_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_obj, d_img, d.probs, H, fx, fy, cx, cy, d.models, d.valid);
+  hipLaunchKernelGGL(k_pnp_score, dim3(H4, nprob), dim3(256), 0, st, d_obj, d_img, d.probs, H4, d.models, d.valid, fx, fy, cx, cy, thr2, d.counts);
+  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d.counts, H4, d.probs, 3, confidence, kP3pPoses, d.sel);
+  hipLaunchKernelGGL(k_pnp_refine, dim3(nprob), dim3(256), 0, st, d_obj, d_img, d.probs, H4, d.models, d.sel, fx, fy, cx, cy, thr2, d_inl, d_rec);
+}
+// the problem record of a device-resident single problem of the own estimators: the count comes from the device
+__global__ void k_ransac_prob(RansacProb* __restrict__ prob, const int* __restrict__ d_n, unsigned long long seed) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *prob = RansacProb::seeded(0, *d_n, seed);
+}
+
+// cv::findFundamentalMat(FM_RANSAC)'s host policy, which dvs_find_fundamental_cv_batch and fm_cv_device both consult: the defaults, RANSAC
+// or LMedS, and how many iterations get their models fitted.  The adaptive rule ends most RANSAC loops after a few dozen iterations (10 %
+// outliers: ~10), and the sample sequence is the same whatever the number of samples drawn: first the models of first_pass() iterations,
+// then — only where the loop wanted more (sel[3]) — all max_iters: the same result a full run gives, a prefix of the same sequence.
+struct FmCvPolicy {
+  double threshold, confidence;
+  int max_iters;
+  static bool lmeds(int n) { return n < kFmCvRansacPoints; }
+  int lmeds_iters() const { return std::max(ransac_update_iters(confidence, 0.45, 7, max_iters), 3); }   // outlierRatio = 0.45; 300 for 0.99
+  int first_pass() const { return std::min(max_iters, kFmCvFirstPass); }
+  bool wants_full(const int* sel, int H) const { return sel[3] != 0 && H < max_iters; }
+};
+static FmCvPolicy fm_cv_policy(double threshold, double confidence, int max_iters) {
+  if (threshold <= 0) threshold = 3;                                                 // as cv::findFundamentalMat
+  if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
+  return FmCvPolicy{threshold, confidence, max_iters};
+}
+
+// OpenCV's procedure with the models of H iterations: the host draws every problem's 7-point samples from its points (pts1 / pts2: where the
+// HOST reads them) into `h`, the pinned mirror of `d`, with the problem records; [records | ... | samples] go up; 3 H models per problem are
+// fitted and the loop is replayed.  lmeds: the 8..14-point form (H = its fixed count, k_lmeds_select instead of score / select / mask).
+static void fm_cv_pass(hipStream_t st, const PinnedIo* io, const FmLayout& d, const FmLayout& h, int nprob, const int32_t* offsets, const float* pts1,
+                       const float* pts2, int n_bound, const float* d_p1, const float* d_p2, unsigned char* d_mask, int H, bool lmeds, const FmCvPolicy& P) {
+  memset(h.samples, 0, h.sampb);
+  for (int b = 0; b < nprob; b++) {
+    const int n = offsets[b + 1] - offsets[b];
+    const int found = cv_subsets(pts1 + 2 * (size_t)offsets[b], pts2 + 2 * (size_t)offsets[b], n, 7, H, h.samples + (size_t)b * H * 7, lmeds ? 1000 : 10000);
+    h.probs[b] = RansacProb::sampled(offsets[b], n, found);
+  }
+  io->import(st, d.probs, d.inb, (size_t)((const uint8_t*)h.probs - io->h()));
+  const int H3 = kF7Roots * H;
+  hipLaunchKernelGGL(k_f7_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_p1, d_p2, d.probs, d.samples, H, d.models, d.valid);
   if (lmeds) {
-    hipLaunchKernelGGL(k_lmeds_select, dim3(nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H, H, d_F, d_valid, d_sel, d_mask, d_Fb);
+    hipLaunchKernelGGL(k_lmeds_select, dim3(nprob), dim3(256), 0, st, d_p1, d_p2, d.probs, H, H, d.models, d.valid, d.sel, d_mask, d.F);
   } else {
-    hipLaunchKernelGGL(k_f_score, dim3(H3, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H3, d_F, d_valid, threshold * threshold, d_counts, 1);
-    hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H3, d_probs, 7, confidence, 3, d_sel, 1, max_iters);
-    hipLaunchKernelGGL(k_f_mask, dim3((std::max(n_bound, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d_probs, H3, d_F, d_sel, threshold * threshold, d_mask, d_Fb, 1);
+    hipLaunchKernelGGL(k_f_score, dim3(H3, nprob), dim3(256), 0, st, d_p1, d_p2, d.probs, H3, d.models, d.valid, P.threshold * P.threshold, d.counts, 1);
+    hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d.counts, H3, d.probs, 7, P.confidence, kF7Roots, d.sel, 1, P.max_iters);
+    hipLaunchKernelGGL(k_f_mask, dim3((std::max(n_bound, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d.probs, H3, d.models, d.sel, P.threshold * P.threshold, d_mask, d.F, 1);
   }
 }
-static void launch_pnp_own(hipStream_t st, int nprob, const RansacProb* d_probs, const float* d_obj, const float* d_img, int H, const double* K4, double reproj_err,
-                           double confidence, double* d_poses, int* d_valid, int* d_counts, int* d_sel, int* d_inl, unsigned char* d_out) {
-  const int H4 = 4 * H;
-  const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3], thr2 = reproj_err * reproj_err;
-  hipLaunchKernelGGL(k_p3p_hypotheses, dim3((H + 63) / 64, nprob), dim3(64), 0, st, d_obj, d_img, d_probs, H, fx, fy, cx, cy, d_poses, d_valid);
-  hipLaunchKernelGGL(k_pnp_score, dim3(H4, nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H4, d_poses, d_valid, fx, fy, cx, cy, thr2, d_counts);
-  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H4, d_probs, 3, confidence, 4, d_sel);
-  hipLaunchKernelGGL(k_pnp_refine, dim3(nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H4, d_poses, d_sel, fx, fy, cx, cy, thr2, d_inl, d_out);
-}
-// the problem record of a device-resident single problem: the count comes from the device
-__global__ void k_ransac_prob(RansacProb* __restrict__ prob, const int* __restrict__ d_n, unsigned long long seed) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *prob = RansacProb{0, *d_n, seed};
+// cv::solvePnPRansac's procedure likewise: the 5-point samples depend on the counts alone; a problem below kPnpCvMinPoints gets none and runs
+// no iteration (n == 5 would be solvePnP on all points, n == 4 the P3P kernel: not what the reference can reach)
+static void pnp_cv_pass(hipStream_t st, const PinnedIo* io, const PnpLayout& d, const PnpLayout& h, int nprob, const int32_t* offsets, const float* d_obj,
+                        const float* d_img, int* d_inl, unsigned char* d_rec, int* d_sel, int H, const double* K4, double reproj_err, double confidence) {
+  memset(h.samples, 0, h.sampb);
+  for (int b = 0; b < nprob; b++) {
+    const int n = offsets[b + 1] - offsets[b];
+    const bool run = n >= kPnpCvMinPoints;
+    if (run) cv_subsets(nullptr, nullptr, n, 5, H, h.samples + (size_t)b * H * 5);
+    h.probs[b] = RansacProb::sampled(offsets[b], n, run ? H : 0);
+  }
+  io->import(st, d.probs, d.inb);
+  const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3];
+  const float thr = (float)(reproj_err * reproj_err);
+  hipLaunchKernelGGL(k_epnp_hypotheses, dim3((H + kEpnpGroups - 1) / kEpnpGroups, nprob), dim3(64), 0, st, d_obj, d_img, d.probs, d.samples, H, fx, fy, cx, cy, d.models);
+  hipLaunchKernelGGL(k_pnpcv_score, dim3(H, nprob), dim3(256), 0, st, d_obj, d_img, d.probs, H, d.models, fx, fy, cx, cy, thr, d.counts);
+  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d.counts, H, d.probs, 5, confidence, 1, d_sel, 1, H);
+  hipLaunchKernelGGL(k_pnpcv_refit, dim3(nprob), dim3(64), 0, st, d_obj, d_img, d.probs, H, d.models, d_sel, fx, fy, cx, cy, thr, d_inl, d_rec DVS_REFIT_DBG_NONE);
 }
 
 // Results up to this size leave through the export kernel and a polled sequence number (no copy command, no wake-up), larger ones
 // by a copy command and the stream wait.
 constexpr size_t kExportMax = 65536;
 
-// A batch of F problems in scratch slot 0 and, without the work region, in the pinned block — one definition for the device carve,
-// the host placement and the host unpack.
-//   in   [problem records | pts1 | pts2 | samples 7 x nsamples (cv form)], blocks of 16 bytes: placed by the host, imported
-//   work [models 72 x nmodels | valid | counts], device only (nmodels = 0: none)
-//   out  [sel 16 x nprob | F 72 x nprob | mask total], whole dwords: fetched
-struct FmIo {
-  RansacProb* probs; float *p1, *p2; int32_t* samples;
-  double* models; int *valid, *counts;
-  int* sel; double* F; uint8_t* mask;
-  size_t sampb, inb, outb, bytes;   // the samples block, in, out, everything
-  FmIo(uint8_t* base, int nprob, int total, size_t nsamples, size_t nmodels) {
-    Carver c{base, 16};
-    c.take(probs, nprob); c.take(p1, 2 * (size_t)total); c.take(p2, 2 * (size_t)total);
-    samples = nullptr; sampb = c.used;
-    if (nsamples) c.take(samples, 7 * nsamples);
-    inb = c.used; sampb = inb - sampb;
-    c.align = 4;
-    models = nullptr; valid = counts = nullptr;
-    if (nmodels) { c.take(models, 9 * nmodels); c.take(valid, nmodels); c.take(counts, nmodels); }
-    const size_t out0 = c.used;
-    c.take(sel, 4 * (size_t)nprob); c.take(F, 9 * (size_t)nprob); c.take(mask, total);
-    outb = c.used - out0; bytes = c.used;
-  }
-  // out of the fetched region: inlier counts (0 where nothing was selected), models, masks
-  void unpack(int nprob, int total, double* F9, uint8_t* inlier_mask, int32_t* n_inliers) const {
-    for (int b = 0; b < nprob; b++)
-      if (n_inliers) n_inliers[b] = sel[4 * b] >= 0 ? sel[4 * b + 2] : 0;
-    if (F9) memcpy(F9, F, (size_t)nprob * 72);
-    if (total) memcpy(inlier_mask, mask, (size_t)total);
-  }
-};
-
-// The same for a batch of PnP problems; the work region differs between the two estimators and is carved by the caller at `work`.
-//   in   [problem records | object points 12 x total | image points 8 x total | samples 5 x nsamples (cv form)], blocks of 16 bytes
-//   work workb bytes, device only
-//   out  [result records 64 x nprob | inlier lists 4 x total | select records 16 x nprob (cv form: sel_tail)]
-struct PnpIo {
-  RansacProb* probs; float *obj, *img; int32_t* samples;
-  uint8_t *work, *rec; int *inl, *sel;
-  size_t sampb, inb, outb, bytes;
-  PnpIo(uint8_t* base, int nprob, int total, size_t nsamples, size_t workb, bool sel_tail) {
-    Carver c{base, 16};
-    c.take(probs, nprob); c.take(obj, 3 * (size_t)total); c.take(img, 2 * (size_t)total);
-    samples = nullptr; sampb = c.used;
-    if (nsamples) c.take(samples, 5 * nsamples);
-    inb = c.used; sampb = inb - sampb;
-    c.align = 4;
-    work = nullptr;
-    if (workb) c.take(work, workb);
-    const size_t out0 = c.used;
-    c.take(rec, 64 * (size_t)nprob); c.take(inl, total);
-    sel = nullptr;
-    if (sel_tail) c.take(sel, 4 * (size_t)nprob);
-    outb = c.used - out0; bytes = c.used;
-  }
-  // out of the fetched region; a pose is written where the estimator succeeded, or (by_sel: the cv form) wherever a model was selected
-  void unpack(int nprob, const int32_t* offsets, bool by_sel, double* rvec3, double* tvec3, int32_t* inliers, int32_t* n_inliers, int32_t* success) const {
-    for (int b = 0; b < nprob; b++) {
-      const uint8_t* r = rec + 64 * (size_t)b;
-      int nin = 0, succ = 0;
-      memcpy(&nin, r, 4); memcpy(&succ, r + 4, 4);
-      if (n_inliers) n_inliers[b] = nin;
-      success[b] = succ;
-      if (by_sel ? sel[4 * b] >= 0 : succ != 0) { memcpy(rvec3 + 3 * (size_t)b, r + 16, 24); memcpy(tvec3 + 3 * (size_t)b, r + 40, 24); }
-      if (inliers && nin > 0) memcpy(inliers + offsets[b], inl + offsets[b], (size_t)nin * 4);
-    }
-  }
-};
-
-// In the test library alone the batch bodies below have one more parameter, `dev`, which receives where the stage arrays of the call lie
-// in the handle's scratch block — all NULL where the call returned before any launch — for the dvs_test_*_stages hooks at the end of
-// this file; the product library's translation unit does not see it.  (samples, probs, best: the OpenCV-procedure forms only.)
-#ifdef DVS_TEST_HOOKS
-struct StagesDev { const double* models; const int* valid; const int* counts; const int* sel; const int32_t* samples; const RansacProb* probs; const double* best; };
-#define DVS_STAGES_PARAM , StagesDev* dev
-#define DVS_STAGES_NONE , nullptr
-#define DVS_STAGES_SET(...) do { if (dev) *dev = StagesDev{__VA_ARGS__}; } while (0)
-#else
-#define DVS_STAGES_PARAM
-#define DVS_STAGES_NONE
-#define DVS_STAGES_SET(...) do { } while (0)
-#endif
-
-// one pass over `nprob` problems with the models of the first H iterations; unfinished[b] = 1 where the loop wanted more than H
-// (lmeds: the problems are below 15 points — H = the fixed iteration count, k_lmeds_select instead of score / select / mask,
-//  unfinished[b] = 1 where the call FAILED, i.e. fewer than 7 inliers: OpenCV returns an empty matrix then, the mask stays as written)
-static dvs_status fm_cv_pass(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold, double confidence,
-                             int32_t max_iters, int32_t H, double* F9, uint8_t* inlier_mask, int32_t* n_inliers, int32_t* iterations, uint8_t* unfinished
-                             DVS_STAGES_PARAM, bool lmeds = false) {
-  DVS_STAGES_SET(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  int maxn = 0;
-  for (int b = 0; b < nprob; b++) maxn = std::max(maxn, offsets[b + 1] - offsets[b]);
-  const int total = offsets[nprob];
-  hipStream_t st = ctx->stream;
-  const size_t nsamples = (size_t)nprob * H, nmodels = 3 * nsamples;
+// lay out: scratch slot 0 carved as `r` says; for a host batch also the pinned block as the mirror of its [in | out]
+template <class Layout>
+static dvs_status lay_out(dvs_matcher* ctx, RansacRegions r, bool cv, int nprob, int total, int H, Layout* d) {
   uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, FmIo(nullptr, nprob, total, nsamples, nmodels).bytes + 64, (void**)&base));
-  const FmIo d(base, nprob, total, nsamples, nmodels);
+  DVS_TRY(matcher_scratch(ctx, 0, Layout(nullptr, r, cv, nprob, total, H).bytes + kScratchSlack, (void**)&base));
+  *d = Layout(base, r, cv, nprob, total, H);
+  return DVS_OK;
+}
+template <class Layout>
+static dvs_status lay_out_batch(dvs_matcher* ctx, bool cv, int nprob, int total, int H, Layout* d, Layout* h, PinnedIo** io) {
+  DVS_TRY(lay_out(ctx, kBatchDevice, cv, nprob, total, H, d));
+  DVS_TRY(matcher_pinned(ctx, d->inb + d->outb, io));
+  *h = Layout((*io)->h(), kBatchPinned, cv, nprob, total, H);
+  return DVS_OK;
+}
+
+// check: the offsets of a batch rise from 0; its longest problem and its correspondences in all
+static dvs_status batch_extent(int32_t nprob, const int32_t* offsets, int* maxn, int* total) {
+  DVS_ARG(offsets && offsets[0] == 0);
+  *maxn = 0;
+  for (int b = 0; b < nprob; b++) { DVS_ARG(offsets[b + 1] >= offsets[b]); *maxn = std::max(*maxn, offsets[b + 1] - offsets[b]); }
+  *total = offsets[nprob];
+  return DVS_OK;
+}
+static void pnp_zero_outputs(int32_t nprob, double* rvec3, double* tvec3, int32_t* n_inliers, int32_t* success, int32_t* iterations_run) {
+  memset(success, 0, (size_t)nprob * 4);
+  if (n_inliers) memset(n_inliers, 0, (size_t)nprob * 4);
+  if (iterations_run) memset(iterations_run, 0, (size_t)nprob * 4);
+  memset(rvec3, 0, (size_t)nprob * 24); memset(tvec3, 0, (size_t)nprob * 24);
+}
+
+// ---- the batch bodies.  `dev` (may be NULL) receives the call's device layout — default, all NULL, where the call returned before any
+// launch — for the dvs_test_*_stages hooks at the end of this file.
+
+// the body of dvs_find_fundamental_ransac_batch: problem b = correspondences [offsets[b], offsets[b + 1]) of the concatenated point
+// arrays, sampler seed seeds[b]
+static dvs_status fm_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
+                               double confidence, int32_t max_iters, const uint64_t* seeds, double* F9, uint8_t* inlier_mask, int32_t* n_inliers,
+                               FmLayout* dev = nullptr) {
+  if (dev) *dev = FmLayout();
+  DVS_ARG(ctx && nprob >= 0 && max_iters >= 1 && max_iters <= kFmMaxIters && threshold > 0);
+  if (nprob == 0) return DVS_OK;
+  int maxn, total;
+  DVS_TRY(batch_extent(nprob, offsets, &maxn, &total));
+  DVS_ARG(seeds && (total == 0 || (pts1 && pts2 && inlier_mask)));
+  if (n_inliers) memset(n_inliers, 0, (size_t)nprob * 4);
+  if (F9) memset(F9, 0, (size_t)nprob * kFmModelBytes);
+  if (total) memset(inlier_mask, 0, (size_t)total);
+  if (maxn < kFmOwnMinPoints) return DVS_OK;   // cv::findFundamentalMat needs >= 7 points for FM_RANSAC (8 for our kernel): empty F, masks of zeros
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  FmLayout d, h;
   PinnedIo* io;
-  DVS_TRY(matcher_pinned(ctx, d.inb + d.outb, &io));
-  const FmIo h(io->h(), nprob, total, nsamples, 0);
+  DVS_TRY(lay_out_batch(ctx, false, nprob, total, max_iters, &d, &h, &io));
+  for (int b = 0; b < nprob; b++) h.probs[b] = RansacProb::seeded(offsets[b], offsets[b + 1] - offsets[b], seeds[b]);
   memcpy(h.p1, pts1, (size_t)total * 8); memcpy(h.p2, pts2, (size_t)total * 8);
-  memset(h.samples, 0, h.sampb);
-  for (int b = 0; b < nprob; b++) {
-    const int n = offsets[b + 1] - offsets[b];
-    const int found = cv_subsets(pts1 + 2 * (size_t)offsets[b], pts2 + 2 * (size_t)offsets[b], n, 7, H, h.samples + (size_t)b * H * 7, lmeds ? 1000 : 10000);
-    h.probs[b] = RansacProb{offsets[b], n, (unsigned long long)found};   // the seed field carries the iterations that have a sample
-  }
-  io->import(st, base, d.inb);
-  launch_fm_cv(st, nprob, maxn, d.probs, d.p1, d.p2, d.samples, H, lmeds, threshold, confidence, max_iters, d.models, d.valid, d.counts, d.sel, d.mask, d.F);
-  DVS_STAGES_SET(d.models, d.valid, d.counts, d.sel, d.samples, d.probs, d.F);
+  io->import(st, d.probs, d.inb);
+  fm_own_pass(st, d, nprob, maxn, d.p1, d.p2, d.mask, max_iters, threshold, confidence);
+  if (dev) *dev = d;
+  DVS_TRY(io->fetch(st, d.sel, h.sel, d.outb, kExportMax));
+  h.unpack(nprob, total, F9, inlier_mask, n_inliers);
+  return DVS_OK;
+}
+
+// one pass of the OpenCV procedure over a batch of ONE kind (all RANSAC or all LMedS) with the models of the first H iterations;
+// unfinished[b] = 1 where the loop wanted more than H (lmeds: where the call FAILED, i.e. fewer than 7 inliers: OpenCV returns an empty
+// matrix then, the mask stays as written)
+static dvs_status fm_cv_batch_pass(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, const FmCvPolicy& P, int32_t H,
+                                   bool lmeds, double* F9, uint8_t* inlier_mask, int32_t* n_inliers, int32_t* iterations, uint8_t* unfinished,
+                                   FmLayout* dev = nullptr) {
+  int maxn, total;
+  DVS_TRY(batch_extent(nprob, offsets, &maxn, &total));
+  hipStream_t st = ctx->stream;
+  FmLayout d, h;
+  PinnedIo* io;
+  DVS_TRY(lay_out_batch(ctx, true, nprob, total, H, &d, &h, &io));
+  memcpy(h.p1, pts1, (size_t)total * 8); memcpy(h.p2, pts2, (size_t)total * 8);
+  fm_cv_pass(st, io, d, h, nprob, offsets, pts1, pts2, maxn, d.p1, d.p2, d.mask, H, lmeds, P);
+  if (dev) *dev = d;
   DVS_TRY(io->fetch(st, d.sel, h.sel, d.outb, kExportMax));
   h.unpack(nprob, total, F9, inlier_mask, n_inliers);
   for (int b = 0; b < nprob; b++) {
-    if (iterations) iterations[b] = h.sel[4 * b + 1];
-    unfinished[b] = lmeds ? (uint8_t)(h.sel[4 * b + 3] ? 0 : 1) : (uint8_t)h.sel[4 * b + 3];
-    if (F9 && lmeds && !h.sel[4 * b + 3]) memset(F9 + 9 * (size_t)b, 0, 72);   // the call failed: OpenCV returns an empty matrix
+    const int* sel = h.sel + kSel * b;
+    if (iterations) iterations[b] = sel[1];
+    unfinished[b] = lmeds ? (uint8_t)(sel[3] ? 0 : 1) : (uint8_t)sel[3];
+    if (F9 && lmeds && !sel[3]) memset(F9 + 9 * (size_t)b, 0, kFmModelBytes);   // the call failed: OpenCV returns an empty matrix
   }
   return DVS_OK;
 }
 
-// a subset of a batch's problems as a batch of its own (concatenated copies), and its results written back
-struct FmSubset {
-  std::vector<int> which;
-  std::vector<int32_t> off;
-  std::vector<float> q1, q2;
-  std::vector<double> F;
-  std::vector<uint8_t> mask, flag;
-  std::vector<int32_t> nin, its;
-  void gather(const std::vector<int>& w, const int32_t* offsets, const float* pts1, const float* pts2) {
-    which = w;
-    off.assign(w.size() + 1, 0);
-    for (size_t i = 0; i < w.size(); i++) off[i + 1] = off[i] + (offsets[w[i] + 1] - offsets[w[i]]);
-    q1.resize((size_t)off.back() * 2 + 2); q2.resize((size_t)off.back() * 2 + 2);
-    for (size_t i = 0; i < w.size(); i++) {
-      const int b = w[i], n = offsets[b + 1] - offsets[b];
-      memcpy(q1.data() + 2 * (size_t)off[i], pts1 + 2 * (size_t)offsets[b], (size_t)n * 8);
-      memcpy(q2.data() + 2 * (size_t)off[i], pts2 + 2 * (size_t)offsets[b], (size_t)n * 8);
-    }
-    F.assign(w.size() * 9, 0.0); mask.assign((size_t)off.back() + 1, 0); flag.assign(w.size(), 0); nin.assign(w.size(), 0); its.assign(w.size(), 0);
+// the problems `which` of a batch as a batch of their own (concatenated copies) through one pass, their results written back; `again`
+// (may be NULL) collects those the pass left unfinished
+static dvs_status fm_cv_subset_pass(dvs_matcher* ctx, const std::vector<int>& which, const int32_t* offsets, const float* pts1, const float* pts2, const FmCvPolicy& P,
+                                    int32_t H, bool lmeds, double* F9, uint8_t* inlier_mask, int32_t* n_inliers, int32_t* iterations, std::vector<int>* again) {
+  const size_t m = which.size();
+  std::vector<int32_t> off(m + 1, 0);
+  for (size_t i = 0; i < m; i++) off[i + 1] = off[i] + (offsets[which[i] + 1] - offsets[which[i]]);
+  std::vector<float> q1((size_t)off[m] * 2 + 2), q2((size_t)off[m] * 2 + 2);
+  for (size_t i = 0; i < m; i++) {
+    memcpy(q1.data() + 2 * (size_t)off[i], pts1 + 2 * (size_t)offsets[which[i]], (size_t)(off[i + 1] - off[i]) * 8);
+    memcpy(q2.data() + 2 * (size_t)off[i], pts2 + 2 * (size_t)offsets[which[i]], (size_t)(off[i + 1] - off[i]) * 8);
   }
-  void scatter(const int32_t* offsets, double* F9, uint8_t* inlier_mask, int32_t* n_inliers, int32_t* iterations) const {
-    for (size_t i = 0; i < which.size(); i++) {
-      const int b = which[i], n = offsets[b + 1] - offsets[b];
-      memcpy(inlier_mask + offsets[b], mask.data() + off[i], (size_t)n);
-      if (n_inliers) n_inliers[b] = nin[i];
-      if (iterations) iterations[b] = its[i];
-      if (F9) memcpy(F9 + 9 * (size_t)b, F.data() + 9 * i, 72);
-    }
+  std::vector<double> F(m * 9, 0.0);
+  std::vector<uint8_t> mask((size_t)off[m] + 1, 0), flag(m, 0);
+  std::vector<int32_t> nin(m, 0), its(m, 0);
+  DVS_TRY(fm_cv_batch_pass(ctx, (int)m, off.data(), q1.data(), q2.data(), P, H, lmeds, F.data(), mask.data(), nin.data(), its.data(), flag.data()));
+  for (size_t i = 0; i < m; i++) {
+    const int b = which[i];
+    memcpy(inlier_mask + offsets[b], mask.data() + off[i], (size_t)(off[i + 1] - off[i]));
+    if (n_inliers) n_inliers[b] = nin[i];
+    if (iterations) iterations[b] = its[i];
+    if (F9) memcpy(F9 + 9 * (size_t)b, F.data() + 9 * i, kFmModelBytes);
+    if (again && flag[i]) again->push_back(b);
   }
-};
-
-}  // namespace dvs
-
-using namespace dvs;
-
-// the 5-point samples of cv::solvePnPRansac's RANSAC stage: getSubset without a checkSubset (host: the sequence is sequential by nature)
-static void cv_subsets_nocheck(int n, int modelPoints, int iters, int32_t* idx_out) {
-  CvRng rng(~0ull);
-  for (int it = 0; it < iters; it++)
-    for (int i = 0; i < modelPoints; i++) {
-      int v;
-      bool dup;
-      do {
-        v = rng.uniform(0, n);
-        dup = false;
-        for (int j = 0; j < i; j++) dup = dup || idx_out[(size_t)it * modelPoints + j] == v;
-      } while (dup);
-      idx_out[(size_t)it * modelPoints + i] = v;
-    }
+  return DVS_OK;
 }
 
-static void launch_pnp_cv(hipStream_t st, int nprob, const RansacProb* d_probs, const float* d_obj, const float* d_img, const int* d_samples, int H, const double* K4,
-                          double reproj_err, double confidence, double* d_models, int* d_counts, int* d_sel, int* d_inl, unsigned char* d_out) {
-  const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3];
-  const float thr = (float)(reproj_err * reproj_err);
-  hipLaunchKernelGGL(k_epnp_hypotheses, dim3((H + kEpnpGroups - 1) / kEpnpGroups, nprob), dim3(64), 0, st, d_obj, d_img, d_probs, d_samples, H, fx, fy, cx, cy, d_models);
-  hipLaunchKernelGGL(k_pnpcv_score, dim3(H, nprob), dim3(256), 0, st, d_obj, d_img, d_probs, H, d_models, fx, fy, cx, cy, thr, d_counts);
-  hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d_counts, H, d_probs, 5, confidence, 1, d_sel, 1, H);
-  hipLaunchKernelGGL(k_pnpcv_refit, dim3(nprob), dim3(64), 0, st, d_obj, d_img, d_probs, H, d_models, d_sel, fx, fy, cx, cy, thr, d_inl, d_out DVS_REFIT_DBG_NONE);
+// the body of dvs_solve_pnp_ransac_batch; inliers: concatenated like the points (problem b's ascending inlier indices at inliers +
+// offsets[b], n_inliers[b] of them)
+static dvs_status pnp_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
+                                int32_t iterations, double reproj_err, double confidence, const uint64_t* seeds, double* rvec3, double* tvec3,
+                                int32_t* inliers, int32_t* n_inliers, int32_t* success, PnpLayout* dev = nullptr) {
+  if (dev) *dev = PnpLayout();
+  DVS_ARG(ctx && nprob >= 0 && iterations >= 1 && iterations <= kPnpMaxIters && K4 && reproj_err > 0);
+  if (nprob == 0) return DVS_OK;
+  int maxn, total;
+  DVS_TRY(batch_extent(nprob, offsets, &maxn, &total));
+  DVS_ARG(seeds && rvec3 && tvec3 && success && (total == 0 || (pts3d && pts2d)));
+  pnp_zero_outputs(nprob, rvec3, tvec3, n_inliers, success, nullptr);
+  if (maxn < kPnpOwnMinPoints) return DVS_OK;   // cv::solvePnPRansac: "npoints >= 4"
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  PnpLayout d, h;
+  PinnedIo* io;
+  DVS_TRY(lay_out_batch(ctx, false, nprob, total, iterations, &d, &h, &io));
+  for (int b = 0; b < nprob; b++) h.probs[b] = RansacProb::seeded(offsets[b], offsets[b + 1] - offsets[b], seeds[b]);
+  memcpy(h.obj, pts3d, (size_t)total * 12); memcpy(h.img, pts2d, (size_t)total * 8);
+  io->import(st, d.probs, d.inb);
+  pnp_own_pass(st, d, nprob, d.obj, d.img, d.inl, d.rec, iterations, K4, reproj_err, confidence);
+  if (dev) *dev = d;
+  DVS_TRY(io->fetch(st, d.rec, h.rec, d.outb, kExportMax));
+  h.unpack(nprob, offsets, false, rvec3, tvec3, inliers, n_inliers, success);
+  return DVS_OK;
+}
+
+// the body of dvs_solve_pnp_ransac_cv_batch: cv::solvePnPRansac(obj, img, K, no distortion, rvec, tvec, false, iterations, reproj_err,
+// confidence, inliers) as OpenCV 4.x runs it with its default flags (csrc/pnp_cv.h).  Problems with fewer than 6 points are refused per
+// problem (success 0; the reference returns before the call, frontend.cpp:900).  iterations_run[b] = iterations the adaptive loop used
+// (may be NULL).
+static dvs_status pnp_cv_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
+                               int32_t iterations, double reproj_err, double confidence, double* rvec3, double* tvec3, int32_t* inliers,
+                               int32_t* n_inliers, int32_t* success, int32_t* iterations_run, PnpLayout* dev = nullptr) {
+  if (dev) *dev = PnpLayout();
+  DVS_ARG(ctx && nprob >= 0 && iterations >= 1 && iterations <= kPnpMaxIters && K4 && reproj_err > 0 && confidence > 0 && confidence < 1);
+  if (nprob == 0) return DVS_OK;
+  int maxn, total;
+  DVS_TRY(batch_extent(nprob, offsets, &maxn, &total));
+  DVS_ARG(rvec3 && tvec3 && success && (total == 0 || (pts3d && pts2d)));
+  pnp_zero_outputs(nprob, rvec3, tvec3, n_inliers, success, iterations_run);
+  DVS_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  PnpLayout d, h;
+  PinnedIo* io;
+  DVS_TRY(lay_out_batch(ctx, true, nprob, total, iterations, &d, &h, &io));
+  memcpy(h.obj, pts3d, (size_t)total * 12); memcpy(h.img, pts2d, (size_t)total * 8);
+  pnp_cv_pass(st, io, d, h, nprob, offsets, d.obj, d.img, d.inl, d.rec, d.sel, iterations, K4, reproj_err, confidence);
+  if (dev) *dev = d;
+  DVS_TRY(io->fetch(st, d.rec, h.rec, d.outb, kExportMax));
+  h.unpack(nprob, offsets, true, rvec3, tvec3, inliers, n_inliers, success);
+  if (iterations_run) for (int b = 0; b < nprob; b++) iterations_run[b] = h.sel[kSel * b + 1];
+  return DVS_OK;
 }
 
 // ---- the device forms (ransac_device.h): one problem whose points already live on the device; argument rules as the host entry points'
-namespace dvs {
-
 dvs_status fm_own_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, const int* d_n, int n_bound, unsigned long long seed, double threshold,
                          double confidence, int max_iters, unsigned char* d_mask) {
-  DVS_ARG(ctx && d_p1 && d_p2 && d_n && d_mask && n_bound >= 0 && max_iters >= 1 && max_iters <= 4096 && threshold > 0);
+  DVS_ARG(ctx && d_p1 && d_p2 && d_n && d_mask && n_bound >= 0 && max_iters >= 1 && max_iters <= kFmMaxIters && threshold > 0);
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int H = max_iters;
-  const size_t fb = (size_t)H * 72, vb = (size_t)H * 4;
-  uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, 16 + fb + 2 * vb + 16 + 72 + 64, (void**)&base));
-  RansacProb* d_prob = (RansacProb*)base;
-  double* d_F = (double*)(base + 16);
-  int* d_valid = (int*)(base + 16 + fb); int* d_counts = (int*)(base + 16 + fb + vb);
-  int* d_sel = (int*)(base + 16 + fb + 2 * vb); double* d_Fb = (double*)(base + 16 + fb + 2 * vb + 16);
-  hipLaunchKernelGGL(k_ransac_prob, dim3(1), dim3(1), 0, st, d_prob, d_n, seed);
-  launch_fm_own(st, 1, n_bound, d_prob, d_p1, d_p2, H, threshold, confidence, d_F, d_valid, d_counts, d_sel, d_mask, d_Fb);
+  FmLayout d;
+  DVS_TRY(lay_out(ctx, kFormDevice, false, 1, 0, max_iters, &d));
+  hipLaunchKernelGGL(k_ransac_prob, dim3(1), dim3(1), 0, st, d.probs, d_n, seed);
+  fm_own_pass(st, d, 1, n_bound, d_p1, d_p2, d_mask, max_iters, threshold, confidence);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
 
 dvs_status pnp_own_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, const int* d_n, unsigned long long seed, const double* K4,
                           int iterations, double reproj_err, double confidence, int* d_inl, unsigned char* d_out64) {
-  DVS_ARG(ctx && d_obj && d_img && d_n && K4 && d_inl && d_out64 && iterations >= 1 && iterations <= 1024 && reproj_err > 0);
+  DVS_ARG(ctx && d_obj && d_img && d_n && K4 && d_inl && d_out64 && iterations >= 1 && iterations <= kPnpMaxIters && reproj_err > 0);
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int H = iterations, H4 = 4 * H;
-  const size_t posb = (size_t)H4 * 96, vb = (size_t)H4 * 4;
-  uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, 16 + posb + 2 * vb + 16 + 64, (void**)&base));
-  RansacProb* d_prob = (RansacProb*)base;
-  double* d_poses = (double*)(base + 16);
-  int* d_valid = (int*)(base + 16 + posb); int* d_counts = (int*)(base + 16 + posb + vb);
-  int* d_sel = (int*)(base + 16 + posb + 2 * vb);
-  hipLaunchKernelGGL(k_ransac_prob, dim3(1), dim3(1), 0, st, d_prob, d_n, seed);
-  launch_pnp_own(st, 1, d_prob, d_obj, d_img, H, K4, reproj_err, confidence, d_poses, d_valid, d_counts, d_sel, d_inl, d_out64);
+  PnpLayout d;
+  DVS_TRY(lay_out(ctx, kFormDevice, false, 1, 0, iterations, &d));
+  hipLaunchKernelGGL(k_ransac_prob, dim3(1), dim3(1), 0, st, d.probs, d_n, seed);
+  pnp_own_pass(st, d, 1, d_obj, d_img, d_inl, d_out64, iterations, K4, reproj_err, confidence);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
 
 dvs_status fm_cv_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, int n, double threshold, double confidence, int max_iters,
                         unsigned char* d_mask) {
-  DVS_ARG(ctx && d_p1 && d_p2 && d_mask && n >= 8 && max_iters >= 1 && max_iters <= 4096);
-  if (threshold <= 0) threshold = 3;                                                 // as cv::findFundamentalMat
-  if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
+  DVS_ARG(ctx && d_p1 && d_p2 && d_mask && n >= kFmCvMinPoints && max_iters >= 1 && max_iters <= kFmMaxIters);
+  const FmCvPolicy P = fm_cv_policy(threshold, confidence, max_iters);
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const bool lmeds = n < 15;
-  const int Hfull = lmeds ? std::max(ransac_update_iters_host(confidence, 0.45, 7, max_iters), 3) : max_iters;
-  const size_t pb = ((size_t)n * 8 + 15) & ~(size_t)15, sbmax = ((size_t)Hfull * 7 * 4 + 15) & ~(size_t)15;
+  const bool lmeds = P.lmeds(n);
+  const int Hfull = lmeds ? P.lmeds_iters() : max_iters;
+  // pinned: [pts1 | pts2 | the mirror of a pass's layout, with room for the longest pass]
+  float *hp1, *hp2;
+  uint8_t* hpass;
+  const auto carve = [&](Carver c) {
+    c.take(hp1, 2 * (size_t)n); c.take(hp2, 2 * (size_t)n); c.take(hpass, FmLayout(nullptr, kFormPinned, true, 1, 0, Hfull).bytes);
+    return c.used;
+  };
   PinnedIo* io;
-  DVS_TRY(matcher_pinned(ctx, 2 * pb + 16 + sbmax + 128, &io));
-  uint8_t* hio = io->h();
-  float* hp1 = (float*)hio; float* hp2 = (float*)(hio + pb);
-  uint8_t* hin = hio + 2 * pb;                 // [problem record | samples] of a pass
-  int* hsel = (int*)(hio + 2 * pb + 16 + sbmax);
+  DVS_TRY(matcher_pinned(ctx, carve(Carver{nullptr, 16}), &io));
+  carve(Carver{io->h(), 16});
   DVS_HIP(hipMemcpyAsync(hp1, d_p1, (size_t)n * 8, hipMemcpyDeviceToHost, st));   // what the sampler's collinearity test reads
   DVS_HIP(hipMemcpyAsync(hp2, d_p2, (size_t)n * 8, hipMemcpyDeviceToHost, st));
   DVS_HIP(hipStreamSynchronize(st));
-  int H = lmeds ? Hfull : std::min<int>(max_iters, 96);   // RANSAC: the models of 96 iterations first, all of them only if the loop asks (dvs_find_fundamental_cv_batch)
-  for (;;) {
-    const int H3 = 3 * H;
-    const size_t sb = ((size_t)H * 7 * 4 + 15) & ~(size_t)15, inb = 16 + sb;
-    const size_t fb = (size_t)H3 * 72, vb = (size_t)H3 * 4;
-    uint8_t* base;
-    DVS_TRY(matcher_scratch(ctx, 0, inb + fb + 2 * vb + 16 + 72 + 64, (void**)&base));
-    int32_t* hs = (int32_t*)(hin + 16);
-    memset(hs, 0, sb);
-    const int found = cv_subsets(hp1, hp2, n, 7, H, hs, lmeds ? 1000 : 10000);
-    *(RansacProb*)hin = RansacProb{0, n, (unsigned long long)found};
-    double* d_F = (double*)(base + inb);
-    int* d_valid = (int*)(base + inb + fb); int* d_counts = (int*)(base + inb + fb + vb);
-    int* d_sel = (int*)(base + inb + fb + 2 * vb); double* d_Fb = (double*)(base + inb + fb + 2 * vb + 16);
-    io->import(st, base, inb, 2 * pb);
-    launch_fm_cv(st, 1, n, (const RansacProb*)base, d_p1, d_p2, (const int32_t*)(base + 16), H, lmeds, threshold, confidence, max_iters, d_F, d_valid, d_counts,
-                 d_sel, d_mask, d_Fb);
-    DVS_TRY(io->fetch(st, d_sel, hsel, 16, 16));   // the select record alone: the mask stays on the device
-    if (lmeds || !hsel[3] || H >= max_iters) break;
-    H = max_iters;
+  const int32_t offsets[2] = {0, n};
+  for (int H = lmeds ? Hfull : P.first_pass();; H = max_iters) {
+    FmLayout d;
+    DVS_TRY(lay_out(ctx, kFormDevice, true, 1, 0, H, &d));
+    const FmLayout h(hpass, kFormPinned, true, 1, 0, H);
+    fm_cv_pass(st, io, d, h, 1, offsets, hp1, hp2, n, d_p1, d_p2, d_mask, H, lmeds, P);
+    DVS_TRY(io->fetch(st, d.sel, h.sel, 16, 16));   // the select record alone: the mask stays on the device
+    if (lmeds || !P.wants_full(h.sel, H)) break;
   }
   return DVS_OK;
 }
 
 dvs_status pnp_cv_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, int n, const double* K4, int iterations, double reproj_err,
                          double confidence, int* d_inl, unsigned char* d_out64, int* d_sel4) {
-  DVS_ARG(ctx && d_obj && d_img && K4 && d_inl && d_out64 && d_sel4 && n >= 6 && iterations >= 1 && iterations <= 1024 && reproj_err > 0 && confidence > 0 &&
-          confidence < 1);
+  DVS_ARG(ctx && d_obj && d_img && K4 && d_inl && d_out64 && d_sel4 && n >= kPnpCvMinPoints && iterations >= 1 && iterations <= kPnpMaxIters && reproj_err > 0 &&
+          confidence > 0 && confidence < 1);
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int H = iterations;
-  const size_t sb = ((size_t)H * 5 * 4 + 15) & ~(size_t)15, inb = 16 + sb;
-  const size_t mb = (size_t)H * 18 * 8, vb = (size_t)H * 4;
-  uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, inb + mb + vb + 64, (void**)&base));
+  PnpLayout d;
+  DVS_TRY(lay_out(ctx, kFormDevice, true, 1, 0, iterations, &d));
   PinnedIo* io;
-  DVS_TRY(matcher_pinned(ctx, inb, &io));
-  int32_t* hs = (int32_t*)(io->h() + 16);
-  memset(hs, 0, sb);
-  cv_subsets_nocheck(n, 5, H, hs);
-  *(RansacProb*)io->h() = RansacProb{0, n, (unsigned long long)H};
-  io->import(st, base, inb);   // (returns with the import still reading the block: PinnedIo::reserve waits before it releases one)
-  launch_pnp_cv(st, 1, (const RansacProb*)base, d_obj, d_img, (const int*)(base + 16), H, K4, reproj_err, confidence, (double*)(base + inb),
-                (int*)(base + inb + mb), d_sel4, d_inl, d_out64);
+  DVS_TRY(matcher_pinned(ctx, d.inb, &io));
+  const PnpLayout h(io->h(), kFormPinned, true, 1, 0, iterations);
+  const int32_t offsets[2] = {0, n};
+  // (returns with the import still reading the block: PinnedIo::reserve waits before it releases one)
+  pnp_cv_pass(st, io, d, h, 1, offsets, d_obj, d_img, d_inl, d_out64, d_sel4, iterations, K4, reproj_err, confidence);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
 
 }  // namespace dvs
+
+using namespace dvs;
 
 extern "C" {
 
@@ -1274,94 +1279,32 @@ int32_t dvs_test_p3p(const double* P9, const double* j9, double* poses48) {
 #endif  // DVS_TEST_HOOKS
 
 // ---- batches of independent RANSAC problems (one launch sequence for all of them; the single-problem entry points are batches of one) ----
-// problem b = correspondences [offsets[b], offsets[b + 1]) of the concatenated point arrays, sampler seed seeds[b]
-// (the body of dvs_find_fundamental_ransac_batch; `dev`: DVS_STAGES_PARAM above, for dvs_test_fm_stages)
-static dvs_status fm_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
-                               double confidence, int32_t max_iters, const uint64_t* seeds, double* F9, uint8_t* inlier_mask, int32_t* n_inliers
-                               DVS_STAGES_PARAM) {
-  DVS_STAGES_SET(nullptr, nullptr, nullptr, nullptr);
-  DVS_ARG(ctx && nprob >= 0 && max_iters >= 1 && max_iters <= 4096 && threshold > 0);
-  if (nprob == 0) return DVS_OK;
-  DVS_ARG(offsets && seeds && offsets[0] == 0);
-  int maxn = 0;
-  for (int b = 0; b < nprob; b++) { DVS_ARG(offsets[b + 1] >= offsets[b]); maxn = std::max(maxn, offsets[b + 1] - offsets[b]); }
-  const int total = offsets[nprob];
-  DVS_ARG(total == 0 || (pts1 && pts2 && inlier_mask));
-  if (n_inliers) memset(n_inliers, 0, (size_t)nprob * 4);
-  if (F9) memset(F9, 0, (size_t)nprob * 72);
-  if (total) memset(inlier_mask, 0, (size_t)total);
-  if (maxn < 8) return DVS_OK;   // cv::findFundamentalMat needs >= 7 points for FM_RANSAC (8 for our kernel): empty F, masks of zeros
-  DVS_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int H = max_iters;
-  const size_t nmodels = (size_t)nprob * H;
-  uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, FmIo(nullptr, nprob, total, 0, nmodels).bytes + 64, (void**)&base));
-  const FmIo d(base, nprob, total, 0, nmodels);
-  PinnedIo* io;
-  DVS_TRY(matcher_pinned(ctx, d.inb + d.outb, &io));
-  const FmIo h(io->h(), nprob, total, 0, 0);
-  for (int b = 0; b < nprob; b++) h.probs[b] = RansacProb{offsets[b], offsets[b + 1] - offsets[b], (unsigned long long)seeds[b]};
-  memcpy(h.p1, pts1, (size_t)total * 8); memcpy(h.p2, pts2, (size_t)total * 8);
-  io->import(st, base, d.inb);
-  launch_fm_own(st, nprob, maxn, d.probs, d.p1, d.p2, H, threshold, confidence, d.models, d.valid, d.counts, d.sel, d.mask, d.F);
-  DVS_STAGES_SET(d.models, d.valid, d.counts, d.sel);
-  DVS_TRY(io->fetch(st, d.sel, h.sel, d.outb, kExportMax));
-  h.unpack(nprob, total, F9, inlier_mask, n_inliers);
-  return DVS_OK;
-}
 dvs_status dvs_find_fundamental_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
                                              double confidence, int32_t max_iters, const uint64_t* seeds, double* F9, uint8_t* inlier_mask,
                                              int32_t* n_inliers) {
-  return fm_own_batch(ctx, nprob, offsets, pts1, pts2, threshold, confidence, max_iters, seeds, F9, inlier_mask, n_inliers DVS_STAGES_NONE);
+  return fm_own_batch(ctx, nprob, offsets, pts1, pts2, threshold, confidence, max_iters, seeds, F9, inlier_mask, n_inliers);
 }
 
 // cv::findFundamentalMat(FM_RANSAC) the way OpenCV 4.x runs it (see k_f7_hypotheses): RANSAC from 15 correspondences on, LMedS for 8..14
 // (OpenCV switches there: k_lmeds_select); fewer than 8 are DVS_ERR_UNSUPPORTED (the reference calls with >= 8, frontend.cpp:627)
 dvs_status dvs_find_fundamental_cv_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
                                          double confidence, int32_t max_iters, double* F9, uint8_t* inlier_mask, int32_t* n_inliers, int32_t* iterations) {
-  DVS_ARG(ctx && nprob >= 0 && max_iters >= 1 && max_iters <= 4096);
+  DVS_ARG(ctx && nprob >= 0 && max_iters >= 1 && max_iters <= kFmMaxIters);
   if (nprob == 0) return DVS_OK;
   DVS_ARG(offsets && offsets[0] == 0 && pts1 && pts2 && inlier_mask);
-  if (threshold <= 0) threshold = 3;                                                 // as cv::findFundamentalMat
-  if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
-  std::vector<int> big, small;
+  const FmCvPolicy P = fm_cv_policy(threshold, confidence, max_iters);
+  std::vector<int> big, small, again;
   for (int b = 0; b < nprob; b++) {
     DVS_ARG(offsets[b + 1] >= offsets[b]);
     const int n = offsets[b + 1] - offsets[b];
-    if (n < 8) { set_error("dvs_find_fundamental_cv: problem %d has %d correspondences (the reference calls with >= 8, frontend.cpp:627)", b, n); return DVS_ERR_UNSUPPORTED; }
-    (n >= 15 ? big : small).push_back(b);
+    if (n < kFmCvMinPoints) { set_error("dvs_find_fundamental_cv: problem %d has %d correspondences (the reference calls with >= 8, frontend.cpp:627)", b, n); return DVS_ERR_UNSUPPORTED; }
+    (P.lmeds(n) ? small : big).push_back(b);
   }
   DVS_HIP(hipSetDevice(ctx->device));
-  // ---- >= 15 points: RANSAC.  The adaptive rule ends most loops after a few dozen iterations (10 % outliers: ~10), and the sample
-  // sequence is the same whatever the number of samples drawn: first the models of 96 iterations for every problem, then — only for
-  // the problems whose loop wanted more — all max_iters (the same result a full run gives, by construction: a prefix of the same sequence).
-  if (!big.empty()) {
-    FmSubset A;
-    A.gather(big, offsets, pts1, pts2);
-    const int H1 = std::min<int>(max_iters, 96);
-    DVS_TRY(fm_cv_pass(ctx, (int)big.size(), A.off.data(), A.q1.data(), A.q2.data(), threshold, confidence, max_iters, H1, A.F.data(), A.mask.data(), A.nin.data(),
-                       A.its.data(), A.flag.data() DVS_STAGES_NONE));
-    A.scatter(offsets, F9, inlier_mask, n_inliers, iterations);
-    std::vector<int> again;
-    for (size_t i = 0; i < big.size(); i++) if (A.flag[i]) again.push_back(big[i]);
-    if (!again.empty() && H1 < max_iters) {
-      FmSubset B;
-      B.gather(again, offsets, pts1, pts2);
-      DVS_TRY(fm_cv_pass(ctx, (int)again.size(), B.off.data(), B.q1.data(), B.q2.data(), threshold, confidence, max_iters, max_iters, B.F.data(), B.mask.data(),
-                         B.nin.data(), B.its.data(), B.flag.data() DVS_STAGES_NONE));
-      B.scatter(offsets, F9, inlier_mask, n_inliers, iterations);
-    }
-  }
-  // ---- 8 .. 14 points: LMedS with its fixed iteration count (k_lmeds_select)
-  if (!small.empty()) {
-    const int niters = std::max(ransac_update_iters_host(confidence, 0.45, 7, max_iters), 3);   // outlierRatio = 0.45; 300 for 0.99
-    FmSubset C;
-    C.gather(small, offsets, pts1, pts2);
-    DVS_TRY(fm_cv_pass(ctx, (int)small.size(), C.off.data(), C.q1.data(), C.q2.data(), threshold, confidence, max_iters, niters, C.F.data(), C.mask.data(), C.nin.data(),
-                       C.its.data(), C.flag.data() DVS_STAGES_NONE, true));
-    C.scatter(offsets, F9, inlier_mask, n_inliers, iterations);
-  }
+  if (!big.empty()) DVS_TRY(fm_cv_subset_pass(ctx, big, offsets, pts1, pts2, P, P.first_pass(), false, F9, inlier_mask, n_inliers, iterations, &again));
+  if (!again.empty() && P.first_pass() < max_iters)
+    DVS_TRY(fm_cv_subset_pass(ctx, again, offsets, pts1, pts2, P, max_iters, false, F9, inlier_mask, n_inliers, iterations, nullptr));
+  if (!small.empty()) DVS_TRY(fm_cv_subset_pass(ctx, small, offsets, pts1, pts2, P, P.lmeds_iters(), true, F9, inlier_mask, n_inliers, iterations, nullptr));
   return DVS_OK;
 }
 
@@ -1373,66 +1316,17 @@ dvs_status dvs_find_fundamental_cv(dvs_matcher* ctx, const float* pts1, const fl
 }
 
 // host only (no GPU): the sample sequence of the call above — iteration it draws idx[7 it .. 7 it + 6]; *found = iterations that have one
+// (pts1 = pts2 = NULL: a callback without checkSubset, as cv::solvePnPRansac's)
 dvs_status dvs_cv_ransac_subsets(const float* pts1, const float* pts2, int32_t n, int32_t model_points, int32_t iterations, int32_t* idx, int32_t* found) {
   DVS_ARG(idx && found && n >= model_points && model_points >= 1 && model_points <= 16 && iterations >= 0 && (pts1 == nullptr) == (pts2 == nullptr));
-  if (!pts1) { cv_subsets_nocheck(n, model_points, iterations, idx); *found = iterations; }   // a callback without checkSubset (solvePnPRansac)
-  else *found = cv_subsets(pts1, pts2, n, model_points, iterations, idx);
+  *found = cv_subsets(pts1, pts2, n, model_points, iterations, idx);
   return DVS_OK;
 }
 
-// cv::solvePnPRansac(obj, img, K, no distortion, rvec, tvec, false, iterations, reproj_err, confidence, inliers) as OpenCV 4.x runs it with
-// its default flags (csrc/pnp_cv.h).  Problems with fewer than 6 points are refused per problem (success 0; the reference returns before
-// the call, frontend.cpp:900).  iterations_run[b] = iterations the adaptive loop used (may be NULL).
-// (the body of dvs_solve_pnp_ransac_cv_batch; `dev`: DVS_STAGES_PARAM above, for dvs_test_pnp_cv_stages — no `valid` array in this form)
-static dvs_status pnp_cv_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
-                               int32_t iterations, double reproj_err, double confidence, double* rvec3, double* tvec3, int32_t* inliers,
-                               int32_t* n_inliers, int32_t* success, int32_t* iterations_run DVS_STAGES_PARAM) {
-  DVS_STAGES_SET(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  DVS_ARG(ctx && nprob >= 0 && iterations >= 1 && iterations <= 1024 && K4 && reproj_err > 0 && confidence > 0 && confidence < 1);
-  if (nprob == 0) return DVS_OK;
-  DVS_ARG(offsets && rvec3 && tvec3 && success && offsets[0] == 0);
-  for (int b = 0; b < nprob; b++) DVS_ARG(offsets[b + 1] >= offsets[b]);
-  const int total = offsets[nprob];
-  DVS_ARG(total == 0 || (pts3d && pts2d));
-  memset(success, 0, (size_t)nprob * 4);
-  if (n_inliers) memset(n_inliers, 0, (size_t)nprob * 4);
-  if (iterations_run) memset(iterations_run, 0, (size_t)nprob * 4);
-  memset(rvec3, 0, (size_t)nprob * 24); memset(tvec3, 0, (size_t)nprob * 24);
-  DVS_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int H = iterations;
-  const size_t nh = (size_t)nprob * H;
-  const size_t workb = nh * (144 + 4);                                    // [models 144 x nh | counts 4 x nh]
-  uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, PnpIo(nullptr, nprob, total, nh, workb, true).bytes + 64, (void**)&base));
-  const PnpIo d(base, nprob, total, nh, workb, true);
-  double* d_models; int* d_counts;
-  Carver w{d.work, 4};
-  w.take(d_models, 18 * nh); w.take(d_counts, nh);
-  PinnedIo* io;
-  DVS_TRY(matcher_pinned(ctx, d.inb + d.outb, &io));
-  const PnpIo h(io->h(), nprob, total, nh, 0, true);
-  memset(h.samples, 0, h.sampb);
-  for (int b = 0; b < nprob; b++) {
-    const int n = offsets[b + 1] - offsets[b];
-    const bool run = n >= 6;     // (n == 5 would be solvePnP on all points, n == 4 the P3P kernel: not what the reference can reach)
-    if (run) cv_subsets_nocheck(n, 5, H, h.samples + (size_t)b * H * 5);
-    h.probs[b] = RansacProb{offsets[b], n, (unsigned long long)(run ? H : 0)};   // the seed field: iterations that have a sample
-  }
-  memcpy(h.obj, pts3d, (size_t)total * 12); memcpy(h.img, pts2d, (size_t)total * 8);
-  io->import(st, base, d.inb);
-  launch_pnp_cv(st, nprob, d.probs, d.obj, d.img, d.samples, H, K4, reproj_err, confidence, d_models, d_counts, d.sel, d.inl, d.rec);
-  DVS_STAGES_SET(d_models, nullptr, d_counts, d.sel, d.samples, d.probs, nullptr);
-  DVS_TRY(io->fetch(st, d.rec, h.rec, d.outb, kExportMax));
-  h.unpack(nprob, offsets, true, rvec3, tvec3, inliers, n_inliers, success);
-  if (iterations_run) for (int b = 0; b < nprob; b++) iterations_run[b] = h.sel[4 * b + 1];
-  return DVS_OK;
-}
 dvs_status dvs_solve_pnp_ransac_cv_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
                                          int32_t iterations, double reproj_err, double confidence, double* rvec3, double* tvec3, int32_t* inliers,
                                          int32_t* n_inliers, int32_t* success, int32_t* iterations_run) {
-  return pnp_cv_batch(ctx, nprob, offsets, pts3d, pts2d, K4, iterations, reproj_err, confidence, rvec3, tvec3, inliers, n_inliers, success,
-                      iterations_run DVS_STAGES_NONE);
+  return pnp_cv_batch(ctx, nprob, offsets, pts3d, pts2d, K4, iterations, reproj_err, confidence, rvec3, tvec3, inliers, n_inliers, success, iterations_run);
 }
 
 dvs_status dvs_solve_pnp_ransac_cv(dvs_matcher* ctx, const float* pts3d, const float* pts2d, int32_t n, const double* K4, int32_t iterations,
@@ -1451,49 +1345,10 @@ dvs_status dvs_find_fundamental_ransac(dvs_matcher* ctx, const float* pts1, cons
   return dvs_find_fundamental_ransac_batch(ctx, 1, offsets, pts1, pts2, threshold, confidence, max_iters, &seed, F9, inlier_mask, n_inliers);
 }
 
-// inliers: concatenated like the points (problem b's ascending inlier indices at inliers + offsets[b], n_inliers[b] of them)
-static dvs_status pnp_own_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
-                                int32_t iterations, double reproj_err, double confidence, const uint64_t* seeds, double* rvec3, double* tvec3,
-                                int32_t* inliers, int32_t* n_inliers, int32_t* success DVS_STAGES_PARAM) {   // `dev`: as fm_own_batch's
-  DVS_STAGES_SET(nullptr, nullptr, nullptr, nullptr);
-  DVS_ARG(ctx && nprob >= 0 && iterations >= 1 && iterations <= 1024 && K4 && reproj_err > 0);
-  if (nprob == 0) return DVS_OK;
-  DVS_ARG(offsets && seeds && rvec3 && tvec3 && success && offsets[0] == 0);
-  int maxn = 0;
-  for (int b = 0; b < nprob; b++) { DVS_ARG(offsets[b + 1] >= offsets[b]); maxn = std::max(maxn, offsets[b + 1] - offsets[b]); }
-  const int total = offsets[nprob];
-  DVS_ARG(total == 0 || (pts3d && pts2d));
-  memset(success, 0, (size_t)nprob * 4);
-  if (n_inliers) memset(n_inliers, 0, (size_t)nprob * 4);
-  memset(rvec3, 0, (size_t)nprob * 24); memset(tvec3, 0, (size_t)nprob * 24);
-  if (maxn < 4) return DVS_OK;   // cv::solvePnPRansac: "npoints >= 4"
-  DVS_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int H = iterations;
-  const size_t nh4 = (size_t)nprob * 4 * H;
-  const size_t workb = nh4 * (96 + 4 + 4) + (size_t)nprob * 16;   // [poses 96 x nh4 | valid | counts | select records 16 x nprob]
-  uint8_t* base;
-  DVS_TRY(matcher_scratch(ctx, 0, PnpIo(nullptr, nprob, total, 0, workb, false).bytes + 64, (void**)&base));
-  const PnpIo d(base, nprob, total, 0, workb, false);
-  double* d_poses; int *d_valid, *d_counts, *d_sel;
-  Carver w{d.work, 4};
-  w.take(d_poses, 12 * nh4); w.take(d_valid, nh4); w.take(d_counts, nh4); w.take(d_sel, 4 * (size_t)nprob);
-  PinnedIo* io;
-  DVS_TRY(matcher_pinned(ctx, d.inb + d.outb, &io));
-  const PnpIo h(io->h(), nprob, total, 0, 0, false);
-  for (int b = 0; b < nprob; b++) h.probs[b] = RansacProb{offsets[b], offsets[b + 1] - offsets[b], (unsigned long long)seeds[b]};
-  memcpy(h.obj, pts3d, (size_t)total * 12); memcpy(h.img, pts2d, (size_t)total * 8);
-  io->import(st, base, d.inb);
-  launch_pnp_own(st, nprob, d.probs, d.obj, d.img, H, K4, reproj_err, confidence, d_poses, d_valid, d_counts, d_sel, d.inl, d.rec);
-  DVS_STAGES_SET(d_poses, d_valid, d_counts, d_sel);
-  DVS_TRY(io->fetch(st, d.rec, h.rec, d.outb, kExportMax));
-  h.unpack(nprob, offsets, false, rvec3, tvec3, inliers, n_inliers, success);
-  return DVS_OK;
-}
 dvs_status dvs_solve_pnp_ransac_batch(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts3d, const float* pts2d, const double* K4,
                                       int32_t iterations, double reproj_err, double confidence, const uint64_t* seeds, double* rvec3, double* tvec3,
                                       int32_t* inliers, int32_t* n_inliers, int32_t* success) {
-  return pnp_own_batch(ctx, nprob, offsets, pts3d, pts2d, K4, iterations, reproj_err, confidence, seeds, rvec3, tvec3, inliers, n_inliers, success DVS_STAGES_NONE);
+  return pnp_own_batch(ctx, nprob, offsets, pts3d, pts2d, K4, iterations, reproj_err, confidence, seeds, rvec3, tvec3, inliers, n_inliers, success);
 }
 
 dvs_status dvs_solve_pnp_ransac(dvs_matcher* ctx, const float* pts3d, const float* pts2d, int32_t n, const double* K4, int32_t iterations,
@@ -1505,24 +1360,25 @@ dvs_status dvs_solve_pnp_ransac(dvs_matcher* ctx, const float* pts3d, const floa
 }
 
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h): the stages of the two own estimators, one by one
-// the product call (fm_own_batch: same import, same launches, same grids) and, beside its results, what each stage left on the device
+// the product call (fm_own_batch: same import, same launches, same grids) and, beside its results, what each stage left on the device,
+// read through the layout the call hands back
 dvs_status dvs_test_fm_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold, double confidence,
                               int32_t H, const uint64_t* seeds, double* F_all, int32_t* valid, int32_t* counts, int32_t* sel, uint8_t* mask, double* Fbest) {
   DVS_ARG(ctx && nprob >= 1 && H >= 1 && offsets && F_all && valid && counts && sel && Fbest);
-  StagesDev dev;
+  FmLayout dev;
   DVS_TRY(fm_own_batch(ctx, nprob, offsets, pts1, pts2, threshold, confidence, H, seeds, Fbest, mask, nullptr, &dev));
   const size_t nh = (size_t)nprob * H;
   if (!dev.models) {   // no problem had 8 points: nothing ran
-    memset(F_all, 0, nh * 72); memset(valid, 0, nh * 4); memset(counts, 0, nh * 4);
+    memset(F_all, 0, nh * kFmModelBytes); memset(valid, 0, nh * 4); memset(counts, 0, nh * 4);
     for (int b = 0; b < nprob; b++) { sel[4 * b] = -1; sel[4 * b + 1] = sel[4 * b + 2] = sel[4 * b + 3] = 0; }
     return DVS_OK;
   }
-  DVS_HIP(hipMemcpy(F_all, dev.models, nh * 72, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(F_all, dev.models, nh * kFmModelBytes, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(valid, dev.valid, nh * 4, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(counts, dev.counts, nh * 4, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(sel, dev.sel, (size_t)nprob * 16, hipMemcpyDeviceToHost));
   // k_f_hypotheses writes no model for a problem of fewer than 8 points (its `valid` says so): zeros, not what the scratch block held
-  for (int b = 0; b < nprob; b++) if (offsets[b + 1] - offsets[b] < 8) memset(F_all + 9 * (size_t)H * b, 0, (size_t)H * 72);
+  for (int b = 0; b < nprob; b++) if (offsets[b + 1] - offsets[b] < 8) memset(F_all + 9 * (size_t)H * b, 0, (size_t)H * kFmModelBytes);
   return DVS_OK;
 }
 
@@ -1530,15 +1386,15 @@ dvs_status dvs_test_pnp_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* o
                                double confidence, int32_t H, const uint64_t* seeds, double* poses, int32_t* valid, int32_t* counts, int32_t* sel,
                                int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
   DVS_ARG(ctx && nprob >= 1 && H >= 1 && offsets && poses && valid && counts && sel && n_inliers && success && rvec3 && tvec3);
-  StagesDev dev;
+  PnpLayout dev;
   DVS_TRY(pnp_own_batch(ctx, nprob, offsets, pts3d, pts2d, K4, H, reproj_err, confidence, seeds, rvec3, tvec3, inliers, n_inliers, success, &dev));
   const size_t nh = (size_t)nprob * 4 * H;
   if (!dev.models) {   // no problem had 4 points: nothing ran
-    memset(poses, 0, nh * 96); memset(valid, 0, nh * 4); memset(counts, 0, nh * 4);
+    memset(poses, 0, nh * kPosePnpBytes); memset(valid, 0, nh * 4); memset(counts, 0, nh * 4);
     for (int b = 0; b < nprob; b++) { sel[4 * b] = -1; sel[4 * b + 1] = sel[4 * b + 2] = sel[4 * b + 3] = 0; }
     return DVS_OK;
   }
-  DVS_HIP(hipMemcpy(poses, dev.models, nh * 96, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(poses, dev.models, nh * kPosePnpBytes, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(valid, dev.valid, nh * 4, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(counts, dev.counts, nh * 4, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(sel, dev.sel, (size_t)nprob * 16, hipMemcpyDeviceToHost));
@@ -1550,7 +1406,7 @@ dvs_status dvs_test_ransac_select(const int32_t* counts, int32_t H, int32_t n, i
   DVS_ARG(counts && sel4 && H >= 1 && n >= 1 && model_points >= 1 && group >= 1 && H % group == 0);
   DeviceBuf<int> dc, ds; DeviceBuf<RansacProb> dp;
   DVS_TRY(dc.upload(std::vector<int>(counts, counts + H)));
-  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb{0, n, 0ull})));
+  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb::seeded(0, n, 0ull))));
   DVS_TRY(ds.alloc(4));
   hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(1), 0, 0, dc.get(), H, dp.get(), model_points, confidence, group, ds.get(), 0, 0);
   DVS_HIP(hipGetLastError());
@@ -1559,7 +1415,7 @@ dvs_status dvs_test_ransac_select(const int32_t* counts, int32_t H, int32_t n, i
 }
 
 // k_pnp_refine alone on ONE problem with a pose of the caller's as the selected one (pose12 = R row-major, t; NULL: nothing selected,
-// sel[0] = -1), grid and block as launch_pnp_own's for one problem.  What launch_pnp_own cannot reach: select takes no pose with fewer
+// sel[0] = -1), grid and block as pnp_own_pass's for one problem.  What pnp_own_pass cannot reach: select takes no pose with fewer
 // than 3 inliers, so the kernel's "fewer than 3 inliers: no LM step" path never runs through it.  inliers: room for n indices.
 dvs_status dvs_test_pnp_refine(const float* pts3d, const float* pts2d, int32_t n, const double* K4, const double* pose12, double reproj_err,
                                int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
@@ -1567,16 +1423,16 @@ dvs_status dvs_test_pnp_refine(const float* pts3d, const float* pts2d, int32_t n
   DeviceBuf<float> dobj, dimg; DeviceBuf<RansacProb> dp; DeviceBuf<double> dpose; DeviceBuf<int> dsel, dinl; DeviceBuf<unsigned char> dres;
   DVS_TRY(dobj.upload(std::vector<float>(pts3d, pts3d + 3 * (size_t)n)));
   DVS_TRY(dimg.upload(std::vector<float>(pts2d, pts2d + 2 * (size_t)n)));
-  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb{0, n, 0ull})));
+  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb::seeded(0, n, 0ull))));
   DVS_TRY(dpose.upload(pose12 ? std::vector<double>(pose12, pose12 + 12) : std::vector<double>(12, 0.0)));
   DVS_TRY(dsel.upload(std::vector<int>{pose12 ? 0 : -1, 1, 0, 0}));
   DVS_TRY(dinl.upload(std::vector<int>((size_t)n, -1)));
-  DVS_TRY(dres.alloc(64));
+  DVS_TRY(dres.alloc(kPnpRecord));
   hipLaunchKernelGGL(k_pnp_refine, dim3(1), dim3(256), 0, 0, dobj.get(), dimg.get(), dp.get(), 1, dpose.get(), dsel.get(), K4[0], K4[1], K4[2], K4[3],
                      reproj_err * reproj_err, dinl.get(), dres.get());
   DVS_HIP(hipGetLastError());
-  unsigned char res[64];
-  DVS_HIP(hipMemcpy(res, dres.get(), 64, hipMemcpyDeviceToHost));
+  unsigned char res[kPnpRecord];
+  DVS_HIP(hipMemcpy(res, dres.get(), kPnpRecord, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(inliers, dinl.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
   memcpy(n_inliers, res, 4); memcpy(success, res + 4, 4); memcpy(rvec3, res + 16, 24); memcpy(tvec3, res + 40, 24);
   return DVS_OK;
@@ -1586,7 +1442,7 @@ dvs_status dvs_test_pnp_refine(const float* pts3d, const float* pts2d, int32_t n
 void dvs_test_rotation_to_rodrigues(const double* R9, double* w3) { rotation_to_rodrigues(R9, w3); }
 
 // ---- the OpenCV-procedure forms (include/dvslam_hip_test_ransac_cv.h; tests/test_gpu_ransac_cv_stages.py)
-// ONE fm_cv_pass with the models of H iterations (the product's passes: H = min(max_iters, 96), then max_iters where the loop asked; LMedS:
+// ONE fm_cv_batch_pass with the models of H iterations (the product's passes: H = min(max_iters, 96), then max_iters where the loop asked; LMedS:
 // the fixed count) and, beside its results, what every stage left on the device.  A batch is of one kind — all problems >= 15 points
 // (RANSAC) or all 8 .. 14 (LMedS: no counts, zeros) — as the product's passes are.
 dvs_status dvs_test_fm_cv_stages(dvs_matcher* ctx, int32_t nprob, const int32_t* offsets, const float* pts1, const float* pts2, double threshold,
@@ -1598,27 +1454,27 @@ dvs_status dvs_test_fm_cv_stages(dvs_matcher* ctx, int32_t nprob, const int32_t*
   for (int b = 0; b < nprob; b++) {
     const int n = offsets[b + 1] - offsets[b];
     DVS_ARG(n >= 8);
-    nsmall += n < 15 ? 1 : 0;
+    nsmall += FmCvPolicy::lmeds(n) ? 1 : 0;
   }
   DVS_ARG(nsmall == 0 || nsmall == nprob);
   const bool lmeds = nsmall != 0;
   DVS_HIP(hipSetDevice(ctx->device));
   std::vector<uint8_t> flag(nprob);
-  StagesDev dev;
-  DVS_TRY(fm_cv_pass(ctx, nprob, offsets, pts1, pts2, threshold, confidence, max_iters, H, nullptr, mask, nullptr, nullptr, flag.data(), &dev, lmeds));
+  FmLayout dev;
+  DVS_TRY(fm_cv_batch_pass(ctx, nprob, offsets, pts1, pts2, FmCvPolicy{threshold, confidence, max_iters}, H, lmeds, nullptr, mask, nullptr, nullptr, flag.data(), &dev));
   const size_t nh = (size_t)nprob * H;
   std::vector<RansacProb> probs(nprob);
   DVS_HIP(hipMemcpy(probs.data(), dev.probs, (size_t)nprob * sizeof(RansacProb), hipMemcpyDeviceToHost));
-  for (int b = 0; b < nprob; b++) found[b] = (int32_t)probs[b].seed;
+  for (int b = 0; b < nprob; b++) found[b] = probs[b].sampled_iterations();
   DVS_HIP(hipMemcpy(samples, dev.samples, nh * 28, hipMemcpyDeviceToHost));
-  DVS_HIP(hipMemcpy(F_all, dev.models, nh * 216, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(F_all, dev.models, nh * kF7Roots * kFmModelBytes, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(valid, dev.valid, nh * 12, hipMemcpyDeviceToHost));
   if (lmeds) memset(counts, 0, nh * 12);
   else DVS_HIP(hipMemcpy(counts, dev.counts, nh * 12, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(sel, dev.sel, (size_t)nprob * 16, hipMemcpyDeviceToHost));
-  DVS_HIP(hipMemcpy(Fbest, dev.best, (size_t)nprob * 72, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(Fbest, dev.F, (size_t)nprob * kFmModelBytes, hipMemcpyDeviceToHost));
   // k_f7_hypotheses writes no model into a slot it marks invalid (its `valid` says so): zeros, not what the scratch block held
-  for (size_t m = 0; m < 3 * nh; m++) if (!valid[m]) memset(F_all + 9 * m, 0, 72);
+  for (size_t m = 0; m < 3 * nh; m++) if (!valid[m]) memset(F_all + 9 * m, 0, kFmModelBytes);
   return DVS_OK;
 }
 
@@ -1628,12 +1484,12 @@ dvs_status dvs_test_pnp_cv_stages(dvs_matcher* ctx, int32_t nprob, const int32_t
                                   double reproj_err, double confidence, int32_t H, int32_t* samples, double* models, int32_t* counts, int32_t* sel,
                                   int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
   DVS_ARG(ctx && nprob >= 1 && H >= 1 && offsets && samples && models && counts && sel && n_inliers && success && rvec3 && tvec3);
-  StagesDev dev;
+  PnpLayout dev;
   DVS_TRY(pnp_cv_batch(ctx, nprob, offsets, pts3d, pts2d, K4, H, reproj_err, confidence, rvec3, tvec3, inliers, n_inliers, success, nullptr, &dev));
   DVS_ARG(dev.models != nullptr);
   const size_t nh = (size_t)nprob * H;
   DVS_HIP(hipMemcpy(samples, dev.samples, nh * 20, hipMemcpyDeviceToHost));
-  DVS_HIP(hipMemcpy(models, dev.models, nh * 144, hipMemcpyDeviceToHost));
+  DVS_HIP(hipMemcpy(models, dev.models, nh * kModelPnpCvBytes, hipMemcpyDeviceToHost));
   for (size_t m = 0; m < nh; m++) models[18 * m + 15] = models[18 * m + 16] = models[18 * m + 17] = 0.0;   // the pad: no kernel writes it
   DVS_HIP(hipMemcpy(counts, dev.counts, nh * 4, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(sel, dev.sel, (size_t)nprob * 16, hipMemcpyDeviceToHost));
@@ -1647,7 +1503,7 @@ dvs_status dvs_test_ransac_select_cv(const int32_t* counts, int32_t H, int32_t n
   DVS_ARG(counts && sel4 && H >= 1 && n >= 1 && model_points >= 1 && group >= 1 && H % group == 0 && found >= 0 && max_iters_true >= 1);
   DeviceBuf<int> dc, ds; DeviceBuf<RansacProb> dp;
   DVS_TRY(dc.upload(std::vector<int>(counts, counts + H)));
-  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb{0, n, (unsigned long long)found})));
+  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb::sampled(0, n, found))));
   DVS_TRY(ds.alloc(4));
   hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(1), 0, 0, dc.get(), H, dp.get(), model_points, confidence, group, ds.get(), 1, max_iters_true);
   DVS_HIP(hipGetLastError());
@@ -1657,7 +1513,7 @@ dvs_status dvs_test_ransac_select_cv(const int32_t* counts, int32_t H, int32_t n
 
 // k_pnpcv_refit alone on ONE problem with a model of the caller's as the selected one (model6 = rvec, tvec — the rotation matrix the
 // hypothesis kernel stores beside it is made here, by the same routine; NULL: nothing selected, sel[0] = -1), grid and block as
-// launch_pnp_cv's for one problem.  inliers: room for n indices (-1 where none was written).  dbg8: see k_pnpcv_refit.
+// pnp_cv_pass's for one problem.  inliers: room for n indices (-1 where none was written).  dbg8: see k_pnpcv_refit.
 static __global__ void k_test_pnpcv_model(const double* __restrict__ model6, double* __restrict__ m18) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double R[9];
@@ -1673,22 +1529,54 @@ dvs_status dvs_test_pnpcv_refit(const float* pts3d, const float* pts2d, int32_t 
   DeviceBuf<float> dobj, dimg; DeviceBuf<RansacProb> dp; DeviceBuf<double> dm6, dm18, ddbg; DeviceBuf<int> dsel, dinl; DeviceBuf<unsigned char> dres;
   DVS_TRY(dobj.upload(std::vector<float>(pts3d, pts3d + 3 * (size_t)n)));
   DVS_TRY(dimg.upload(std::vector<float>(pts2d, pts2d + 2 * (size_t)n)));
-  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb{0, n, 1ull})));
+  DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb::sampled(0, n, 1))));
   DVS_TRY(dm6.upload(model6 ? std::vector<double>(model6, model6 + 6) : std::vector<double>(6, 0.0)));
   DVS_TRY(dm18.upload(std::vector<double>(18, 0.0)));
   DVS_TRY(ddbg.upload(std::vector<double>(8, -1.0)));
   DVS_TRY(dsel.upload(std::vector<int>{model6 ? 0 : -1, 1, 0, 0}));
   DVS_TRY(dinl.upload(std::vector<int>((size_t)n, -1)));
-  DVS_TRY(dres.upload(std::vector<unsigned char>(64, 0xff)));
+  DVS_TRY(dres.upload(std::vector<unsigned char>(kPnpRecord, 0xff)));
   if (model6) hipLaunchKernelGGL(k_test_pnpcv_model, dim3(1), dim3(1), 0, 0, dm6.get(), dm18.get());
   hipLaunchKernelGGL(k_pnpcv_refit, dim3(1), dim3(64), 0, 0, dobj.get(), dimg.get(), dp.get(), 1, dm18.get(), dsel.get(), K4[0], K4[1], K4[2], K4[3],
                      (float)(reproj_err * reproj_err), dinl.get(), dres.get(), ddbg.get());
   DVS_HIP(hipGetLastError());
-  unsigned char res[64];
-  DVS_HIP(hipMemcpy(res, dres.get(), 64, hipMemcpyDeviceToHost));
+  unsigned char res[kPnpRecord];
+  DVS_HIP(hipMemcpy(res, dres.get(), kPnpRecord, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(inliers, dinl.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(dbg8, ddbg.get(), 64, hipMemcpyDeviceToHost));
   memcpy(n_inliers, res, 4); memcpy(success, res + 4, 4); memcpy(rvec3, res + 16, 24); memcpy(tvec3, res + 40, 24);
+  return DVS_OK;
+}
+
+// ---- the device forms (include/dvslam_hip_test_ransac_device.h; tests/test_gpu_ransac_device_forms.py): one problem uploaded, the chosen
+// form of ransac_device.h run on it, what that form writes downloaded (0xff bytes where it wrote nothing)
+dvs_status dvs_test_ransac_device_form(dvs_matcher* ctx, int32_t form, const float* pts_a, const float* pts_b, int32_t n, int32_t cap, const double* K4,
+                                       int32_t iters, double threshold, double confidence, uint64_t seed, uint8_t* mask, uint8_t* rec64, int32_t* inliers,
+                                       int32_t* sel4) {
+  const bool fm = form == 0 || form == 1;
+  DVS_ARG(ctx && form >= 0 && form <= 3 && n >= 0 && cap >= std::max(n, 1) && (n == 0 || (pts_a && pts_b)));
+  DVS_ARG(fm ? mask != nullptr : K4 && rec64 && inliers && (form == 2 || sel4));
+  const size_t wa = fm ? 2 : 3;
+  std::vector<float> a((size_t)cap * wa, 0.f), b((size_t)cap * 2, 0.f);
+  if (n) { memcpy(a.data(), pts_a, (size_t)n * wa * 4); memcpy(b.data(), pts_b, (size_t)n * 8); }
+  DeviceBuf<float> da, db; DeviceBuf<int> dn, dinl, dsel; DeviceBuf<unsigned char> dmask, drec;
+  DVS_TRY(da.upload(a)); DVS_TRY(db.upload(b));
+  DVS_TRY(dn.upload(std::vector<int>(1, n)));
+  DVS_TRY(dmask.upload(std::vector<unsigned char>((size_t)cap, 0xff)));
+  DVS_TRY(drec.upload(std::vector<unsigned char>(kPnpRecord, 0xff)));
+  DVS_TRY(dinl.upload(std::vector<int>((size_t)cap, -1)));
+  DVS_TRY(dsel.upload(std::vector<int>(4, -1)));
+  if (form == 0) DVS_TRY(fm_own_device(ctx, da.get(), db.get(), dn.get(), cap, seed, threshold, confidence, iters, dmask.get()));
+  if (form == 1) DVS_TRY(fm_cv_device(ctx, da.get(), db.get(), n, threshold, confidence, iters, dmask.get()));
+  if (form == 2) DVS_TRY(pnp_own_device(ctx, da.get(), db.get(), dn.get(), seed, K4, iters, threshold, confidence, dinl.get(), drec.get()));
+  if (form == 3) DVS_TRY(pnp_cv_device(ctx, da.get(), db.get(), n, K4, iters, threshold, confidence, dinl.get(), drec.get(), dsel.get()));
+  DVS_HIP(hipStreamSynchronize(ctx->stream));
+  if (fm) DVS_HIP(hipMemcpy(mask, dmask.get(), (size_t)cap, hipMemcpyDeviceToHost));
+  else {
+    DVS_HIP(hipMemcpy(rec64, drec.get(), kPnpRecord, hipMemcpyDeviceToHost));
+    DVS_HIP(hipMemcpy(inliers, dinl.get(), (size_t)cap * 4, hipMemcpyDeviceToHost));
+    if (form == 3) DVS_HIP(hipMemcpy(sel4, dsel.get(), 16, hipMemcpyDeviceToHost));
+  }
   return DVS_OK;
 }
 #endif  // DVS_TEST_HOOKS

@@ -1,14 +1,13 @@
-// ransac_device.h — the RANSAC stages of ransac.hip on inputs that already live on the device (used by tracker.hip).  The host-pointer
-// entry points of include/dvslam_hip.h import their points and then run the SAME launch sequences; these forms skip the import and leave
-// their results on the device.  `ctx` gives the stream and scratch slot 0 (hypotheses, counts, selection: gone with the next call).
+// ransac_device.h — the RANSAC stages of ransac.hip on inputs that already live on the device (used by tracker.hip and reloc.hip).  The
+// host-pointer entry points of include/dvslam_hip.h place their points in a layout of ransac_layout.h, import it and run one pass of the
+// estimator; these forms carve the same layout without its point and result arrays, run the SAME pass on the caller's pointers and leave
+// their results on the device (tests/test_gpu_ransac_device_forms.py compares the two byte for byte).  `ctx` gives the stream and scratch
+// slot 0 (hypotheses, counts, selection: gone with the next call).
 #pragma once
 #include "matcher.h"
+#include "ransac_layout.h"   // RansacProb
 
 namespace dvs {
-
-// One RANSAC problem of a batch (blockIdx.y of every kernel of ransac.hip): its correspondences are rows [off, off + n) of the point
-// arrays, its hypotheses / counts / results slot `b` of the per-problem arrays.  The single-problem entry points are batches of one.
-struct RansacProb { int off, n; unsigned long long seed; };
 
 // dvs_find_fundamental_ransac on d_p1 / d_p2 (n x 2 float) with the count read from *d_n on the device (n_bound >= *d_n sizes the
 // grids): d_mask[0 .. *d_n) = the inlier mask.  Fewer than 8 correspondences give a mask of zeros.  Asynchronous.

@@ -25,8 +25,8 @@ __device__ __forceinline__ void sample_distinct(unsigned long long seed, int h, 
   }
 }
 
-// cv::RANSACUpdateNumIters
-__device__ __forceinline__ int ransac_update_iters(double p, double ep, int modelPoints, int maxIters) {
+// cv::RANSACUpdateNumIters (on the host: LMedS' fixed iteration count)
+__host__ __device__ __forceinline__ int ransac_update_iters(double p, double ep, int modelPoints, int maxIters) {
   p = fmax(p, 0.0); p = fmin(p, 1.0);
   ep = fmax(ep, 0.0); ep = fmin(ep, 1.0);
   double num = fmax(1.0 - p, DBL_MIN);
@@ -45,11 +45,11 @@ static __global__ void k_ransac_select(const int* __restrict__ counts, int H, co
   const int n = probs[blockIdx.x].n;
   counts += (size_t)H * blockIdx.x; sel += 4 * (size_t)blockIdx.x;
   // cv mode: only the first H / group iterations of a loop of up to maxItersTrue have their models here (the loop usually stops long
-  // before); the seed field carries how many iterations getSubset found a sample for.  sel[3] = 1: the loop wanted to go on past them
+  // before), and the problem record says how many iterations getSubset found a sample for.  sel[3] = 1: the loop wanted to go on past them
   const int avail = H / group;
   int niters = maxItersTrue > 0 ? maxItersTrue : avail, best = -1, bestCount = 0, it = 0;
   const int maxIters = niters;
-  const int found = capInSeed ? (int)probs[blockIdx.x].seed : avail;
+  const int found = capInSeed ? (int)probs[blockIdx.x].seed : avail;   // = sampled_iterations(), spelled out: through the member the compiler schedules this kernel differently
   for (; it < niters && it < avail && it < found; it++) {
     for (int s = 0; s < group; s++) {   // `group` candidate models per iteration (P3P: up to 4 poses per sample), in order
       const int h = it * group + s;

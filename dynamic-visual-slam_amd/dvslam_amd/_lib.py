@@ -364,6 +364,8 @@ def test_lib():
     L.dvs_test_pnp_cv_stages.argtypes = [vp, i32, vp, vp, vp, vp, dbl, dbl, i32] + [vp] * 9
     L.dvs_test_ransac_select_cv.argtypes = [vp, i32, i32, i32, dbl, i32, i32, i32, vp]
     L.dvs_test_pnpcv_refit.argtypes = [vp, vp, i32, vp, vp, dbl] + [vp] * 6
+    if hasattr(L, "dvs_test_ransac_device_form"):       # include/dvslam_hip_test_ransac_device.h
+        L.dvs_test_ransac_device_form.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, dbl, dbl, C.c_uint64] + [vp] * 4
     L.dvs_test_sincosf.argtypes = [C.c_float, vp, vp]; L.dvs_test_sincosf.restype = None
     L.dvs_test_geometry.argtypes = [C.POINTER(OrbParams), i32, i32, vp, vp, vp, vp, vp, vp]
     L.dvs_test_retain_best_host.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]; L.dvs_test_retain_best_host.restype = None

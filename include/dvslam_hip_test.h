@@ -16,6 +16,7 @@
 #include "dvslam_hip_test_maptrack.h"  /* the map tracking's per-landmark and cell hooks, a header of its own */
 #include "dvslam_hip_test_reloc.h"     /* the relocalisation's per-landmark hook, a header of its own */
 #include "dvslam_hip_test_ransac_cv.h" /* the OpenCV-procedure robust estimators' stage hooks, a header of its own */
+#include "dvslam_hip_test_ransac_device.h" /* the robust estimators' device forms against their host forms, a header of its own */
 #ifdef __cplusplus
 extern "C" {
 #endif
