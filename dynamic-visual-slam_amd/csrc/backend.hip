@@ -319,47 +319,18 @@ using namespace dvs;
 
 namespace {
 
-const int kSmall = 256;   // s_small: [0, 64) filtered ids, [64, 128) class list, [128, 192) class counts, [192, 196) counts, [196] marked landmarks, [200, 208) loop_close.hip, [208] covisibility.hip
-
 dvs_status backend_grow_tables(dvs_backend* h, size_t need_lm, size_t need_ob, size_t need_kf) {
   hipStream_t st = h->ctx->stream;
-  if (need_lm > h->lm.cap) {
-    size_t c = std::max<size_t>(h->lm.cap, 1);
-    while (c < need_lm) c *= 2;
-    LmTable t;
-    DVS_TRY(t.alloc(c));
-    const size_t n = (size_t)h->nlm;
-    if (n) {
-      DVS_HIP(hipMemcpyAsync(t.id.get(), h->lm.id.get(), n * 8, hipMemcpyDeviceToDevice, st)); DVS_HIP(hipMemcpyAsync(t.seen.get(), h->lm.seen.get(), n * 8, hipMemcpyDeviceToDevice, st));
-      DVS_HIP(hipMemcpyAsync(t.cls.get(), h->lm.cls.get(), n * 4, hipMemcpyDeviceToDevice, st)); DVS_HIP(hipMemcpyAsync(t.cnt.get(), h->lm.cnt.get(), n * 4, hipMemcpyDeviceToDevice, st));
-      DVS_HIP(hipMemcpyAsync(t.xyz.get(), h->lm.xyz.get(), n * 12, hipMemcpyDeviceToDevice, st)); DVS_HIP(hipMemcpyAsync(t.desc.get(), h->lm.desc.get(), n * 32, hipMemcpyDeviceToDevice, st));
-    }
-    DVS_HIP(hipStreamSynchronize(st));   // the old blocks are freed by the assignment
-    h->lm = std::move(t);
-  }
-  if (need_ob > h->ob.cap) {
-    size_t c = std::max<size_t>(h->ob.cap, 1);
-    while (c < need_ob) c *= 2;
-    ObTable t;
-    DVS_TRY(t.alloc(c));
-    const size_t n = (size_t)h->nob;
-    if (n) {
-      DVS_HIP(hipMemcpyAsync(t.id.get(), h->ob.id.get(), n * 8, hipMemcpyDeviceToDevice, st)); DVS_HIP(hipMemcpyAsync(t.frame.get(), h->ob.frame.get(), n * 8, hipMemcpyDeviceToDevice, st));
-      DVS_HIP(hipMemcpyAsync(t.lm.get(), h->ob.lm.get(), n * 8, hipMemcpyDeviceToDevice, st)); DVS_HIP(hipMemcpyAsync(t.kf.get(), h->ob.kf.get(), n * 4, hipMemcpyDeviceToDevice, st));
-      DVS_HIP(hipMemcpyAsync(t.cls.get(), h->ob.cls.get(), n * 4, hipMemcpyDeviceToDevice, st)); DVS_HIP(hipMemcpyAsync(t.px.get(), h->ob.px.get(), n * 8, hipMemcpyDeviceToDevice, st));
-      DVS_HIP(hipMemcpyAsync(t.desc.get(), h->ob.desc.get(), n * 32, hipMemcpyDeviceToDevice, st));
-    }
-    DVS_HIP(hipStreamSynchronize(st));
-    h->ob = std::move(t);
-  }
+  DVS_TRY(table_regrow(h->lm, need_lm, (size_t)h->nlm, st));
+  DVS_TRY(table_regrow(h->ob, need_ob, (size_t)h->nob, st));
   if (need_kf > h->cap_kf) {
     size_t c = std::max<size_t>(h->cap_kf, 1);
     while (c < need_kf) c *= 2;
-    DeviceBuf<double> r, t;
-    DVS_TRY(r.alloc(c * 9)); DVS_TRY(t.alloc(c * 3));
+    Column<double, 9> r; Column<double, 3> t;
+    DVS_TRY(alloc_rows(c, r, t));
     const size_t n = h->kfs.size();
     if (n) {
-      DVS_HIP(hipMemcpyAsync(r.get(), h->kf_R.get(), n * 72, hipMemcpyDeviceToDevice, st)); DVS_HIP(hipMemcpyAsync(t.get(), h->kf_t.get(), n * 24, hipMemcpyDeviceToDevice, st));
+      DVS_HIP(hipMemcpyAsync(r.get(), h->kf_R.get(), n * r.row_bytes, hipMemcpyDeviceToDevice, st)); DVS_HIP(hipMemcpyAsync(t.get(), h->kf_t.get(), n * t.row_bytes, hipMemcpyDeviceToDevice, st));
     }
     DVS_HIP(hipStreamSynchronize(st));
     h->kf_R = std::move(r); h->kf_t = std::move(t); h->cap_kf = c;
@@ -376,36 +347,22 @@ void quat_to_R(const double* q_xyzw, double* R) {   // extractPoseFromTransform 
   R[6] = 2 * (qx * qz - qw * qy); R[7] = 2 * (qy * qz + qw * qx); R[8] = 1 - 2 * (qx * qx + qy * qy);
 }
 
-template <class T>
-dvs_status grow_to(DeviceBuf<T>& b, size_t& cap, size_t need) { return grow(b, cap, need); }
-
 }  // namespace
 
-// landmark -> views CSR over the whole table into view_offs / view_kf / view_px / view_oid (nothing to do for an empty landmark table)
+// landmark -> views CSR over the whole table into v_lm.offs and v_ob.kf / .px / .oid (nothing to do for an empty landmark table)
 dvs_status dvs::backend_views_build(dvs_backend* h) {
   hipStream_t st = h->ctx->stream;
   const int nlm = h->nlm, nob = h->nob;
   if (nlm == 0) return DVS_OK;
-  if ((size_t)nlm + 1 > h->c_vlm) {
-    const size_t c = (size_t)nlm + 1 + (size_t)nlm / 2;
-    h->c_vlm = 0;
-    DVS_TRY(h->v_cnt.alloc(c)); DVS_TRY(h->v_fill.alloc(c)); DVS_TRY(h->view_offs.alloc(c)); DVS_TRY(h->tri_xyz.alloc(c * 3)); DVS_TRY(h->tri_status.alloc(c));
-    h->c_vlm = c;
-  }
-  if ((size_t)nob > h->c_vob) {
-    const size_t c = (size_t)nob + (size_t)nob / 2 + 64;
-    h->c_vob = 0;
-    DVS_TRY(h->ob_slot.alloc(c)); DVS_TRY(h->v_obs.alloc(c)); DVS_TRY(h->view_kf.alloc(c)); DVS_TRY(h->view_px.alloc(c * 2)); DVS_TRY(h->view_oid.alloc(c));
-    h->c_vob = c;
-  }
-  DVS_HIP(hipMemsetAsync(h->v_cnt.get(), 0, (size_t)nlm * 4, st));
-  DVS_HIP(hipMemsetAsync(h->v_fill.get(), 0, (size_t)nlm * 4, st));
+  DVS_TRY(h->v_lm.grow((size_t)nlm)); DVS_TRY(h->v_ob.grow((size_t)nob));
+  DVS_HIP(hipMemsetAsync(h->v_lm.cnt.get(), 0, (size_t)nlm * 4, st));
+  DVS_HIP(hipMemsetAsync(h->v_lm.fill.get(), 0, (size_t)nlm * 4, st));
   const ObView ob = h->ob.view();
-  if (nob) hipLaunchKernelGGL(k_views_count, dim3((nob + 255) / 256), dim3(256), 0, st, ob, nob, (const i64*)h->lm.id.get(), nlm, h->ob_slot.get(), h->v_cnt.get());
-  launch_scan_counts(st, (const int*)h->v_cnt.get(), nlm, h->view_offs.get());
-  if (nob) hipLaunchKernelGGL(k_views_scatter, dim3((nob + 255) / 256), dim3(256), 0, st, (const int*)h->ob_slot.get(), nob, (const i64*)h->view_offs.get(), h->v_fill.get(), h->v_obs.get());
-  hipLaunchKernelGGL(k_views_finish, dim3((nlm + 255) / 256), dim3(256), 0, st, ob, (int)h->kfs.size(), nlm, (const i64*)h->view_offs.get(), h->v_obs.get(), h->view_kf.get(),
-                     h->view_px.get(), h->view_oid.get());
+  if (nob) hipLaunchKernelGGL(k_views_count, dim3((nob + 255) / 256), dim3(256), 0, st, ob, nob, (const i64*)h->lm.id.get(), nlm, h->v_ob.slot.get(), h->v_lm.cnt.get());
+  launch_scan_counts(st, (const int*)h->v_lm.cnt.get(), nlm, h->v_lm.offs.get());
+  if (nob) hipLaunchKernelGGL(k_views_scatter, dim3((nob + 255) / 256), dim3(256), 0, st, (const int*)h->v_ob.slot.get(), nob, (const i64*)h->v_lm.offs.get(), h->v_lm.fill.get(), h->v_ob.rows.get());
+  hipLaunchKernelGGL(k_views_finish, dim3((nlm + 255) / 256), dim3(256), 0, st, ob, (int)h->kfs.size(), nlm, (const i64*)h->v_lm.offs.get(), h->v_ob.rows.get(), h->v_ob.kf.get(),
+                     h->v_ob.px.get(), h->v_ob.oid.get());
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
@@ -434,7 +391,7 @@ dvs_status dvs_backend_create(const dvs_backend_params* params, int32_t device, 
   dvs_status s = dvs_matcher_create(device, &h->ctx);
   auto alloc_all = [&]() -> dvs_status {
     DVS_TRY(backend_grow_tables(h, (size_t)P.initial_capacity, (size_t)P.initial_capacity, 16));
-    DVS_TRY(h->s_small.alloc(kSmall)); DVS_TRY(h->d_Rt.alloc(12));
+    DVS_TRY(h->s_small.alloc(1)); DVS_TRY(h->d_Rt.alloc(12));
     return DVS_OK;
   };
   if (s == DVS_OK) s = alloc_all();
@@ -498,43 +455,35 @@ dvs_status dvs_backend_add_keyframe(dvs_backend* h, const dvs_keyframe_header* h
   std::map<int, Hit> hits;                            // landmark row -> matches in this keyframe
   if (n > 0) {
     // ---- :735-751: pixels as cv::Point2f, positions as cv::Point3f, categories
-    if ((size_t)n > h->c_n) {
-      const size_t c = (size_t)n + (size_t)n / 4;
-      h->c_n = 0;
-      DVS_TRY(h->s_px.alloc(c * 2)); DVS_TRY(h->s_xyz.alloc(c * 3)); DVS_TRY(h->s_desc.alloc(c * 32)); DVS_TRY(h->q_px.alloc(c * 2)); DVS_TRY(h->q_desc.alloc(c * 32));
-      DVS_TRY(h->s_code.alloc(c)); DVS_TRY(h->s_order.alloc(c)); DVS_TRY(h->d_best.alloc(c));
-      h->c_n = c;
-    }
-    DVS_TRY(grow_to(h->s_det, h->c_det, (size_t)ndet));
+    DVS_TRY(h->kf_ob.grow((size_t)n));
+    DVS_TRY(grow(h->s_det, h->c_det, (size_t)ndet));
     h->h_px.resize((size_t)n * 2); h->h_xyz.resize((size_t)n * 3); h->h_det.resize((size_t)ndet);
     for (size_t k = 0; k < (size_t)n * 2; k++) h->h_px[k] = (float)obs_pixels[k];
     for (size_t k = 0; k < (size_t)n * 3; k++) h->h_xyz[k] = (float)landmark_xyz[k];
     for (int d = 0; d < ndet; d++) h->h_det[d] = DetRec{detections[d].cx, detections[d].cy, detections[d].w, detections[d].h, detections[d].class_id, 0};
-    h->h_int.assign(kSmall, 0);
-    for (int k = 0; k < P.n_filtered; k++) h->h_int[k] = P.filtered_class_ids[k];
-    for (size_t k = 0; k < classes.size(); k++) h->h_int[64 + k] = classes[k];
-    DVS_HIP(hipMemcpyAsync(h->s_px.get(), h->h_px.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    DVS_HIP(hipMemcpyAsync(h->s_xyz.get(), h->h_xyz.data(), (size_t)n * 12, hipMemcpyHostToDevice, st));
-    DVS_HIP(hipMemcpyAsync(h->s_desc.get(), obs_desc, (size_t)n * 32, hipMemcpyHostToDevice, st));
+    h->h_small = BackendSmall();
+    for (int k = 0; k < P.n_filtered; k++) h->h_small.filtered[k] = P.filtered_class_ids[k];
+    for (size_t k = 0; k < classes.size(); k++) h->h_small.classes[k] = classes[k];
+    DVS_TRY(copy_in(h->kf_ob.s_px, h->h_px.data(), (size_t)n, st)); DVS_TRY(copy_in(h->kf_ob.s_xyz, h->h_xyz.data(), (size_t)n, st)); DVS_TRY(copy_in(h->kf_ob.s_desc, obs_desc, (size_t)n, st));
     if (ndet) DVS_HIP(hipMemcpyAsync(h->s_det.get(), h->h_det.data(), (size_t)ndet * sizeof(DetRec), hipMemcpyHostToDevice, st));
-    DVS_HIP(hipMemcpyAsync(h->s_small.get(), h->h_int.data(), kSmall * 4, hipMemcpyHostToDevice, st));
+    DVS_HIP(hipMemcpyAsync(h->s_small.get(), &h->h_small, sizeof(BackendSmall), hipMemcpyHostToDevice, st));
     double Rt[12];
     memcpy(Rt, K.R, 72); memcpy(Rt + 9, K.t, 24);
     DVS_HIP(hipMemcpyAsync(h->d_Rt.get(), Rt, 96, hipMemcpyHostToDevice, st));
-    int* sm = h->s_small.get();
-    hipLaunchKernelGGL(k_categorize, dim3(1), dim3(256), 0, st, (const float*)h->s_px.get(), (const uint8_t*)h->s_desc.get(), n, (const DetRec*)h->s_det.get(), ndet,
-                       (const int*)sm, P.n_filtered, (const int*)(sm + 64), (int)classes.size(), h->s_code.get(), h->s_order.get(), h->q_px.get(), h->q_desc.get(), sm + 128);
+    BackendSmall* sm = h->s_small.get();
+    hipLaunchKernelGGL(k_categorize, dim3(1), dim3(256), 0, st, (const float*)h->kf_ob.s_px.get(), (const uint8_t*)h->kf_ob.s_desc.get(), n, (const DetRec*)h->s_det.get(), ndet,
+                       (const int*)sm->filtered, P.n_filtered, (const int*)sm->classes, (int)classes.size(), h->kf_ob.s_code.get(), h->kf_ob.s_order.get(), h->kf_ob.q_px.get(), h->kf_ob.q_desc.get(),
+                       sm->class_cnt);
     DVS_HIP(hipGetLastError());
     // ---- :772 for every landmark at once, from the views stored before this keyframe
     if (nlm > 0) {
       DVS_TRY(backend_views_build(h));
-      DVS_TRY(dvs_triangulate_landmarks_device(h->ctx, kf, h->kf_R.get(), h->kf_t.get(), P.fx, P.fy, P.cx, P.cy, nlm, (const int64_t*)h->view_offs.get(), h->view_kf.get(),
-                                               h->view_px.get(), h->lm.xyz.get(), h->tri_xyz.get(), h->tri_status.get()));
+      DVS_TRY(dvs_triangulate_landmarks_device(h->ctx, kf, h->kf_R.get(), h->kf_t.get(), P.fx, P.fy, P.cx, P.cy, nlm, (const int64_t*)h->v_lm.offs.get(), h->v_ob.kf.get(),
+                                               h->v_ob.px.get(), h->lm.xyz.get(), h->v_lm.tri_xyz.get(), h->v_lm.tri_status.get()));
     }
     int class_cnt[64] = {0};
-    DVS_HIP(hipMemcpyAsync(code.data(), h->s_code.get(), (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(class_cnt, sm + 128, sizeof(class_cnt), hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipStreamSynchronize(st));
+    DVS_TRY(copy_out(code.data(), h->kf_ob.s_code, (size_t)n, st));
+    DVS_TRY(small_read(h, sm->class_cnt, class_cnt, 64));
     // ---- :758 per class present: gather, associate, walk
     std::vector<std::vector<int>> by_class(classes.size());
     for (int i = 0; i < n; i++) {
@@ -550,30 +499,24 @@ dvs_status dvs_backend_add_keyframe(dvs_backend* h, const dvs_keyframe_header* h
       const std::vector<int>& mine = by_class[k];
       const int no = (int)mine.size();
       if (no == 0 || nlm == 0) continue;
-      if ((size_t)nlm > h->c_glm) {
-        const size_t c = (size_t)nlm + (size_t)nlm / 2;
-        h->c_glm = 0;
-        DVS_TRY(h->g_slot.alloc(c)); DVS_TRY(h->g_desc.alloc(c * 32)); DVS_TRY(h->g_xyz.alloc(c * 3));
-        h->c_glm = c;
-      }
-      hipLaunchKernelGGL(k_class_gather, dim3(1), dim3(256), 0, st, h->lm.view(), nlm, classes[k], h->g_slot.get(), h->g_desc.get(), h->g_xyz.get(), sm + 192);
+      DVS_TRY(h->cls_lm.grow((size_t)nlm));
+      hipLaunchKernelGGL(k_class_gather, dim3(1), dim3(256), 0, st, h->lm.view(), nlm, classes[k], h->cls_lm.slot.get(), h->cls_lm.desc.get(), h->cls_lm.xyz.get(), sm->counts);
       DVS_HIP(hipGetLastError());
       int nl = 0;
-      DVS_HIP(hipMemcpyAsync(&nl, sm + 192, 4, hipMemcpyDeviceToHost, st));
-      DVS_HIP(hipStreamSynchronize(st));
+      DVS_TRY(small_read(h, sm->counts, &nl));
       if (nl <= 0) continue;                          // a class seen for the first time
       const long long* d_offs; const int* d_pairs; long long total = 0;
-      DVS_TRY(associate_rows_device(h->ctx, h->q_desc.get() + 32 * off, h->q_px.get() + 2 * off, no, h->g_desc.get(), h->g_xyz.get(), nl, h->d_Rt.get(), P.fx, P.fy, P.cx,
-                                    P.cy, P.max_descriptor_distance, P.max_reprojection_distance, h->d_best.get(), &d_offs, &d_pairs, &total));
+      DVS_TRY(associate_rows_device(h->ctx, h->kf_ob.q_desc.get() + 32 * off, h->kf_ob.q_px.get() + 2 * off, no, h->cls_lm.desc.get(), h->cls_lm.xyz.get(), nl, h->d_Rt.get(), P.fx, P.fy, P.cx,
+                                    P.cy, P.max_descriptor_distance, P.max_reprojection_distance, h->kf_ob.d_best.get(), &d_offs, &d_pairs, &total));
       if (total == 0) continue;
-      DVS_TRY(grow_to(h->p_rec, h->c_pair, (size_t)total));
-      hipLaunchKernelGGL(k_pair_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_pairs, (i64)total, (const int*)h->g_slot.get(), (const i64*)h->lm.id.get(),
-                         (const float*)h->lm.xyz.get(), (const float*)h->tri_xyz.get(), (const int*)h->tri_status.get(), h->p_rec.get());
+      DVS_TRY(grow(h->p_rec, h->c_pair, (size_t)total));
+      hipLaunchKernelGGL(k_pair_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_pairs, (i64)total, (const int*)h->cls_lm.slot.get(), (const i64*)h->lm.id.get(),
+                         (const float*)h->lm.xyz.get(), (const float*)h->v_lm.tri_xyz.get(), (const int*)h->v_lm.tri_status.get(), h->p_rec.get());
       DVS_HIP(hipGetLastError());
       std::vector<int> best((size_t)no);
       std::vector<i64> offs((size_t)no + 1);
       std::vector<PairRec> rec((size_t)total);
-      DVS_HIP(hipMemcpyAsync(best.data(), h->d_best.get(), (size_t)no * 4, hipMemcpyDeviceToHost, st));
+      DVS_TRY(copy_out(best.data(), h->kf_ob.d_best, (size_t)no, st));
       DVS_HIP(hipMemcpyAsync(offs.data(), d_offs, ((size_t)no + 1) * 8, hipMemcpyDeviceToHost, st));
       DVS_HIP(hipMemcpyAsync(rec.data(), h->p_rec.get(), (size_t)total * sizeof(PairRec), hipMemcpyDeviceToHost, st));
       DVS_HIP(hipStreamSynchronize(st));
@@ -626,19 +569,19 @@ dvs_status dvs_backend_add_keyframe(dvs_backend* h, const dvs_keyframe_header* h
   for (const auto& kv : hits) h->h_int.push_back(kv.first);
   for (const auto& kv : hits) h->h_int.push_back(kv.second.inc);
   for (const auto& kv : hits) { h->h_int.push_back(kv.second.moved); result->n_moved += kv.second.moved; }
-  DVS_TRY(grow_to(h->a_int, h->c_aint, h->h_int.size())); DVS_TRY(grow_to(h->a_i64, h->c_ai64, h->h_i64.size()));
+  DVS_TRY(grow(h->a_int, h->c_aint, h->h_int.size())); DVS_TRY(grow(h->a_i64, h->c_ai64, h->h_i64.size()));
   if (!h->h_int.empty()) DVS_HIP(hipMemcpyAsync(h->a_int.get(), h->h_int.data(), h->h_int.size() * 4, hipMemcpyHostToDevice, st));
   if (m) DVS_HIP(hipMemcpyAsync(h->a_i64.get(), h->h_i64.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
   const int* a = h->a_int.get();
-  if (mh) hipLaunchKernelGGL(k_match_apply, dim3((mh + 255) / 256), dim3(256), 0, st, mh, a + m + mn, a + m + mn + mh, a + m + mn + 2 * mh, stamp, (const float*)h->tri_xyz.get(),
+  if (mh) hipLaunchKernelGGL(k_match_apply, dim3((mh + 255) / 256), dim3(256), 0, st, mh, a + m + mn, a + m + mn + mh, a + m + mn + 2 * mh, stamp, (const float*)h->v_lm.tri_xyz.get(),
                              h->lm.view(), nlm);
   if (m) hipLaunchKernelGGL(k_append_obs, dim3((m + 255) / 256), dim3(256), 0, st, m, a, (const i64*)h->a_i64.get(), result->first_observation_id, (i64)K.frame_id, kf,
-                            (const float*)h->s_px.get(), (const uint8_t*)h->s_desc.get(), (const int*)h->s_code.get(), n, h->ob.view(), h->nob);
-  if (mn) hipLaunchKernelGGL(k_append_lm, dim3((mn + 255) / 256), dim3(256), 0, st, mn, a + m, result->first_landmark_id, stamp, (const float*)h->s_xyz.get(),
-                             (const uint8_t*)h->s_desc.get(), (const int*)h->s_code.get(), n, h->lm.view(), nlm);
+                            (const float*)h->kf_ob.s_px.get(), (const uint8_t*)h->kf_ob.s_desc.get(), (const int*)h->kf_ob.s_code.get(), n, h->ob.view(), h->nob);
+  if (mn) hipLaunchKernelGGL(k_append_lm, dim3((mn + 255) / 256), dim3(256), 0, st, mn, a + m, result->first_landmark_id, stamp, (const float*)h->kf_ob.s_xyz.get(),
+                             (const uint8_t*)h->kf_ob.s_desc.get(), (const int*)h->kf_ob.s_code.get(), n, h->lm.view(), nlm);
   DVS_HIP(hipGetLastError());
-  DVS_HIP(hipMemcpyAsync(h->kf_R.get() + 9 * (size_t)kf, K.R, 72, hipMemcpyHostToDevice, st));
-  DVS_HIP(hipMemcpyAsync(h->kf_t.get() + 3 * (size_t)kf, K.t, 24, hipMemcpyHostToDevice, st));
+  DVS_HIP(hipMemcpyAsync(h->kf_R.get() + 9 * (size_t)kf, K.R, h->kf_R.row_bytes, hipMemcpyHostToDevice, st));
+  DVS_HIP(hipMemcpyAsync(h->kf_t.get() + 3 * (size_t)kf, K.t, h->kf_t.row_bytes, hipMemcpyHostToDevice, st));
   DVS_HIP(hipStreamSynchronize(st));
   h->nob += m; h->nlm += mn;
   h->kf_index[K.frame_id] = kf;
@@ -671,26 +614,13 @@ dvs_status dvs_backend_get_window(dvs_backend* h, int32_t cap_kf, int32_t cap_ob
   const int nob = h->nob, nlm = h->nlm;
   int counts[2] = {0, 0};
   if (w > 0 && nob > 0) {
-    if ((size_t)nob > h->c_wob) {
-      const size_t c = (size_t)nob + (size_t)nob / 2;
-      h->c_wob = 0;
-      DVS_TRY(h->w_oi.alloc(c)); DVS_TRY(h->w_slot.alloc(c)); DVS_TRY(h->w_px.alloc(c * 2)); DVS_TRY(h->w_lm.alloc(c)); DVS_TRY(h->w_cls.alloc(c)); DVS_TRY(h->w_frame.alloc(c));
-      DVS_TRY(h->w_lmidx.alloc(c));
-      h->c_wob = c;
-    }
-    if ((size_t)nlm + 1 > h->c_wlm) {
-      const size_t c = (size_t)nlm + 1 + (size_t)nlm / 2;
-      h->c_wlm = 0;
-      DVS_TRY(h->w_lid.alloc(c)); DVS_TRY(h->w_lcls.alloc(c)); DVS_TRY(h->w_lxyz.alloc(c * 3)); DVS_TRY(h->w_flag.alloc(c)); DVS_TRY(h->w_pos.alloc(c));
-      h->c_wlm = c;
-    }
-    int* sm = h->s_small.get();
-    hipLaunchKernelGGL(k_window_gather, dim3(1), dim3(256), 0, st, h->ob.view(), nob, h->lm.view(), nlm, start, h->w_flag.get(), h->w_pos.get(), h->w_oi.get(),
-                       h->w_slot.get(), h->w_px.get(), h->w_lm.get(), h->w_cls.get(), h->w_frame.get(), h->w_lmidx.get(), h->w_lid.get(), h->w_lcls.get(), h->w_lxyz.get(),
-                       sm + 192);
+    DVS_TRY(h->win_ob.grow((size_t)nob)); DVS_TRY(h->win_lm.grow((size_t)nlm));
+    int* d_counts = h->s_small.get()->counts;
+    hipLaunchKernelGGL(k_window_gather, dim3(1), dim3(256), 0, st, h->ob.view(), nob, h->lm.view(), nlm, start, h->win_lm.flag.get(), h->win_lm.pos.get(), h->win_ob.oi.get(),
+                       h->win_ob.slot.get(), h->win_ob.o.px.get(), h->win_ob.o.lm.get(), h->win_ob.o.cls.get(), h->win_ob.o.frame.get(), h->win_ob.o.lmidx.get(), h->win_lm.l.id.get(), h->win_lm.l.cls.get(), h->win_lm.l.xyz.get(),
+                       d_counts);
     DVS_HIP(hipGetLastError());
-    DVS_HIP(hipMemcpyAsync(counts, sm + 192, 8, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipStreamSynchronize(st));
+    DVS_TRY(small_read(h, d_counts, counts, 2));
   }
   *n_obs = counts[0]; *n_lm = counts[1];
   if (w > cap_kf || counts[0] > cap_obs || counts[1] > cap_lm) {
@@ -703,19 +633,7 @@ dvs_status dvs_backend_get_window(dvs_backend* h, int32_t cap_kf, int32_t cap_ob
     if (kf_R) memcpy(kf_R + 9 * (size_t)k, K.R, 72);
     if (kf_t) memcpy(kf_t + 3 * (size_t)k, K.t, 24);
   }
-  const size_t no = (size_t)counts[0], nl = (size_t)counts[1];
-  if (no) {
-    if (obs_px) DVS_HIP(hipMemcpyAsync(obs_px, h->w_px.get(), no * 8, hipMemcpyDeviceToHost, st));
-    if (obs_lm_id) DVS_HIP(hipMemcpyAsync(obs_lm_id, h->w_lm.get(), no * 8, hipMemcpyDeviceToHost, st));
-    if (obs_class) DVS_HIP(hipMemcpyAsync(obs_class, h->w_cls.get(), no * 4, hipMemcpyDeviceToHost, st));
-    if (obs_frame_id) DVS_HIP(hipMemcpyAsync(obs_frame_id, h->w_frame.get(), no * 8, hipMemcpyDeviceToHost, st));
-    if (obs_lm_index) DVS_HIP(hipMemcpyAsync(obs_lm_index, h->w_lmidx.get(), no * 4, hipMemcpyDeviceToHost, st));
-  }
-  if (nl) {
-    if (lm_id) DVS_HIP(hipMemcpyAsync(lm_id, h->w_lid.get(), nl * 8, hipMemcpyDeviceToHost, st));
-    if (lm_class) DVS_HIP(hipMemcpyAsync(lm_class, h->w_lcls.get(), nl * 4, hipMemcpyDeviceToHost, st));
-    if (lm_xyz) DVS_HIP(hipMemcpyAsync(lm_xyz, h->w_lxyz.get(), nl * 12, hipMemcpyDeviceToHost, st));
-  }
+  DVS_TRY(window_copy_out(h->win_ob.o, (size_t)counts[0], h->win_lm.l, (size_t)counts[1], obs_px, obs_lm_id, obs_class, obs_frame_id, obs_lm_index, lm_id, lm_class, lm_xyz, st));
   DVS_HIP(hipStreamSynchronize(st));
   return DVS_OK;
 }
@@ -741,7 +659,7 @@ dvs_status dvs_backend_apply_optimized(dvs_backend* h, int32_t nposes, const uin
     h->h_dbl.insert(h->h_dbl.end(), K.R, K.R + 9); h->h_dbl.insert(h->h_dbl.end(), K.t, K.t + 3);
     np++;
   }
-  DVS_TRY(grow_to(h->a_int, h->c_aint, h->h_int.size())); DVS_TRY(grow_to(h->a_i64, h->c_ai64, h->h_i64.size())); DVS_TRY(grow_to(h->a_dbl, h->c_adbl, h->h_dbl.size()));
+  DVS_TRY(grow(h->a_int, h->c_aint, h->h_int.size())); DVS_TRY(grow(h->a_i64, h->c_ai64, h->h_i64.size())); DVS_TRY(grow(h->a_dbl, h->c_adbl, h->h_dbl.size()));
   if (!h->h_int.empty()) DVS_HIP(hipMemcpyAsync(h->a_int.get(), h->h_int.data(), h->h_int.size() * 4, hipMemcpyHostToDevice, st));
   if (!h->h_i64.empty()) DVS_HIP(hipMemcpyAsync(h->a_i64.get(), h->h_i64.data(), h->h_i64.size() * 8, hipMemcpyHostToDevice, st));
   if (!h->h_dbl.empty()) DVS_HIP(hipMemcpyAsync(h->a_dbl.get(), h->h_dbl.data(), h->h_dbl.size() * 8, hipMemcpyHostToDevice, st));
@@ -761,33 +679,29 @@ dvs_status dvs_backend_prune(dvs_backend* h, int32_t now_sec, uint32_t now_nanos
   DVS_HIP(hipSetDevice(h->device));
   hipStream_t st = h->ctx->stream;
   const i64 now = (i64)now_sec * 1000000000ll + (i64)now_nanosec;
-  int* sm = h->s_small.get();
-  if ((size_t)nlm > h->c_pflag) { h->c_pflag = 0; DVS_TRY(h->p_flag.alloc((size_t)nlm + (size_t)nlm / 2)); h->c_pflag = (size_t)nlm + (size_t)nlm / 2; }
-  DVS_HIP(hipMemsetAsync(sm + 196, 0, 4, st));
-  hipLaunchKernelGGL(k_prune_mark, dim3((nlm + 255) / 256), dim3(256), 0, st, h->lm.view(), nlm, now, h->P.prune_min_observations, h->P.prune_max_age_sec, h->p_flag.get(), sm + 196);
+  BackendSmall* sm = h->s_small.get();
+  DVS_TRY(h->prune_lm.grow((size_t)nlm));
+  DVS_HIP(hipMemsetAsync(&sm->marked, 0, 4, st));
+  hipLaunchKernelGGL(k_prune_mark, dim3((nlm + 255) / 256), dim3(256), 0, st, h->lm.view(), nlm, now, h->P.prune_min_observations, h->P.prune_max_age_sec, h->prune_lm.flag.get(), &sm->marked);
   DVS_HIP(hipGetLastError());
   int marked = 0;
-  DVS_HIP(hipMemcpyAsync(&marked, sm + 196, 4, hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipStreamSynchronize(st));
+  DVS_TRY(small_read(h, &sm->marked, &marked));
   if (marked == 0) return DVS_OK;                    // the common BA cycle: nothing to compact
   // the tables are compacted into the handle's spare pair, which then changes places with them
-  if (h->lm_spare.cap != h->lm.cap) DVS_TRY(h->lm_spare.alloc(h->lm.cap));
-  if (h->ob_spare.cap != h->ob.cap) DVS_TRY(h->ob_spare.alloc(h->ob.cap));
-  if ((size_t)nob > h->c_rem) { h->c_rem = 0; DVS_TRY(h->rem_kf.alloc((size_t)nob + (size_t)nob / 2)); DVS_TRY(h->rem_id.alloc((size_t)nob + (size_t)nob / 2)); h->c_rem = (size_t)nob + (size_t)nob / 2; }
+  DVS_TRY(table_match_spare(h->lm_spare, h->lm)); DVS_TRY(table_match_spare(h->ob_spare, h->ob));
+  DVS_TRY(h->prune_ob.grow((size_t)nob));
   LmTable& nl = h->lm_spare; ObTable& no = h->ob_spare;
-  DeviceBuf<int>& rem_kf = h->rem_kf; DeviceBuf<i64>& rem_id = h->rem_id;
-  hipLaunchKernelGGL(k_prune_compact, dim3(1), dim3(256), 0, st, h->lm.view(), nlm, (const int*)h->p_flag.get(), nl.view(), h->ob.view(), nob, no.view(), rem_id.get(), rem_kf.get(),
-                     sm + 192);
+  const Column<int>& rem_kf = h->prune_ob.rem_kf; const Column<i64>& rem_id = h->prune_ob.rem_id;
+  hipLaunchKernelGGL(k_prune_compact, dim3(1), dim3(256), 0, st, h->lm.view(), nlm, (const int*)h->prune_lm.flag.get(), nl.view(), h->ob.view(), nob, no.view(), rem_id.get(), rem_kf.get(),
+                     sm->counts);
   DVS_HIP(hipGetLastError());
   int counts[3] = {0, 0, 0};
-  DVS_HIP(hipMemcpyAsync(counts, sm + 192, 12, hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipStreamSynchronize(st));
+  DVS_TRY(small_read(h, sm->counts, counts, 3));
   if (counts[0] < 0 || counts[0] > nlm || counts[1] + counts[2] != nob) { set_error("dvs_backend_prune: inconsistent counts %d %d %d", counts[0], counts[1], counts[2]); return DVS_ERR_HIP; }
   std::vector<i64> rid((size_t)counts[2]);
   std::vector<int> rkf((size_t)counts[2]);
   if (counts[2]) {
-    DVS_HIP(hipMemcpyAsync(rid.data(), rem_id.get(), rid.size() * 8, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(rkf.data(), rem_kf.get(), rkf.size() * 4, hipMemcpyDeviceToHost, st));
+    DVS_TRY(copy_out(rid.data(), rem_id, rid.size(), st)); DVS_TRY(copy_out(rkf.data(), rem_kf, rkf.size(), st));
     DVS_HIP(hipStreamSynchronize(st));
   }
   // :1303-1312 keyframes' observation_ids lose the removed ids
@@ -817,7 +731,7 @@ dvs_status dvs_backend_get_landmarks(dvs_backend* h, int32_t cap, int64_t cap_ob
   const bool want_csr = obs_offsets || obs_ids || n_obs_ids;
   if (want_csr && nlm) {
     DVS_TRY(backend_views_build(h));
-    DVS_HIP(hipMemcpyAsync(&nv, h->view_offs.get() + nlm, 8, hipMemcpyDeviceToHost, st));
+    DVS_HIP(hipMemcpyAsync(&nv, h->v_lm.offs.get() + nlm, sizeof(i64), hipMemcpyDeviceToHost, st));
     DVS_HIP(hipStreamSynchronize(st));
     if (n_obs_ids) *n_obs_ids = nv;
   }
@@ -827,14 +741,10 @@ dvs_status dvs_backend_get_landmarks(dvs_backend* h, int32_t cap, int64_t cap_ob
   }
   if (obs_offsets && nlm == 0) obs_offsets[0] = 0;
   if (nlm == 0) return DVS_OK;
-  if (id) DVS_HIP(hipMemcpyAsync(id, h->lm.id.get(), nlm * 8, hipMemcpyDeviceToHost, st));
-  if (class_id) DVS_HIP(hipMemcpyAsync(class_id, h->lm.cls.get(), nlm * 4, hipMemcpyDeviceToHost, st));
-  if (xyz) DVS_HIP(hipMemcpyAsync(xyz, h->lm.xyz.get(), nlm * 12, hipMemcpyDeviceToHost, st));
-  if (desc) DVS_HIP(hipMemcpyAsync(desc, h->lm.desc.get(), nlm * 32, hipMemcpyDeviceToHost, st));
-  if (observation_count) DVS_HIP(hipMemcpyAsync(observation_count, h->lm.cnt.get(), nlm * 4, hipMemcpyDeviceToHost, st));
-  if (last_seen_ns) DVS_HIP(hipMemcpyAsync(last_seen_ns, h->lm.seen.get(), nlm * 8, hipMemcpyDeviceToHost, st));
-  if (obs_offsets) DVS_HIP(hipMemcpyAsync(obs_offsets, h->view_offs.get(), (nlm + 1) * 8, hipMemcpyDeviceToHost, st));
-  if (obs_ids && nv) DVS_HIP(hipMemcpyAsync(obs_ids, h->view_oid.get(), (size_t)nv * 8, hipMemcpyDeviceToHost, st));
+  DVS_TRY(copy_out(id, h->lm.id, nlm, st)); DVS_TRY(copy_out(class_id, h->lm.cls, nlm, st)); DVS_TRY(copy_out(xyz, h->lm.xyz, nlm, st));
+  DVS_TRY(copy_out(desc, h->lm.desc, nlm, st)); DVS_TRY(copy_out(observation_count, h->lm.cnt, nlm, st)); DVS_TRY(copy_out(last_seen_ns, h->lm.seen, nlm, st));
+  DVS_TRY(copy_out(obs_offsets, h->v_lm.offs, nlm + 1, st));
+  if (nv) DVS_TRY(copy_out(obs_ids, h->v_ob.oid, (size_t)nv, st));
   DVS_HIP(hipStreamSynchronize(st));
   return DVS_OK;
 }
@@ -848,12 +758,8 @@ dvs_status dvs_backend_get_observations(dvs_backend* h, int32_t cap, uint64_t* i
   if (nob == 0) return DVS_OK;
   DVS_HIP(hipSetDevice(h->device));
   hipStream_t st = h->ctx->stream;
-  if (id) DVS_HIP(hipMemcpyAsync(id, h->ob.id.get(), nob * 8, hipMemcpyDeviceToHost, st));
-  if (frame_id) DVS_HIP(hipMemcpyAsync(frame_id, h->ob.frame.get(), nob * 8, hipMemcpyDeviceToHost, st));
-  if (px) DVS_HIP(hipMemcpyAsync(px, h->ob.px.get(), nob * 8, hipMemcpyDeviceToHost, st));
-  if (desc) DVS_HIP(hipMemcpyAsync(desc, h->ob.desc.get(), nob * 32, hipMemcpyDeviceToHost, st));
-  if (class_id) DVS_HIP(hipMemcpyAsync(class_id, h->ob.cls.get(), nob * 4, hipMemcpyDeviceToHost, st));
-  if (landmark_id) DVS_HIP(hipMemcpyAsync(landmark_id, h->ob.lm.get(), nob * 8, hipMemcpyDeviceToHost, st));
+  DVS_TRY(copy_out(id, h->ob.id, nob, st)); DVS_TRY(copy_out(frame_id, h->ob.frame, nob, st)); DVS_TRY(copy_out(px, h->ob.px, nob, st));
+  DVS_TRY(copy_out(desc, h->ob.desc, nob, st)); DVS_TRY(copy_out(class_id, h->ob.cls, nob, st)); DVS_TRY(copy_out(landmark_id, h->ob.lm, nob, st));
   DVS_HIP(hipStreamSynchronize(st));
   return DVS_OK;
 }
@@ -874,8 +780,7 @@ dvs_status dvs_backend_get_keyframes(dvs_backend* h, int32_t cap, int64_t cap_ob
   if (nkf && (R || t)) {
     DVS_HIP(hipSetDevice(h->device));
     hipStream_t st = h->ctx->stream;
-    if (R) DVS_HIP(hipMemcpyAsync(R, h->kf_R.get(), nkf * 72, hipMemcpyDeviceToHost, st));
-    if (t) DVS_HIP(hipMemcpyAsync(t, h->kf_t.get(), nkf * 24, hipMemcpyDeviceToHost, st));
+    DVS_TRY(copy_out(R, h->kf_R, nkf, st)); DVS_TRY(copy_out(t, h->kf_t, nkf, st));
     DVS_HIP(hipStreamSynchronize(st));
   }
   int64_t o = 0;

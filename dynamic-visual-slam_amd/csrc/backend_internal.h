@@ -1,8 +1,12 @@
-// backend_internal.h — the mapping backend handle (dvs_backend, include/dvslam_hip.h) shared by backend.hip and loop_close.hip: the views of
-// the landmark and observation tables that kernels take, the owners of the tables, the keyframe record and the handle itself.  Internal
-// to the library, as loop_internal.h and bow_internal.h are.
+// backend_internal.h — the mapping backend handle (dvs_backend, include/dvslam_hip.h) shared by backend.hip, loop_close.hip and
+// covisibility.hip: the views of the landmark and observation tables that kernels take, the owners of the tables, the keyframe record,
+// the counter block, the row groups of per-call scratch and the handle itself.  Internal to the library, as loop_internal.h and
+// bow_internal.h are.
 #pragma once
+#include <stddef.h>
+#include <tuple>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 #include "common.h"
 #include "device_mem.h"
@@ -31,29 +35,155 @@ __device__ __forceinline__ void copy32(uint8_t* __restrict__ dst, const uint8_t*
   reinterpret_cast<uint4*>(dst)[0] = a; reinterpret_cast<uint4*>(dst)[1] = b;
 }
 
+// A table states its columns once, in columns(): owner, elements per row and element type are the member's Column type.  alloc, view,
+// table_copy and the getters' byte counts (copy_out) all come from there.
+template <class Table> dvs_status table_alloc(Table& t, size_t c) {
+  DVS_TRY(std::apply([&](auto&... col) { return alloc_rows(c, col...); }, Table::columns(t)));
+  t.cap = c;
+  return DVS_OK;
+}
+template <class Table, size_t... I> dvs_status table_copy(Table& dst, const Table& src, size_t n, hipStream_t st, std::index_sequence<I...>) {
+  const auto d = Table::columns(dst);
+  const auto s = Table::columns(src);
+  hipError_t e = hipSuccess;
+  (void)(... && ((e = hipMemcpyAsync(std::get<I>(d).get(), std::get<I>(s).get(), n * std::get<I>(s).row_bytes, hipMemcpyDeviceToDevice, st)) == hipSuccess));
+  DVS_HIP(e);
+  return DVS_OK;
+}
 struct LmTable {
-  DeviceBuf<i64> id, seen; DeviceBuf<int> cls, cnt; DeviceBuf<float> xyz; DeviceBuf<uint8_t> desc;
+  Column<i64> id, seen; Column<int> cls, cnt; Column<float, 3> xyz; Column<uint8_t, 32> desc;
   size_t cap = 0;
-  dvs_status alloc(size_t c) {
-    DVS_TRY(id.alloc(c)); DVS_TRY(seen.alloc(c)); DVS_TRY(cls.alloc(c)); DVS_TRY(cnt.alloc(c)); DVS_TRY(xyz.alloc(c * 3)); DVS_TRY(desc.alloc(c * 32));
-    cap = c;
-    return DVS_OK;
-  }
-  LmView view() const { return LmView{id.get(), seen.get(), cls.get(), cnt.get(), xyz.get(), desc.get()}; }
+  template <class S> static auto columns(S& t) { return std::tie(t.id, t.seen, t.cls, t.cnt, t.xyz, t.desc); }
+  LmView view() const { return std::apply([](auto&... c) { return LmView{c.get()...}; }, columns(*this)); }
 };
 struct ObTable {
-  DeviceBuf<i64> id, frame, lm; DeviceBuf<int> kf, cls; DeviceBuf<float> px; DeviceBuf<uint8_t> desc;
+  Column<i64> id, frame, lm; Column<int> kf, cls; Column<float, 2> px; Column<uint8_t, 32> desc;
   size_t cap = 0;
-  dvs_status alloc(size_t c) {
-    DVS_TRY(id.alloc(c)); DVS_TRY(frame.alloc(c)); DVS_TRY(lm.alloc(c)); DVS_TRY(kf.alloc(c)); DVS_TRY(cls.alloc(c)); DVS_TRY(px.alloc(c * 2));
-    DVS_TRY(desc.alloc(c * 32));
-    cap = c;
-    return DVS_OK;
-  }
-  ObView view() const { return ObView{id.get(), frame.get(), lm.get(), kf.get(), cls.get(), px.get(), desc.get()}; }
+  template <class S> static auto columns(S& t) { return std::tie(t.id, t.frame, t.lm, t.kf, t.cls, t.px, t.desc); }
+  ObView view() const { return std::apply([](auto&... c) { return ObView{c.get()...}; }, columns(*this)); }
 };
+// a table of capacity `c` (at least `need` rows; doubled from the live one) with the first n rows of `live`, which it then replaces; the
+// old blocks are freed by the assignment, after the stream has drained
+template <class Table> dvs_status table_regrow(Table& live, size_t need, size_t n, hipStream_t st) {
+  if (need <= live.cap) return DVS_OK;
+  size_t c = std::max<size_t>(live.cap, 1);
+  while (c < need) c *= 2;
+  Table t;
+  DVS_TRY(table_alloc(t, c));
+  if (n) DVS_TRY(table_copy(t, live, n, st, std::make_index_sequence<std::tuple_size<decltype(Table::columns(t))>::value>()));
+  DVS_HIP(hipStreamSynchronize(st));
+  live = std::move(t);
+  return DVS_OK;
+}
+// the spare table that receives a compaction of `live` and then changes places with it: as large as the live one
+template <class Table> dvs_status table_match_spare(Table& spare, const Table& live) { return spare.cap != live.cap ? table_alloc(spare, live.cap) : DVS_OK; }
 
 struct KeyframeRec { uint64_t frame_id; i64 stamp; std::vector<uint64_t> obs_ids; double R[9], t[3]; };
+
+// The 256 ints of counters and small lists that kernels write and the host reads back, one block per handle (dvs_backend::s_small).
+// add_keyframe uploads the whole block: its two lists, and zeros everywhere else.
+struct FuseCounts { int n_query, n_sources, n_targets, n_proposals, n_fused, n_kept, n_anchored, pad; };   // n_anchored: k_anchors, cleared on its own
+struct BackendSmall {
+  int filtered[64];      // add_keyframe: the filtered class ids
+  int classes[64];       //               the distinct unfiltered classes of the keyframe
+  int class_cnt[64];     //               k_categorize: kept observations per class
+  int counts[4];         // the call's one-block kernel: k_class_gather {landmarks of the class}, k_window_gather {observations, landmarks},
+                         // k_prune_compact {landmarks kept, observations kept, observations removed}
+  int marked, pad0[3];   // k_prune_mark: marked landmarks
+  FuseCounts fuse;       // loop_close.hip
+  int left_out, pad1[47];   // covisibility.hip, k_covis_ob_flag: rows left out of the local window
+};
+static_assert(sizeof(BackendSmall) == 256 * 4 && offsetof(BackendSmall, classes) == 64 * 4 && offsetof(BackendSmall, class_cnt) == 128 * 4 &&
+              offsetof(BackendSmall, counts) == 192 * 4 && offsetof(BackendSmall, marked) == 196 * 4 && offsetof(BackendSmall, fuse) == 200 * 4 &&
+              offsetof(BackendSmall, fuse.n_anchored) == 206 * 4 && offsetof(BackendSmall, left_out) == 208 * 4, "kernels and the upload keep these addresses");
+
+// The eight columns a BA window hands out, in two halves by row domain; the sliding window and the local window each hold both.
+struct WindowObs { Column<float, 2> px; Column<i64> lm; Column<int> cls; Column<i64> frame; Column<int> lmidx; };
+struct WindowLms { Column<i64> id; Column<int> cls; Column<float, 3> xyz; };
+inline dvs_status window_copy_out(const WindowObs& o, size_t no, const WindowLms& l, size_t nl, float* o_px, uint64_t* o_lm, int32_t* o_cls, uint64_t* o_frame,
+                                  int32_t* o_lmidx, uint64_t* l_id, int32_t* l_cls, float* l_xyz, hipStream_t st) {
+  if (no) { DVS_TRY(copy_out(o_px, o.px, no, st)); DVS_TRY(copy_out(o_lm, o.lm, no, st)); DVS_TRY(copy_out(o_cls, o.cls, no, st)); DVS_TRY(copy_out(o_frame, o.frame, no, st)); DVS_TRY(copy_out(o_lmidx, o.lmidx, no, st)); }
+  if (nl) { DVS_TRY(copy_out(l_id, l.id, nl, st)); DVS_TRY(copy_out(l_cls, l.cls, nl, st)); DVS_TRY(copy_out(l_xyz, l.xyz, nl, st)); }
+  return DVS_OK;
+}
+
+// Row groups (device_mem.h, grow_rows): per-call scratch, grow-only.  Each names its row domain, its need and its size rule once.  The
+// rules differ because each was chosen with its call; they are kept as they were, so that a map grows through the same allocations.
+struct KeyframeObRows {   // per observation of the keyframe being added: a quarter to spare
+  Column<float, 2> s_px; Column<float, 3> s_xyz; Column<uint8_t, 32> s_desc; Column<float, 2> q_px; Column<uint8_t, 32> q_desc; Column<int> s_code, s_order, d_best;
+  size_t cap = 0;
+  dvs_status grow(size_t n) { return grow_rows(cap, n, n + n / 4, s_px, s_xyz, s_desc, q_px, q_desc, s_code, s_order, d_best); }
+};
+struct ClassLmRows {      // per landmark gathered for one class: half to spare
+  Column<int> slot; Column<uint8_t, 32> desc; Column<float, 3> xyz;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2, slot, desc, xyz); }
+};
+struct ViewLmRows {       // views CSR and triangulation per landmark, one row more for the CSR's end
+  Column<int> cnt, fill; Column<i64> offs; Column<float, 3> tri_xyz; Column<int> tri_status;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm + 1, nlm + 1 + nlm / 2, cnt, fill, offs, tri_xyz, tri_status); }
+};
+struct ViewObRows {       // views per observation: its landmark row; the CSR's values (observation row, keyframe, pixel, observation id)
+  Column<int> slot, rows, kf; Column<float, 2> px; Column<i64> oid;
+  size_t cap = 0;
+  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2 + 64, slot, rows, kf, px, oid); }
+};
+struct SlidingObRows {    // the sliding window per observation: table row and landmark row, then the window's columns
+  Column<int> oi, slot; WindowObs o;
+  size_t cap = 0;
+  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2, oi, slot, o.px, o.lm, o.cls, o.frame, o.lmidx); }
+};
+struct SlidingLmRows {    // the sliding window per landmark: the window's columns, then in-window flag and row in the window
+  WindowLms l; Column<int> flag, pos;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm + 1, nlm + 1 + nlm / 2, l.id, l.cls, l.xyz, flag, pos); }
+};
+struct PruneLmRows {
+  Column<int> flag;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2, flag); }
+};
+struct PruneObRows {      // the removed observations
+  Column<int> rem_kf; Column<i64> rem_id;
+  size_t cap = 0;
+  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2, rem_kf, rem_id); }
+};
+struct FuseLmRows {       // fusion per landmark row: flags, proposals, the resolved pairs and the pair list
+  Column<int> flag, src, propb, bsrc, redirect, partner; Column<unsigned long long> prope, beste; Column<i64> psurv, prem; Column<double> pe;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 1, flag, src, propb, bsrc, redirect, partner, prope, beste, psurv, prem, pe); }
+};
+struct FuseQueryRows {    // fusion per observation of the query keyframe
+  Column<float, 2> px; Column<int> cls; Column<i64> oid; Column<int> brow; Column<uint8_t, 32> desc;
+  size_t cap = 0;
+  dvs_status grow(size_t nq) { return grow_rows(cap, nq, nq + nq / 4, px, cls, oid, brow, desc); }
+};
+struct CovisObRows {      // covisibility per observation: the keyframe where the view counts, keyframe -> landmarks CSR; in-window flag, the local window's columns
+  Column<int> kf, tmp, list, flag; WindowObs o;
+  size_t cap = 0;
+  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2 + 64, kf, tmp, list, flag, o.cls, o.lmidx, o.lm, o.frame, o.px); }
+};
+struct CovisKfRows {      // per keyframe, one row more for the CSRs' ends
+  Column<int> cnt, fill, role, f, nbc; Column<i64> offs, nboffs;
+  size_t cap = 0;
+  dvs_status grow(size_t nkf) { return grow_rows(cap, nkf + 1, nkf + 1 + nkf / 2, cnt, fill, role, f, nbc, offs, nboffs); }
+};
+struct CovisLmRows {      // per landmark row: in U, row in U; U's columns (the local window's landmark half, and descriptors for the local map)
+  Column<int> flag, pos, slot; WindowLms u; Column<uint8_t, 32> desc;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, flag, pos, slot, u.cls, u.id, u.xyz, desc); }
+};
+struct CovisBlockRows {   // per 256-row block of a table: the ordered compaction's counts and their scan, which ends with the total
+  Column<int> cnt; Column<i64, 1, 1> offs;
+  size_t cap = 0;
+  dvs_status grow(size_t nblk) { return grow_rows(cap, nblk, nblk + nblk / 2, cnt, offs); }
+};
+struct CovisWeightRows {  // requested rows x keyframes: weights and neighbour lists, packed CSR.  Exact: the full graph asks for nkf * nkf once
+  Column<int> w, nbt, nbi, nbw, pki, pkw;
+  size_t cap = 0;
+  dvs_status grow(size_t n) { return grow_rows(cap, n, n, w, nbt, nbi, nbw, pki, pkw); }
+};
 
 }  // namespace dvs
 
@@ -63,56 +193,44 @@ struct dvs_backend {
   dvs_matcher* ctx = nullptr;
   // the map
   dvs::LmTable lm, lm_spare; dvs::ObTable ob, ob_spare;          // the spare pair receives dvs_backend_prune's compaction
-  dvs::DeviceBuf<double> kf_R, kf_t;
+  dvs::Column<double, 9> kf_R; dvs::Column<double, 3> kf_t;
   size_t cap_kf = 0;
   int nlm = 0, nob = 0;
   std::vector<dvs::KeyframeRec> kfs;                      // keyframes_
   std::unordered_map<uint64_t, int> kf_index;        // frame_id -> index
   dvs::i64 next_obs = 0, next_lm = 0;                     // next_observation_id_, next_global_landmark_id_
-  // per-call staging and scratch (grow-only)
-  dvs::DeviceBuf<float> s_px, s_xyz, q_px, g_xyz, tri_xyz, view_px, w_px, w_lxyz;
-  dvs::DeviceBuf<uint8_t> s_desc, q_desc, g_desc;
-  dvs::DeviceBuf<int> s_code, s_order, s_small, g_slot, d_best, ob_slot, v_cnt, v_fill, v_obs, view_kf, tri_status, a_int, w_flag, w_pos, w_oi, w_slot, w_cls,
-      w_lmidx, w_lcls;
-  dvs::DeviceBuf<dvs::i64> view_offs, view_oid, a_i64, w_lm, w_frame, w_lid;
-  dvs::DeviceBuf<dvs::DetRec> s_det;
-  dvs::DeviceBuf<dvs::PairRec> p_rec;
-  dvs::DeviceBuf<int> p_flag, rem_kf;
-  dvs::DeviceBuf<dvs::i64> rem_id;
-  size_t c_pflag = 0, c_rem = 0;
-  dvs::DeviceBuf<double> d_Rt, a_dbl;
-  size_t c_n = 0, c_det = 0, c_glm = 0, c_vlm = 0, c_vob = 0, c_pair = 0, c_aint = 0, c_ai64 = 0, c_adbl = 0, c_wob = 0, c_wlm = 0;
+  // the counter block, the keyframe's pose
+  dvs::DeviceBuf<dvs::BackendSmall> s_small;
+  dvs::DeviceBuf<double> d_Rt;
+  // row groups: add_keyframe and the views; the sliding window; prune; fusion (loop_close.hip); covisibility (covisibility.hip)
+  dvs::KeyframeObRows kf_ob; dvs::ClassLmRows cls_lm; dvs::ViewLmRows v_lm; dvs::ViewObRows v_ob;
+  dvs::SlidingObRows win_ob; dvs::SlidingLmRows win_lm;
+  dvs::PruneLmRows prune_lm; dvs::PruneObRows prune_ob;
+  dvs::FuseLmRows fuse_lm; dvs::FuseQueryRows fuse_q;
+  dvs::CovisObRows cv_ob; dvs::CovisKfRows cv_kf; dvs::CovisLmRows cv_lm; dvs::CovisBlockRows cv_blk; dvs::CovisWeightRows cv_w;
+  // single blocks (device_mem.h, grow): detections, candidate pairs, per-call arguments, anchors per landmark, landmark row per observation
+  dvs::DeviceBuf<dvs::DetRec> s_det; dvs::DeviceBuf<dvs::PairRec> p_rec; dvs::DeviceBuf<int> a_int, f_obrow; dvs::Column<int> f_anchor; dvs::DeviceBuf<dvs::i64> a_i64; dvs::DeviceBuf<double> a_dbl;
+  size_t c_det = 0, c_pair = 0, c_aint = 0, c_ai64 = 0, c_adbl = 0, c_flm = 0, c_fob = 0;
   // host staging that asynchronous copies read until the call's last synchronisation
+  dvs::BackendSmall h_small;
   std::vector<float> h_px, h_xyz;
   std::vector<int> h_int;
   std::vector<dvs::i64> h_i64;
   std::vector<double> h_dbl;
   std::vector<dvs::DetRec> h_det;
-  // loop closing (loop_close.hip): anchors, fusion flags and lists, all grow-only
-  dvs::DeviceBuf<int> f_anchor, f_obrow, f_flag, f_src, f_qbrow, f_qcls, f_propb, f_bsrc, f_redirect, f_partner;
-  dvs::DeviceBuf<float> f_qpx;
-  dvs::DeviceBuf<uint8_t> f_qdesc;
-  dvs::DeviceBuf<dvs::i64> f_qoid, f_psurv, f_prem;
-  dvs::DeviceBuf<unsigned long long> f_prope, f_beste;
-  dvs::DeviceBuf<double> f_pe;
-  size_t c_flm = 0, c_frow = 0, c_fob = 0, c_fq = 0;   // anchors; fusion per landmark row / per observation / per query observation
-  // covisibility (covisibility.hip), all grow-only: per view / per keyframe / per landmark row / per observation / per requested row x keyframe
-  dvs::DeviceBuf<int> cv_kf, cv_tmp, cv_list;                                    // per view: the keyframe where the view counts, keyframe -> landmarks CSR
-  dvs::DeviceBuf<int> cv_cnt, cv_fill, cv_role, cv_f, cv_blk;                    // per keyframe (cv_blk: per 256-row block of a table)
-  dvs::DeviceBuf<dvs::i64> cv_offs, cv_nboffs, cv_blkoffs;
-  dvs::DeviceBuf<int> cv_lflag, cv_lpos, cv_uslot, cv_ucls;                      // per landmark row: in U, row in U; U's columns
-  dvs::DeviceBuf<dvs::i64> cv_uid;
-  dvs::DeviceBuf<float> cv_uxyz;
-  dvs::DeviceBuf<uint8_t> cv_udesc;
-  dvs::DeviceBuf<int> cv_oflag, cv_ocls, cv_olmidx;                              // per observation: in the window; the window's columns
-  dvs::DeviceBuf<dvs::i64> cv_olm, cv_oframe;
-  dvs::DeviceBuf<float> cv_opx;
-  dvs::DeviceBuf<int> cv_w, cv_nbt, cv_nbi, cv_nbw, cv_nbc, cv_pki, cv_pkw;      // weights and neighbour lists, rows x keyframes; packed CSR
-  size_t c_cvv = 0, c_cvk = 0, c_cvl = 0, c_cvo = 0, c_cvw = 0, c_cvb = 0;
 };
 
 namespace dvs {
-// landmark -> views CSR over the whole table into view_offs / view_kf / view_px / view_oid, segments in observation order, on the
+// `n` ints of the counter block from device address `field` on, to dst: enqueued, then the stream is synchronised
+inline dvs_status small_read(dvs_backend* h, const int* field, int* dst, int n = 1) {
+  DVS_HIP(hipMemcpyAsync(dst, field, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->ctx->stream));
+  DVS_HIP(hipStreamSynchronize(h->ctx->stream));
+  return DVS_OK;
+}
+}  // namespace dvs
+
+namespace dvs {
+// landmark -> views CSR over the whole table into v_lm.offs and v_ob.kf / .px / .oid, segments in observation order, on the
 // handle's stream (backend.hip); nothing to do for an empty landmark table
 dvs_status backend_views_build(dvs_backend* h);
 // the local map of keyframe ref_frame_id ("Covisibility" in the header; covisibility.hip): U's positions, descriptors and ids compacted in

@@ -1,7 +1,7 @@
 // covisibility.hip — the covisibility graph of the map the backend keeps on the device, and its two consumers: the local BA window and the
 // local map for tracking (include/dvslam_hip.h "Covisibility"; the rule is stated there in full and restated in tests/covisibility_ref.py).
 //
-// Everything is derived from backend_views_build's landmark -> views CSR (view_offs / view_kf / v_obs, segments in observation order):
+// Everything is derived from backend_views_build's landmark -> views CSR (v_lm.offs / v_ob.kf / v_ob.rows, segments in observation order):
 //   k_covis_first      per view: the keyframe where the view COUNTS (cv_kf) — its keyframe if no earlier view of the segment has the same
 //                      one, else -1 — so a keyframe that names a landmark twice observes it once; histogram of the counting views by keyframe.
 //                      The earlier views are searched, not assumed adjacent: nothing here rests on the order of the observation table
@@ -222,8 +222,6 @@ using namespace dvs;
 
 namespace {
 
-const int kLeft = 208;   // s_small[208]: left-out rows (backend.hip's kSmall lists the other slots)
-
 dvs_status covis_check(const dvs_covis_params& P) {
   DVS_ARG(P.min_weight >= 1);
   DVS_ARG(P.max_neighbours >= 0 && P.max_neighbours <= 62);
@@ -244,48 +242,9 @@ dvs_status covis_limit(const dvs_backend* h, const char* who) {
 // scratch for nkf keyframes, the tables as they stand and `rows` rows of weights
 dvs_status covis_grow(dvs_backend* h, size_t rows) {
   const size_t nkf = h->kfs.size(), nlm = (size_t)h->nlm, nob = (size_t)h->nob;
-  if (nob > h->c_cvv) {
-    const size_t c = nob + nob / 2 + 64;
-    h->c_cvv = 0;
-    DVS_TRY(h->cv_kf.alloc(c)); DVS_TRY(h->cv_tmp.alloc(c)); DVS_TRY(h->cv_list.alloc(c));
-    h->c_cvv = c;
-  }
-  if (nkf + 1 > h->c_cvk) {
-    const size_t c = nkf + 1 + nkf / 2;
-    h->c_cvk = 0;
-    DVS_TRY(h->cv_cnt.alloc(c)); DVS_TRY(h->cv_fill.alloc(c)); DVS_TRY(h->cv_role.alloc(c)); DVS_TRY(h->cv_f.alloc(c)); DVS_TRY(h->cv_nbc.alloc(c));
-    DVS_TRY(h->cv_offs.alloc(c)); DVS_TRY(h->cv_nboffs.alloc(c));
-    h->c_cvk = c;
-  }
-  if (nlm > h->c_cvl) {
-    const size_t c = nlm + nlm / 2 + 64;
-    h->c_cvl = 0;
-    DVS_TRY(h->cv_lflag.alloc(c)); DVS_TRY(h->cv_lpos.alloc(c)); DVS_TRY(h->cv_uslot.alloc(c)); DVS_TRY(h->cv_ucls.alloc(c)); DVS_TRY(h->cv_uid.alloc(c));
-    DVS_TRY(h->cv_uxyz.alloc(c * 3)); DVS_TRY(h->cv_udesc.alloc(c * 32));
-    h->c_cvl = c;
-  }
-  if (nob > h->c_cvo) {
-    const size_t c = nob + nob / 2 + 64;
-    h->c_cvo = 0;
-    DVS_TRY(h->cv_oflag.alloc(c)); DVS_TRY(h->cv_ocls.alloc(c)); DVS_TRY(h->cv_olmidx.alloc(c)); DVS_TRY(h->cv_olm.alloc(c)); DVS_TRY(h->cv_oframe.alloc(c));
-    DVS_TRY(h->cv_opx.alloc(c * 2));
-    h->c_cvo = c;
-  }
-  const size_t nblk = std::max(nlm, nob) / 256 + 2;
-  if (nblk > h->c_cvb) {
-    const size_t c = nblk + nblk / 2;
-    h->c_cvb = 0;
-    DVS_TRY(h->cv_blk.alloc(c)); DVS_TRY(h->cv_blkoffs.alloc(c + 1));
-    h->c_cvb = c;
-  }
-  const size_t nw = std::max<size_t>(rows * nkf, 1);
-  if (nw > h->c_cvw) {
-    h->c_cvw = 0;
-    DVS_TRY(h->cv_w.alloc(nw)); DVS_TRY(h->cv_nbt.alloc(nw)); DVS_TRY(h->cv_nbi.alloc(nw)); DVS_TRY(h->cv_nbw.alloc(nw)); DVS_TRY(h->cv_pki.alloc(nw));
-    DVS_TRY(h->cv_pkw.alloc(nw));
-    h->c_cvw = nw;
-  }
-  return DVS_OK;
+  DVS_TRY(h->cv_ob.grow(nob)); DVS_TRY(h->cv_kf.grow(nkf)); DVS_TRY(h->cv_lm.grow(nlm));
+  DVS_TRY(h->cv_blk.grow(std::max(nlm, nob) / 256 + 2));
+  return h->cv_w.grow(std::max<size_t>(rows * nkf, 1));
 }
 
 // the views CSR, the counting views and the keyframe -> landmarks CSR, enqueued; needs at least one landmark and one keyframe
@@ -293,26 +252,26 @@ dvs_status covis_prepare(dvs_backend* h) {
   hipStream_t st = h->ctx->stream;
   const int nkf = (int)h->kfs.size(), nlm = h->nlm;
   DVS_TRY(backend_views_build(h));
-  DVS_HIP(hipMemsetAsync(h->cv_cnt.get(), 0, (size_t)nkf * 4, st));
-  DVS_HIP(hipMemsetAsync(h->cv_fill.get(), 0, (size_t)nkf * 4, st));
-  const i64* voffs = h->view_offs.get();
-  hipLaunchKernelGGL(k_covis_first, dim3((nlm + 3) / 4), dim3(256), 0, st, nlm, nkf, voffs, (const int*)h->view_kf.get(), h->cv_kf.get(), h->cv_cnt.get());
-  launch_scan_counts(st, (const int*)h->cv_cnt.get(), nkf, h->cv_offs.get());
-  hipLaunchKernelGGL(k_covis_scatter, dim3((nlm + 3) / 4), dim3(256), 0, st, nlm, voffs, (const int*)h->cv_kf.get(), (const i64*)h->cv_offs.get(), h->cv_fill.get(),
-                     h->cv_tmp.get());
-  hipLaunchKernelGGL(k_covis_order, dim3(nkf), dim3(256), 0, st, (const i64*)h->cv_offs.get(), (const int*)h->cv_tmp.get(), h->cv_list.get());
+  DVS_HIP(hipMemsetAsync(h->cv_kf.cnt.get(), 0, (size_t)nkf * 4, st));
+  DVS_HIP(hipMemsetAsync(h->cv_kf.fill.get(), 0, (size_t)nkf * 4, st));
+  const i64* voffs = h->v_lm.offs.get();
+  hipLaunchKernelGGL(k_covis_first, dim3((nlm + 3) / 4), dim3(256), 0, st, nlm, nkf, voffs, (const int*)h->v_ob.kf.get(), h->cv_ob.kf.get(), h->cv_kf.cnt.get());
+  launch_scan_counts(st, (const int*)h->cv_kf.cnt.get(), nkf, h->cv_kf.offs.get());
+  hipLaunchKernelGGL(k_covis_scatter, dim3((nlm + 3) / 4), dim3(256), 0, st, nlm, voffs, (const int*)h->cv_ob.kf.get(), (const i64*)h->cv_kf.offs.get(), h->cv_kf.fill.get(),
+                     h->cv_ob.tmp.get());
+  hipLaunchKernelGGL(k_covis_order, dim3(nkf), dim3(256), 0, st, (const i64*)h->cv_kf.offs.get(), (const int*)h->cv_ob.tmp.get(), h->cv_ob.list.get());
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
 
-// `rows` rows of W from keyframe row0 on into cv_w, and their neighbour lists at theta into cv_nbi / cv_nbw / cv_nbc
+// `rows` rows of W from keyframe row0 on into cv_w.w, and their neighbour lists at theta into cv_w.nbi / cv_w.nbw / cv_kf.nbc
 dvs_status covis_rows(dvs_backend* h, int row0, int rows, int theta) {
   hipStream_t st = h->ctx->stream;
   const int nkf = (int)h->kfs.size();
-  hipLaunchKernelGGL(k_covis_row, dim3(rows), dim3(256), (size_t)nkf * 4, st, nkf, row0, (const i64*)h->cv_offs.get(), (const int*)h->cv_list.get(),
-                     (const i64*)h->view_offs.get(), (const int*)h->cv_kf.get(), h->cv_w.get());
-  hipLaunchKernelGGL(k_covis_neighbours, dim3(rows), dim3(256), 0, st, nkf, row0, (const int*)h->cv_w.get(), theta, (const int*)nullptr, h->cv_nbt.get(), h->cv_nbi.get(),
-                     h->cv_nbw.get(), h->cv_nbc.get());
+  hipLaunchKernelGGL(k_covis_row, dim3(rows), dim3(256), (size_t)nkf * 4, st, nkf, row0, (const i64*)h->cv_kf.offs.get(), (const int*)h->cv_ob.list.get(),
+                     (const i64*)h->v_lm.offs.get(), (const int*)h->cv_ob.kf.get(), h->cv_w.w.get());
+  hipLaunchKernelGGL(k_covis_neighbours, dim3(rows), dim3(256), 0, st, nkf, row0, (const int*)h->cv_w.w.get(), theta, (const int*)nullptr, h->cv_w.nbt.get(), h->cv_w.nbi.get(),
+                     h->cv_w.nbw.get(), h->cv_kf.nbc.get());
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
@@ -321,8 +280,8 @@ dvs_status covis_rows(dvs_backend* h, int row0, int rows, int theta) {
 dvs_status covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk) {
   hipStream_t st = h->ctx->stream;
   *nblk = (n + 255) / 256;
-  if (*nblk) hipLaunchKernelGGL(k_covis_blk_count, dim3(*nblk), dim3(256), 0, st, flag, n, h->cv_blk.get());
-  launch_scan_counts(st, (const int*)h->cv_blk.get(), *nblk, h->cv_blkoffs.get());
+  if (*nblk) hipLaunchKernelGGL(k_covis_blk_count, dim3(*nblk), dim3(256), 0, st, flag, n, h->cv_blk.cnt.get());
+  launch_scan_counts(st, (const int*)h->cv_blk.cnt.get(), *nblk, h->cv_blk.offs.get());
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
@@ -334,8 +293,8 @@ struct LocalSet {
   int n_u = 0, n_obs = 0, n_left = 0;
 };
 
-// The local set of keyframe r on the device: U's columns in cv_u* (descriptors if want_desc); with want_window the fixed keyframes and the
-// window's observation columns in cv_o*.  Returns synchronised.
+// The local set of keyframe r on the device: U's columns in cv_lm.u and cv_lm.desc (descriptors if want_desc); with want_window the fixed keyframes and the
+// window's observation columns in cv_ob.o.  Returns synchronised.
 dvs_status covis_local(dvs_backend* h, int r, const dvs_covis_params& P, bool want_window, bool want_desc, LocalSet* out) {
   const int nkf = (int)h->kfs.size(), nlm = h->nlm, nob = h->nob;
   *out = LocalSet();
@@ -351,9 +310,9 @@ dvs_status covis_local(dvs_backend* h, int r, const dvs_covis_params& P, bool wa
   std::vector<int> w((size_t)nkf), nb((size_t)std::max(P.max_neighbours, 1)), role((size_t)nkf, 0);
   int cnt = 0;
   const int take = std::min(P.max_neighbours, nkf);
-  DVS_HIP(hipMemcpyAsync(w.data(), h->cv_w.get(), (size_t)nkf * 4, hipMemcpyDeviceToHost, st));
-  if (take) DVS_HIP(hipMemcpyAsync(nb.data(), h->cv_nbi.get(), (size_t)take * 4, hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipMemcpyAsync(&cnt, h->cv_nbc.get(), 4, hipMemcpyDeviceToHost, st));
+  DVS_TRY(copy_out(w.data(), h->cv_w.w, (size_t)nkf, st));
+  if (take) DVS_TRY(copy_out(nb.data(), h->cv_w.nbi, (size_t)take, st));
+  DVS_TRY(copy_out(&cnt, h->cv_kf.nbc, 1, st));
   DVS_HIP(hipStreamSynchronize(st));
   if (cnt < 0 || cnt > nkf) { set_error("covisibility: inconsistent neighbour count %d", cnt); return DVS_ERR_HIP; }
   role[(size_t)r] = 1;
@@ -362,28 +321,28 @@ dvs_status covis_local(dvs_backend* h, int r, const dvs_covis_params& P, bool wa
     role[(size_t)nb[(size_t)j]] = 1;
   }
   // U
-  DVS_HIP(hipMemcpyAsync(h->cv_role.get(), role.data(), (size_t)nkf * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_covis_lm_flag, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, (const i64*)h->view_offs.get(), (const int*)h->cv_kf.get(), (const int*)h->cv_role.get(),
-                     h->cv_lflag.get());
+  DVS_HIP(hipMemcpyAsync(h->cv_kf.role.get(), role.data(), (size_t)nkf * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_covis_lm_flag, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, (const i64*)h->v_lm.offs.get(), (const int*)h->cv_ob.kf.get(), (const int*)h->cv_kf.role.get(),
+                     h->cv_lm.flag.get());
   int nblk = 0;
-  DVS_TRY(covis_block_offsets(h, h->cv_lflag.get(), nlm, &nblk));
-  hipLaunchKernelGGL(k_covis_lm_gather, dim3(nblk), dim3(256), 0, st, h->lm.view(), nlm, (const int*)h->cv_lflag.get(), (const i64*)h->cv_blkoffs.get(), want_desc ? 1 : 0,
-                     h->cv_lpos.get(), h->cv_uslot.get(), h->cv_uid.get(), h->cv_ucls.get(), h->cv_uxyz.get(), h->cv_udesc.get());
+  DVS_TRY(covis_block_offsets(h, h->cv_lm.flag.get(), nlm, &nblk));
+  hipLaunchKernelGGL(k_covis_lm_gather, dim3(nblk), dim3(256), 0, st, h->lm.view(), nlm, (const int*)h->cv_lm.flag.get(), (const i64*)h->cv_blk.offs.get(), want_desc ? 1 : 0,
+                     h->cv_lm.pos.get(), h->cv_lm.slot.get(), h->cv_lm.u.id.get(), h->cv_lm.u.cls.get(), h->cv_lm.u.xyz.get(), h->cv_lm.desc.get());
   DVS_HIP(hipGetLastError());
   i64 nu = 0;
   int nfix = 0;
   std::vector<int> fx((size_t)std::max(P.max_fixed, 1));
   const int take_f = want_window ? std::min(P.max_fixed, nkf) : 0;
   if (want_window) {                                   // f over U, ranked among the keyframes that are not free
-    hipLaunchKernelGGL(k_covis_count, dim3(1), dim3(256), (size_t)nkf * 4, st, nkf, (const int*)h->cv_uslot.get(), (const i64*)h->cv_blkoffs.get() + nblk,
-                       (const i64*)h->view_offs.get(), (const int*)h->cv_kf.get(), h->cv_f.get());
-    hipLaunchKernelGGL(k_covis_neighbours, dim3(1), dim3(256), 0, st, nkf, -1, (const int*)h->cv_f.get(), 1, (const int*)h->cv_role.get(), h->cv_nbt.get(), h->cv_nbi.get(),
-                       h->cv_nbw.get(), h->cv_nbc.get());
+    hipLaunchKernelGGL(k_covis_count, dim3(1), dim3(256), (size_t)nkf * 4, st, nkf, (const int*)h->cv_lm.slot.get(), (const i64*)h->cv_blk.offs.get() + nblk,
+                       (const i64*)h->v_lm.offs.get(), (const int*)h->cv_ob.kf.get(), h->cv_kf.f.get());
+    hipLaunchKernelGGL(k_covis_neighbours, dim3(1), dim3(256), 0, st, nkf, -1, (const int*)h->cv_kf.f.get(), 1, (const int*)h->cv_kf.role.get(), h->cv_w.nbt.get(), h->cv_w.nbi.get(),
+                       h->cv_w.nbw.get(), h->cv_kf.nbc.get());
     DVS_HIP(hipGetLastError());
-    if (take_f) DVS_HIP(hipMemcpyAsync(fx.data(), h->cv_nbi.get(), (size_t)take_f * 4, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(&nfix, h->cv_nbc.get(), 4, hipMemcpyDeviceToHost, st));
+    if (take_f) DVS_TRY(copy_out(fx.data(), h->cv_w.nbi, (size_t)take_f, st));
+    DVS_TRY(copy_out(&nfix, h->cv_kf.nbc, 1, st));
   }
-  DVS_HIP(hipMemcpyAsync(&nu, h->cv_blkoffs.get() + nblk, 8, hipMemcpyDeviceToHost, st));
+  DVS_HIP(hipMemcpyAsync(&nu, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
   DVS_HIP(hipStreamSynchronize(st));
   if (nu < 0 || nu > nlm || nfix < 0 || nfix > nkf) { set_error("covisibility: inconsistent counts %lld %d", (long long)nu, nfix); return DVS_ERR_HIP; }
   out->n_u = (int)nu;
@@ -400,21 +359,20 @@ dvs_status covis_local(dvs_backend* h, int r, const dvs_covis_params& P, bool wa
     if (role[(size_t)k]) { out->kf.push_back(k); out->fixed.push_back(role[(size_t)k] == 2 ? 1 : 0); out->weight.push_back(w[(size_t)k]); }
   if (!want_window || nob == 0) return DVS_OK;
   // the window's observations
-  int* sm = h->s_small.get();
-  DVS_HIP(hipMemcpyAsync(h->cv_role.get(), role.data(), (size_t)nkf * 4, hipMemcpyHostToDevice, st));
-  DVS_HIP(hipMemsetAsync(h->cv_oflag.get(), 0, (size_t)nob * 4, st));
-  DVS_HIP(hipMemsetAsync(sm + kLeft, 0, 4, st));
-  hipLaunchKernelGGL(k_covis_ob_flag, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, (const i64*)h->view_offs.get(), (const int*)h->view_kf.get(), (const int*)h->cv_kf.get(),
-                     (const int*)h->v_obs.get(), (const int*)h->cv_role.get(), (const int*)h->cv_lflag.get(), h->cv_oflag.get(), sm + kLeft);
-  DVS_TRY(covis_block_offsets(h, h->cv_oflag.get(), nob, &nblk));
-  hipLaunchKernelGGL(k_covis_ob_gather, dim3(nblk), dim3(256), 0, st, h->ob.view(), nob, (const int*)h->cv_oflag.get(), (const i64*)h->cv_blkoffs.get(),
-                     (const int*)h->ob_slot.get(), (const int*)h->cv_lpos.get(), h->cv_opx.get(), h->cv_olm.get(), h->cv_ocls.get(), h->cv_oframe.get(), h->cv_olmidx.get());
+  int* d_left = &h->s_small.get()->left_out;
+  DVS_HIP(hipMemcpyAsync(h->cv_kf.role.get(), role.data(), (size_t)nkf * sizeof(int), hipMemcpyHostToDevice, st));
+  DVS_HIP(hipMemsetAsync(h->cv_ob.flag.get(), 0, (size_t)nob * 4, st));
+  DVS_HIP(hipMemsetAsync(d_left, 0, 4, st));
+  hipLaunchKernelGGL(k_covis_ob_flag, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, (const i64*)h->v_lm.offs.get(), (const int*)h->v_ob.kf.get(), (const int*)h->cv_ob.kf.get(),
+                     (const int*)h->v_ob.rows.get(), (const int*)h->cv_kf.role.get(), (const int*)h->cv_lm.flag.get(), h->cv_ob.flag.get(), d_left);
+  DVS_TRY(covis_block_offsets(h, h->cv_ob.flag.get(), nob, &nblk));
+  hipLaunchKernelGGL(k_covis_ob_gather, dim3(nblk), dim3(256), 0, st, h->ob.view(), nob, (const int*)h->cv_ob.flag.get(), (const i64*)h->cv_blk.offs.get(),
+                     (const int*)h->v_ob.slot.get(), (const int*)h->cv_lm.pos.get(), h->cv_ob.o.px.get(), h->cv_ob.o.lm.get(), h->cv_ob.o.cls.get(), h->cv_ob.o.frame.get(), h->cv_ob.o.lmidx.get());
   DVS_HIP(hipGetLastError());
   i64 no = 0;
   int left = 0;
-  DVS_HIP(hipMemcpyAsync(&no, h->cv_blkoffs.get() + nblk, 8, hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipMemcpyAsync(&left, sm + kLeft, 4, hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipStreamSynchronize(st));
+  DVS_HIP(hipMemcpyAsync(&no, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
+  DVS_TRY(small_read(h, d_left, &left));
   if (no < 0 || no > nob || left < 0 || left > nob) { set_error("covisibility: inconsistent counts %lld %d", (long long)no, left); return DVS_ERR_HIP; }
   out->n_obs = (int)no; out->n_left = left;
   return DVS_OK;
@@ -435,18 +393,8 @@ dvs_status covis_window_host(dvs_backend* h, int r, const dvs_covis_params& P, W
   W->l_xyz.resize(3 * nl); W->l_id.resize(nl); W->l_cls.resize(nl);
   if (no == 0 && nl == 0) return DVS_OK;
   hipStream_t st = h->ctx->stream;
-  if (no) {
-    DVS_HIP(hipMemcpyAsync(W->o_px.data(), h->cv_opx.get(), no * 8, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(W->o_lm.data(), h->cv_olm.get(), no * 8, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(W->o_frame.data(), h->cv_oframe.get(), no * 8, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(W->o_cls.data(), h->cv_ocls.get(), no * 4, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(W->o_lmidx.data(), h->cv_olmidx.get(), no * 4, hipMemcpyDeviceToHost, st));
-  }
-  if (nl) {
-    DVS_HIP(hipMemcpyAsync(W->l_id.data(), h->cv_uid.get(), nl * 8, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(W->l_cls.data(), h->cv_ucls.get(), nl * 4, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipMemcpyAsync(W->l_xyz.data(), h->cv_uxyz.get(), nl * 12, hipMemcpyDeviceToHost, st));
-  }
+  DVS_TRY(window_copy_out(h->cv_ob.o, no, h->cv_lm.u, nl, W->o_px.data(), W->o_lm.data(), W->o_cls.data(), W->o_frame.data(), W->o_lmidx.data(), W->l_id.data(), W->l_cls.data(),
+                          W->l_xyz.data(), st));
   DVS_HIP(hipStreamSynchronize(st));
   return DVS_OK;
 }
@@ -470,7 +418,7 @@ dvs_status dvs::backend_local_map(dvs_backend* h, uint64_t ref_frame_id, const d
   DVS_TRY(covis_limit(h, "dvs_backend_track_frame_local"));
   LocalSet S;
   DVS_TRY(covis_local(h, r, P, false, true, &S));
-  *d_xyz = h->cv_uxyz.get(); *d_desc = h->cv_udesc.get(); *d_id = h->cv_uid.get(); *n = S.n_u;
+  *d_xyz = h->cv_lm.u.xyz.get(); *d_desc = h->cv_lm.desc.get(); *d_id = h->cv_lm.u.id.get(); *n = S.n_u;
   return DVS_OK;
 }
 
@@ -500,12 +448,12 @@ dvs_status dvs_backend_covisibility(dvs_backend* h, int32_t min_weight, int32_t 
   DVS_TRY(covis_grow(h, (size_t)nkf));
   DVS_TRY(covis_prepare(h));
   DVS_TRY(covis_rows(h, 0, nkf, min_weight));
-  launch_scan_counts(st, (const int*)h->cv_nbc.get(), nkf, h->cv_nboffs.get());
-  hipLaunchKernelGGL(k_covis_pack, dim3(nkf), dim3(256), 0, st, nkf, (const i64*)h->cv_nboffs.get(), (const int*)h->cv_nbi.get(), (const int*)h->cv_nbw.get(), h->cv_pki.get(),
-                     h->cv_pkw.get());
+  launch_scan_counts(st, (const int*)h->cv_kf.nbc.get(), nkf, h->cv_kf.nboffs.get());
+  hipLaunchKernelGGL(k_covis_pack, dim3(nkf), dim3(256), 0, st, nkf, (const i64*)h->cv_kf.nboffs.get(), (const int*)h->cv_w.nbi.get(), (const int*)h->cv_w.nbw.get(), h->cv_w.pki.get(),
+                     h->cv_w.pkw.get());
   DVS_HIP(hipGetLastError());
   i64 total = 0;
-  DVS_HIP(hipMemcpyAsync(&total, h->cv_nboffs.get() + nkf, 8, hipMemcpyDeviceToHost, st));
+  DVS_HIP(hipMemcpyAsync(&total, h->cv_kf.nboffs.get() + nkf, sizeof(i64), hipMemcpyDeviceToHost, st));
   DVS_HIP(hipStreamSynchronize(st));
   if (total < 0 || total > (i64)nkf * nkf) { set_error("dvs_backend_covisibility: inconsistent count %lld", (long long)total); return DVS_ERR_HIP; }
   *n_nb = total;
@@ -513,10 +461,8 @@ dvs_status dvs_backend_covisibility(dvs_backend* h, int32_t min_weight, int32_t 
     set_error("dvs_backend_covisibility: %d keyframes / %lld neighbours, capacities %d / %lld", nkf, (long long)total, cap_kf, (long long)cap_nb);
     return DVS_ERR_CAPACITY;
   }
-  if (weights) DVS_HIP(hipMemcpyAsync(weights, h->cv_w.get(), (size_t)nkf * (size_t)nkf * 4, hipMemcpyDeviceToHost, st));
-  if (nb_offsets) DVS_HIP(hipMemcpyAsync(nb_offsets, h->cv_nboffs.get(), ((size_t)nkf + 1) * 8, hipMemcpyDeviceToHost, st));
-  if (nb_index && total) DVS_HIP(hipMemcpyAsync(nb_index, h->cv_pki.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st));
-  if (nb_weight && total) DVS_HIP(hipMemcpyAsync(nb_weight, h->cv_pkw.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st));
+  DVS_TRY(copy_out(weights, h->cv_w.w, (size_t)nkf * (size_t)nkf, st)); DVS_TRY(copy_out(nb_offsets, h->cv_kf.nboffs, (size_t)nkf + 1, st));
+  if (total) { DVS_TRY(copy_out(nb_index, h->cv_w.pki, (size_t)total, st)); DVS_TRY(copy_out(nb_weight, h->cv_w.pkw, (size_t)total, st)); }
   DVS_HIP(hipStreamSynchronize(st));
   return DVS_OK;
 }

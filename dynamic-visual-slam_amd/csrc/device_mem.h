@@ -36,8 +36,47 @@ class Buf {
 template <class T> using DeviceBuf = Buf<T, false>;
 template <class T> using PinnedBuf = Buf<T, true>;
 
-// A block that only grows: kept while `need` elements fit in its `cap`, else freed first and allocated with a quarter to spare.  After
-// a failed allocation it is empty with cap 0, so the next call allocates again and the owner still frees once.
+// A device column of a table or of a row group: Per elements for every row, and Extra more behind the last row.  The type carries what
+// an allocation and a copy of `rows` rows need, so no caller writes a byte count.
+template <class T, int Per = 1, int Extra = 0>
+struct Column : DeviceBuf<T> {
+  dvs_status alloc_rows(size_t rows) { return this->alloc(rows * Per + Extra); }
+  static constexpr size_t row_bytes = Per * sizeof(T);
+};
+template <class... C>
+dvs_status alloc_rows(size_t rows, C&... cols) {   // in the order given; stops at the first failure
+  dvs_status s = DVS_OK;
+  (void)(... && ((s = cols.alloc_rows(rows)) == DVS_OK));
+  return s;
+}
+// `n` rows of a column to the host, enqueued; nothing for a null destination (an output the caller did not ask for)
+template <class D, class T, int Per, int Extra>
+dvs_status copy_out(D* dst, const Column<T, Per, Extra>& src, size_t n, hipStream_t st) {
+  static_assert(sizeof(D) == sizeof(T), "the destination's elements are the column's");
+  if (dst) DVS_HIP(hipMemcpyAsync(dst, src.get(), n * src.row_bytes, hipMemcpyDeviceToHost, st));
+  return DVS_OK;
+}
+
+// and `n` rows from the host into a column, enqueued
+template <class S, class T, int Per, int Extra>
+dvs_status copy_in(Column<T, Per, Extra>& dst, const S* src, size_t n, hipStream_t st) {
+  static_assert(sizeof(S) == sizeof(T), "the source's elements are the column's");
+  DVS_HIP(hipMemcpyAsync(dst.get(), src, n * dst.row_bytes, hipMemcpyHostToDevice, st));
+  return DVS_OK;
+}
+
+// A row group: columns that share a row count and only grow.  Kept while `need` rows fit in `cap`, else every column is freed and
+// allocated for `size` rows.  cap is zero from before the first allocation until the last one has succeeded: after a failure the group
+// counts as empty, so the next call allocates all of it again and every owner still frees once.
+template <class... C>
+dvs_status grow_rows(size_t& cap, size_t need, size_t size, C&... cols) {
+  if (need <= cap) return DVS_OK;
+  cap = 0;
+  DVS_TRY(alloc_rows(size, cols...));
+  cap = size;
+  return DVS_OK;
+}
+// The group of one block, with a quarter to spare.
 template <class T, bool Pinned>
 dvs_status grow(Buf<T, Pinned>& buf, size_t& cap, size_t need) {
   if (need <= cap) return DVS_OK;

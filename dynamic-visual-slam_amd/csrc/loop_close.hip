@@ -273,8 +273,6 @@ using namespace dvs;
 
 namespace {
 
-const int kCounts = 200;   // s_small [200, 208): {q observations, sources, targets, proposals, fused, kept rows, anchored}
-
 bool finite3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
 
 struct Graph {
@@ -336,21 +334,21 @@ bool fuse_params_ok(const dvs_fuse_params& p) {
          p.fuse_neighbours >= 0 && p.fuse_neighbours <= 31;   // at most 63 entry keyframes
 }
 
-// anchors of all landmarks into f_anchor, the number of anchored ones into s_small[kCounts + 6]; asynchronous on the handle's stream
+// anchors of all landmarks into f_anchor, the number of anchored ones into s_small's fuse.n_anchored; asynchronous on the handle's stream
 dvs_status anchors_build(dvs_backend* h) {
   hipStream_t st = h->ctx->stream;
   const int nlm = h->nlm;
   if (nlm == 0) return DVS_OK;
   DVS_TRY(backend_views_build(h));
   DVS_TRY(grow(h->f_anchor, h->c_flm, (size_t)nlm));
-  int* sm = h->s_small.get() + kCounts;
-  DVS_HIP(hipMemsetAsync(sm + 6, 0, 4, st));
-  hipLaunchKernelGGL(k_anchors, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, (const i64*)h->view_offs.get(), (const int*)h->view_kf.get(), h->f_anchor.get(), sm + 6);
+  int* n_anchored = &h->s_small.get()->fuse.n_anchored;
+  DVS_HIP(hipMemsetAsync(n_anchored, 0, 4, st));
+  hipLaunchKernelGGL(k_anchors, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, (const i64*)h->v_lm.offs.get(), (const int*)h->v_ob.kf.get(), h->f_anchor.get(), n_anchored);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
 
-// fusion over the keyframe indices q and E (checked by the caller); the pair list stays on the device in f_psurv / f_prem / f_pe
+// fusion over the keyframe indices q and E (checked by the caller); the pair list stays on the device in fuse_lm.psurv / .prem / .pe
 dvs_status fuse_run(dvs_backend* h, int q, const std::vector<int>& E, const dvs_fuse_params& P, bool apply, dvs_fuse_result* out, int32_t cap_pairs,
                     uint64_t* survivor_id, uint64_t* removed_id, double* err, int32_t* n_pairs) {
   memset(out, 0, sizeof(*out));
@@ -361,34 +359,22 @@ dvs_status fuse_run(dvs_backend* h, int q, const std::vector<int>& E, const dvs_
   hipStream_t st = h->ctx->stream;
   const KeyframeRec& K = h->kfs[(size_t)q];
   const int cap_q = (int)std::max<size_t>(K.obs_ids.size(), 1);
-  if ((size_t)nlm > h->c_frow) {                     // per landmark row
-    const size_t c = (size_t)nlm + (size_t)nlm / 2 + 1;
-    h->c_frow = 0;
-    DVS_TRY(h->f_flag.alloc(c)); DVS_TRY(h->f_src.alloc(c)); DVS_TRY(h->f_propb.alloc(c)); DVS_TRY(h->f_bsrc.alloc(c)); DVS_TRY(h->f_redirect.alloc(c));
-    DVS_TRY(h->f_partner.alloc(c)); DVS_TRY(h->f_prope.alloc(c)); DVS_TRY(h->f_beste.alloc(c)); DVS_TRY(h->f_psurv.alloc(c)); DVS_TRY(h->f_prem.alloc(c));
-    DVS_TRY(h->f_pe.alloc(c));
-    h->c_frow = c;
-  }
+  DVS_TRY(h->fuse_lm.grow((size_t)nlm));
   DVS_TRY(grow(h->f_obrow, h->c_fob, (size_t)nob));
-  if ((size_t)cap_q > h->c_fq) {
-    const size_t c = (size_t)cap_q + (size_t)cap_q / 4;
-    h->c_fq = 0;
-    DVS_TRY(h->f_qpx.alloc(c * 2)); DVS_TRY(h->f_qcls.alloc(c)); DVS_TRY(h->f_qoid.alloc(c)); DVS_TRY(h->f_qbrow.alloc(c)); DVS_TRY(h->f_qdesc.alloc(c * 32));
-    h->c_fq = c;
-  }
+  DVS_TRY(h->fuse_q.grow((size_t)cap_q));
   // keyframe roles ride in a_int
   h->h_int.assign((size_t)nkf, 0);
   for (int k : E) h->h_int[(size_t)k] = kRoleEntry;
   h->h_int[(size_t)q] = kRoleQuery;
   DVS_TRY(grow(h->a_int, h->c_aint, (size_t)nkf));
   DVS_HIP(hipMemcpyAsync(h->a_int.get(), h->h_int.data(), (size_t)nkf * 4, hipMemcpyHostToDevice, st));
-  int* sm = h->s_small.get() + kCounts;
-  DVS_HIP(hipMemsetAsync(sm, 0, 6 * 4, st));
-  DVS_HIP(hipMemsetAsync(h->f_flag.get(), 0, (size_t)nlm * 4, st));
-  DVS_HIP(hipMemsetAsync(h->f_beste.get(), 0xFF, (size_t)nlm * 8, st));
-  DVS_HIP(hipMemsetAsync(h->f_bsrc.get(), 0x7F, (size_t)nlm * 4, st));
-  DVS_HIP(hipMemsetAsync(h->f_redirect.get(), 0xFF, (size_t)nlm * 4, st));
-  DVS_HIP(hipMemsetAsync(h->f_partner.get(), 0xFF, (size_t)nlm * 4, st));
+  FuseCounts* fc = &h->s_small.get()->fuse;              // kernels take the record as ints from n_query on
+  DVS_HIP(hipMemsetAsync(fc, 0, offsetof(FuseCounts, n_anchored), st));
+  DVS_HIP(hipMemsetAsync(h->fuse_lm.flag.get(), 0, (size_t)nlm * 4, st));
+  DVS_HIP(hipMemsetAsync(h->fuse_lm.beste.get(), 0xFF, (size_t)nlm * 8, st));
+  DVS_HIP(hipMemsetAsync(h->fuse_lm.bsrc.get(), 0x7F, (size_t)nlm * 4, st));
+  DVS_HIP(hipMemsetAsync(h->fuse_lm.redirect.get(), 0xFF, (size_t)nlm * 4, st));
+  DVS_HIP(hipMemsetAsync(h->fuse_lm.partner.get(), 0xFF, (size_t)nlm * 4, st));
   FuseCam cam;
   memcpy(cam.R, K.R, 72); memcpy(cam.t, K.t, 24);
   cam.fx = h->P.fx; cam.fy = h->P.fy; cam.cx = h->P.cx; cam.cy = h->P.cy;
@@ -398,20 +384,19 @@ dvs_status fuse_run(dvs_backend* h, int q, const std::vector<int>& E, const dvs_
   const dim3 g_ob((nob + 255) / 256), g_lm((nlm + 255) / 256), b(256);
   const LmView lm = h->lm.view();
   const ObView ob = h->ob.view();
-  hipLaunchKernelGGL(k_fuse_mark, g_ob, b, 0, st, ob, nob, (const i64*)lm.id, nlm, (const int*)h->a_int.get(), nkf, h->f_obrow.get(), h->f_flag.get(), sm + 2);
-  hipLaunchKernelGGL(k_fuse_lists, dim3(1), b, 0, st, ob, nob, nlm, q, (const int*)h->f_obrow.get(), (const int*)h->f_flag.get(), cap_q, h->f_qpx.get(), h->f_qcls.get(),
-                     h->f_qoid.get(), h->f_qbrow.get(), h->f_qdesc.get(), h->f_src.get(), sm);
-  hipLaunchKernelGGL(k_fuse_propose, g_lm, b, 0, st, lm, (const int*)h->f_src.get(), (const int*)sm, cap_q, cam, (const float*)h->f_qpx.get(), (const int*)h->f_qcls.get(),
-                     (const i64*)h->f_qoid.get(), (const int*)h->f_qbrow.get(), (const uint8_t*)h->f_qdesc.get(), h->f_prope.get(), h->f_propb.get(), h->f_beste.get(), sm + 3);
-  hipLaunchKernelGGL(k_fuse_resolve, g_lm, b, 0, st, (const int*)h->f_src.get(), (const int*)sm, (const u64*)h->f_prope.get(), (const int*)h->f_propb.get(),
-                     (const u64*)h->f_beste.get(), h->f_bsrc.get());
-  hipLaunchKernelGGL(k_fuse_pairs, g_lm, b, 0, st, nlm, (const int*)h->f_flag.get(), (const int*)h->f_bsrc.get(), h->f_redirect.get(), h->f_partner.get());
-  hipLaunchKernelGGL(k_fuse_pairlist, dim3(1), b, 0, st, nlm, (const i64*)lm.id, (const int*)h->f_flag.get(), (const int*)h->f_redirect.get(), (const u64*)h->f_beste.get(),
-                     h->f_psurv.get(), h->f_prem.get(), h->f_pe.get(), sm + 4);
+  hipLaunchKernelGGL(k_fuse_mark, g_ob, b, 0, st, ob, nob, (const i64*)lm.id, nlm, (const int*)h->a_int.get(), nkf, h->f_obrow.get(), h->fuse_lm.flag.get(), &fc->n_targets);
+  hipLaunchKernelGGL(k_fuse_lists, dim3(1), b, 0, st, ob, nob, nlm, q, (const int*)h->f_obrow.get(), (const int*)h->fuse_lm.flag.get(), cap_q, h->fuse_q.px.get(), h->fuse_q.cls.get(),
+                     h->fuse_q.oid.get(), h->fuse_q.brow.get(), h->fuse_q.desc.get(), h->fuse_lm.src.get(), &fc->n_query);
+  hipLaunchKernelGGL(k_fuse_propose, g_lm, b, 0, st, lm, (const int*)h->fuse_lm.src.get(), (const int*)&fc->n_query, cap_q, cam, (const float*)h->fuse_q.px.get(), (const int*)h->fuse_q.cls.get(),
+                     (const i64*)h->fuse_q.oid.get(), (const int*)h->fuse_q.brow.get(), (const uint8_t*)h->fuse_q.desc.get(), h->fuse_lm.prope.get(), h->fuse_lm.propb.get(), h->fuse_lm.beste.get(), &fc->n_proposals);
+  hipLaunchKernelGGL(k_fuse_resolve, g_lm, b, 0, st, (const int*)h->fuse_lm.src.get(), (const int*)&fc->n_query, (const u64*)h->fuse_lm.prope.get(), (const int*)h->fuse_lm.propb.get(),
+                     (const u64*)h->fuse_lm.beste.get(), h->fuse_lm.bsrc.get());
+  hipLaunchKernelGGL(k_fuse_pairs, g_lm, b, 0, st, nlm, (const int*)h->fuse_lm.flag.get(), (const int*)h->fuse_lm.bsrc.get(), h->fuse_lm.redirect.get(), h->fuse_lm.partner.get());
+  hipLaunchKernelGGL(k_fuse_pairlist, dim3(1), b, 0, st, nlm, (const i64*)lm.id, (const int*)h->fuse_lm.flag.get(), (const int*)h->fuse_lm.redirect.get(), (const u64*)h->fuse_lm.beste.get(),
+                     h->fuse_lm.psurv.get(), h->fuse_lm.prem.get(), h->fuse_lm.pe.get(), &fc->n_fused);
   DVS_HIP(hipGetLastError());
-  int c[5] = {0, 0, 0, 0, 0};
-  DVS_HIP(hipMemcpyAsync(c, sm, sizeof(c), hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipStreamSynchronize(st));
+  int c[5] = {0, 0, 0, 0, 0};                          // n_query .. n_fused
+  DVS_TRY(small_read(h, &fc->n_query, c, 5));
   if (c[0] < 0 || c[0] > cap_q || c[1] < 0 || c[1] > nlm || c[4] < 0 || c[4] > c[3] || c[4] > c[2]) {
     set_error("dvs_backend_fuse: inconsistent counts %d %d %d %d %d (keyframe %d lists %d observations)", c[0], c[1], c[2], c[3], c[4], q, cap_q);
     return DVS_ERR_HIP;
@@ -422,18 +407,15 @@ dvs_status fuse_run(dvs_backend* h, int q, const std::vector<int>& E, const dvs_
   const bool want = survivor_id || removed_id || err;
   if (want && nf > cap_pairs) { set_error("dvs_backend_fuse: %d pairs, capacity %d", nf, cap_pairs); return DVS_ERR_CAPACITY; }
   if (want && nf) {
-    if (survivor_id) DVS_HIP(hipMemcpyAsync(survivor_id, h->f_psurv.get(), (size_t)nf * 8, hipMemcpyDeviceToHost, st));
-    if (removed_id) DVS_HIP(hipMemcpyAsync(removed_id, h->f_prem.get(), (size_t)nf * 8, hipMemcpyDeviceToHost, st));
-    if (err) DVS_HIP(hipMemcpyAsync(err, h->f_pe.get(), (size_t)nf * 8, hipMemcpyDeviceToHost, st));
+    DVS_TRY(copy_out(survivor_id, h->fuse_lm.psurv, (size_t)nf, st)); DVS_TRY(copy_out(removed_id, h->fuse_lm.prem, (size_t)nf, st)); DVS_TRY(copy_out(err, h->fuse_lm.pe, (size_t)nf, st));
   }
   if (apply && nf) {
-    if (h->lm_spare.cap != h->lm.cap) DVS_TRY(h->lm_spare.alloc(h->lm.cap));
-    hipLaunchKernelGGL(k_fuse_repoint, g_ob, b, 0, st, ob.lm, nob, (const int*)h->f_obrow.get(), (const int*)h->f_redirect.get(), (const i64*)lm.id);
-    hipLaunchKernelGGL(k_fuse_compact, dim3(1), b, 0, st, lm, nlm, (const int*)h->f_redirect.get(), (const int*)h->f_partner.get(), h->lm_spare.view(), sm + 5);
+    DVS_TRY(table_match_spare(h->lm_spare, h->lm));
+    hipLaunchKernelGGL(k_fuse_repoint, g_ob, b, 0, st, ob.lm, nob, (const int*)h->f_obrow.get(), (const int*)h->fuse_lm.redirect.get(), (const i64*)lm.id);
+    hipLaunchKernelGGL(k_fuse_compact, dim3(1), b, 0, st, lm, nlm, (const int*)h->fuse_lm.redirect.get(), (const int*)h->fuse_lm.partner.get(), h->lm_spare.view(), &fc->n_kept);
     DVS_HIP(hipGetLastError());
     int kept = -1;
-    DVS_HIP(hipMemcpyAsync(&kept, sm + 5, 4, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipStreamSynchronize(st));
+    DVS_TRY(small_read(h, &fc->n_kept, &kept));
     if (kept != nlm - nf) { set_error("dvs_backend_fuse: %d rows kept of %d with %d pairs", kept, nlm, nf); return DVS_ERR_HIP; }
     std::swap(h->lm, h->lm_spare);
     h->nlm = kept;
@@ -478,8 +460,7 @@ dvs_status dvs_backend_get_anchors(dvs_backend* h, int32_t cap, uint64_t* lm_id,
   DVS_HIP(hipSetDevice(h->device));
   hipStream_t st = h->ctx->stream;
   DVS_TRY(anchors_build(h));
-  if (lm_id) DVS_HIP(hipMemcpyAsync(lm_id, h->lm.id.get(), (size_t)h->nlm * 8, hipMemcpyDeviceToHost, st));
-  if (anchor_kf) DVS_HIP(hipMemcpyAsync(anchor_kf, h->f_anchor.get(), (size_t)h->nlm * 4, hipMemcpyDeviceToHost, st));
+  DVS_TRY(copy_out(lm_id, h->lm.id, (size_t)h->nlm, st)); DVS_TRY(copy_out(anchor_kf, h->f_anchor, (size_t)h->nlm, st));
   DVS_HIP(hipStreamSynchronize(st));
   return DVS_OK;
 }
@@ -544,14 +525,12 @@ dvs_status dvs_backend_close_loop(dvs_backend* h, dvs_pgo* pgo, int32_t n_loops,
   DVS_TRY(dvs_pgo_get_nodes(pgo, g.R.data(), g.t.data()));
   for (int k = 0; k < nkf; k++) { memcpy(h->kfs[(size_t)k].R, &g.R[9 * (size_t)k], 72); memcpy(h->kfs[(size_t)k].t, &g.t[3 * (size_t)k], 24); }
   DVS_HIP(hipSetDevice(h->device));
-  DVS_HIP(hipMemcpyAsync(h->kf_R.get(), g.R.data(), (size_t)nkf * 72, hipMemcpyHostToDevice, st));
-  DVS_HIP(hipMemcpyAsync(h->kf_t.get(), g.t.data(), (size_t)nkf * 24, hipMemcpyHostToDevice, st));
+  DVS_TRY(copy_in(h->kf_R, g.R.data(), (size_t)nkf, st)); DVS_TRY(copy_in(h->kf_t, g.t.data(), (size_t)nkf, st));
   // landmarks: in place on the table's xyz column with the device anchors
   if (h->nlm) {
     DVS_TRY(anchors_build(h));
     int moved = 0;
-    DVS_HIP(hipMemcpyAsync(&moved, h->s_small.get() + kCounts + 6, 4, hipMemcpyDeviceToHost, st));
-    DVS_HIP(hipStreamSynchronize(st));
+    DVS_TRY(small_read(h, &h->s_small.get()->fuse.n_anchored, &moved));
     out->n_landmarks_moved = moved;
     DVS_TRY(dvs_pgo_correct_points_device(pgo, h->nlm, h->lm.xyz.get(), h->f_anchor.get()));
     DVS_TRY(dvs_pgo_synchronize(pgo));

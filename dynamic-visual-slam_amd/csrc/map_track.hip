@@ -444,18 +444,13 @@ struct dvs_maptrack {
   // per cell: [cnt ncell | fill ncell | counters MC_INTS] cleared by one memset per call, and the CSR row starts
   DeviceBuf<int> cells, start;
   // per keypoint (grow-only)
-  DeviceBuf<int> cellid, arrival, order, kp_lm, kp_dist;
-  DeviceBuf<long long> kp_id;
-  DeviceBuf<unsigned long long> key;
-  DeviceBuf<uint8_t> kp_inl;
+  Column<int> cellid, arrival, order, kp_lm, kp_dist; Column<long long> kp_id; Column<unsigned long long> key; Column<uint8_t> kp_inl;
   size_t c_kp = 0;
   // per landmark (grow-only)
   DeviceBuf<MtRec> rec;
   size_t c_lm = 0;
   // the correspondences of the refinement (grow-only)
-  DeviceBuf<double> cX, cpx;
-  DeviceBuf<int> coct, ckp;
-  DeviceBuf<uint8_t> cinl;
+  Column<double, 3> cX; Column<double, 2> cpx; Column<int> coct, ckp; Column<uint8_t> cinl;
   size_t c_corr = 0;
   DeviceBuf<dvs_maptrack_result> d_res;
   // staging of the host form (grow-only)
@@ -476,22 +471,9 @@ static int* mt_fill(dvs_maptrack* h) { return h->cells.get() + h->ncell; }
 static int* mt_counters(dvs_maptrack* h) { return h->cells.get() + 2 * (size_t)h->ncell; }
 
 static dvs_status mt_grow_kp(dvs_maptrack* h, size_t n) {
-  if (n <= h->c_kp) return DVS_OK;
-  h->c_kp = 0;
-  const size_t c = n + n / 4;
-  DVS_TRY(h->cellid.alloc(c)); DVS_TRY(h->arrival.alloc(c)); DVS_TRY(h->order.alloc(c)); DVS_TRY(h->kp_lm.alloc(c)); DVS_TRY(h->kp_dist.alloc(c));
-  DVS_TRY(h->kp_id.alloc(c)); DVS_TRY(h->key.alloc(c)); DVS_TRY(h->kp_inl.alloc(c));
-  h->c_kp = c;
-  return DVS_OK;
+  return grow_rows(h->c_kp, n, n + n / 4, h->cellid, h->arrival, h->order, h->kp_lm, h->kp_dist, h->kp_id, h->key, h->kp_inl);
 }
-static dvs_status mt_grow_corr(dvs_maptrack* h, size_t n) {
-  if (n <= h->c_corr) return DVS_OK;
-  h->c_corr = 0;
-  const size_t c = n + n / 4;
-  DVS_TRY(h->cX.alloc(c * 3)); DVS_TRY(h->cpx.alloc(c * 2)); DVS_TRY(h->coct.alloc(c)); DVS_TRY(h->ckp.alloc(c)); DVS_TRY(h->cinl.alloc(c));
-  h->c_corr = c;
-  return DVS_OK;
-}
+static dvs_status mt_grow_corr(dvs_maptrack* h, size_t n) { return grow_rows(h->c_corr, n, n + n / 4, h->cX, h->cpx, h->coct, h->ckp, h->cinl); }
 
 static dvs_status mt_check_search_args(const dvs_maptrack* h, const void* xyz, const void* ldesc, int n_lm, const void* kps, const void* kdesc, int n_kp) {
   DVS_ARG(h && n_lm >= 0 && n_kp >= 0 && n_lm <= (1 << 30) && n_kp <= (1 << 30));

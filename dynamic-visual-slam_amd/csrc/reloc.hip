@@ -139,13 +139,10 @@ struct dvs_reloc {
   dvs_matcher* ctx = nullptr;      // the stream, RANSAC's scratch and the pinned block; works on the legacy default stream until set_stream
   DeviceBuf<int> counters;         // RC_INTS
   // per landmark (grow-only): the two nearest keypoints and the state
-  DeviceBuf<int> top_idx, top_dist;
-  DeviceBuf<signed char> state;
+  Column<int, 2> top_idx, top_dist; Column<signed char> state;
   size_t c_lm = 0;
   // per keypoint (grow-only): the proposal keys and the list
-  DeviceBuf<unsigned long long> key;
-  DeviceBuf<float> obj, img;
-  DeviceBuf<int> p_lm, p_kp, p_dist, p_inl;
+  Column<unsigned long long> key; Column<float, 3> obj; Column<float, 2> img; Column<int> p_lm, p_kp, p_dist, p_inl;
   size_t c_kp = 0;
   DeviceBuf<unsigned char> pnp64;
   DeviceBuf<RlRec> d_rec;
@@ -160,23 +157,8 @@ struct dvs_reloc {
   unsigned char last_pnp[64] = {0};   // stage 4's record as it came back (zeros when nothing was solved)
 };
 
-static dvs_status rl_grow_kp(dvs_reloc* h, size_t n) {
-  if (n <= h->c_kp) return DVS_OK;
-  h->c_kp = 0;
-  const size_t c = n + n / 4;
-  DVS_TRY(h->key.alloc(c)); DVS_TRY(h->obj.alloc(c * 3)); DVS_TRY(h->img.alloc(c * 2)); DVS_TRY(h->p_lm.alloc(c)); DVS_TRY(h->p_kp.alloc(c));
-  DVS_TRY(h->p_dist.alloc(c)); DVS_TRY(h->p_inl.alloc(c));
-  h->c_kp = c;
-  return DVS_OK;
-}
-static dvs_status rl_grow_lm(dvs_reloc* h, size_t n) {
-  if (n <= h->c_lm) return DVS_OK;
-  h->c_lm = 0;
-  const size_t c = n + n / 4;
-  DVS_TRY(h->top_idx.alloc(c * 2)); DVS_TRY(h->top_dist.alloc(c * 2)); DVS_TRY(h->state.alloc(c));
-  h->c_lm = c;
-  return DVS_OK;
-}
+static dvs_status rl_grow_kp(dvs_reloc* h, size_t n) { return grow_rows(h->c_kp, n, n + n / 4, h->key, h->obj, h->img, h->p_lm, h->p_kp, h->p_dist, h->p_inl); }
+static dvs_status rl_grow_lm(dvs_reloc* h, size_t n) { return grow_rows(h->c_lm, n, n + n / 4, h->top_idx, h->top_dist, h->state); }
 
 static dvs_status rl_check_args(const dvs_reloc* h, const dvs_maptrack* mt, const void* xyz, const void* ldesc, int n_lm, const void* kps, const void* kdesc,
                                 int n_kp, const void* result) {
