@@ -1,5 +1,5 @@
-// backend_internal.h — the mapping backend handle (dvs_backend, include/dvslam_hip.h) shared by backend.hip, loop_close.hip and
-// covisibility.hip: the views of the landmark and observation tables that kernels take, the owners of the tables, the keyframe record,
+// backend_internal.h — the mapping backend handle (dvs_backend, include/dvslam_hip.h) shared by backend.hip, loop_close.hip,
+// covisibility.hip and kf_cull.hip: the views of the landmark and observation tables that kernels take, the owners of the tables, the keyframe record,
 // the counter block, the row groups of per-call scratch and the handle itself.  Internal to the library, as loop_internal.h and
 // bow_internal.h are.
 #pragma once
@@ -83,19 +83,23 @@ struct KeyframeRec { uint64_t frame_id; i64 stamp; std::vector<uint64_t> obs_ids
 // The 256 ints of counters and small lists that kernels write and the host reads back, one block per handle (dvs_backend::s_small).
 // add_keyframe uploads the whole block: its two lists, and zeros everywhere else.
 struct FuseCounts { int n_query, n_sources, n_targets, n_proposals, n_fused, n_kept, n_anchored, pad; };   // n_anchored: k_anchors, cleared on its own
+struct CullCounts { int n_culled, n_ob_removed, n_lm_removed, pad; };   // k_cull_walk; k_cull_ob_flag; k_cull_lm_flag
 struct BackendSmall {
-  int filtered[64];      // add_keyframe: the filtered class ids
+  int filtered[64];     // add_keyframe: the filtered class ids
   int classes[64];       //               the distinct unfiltered classes of the keyframe
   int class_cnt[64];     //               k_categorize: kept observations per class
   int counts[4];         // the call's one-block kernel: k_class_gather {landmarks of the class}, k_window_gather {observations, landmarks},
                          // k_prune_compact {landmarks kept, observations kept, observations removed}
   int marked, pad0[3];   // k_prune_mark: marked landmarks
   FuseCounts fuse;       // loop_close.hip
-  int left_out, pad1[47];   // covisibility.hip, k_covis_ob_flag: rows left out of the local window
+  int left_out, pad1[3];    // covisibility.hip, k_covis_ob_flag: rows left out of the local window
+  CullCounts cull;          // kf_cull.hip
+  int pad2[40];
 };
 static_assert(sizeof(BackendSmall) == 256 * 4 && offsetof(BackendSmall, classes) == 64 * 4 && offsetof(BackendSmall, class_cnt) == 128 * 4 &&
               offsetof(BackendSmall, counts) == 192 * 4 && offsetof(BackendSmall, marked) == 196 * 4 && offsetof(BackendSmall, fuse) == 200 * 4 &&
               offsetof(BackendSmall, fuse.n_anchored) == 206 * 4 && offsetof(BackendSmall, left_out) == 208 * 4, "kernels and the upload keep these addresses");
+static_assert(offsetof(BackendSmall, cull) == 212 * 4, "the culling counters take the padding behind left_out");
 
 // The eight columns a BA window hands out, in two halves by row domain; the sliding window and the local window each hold both.
 struct WindowObs { Column<float, 2> px; Column<i64> lm; Column<int> cls; Column<i64> frame; Column<int> lmidx; };
@@ -184,6 +188,22 @@ struct CovisWeightRows {  // requested rows x keyframes: weights and neighbour l
   size_t cap = 0;
   dvs_status grow(size_t n) { return grow_rows(cap, n, n, w, nbt, nbi, nbw, pki, pkw); }
 };
+struct CullKfRows {       // culling per keyframe, one row more for the scan's end: scope and protection from the host, n_k, the initial R_k, initially
+                          // redundant candidates and their list, culled and kept flags, index in the table after the apply
+  Column<uint8_t> state; Column<int> n_obs, r0, flag, walk, culled, keep; Column<i64> newidx;
+  size_t cap = 0;
+  dvs_status grow(size_t nkf) { return grow_rows(cap, nkf + 1, nkf + 1 + nkf / 2, state, n_obs, r0, flag, walk, culled, keep, newidx); }
+};
+struct CullLmRows {       // culling per landmark row: c(L), removed rows, stays in the table
+  Column<int> c, removed, keep;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, c, removed, keep); }
+};
+struct CullObRows {       // culling per observation row: stays in the table
+  Column<int> keep;
+  size_t cap = 0;
+  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2 + 64, keep); }
+};
 
 }  // namespace dvs
 
@@ -208,6 +228,7 @@ struct dvs_backend {
   dvs::PruneLmRows prune_lm; dvs::PruneObRows prune_ob;
   dvs::FuseLmRows fuse_lm; dvs::FuseQueryRows fuse_q;
   dvs::CovisObRows cv_ob; dvs::CovisKfRows cv_kf; dvs::CovisLmRows cv_lm; dvs::CovisBlockRows cv_blk; dvs::CovisWeightRows cv_w;
+  dvs::CullKfRows cull_kf; dvs::CullLmRows cull_lm; dvs::CullObRows cull_ob;
   // single blocks (device_mem.h, grow): detections, candidate pairs, per-call arguments, anchors per landmark, landmark row per observation
   dvs::DeviceBuf<dvs::DetRec> s_det; dvs::DeviceBuf<dvs::PairRec> p_rec; dvs::DeviceBuf<int> a_int, f_obrow; dvs::Column<int> f_anchor; dvs::DeviceBuf<dvs::i64> a_i64; dvs::DeviceBuf<double> a_dbl;
   size_t c_det = 0, c_pair = 0, c_aint = 0, c_ai64 = 0, c_adbl = 0, c_flm = 0, c_fob = 0;
@@ -238,4 +259,16 @@ dvs_status backend_views_build(dvs_backend* h);
 // argument errors of the section are returned before any device work.
 dvs_status backend_local_map(dvs_backend* h, uint64_t ref_frame_id, const dvs_covis_params* params, const float** d_xyz, const uint8_t** d_desc,
                              const i64** d_id, int* n);
+// What covisibility.hip shares with kf_cull.hip, all enqueued on the handle's stream:
+// DVS_ERR_CAPACITY if the map holds more keyframes than the row kernel's LDS histogram takes
+dvs_status covis_limit(const dvs_backend* h, const char* who);
+// the covisibility row groups for the keyframes and tables as they stand and `rows` rows of weights
+dvs_status covis_grow(dvs_backend* h, size_t rows);
+// the views CSR, the counting views (cv_ob.kf: the keyframe where a view counts, or -1) and the keyframe -> landmarks CSR (cv_kf.offs,
+// cv_ob.list); needs at least one landmark and one keyframe
+dvs_status covis_prepare(dvs_backend* h);
+// `rows` rows of W from keyframe row0 on into cv_w.w, and their neighbour lists at theta into cv_w.nbi / cv_w.nbw / cv_kf.nbc
+dvs_status covis_rows(dvs_backend* h, int row0, int rows, int theta);
+// the ordered compaction's steps 1 and 2 over n flags (flag == 1: the row stays): cv_blk.offs[0 .. *nblk], the total last
+dvs_status covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk);
 }  // namespace dvs

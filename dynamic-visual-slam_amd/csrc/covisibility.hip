@@ -231,7 +231,10 @@ dvs_status covis_check(const dvs_covis_params& P) {
   return DVS_OK;
 }
 
-dvs_status covis_limit(const dvs_backend* h, const char* who) {
+}  // namespace
+
+// covis_limit, covis_grow, covis_prepare, covis_rows and covis_block_offsets are shared with kf_cull.hip (backend_internal.h)
+dvs_status dvs::covis_limit(const dvs_backend* h, const char* who) {
   if (h->kfs.size() > (size_t)DVS_COVIS_MAX_KEYFRAMES) {
     set_error("%s: %zu keyframes, the row kernel's LDS histogram takes %d", who, h->kfs.size(), DVS_COVIS_MAX_KEYFRAMES);
     return DVS_ERR_CAPACITY;
@@ -240,7 +243,7 @@ dvs_status covis_limit(const dvs_backend* h, const char* who) {
 }
 
 // scratch for nkf keyframes, the tables as they stand and `rows` rows of weights
-dvs_status covis_grow(dvs_backend* h, size_t rows) {
+dvs_status dvs::covis_grow(dvs_backend* h, size_t rows) {
   const size_t nkf = h->kfs.size(), nlm = (size_t)h->nlm, nob = (size_t)h->nob;
   DVS_TRY(h->cv_ob.grow(nob)); DVS_TRY(h->cv_kf.grow(nkf)); DVS_TRY(h->cv_lm.grow(nlm));
   DVS_TRY(h->cv_blk.grow(std::max(nlm, nob) / 256 + 2));
@@ -248,7 +251,7 @@ dvs_status covis_grow(dvs_backend* h, size_t rows) {
 }
 
 // the views CSR, the counting views and the keyframe -> landmarks CSR, enqueued; needs at least one landmark and one keyframe
-dvs_status covis_prepare(dvs_backend* h) {
+dvs_status dvs::covis_prepare(dvs_backend* h) {
   hipStream_t st = h->ctx->stream;
   const int nkf = (int)h->kfs.size(), nlm = h->nlm;
   DVS_TRY(backend_views_build(h));
@@ -265,7 +268,7 @@ dvs_status covis_prepare(dvs_backend* h) {
 }
 
 // `rows` rows of W from keyframe row0 on into cv_w.w, and their neighbour lists at theta into cv_w.nbi / cv_w.nbw / cv_kf.nbc
-dvs_status covis_rows(dvs_backend* h, int row0, int rows, int theta) {
+dvs_status dvs::covis_rows(dvs_backend* h, int row0, int rows, int theta) {
   hipStream_t st = h->ctx->stream;
   const int nkf = (int)h->kfs.size();
   hipLaunchKernelGGL(k_covis_row, dim3(rows), dim3(256), (size_t)nkf * 4, st, nkf, row0, (const i64*)h->cv_kf.offs.get(), (const int*)h->cv_ob.list.get(),
@@ -277,7 +280,7 @@ dvs_status covis_rows(dvs_backend* h, int row0, int rows, int theta) {
 }
 
 // ordered compaction's steps 1 and 2 over n flags: cv_blkoffs[0 .. nblk], the total last
-dvs_status covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk) {
+dvs_status dvs::covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk) {
   hipStream_t st = h->ctx->stream;
   *nblk = (n + 255) / 256;
   if (*nblk) hipLaunchKernelGGL(k_covis_blk_count, dim3(*nblk), dim3(256), 0, st, flag, n, h->cv_blk.cnt.get());
@@ -285,6 +288,8 @@ dvs_status covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
+
+namespace {
 
 struct LocalSet {
   std::vector<int> kf;            // the window's keyframes, ascending index (without want_window: the free keyframes)

@@ -61,6 +61,17 @@ class LocalBaResult(C.Structure):
                 ("n_left_out", C.c_int32), ("n_dropped", C.c_int32)]
 
 
+class CullParams(C.Structure):
+    """dvs_cull_params (fill it with dvs_cull_default_params)"""
+    _fields_ = [(k, C.c_int32) for k in ("min_observers", "redundancy_percent", "min_weight", "local", "keep_recent", "max_cull", "drop_orphans", "reserved")]
+
+
+class CullResult(C.Structure):
+    """dvs_cull_result"""
+    _fields_ = [(k, C.c_int32) for k in ("n_keyframes", "n_candidates", "n_redundant_initial", "n_culled", "n_observations_removed", "n_landmarks_removed")] + \
+               [("reserved", C.c_int32 * 2)]
+
+
 def _bind(L):
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
     pi32, pi64 = C.POINTER(i32), C.POINTER(i64)
@@ -89,6 +100,8 @@ def _bind(L):
     L.dvs_backend_covisibility.argtypes = [vp, i32, i32, i64, vp, vp, vp, vp, pi32, pi64]
     L.dvs_backend_get_local_window.argtypes = [vp, u64, pcv, i32, i32, i32, vp, vp, vp, vp, vp, pi32, vp, vp, vp, vp, vp, pi32, vp, vp, vp, pi32, pi32]
     L.dvs_backend_local_ba.argtypes = [vp, vp, u64, pcv, C.POINTER(LocalBaResult)]
+    L.dvs_cull_default_params.argtypes = [C.POINTER(CullParams)]; L.dvs_cull_default_params.restype = None
+    L.dvs_backend_cull_keyframes.argtypes = [vp, u64, C.POINTER(CullParams), vp, i32, i32, C.POINTER(CullResult), i32, vp, vp, vp, vp, pi32]
     return L
 
 
@@ -109,6 +122,17 @@ def covis_params(**kw):
     _bind(lib()).dvs_covis_default_params(C.byref(p))
     for k, v in kw.items():
         if k not in dict(CovisParams._fields_):
+            raise TypeError(f"unknown parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def cull_params(**kw):
+    """dvs_cull_default_params with field overrides"""
+    p = CullParams()
+    _bind(lib()).dvs_cull_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(CullParams._fields_) or k == "reserved":
             raise TypeError(f"unknown parameter {k}")
         setattr(p, k, v)
     return p
@@ -420,6 +444,26 @@ class MappingBackend:
                                                     C.byref(r)))
         return r.as_dict()
 
+    # ---- keyframe culling (include/dvslam_hip.h "Keyframe culling")
+    def cull_keyframes(self, ref_frame_id=None, protected=(), apply=True, **params):
+        """dvs_backend_cull_keyframes: redundant keyframes leave the map (apply=False: a dry run that only reports).  ref_frame_id None: every
+        keyframe is in scope; else only the covisibility neighbours of that keyframe at min_weight.  protected: frame ids that are never culled.
+        params: the fields of dvs_cull_params but `local`.  -> dict of the fields of dvs_cull_result plus culled_frame_id (uint64, ascending
+        index) and, per keyframe in table order before the call, kf_observed, kf_redundant (int32) and kf_state (uint8: 0 out of scope,
+        1 protected, 2 kept, 3 culled)"""
+        if "local" in params:
+            raise TypeError("local follows from ref_frame_id")
+        p = cull_params(local=0 if ref_frame_id is None else 1, **params)
+        prot = np.array([int(f) for f in protected], np.uint64)
+        n = max(self.counts()["n_keyframes"], 1)
+        fid = np.zeros(n, np.uint64); seen = np.zeros(n, np.int32); red = np.zeros(n, np.int32); state = np.zeros(n, np.uint8)
+        r = CullResult(); nk = C.c_int32()
+        check(self._L.dvs_backend_cull_keyframes(self._h, 0 if ref_frame_id is None else int(ref_frame_id), C.byref(p), ptr(prot) if len(prot) else None, len(prot),
+                                                 1 if apply else 0, C.byref(r), n, ptr(fid), ptr(seen), ptr(red), ptr(state), C.byref(nk)))
+        out = {k: int(getattr(r, k)) for k, _ in CullResult._fields_ if k != "reserved"}
+        out.update(culled_frame_id=fid[:r.n_culled], kf_observed=seen[:nk.value], kf_redundant=red[:nk.value], kf_state=state[:nk.value])
+        return out
+
     def reset(self):
         check(self._L.dvs_backend_reset(self._h))
 
@@ -435,4 +479,4 @@ class MappingBackend:
             pass
 
 
-__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "CovisParams", "LocalBaResult", "covis_params", "default_params", "fuse_params", "DvsError"]
+__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "CovisParams", "LocalBaResult", "covis_params", "CullParams", "CullResult", "cull_params", "default_params", "fuse_params", "DvsError"]

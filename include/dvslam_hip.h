@@ -1513,7 +1513,8 @@ dvs_status dvs_tracker_get_filtered_features(dvs_tracker* h, dvs_keypoint* kps, 
  * than DVS_COVIS_MAX_KEYFRAMES keyframes is refused with DVS_ERR_CAPACITY by every call of this section.
  * DVS_ERR_ARG before any device work: min_weight < 1, max_neighbours outside 0..62, max_fixed outside 0..63, max_neighbours + 1 +
  * max_fixed > 64 (the device solver's camera limit), ba_max_iterations < 1, an unknown ref_frame_id.
- * Out of scope: covisibility edges in the pose graph, keyframe culling, a cached graph, scale and viewing-angle conditions, several GPUs. */
+ * Out of scope: covisibility edges in the pose graph, a cached graph, scale and viewing-angle conditions, several GPUs.  Removing redundant
+ * keyframes is the next section, "Keyframe culling". */
 #define DVS_COVIS_MAX_KEYFRAMES 8192
 typedef struct dvs_covis_params {
   int32_t min_weight;          /* 15: theta */
@@ -1559,6 +1560,66 @@ dvs_status dvs_backend_local_ba(dvs_backend* h, dvs_ba* ba, uint64_t ref_frame_i
 dvs_status dvs_backend_track_frame_local(dvs_backend* h, dvs_maptrack* mt, uint64_t ref_frame_id, const dvs_covis_params* params /* NULL: defaults */,
                                          const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3,
                                          dvs_maptrack_result* result);
+
+/* ======================================= Keyframe culling ================================= */
+/* Redundant keyframes leave the map the backend keeps on the device (csrc/kf_cull.hip; INTEGRATION.md "Keyframe culling"): a keyframe goes
+ * when almost everything it sees is seen well enough by others — the idea of ORB-SLAM's KeyFrameCulling (Mur-Artal, Montiel, Tardos 2015,
+ * section VI-E) as published, not its code.  PARITY UNPINNED: the reference has no counterpart; the rule is the library's own, defined over
+ * the tables as the getters return them BEFORE the call, stated here in full and restated with Python sets in tests/keyframe_culling_ref.py.
+ * Observes, S_k and the neighbour lists N(a; theta) are exactly those of "Covisibility": two rows of one keyframe naming one landmark count
+ * once, and a row naming a landmark the table does not hold counts nowhere.
+ *  Observers  c(L) = the number of keyframes that observe L.
+ *  Redundancy for keyframe k: n_k = |S_k|; R_k = the number of L in S_k with c(L) - 1 >= min_observers; k is REDUNDANT iff n_k >= 1 and
+ *             100 * R_k > redundancy_percent * n_k, evaluated in 64-bit integers with a strict >.
+ *  Protected  never culled: the keyframe at index 0 (the gauge of sliding, local and global BA); the last keep_recent keyframes in table
+ *             order; every keyframe named in protected_frame_ids; ref_frame_id itself in local scope.
+ *  Scope      local == 0: every keyframe is in scope and ref_frame_id is not read.  local != 0: only the keyframes of N(ref; min_weight)
+ *             are in scope — the whole list, not truncated by any max_neighbours.
+ *  Candidates the keyframes that are in scope and not protected.
+ *  Walk       SEQUENTIAL, which is what makes the rule safe: candidates are visited in ascending table index; at its turn k is tested with
+ *             the CURRENT c(.); if it is redundant it is CULLED and c(L) -= 1 for every L in S_k before the next candidate is tested.  The
+ *             walk stops early when max_cull > 0 and that many keyframes have been culled.  A one-shot test of all candidates against the
+ *             initial counts is NOT this rule: it can remove every observer of a landmark.
+ *  Report     per keyframe in table order before the call: kf_observed = n_k; kf_redundant = R_k from the INITIAL counts, for every
+ *             keyframe whatever its state; kf_state: 1 = protected, else 0 = out of scope, else 3 = culled, else 2 = kept.
+ *             culled_frame_id: the culled keyframes' frame ids in ascending index (the first out->n_culled entries).
+ *  Apply      (apply != 0 and at least one keyframe culled)
+ *             Observation rows  every row whose keyframe is culled leaves the observation table by ordered compaction: the other rows keep
+ *                               their order and every column.
+ *             Landmarks         observation_count drops by the number of removed rows naming the landmark, never below 0.  With
+ *                               drop_orphans != 0 a landmark that had at least one row before the call and has none after it leaves the
+ *                               landmark table, again by ordered compaction.  Position, descriptor and last_seen of those that stay are
+ *                               untouched.
+ *             Keyframes         the culled keyframes leave the keyframe list and the poses, order kept; the kept keyframes'
+ *                               observation_ids are untouched; both id counters are untouched.
+ *             If nothing is culled, or apply == 0, the map stays byte for byte as it was.
+ * Every quantity is an integer and every order is total: two identical calls on identical maps give identical bytes.
+ * DVS_ERR_ARG before any device work: min_observers < 1, redundancy_percent outside 0..99, min_weight < 1, keep_recent < 0, max_cull < 0,
+ * n_protected < 0, an unknown protected or (local scope) reference frame id.  DVS_ERR_CAPACITY: more than DVS_COVIS_MAX_KEYFRAMES keyframes
+ * when local != 0 (the row kernel's limit); count-then-capacity as everywhere: *n_kf is always set, and if an output array is given with
+ * cap_kf < *n_kf nothing is computed and nothing is applied.  An empty map returns DVS_OK with zeros.
+ * Out of scope: scale and viewing-angle conditions (the observation table has no octave), time-spacing conditions, removing entries from a
+ * dvs_loop database (the caller does that with culled_frame_id), a cached graph, several GPUs. */
+typedef struct dvs_cull_params {
+  int32_t min_observers;       /* 3 */
+  int32_t redundancy_percent;  /* 90 */
+  int32_t min_weight;          /* 15: theta; read only when local != 0 */
+  int32_t local;               /* 0 */
+  int32_t keep_recent;         /* 2 */
+  int32_t max_cull;            /* 0: no limit */
+  int32_t drop_orphans;        /* 1 */
+  int32_t reserved;
+} dvs_cull_params;             /* 32 bytes */
+typedef struct dvs_cull_result {
+  int32_t n_keyframes, n_candidates, n_redundant_initial, n_culled;   /* n_redundant_initial: over every keyframe, whatever its state */
+  int32_t n_observations_removed, n_landmarks_removed, reserved[2];   /* what apply removes, also in a dry run */
+} dvs_cull_result;             /* 32 bytes */
+void dvs_cull_default_params(dvs_cull_params* p);
+/* out and the four arrays are nullable; each array takes *n_kf entries (culled_frame_id: out->n_culled of them are written). */
+dvs_status dvs_backend_cull_keyframes(dvs_backend* h, uint64_t ref_frame_id, const dvs_cull_params* params /* NULL: defaults */,
+                                      const uint64_t* protected_frame_ids, int32_t n_protected, int32_t apply, dvs_cull_result* out,
+                                      int32_t cap_kf, uint64_t* culled_frame_id, int32_t* kf_observed, int32_t* kf_redundant,
+                                      uint8_t* kf_state, int32_t* n_kf);
 
 /* ======================================= Relocalisation ================================= */
 /* A frame's pose in the map WITHOUT a prior (csrc/reloc.hip; INTEGRATION.md "Relocalisation"): what recovers a tracker after a tracking
