@@ -1,5 +1,5 @@
 // backend_internal.h — the mapping backend handle (dvs_backend, include/dvslam_hip.h) shared by backend.hip, loop_close.hip,
-// covisibility.hip and kf_cull.hip: the views of the landmark and observation tables that kernels take, the owners of the tables, the keyframe record,
+// covisibility.hip, kf_cull.hip and landmark_refresh.hip: the views of the landmark and observation tables that kernels take, the owners of the tables, the keyframe record,
 // the counter block, the row groups of per-call scratch and the handle itself.  Internal to the library, as loop_internal.h and
 // bow_internal.h are.
 #pragma once
@@ -84,6 +84,7 @@ struct KeyframeRec { uint64_t frame_id; i64 stamp; std::vector<uint64_t> obs_ids
 // add_keyframe uploads the whole block: its two lists, and zeros everywhere else.
 struct FuseCounts { int n_query, n_sources, n_targets, n_proposals, n_fused, n_kept, n_anchored, pad; };   // n_anchored: k_anchors, cleared on its own
 struct CullCounts { int n_culled, n_ob_removed, n_lm_removed, pad; };   // k_cull_walk; k_cull_ob_flag; k_cull_lm_flag
+struct RefreshCounts { int n_bin[3], n_in_scope, n_without_views, max_views, n_changed, pad; };   // k_lr_bin; n_changed: k_lr_apply
 struct BackendSmall {
   int filtered[64];     // add_keyframe: the filtered class ids
   int classes[64];       //               the distinct unfiltered classes of the keyframe
@@ -94,12 +95,14 @@ struct BackendSmall {
   FuseCounts fuse;       // loop_close.hip
   int left_out, pad1[3];    // covisibility.hip, k_covis_ob_flag: rows left out of the local window
   CullCounts cull;          // kf_cull.hip
-  int pad2[40];
+  RefreshCounts refresh;    // landmark_refresh.hip
+  int pad2[32];
 };
 static_assert(sizeof(BackendSmall) == 256 * 4 && offsetof(BackendSmall, classes) == 64 * 4 && offsetof(BackendSmall, class_cnt) == 128 * 4 &&
               offsetof(BackendSmall, counts) == 192 * 4 && offsetof(BackendSmall, marked) == 196 * 4 && offsetof(BackendSmall, fuse) == 200 * 4 &&
               offsetof(BackendSmall, fuse.n_anchored) == 206 * 4 && offsetof(BackendSmall, left_out) == 208 * 4, "kernels and the upload keep these addresses");
 static_assert(offsetof(BackendSmall, cull) == 212 * 4, "the culling counters take the padding behind left_out");
+static_assert(offsetof(BackendSmall, refresh) == 216 * 4, "and the refresh counters the padding behind them");
 
 // The eight columns a BA window hands out, in two halves by row domain; the sliding window and the local window each hold both.
 struct WindowObs { Column<float, 2> px; Column<i64> lm; Column<int> cls; Column<i64> frame; Column<int> lmidx; };
@@ -204,6 +207,12 @@ struct CullObRows {       // culling per observation row: stays in the table
   size_t cap = 0;
   dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2 + 64, keep); }
 };
+struct RefreshLmRows {    // landmark refresh per landmark row: views, in scope; the three bins' lists; the chosen view (index into the views), its
+                          // median and observation id; the viewing geometry
+  Column<int> n, scope, list0, list1, list2, best, med, ncnt; Column<i64> oid; Column<double, 3> normal; Column<double, 2> range;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, n, scope, list0, list1, list2, best, med, ncnt, oid, normal, range); }
+};
 
 }  // namespace dvs
 
@@ -229,6 +238,7 @@ struct dvs_backend {
   dvs::FuseLmRows fuse_lm; dvs::FuseQueryRows fuse_q;
   dvs::CovisObRows cv_ob; dvs::CovisKfRows cv_kf; dvs::CovisLmRows cv_lm; dvs::CovisBlockRows cv_blk; dvs::CovisWeightRows cv_w;
   dvs::CullKfRows cull_kf; dvs::CullLmRows cull_lm; dvs::CullObRows cull_ob;
+  dvs::RefreshLmRows lr_lm;
   // single blocks (device_mem.h, grow): detections, candidate pairs, per-call arguments, anchors per landmark, landmark row per observation
   dvs::DeviceBuf<dvs::DetRec> s_det; dvs::DeviceBuf<dvs::PairRec> p_rec; dvs::DeviceBuf<int> a_int, f_obrow; dvs::Column<int> f_anchor; dvs::DeviceBuf<dvs::i64> a_i64; dvs::DeviceBuf<double> a_dbl;
   size_t c_det = 0, c_pair = 0, c_aint = 0, c_ai64 = 0, c_adbl = 0, c_flm = 0, c_fob = 0;
@@ -271,4 +281,7 @@ dvs_status covis_prepare(dvs_backend* h);
 dvs_status covis_rows(dvs_backend* h, int row0, int rows, int theta);
 // the ordered compaction's steps 1 and 2 over n flags (flag == 1: the row stays): cv_blk.offs[0 .. *nblk], the total last
 dvs_status covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk);
+// the viewing geometry of every landmark row ("Landmark refresh" in the header; landmark_refresh.hip) into lr_lm.normal / .range / .ncnt:
+// the views are rebuilt, everything is enqueued on the handle's stream; needs at least one landmark
+dvs_status refresh_geometry(dvs_backend* h);
 }  // namespace dvs

@@ -29,7 +29,9 @@ namespace dvs {
 struct MtPose { double Rcw[9], tcw[3], R[9], t[3]; };   // the prior both ways: the kernels compute with the first, return the bytes of the second
 struct MtRec { double u, v; int visible, best_k, d_best, d_second, proposed, kept; };   // dvs_maptrack_lm_record
 static_assert(sizeof(MtRec) == sizeof(dvs_maptrack_lm_record), "record layout");
-enum { MC_VISIBLE = 0, MC_PROPOSED = 1, MC_MATCHES = 2, MC_UNBINNED = 3, MC_INTS = 8 };
+enum { MC_VISIBLE = 0, MC_PROPOSED = 1, MC_MATCHES = 2, MC_UNBINNED = 3, MC_GATE = 4, MC_INTS = 8 };   // MC_GATE .. + 3: near, far, back-facing, angle
+// "Landmark refresh" in the header: the per-landmark viewing geometry and the gates' constants; read by k_mt_search<true> only
+struct MtGateArgs { const double* normal; const double* range; const int* ncnt; double range_factor, cc; };
 constexpr unsigned long long kNoKey = ~0ull;
 constexpr int kRefThreads = 256, kSums = 28;   // 21 of H's upper triangle, 6 of b, the cost
 
@@ -98,7 +100,9 @@ __device__ __forceinline__ void mt_camera_point(const MtPose& T, double X0, doub
   for (int i = 0; i < 3; i++) c[i] = ((T.Rcw[3 * i] * X0 + T.Rcw[3 * i + 1] * X1) + T.Rcw[3 * i + 2] * X2) + T.tcw[i];
 }
 
-__global__ __launch_bounds__(256) void k_mt_search(dvs_maptrack_params P, MtPose T, const float* __restrict__ xyz, const uint8_t* __restrict__ ldesc, int n_lm,
+// kGated is a template argument, so the ungated instantiation holds none of the gates' code
+template <bool kGated>
+__global__ __launch_bounds__(256) void k_mt_search(dvs_maptrack_params P, MtPose T, MtGateArgs g, const float* __restrict__ xyz, const uint8_t* __restrict__ ldesc, int n_lm,
                                                    const dvs_keypoint* __restrict__ kps, const uint8_t* __restrict__ kdesc, const int* __restrict__ start,
                                                    const int* __restrict__ order, int gw, int gh, MtRec* __restrict__ rec,
                                                    unsigned long long* __restrict__ key, int* __restrict__ counters) {
@@ -109,6 +113,16 @@ __global__ __launch_bounds__(256) void k_mt_search(dvs_maptrack_params P, MtPose
   MtRec r;
   r.u = 0.0; r.v = 0.0; r.visible = 0; r.best_k = -1; r.d_best = -1; r.d_second = -1; r.proposed = 0; r.kept = 0;
   bool vis = P.min_z < c[2] && c[2] < P.max_z;
+  if (kGated) {
+    if (g.ncnt[j] > 0) {
+      const double p0 = (double)xyz[3 * (size_t)j] - T.t[0], p1 = (double)xyz[3 * (size_t)j + 1] - T.t[1], p2 = (double)xyz[3 * (size_t)j + 2] - T.t[2];
+      const double q = (p0 * p0 + p1 * p1) + p2 * p2;
+      const double s = (p0 * g.normal[3 * (size_t)j] + p1 * g.normal[3 * (size_t)j + 1]) + p2 * g.normal[3 * (size_t)j + 2];
+      const double a = g.range[2 * (size_t)j] / g.range_factor, b = g.range[2 * (size_t)j + 1] * g.range_factor;
+      const int gate = q < a * a ? 0 : (q > b * b ? 1 : (s < 0.0 ? 2 : (s * s < g.cc * q ? 3 : -1)));
+      if (gate >= 0) { vis = false; atomicAdd(&counters[MC_GATE + gate], 1); }
+    }
+  }
   double u = 0.0, v = 0.0;
   if (vis) {
     u = P.fx * c[0] / c[2] + P.cx;
@@ -484,7 +498,7 @@ static dvs_status mt_check_search_args(const dvs_maptrack* h, const void* xyz, c
 }
 
 // stages 1-3, enqueued; arguments checked by the caller
-static dvs_status mt_search(dvs_maptrack* h, const MtPose& T, const float* d_xyz, const uint8_t* d_ldesc, const int64_t* d_id, int n_lm, const dvs_keypoint* d_kps,
+static dvs_status mt_search(dvs_maptrack* h, const MtPose& T, const MtGateArgs* gate, const float* d_xyz, const uint8_t* d_ldesc, const int64_t* d_id, int n_lm, const dvs_keypoint* d_kps,
                             const uint8_t* d_kdesc, int n_kp) {
   DVS_HIP(hipSetDevice(h->device));
   hipStream_t st = h->stream;
@@ -504,9 +518,12 @@ static dvs_status mt_search(dvs_maptrack* h, const MtPose& T, const float* d_xyz
     hipLaunchKernelGGL(k_mt_order, dim3(gk), dim3(256), 0, st, (const int*)h->cellid.get(), (const int*)h->arrival.get(), (const int*)h->start.get(), h->ncell,
                        h->order.get());
   }
-  if (n_lm > 0)
-    hipLaunchKernelGGL(k_mt_search, dim3(gl), dim3(256), 0, st, P, T, d_xyz, d_ldesc, n_lm, d_kps, d_kdesc, (const int*)h->start.get(), (const int*)h->order.get(),
-                       h->gw, h->gh, h->rec.get(), h->key.get(), mt_counters(h));
+  if (n_lm > 0 && gate)
+    hipLaunchKernelGGL(k_mt_search<true>, dim3(gl), dim3(256), 0, st, P, T, *gate, d_xyz, d_ldesc, n_lm, d_kps, d_kdesc, (const int*)h->start.get(),
+                       (const int*)h->order.get(), h->gw, h->gh, h->rec.get(), h->key.get(), mt_counters(h));
+  else if (n_lm > 0)
+    hipLaunchKernelGGL(k_mt_search<false>, dim3(gl), dim3(256), 0, st, P, T, MtGateArgs{nullptr, nullptr, nullptr, 0.0, 0.0}, d_xyz, d_ldesc, n_lm, d_kps, d_kdesc,
+                       (const int*)h->start.get(), (const int*)h->order.get(), h->gw, h->gh, h->rec.get(), h->key.get(), mt_counters(h));
   if (n_kp > 0)
     hipLaunchKernelGGL(k_mt_finalize, dim3(gk), dim3(256), 0, st, (const unsigned long long*)h->key.get(), n_kp, (const long long*)d_id, h->rec.get(),
                        h->kp_lm.get(), h->kp_id.get(), h->kp_dist.get(), h->kp_inl.get(), mt_counters(h));
@@ -550,7 +567,28 @@ static dvs_status mt_refine_explicit(dvs_maptrack* h, const double* d_X, const d
   return mt_read_result(h, result);
 }
 
+// the gated calls' extra arguments ("Landmark refresh" in the header): ranges checked, the constants formed once
+static dvs_status mt_gate_args(const dvs_maptrack_gates* gates, const double* d_normal, const double* d_range, const int32_t* d_ncnt, int n_lm, MtGateArgs* g) {
+  dvs_maptrack_gates G;
+  if (gates) G = *gates; else dvs_mapgate_default_gates(&G);
+  DVS_ARG(G.cos_min >= 0.0 && G.cos_min <= 1.0 && __builtin_isfinite(G.range_factor) && G.range_factor >= 1.0);
+  DVS_ARG(n_lm <= 0 || (d_normal && d_range && d_ncnt));
+  DVS_ARG(((uintptr_t)d_normal & 7) == 0 && ((uintptr_t)d_range & 7) == 0 && ((uintptr_t)d_ncnt & 3) == 0);
+  g->normal = d_normal; g->range = d_range; g->ncnt = d_ncnt; g->range_factor = G.range_factor; g->cc = G.cos_min * G.cos_min;
+  return DVS_OK;
+}
+// the bodies the ungated and the gated entry points share (gate NULL: ungated)
+static dvs_status mt_search_call(dvs_maptrack* h, const MtGateArgs* gate, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                 const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result);
+static dvs_status mt_track_call(dvs_maptrack* h, const MtGateArgs* gate, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result);
+
 extern "C" {
+
+void dvs_mapgate_default_gates(dvs_maptrack_gates* g) {
+  if (!g) return;
+  g->cos_min = 0.5; g->range_factor = 2.0;
+}
 
 void dvs_maptrack_default_params(dvs_maptrack_params* p) {
   if (!p) return;
@@ -605,10 +643,24 @@ dvs_status dvs_maptrack_set_stream(dvs_maptrack* h, void* hip_stream) {
 dvs_status dvs_maptrack_search_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
                                       const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3,
                                       dvs_maptrack_result* result) {
+  return mt_search_call(h, nullptr, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp, R9, t3, result);
+}
+
+dvs_status dvs_mapgate_search_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                     const double* d_lm_normal, const double* d_lm_range, const int32_t* d_lm_ncounted,
+                                     const dvs_maptrack_gates* gates, const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp,
+                                     const double* R9, const double* t3, dvs_maptrack_result* result) {
+  MtGateArgs g;
+  DVS_TRY(mt_gate_args(gates, d_lm_normal, d_lm_range, d_lm_ncounted, n_lm, &g));
+  return mt_search_call(h, &g, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp, R9, t3, result);
+}
+
+static dvs_status mt_search_call(dvs_maptrack* h, const MtGateArgs* gate, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                 const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result) {
   DVS_TRY(mt_check_search_args(h, d_lm_xyz, d_lm_desc, n_lm, d_kps, d_desc, n_kp));
   MtPose T;
   DVS_TRY(maptrack_pose(R9, t3, &T));
-  DVS_TRY(mt_search(h, T, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp));
+  DVS_TRY(mt_search(h, T, gate, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp));
   if (!result) return DVS_OK;
   hipLaunchKernelGGL(k_mt_search_record, dim3(1), dim3(64), 0, h->stream, T, (const int*)mt_counters(h), h->d_res.get());
   DVS_HIP(hipGetLastError());
@@ -623,6 +675,30 @@ dvs_status dvs_maptrack_refine_device(dvs_maptrack* h, const double* d_X, const 
 dvs_status dvs_maptrack_track_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
                                      const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3,
                                      dvs_maptrack_result* result) {
+  return mt_track_call(h, nullptr, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp, R9, t3, result);
+}
+
+dvs_status dvs_mapgate_track_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                    const double* d_lm_normal, const double* d_lm_range, const int32_t* d_lm_ncounted,
+                                    const dvs_maptrack_gates* gates, const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp,
+                                    const double* R9, const double* t3, dvs_maptrack_result* result) {
+  MtGateArgs g;
+  DVS_TRY(mt_gate_args(gates, d_lm_normal, d_lm_range, d_lm_ncounted, n_lm, &g));
+  return mt_track_call(h, &g, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp, R9, t3, result);
+}
+
+dvs_status dvs_mapgate_get_counts(dvs_maptrack* h, int32_t out[4]) {
+  DVS_ARG(h && out);
+  memset(out, 0, 4 * sizeof(int32_t));
+  if (!h->last_search) return DVS_OK;                  // the counters are those of a search
+  DVS_HIP(hipSetDevice(h->device));
+  DVS_HIP(hipMemcpyAsync(out, mt_counters(h) + MC_GATE, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  DVS_HIP(hipStreamSynchronize(h->stream));
+  return DVS_OK;
+}
+
+static dvs_status mt_track_call(dvs_maptrack* h, const MtGateArgs* gate, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result) {
   DVS_TRY(mt_check_search_args(h, d_lm_xyz, d_lm_desc, n_lm, d_kps, d_desc, n_kp));
   DVS_ARG(result);
   MtPose T;
@@ -630,7 +706,7 @@ dvs_status dvs_maptrack_track_device(dvs_maptrack* h, const float* d_lm_xyz, con
   DVS_HIP(hipSetDevice(h->device));
   if ((size_t)n_kp > h->c_corr) DVS_HIP(hipStreamSynchronize(h->stream));
   DVS_TRY(mt_grow_corr(h, (size_t)n_kp));   // a keypoint keeps at most one landmark
-  DVS_TRY(mt_search(h, T, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp));
+  DVS_TRY(mt_search(h, T, gate, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp));
   MtGather G; G.kp_lm = h->kp_lm.get(); G.xyz = d_lm_xyz; G.kps = d_kps; G.n_kp = n_kp; G.gather = 1;
   MtCorr C; C.X = h->cX.get(); C.px = h->cpx.get(); C.oct = h->coct.get(); C.kp = h->ckp.get(); C.inl = h->cinl.get();
   hipLaunchKernelGGL(k_mt_refine<false>, dim3(1), dim3(kRefThreads), 0, h->stream, h->P, T, G, C, 0, h->kp_inl.get(), h->kp_lm.get(), h->kp_id.get(), h->kp_dist.get(),
@@ -705,6 +781,22 @@ dvs_status dvs_backend_track_frame(dvs_backend* h, dvs_maptrack* mt, const dvs_k
   DVS_HIP(hipSetDevice(h->device));
   DVS_HIP(hipStreamSynchronize(h->ctx->stream));   // the table as the backend's last call left it
   return dvs_maptrack_track_device(mt, h->lm.xyz.get(), h->lm.desc.get(), (const int64_t*)h->lm.id.get(), h->nlm, d_kps, d_desc, n_kp, R9, t3, result);
+}
+
+// the same with the gates of "Landmark refresh": landmark_refresh.hip computes the geometry of the table as it stands into the backend's scratch
+dvs_status dvs_backend_track_frame_gated(dvs_backend* h, dvs_maptrack* mt, const dvs_maptrack_gates* gates, const dvs_keypoint* d_kps, const uint8_t* d_desc,
+                                         int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result) {
+  DVS_ARG(h && mt && result && h->device == mt->device);
+  DVS_TRY(mt_check_search_args(mt, h->lm.xyz.get(), h->lm.desc.get(), h->nlm, d_kps, d_desc, n_kp));
+  MtPose T;
+  DVS_TRY(maptrack_pose(R9, t3, &T));
+  MtGateArgs g;
+  DVS_TRY(mt_gate_args(gates, nullptr, nullptr, nullptr, 0, &g));
+  DVS_HIP(hipSetDevice(h->device));
+  if (h->nlm > 0) DVS_TRY(dvs::refresh_geometry(h));
+  DVS_HIP(hipStreamSynchronize(h->ctx->stream));   // the table as the backend's last call left it, and its geometry
+  g.normal = h->lr_lm.normal.get(); g.range = h->lr_lm.range.get(); g.ncnt = h->lr_lm.ncnt.get();
+  return mt_track_call(mt, &g, h->lm.xyz.get(), h->lm.desc.get(), (const int64_t*)h->lm.id.get(), h->nlm, d_kps, d_desc, n_kp, R9, t3, result);
 }
 
 // the same against the local map of one keyframe ("Covisibility" in the header): covisibility.hip compacts U's columns on the device

@@ -755,6 +755,19 @@ dvs_status dvs_tracker_track_map(dvs_tracker* h, dvs_backend* backend, dvs_maptr
   return DVS_OK;
 }
 
+// include/dvslam_hip.h "Landmark refresh": the same through the gated call
+dvs_status dvs_tracker_track_map_gated(dvs_tracker* h, dvs_backend* backend, dvs_maptrack* mt, const dvs_maptrack_gates* gates, int32_t apply,
+                                       dvs_maptrack_result* result) {
+  DVS_ARG(h && backend && mt && result && backend->device == h->device);
+  if (!h->prev_valid) { set_error("dvs_tracker_track_map_gated: no frame has been tracked"); return DVS_ERR_EMPTY; }
+  DVS_HIP(hipSetDevice(h->device));
+  DVS_HIP(hipStreamSynchronize(h->ctx->stream));
+  const int q = 1 - h->p;
+  DVS_TRY(dvs_backend_track_frame_gated(backend, mt, gates, h->f_k[q].get(), h->f_d[q].get(), h->prev_n, h->R, h->tt, result));
+  if (apply && result->status == DVS_MAPTRACK_OK) { memcpy(h->R, result->R, sizeof(h->R)); memcpy(h->tt, result->t, sizeof(h->tt)); }
+  return DVS_OK;
+}
+
 // include/dvslam_hip.h "Relocalisation": that set against the backend's landmark table with no prior; the tracker itself launches nothing here.
 // After a frame with tracking_reset the set may be empty: FEW_PAIRS, not an error
 dvs_status dvs_tracker_relocalize(dvs_tracker* h, dvs_backend* backend, dvs_reloc* reloc, dvs_maptrack* mt, int32_t apply, dvs_reloc_result* result) {

@@ -72,6 +72,21 @@ class CullResult(C.Structure):
                [("reserved", C.c_int32 * 2)]
 
 
+class LmRefreshParams(C.Structure):
+    """dvs_lm_refresh_params (fill it with dvs_lm_refresh_default_params)"""
+    _fields_ = [("update_descriptors", C.c_int32), ("min_views", C.c_int32), ("use_scope", C.c_int32), ("reserved", C.c_int32), ("scope_frame_id", C.c_uint64)]
+
+
+class LmRefreshResult(C.Structure):
+    """dvs_lm_refresh_result"""
+    _fields_ = [(k, C.c_int32) for k in ("n_in_scope", "n_changed", "n_without_views", "max_views")]
+
+
+class MapTrackGates(C.Structure):
+    """dvs_maptrack_gates (fill it with dvs_mapgate_default_gates)"""
+    _fields_ = [("cos_min", C.c_double), ("range_factor", C.c_double)]
+
+
 def _bind(L):
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
     pi32, pi64 = C.POINTER(i32), C.POINTER(i64)
@@ -102,6 +117,11 @@ def _bind(L):
     L.dvs_backend_local_ba.argtypes = [vp, vp, u64, pcv, C.POINTER(LocalBaResult)]
     L.dvs_cull_default_params.argtypes = [C.POINTER(CullParams)]; L.dvs_cull_default_params.restype = None
     L.dvs_backend_cull_keyframes.argtypes = [vp, u64, C.POINTER(CullParams), vp, i32, i32, C.POINTER(CullResult), i32, vp, vp, vp, vp, pi32]
+    L.dvs_lm_refresh_default_params.argtypes = [C.POINTER(LmRefreshParams)]; L.dvs_lm_refresh_default_params.restype = None
+    L.dvs_mapgate_default_gates.argtypes = [C.POINTER(MapTrackGates)]; L.dvs_mapgate_default_gates.restype = None
+    L.dvs_backend_refresh_landmarks.argtypes = [vp, C.POINTER(LmRefreshParams), C.POINTER(LmRefreshResult)]
+    L.dvs_backend_get_landmark_geometry.argtypes = [vp, i32, vp, vp, vp, vp, vp, pi32]
+    L.dvs_backend_track_frame_gated.argtypes = [vp, vp, C.POINTER(MapTrackGates), vp, vp, i32, vp, vp, vp]
     return L
 
 
@@ -136,6 +156,30 @@ def cull_params(**kw):
             raise TypeError(f"unknown parameter {k}")
         setattr(p, k, v)
     return p
+
+
+def lm_refresh_params(scope_frame_id=None, **kw):
+    """dvs_lm_refresh_default_params with field overrides; scope_frame_id None: the whole table"""
+    p = LmRefreshParams()
+    _bind(lib()).dvs_lm_refresh_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("update_descriptors", "min_views"):
+            raise TypeError(f"unknown parameter {k}")
+        setattr(p, k, int(v))
+    if scope_frame_id is not None:
+        p.use_scope, p.scope_frame_id = 1, int(scope_frame_id)
+    return p
+
+
+def maptrack_gates(**kw):
+    """dvs_mapgate_default_gates with field overrides"""
+    g = MapTrackGates()
+    _bind(lib()).dvs_mapgate_default_gates(C.byref(g))
+    for k, v in kw.items():
+        if k not in dict(MapTrackGates._fields_):
+            raise TypeError(f"unknown parameter {k}")
+        setattr(g, k, float(v))
+    return g
 
 
 def _loop_arrays(loops):
@@ -464,6 +508,38 @@ class MappingBackend:
         out.update(culled_frame_id=fid[:r.n_culled], kf_observed=seen[:nk.value], kf_redundant=red[:nk.value], kf_state=state[:nk.value])
         return out
 
+    # ---- landmark refresh (include/dvslam_hip.h "Landmark refresh")
+    def refresh_landmarks(self, scope_frame_id=None, **params):
+        """dvs_backend_refresh_landmarks: every landmark in scope (scope_frame_id None: the whole table; else the landmarks that keyframe
+        observes) gets the descriptor of the view with the smallest median distance to its other views.  params: update_descriptors,
+        min_views.  -> dict of the fields of dvs_lm_refresh_result"""
+        p = lm_refresh_params(scope_frame_id, **params)
+        r = LmRefreshResult()
+        check(self._L.dvs_backend_refresh_landmarks(self._h, C.byref(p), C.byref(r)))
+        return {k: int(getattr(r, k)) for k, _ in LmRefreshResult._fields_}
+
+    def landmark_geometry(self):
+        """dvs_backend_get_landmark_geometry, a dry run over the whole table -> dict(normal (n, 3) float64, range (n, 2) float64 (dmin, dmax),
+        n_counted int32, best_obs_id uint64, best_median int32), rows as landmarks()"""
+        nn = C.c_int32()
+        check(self._L.dvs_backend_get_landmark_geometry(self._h, 0, None, None, None, None, None, C.byref(nn)))
+        n = nn.value
+        c = max(n, 1)
+        normal = np.zeros((c, 3)); rng = np.zeros((c, 2)); cnt = np.zeros(c, np.int32); oid = np.zeros(c, np.uint64); med = np.zeros(c, np.int32)
+        check(self._L.dvs_backend_get_landmark_geometry(self._h, c, ptr(normal), ptr(rng), ptr(cnt), ptr(oid), ptr(med), C.byref(nn)))
+        return dict(normal=normal[:n], range=rng[:n], n_counted=cnt[:n], best_obs_id=oid[:n], best_median=med[:n])
+
+    def track_frame_gated(self, map_tracker, d_kps, d_desc, n_kp, R, t, **gates):
+        """dvs_backend_track_frame_gated: track_frame with the distance and viewing-angle gates (gates: cos_min, range_factor); the geometry
+        is computed for the table as it stands; map_tracker.gate_counts() then tells what each gate removed"""
+        from . import map_track as M
+        M._bind(self._L)
+        g = maptrack_gates(**gates)
+        R = np.ascontiguousarray(R, np.float64).reshape(9); t = np.ascontiguousarray(t, np.float64).reshape(3)
+        r = M.MapTrackResult()
+        check(self._L.dvs_backend_track_frame_gated(self._h, map_tracker.handle, C.byref(g), M._raw(d_kps), M._raw(d_desc), int(n_kp), ptr(R), ptr(t), C.byref(r)))
+        return r.as_dict()
+
     def reset(self):
         check(self._L.dvs_backend_reset(self._h))
 
@@ -479,4 +555,4 @@ class MappingBackend:
             pass
 
 
-__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "CovisParams", "LocalBaResult", "covis_params", "CullParams", "CullResult", "cull_params", "default_params", "fuse_params", "DvsError"]
+__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "CovisParams", "LocalBaResult", "covis_params", "CullParams", "CullResult", "cull_params", "LmRefreshParams", "LmRefreshResult", "MapTrackGates", "lm_refresh_params", "maptrack_gates", "default_params", "fuse_params", "DvsError"]

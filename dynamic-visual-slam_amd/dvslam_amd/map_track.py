@@ -47,6 +47,10 @@ def _bind(L):
     L.dvs_backend_track_frame_local.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, i32, vp, vp, pr]
     L.dvs_tracker_track_map.argtypes = [vp, vp, vp, i32, pr]
     L.dvs_tracker_get_filtered_features.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
+    L.dvs_mapgate_search_device.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, pr]
+    L.dvs_mapgate_track_device.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, pr]
+    L.dvs_mapgate_get_counts.argtypes = [vp, vp]
+    L.dvs_tracker_track_map_gated.argtypes = [vp, vp, vp, vp, i32, pr]
     if hasattr(L, "dvs_test_maptrack_landmarks"):
         L.dvs_test_maptrack_landmarks.argtypes = [vp, i32, vp, C.POINTER(i32)]
         L.dvs_test_maptrack_cells.argtypes = [vp, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]
@@ -131,6 +135,31 @@ class MapTracker:
         check(self._L.dvs_maptrack_track_device(self._h, _raw(d_xyz), _raw(d_ldesc), _raw(d_ids), n_lm, _raw(d_kps), _raw(d_kdesc), n_kp, ptr(R), ptr(t),
                                                 C.byref(r)))
         return r.as_dict()
+
+    def _gated(self, fn, d_xyz, d_ldesc, d_ids, n_lm, d_normal, d_range, d_ncounted, d_kps, d_kdesc, n_kp, R, t, gates, want):
+        from .backend import maptrack_gates
+        g = maptrack_gates(**gates)
+        R, t = _pose(R, t)
+        r = MapTrackResult()
+        check(fn(self._h, _raw(d_xyz), _raw(d_ldesc), _raw(d_ids), n_lm, _raw(d_normal), _raw(d_range), _raw(d_ncounted), C.byref(g), _raw(d_kps), _raw(d_kdesc),
+                 n_kp, ptr(R), ptr(t), C.byref(r) if want else None))
+        return r.as_dict() if want else None
+
+    def search_gated(self, d_xyz, d_ldesc, d_ids, n_lm, d_normal, d_range, d_ncounted, d_kps, d_kdesc, n_kp, R, t, want_counts=True, **gates):
+        """search_device with the gates of "Landmark refresh": d_normal n_lm x 3 and d_range n_lm x 2 doubles, d_ncounted n_lm int32 on the
+        device; gates: cos_min, range_factor"""
+        return self._gated(self._L.dvs_mapgate_search_device, d_xyz, d_ldesc, d_ids, n_lm, d_normal, d_range, d_ncounted, d_kps, d_kdesc, n_kp, R, t, gates,
+                           want_counts)
+
+    def track_gated(self, d_xyz, d_ldesc, d_ids, n_lm, d_normal, d_range, d_ncounted, d_kps, d_kdesc, n_kp, R, t, **gates):
+        """track_device with the gates"""
+        return self._gated(self._L.dvs_mapgate_track_device, d_xyz, d_ldesc, d_ids, n_lm, d_normal, d_range, d_ncounted, d_kps, d_kdesc, n_kp, R, t, gates, True)
+
+    def gate_counts(self):
+        """what the last call's gates removed -> int32 [near, far, back-facing, angle]"""
+        out = np.zeros(4, np.int32)
+        check(self._L.dvs_mapgate_get_counts(self._h, ptr(out)))
+        return out
 
     def track(self, xyz, ldesc, ids, kps, kdesc, R, t):
         """host form: xyz float32 (n_lm, 3), ldesc uint8 (n_lm, 32), ids int64 ascending or None, kps KP_DTYPE, kdesc uint8 (n_kp, 32)"""

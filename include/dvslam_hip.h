@@ -1416,8 +1416,8 @@ dvs_status dvs_backend_global_ba(dvs_backend* h, dvs_ba* ba, const dvs_ba_global
  *            it is R = R_cw^T, t[i] = -((R_cw[i] * t_cw[0] + R_cw[3 + i] * t_cw[1]) + R_cw[6 + i] * t_cw[2]), converted once at the end.
  *            cost = sum of chi_i over the final inliers at the final pose (0 unless the four rounds ran).  Every status is DVS_OK.
  * All four rounds run inside ONE kernel of one call; no host decision is taken between iterations; one 128-byte record comes back.
- * Out of scope: predicted octave and viewing-angle gates, descriptor re-selection, several GPUs.  (A frame whose prior is not within `radius`
- * of the truth is what "Relocalisation" below is for.) */
+ * Out of scope: a predicted octave (the observation table has none), several GPUs.  The viewing-angle and distance gates and the descriptor
+ * re-selection are "Landmark refresh" below.  (A frame whose prior is not within `radius` of the truth is what "Relocalisation" below is for.) */
 typedef struct dvs_maptrack dvs_maptrack;
 #define DVS_MAPTRACK_MAX_LEVELS 16
 enum { DVS_MAPTRACK_OK = 0, DVS_MAPTRACK_FEW_MATCHES = 1, DVS_MAPTRACK_FEW_INLIERS = 2, DVS_MAPTRACK_DEGENERATE = 3 };
@@ -1620,6 +1620,82 @@ dvs_status dvs_backend_cull_keyframes(dvs_backend* h, uint64_t ref_frame_id, con
                                       const uint64_t* protected_frame_ids, int32_t n_protected, int32_t apply, dvs_cull_result* out,
                                       int32_t cap_kf, uint64_t* culled_frame_id, int32_t* kf_observed, int32_t* kf_redundant,
                                       uint8_t* kf_state, int32_t* n_kf);
+
+/* ======================================= Landmark refresh ================================= */
+/* A landmark's descriptor re-selected from all its views, its viewing geometry, and map tracking gated by that geometry
+ * (csrc/landmark_refresh.hip, csrc/map_track.hip; INTEGRATION.md "Landmark refresh"): what ORB-SLAM runs per keyframe as
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth and tests in isInFrustum (Mur-Artal, Montiel, Tardos 2015, sections III-C and V-D),
+ * as published ideas.  PARITY UNPINNED: the reference has no counterpart; the rule is the library's own, defined over the tables as the
+ * getters return them, stated here in full and restated in numpy and Python sets in tests/landmark_refresh_ref.py.  Everything is opt-in:
+ * a program that never calls this section computes and allocates what it did before.
+ *  Views      The views of landmark row s are the observation rows whose landmark_id is the row's id, in observation-table order (the
+ *             obs_offsets / obs_ids segment of dvs_backend_get_landmarks).  Two rows of one keyframe naming one landmark are two views.
+ *  Descriptor integers only.  With n views of descriptors d_0 .. d_{n-1}: D[i][j] = hamming(d_i, d_j), D[i][i] = 0 included; med_i = the
+ *             element at index (n - 1) / 2 (integer division) of row i sorted ascending; the CHOSEN view is the one with the smallest
+ *             (med_i, i): the first view in table order wins ties.  n == 0 or n < min_views: the landmark keeps its bytes.  No upper
+ *             limit on n.
+ *  Geometry   FP64, no contraction, every expression left to right as written.  View p of keyframe index k COUNTS iff k is a keyframe of
+ *             the map and r is finite and > 0, with C = kf_t[k], X = the float position widened, d = X - C,
+ *             r = sqrt((d0 * d0 + d1 * d1) + d2 * d2).  With the m counted views in view order: normal[c] = (sum of d[c] / r) / m, each
+ *             component summed sequentially from 0.0 and NOT re-normalised; dmin = min r, dmax = max r.  m == 0: normal = 0, dmin = dmax = 0.
+ *  Gates      stage 1 of "Tracking against the map", before the projection; only + - * / and comparisons.  O = the prior's t, p = X - O,
+ *             q = (p0 * p0 + p1 * p1) + p2 * p2, s = (p0 * N0 + p1 * N1) + p2 * N2, a = dmin / range_factor, b = dmax * range_factor,
+ *             cc = cos_min * cos_min.  A landmark with m > 0 is GATED OUT, and counted at the FIRST test that holds, in this order:
+ *             near q < a * a; far q > b * b; back-facing s < 0; angle s * s < cc * q.  A gated landmark is treated exactly as one that is
+ *             not visible (u = v = 0, it proposes nothing, it is not in n_visible); it is counted whether or not it would have been
+ *             visible.  A landmark with m == 0 passes and is counted nowhere.
+ *  Scope      use_scope == 0: every landmark row.  use_scope != 0: the landmarks keyframe scope_frame_id observes ("Covisibility": S_k).
+ * cos_min in [0, 1], range_factor >= 1 and finite, min_views >= 1; an unknown scope_frame_id: DVS_ERR_ARG before any device work.  The
+ * defaults — cos_min 0.5 (60 degrees), range_factor 2.0, min_views 1 — are usual values, never fitted to a sensor.
+ * The selection is integers and total orders: two identical calls give identical bytes.  Nothing is cached between calls: every call
+ * rebuilds the views from the tables as they stand, as "Covisibility" does.
+ * Names: the gated calls on a dvs_maptrack handle carry the prefix dvs_mapgate_, not dvs_maptrack_: tests/test_map_track_cpu.py pins the
+ * exact set of dvs_maptrack_ functions, as tests/test_loop_cpu.py does for dvs_loop_.
+ * Out of scope: an octave column and octave prediction from distance, cached geometry or new landmark columns, gates in relocalisation,
+ * fusion, dvs_backend_track_frame_local and the association of dvs_backend_add_keyframe, a policy that calls the refresh, several GPUs. */
+typedef struct dvs_lm_refresh_params {
+  int32_t update_descriptors;  /* 1; 0: a dry run that only fills the result */
+  int32_t min_views;           /* 1 */
+  int32_t use_scope;           /* 0 */
+  int32_t reserved;
+  uint64_t scope_frame_id;     /* read only when use_scope != 0 */
+} dvs_lm_refresh_params;       /* 24 bytes */
+typedef struct dvs_lm_refresh_result {
+  int32_t n_in_scope;          /* landmark rows in scope */
+  int32_t n_changed;           /* of them: n >= max(min_views, 1) and the chosen view's bytes differ from the landmark's */
+  int32_t n_without_views;     /* of them: n == 0 */
+  int32_t max_views;           /* the largest n in scope */
+} dvs_lm_refresh_result;       /* 16 bytes */
+typedef struct dvs_maptrack_gates { double cos_min, range_factor; } dvs_maptrack_gates;   /* 0.5, 2.0 */
+void dvs_lm_refresh_default_params(dvs_lm_refresh_params* p);
+void dvs_mapgate_default_gates(dvs_maptrack_gates* g);
+/* Builds the views, selects the view of every landmark in scope and (update_descriptors != 0) writes the chosen descriptor into the landmark
+ * table in place; nothing else in the map changes, and with n_changed == 0 no byte does.  params NULL: the defaults; result nullable. */
+dvs_status dvs_backend_refresh_landmarks(dvs_backend* h, const dvs_lm_refresh_params* params, dvs_lm_refresh_result* result);
+/* A dry run over the whole table, count-then-capacity (*n = landmark rows is always set; DVS_ERR_CAPACITY, nothing written, if an array is
+ * given and cap < *n), every output nullable, the map never modified: normal n x 3, range n x 2 (dmin, dmax), n_counted = m, best_obs_id =
+ * the chosen view's observation id (UINT64_MAX where n == 0), best_median = its med_i (-1 where n == 0) — chosen as with min_views 1. */
+dvs_status dvs_backend_get_landmark_geometry(dvs_backend* h, int32_t cap, double* normal, double* range, int32_t* n_counted, uint64_t* best_obs_id,
+                                             int32_t* best_median, int32_t* n);
+/* dvs_maptrack_search_device / dvs_maptrack_track_device with the gates: d_lm_normal n_lm x 3 doubles, d_lm_range n_lm x 2 doubles,
+ * d_lm_ncounted n_lm int32 (device, 8 / 8 / 4-byte aligned), gates NULL: the defaults.  The ungated calls are untouched. */
+dvs_status dvs_mapgate_search_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                     const double* d_lm_normal, const double* d_lm_range, const int32_t* d_lm_ncounted,
+                                     const dvs_maptrack_gates* gates, const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp,
+                                     const double* R9, const double* t3, dvs_maptrack_result* result);
+dvs_status dvs_mapgate_track_device(dvs_maptrack* h, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
+                                    const double* d_lm_normal, const double* d_lm_range, const int32_t* d_lm_ncounted,
+                                    const dvs_maptrack_gates* gates, const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp,
+                                    const double* R9, const double* t3, dvs_maptrack_result* result);
+/* the last call's gate counts: near, far, back-facing, angle (all 0 after an ungated call); synchronises */
+dvs_status dvs_mapgate_get_counts(dvs_maptrack* h, int32_t out[4]);
+/* dvs_backend_track_frame with the gates: the geometry of the table as it stands is computed into the backend's scratch (the views and one
+ * sequential FP64 walk per landmark), then dvs_mapgate_track_device runs; the map is not modified. */
+dvs_status dvs_backend_track_frame_gated(dvs_backend* h, dvs_maptrack* mt, const dvs_maptrack_gates* gates /* NULL: defaults */, const dvs_keypoint* d_kps,
+                                         const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result);
+/* dvs_tracker_track_map through dvs_backend_track_frame_gated */
+dvs_status dvs_tracker_track_map_gated(dvs_tracker* h, dvs_backend* backend, dvs_maptrack* mt, const dvs_maptrack_gates* gates, int32_t apply,
+                                       dvs_maptrack_result* result);
 
 /* ======================================= Relocalisation ================================= */
 /* A frame's pose in the map WITHOUT a prior (csrc/reloc.hip; INTEGRATION.md "Relocalisation"): what recovers a tracker after a tracking
