@@ -367,6 +367,21 @@ dvs_status dvs::backend_views_build(dvs_backend* h) {
   return DVS_OK;
 }
 
+// :1303-1312 keyframes' observation_ids lose the removed ids
+int dvs::backend_drop_observation_ids(dvs_backend* h, const std::vector<i64>& rid, const std::vector<int>& rkf) {
+  std::unordered_set<uint64_t> gone(rid.begin(), rid.end());
+  std::unordered_set<int> touched(rkf.begin(), rkf.end());
+  int n = 0;
+  for (int k : touched) {
+    if (k < 0 || k >= (int)h->kfs.size()) continue;
+    std::vector<uint64_t>& ids = h->kfs[(size_t)k].obs_ids;
+    const size_t before = ids.size();
+    ids.erase(std::remove_if(ids.begin(), ids.end(), [&](uint64_t id) { return gone.count(id) != 0; }), ids.end());
+    n += ids.size() != before ? 1 : 0;
+  }
+  return n;
+}
+
 extern "C" {
 
 void dvs_backend_default_params(dvs_backend_params* p) {
@@ -411,6 +426,7 @@ dvs_status dvs_backend_reset(dvs_backend* h) {
   DVS_ARG(h);
   DVS_TRY(dvs_matcher_synchronize(h->ctx));
   h->nlm = h->nob = 0; h->kfs.clear(); h->kf_index.clear(); h->next_obs = h->next_lm = 0;
+  h->nstat = 0; h->n_recorded = 0;                   // "Landmark culling": the statistics are emptied, the recording switch stays as set
   return DVS_OK;
 }
 
@@ -704,14 +720,7 @@ dvs_status dvs_backend_prune(dvs_backend* h, int32_t now_sec, uint32_t now_nanos
     DVS_TRY(copy_out(rid.data(), rem_id, rid.size(), st)); DVS_TRY(copy_out(rkf.data(), rem_kf, rkf.size(), st));
     DVS_HIP(hipStreamSynchronize(st));
   }
-  // :1303-1312 keyframes' observation_ids lose the removed ids
-  std::unordered_set<uint64_t> gone(rid.begin(), rid.end());
-  std::unordered_set<int> touched(rkf.begin(), rkf.end());
-  for (int k : touched) {
-    if (k < 0 || k >= (int)h->kfs.size()) continue;
-    std::vector<uint64_t>& ids = h->kfs[(size_t)k].obs_ids;
-    ids.erase(std::remove_if(ids.begin(), ids.end(), [&](uint64_t id) { return gone.count(id) != 0; }), ids.end());
-  }
+  backend_drop_observation_ids(h, rid, rkf);
   std::swap(h->lm, h->lm_spare); std::swap(h->ob, h->ob_spare);
   *removed_landmarks = nlm - counts[0]; *removed_observations = counts[2];
   h->nlm = counts[0]; h->nob = counts[1];

@@ -1,5 +1,5 @@
 // backend_internal.h — the mapping backend handle (dvs_backend, include/dvslam_hip.h) shared by backend.hip, loop_close.hip,
-// covisibility.hip, kf_cull.hip and landmark_refresh.hip: the views of the landmark and observation tables that kernels take, the owners of the tables, the keyframe record,
+// covisibility.hip, kf_cull.hip, landmark_refresh.hip, lm_cull.hip and map_track.hip's recording: the views of the landmark and observation tables that kernels take, the owners of the tables, the keyframe record,
 // the counter block, the row groups of per-call scratch and the handle itself.  Internal to the library, as loop_internal.h and
 // bow_internal.h are.
 #pragma once
@@ -85,6 +85,7 @@ struct KeyframeRec { uint64_t frame_id; i64 stamp; std::vector<uint64_t> obs_ids
 struct FuseCounts { int n_query, n_sources, n_targets, n_proposals, n_fused, n_kept, n_anchored, pad; };   // n_anchored: k_anchors, cleared on its own
 struct CullCounts { int n_culled, n_ob_removed, n_lm_removed, pad; };   // k_cull_walk; k_cull_ob_flag; k_cull_lm_flag
 struct RefreshCounts { int n_bin[3], n_in_scope, n_without_views, max_views, n_changed, pad; };   // k_lr_bin; n_changed: k_lr_apply
+struct LmCullCounts { int n_by_ratio, n_weak, pad[2]; };   // k_lc_decide
 struct BackendSmall {
   int filtered[64];     // add_keyframe: the filtered class ids
   int classes[64];       //               the distinct unfiltered classes of the keyframe
@@ -96,13 +97,15 @@ struct BackendSmall {
   int left_out, pad1[3];    // covisibility.hip, k_covis_ob_flag: rows left out of the local window
   CullCounts cull;          // kf_cull.hip
   RefreshCounts refresh;    // landmark_refresh.hip
-  int pad2[32];
+  LmCullCounts lmcull;      // lm_cull.hip
+  int pad2[28];
 };
 static_assert(sizeof(BackendSmall) == 256 * 4 && offsetof(BackendSmall, classes) == 64 * 4 && offsetof(BackendSmall, class_cnt) == 128 * 4 &&
               offsetof(BackendSmall, counts) == 192 * 4 && offsetof(BackendSmall, marked) == 196 * 4 && offsetof(BackendSmall, fuse) == 200 * 4 &&
               offsetof(BackendSmall, fuse.n_anchored) == 206 * 4 && offsetof(BackendSmall, left_out) == 208 * 4, "kernels and the upload keep these addresses");
 static_assert(offsetof(BackendSmall, cull) == 212 * 4, "the culling counters take the padding behind left_out");
 static_assert(offsetof(BackendSmall, refresh) == 216 * 4, "and the refresh counters the padding behind them");
+static_assert(offsetof(BackendSmall, lmcull) == 224 * 4, "and the landmark culling counters the padding behind those");
 
 // The eight columns a BA window hands out, in two halves by row domain; the sliding window and the local window each hold both.
 struct WindowObs { Column<float, 2> px; Column<i64> lm; Column<int> cls; Column<i64> frame; Column<int> lmidx; };
@@ -213,6 +216,25 @@ struct RefreshLmRows {    // landmark refresh per landmark row: views, in scope;
   size_t cap = 0;
   dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, n, scope, list0, list1, list2, best, med, ncnt, oid, normal, range); }
 };
+struct LmStatRows {      // the tracking statistics, a side table of the landmark table joined by id ("Landmark culling" in the header): after
+                          // lm_stats_align row s is landmark row s.  The handle holds a live one and a spare the alignment and the cull write
+  Column<i64> id; Column<int> visible, found;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, id, visible, found); }
+};
+struct StatView { i64* id; int* visible; int* found; };
+inline StatView stat_view(const LmStatRows& t) { return StatView{t.id.get(), t.visible.get(), t.found.get()}; }
+struct LmCullLmRows {     // landmark culling per landmark row: views, age in keyframes, the rule that holds (0: none), stays, leaves; the culled ids and
+                          // their reasons compacted
+  Column<int> n, age, reason, keep, mark, creason; Column<i64> cid;
+  size_t cap = 0;
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, n, age, reason, keep, mark, creason, cid); }
+};
+struct LmCullObRows {     // landmark culling per observation row: stays, leaves
+  Column<int> keep, gone;
+  size_t cap = 0;
+  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2 + 64, keep, gone); }
+};
 
 }  // namespace dvs
 
@@ -239,6 +261,9 @@ struct dvs_backend {
   dvs::CovisObRows cv_ob; dvs::CovisKfRows cv_kf; dvs::CovisLmRows cv_lm; dvs::CovisBlockRows cv_blk; dvs::CovisWeightRows cv_w;
   dvs::CullKfRows cull_kf; dvs::CullLmRows cull_lm; dvs::CullObRows cull_ob;
   dvs::RefreshLmRows lr_lm;
+  // landmark culling (lm_cull.hip): the statistics and their spare (not allocated before first use), the recording switch, the calls that recorded
+  dvs::LmStatRows stat, stat_spare; int nstat = 0; int stats_on = 0; dvs::i64 n_recorded = 0;
+  dvs::LmCullLmRows lc_lm; dvs::LmCullObRows lc_ob;
   // single blocks (device_mem.h, grow): detections, candidate pairs, per-call arguments, anchors per landmark, landmark row per observation
   dvs::DeviceBuf<dvs::DetRec> s_det; dvs::DeviceBuf<dvs::PairRec> p_rec; dvs::DeviceBuf<int> a_int, f_obrow; dvs::Column<int> f_anchor; dvs::DeviceBuf<dvs::i64> a_i64; dvs::DeviceBuf<double> a_dbl;
   size_t c_det = 0, c_pair = 0, c_aint = 0, c_ai64 = 0, c_adbl = 0, c_flm = 0, c_fob = 0;
@@ -284,4 +309,10 @@ dvs_status covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk
 // the viewing geometry of every landmark row ("Landmark refresh" in the header; landmark_refresh.hip) into lr_lm.normal / .range / .ncnt:
 // the views are rebuilt, everything is enqueued on the handle's stream; needs at least one landmark
 dvs_status refresh_geometry(dvs_backend* h);
+// the keyframes' observation_ids lose the ids in `gone` (:1303-1312); kf: the keyframe index of each removed row -> the keyframes that lost
+// at least one id (backend.hip; the host half of dvs_backend_prune and dvs_backend_cull_landmarks)
+int backend_drop_observation_ids(dvs_backend* h, const std::vector<i64>& gone, const std::vector<int>& kf);
+// the statistics aligned to the landmark table as it stands ("Landmark culling" in the header; lm_cull.hip): enqueued on the handle's stream;
+// afterwards h->nstat == h->nlm and statistics row s is landmark row s
+dvs_status lm_stats_align(dvs_backend* h);
 }  // namespace dvs

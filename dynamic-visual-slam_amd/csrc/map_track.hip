@@ -13,7 +13,9 @@
 //                  per-lane strided partial sums, added through LDS in one fixed order, the 6 x 6 Cholesky on lane 0 — and writes the 128-byte record.  No host decision between iterations.
 //                  The schedule (first round, rounds, steps per round) is an argument, 0, 4, 10 in every product launch; the product's
 //                  instantiation has it as constants, the test hook's (dvs_test_maptrack_refine_steps: single steps compared) reads it.
-// Every launch is on the handle's stream; nothing is read back but the record.
+//   k_mt_record_stats  (only from the dvs_backend_track_frame* calls, and only while the backend's recording is on; "Landmark culling" in the
+//                  header) a row of the call per lane: visible and found of the row's id in the backend's statistics
+// Every launch is on the handle's stream but that last one, which runs on the backend's; nothing is read back but the record.
 #include <math.h>
 #include <string.h>
 #include <new>
@@ -419,6 +421,22 @@ __global__ void k_mt_search_record(MtPose T, const int* counters, dvs_maptrack_r
   *out = r;
 }
 
+// "Landmark culling" in the header, the recording: thread j owns row j of the arrays the call handed to the tracker and the statistics row
+// of that row's id, which no other thread writes (the ids of a call are distinct).  Nothing changes unless the device record says OK.
+__global__ __launch_bounds__(256) void k_mt_record_stats(const MtRec* __restrict__ rec, const i64* __restrict__ id, int n, const uint8_t* __restrict__ kp_inl, int n_kp,
+                                                         const dvs_maptrack_result* __restrict__ res, StatView st, int nstat) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n || res->status != DVS_MAPTRACK_OK) return;
+  if (rec[j].visible == 0) return;
+  const int s = lm_find(st.id, nstat, id[j]);
+  if (s < 0) return;
+  const int v = st.visible[s];
+  if (v == 0x7fffffff) return;
+  st.visible[s] = v + 1;
+  const int k = rec[j].best_k;
+  if (rec[j].kept != 0 && k >= 0 && k < n_kp && kp_inl[k] != 0) st.found[s] += 1;
+}
+
 static dvs_status maptrack_check_params(const dvs_maptrack_params& P) {
   DVS_ARG(P.rows >= 1 && P.rows <= 16384 && P.cols >= 1 && P.cols <= 16384);
   DVS_ARG(__builtin_isfinite(P.fx) && __builtin_isfinite(P.fy) && __builtin_isfinite(P.cx) && __builtin_isfinite(P.cy) && P.fx > 0 && P.fy > 0);
@@ -582,6 +600,22 @@ static dvs_status mt_search_call(dvs_maptrack* h, const MtGateArgs* gate, const 
                                  const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result);
 static dvs_status mt_track_call(dvs_maptrack* h, const MtGateArgs* gate, const float* d_lm_xyz, const uint8_t* d_lm_desc, const int64_t* d_lm_id, int32_t n_lm,
                                 const dvs_keypoint* d_kps, const uint8_t* d_desc, int32_t n_kp, const double* R9, const double* t3, dvs_maptrack_result* result);
+
+// the end of the three dvs_backend_track_frame* calls ("Landmark culling" in the header): with the switch off nothing is launched or waited
+// for.  d_id / n: the rows the call handed to the tracker, whose records, flags and device record mt still holds; mt's stream has been
+// synchronised by the read of the result, so the backend's stream may read them.
+static dvs_status mt_record_stats(dvs_backend* h, dvs_maptrack* mt, const i64* d_id, int n, const dvs_maptrack_result* result) {
+  if (!h->stats_on) return DVS_OK;
+  DVS_TRY(dvs::lm_stats_align(h));
+  hipStream_t st = h->ctx->stream;
+  if (n > 0 && h->nstat > 0 && mt->last_search && mt->last_n_lm == n)
+    hipLaunchKernelGGL(k_mt_record_stats, dim3((n + 255) / 256), dim3(256), 0, st, (const MtRec*)mt->rec.get(), d_id, n, (const uint8_t*)mt->kp_inl.get(), mt->last_n_kp,
+                       (const dvs_maptrack_result*)mt->d_res.get(), stat_view(h->stat), h->nstat);
+  DVS_HIP(hipGetLastError());
+  DVS_HIP(hipStreamSynchronize(st));
+  if (result->status == DVS_MAPTRACK_OK) h->n_recorded++;
+  return DVS_OK;
+}
 
 extern "C" {
 
@@ -780,7 +814,8 @@ dvs_status dvs_backend_track_frame(dvs_backend* h, dvs_maptrack* mt, const dvs_k
   DVS_TRY(maptrack_pose(R9, t3, &T));
   DVS_HIP(hipSetDevice(h->device));
   DVS_HIP(hipStreamSynchronize(h->ctx->stream));   // the table as the backend's last call left it
-  return dvs_maptrack_track_device(mt, h->lm.xyz.get(), h->lm.desc.get(), (const int64_t*)h->lm.id.get(), h->nlm, d_kps, d_desc, n_kp, R9, t3, result);
+  DVS_TRY(dvs_maptrack_track_device(mt, h->lm.xyz.get(), h->lm.desc.get(), (const int64_t*)h->lm.id.get(), h->nlm, d_kps, d_desc, n_kp, R9, t3, result));
+  return mt_record_stats(h, mt, h->lm.id.get(), h->nlm, result);
 }
 
 // the same with the gates of "Landmark refresh": landmark_refresh.hip computes the geometry of the table as it stands into the backend's scratch
@@ -796,7 +831,8 @@ dvs_status dvs_backend_track_frame_gated(dvs_backend* h, dvs_maptrack* mt, const
   if (h->nlm > 0) DVS_TRY(dvs::refresh_geometry(h));
   DVS_HIP(hipStreamSynchronize(h->ctx->stream));   // the table as the backend's last call left it, and its geometry
   g.normal = h->lr_lm.normal.get(); g.range = h->lr_lm.range.get(); g.ncnt = h->lr_lm.ncnt.get();
-  return mt_track_call(mt, &g, h->lm.xyz.get(), h->lm.desc.get(), (const int64_t*)h->lm.id.get(), h->nlm, d_kps, d_desc, n_kp, R9, t3, result);
+  DVS_TRY(mt_track_call(mt, &g, h->lm.xyz.get(), h->lm.desc.get(), (const int64_t*)h->lm.id.get(), h->nlm, d_kps, d_desc, n_kp, R9, t3, result));
+  return mt_record_stats(h, mt, h->lm.id.get(), h->nlm, result);
 }
 
 // the same against the local map of one keyframe ("Covisibility" in the header): covisibility.hip compacts U's columns on the device
@@ -809,7 +845,8 @@ dvs_status dvs_backend_track_frame_local(dvs_backend* h, dvs_maptrack* mt, uint6
   const float* xyz = nullptr; const uint8_t* desc = nullptr; const dvs::i64* id = nullptr;
   int n = 0;
   DVS_TRY(dvs::backend_local_map(h, ref_frame_id, params, &xyz, &desc, &id, &n));   // returns with the backend's stream synchronised
-  return dvs_maptrack_track_device(mt, xyz, desc, (const int64_t*)id, n, d_kps, d_desc, n_kp, R9, t3, result);
+  DVS_TRY(dvs_maptrack_track_device(mt, xyz, desc, (const int64_t*)id, n, d_kps, d_desc, n_kp, R9, t3, result));
+  return mt_record_stats(h, mt, id, n, result);   // U's ids are scratch of the backend, valid until its next call: the alignment leaves them alone
 }
 
 #ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test_maptrack.h)

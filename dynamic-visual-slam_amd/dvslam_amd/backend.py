@@ -82,6 +82,17 @@ class LmRefreshResult(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n_in_scope", "n_changed", "n_without_views", "max_views")]
 
 
+class LmCullParams(C.Structure):
+    """dvs_lm_cull_params (fill it with dvs_lm_cull_default_params)"""
+    _fields_ = [(k, C.c_int32) for k in ("found_ratio_pct", "min_visible", "weak_age_kf", "weak_max_views")]
+
+
+class LmCullResult(C.Structure):
+    """dvs_lm_cull_result"""
+    _fields_ = [(k, C.c_int32) for k in ("n_landmarks", "n_by_ratio", "n_weak", "n_landmarks_removed", "n_observations_removed", "n_keyframes_touched")] + \
+               [("reserved", C.c_int32 * 2)]
+
+
 class MapTrackGates(C.Structure):
     """dvs_maptrack_gates (fill it with dvs_mapgate_default_gates)"""
     _fields_ = [("cos_min", C.c_double), ("range_factor", C.c_double)]
@@ -122,6 +133,12 @@ def _bind(L):
     L.dvs_backend_refresh_landmarks.argtypes = [vp, C.POINTER(LmRefreshParams), C.POINTER(LmRefreshResult)]
     L.dvs_backend_get_landmark_geometry.argtypes = [vp, i32, vp, vp, vp, vp, vp, pi32]
     L.dvs_backend_track_frame_gated.argtypes = [vp, vp, C.POINTER(MapTrackGates), vp, vp, i32, vp, vp, vp]
+    L.dvs_lm_cull_default_params.argtypes = [C.POINTER(LmCullParams)]; L.dvs_lm_cull_default_params.restype = None
+    L.dvs_backend_set_tracking_stats.argtypes = [vp, i32]
+    L.dvs_backend_cull_landmarks.argtypes = [vp, C.POINTER(LmCullParams), i32, C.POINTER(LmCullResult), i32, vp, vp, pi32]
+    L.dvs_backend_get_landmark_stats.argtypes = [vp, i32, vp, vp, vp, vp, vp, pi32, pi64]
+    L.dvs_backend_set_landmark_stats.argtypes = [vp, i32, vp, vp, vp]
+    L.dvs_backend_clear_landmark_stats.argtypes = [vp]
     return L
 
 
@@ -155,6 +172,17 @@ def cull_params(**kw):
         if k not in dict(CullParams._fields_) or k == "reserved":
             raise TypeError(f"unknown parameter {k}")
         setattr(p, k, v)
+    return p
+
+
+def lm_cull_params(**kw):
+    """dvs_lm_cull_default_params with field overrides"""
+    p = LmCullParams()
+    _bind(lib()).dvs_lm_cull_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(LmCullParams._fields_) or k == "reserved":
+            raise TypeError(f"unknown parameter {k}")
+        setattr(p, k, int(v))
     return p
 
 
@@ -540,6 +568,46 @@ class MappingBackend:
         check(self._L.dvs_backend_track_frame_gated(self._h, map_tracker.handle, C.byref(g), M._raw(d_kps), M._raw(d_desc), int(n_kp), ptr(R), ptr(t), C.byref(r)))
         return r.as_dict()
 
+    # ---- landmark culling (include/dvslam_hip.h "Landmark culling")
+    def set_tracking_stats(self, on=True):
+        """dvs_backend_set_tracking_stats: while on, track_frame, track_frame_gated and track_frame_local record per landmark whether it was
+        predicted visible and whether it was found"""
+        check(self._L.dvs_backend_set_tracking_stats(self._h, 1 if on else 0))
+
+    def landmark_stats(self):
+        """dvs_backend_get_landmark_stats -> dict(id uint64, visible, found, n_views, age_kf int32, rows as landmarks(); n_frames_recorded int)"""
+        nn, nf = C.c_int32(), C.c_int64()
+        check(self._L.dvs_backend_get_landmark_stats(self._h, 0, None, None, None, None, None, C.byref(nn), C.byref(nf)))
+        n = nn.value
+        c = max(n, 1)
+        lid = np.zeros(c, np.uint64); vis = np.zeros(c, np.int32); fnd = np.zeros(c, np.int32); nv = np.zeros(c, np.int32); age = np.zeros(c, np.int32)
+        check(self._L.dvs_backend_get_landmark_stats(self._h, c, ptr(lid), ptr(vis), ptr(fnd), ptr(nv), ptr(age), C.byref(nn), C.byref(nf)))
+        return dict(id=lid[:n], visible=vis[:n], found=fnd[:n], n_views=nv[:n], age_kf=age[:n], n_frames_recorded=int(nf.value))
+
+    def set_landmark_stats(self, ids, visible, found):
+        """dvs_backend_set_landmark_stats: ids strictly ascending; ids the map does not hold are skipped"""
+        lid = np.ascontiguousarray(ids, np.uint64); vis = np.ascontiguousarray(visible, np.int32); fnd = np.ascontiguousarray(found, np.int32)
+        if not len(lid) == len(vis) == len(fnd):
+            raise ValueError("ids, visible and found must have one entry per row")
+        check(self._L.dvs_backend_set_landmark_stats(self._h, len(lid), ptr(lid), ptr(vis), ptr(fnd)))
+
+    def clear_landmark_stats(self):
+        check(self._L.dvs_backend_clear_landmark_stats(self._h))
+
+    def cull_landmarks(self, apply=True, cap=None, **params):
+        """dvs_backend_cull_landmarks: the landmarks found in too few of the frames that predicted them, and the weak ones, leave the map
+        (apply=False: a dry run that only reports).  params: the fields of dvs_lm_cull_params.  cap None: as many entries as the map has
+        landmarks.  -> dict of the fields of dvs_lm_cull_result plus culled_id (uint64, ascending) and culled_reason (int32: 1 found
+        ratio, 2 weak)"""
+        p = lm_cull_params(**params)
+        n = max(self.counts()["n_landmarks"], 1) if cap is None else int(cap)
+        cid = np.zeros(max(n, 1), np.uint64); why = np.zeros(max(n, 1), np.int32)
+        r = LmCullResult(); nc = C.c_int32()
+        check(self._L.dvs_backend_cull_landmarks(self._h, C.byref(p), 1 if apply else 0, C.byref(r), n, ptr(cid), ptr(why), C.byref(nc)))
+        out = {k: int(getattr(r, k)) for k, _ in LmCullResult._fields_ if k != "reserved"}
+        out.update(culled_id=cid[:nc.value], culled_reason=why[:nc.value])
+        return out
+
     def reset(self):
         check(self._L.dvs_backend_reset(self._h))
 
@@ -555,4 +623,4 @@ class MappingBackend:
             pass
 
 
-__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "CovisParams", "LocalBaResult", "covis_params", "CullParams", "CullResult", "cull_params", "LmRefreshParams", "LmRefreshResult", "MapTrackGates", "lm_refresh_params", "maptrack_gates", "default_params", "fuse_params", "DvsError"]
+__all__ = ["MappingBackend", "BackendParams", "BackendResult", "Detection", "FuseParams", "FuseResult", "CloseLoopResult", "GlobalBaResult", "CovisParams", "LocalBaResult", "covis_params", "CullParams", "CullResult", "cull_params", "LmRefreshParams", "LmRefreshResult", "MapTrackGates", "LmCullParams", "LmCullResult", "lm_cull_params", "lm_refresh_params", "maptrack_gates", "default_params", "fuse_params", "DvsError"]

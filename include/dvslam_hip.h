@@ -1697,6 +1697,80 @@ dvs_status dvs_backend_track_frame_gated(dvs_backend* h, dvs_maptrack* mt, const
 dvs_status dvs_tracker_track_map_gated(dvs_tracker* h, dvs_backend* backend, dvs_maptrack* mt, const dvs_maptrack_gates* gates, int32_t apply,
                                        dvs_maptrack_result* result);
 
+/* ======================================= Landmark culling ================================= */
+/* What a frame learns while it is tracked against the map reaches the map: two counters per landmark, recorded by the map-tracking calls
+ * of the backend, and a cull that removes the landmarks the frames keep predicting and never find — a chair that was moved — and the
+ * landmarks only their creating keyframe ever saw (csrc/lm_cull.hip, csrc/map_track.hip; INTEGRATION.md "Landmark culling"): the ideas of
+ * ORB-SLAM's mnVisible / mnFound and MapPointCulling (Mur-Artal, Montiel, Tardos 2015, section VI-B) as published, not its code.  PARITY
+ * UNPINNED: the reference has no counterpart; the rule is the library's own, stated here in full and restated with dicts and Python sets in
+ * tests/landmark_culling_ref.py.  Everything is integers and total orders: the device matches the restatement bit for bit.  Everything is
+ * opt-in: a program that never calls this section allocates, launches and computes what it did before.
+ *  Statistics two int32 counters per landmark, visible and found, kept in a side table of the handle joined to the landmark table BY ID; the
+ *             landmark table has no new column.  Every call of this section first ALIGNS the side table to the landmark table as it
+ *             stands: an id the statistics hold keeps its counters, an id they do not hold starts at 0 / 0, the statistics of ids no longer
+ *             in the table are dropped.  Landmark ids only grow, so an id never comes back with another landmark's counters.  After a
+ *             fusion the survivor keeps its own counters and the removed id's are dropped; they are not merged.  dvs_backend_reset empties
+ *             the statistics and leaves the switch as set.  Nothing is cached about "the map did not change": every call aligns.
+ *  Recording  off until dvs_backend_set_tracking_stats(h, 1).  While it is on, dvs_backend_track_frame, dvs_backend_track_frame_gated and
+ *             dvs_backend_track_frame_local (and so dvs_tracker_track_map and dvs_tracker_track_map_gated) end by recording their own
+ *             outcome, before they return.  With j over the rows handed to the tracker — the whole table, or the local map U, where the
+ *             id decides, not the row: if the result's status != DVS_MAPTRACK_OK nothing changes, byte for byte (a frame whose pose was not
+ *             accepted says nothing about the map).  Otherwise a landmark that is VISIBLE — stage 1 of "Tracking against the map", after
+ *             the gates where there are any: a gated-out landmark is not visible — gets visible += 1; if it was KEPT by a keypoint in
+ *             stage 3 and that keypoint's pair ended as an inlier after round 3, it also gets found += 1.  A landmark whose visible is
+ *             INT32_MAX is not updated, so found <= visible always holds.  No atomics and no order dependence.  The recording costs one
+ *             alignment kernel, one kernel over the call's rows and one more wait; with the switch off the three calls launch and wait
+ *             for nothing new.
+ *  Views      for landmark row s: n = the number of its views, the observation rows naming it, as in "Landmark refresh"; k_first = the kf
+ *             of its first view in observation-table order that is a keyframe of the map (0 <= kf < nkf); age_kf = (nkf - 1) - k_first,
+ *             or -1 without such a view.  If its keyframe was culled a landmark's first remaining view is later, so it looks younger:
+ *             accepted.
+ *  Rules      F (found ratio): found_ratio_pct > 0 and visible >= min_visible and (int64) found * 100 < (int64) found_ratio_pct * visible —
+ *             strict, equality stays.  W (weak): weak_age_kf >= 0 and age_kf >= weak_age_kf and n <= weak_max_views; a landmark with
+ *             age_kf == -1 is never weak.  A landmark is CULLED iff F or W holds, and counted at the FIRST that holds, F then W: reason 1
+ *             for F, 2 for W.  culled_id comes out ascending.
+ *  Apply      (apply != 0 and at least one landmark culled) dvs_backend_prune's cascade: the culled landmark rows and every observation
+ *             row naming one leave both tables by ordered compaction, the other rows keep their order and every column; the statistics
+ *             are compacted alongside; the keyframes' observation_ids lose the removed ids; keyframes stay even if emptied;
+ *             observation_count and last_seen of the survivors are untouched, as are both id counters.  n_keyframes_touched = the
+ *             keyframes whose observation_ids lost at least one id.  If nothing is culled, or apply == 0, the map stays byte for byte as it
+ *             was and the three removal counts are 0.
+ * DVS_ERR_ARG before any device work: found_ratio_pct > 100, min_visible < 1, weak_max_views < 0.  Count-then-capacity: *n_culled is always
+ * set; DVS_ERR_CAPACITY, with nothing written and nothing applied, if an array is given and cap < *n_culled.  An empty map: DVS_OK, zeros.
+ * The defaults — found_ratio_pct 25, min_visible 4, weak_age_kf 2, weak_max_views 1 — are usual values (ORB-SLAM's quarter and its two
+ * keyframes), never fitted to a sensor.
+ * Out of scope: a policy that calls the cull or switches recording on by itself, new landmark columns, decay or windowing of the counters,
+ * counters merged on fusion, a class or id protection list, a scope argument, recording from dvs_maptrack_* calls made without a backend
+ * or from relocalisation, creation of new landmarks, several GPUs. */
+typedef struct dvs_lm_cull_params {
+  int32_t found_ratio_pct;     /* 25; <= 0 switches rule F off; at most 100 */
+  int32_t min_visible;         /* 4; >= 1 */
+  int32_t weak_age_kf;         /* 2; < 0 switches rule W off */
+  int32_t weak_max_views;      /* 1; >= 0 */
+} dvs_lm_cull_params;          /* 16 bytes */
+typedef struct dvs_lm_cull_result {
+  int32_t n_landmarks;         /* rows examined */
+  int32_t n_by_ratio, n_weak;  /* counted at the FIRST rule that holds: F, then W */
+  int32_t n_landmarks_removed, n_observations_removed, n_keyframes_touched;   /* 0 with apply == 0 */
+  int32_t reserved[2];
+} dvs_lm_cull_result;          /* 32 bytes */
+void dvs_lm_cull_default_params(dvs_lm_cull_params* p);
+/* the recording switch, off in a new handle; allocates and launches nothing */
+dvs_status dvs_backend_set_tracking_stats(dvs_backend* h, int32_t on);
+/* out and the two arrays are nullable; each array takes *n_culled entries */
+dvs_status dvs_backend_cull_landmarks(dvs_backend* h, const dvs_lm_cull_params* params /* NULL: defaults */, int32_t apply, dvs_lm_cull_result* out,
+                                      int32_t cap, uint64_t* culled_id, int32_t* culled_reason, int32_t* n_culled);
+/* The statistics and the views of every landmark row, rows as dvs_backend_get_landmarks; count-then-capacity (*n = landmark rows is always
+ * set; DVS_ERR_CAPACITY, nothing written, if an array is given and cap < *n), every output nullable, the map never modified.
+ * n_frames_recorded: the calls that recorded (status OK with the switch on) since the handle was created, reset or cleared. */
+dvs_status dvs_backend_get_landmark_stats(dvs_backend* h, int32_t cap, uint64_t* id, int32_t* visible, int32_t* found, int32_t* n_views, int32_t* age_kf,
+                                          int32_t* n, int64_t* n_frames_recorded);
+/* What a caller that saves and reloads a map needs.  ids strictly ascending (else DVS_ERR_ARG, nothing changed); ids the map does not hold
+ * are skipped; found > visible or a negative counter: DVS_ERR_ARG, nothing changed. */
+dvs_status dvs_backend_set_landmark_stats(dvs_backend* h, int32_t n_rows, const uint64_t* id, const int32_t* visible, const int32_t* found);
+/* all counters 0, n_frames_recorded 0; the switch stays as set */
+dvs_status dvs_backend_clear_landmark_stats(dvs_backend* h);
+
 /* ======================================= Relocalisation ================================= */
 /* A frame's pose in the map WITHOUT a prior (csrc/reloc.hip; INTEGRATION.md "Relocalisation"): what recovers a tracker after a tracking
  * reset, when R_, t_ are stale and the window search of "Tracking against the map" finds nothing.  It is what ORB-SLAM's Relocalization
