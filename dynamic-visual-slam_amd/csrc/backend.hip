@@ -14,8 +14,10 @@
 //   k_append_obs / k_append_lm   the keyframe's observations and new landmarks join the tables                              (:803-820)
 //   k_window_gather    the window's observations, the distinct landmarks in id order, indices into that list                (:916-945)
 //   k_apply            optimised positions and poses                                                                        (:1356-1392)
-//   k_prune_mark / k_prune_compact   mark, then compact both tables in order and list the removed observations              (:1249-1322)
-// Compactions are one workgroup of four wavefronts walking the table in trips of 256 (block_ops.h), as tracker.hip does it.
+//   k_prune_mark / k_prune_ob_flag   the landmarks that leave and the observations that name one; table_compact.h's tables_replace
+//                      then writes both tables without them, in order, and lists the removed observations                      (:1249-1322)
+// The list builders are one workgroup of four wavefronts walking the table in trips of 256 (block_ops.h), as tracker.hip does it; what
+// removes rows from the tables is the three-step compaction of table_compact.h.
 //
 // Triangulation: LandmarkInfo::triangulate at :772 reads the views stored BEFORE this keyframe and the landmark's position at the start of
 // the keyframe only (include/dvslam/triangulation.hpp states why), so it runs once per keyframe over the whole table, before the classes.
@@ -36,6 +38,7 @@
 #include "backend_internal.h"
 #include "associate_device.h"
 #include "block_ops.h"
+#include "table_compact.h"
 #include "../../include/dvslam/association.hpp"   // reprojection_error: the device kernel's arithmetic on the host
 
 namespace dvs {
@@ -263,55 +266,31 @@ __global__ __launch_bounds__(256) void k_apply(int nl, const i64* __restrict__ i
 }
 
 // :1258-1273: observation_count < min_obs AND (double)(now - last_seen) / 1e9 > max_age
-__global__ __launch_bounds__(256) void k_prune_mark(LmView lm, int nlm, i64 now, int min_obs, double max_age, int* __restrict__ flag, int* __restrict__ n_marked) {
+__global__ __launch_bounds__(256) void k_prune_mark(LmView lm, int nlm, i64 now, int min_obs, double max_age, int* __restrict__ keep, int* __restrict__ gone,
+                                                    int* __restrict__ n_marked) {
   const int s = blockIdx.x * 256 + threadIdx.x;
   if (s >= nlm) return;
   const double age = (double)(now - lm.seen[s]) / 1e9;
   const int f = (lm.cnt[s] < min_obs && age > max_age) ? 1 : 0;
-  flag[s] = f;
+  keep[s] = 1 - f; gone[s] = f;
   if (f) atomicAdd(n_marked, 1);
 }
-// :1279-1312: both tables into `nl` / `no` without the marked landmarks and the observations that name one, order kept; the removed
-// observations' ids and keyframe indices in rem_id / rem_kf.  counts: {landmarks kept, observations kept, observations removed}.
-__global__ __launch_bounds__(256) void k_prune_compact(LmView lm, int nlm, const int* __restrict__ flag, LmView nl, ObView ob, int nob, ObView no,
-                                                       i64* __restrict__ rem_id, int* __restrict__ rem_kf, int* __restrict__ counts) {
-  __shared__ int s_w[4];
-  int kl = 0;
-  for (int s0 = 0; s0 < nlm; s0 += 256) {
-    const int s = s0 + threadIdx.x;
-    const bool keep = s < nlm && flag[s] == 0;
-    int total;
-    const int p = kl + block_rank256(keep, s_w, total);
-    if (keep) {
-      nl.id[p] = lm.id[s]; nl.seen[p] = lm.seen[s]; nl.cls[p] = lm.cls[s]; nl.cnt[p] = lm.cnt[s];
-      nl.xyz[3 * p] = lm.xyz[3 * s]; nl.xyz[3 * p + 1] = lm.xyz[3 * s + 1]; nl.xyz[3 * p + 2] = lm.xyz[3 * s + 2];
-      copy32(nl.desc + 32 * (size_t)p, lm.desc + 32 * (size_t)s);
-    }
-    kl += total;
-  }
-  int ko = 0, kr = 0;
-  for (int i0 = 0; i0 < nob; i0 += 256) {
-    const int i = i0 + threadIdx.x;
-    bool keep = false, gone = false;
-    if (i < nob) {
-      const int s = lm_find(lm.id, nlm, ob.lm[i]);
-      gone = s >= 0 && flag[s] != 0;
-      keep = !gone;
-    }
-    int total;
-    const int p = ko + block_rank256(keep, s_w, total);
-    if (keep) {
-      no.id[p] = ob.id[i]; no.frame[p] = ob.frame[i]; no.lm[p] = ob.lm[i]; no.kf[p] = ob.kf[i]; no.cls[p] = ob.cls[i];
-      no.px[2 * p] = ob.px[2 * i]; no.px[2 * p + 1] = ob.px[2 * i + 1];
-      copy32(no.desc + 32 * (size_t)p, ob.desc + 32 * (size_t)i);
-    }
-    ko += total;
-    const int r = kr + block_rank256(gone, s_w, total);
-    if (gone) { rem_id[r] = ob.id[i]; rem_kf[r] = ob.kf[i]; }
-    kr += total;
-  }
-  if (threadIdx.x == 0) { counts[0] = kl; counts[1] = ko; counts[2] = kr; }
+// :1279-1312: an observation leaves iff it names a marked landmark
+__global__ __launch_bounds__(256) void k_prune_ob_flag(const i64* __restrict__ lm_id, int nlm, const int* __restrict__ lm_gone, const i64* __restrict__ ob_lm, int nob,
+                                                       int* __restrict__ keep, int* __restrict__ gone) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nob) return;
+  const int s = lm_find(lm_id, nlm, ob_lm[i]);
+  const int g = (s >= 0 && lm_gone[s] != 0) ? 1 : 0;
+  keep[i] = 1 - g; gone[i] = g;
 }
+
+#ifdef DVS_TEST_HOOKS
+struct IndexEmit {   // dvs_test_compact_rows: the flagged rows' indices
+  int* out;
+  __device__ void operator()(size_t i, size_t p) const { out[p] = (int)i; }
+};
+#endif
 
 }  // namespace dvs
 
@@ -696,34 +675,19 @@ dvs_status dvs_backend_prune(dvs_backend* h, int32_t now_sec, uint32_t now_nanos
   hipStream_t st = h->ctx->stream;
   const i64 now = (i64)now_sec * 1000000000ll + (i64)now_nanosec;
   BackendSmall* sm = h->s_small.get();
-  DVS_TRY(h->prune_lm.grow((size_t)nlm));
+  DVS_TRY(compact_grow(h));
   DVS_HIP(hipMemsetAsync(&sm->marked, 0, 4, st));
-  hipLaunchKernelGGL(k_prune_mark, dim3((nlm + 255) / 256), dim3(256), 0, st, h->lm.view(), nlm, now, h->P.prune_min_observations, h->P.prune_max_age_sec, h->prune_lm.flag.get(), &sm->marked);
+  hipLaunchKernelGGL(k_prune_mark, dim3((nlm + 255) / 256), dim3(256), 0, st, h->lm.view(), nlm, now, h->P.prune_min_observations, h->P.prune_max_age_sec, h->cmp_lm.keep.get(),
+                     h->cmp_lm.gone.get(), &sm->marked);
   DVS_HIP(hipGetLastError());
   int marked = 0;
   DVS_TRY(small_read(h, &sm->marked, &marked));
   if (marked == 0) return DVS_OK;                    // the common BA cycle: nothing to compact
-  // the tables are compacted into the handle's spare pair, which then changes places with them
-  DVS_TRY(table_match_spare(h->lm_spare, h->lm)); DVS_TRY(table_match_spare(h->ob_spare, h->ob));
-  DVS_TRY(h->prune_ob.grow((size_t)nob));
-  LmTable& nl = h->lm_spare; ObTable& no = h->ob_spare;
-  const Column<int>& rem_kf = h->prune_ob.rem_kf; const Column<i64>& rem_id = h->prune_ob.rem_id;
-  hipLaunchKernelGGL(k_prune_compact, dim3(1), dim3(256), 0, st, h->lm.view(), nlm, (const int*)h->prune_lm.flag.get(), nl.view(), h->ob.view(), nob, no.view(), rem_id.get(), rem_kf.get(),
-                     sm->counts);
-  DVS_HIP(hipGetLastError());
-  int counts[3] = {0, 0, 0};
-  DVS_TRY(small_read(h, sm->counts, counts, 3));
-  if (counts[0] < 0 || counts[0] > nlm || counts[1] + counts[2] != nob) { set_error("dvs_backend_prune: inconsistent counts %d %d %d", counts[0], counts[1], counts[2]); return DVS_ERR_HIP; }
-  std::vector<i64> rid((size_t)counts[2]);
-  std::vector<int> rkf((size_t)counts[2]);
-  if (counts[2]) {
-    DVS_TRY(copy_out(rid.data(), rem_id, rid.size(), st)); DVS_TRY(copy_out(rkf.data(), rem_kf, rkf.size(), st));
-    DVS_HIP(hipStreamSynchronize(st));
-  }
-  backend_drop_observation_ids(h, rid, rkf);
-  std::swap(h->lm, h->lm_spare); std::swap(h->ob, h->ob_spare);
-  *removed_landmarks = nlm - counts[0]; *removed_observations = counts[2];
-  h->nlm = counts[0]; h->nob = counts[1];
+  if (nob) hipLaunchKernelGGL(k_prune_ob_flag, dim3((nob + 255) / 256), dim3(256), 0, st, (const i64*)h->lm.id.get(), nlm, (const int*)h->cmp_lm.gone.get(), (const i64*)h->ob.lm.get(),
+                              nob, h->cmp_ob.keep.get(), h->cmp_ob.gone.get());
+  TablesReplaced done;
+  DVS_TRY(tables_replace(h, "dvs_backend_prune", h->cmp_lm.keep.get(), RowAsIs(), (i64)nlm - marked, h->cmp_ob.keep.get(), RowAsIs(), -1, h->cmp_ob.gone.get(), &done));
+  *removed_landmarks = marked; *removed_observations = done.n_ob_gone;
   return DVS_OK;
 }
 
@@ -804,5 +768,27 @@ dvs_status dvs_backend_get_keyframes(dvs_backend* h, int32_t cap, int64_t cap_ob
   if (obs_offsets) obs_offsets[nkf] = o;
   return DVS_OK;
 }
+
+#ifdef DVS_TEST_HOOKS   // libdvslam_hip_test.so only (include/dvslam_hip_test.h)
+dvs_status dvs_test_compact_rows(dvs_backend* h, int32_t n, const int32_t* flags, int32_t* out_pos, int64_t* out_total) {
+  DVS_ARG(h && n >= 0 && out_total && (n == 0 || (flags && out_pos)));
+  DVS_HIP(hipSetDevice(h->device));
+  hipStream_t st = h->ctx->stream;
+  DVS_TRY(h->blk.grow((size_t)n / 256 + 2));
+  DVS_TRY(grow(h->a_int, h->c_aint, 2 * (size_t)n));
+  int* d_flag = h->a_int.get();
+  int* d_out = d_flag + n;
+  if (n) {
+    DVS_HIP(hipMemcpyAsync(d_flag, flags, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    DVS_HIP(hipMemsetAsync(d_out, 0xFF, (size_t)n * 4, st));
+  }
+  i64 total = -1;
+  DVS_TRY(compact_rows(h, d_flag, n, IndexEmit{d_out}, &total));
+  if (n) DVS_HIP(hipMemcpyAsync(out_pos, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  DVS_HIP(hipStreamSynchronize(st));
+  *out_total = total;
+  return DVS_OK;
+}
+#endif  // DVS_TEST_HOOKS
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // backend_internal.h — the mapping backend handle (dvs_backend, include/dvslam_hip.h) shared by backend.hip, loop_close.hip,
-// covisibility.hip, kf_cull.hip, landmark_refresh.hip, lm_cull.hip and map_track.hip's recording: the views of the landmark and observation tables that kernels take, the owners of the tables, the keyframe record,
-// the counter block, the row groups of per-call scratch and the handle itself.  Internal to the library, as loop_internal.h and
-// bow_internal.h are.
+// covisibility.hip, kf_cull.hip, landmark_refresh.hip, lm_cull.hip and map_track.hip's recording: the views of the landmark and observation
+// tables that kernels take and the one copy of a row of each, the owners of the tables, the keyframe record, the counter block, the row
+// groups of per-call scratch and the handle itself.  What removes rows from the tables does it through table_compact.h, which builds on
+// this header.  Internal to the library, as loop_internal.h and bow_internal.h are.
 #pragma once
 #include <stddef.h>
 #include <tuple>
@@ -75,6 +76,20 @@ template <class Table> dvs_status table_regrow(Table& live, size_t need, size_t 
   live = std::move(t);
   return DVS_OK;
 }
+// One row of a table into row p of another, every column: the only place that lists a table's columns for a copy.  A caller that changes
+// a column stores it again behind the copy.
+static_assert(std::tuple_size<decltype(LmTable::columns(std::declval<LmTable&>()))>::value == 6, "lm_row_copy writes every column of the landmark table");
+__device__ __forceinline__ void lm_row_copy(const LmView& dst, size_t p, const LmView& src, size_t s) {
+  dst.id[p] = src.id[s]; dst.seen[p] = src.seen[s]; dst.cls[p] = src.cls[s]; dst.cnt[p] = src.cnt[s];
+  dst.xyz[3 * p] = src.xyz[3 * s]; dst.xyz[3 * p + 1] = src.xyz[3 * s + 1]; dst.xyz[3 * p + 2] = src.xyz[3 * s + 2];
+  copy32(dst.desc + 32 * p, src.desc + 32 * s);
+}
+static_assert(std::tuple_size<decltype(ObTable::columns(std::declval<ObTable&>()))>::value == 7, "ob_row_copy writes every column of the observation table");
+__device__ __forceinline__ void ob_row_copy(const ObView& dst, size_t p, const ObView& src, size_t s) {
+  dst.id[p] = src.id[s]; dst.frame[p] = src.frame[s]; dst.lm[p] = src.lm[s]; dst.kf[p] = src.kf[s]; dst.cls[p] = src.cls[s];
+  dst.px[2 * p] = src.px[2 * s]; dst.px[2 * p + 1] = src.px[2 * s + 1];
+  copy32(dst.desc + 32 * p, src.desc + 32 * s);
+}
 // the spare table that receives a compaction of `live` and then changes places with it: as large as the live one
 template <class Table> dvs_status table_match_spare(Table& spare, const Table& live) { return spare.cap != live.cap ? table_alloc(spare, live.cap) : DVS_OK; }
 
@@ -82,7 +97,8 @@ struct KeyframeRec { uint64_t frame_id; i64 stamp; std::vector<uint64_t> obs_ids
 
 // The 256 ints of counters and small lists that kernels write and the host reads back, one block per handle (dvs_backend::s_small).
 // add_keyframe uploads the whole block: its two lists, and zeros everywhere else.
-struct FuseCounts { int n_query, n_sources, n_targets, n_proposals, n_fused, n_kept, n_anchored, pad; };   // n_anchored: k_anchors, cleared on its own
+struct FuseCounts { int n_query, n_sources, n_targets, n_proposals, n_fused, n_kept, n_anchored, pad; };   // n_anchored: k_anchors, cleared on its own;
+                                                                                                          // n_kept: no longer written, the compaction's total is read instead
 struct CullCounts { int n_culled, n_ob_removed, n_lm_removed, pad; };   // k_cull_walk; k_cull_ob_flag; k_cull_lm_flag
 struct RefreshCounts { int n_bin[3], n_in_scope, n_without_views, max_views, n_changed, pad; };   // k_lr_bin; n_changed: k_lr_apply
 struct LmCullCounts { int n_by_ratio, n_weak, pad[2]; };   // k_lc_decide
@@ -90,8 +106,8 @@ struct BackendSmall {
   int filtered[64];     // add_keyframe: the filtered class ids
   int classes[64];       //               the distinct unfiltered classes of the keyframe
   int class_cnt[64];     //               k_categorize: kept observations per class
-  int counts[4];         // the call's one-block kernel: k_class_gather {landmarks of the class}, k_window_gather {observations, landmarks},
-                         // k_prune_compact {landmarks kept, observations kept, observations removed}
+  int counts[4];         // the call's one-block kernel: k_class_gather {landmarks of the class}, k_window_gather {observations, landmarks}.
+                         // counts[0 .. 2] are no longer written by prune: its compactions' totals are read instead (table_compact.h)
   int marked, pad0[3];   // k_prune_mark: marked landmarks
   FuseCounts fuse;       // loop_close.hip
   int left_out, pad1[3];    // covisibility.hip, k_covis_ob_flag: rows left out of the local window
@@ -149,15 +165,20 @@ struct SlidingLmRows {    // the sliding window per landmark: the window's colum
   size_t cap = 0;
   dvs_status grow(size_t nlm) { return grow_rows(cap, nlm + 1, nlm + 1 + nlm / 2, l.id, l.cls, l.xyz, flag, pos); }
 };
-struct PruneLmRows {
-  Column<int> flag;
+struct CompactLmRows {    // what removes rows from the tables (table_compact.h) per landmark row: stays, leaves
+  Column<int> keep, gone;
   size_t cap = 0;
-  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2, flag); }
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, keep, gone); }
 };
-struct PruneObRows {      // the removed observations
-  Column<int> rem_kf; Column<i64> rem_id;
+struct CompactObRows {    // and per observation row: stays, leaves; the ids and keyframe indices of the rows that leave
+  Column<int> keep, gone, rem_kf; Column<i64> rem_id;
   size_t cap = 0;
-  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2, rem_kf, rem_id); }
+  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2 + 64, keep, gone, rem_kf, rem_id); }
+};
+struct BlockRows {        // per 256-row block of a table: the ordered compaction's counts and their scan, which ends with the total
+  Column<int> cnt; Column<i64, 1, 1> offs;
+  size_t cap = 0;
+  dvs_status grow(size_t nblk) { return grow_rows(cap, nblk, nblk + nblk / 2, cnt, offs); }
 };
 struct FuseLmRows {       // fusion per landmark row: flags, proposals, the resolved pairs and the pair list
   Column<int> flag, src, propb, bsrc, redirect, partner; Column<unsigned long long> prope, beste; Column<i64> psurv, prem; Column<double> pe;
@@ -184,11 +205,6 @@ struct CovisLmRows {      // per landmark row: in U, row in U; U's columns (the 
   size_t cap = 0;
   dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, flag, pos, slot, u.cls, u.id, u.xyz, desc); }
 };
-struct CovisBlockRows {   // per 256-row block of a table: the ordered compaction's counts and their scan, which ends with the total
-  Column<int> cnt; Column<i64, 1, 1> offs;
-  size_t cap = 0;
-  dvs_status grow(size_t nblk) { return grow_rows(cap, nblk, nblk + nblk / 2, cnt, offs); }
-};
 struct CovisWeightRows {  // requested rows x keyframes: weights and neighbour lists, packed CSR.  Exact: the full graph asks for nkf * nkf once
   Column<int> w, nbt, nbi, nbw, pki, pkw;
   size_t cap = 0;
@@ -200,15 +216,10 @@ struct CullKfRows {       // culling per keyframe, one row more for the scan's e
   size_t cap = 0;
   dvs_status grow(size_t nkf) { return grow_rows(cap, nkf + 1, nkf + 1 + nkf / 2, state, n_obs, r0, flag, walk, culled, keep, newidx); }
 };
-struct CullLmRows {       // culling per landmark row: c(L), removed rows, stays in the table
-  Column<int> c, removed, keep;
+struct CullLmRows {       // culling per landmark row: c(L), removed rows
+  Column<int> c, removed;
   size_t cap = 0;
-  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, c, removed, keep); }
-};
-struct CullObRows {       // culling per observation row: stays in the table
-  Column<int> keep;
-  size_t cap = 0;
-  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2 + 64, keep); }
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, c, removed); }
 };
 struct RefreshLmRows {    // landmark refresh per landmark row: views, in scope; the three bins' lists; the chosen view (index into the views), its
                           // median and observation id; the viewing geometry
@@ -224,16 +235,11 @@ struct LmStatRows {      // the tracking statistics, a side table of the landmar
 };
 struct StatView { i64* id; int* visible; int* found; };
 inline StatView stat_view(const LmStatRows& t) { return StatView{t.id.get(), t.visible.get(), t.found.get()}; }
-struct LmCullLmRows {     // landmark culling per landmark row: views, age in keyframes, the rule that holds (0: none), stays, leaves; the culled ids and
-                          // their reasons compacted
-  Column<int> n, age, reason, keep, mark, creason; Column<i64> cid;
+struct LmCullLmRows {     // landmark culling per landmark row: views, age in keyframes, the rule that holds (0: none), leaves; the culled ids and their
+                          // reasons compacted
+  Column<int> n, age, reason, mark, creason; Column<i64> cid;
   size_t cap = 0;
-  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, n, age, reason, keep, mark, creason, cid); }
-};
-struct LmCullObRows {     // landmark culling per observation row: stays, leaves
-  Column<int> keep, gone;
-  size_t cap = 0;
-  dvs_status grow(size_t nob) { return grow_rows(cap, nob, nob + nob / 2 + 64, keep, gone); }
+  dvs_status grow(size_t nlm) { return grow_rows(cap, nlm, nlm + nlm / 2 + 64, n, age, reason, mark, creason, cid); }
 };
 
 }  // namespace dvs
@@ -243,7 +249,7 @@ struct dvs_backend {
   int device = 0;
   dvs_matcher* ctx = nullptr;
   // the map
-  dvs::LmTable lm, lm_spare; dvs::ObTable ob, ob_spare;          // the spare pair receives dvs_backend_prune's compaction
+  dvs::LmTable lm, lm_spare; dvs::ObTable ob, ob_spare;          // the spare pair receives a compaction and changes places (table_compact.h)
   dvs::Column<double, 9> kf_R; dvs::Column<double, 3> kf_t;
   size_t cap_kf = 0;
   int nlm = 0, nob = 0;
@@ -253,17 +259,18 @@ struct dvs_backend {
   // the counter block, the keyframe's pose
   dvs::DeviceBuf<dvs::BackendSmall> s_small;
   dvs::DeviceBuf<double> d_Rt;
-  // row groups: add_keyframe and the views; the sliding window; prune; fusion (loop_close.hip); covisibility (covisibility.hip)
+  // row groups: add_keyframe and the views; the sliding window; the compaction (table_compact.h); fusion (loop_close.hip); covisibility
+  // (covisibility.hip)
   dvs::KeyframeObRows kf_ob; dvs::ClassLmRows cls_lm; dvs::ViewLmRows v_lm; dvs::ViewObRows v_ob;
   dvs::SlidingObRows win_ob; dvs::SlidingLmRows win_lm;
-  dvs::PruneLmRows prune_lm; dvs::PruneObRows prune_ob;
+  dvs::CompactLmRows cmp_lm; dvs::CompactObRows cmp_ob; dvs::BlockRows blk;
   dvs::FuseLmRows fuse_lm; dvs::FuseQueryRows fuse_q;
-  dvs::CovisObRows cv_ob; dvs::CovisKfRows cv_kf; dvs::CovisLmRows cv_lm; dvs::CovisBlockRows cv_blk; dvs::CovisWeightRows cv_w;
-  dvs::CullKfRows cull_kf; dvs::CullLmRows cull_lm; dvs::CullObRows cull_ob;
+  dvs::CovisObRows cv_ob; dvs::CovisKfRows cv_kf; dvs::CovisLmRows cv_lm; dvs::CovisWeightRows cv_w;
+  dvs::CullKfRows cull_kf; dvs::CullLmRows cull_lm;
   dvs::RefreshLmRows lr_lm;
   // landmark culling (lm_cull.hip): the statistics and their spare (not allocated before first use), the recording switch, the calls that recorded
   dvs::LmStatRows stat, stat_spare; int nstat = 0; int stats_on = 0; dvs::i64 n_recorded = 0;
-  dvs::LmCullLmRows lc_lm; dvs::LmCullObRows lc_ob;
+  dvs::LmCullLmRows lc_lm;
   // single blocks (device_mem.h, grow): detections, candidate pairs, per-call arguments, anchors per landmark, landmark row per observation
   dvs::DeviceBuf<dvs::DetRec> s_det; dvs::DeviceBuf<dvs::PairRec> p_rec; dvs::DeviceBuf<int> a_int, f_obrow; dvs::Column<int> f_anchor; dvs::DeviceBuf<dvs::i64> a_i64; dvs::DeviceBuf<double> a_dbl;
   size_t c_det = 0, c_pair = 0, c_aint = 0, c_ai64 = 0, c_adbl = 0, c_flm = 0, c_fob = 0;
@@ -304,13 +311,11 @@ dvs_status covis_grow(dvs_backend* h, size_t rows);
 dvs_status covis_prepare(dvs_backend* h);
 // `rows` rows of W from keyframe row0 on into cv_w.w, and their neighbour lists at theta into cv_w.nbi / cv_w.nbw / cv_kf.nbc
 dvs_status covis_rows(dvs_backend* h, int row0, int rows, int theta);
-// the ordered compaction's steps 1 and 2 over n flags (flag == 1: the row stays): cv_blk.offs[0 .. *nblk], the total last
-dvs_status covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk);
 // the viewing geometry of every landmark row ("Landmark refresh" in the header; landmark_refresh.hip) into lr_lm.normal / .range / .ncnt:
 // the views are rebuilt, everything is enqueued on the handle's stream; needs at least one landmark
 dvs_status refresh_geometry(dvs_backend* h);
 // the keyframes' observation_ids lose the ids in `gone` (:1303-1312); kf: the keyframe index of each removed row -> the keyframes that lost
-// at least one id (backend.hip; the host half of dvs_backend_prune and dvs_backend_cull_landmarks)
+// at least one id (backend.hip; table_compact.h's cascade for dvs_backend_prune and dvs_backend_cull_landmarks)
 int backend_drop_observation_ids(dvs_backend* h, const std::vector<i64>& gone, const std::vector<int>& kf);
 // the statistics aligned to the landmark table as it stands ("Landmark culling" in the header; lm_cull.hip): enqueued on the handle's stream;
 // afterwards h->nstat == h->nlm and statistics row s is landmark row s

@@ -16,9 +16,9 @@
 //   k_covis_count      the same histogram over U's rows instead of S_a's: f_c = |S_c n U| for every keyframe
 //   k_covis_neighbours per row: ordered compaction of the entries that pass theta, then placement by the rank of the 64-bit key
 //                      (weight, ~index) — the keys are distinct, so the rank is the position.  The fixed ranking is the same kernel on f.
-//   k_covis_lm_flag / k_covis_blk_count / k_covis_lm_gather   U: flags, then an ordered compaction over the whole table in three steps
-//                      (256 rows per workgroup: count, scan of the workgroups' counts, gather at block offset + block_rank256)
-//   k_covis_ob_flag / k_covis_ob_gather   the window's observations: first rows of their (keyframe, landmark) pair, the same compaction
+//   k_covis_lm_flag / CovisLmEmit   U: flags, then the ordered compaction over the whole table (table_compact.h's compact_rows) of the
+//                      columns a window or a local map takes
+//   k_covis_ob_flag / CovisObEmit   the window's observations: first rows of their (keyframe, landmark) pair, the same compaction
 // Host decisions between the launches (who is free, who is fixed) read back one row of weights and one short list each.
 #include <string.h>
 #include <algorithm>
@@ -28,6 +28,7 @@
 #include "matcher.h"
 #include "backend_internal.h"
 #include "block_ops.h"
+#include "table_compact.h"
 
 namespace dvs {
 
@@ -166,29 +167,16 @@ __global__ __launch_bounds__(256) void k_covis_lm_flag(int nlm, const i64* __res
   }
   flag[s] = f;
 }
-// ordered compaction of a whole table, step 1: how many of each workgroup's 256 rows are flagged (step 2: match.hip's scan)
-__global__ __launch_bounds__(256) void k_covis_blk_count(const int* __restrict__ flag, int n, int* __restrict__ blk) {
-  __shared__ int s_w[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  int total;
-  block_rank256(i < n && flag[i] == 1, s_w, total);
-  if (threadIdx.x == 0) blk[blockIdx.x] = total;
-}
-// step 3 for the landmarks: U's columns in ascending id (the table's order), every flagged row's position in U, U's rows
-__global__ __launch_bounds__(256) void k_covis_lm_gather(LmView lm, int nlm, const int* __restrict__ flag, const i64* __restrict__ blk_offs, int want_desc,
-                                                         int* __restrict__ pos, int* __restrict__ uslot, i64* __restrict__ uid, int* __restrict__ ucls,
-                                                         float* __restrict__ uxyz, uint8_t* __restrict__ udesc) {
-  __shared__ int s_w[4];
-  const int s = blockIdx.x * 256 + threadIdx.x;
-  const bool keep = s < nlm && flag[s] == 1;
-  int total;
-  const int p = (int)blk_offs[blockIdx.x] + block_rank256(keep, s_w, total);
-  if (!keep) return;
-  pos[s] = p; uslot[p] = s;
-  uid[p] = lm.id[s]; ucls[p] = lm.cls[s];
-  uxyz[3 * (size_t)p] = lm.xyz[3 * (size_t)s]; uxyz[3 * (size_t)p + 1] = lm.xyz[3 * (size_t)s + 1]; uxyz[3 * (size_t)p + 2] = lm.xyz[3 * (size_t)s + 2];
-  if (want_desc) copy32(udesc + 32 * (size_t)p, lm.desc + 32 * (size_t)s);
-}
+// the compaction for the landmarks: U's columns in ascending id (the table's order), every flagged row's position in U, U's rows
+struct CovisLmEmit {
+  LmView lm; int want_desc; int* pos; int* uslot; i64* uid; int* ucls; float* uxyz; uint8_t* udesc;
+  __device__ void operator()(size_t s, size_t p) const {
+    pos[s] = (int)p; uslot[p] = (int)s;
+    uid[p] = lm.id[s]; ucls[p] = lm.cls[s];
+    uxyz[3 * p] = lm.xyz[3 * s]; uxyz[3 * p + 1] = lm.xyz[3 * s + 1]; uxyz[3 * p + 2] = lm.xyz[3 * s + 2];
+    if (want_desc) copy32(udesc + 32 * p, lm.desc + 32 * s);
+  }
+};
 // the window's observation rows (oflag starts at zero): a view of a landmark of U from a keyframe of the window (role != 0) is in if it
 // counts — it is the first row of its (keyframe, landmark) pair — and is a left-out row otherwise
 __global__ __launch_bounds__(256) void k_covis_ob_flag(int nlm, const i64* __restrict__ view_offs, const int* __restrict__ view_kf, const int* __restrict__ cv_kf,
@@ -202,19 +190,14 @@ __global__ __launch_bounds__(256) void k_covis_ob_flag(int nlm, const i64* __res
     if (cv_kf[p] >= 0) oflag[v_obs[p]] = 1; else atomicAdd(n_left, 1);
   }
 }
-__global__ __launch_bounds__(256) void k_covis_ob_gather(ObView ob, int nob, const int* __restrict__ oflag, const i64* __restrict__ blk_offs, const int* __restrict__ ob_slot,
-                                                         const int* __restrict__ lpos, float* __restrict__ opx, i64* __restrict__ olm, int* __restrict__ ocls,
-                                                         i64* __restrict__ oframe, int* __restrict__ olmidx) {
-  __shared__ int s_w[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool keep = i < nob && oflag[i] == 1;
-  int total;
-  const int p = (int)blk_offs[blockIdx.x] + block_rank256(keep, s_w, total);
-  if (!keep) return;
-  opx[2 * (size_t)p] = ob.px[2 * (size_t)i]; opx[2 * (size_t)p + 1] = ob.px[2 * (size_t)i + 1];
-  olm[p] = ob.lm[i]; ocls[p] = ob.cls[i]; oframe[p] = ob.frame[i];
-  olmidx[p] = lpos[ob_slot[i]];            // flagged rows have a landmark of U: ob_slot >= 0
-}
+struct CovisObEmit {
+  ObView ob; const int* ob_slot; const int* lpos; float* opx; i64* olm; int* ocls; i64* oframe; int* olmidx;
+  __device__ void operator()(size_t i, size_t p) const {
+    opx[2 * p] = ob.px[2 * i]; opx[2 * p + 1] = ob.px[2 * i + 1];
+    olm[p] = ob.lm[i]; ocls[p] = ob.cls[i]; oframe[p] = ob.frame[i];
+    olmidx[p] = lpos[ob_slot[i]];            // flagged rows have a landmark of U: ob_slot >= 0
+  }
+};
 
 }  // namespace dvs
 
@@ -233,7 +216,7 @@ dvs_status covis_check(const dvs_covis_params& P) {
 
 }  // namespace
 
-// covis_limit, covis_grow, covis_prepare, covis_rows and covis_block_offsets are shared with kf_cull.hip (backend_internal.h)
+// covis_limit, covis_grow, covis_prepare and covis_rows are shared with kf_cull.hip (backend_internal.h)
 dvs_status dvs::covis_limit(const dvs_backend* h, const char* who) {
   if (h->kfs.size() > (size_t)DVS_COVIS_MAX_KEYFRAMES) {
     set_error("%s: %zu keyframes, the row kernel's LDS histogram takes %d", who, h->kfs.size(), DVS_COVIS_MAX_KEYFRAMES);
@@ -246,7 +229,7 @@ dvs_status dvs::covis_limit(const dvs_backend* h, const char* who) {
 dvs_status dvs::covis_grow(dvs_backend* h, size_t rows) {
   const size_t nkf = h->kfs.size(), nlm = (size_t)h->nlm, nob = (size_t)h->nob;
   DVS_TRY(h->cv_ob.grow(nob)); DVS_TRY(h->cv_kf.grow(nkf)); DVS_TRY(h->cv_lm.grow(nlm));
-  DVS_TRY(h->cv_blk.grow(std::max(nlm, nob) / 256 + 2));
+  DVS_TRY(h->blk.grow(std::max(nlm, nob) / 256 + 2));
   return h->cv_w.grow(std::max<size_t>(rows * nkf, 1));
 }
 
@@ -275,16 +258,6 @@ dvs_status dvs::covis_rows(dvs_backend* h, int row0, int rows, int theta) {
                      (const i64*)h->v_lm.offs.get(), (const int*)h->cv_ob.kf.get(), h->cv_w.w.get());
   hipLaunchKernelGGL(k_covis_neighbours, dim3(rows), dim3(256), 0, st, nkf, row0, (const int*)h->cv_w.w.get(), theta, (const int*)nullptr, h->cv_w.nbt.get(), h->cv_w.nbi.get(),
                      h->cv_w.nbw.get(), h->cv_kf.nbc.get());
-  DVS_HIP(hipGetLastError());
-  return DVS_OK;
-}
-
-// ordered compaction's steps 1 and 2 over n flags: cv_blkoffs[0 .. nblk], the total last
-dvs_status dvs::covis_block_offsets(dvs_backend* h, const int* flag, int n, int* nblk) {
-  hipStream_t st = h->ctx->stream;
-  *nblk = (n + 255) / 256;
-  if (*nblk) hipLaunchKernelGGL(k_covis_blk_count, dim3(*nblk), dim3(256), 0, st, flag, n, h->cv_blk.cnt.get());
-  launch_scan_counts(st, (const int*)h->cv_blk.cnt.get(), *nblk, h->cv_blk.offs.get());
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
@@ -329,17 +302,14 @@ dvs_status covis_local(dvs_backend* h, int r, const dvs_covis_params& P, bool wa
   DVS_HIP(hipMemcpyAsync(h->cv_kf.role.get(), role.data(), (size_t)nkf * sizeof(int), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_covis_lm_flag, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, (const i64*)h->v_lm.offs.get(), (const int*)h->cv_ob.kf.get(), (const int*)h->cv_kf.role.get(),
                      h->cv_lm.flag.get());
-  int nblk = 0;
-  DVS_TRY(covis_block_offsets(h, h->cv_lm.flag.get(), nlm, &nblk));
-  hipLaunchKernelGGL(k_covis_lm_gather, dim3(nblk), dim3(256), 0, st, h->lm.view(), nlm, (const int*)h->cv_lm.flag.get(), (const i64*)h->cv_blk.offs.get(), want_desc ? 1 : 0,
-                     h->cv_lm.pos.get(), h->cv_lm.slot.get(), h->cv_lm.u.id.get(), h->cv_lm.u.cls.get(), h->cv_lm.u.xyz.get(), h->cv_lm.desc.get());
-  DVS_HIP(hipGetLastError());
   i64 nu = 0;
+  DVS_TRY(compact_rows(h, h->cv_lm.flag.get(), nlm, CovisLmEmit{h->lm.view(), want_desc ? 1 : 0, h->cv_lm.pos.get(), h->cv_lm.slot.get(), h->cv_lm.u.id.get(), h->cv_lm.u.cls.get(),
+                                                                 h->cv_lm.u.xyz.get(), h->cv_lm.desc.get()}, &nu));
   int nfix = 0;
   std::vector<int> fx((size_t)std::max(P.max_fixed, 1));
   const int take_f = want_window ? std::min(P.max_fixed, nkf) : 0;
   if (want_window) {                                   // f over U, ranked among the keyframes that are not free
-    hipLaunchKernelGGL(k_covis_count, dim3(1), dim3(256), (size_t)nkf * 4, st, nkf, (const int*)h->cv_lm.slot.get(), (const i64*)h->cv_blk.offs.get() + nblk,
+    hipLaunchKernelGGL(k_covis_count, dim3(1), dim3(256), (size_t)nkf * 4, st, nkf, (const int*)h->cv_lm.slot.get(), compact_total(h, nlm),
                        (const i64*)h->v_lm.offs.get(), (const int*)h->cv_ob.kf.get(), h->cv_kf.f.get());
     hipLaunchKernelGGL(k_covis_neighbours, dim3(1), dim3(256), 0, st, nkf, -1, (const int*)h->cv_kf.f.get(), 1, (const int*)h->cv_kf.role.get(), h->cv_w.nbt.get(), h->cv_w.nbi.get(),
                        h->cv_w.nbw.get(), h->cv_kf.nbc.get());
@@ -347,7 +317,6 @@ dvs_status covis_local(dvs_backend* h, int r, const dvs_covis_params& P, bool wa
     if (take_f) DVS_TRY(copy_out(fx.data(), h->cv_w.nbi, (size_t)take_f, st));
     DVS_TRY(copy_out(&nfix, h->cv_kf.nbc, 1, st));
   }
-  DVS_HIP(hipMemcpyAsync(&nu, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
   DVS_HIP(hipStreamSynchronize(st));
   if (nu < 0 || nu > nlm || nfix < 0 || nfix > nkf) { set_error("covisibility: inconsistent counts %lld %d", (long long)nu, nfix); return DVS_ERR_HIP; }
   out->n_u = (int)nu;
@@ -370,13 +339,10 @@ dvs_status covis_local(dvs_backend* h, int r, const dvs_covis_params& P, bool wa
   DVS_HIP(hipMemsetAsync(d_left, 0, 4, st));
   hipLaunchKernelGGL(k_covis_ob_flag, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, (const i64*)h->v_lm.offs.get(), (const int*)h->v_ob.kf.get(), (const int*)h->cv_ob.kf.get(),
                      (const int*)h->v_ob.rows.get(), (const int*)h->cv_kf.role.get(), (const int*)h->cv_lm.flag.get(), h->cv_ob.flag.get(), d_left);
-  DVS_TRY(covis_block_offsets(h, h->cv_ob.flag.get(), nob, &nblk));
-  hipLaunchKernelGGL(k_covis_ob_gather, dim3(nblk), dim3(256), 0, st, h->ob.view(), nob, (const int*)h->cv_ob.flag.get(), (const i64*)h->cv_blk.offs.get(),
-                     (const int*)h->v_ob.slot.get(), (const int*)h->cv_lm.pos.get(), h->cv_ob.o.px.get(), h->cv_ob.o.lm.get(), h->cv_ob.o.cls.get(), h->cv_ob.o.frame.get(), h->cv_ob.o.lmidx.get());
-  DVS_HIP(hipGetLastError());
   i64 no = 0;
   int left = 0;
-  DVS_HIP(hipMemcpyAsync(&no, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
+  DVS_TRY(compact_rows(h, h->cv_ob.flag.get(), nob, CovisObEmit{h->ob.view(), h->v_ob.slot.get(), h->cv_lm.pos.get(), h->cv_ob.o.px.get(), h->cv_ob.o.lm.get(), h->cv_ob.o.cls.get(),
+                                                                 h->cv_ob.o.frame.get(), h->cv_ob.o.lmidx.get()}, &no));
   DVS_TRY(small_read(h, d_left, &left));
   if (no < 0 || no > nob || left < 0 || left > nob) { set_error("covisibility: inconsistent counts %lld %d", (long long)no, left); return DVS_ERR_HIP; }
   out->n_obs = (int)no; out->n_left = left;

@@ -5,7 +5,7 @@
 // (cv_ob.kf) and the keyframe -> landmarks CSR (cv_kf.offs / cv_ob.list, a keyframe's landmark rows distinct and ascending).
 //   k_cull_observers   c(L): a wavefront per landmark, its lanes stride the segment and count the counting views
 //   k_cull_initial     one workgroup per keyframe: n_k, R_k under the initial counts, and whether it is a candidate that is redundant now
-//   k_cull_walk_gather the initially redundant candidates in ascending index (ordered compaction, three steps).  c(.) only decreases
+//   WalkEmit           the initially redundant candidates in ascending index (table_compact.h's compact_rows).  c(.) only decreases
 //                      during the walk and n_k is constant, so a keyframe that is not redundant under the initial counts never becomes
 //                      redundant: the walk visits only this list.
 //   k_cull_walk        THE SEQUENTIAL PART.  One workgroup takes the listed keyframes in turn: its threads stride the keyframe's landmark
@@ -16,8 +16,8 @@
 //   k_cull_ob_flag / k_cull_lm_flag   the apply's flags: an observation row leaves iff its keyframe is culled; per landmark the removed
 //                      rows among ALL its views and whether it stays (it leaves only as an orphan, and only if asked)
 //   k_cull_kf_keep     keep flags of the keyframes; their exclusive scan is the new-index table ob.kf goes through
-//   k_cull_lm_gather / k_cull_ob_gather   both tables into the handle's spare pair by the ordered compaction of covisibility.hip
-//                      (k_covis_blk_count, the scan, gather at block offset + block_rank256), every column of the table
+//   CullLmFix / CullObFix   the apply is table_compact.h's tables_replace: a row that stays is copied, then observation_count loses the
+//                      removed rows and kf goes through the new-index table
 // Scope and protection are decided on the host (local scope reads one neighbour list through covis_rows) and arrive as a byte per keyframe.
 #include <string.h>
 #include <algorithm>
@@ -27,6 +27,7 @@
 #include "matcher.h"
 #include "backend_internal.h"
 #include "block_ops.h"
+#include "table_compact.h"
 
 namespace dvs {
 
@@ -59,15 +60,11 @@ __global__ __launch_bounds__(256) void k_cull_initial(const i64* __restrict__ kl
   if (threadIdx.x == 0) { n_obs[k] = n; r0[k] = r; flag[k] = (state[k] == CULL_KEPT && cull_redundant(r, n, percent)) ? 1 : 0; }
 }
 
-// ordered compaction's step 3 over the keyframes: the flagged ones in ascending index
-__global__ __launch_bounds__(256) void k_cull_walk_gather(const int* __restrict__ flag, int nkf, const i64* __restrict__ blk_offs, int* __restrict__ walk) {
-  __shared__ int s_w[4];
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  const bool keep = k < nkf && flag[k] == 1;
-  int total;
-  const int p = (int)blk_offs[blockIdx.x] + block_rank256(keep, s_w, total);
-  if (keep) walk[p] = k;
-}
+// the compaction over the keyframes: the flagged ones in ascending index
+struct WalkEmit {
+  int* walk;
+  __device__ void operator()(size_t k, size_t p) const { walk[p] = (int)k; }
+};
 
 // ONE workgroup.  culled[] and *n_culled start at zero.  c is read and written here and by nobody else while this runs.
 __global__ __launch_bounds__(256) void k_cull_walk(const i64* __restrict__ n_walk, int nkf, const int* __restrict__ walk, const i64* __restrict__ kl_offs,
@@ -134,36 +131,19 @@ __global__ __launch_bounds__(256) void k_cull_kf_keep(const int* __restrict__ cu
   if (k < nkf) keep[k] = culled[k] != 0 ? 0 : 1;
 }
 
-static_assert(std::tuple_size<decltype(LmTable::columns(std::declval<LmTable&>()))>::value == 6, "k_cull_lm_gather writes every column of the landmark table");
-static_assert(std::tuple_size<decltype(ObTable::columns(std::declval<ObTable&>()))>::value == 7, "k_cull_ob_gather writes every column of the observation table");
-// step 3 for the landmarks: the rows that stay, order kept, observation_count less the removed rows and never below 0
-__global__ __launch_bounds__(256) void k_cull_lm_gather(LmView lm, int nlm, const int* __restrict__ keep, const i64* __restrict__ blk_offs, const int* __restrict__ removed,
-                                                        LmView nl) {
-  __shared__ int s_w[4];
-  const int s = blockIdx.x * 256 + threadIdx.x;
-  const bool k = s < nlm && keep[s] == 1;
-  int total;
-  const size_t p = (size_t)blk_offs[blockIdx.x] + block_rank256(k, s_w, total);
-  if (!k) return;
-  nl.id[p] = lm.id[s]; nl.seen[p] = lm.seen[s]; nl.cls[p] = lm.cls[s]; nl.cnt[p] = max(lm.cnt[s] - removed[s], 0);
-  nl.xyz[3 * p] = lm.xyz[3 * (size_t)s]; nl.xyz[3 * p + 1] = lm.xyz[3 * (size_t)s + 1]; nl.xyz[3 * p + 2] = lm.xyz[3 * (size_t)s + 2];
-  copy32(nl.desc + 32 * p, lm.desc + 32 * (size_t)s);
-}
-// and for the observations: kf through the new-index table (the exclusive scan of the keyframes' keep flags)
-__global__ __launch_bounds__(256) void k_cull_ob_gather(ObView ob, int nob, const int* __restrict__ keep, const i64* __restrict__ blk_offs, const i64* __restrict__ newidx, int nkf,
-                                                        ObView no) {
-  __shared__ int s_w[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool k = i < nob && keep[i] == 1;
-  int total;
-  const size_t p = (size_t)blk_offs[blockIdx.x] + block_rank256(k, s_w, total);
-  if (!k) return;
-  const int kf = ob.kf[i];
-  no.id[p] = ob.id[i]; no.frame[p] = ob.frame[i]; no.lm[p] = ob.lm[i]; no.cls[p] = ob.cls[i];
-  no.kf[p] = (kf >= 0 && kf < nkf) ? (int)newidx[kf] : kf;
-  no.px[2 * p] = ob.px[2 * (size_t)i]; no.px[2 * p + 1] = ob.px[2 * (size_t)i + 1];
-  copy32(no.desc + 32 * p, ob.desc + 32 * (size_t)i);
-}
+// a landmark row that stays: observation_count less the removed rows and never below 0
+struct CullLmFix {
+  const int* removed;
+  __device__ void operator()(const LmView& nl, size_t p, const LmView& lm, size_t s) const { nl.cnt[p] = max(lm.cnt[s] - removed[s], 0); }
+};
+// an observation row that stays: kf through the new-index table (the exclusive scan of the keyframes' keep flags)
+struct CullObFix {
+  const i64* newidx; int nkf;
+  __device__ void operator()(const ObView& no, size_t p, const ObView& ob, size_t i) const {
+    const int kf = ob.kf[i];
+    if (kf >= 0 && kf < nkf) no.kf[p] = (int)newidx[kf];
+  }
+};
 
 }  // namespace dvs
 
@@ -238,8 +218,8 @@ dvs_status dvs_backend_cull_keyframes(dvs_backend* h, uint64_t ref_frame_id, con
     DVS_HIP(hipSetDevice(h->device));
     st = h->ctx->stream;
     DVS_TRY(covis_grow(h, local ? 1 : 0));
-    DVS_TRY(h->cv_blk.grow((size_t)std::max(std::max(nlm, nob), nkf) / 256 + 2));
-    DVS_TRY(h->cull_kf.grow((size_t)nkf)); DVS_TRY(h->cull_lm.grow((size_t)nlm)); DVS_TRY(h->cull_ob.grow((size_t)nob));
+    DVS_TRY(compact_grow(h)); DVS_TRY(h->blk.grow((size_t)nkf / 256 + 2));
+    DVS_TRY(h->cull_kf.grow((size_t)nkf)); DVS_TRY(h->cull_lm.grow((size_t)nlm));
     DVS_TRY(covis_prepare(h));
     if (local) {                                       // N(ref; min_weight), the whole list
       DVS_TRY(covis_rows(h, r, 1, P.min_weight));
@@ -269,10 +249,8 @@ dvs_status dvs_backend_cull_keyframes(dvs_backend* h, uint64_t ref_frame_id, con
     hipLaunchKernelGGL(k_cull_observers, dim3((nlm + 3) / 4), dim3(256), 0, st, nlm, voffs, (const int*)h->cv_ob.kf.get(), h->cull_lm.c.get());
     hipLaunchKernelGGL(k_cull_initial, dim3(nkf), dim3(256), 0, st, kl_offs, list, (const int*)h->cull_lm.c.get(), P.min_observers, P.redundancy_percent,
                        (const uint8_t*)h->cull_kf.state.get(), h->cull_kf.n_obs.get(), h->cull_kf.r0.get(), h->cull_kf.flag.get());
-    int nblk = 0;
-    DVS_TRY(covis_block_offsets(h, h->cull_kf.flag.get(), nkf, &nblk));
-    hipLaunchKernelGGL(k_cull_walk_gather, dim3(nblk), dim3(256), 0, st, (const int*)h->cull_kf.flag.get(), nkf, (const i64*)h->cv_blk.offs.get(), h->cull_kf.walk.get());
-    hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(256), 0, st, (const i64*)h->cv_blk.offs.get() + nblk, nkf, (const int*)h->cull_kf.walk.get(), kl_offs, list, h->cull_lm.c.get(),
+    DVS_TRY(compact_rows(h, h->cull_kf.flag.get(), nkf, WalkEmit{h->cull_kf.walk.get()}));
+    hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(256), 0, st, compact_total(h, nkf), nkf, (const int*)h->cull_kf.walk.get(), kl_offs, list, h->cull_lm.c.get(),
                        P.min_observers, P.redundancy_percent, P.max_cull, h->cull_kf.culled.get(), &sm->cull.n_culled);
     DVS_HIP(hipGetLastError());
     DVS_TRY(copy_out(n_obs.data(), h->cull_kf.n_obs, (size_t)nkf, st)); DVS_TRY(copy_out(r0.data(), h->cull_kf.r0, (size_t)nkf, st));
@@ -292,9 +270,9 @@ dvs_status dvs_backend_cull_keyframes(dvs_backend* h, uint64_t ref_frame_id, con
   }
   if (res.n_culled) {                                  // what the apply removes, also in a dry run
     if (nob) hipLaunchKernelGGL(k_cull_ob_flag, dim3((nob + 255) / 256), dim3(256), 0, st, (const int*)h->ob.kf.get(), nob, nkf, (const int*)h->cull_kf.culled.get(),
-                                h->cull_ob.keep.get(), &sm->cull.n_ob_removed);
+                                h->cmp_ob.keep.get(), &sm->cull.n_ob_removed);
     hipLaunchKernelGGL(k_cull_lm_flag, dim3((nlm + 3) / 4), dim3(256), 0, st, nlm, (const i64*)h->v_lm.offs.get(), (const int*)h->v_ob.kf.get(), (const int*)h->cull_kf.culled.get(),
-                       P.drop_orphans != 0 ? 1 : 0, h->cull_lm.removed.get(), h->cull_lm.keep.get(), &sm->cull.n_lm_removed);
+                       P.drop_orphans != 0 ? 1 : 0, h->cull_lm.removed.get(), h->cmp_lm.keep.get(), &sm->cull.n_lm_removed);
     DVS_HIP(hipGetLastError());
     int cnt[2] = {0, 0};
     DVS_TRY(small_read(h, &sm->cull.n_ob_removed, cnt, 2));
@@ -302,30 +280,12 @@ dvs_status dvs_backend_cull_keyframes(dvs_backend* h, uint64_t ref_frame_id, con
     res.n_observations_removed = cnt[0]; res.n_landmarks_removed = cnt[1];
   }
   if (apply && res.n_culled) {
-    // both tables into the spare pair, which then changes places with them
-    DVS_TRY(table_match_spare(h->lm_spare, h->lm)); DVS_TRY(table_match_spare(h->ob_spare, h->ob));
+    // the keyframes' new indices, then both tables without the rows that leave
     hipLaunchKernelGGL(k_cull_kf_keep, dim3((nkf + 255) / 256), dim3(256), 0, st, (const int*)h->cull_kf.culled.get(), nkf, h->cull_kf.keep.get());
     launch_scan_counts(st, (const int*)h->cull_kf.keep.get(), nkf, h->cull_kf.newidx.get());
-    int nblk = 0;
-    i64 kept_lm = 0, kept_ob = 0;
-    DVS_TRY(covis_block_offsets(h, h->cull_lm.keep.get(), nlm, &nblk));
-    hipLaunchKernelGGL(k_cull_lm_gather, dim3(nblk), dim3(256), 0, st, h->lm.view(), nlm, (const int*)h->cull_lm.keep.get(), (const i64*)h->cv_blk.offs.get(),
-                       (const int*)h->cull_lm.removed.get(), h->lm_spare.view());
-    DVS_HIP(hipMemcpyAsync(&kept_lm, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
-    if (nob) {
-      DVS_TRY(covis_block_offsets(h, h->cull_ob.keep.get(), nob, &nblk));
-      hipLaunchKernelGGL(k_cull_ob_gather, dim3(nblk), dim3(256), 0, st, h->ob.view(), nob, (const int*)h->cull_ob.keep.get(), (const i64*)h->cv_blk.offs.get(),
-                         (const i64*)h->cull_kf.newidx.get(), nkf, h->ob_spare.view());
-      DVS_HIP(hipMemcpyAsync(&kept_ob, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
-    }
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipStreamSynchronize(st));
-    if (kept_lm != (i64)nlm - res.n_landmarks_removed || kept_ob != (i64)nob - res.n_observations_removed) {
-      set_error("dvs_backend_cull_keyframes: inconsistent counts %lld %lld", (long long)kept_lm, (long long)kept_ob);
-      return DVS_ERR_HIP;
-    }
-    std::swap(h->lm, h->lm_spare); std::swap(h->ob, h->ob_spare);
-    h->nlm = (int)kept_lm; h->nob = (int)kept_ob;
+    TablesReplaced done;
+    DVS_TRY(tables_replace(h, "dvs_backend_cull_keyframes", h->cmp_lm.keep.get(), CullLmFix{h->cull_lm.removed.get()}, (i64)nlm - res.n_landmarks_removed, h->cmp_ob.keep.get(),
+                           CullObFix{h->cull_kf.newidx.get(), nkf}, (i64)nob - res.n_observations_removed, nullptr, &done));
   }
   // the report, in the order of the table before the call
   int nc = 0;

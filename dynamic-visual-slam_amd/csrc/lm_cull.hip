@@ -8,11 +8,10 @@
 //   k_ls_set        a row of the caller's arrays per lane: lm_find of its id in the aligned statistics, ids the map does not hold are skipped
 //   k_lc_views      a landmark row per lane over backend.hip's landmark -> views CSR: n, and the age in keyframes of its first valid view
 //   k_lc_decide     a landmark row per lane: the first rule that holds (F, then W), the stay / leave flags, the two counts
-//   k_lc_id_gather  the culled ids and reasons in ascending id: the ordered compaction of covisibility.hip (k_covis_blk_count, the scan,
-//                   gather at block offset + block_rank256)
+//   CulledIdEmit    the culled ids and reasons in ascending id (table_compact.h's compact_rows)
 //   k_lc_ob_flag    an observation row per lane: it leaves iff the landmark row it names leaves
-//   k_lc_lm_gather / k_lc_ob_gather / k_lc_rem_gather   the apply: both tables into the handle's spare pair and the statistics into their
-//                   spare by the same compaction, every column of the table; the removed rows' ids and keyframes for the host's cascade
+//   StatRide        the apply is table_compact.h's tables_replace, dvs_backend_prune's cascade included; a landmark row that stays takes its
+//                   statistics row along into the statistics' spare
 // No atomics but the two counts, no order dependence: everything is integers and total orders.
 #include <string.h>
 #include <algorithm>
@@ -22,6 +21,7 @@
 #include "matcher.h"
 #include "backend_internal.h"
 #include "block_ops.h"
+#include "table_compact.h"
 
 namespace dvs {
 
@@ -72,16 +72,11 @@ __global__ __launch_bounds__(256) void k_lc_decide(int nlm, dvs_lm_cull_params P
   }
 }
 
-// ordered compaction's step 3 over the marked rows: their ids and reasons in table order, which is ascending id
-__global__ __launch_bounds__(256) void k_lc_id_gather(const i64* __restrict__ lm_id, int nlm, const int* __restrict__ mark, const int* __restrict__ reason,
-                                                      const i64* __restrict__ blk_offs, i64* __restrict__ cid, int* __restrict__ creason) {
-  __shared__ int s_w[4];
-  const int s = blockIdx.x * 256 + threadIdx.x;
-  const bool k = s < nlm && mark[s] == 1;
-  int total;
-  const size_t p = (size_t)blk_offs[blockIdx.x] + block_rank256(k, s_w, total);
-  if (k) { cid[p] = lm_id[s]; creason[p] = reason[s]; }
-}
+// the compaction over the marked rows: their ids and reasons in table order, which is ascending id
+struct CulledIdEmit {
+  const i64* lm_id; const int* reason; i64* cid; int* creason;
+  __device__ void operator()(size_t s, size_t p) const { cid[p] = lm_id[s]; creason[p] = reason[s]; }
+};
 
 // ob_slot: the landmark row an observation row names, -1 if the table does not hold it (backend.hip, k_views_count)
 __global__ __launch_bounds__(256) void k_lc_ob_flag(const int* __restrict__ ob_slot, int nob, const int* __restrict__ mark, int* __restrict__ keep, int* __restrict__ gone) {
@@ -92,43 +87,11 @@ __global__ __launch_bounds__(256) void k_lc_ob_flag(const int* __restrict__ ob_s
   keep[i] = 1 - g; gone[i] = g;
 }
 
-static_assert(std::tuple_size<decltype(LmTable::columns(std::declval<LmTable&>()))>::value == 6, "k_lc_lm_gather writes every column of the landmark table");
-static_assert(std::tuple_size<decltype(ObTable::columns(std::declval<ObTable&>()))>::value == 7, "k_lc_ob_gather writes every column of the observation table");
-// step 3 for the landmarks and their statistics: the rows that stay, order kept, every column as it was
-__global__ __launch_bounds__(256) void k_lc_lm_gather(LmView lm, StatView st, int nlm, const int* __restrict__ keep, const i64* __restrict__ blk_offs, LmView nl, StatView ns) {
-  __shared__ int s_w[4];
-  const int s = blockIdx.x * 256 + threadIdx.x;
-  const bool k = s < nlm && keep[s] == 1;
-  int total;
-  const size_t p = (size_t)blk_offs[blockIdx.x] + block_rank256(k, s_w, total);
-  if (!k) return;
-  nl.id[p] = lm.id[s]; nl.seen[p] = lm.seen[s]; nl.cls[p] = lm.cls[s]; nl.cnt[p] = lm.cnt[s];
-  nl.xyz[3 * p] = lm.xyz[3 * (size_t)s]; nl.xyz[3 * p + 1] = lm.xyz[3 * (size_t)s + 1]; nl.xyz[3 * p + 2] = lm.xyz[3 * (size_t)s + 2];
-  copy32(nl.desc + 32 * p, lm.desc + 32 * (size_t)s);
-  ns.id[p] = st.id[s]; ns.visible[p] = st.visible[s]; ns.found[p] = st.found[s];
-}
-// for the observations
-__global__ __launch_bounds__(256) void k_lc_ob_gather(ObView ob, int nob, const int* __restrict__ keep, const i64* __restrict__ blk_offs, ObView no) {
-  __shared__ int s_w[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool k = i < nob && keep[i] == 1;
-  int total;
-  const size_t p = (size_t)blk_offs[blockIdx.x] + block_rank256(k, s_w, total);
-  if (!k) return;
-  no.id[p] = ob.id[i]; no.frame[p] = ob.frame[i]; no.lm[p] = ob.lm[i]; no.kf[p] = ob.kf[i]; no.cls[p] = ob.cls[i];
-  no.px[2 * p] = ob.px[2 * (size_t)i]; no.px[2 * p + 1] = ob.px[2 * (size_t)i + 1];
-  copy32(no.desc + 32 * p, ob.desc + 32 * (size_t)i);
-}
-// and for the rows that leave: what the host's cascade over the keyframes' observation_ids reads
-__global__ __launch_bounds__(256) void k_lc_rem_gather(const i64* __restrict__ ob_id, const int* __restrict__ ob_kf, int nob, const int* __restrict__ gone,
-                                                       const i64* __restrict__ blk_offs, i64* __restrict__ rem_id, int* __restrict__ rem_kf) {
-  __shared__ int s_w[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool k = i < nob && gone[i] == 1;
-  int total;
-  const size_t p = (size_t)blk_offs[blockIdx.x] + block_rank256(k, s_w, total);
-  if (k) { rem_id[p] = ob_id[i]; rem_kf[p] = ob_kf[i]; }
-}
+// a landmark row that stays, every column as it was: its statistics row stays with it
+struct StatRide {
+  StatView st, ns;
+  __device__ void operator()(const LmView&, size_t p, const LmView&, size_t s) const { ns.id[p] = st.id[s]; ns.visible[p] = st.visible[s]; ns.found[p] = st.found[s]; }
+};
 
 }  // namespace dvs
 
@@ -244,12 +207,12 @@ dvs_status dvs_backend_cull_landmarks(dvs_backend* h, const dvs_lm_cull_params* 
   BackendSmall* sm = h->s_small.get();
   DVS_TRY(lm_stats_align(h));
   DVS_TRY(lc_views(h));
-  DVS_TRY(h->cv_blk.grow((size_t)std::max(nlm, nob) / 256 + 2));
+  DVS_TRY(compact_grow(h));
   // decide
   LmCullLmRows& G = h->lc_lm;
   DVS_HIP(hipMemsetAsync(&sm->lmcull, 0, sizeof(LmCullCounts), st));
   hipLaunchKernelGGL(k_lc_decide, dim3((nlm + 255) / 256), dim3(256), 0, st, nlm, P, (const int*)h->stat.visible.get(), (const int*)h->stat.found.get(), (const int*)G.n.get(),
-                     (const int*)G.age.get(), G.reason.get(), G.keep.get(), G.mark.get(), &sm->lmcull);
+                     (const int*)G.age.get(), G.reason.get(), h->cmp_lm.keep.get(), G.mark.get(), &sm->lmcull);
   DVS_HIP(hipGetLastError());
   int cnt[2] = {0, 0};
   DVS_TRY(small_read(h, &sm->lmcull.n_by_ratio, cnt, 2));
@@ -261,51 +224,22 @@ dvs_status dvs_backend_cull_landmarks(dvs_backend* h, const dvs_lm_cull_params* 
     return DVS_ERR_CAPACITY;
   }
   res.n_landmarks = nlm; res.n_by_ratio = cnt[0]; res.n_weak = cnt[1];
-  int nblk = 0;
   if (nc && (culled_id || culled_reason)) {            // the report, in ascending id
-    DVS_TRY(covis_block_offsets(h, G.mark.get(), nlm, &nblk));
-    hipLaunchKernelGGL(k_lc_id_gather, dim3(nblk), dim3(256), 0, st, (const i64*)h->lm.id.get(), nlm, (const int*)G.mark.get(), (const int*)G.reason.get(),
-                       (const i64*)h->cv_blk.offs.get(), G.cid.get(), G.creason.get());
-    DVS_HIP(hipGetLastError());
+    DVS_TRY(compact_rows(h, G.mark.get(), nlm, CulledIdEmit{h->lm.id.get(), G.reason.get(), G.cid.get(), G.creason.get()}));
     DVS_TRY(copy_out(culled_id, G.cid, (size_t)nc, st)); DVS_TRY(copy_out(culled_reason, G.creason, (size_t)nc, st));
     DVS_HIP(hipStreamSynchronize(st));
   }
   if (apply && nc) {
-    // dvs_backend_prune's cascade: both tables into the spare pair and the statistics into their spare, which then change places with them
-    DVS_TRY(table_match_spare(h->lm_spare, h->lm)); DVS_TRY(table_match_spare(h->ob_spare, h->ob));
-    DVS_TRY(h->stat_spare.grow((size_t)nlm)); DVS_TRY(h->lc_ob.grow((size_t)nob)); DVS_TRY(h->prune_ob.grow((size_t)nob));
-    i64 kept_lm = 0, kept_ob = 0, gone_ob = 0;
-    DVS_TRY(covis_block_offsets(h, G.keep.get(), nlm, &nblk));
-    hipLaunchKernelGGL(k_lc_lm_gather, dim3(nblk), dim3(256), 0, st, h->lm.view(), stat_view(h->stat), nlm, (const int*)G.keep.get(), (const i64*)h->cv_blk.offs.get(),
-                       h->lm_spare.view(), stat_view(h->stat_spare));
-    DVS_HIP(hipMemcpyAsync(&kept_lm, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
-    if (nob) {
-      hipLaunchKernelGGL(k_lc_ob_flag, dim3((nob + 255) / 256), dim3(256), 0, st, (const int*)h->v_ob.slot.get(), nob, (const int*)G.mark.get(), h->lc_ob.keep.get(),
-                         h->lc_ob.gone.get());
-      DVS_TRY(covis_block_offsets(h, h->lc_ob.keep.get(), nob, &nblk));
-      hipLaunchKernelGGL(k_lc_ob_gather, dim3(nblk), dim3(256), 0, st, h->ob.view(), nob, (const int*)h->lc_ob.keep.get(), (const i64*)h->cv_blk.offs.get(), h->ob_spare.view());
-      DVS_HIP(hipMemcpyAsync(&kept_ob, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
-      DVS_TRY(covis_block_offsets(h, h->lc_ob.gone.get(), nob, &nblk));
-      hipLaunchKernelGGL(k_lc_rem_gather, dim3(nblk), dim3(256), 0, st, (const i64*)h->ob.id.get(), (const int*)h->ob.kf.get(), nob, (const int*)h->lc_ob.gone.get(),
-                         (const i64*)h->cv_blk.offs.get(), h->prune_ob.rem_id.get(), h->prune_ob.rem_kf.get());
-      DVS_HIP(hipMemcpyAsync(&gone_ob, h->cv_blk.offs.get() + nblk, sizeof(i64), hipMemcpyDeviceToHost, st));
-    }
-    DVS_HIP(hipGetLastError());
-    DVS_HIP(hipStreamSynchronize(st));
-    if (kept_lm != (i64)nlm - nc || kept_ob < 0 || gone_ob < 0 || kept_ob + gone_ob != (i64)nob) {
-      set_error("dvs_backend_cull_landmarks: inconsistent counts %lld %lld %lld", (long long)kept_lm, (long long)kept_ob, (long long)gone_ob);
-      return DVS_ERR_HIP;
-    }
-    std::vector<i64> rid((size_t)gone_ob);
-    std::vector<int> rkf((size_t)gone_ob);
-    if (gone_ob) {
-      DVS_TRY(copy_out(rid.data(), h->prune_ob.rem_id, rid.size(), st)); DVS_TRY(copy_out(rkf.data(), h->prune_ob.rem_kf, rkf.size(), st));
-      DVS_HIP(hipStreamSynchronize(st));
-    }
-    res.n_keyframes_touched = backend_drop_observation_ids(h, rid, rkf);
-    std::swap(h->lm, h->lm_spare); std::swap(h->ob, h->ob_spare); std::swap(h->stat, h->stat_spare);
-    h->nlm = (int)kept_lm; h->nob = (int)kept_ob; h->nstat = (int)kept_lm;
-    res.n_landmarks_removed = nc; res.n_observations_removed = (int)gone_ob;
+    // dvs_backend_prune's cascade; the statistics go into their spare with the landmark rows, and change places as the tables do
+    DVS_TRY(h->stat_spare.grow((size_t)nlm));
+    if (nob) hipLaunchKernelGGL(k_lc_ob_flag, dim3((nob + 255) / 256), dim3(256), 0, st, (const int*)h->v_ob.slot.get(), nob, (const int*)G.mark.get(), h->cmp_ob.keep.get(),
+                                h->cmp_ob.gone.get());
+    TablesReplaced done;
+    DVS_TRY(tables_replace(h, "dvs_backend_cull_landmarks", h->cmp_lm.keep.get(), StatRide{stat_view(h->stat), stat_view(h->stat_spare)}, (i64)nlm - nc, h->cmp_ob.keep.get(),
+                           RowAsIs(), -1, h->cmp_ob.gone.get(), &done));
+    std::swap(h->stat, h->stat_spare);
+    h->nstat = h->nlm;
+    res.n_keyframes_touched = done.n_kf_touched; res.n_landmarks_removed = nc; res.n_observations_removed = done.n_ob_gone;
   }
   if (out) *out = res;
   return DVS_OK;

@@ -18,8 +18,9 @@
 //   k_fuse_pairs     per target with a winner: redirect[removed row] = survivor row, partner[survivor row] = removed row
 //   k_fuse_pairlist  one workgroup: the kept pairs in ascending removed id (survivor id, removed id, e) and their count
 //   k_fuse_repoint   observations naming a removed landmark name its survivor
-//   k_fuse_compact   one workgroup: the landmark table without the removed rows into the spare table, order kept, the survivors with the
-//                    summed observation_count and the later last_seen
+//   k_fuse_keep / FuseLmFix   the landmark table without the removed rows (table_compact.h's tables_replace, the observation table
+//                    untouched): a row stays iff nothing redirects it, the survivors with the summed observation_count and the later
+//                    last_seen
 // No floating-point atomics anywhere: (e, id) is a total order and every minimum is an integer minimum, so two identical calls on
 // identical maps give identical bytes.
 #include <limits.h>
@@ -32,6 +33,7 @@
 #include "matcher.h"
 #include "backend_internal.h"
 #include "block_ops.h"
+#include "table_compact.h"
 
 namespace dvs {
 
@@ -244,28 +246,18 @@ __global__ __launch_bounds__(256) void k_fuse_repoint(i64* __restrict__ ob_lm, i
   if (s >= 0 && redirect[s] >= 0) ob_lm[i] = lm_id[redirect[s]];
 }
 
-__global__ __launch_bounds__(256) void k_fuse_compact(LmView lm, int nlm, const int* __restrict__ redirect, const int* __restrict__ partner, LmView nl,
-                                                      int* __restrict__ n_kept) {
-  __shared__ int s_w[4];
-  int kl = 0;
-  for (int s0 = 0; s0 < nlm; s0 += 256) {
-    const int s = s0 + threadIdx.x;
-    const bool keep = s < nlm && redirect[s] < 0;
-    int total;
-    const int p = kl + block_rank256(keep, s_w, total);
-    if (keep) {
-      const int o = partner[s];
-      const bool merged = o >= 0 && o < nlm;
-      nl.id[p] = lm.id[s]; nl.cls[p] = lm.cls[s];
-      nl.cnt[p] = merged ? lm.cnt[s] + lm.cnt[o] : lm.cnt[s];
-      nl.seen[p] = merged ? max(lm.seen[s], lm.seen[o]) : lm.seen[s];
-      nl.xyz[3 * p] = lm.xyz[3 * s]; nl.xyz[3 * p + 1] = lm.xyz[3 * s + 1]; nl.xyz[3 * p + 2] = lm.xyz[3 * s + 2];
-      copy32(nl.desc + 32 * (size_t)p, lm.desc + 32 * (size_t)s);
-    }
-    kl += total;
-  }
-  if (threadIdx.x == 0) *n_kept = kl;
+__global__ __launch_bounds__(256) void k_fuse_keep(const int* __restrict__ redirect, int nlm, int* __restrict__ keep) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s < nlm) keep[s] = redirect[s] < 0 ? 1 : 0;
 }
+// a landmark row that stays: a survivor takes its partner's observations and the later of the two last_seen
+struct FuseLmFix {
+  const int* partner; int nlm;
+  __device__ void operator()(const LmView& nl, size_t p, const LmView& lm, size_t s) const {
+    const int o = partner[s];
+    if (o >= 0 && o < nlm) { nl.cnt[p] = lm.cnt[s] + lm.cnt[o]; nl.seen[p] = max(lm.seen[s], lm.seen[o]); }
+  }
+};
 
 }  // namespace dvs
 
@@ -410,15 +402,12 @@ dvs_status fuse_run(dvs_backend* h, int q, const std::vector<int>& E, const dvs_
     DVS_TRY(copy_out(survivor_id, h->fuse_lm.psurv, (size_t)nf, st)); DVS_TRY(copy_out(removed_id, h->fuse_lm.prem, (size_t)nf, st)); DVS_TRY(copy_out(err, h->fuse_lm.pe, (size_t)nf, st));
   }
   if (apply && nf) {
-    DVS_TRY(table_match_spare(h->lm_spare, h->lm));
+    DVS_TRY(compact_grow(h));
     hipLaunchKernelGGL(k_fuse_repoint, g_ob, b, 0, st, ob.lm, nob, (const int*)h->f_obrow.get(), (const int*)h->fuse_lm.redirect.get(), (const i64*)lm.id);
-    hipLaunchKernelGGL(k_fuse_compact, dim3(1), b, 0, st, lm, nlm, (const int*)h->fuse_lm.redirect.get(), (const int*)h->fuse_lm.partner.get(), h->lm_spare.view(), &fc->n_kept);
+    hipLaunchKernelGGL(k_fuse_keep, g_lm, b, 0, st, (const int*)h->fuse_lm.redirect.get(), nlm, h->cmp_lm.keep.get());
     DVS_HIP(hipGetLastError());
-    int kept = -1;
-    DVS_TRY(small_read(h, &fc->n_kept, &kept));
-    if (kept != nlm - nf) { set_error("dvs_backend_fuse: %d rows kept of %d with %d pairs", kept, nlm, nf); return DVS_ERR_HIP; }
-    std::swap(h->lm, h->lm_spare);
-    h->nlm = kept;
+    TablesReplaced done;
+    DVS_TRY(tables_replace(h, "dvs_backend_fuse", h->cmp_lm.keep.get(), FuseLmFix{h->fuse_lm.partner.get(), nlm}, (i64)nlm - nf, nullptr, RowAsIs(), -1, nullptr, &done));
   } else if (want && nf) {
     DVS_HIP(hipStreamSynchronize(st));
   }

@@ -80,6 +80,9 @@ dvs_status dvs_test_stream_delay(void* stream, int32_t microseconds);
  * op 3 (nt, nv unused): in = uint8 flags[2][256] -> out = int32 [2][256][3] = {rank, total, count}: block_rank256 on trip 0 and on
  *   trip 1, then block_count256 on both, all four through one scratch with nothing in between. */
 dvs_status dvs_test_block_ops(int32_t op, int32_t nt, int32_t nv, const void* in, void* out);
+/* (needs a GPU) csrc/table_compact.h's ordered compaction on its own, on a backend handle's stream and block scratch: out_pos[0 .. *out_total)
+ * = the indices i < n with flags[i] == 1 in ascending order (any other value is not flagged), out_pos[*out_total .. n) = -1. */
+dvs_status dvs_test_compact_rows(dvs_backend* h, int32_t n, const int32_t* flags, int32_t* out_pos, int64_t* out_total);
 /* KeyPointsFilter::retainBest on bare responses: perm[i] = original index of the i-th survivor.  _host: csrc/lsort.h's sequential
  * restatement of std::nth_element + std::partition (no GPU); _device: the wavefront routine the cv::ORB kernels run */
 void dvs_test_retain_best_host(const float* responses, int32_t n, int32_t n_points, int32_t* perm, int32_t* n_kept);

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import backend_ref as br
+from compaction_scenes import crosses_blocks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["dvs_backend_default_params", "dvs_backend_create", "dvs_backend_destroy", "dvs_backend_reset", "dvs_backend_add_keyframe",
@@ -73,6 +74,17 @@ def test_prune_cascade_counts_and_keyframe_lists():
     assert ref.prune((40, 0)) == (2, 2)                         # landmarks 1, 2 (count 1, 40 s old) and their two observations
     assert [o["id"] for o in ref.obs] == [0, 3] and ref.kfs[0]["obs_ids"] == [0] and ref.kfs[1]["obs_ids"] == [3]
     assert sorted(ref.db[0]) == [0] and ref.prune((10**6, 0)) == (0, 0)
+
+
+def test_the_prune_scene_crosses_the_compaction_blocks():
+    """tests/test_gpu_backend.py's prune in the middle: both tables lose rows in several 256-row blocks and keep rows behind them"""
+    scene = br.make_scene()
+    ref = br.BackendRef(br.FX, br.FY, br.CX, br.CY, filtered=(br.PERSON,))
+    for kf in scene[:8]:
+        ref.add_keyframe(kf["frame_id"], kf["stamp"], kf["t"], kf["q"], kf["xyz"], kf["px"], kf["desc"], kf["det"])
+    lms, obs = ref.landmark_table()["id"], ref.observation_table()["id"]
+    assert ref.prune((scene[2]["stamp"][0] + 20, scene[2]["stamp"][1] + 1))[0] > 20
+    assert crosses_blocks(lms, ref.landmark_table()["id"]) == (True, True) and crosses_blocks(obs, ref.observation_table()["id"]) == (True, True)
 
 
 def test_window_is_the_last_five_keyframes_in_set_order():

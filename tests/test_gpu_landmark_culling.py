@@ -343,20 +343,24 @@ def test_threshold_edges(gpu):
 
 
 # ---------------------------------------------------------------------------------------------------- 6: apply
+BIG_SCENE = dict(seed=17, npoints=330, nkf=4)    # three keyframes of it: more than 513 landmarks (tests/test_landmark_culling_cpu.py), so "block" needs no larger one
+
+
 @pytest.fixture(scope="module")
 def big_scene():
-    return br.make_scene(seed=17, npoints=330, nkf=4)
+    return br.make_scene(**BIG_SCENE)
 
 
-@pytest.mark.parametrize("case", ["edges", "none", "all", "cap"])
+@pytest.mark.parametrize("case", ["edges", "none", "all", "cap", "block", "alternate"])
 def test_apply_equals_the_restatement_and_the_map_goes_on(gpu, big_scene, case):
     from dvslam_amd import DvsError
     mb = _handle(big_scene[:3])
     ref = _ref(mb)
     ids = [int(i) for i in mb.landmarks()["id"]]
-    assert len(ids) > 258
+    assert len(ids) > 513
     base = {i: [9, 3 + i % 5] for i in ids}                                  # found ratio 33 % and more: nobody is in rule F
-    marked = dict(edges=[ids[0], ids[255], ids[256], ids[-1]], none=[], all=ids, cap=[ids[0], ids[255], ids[256], ids[-1]])[case]
+    # block: a whole 256-row block of the compaction leaves between two that stay; alternate: every block loses half its rows
+    marked = dict(edges=[ids[0], ids[255], ids[256], ids[-1]], none=[], all=ids, cap=[ids[0], ids[255], ids[256], ids[-1]], block=ids[256:512], alternate=ids[::2])[case]
     for i in marked:
         base[i] = [9, 2]                                                     # 22 %
     mb.set_landmark_stats(ids, [base[i][0] for i in ids], [base[i][1] for i in ids])

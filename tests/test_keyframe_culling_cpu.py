@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 import backend_ref as br
+from compaction_scenes import crosses_blocks
 import covisibility_ref as cr
 import keyframe_culling_ref as kr
 
@@ -266,6 +267,8 @@ def test_make_scene_meets_its_conditions():
     rep, kfs, lms, obs = kr.cull(*T, **P)
     assert _culled(rep) == [3, 7] and _culled(kr.decide(*T, one_shot=True, **P)) == [3, 4, 5, 7] and rep["n_landmarks_removed"] == 60
     assert (kr.rows_per_landmark(lms, obs) == lms["observation_count"]).all() and len(lms["id"]) == len(T[1]["id"]) - 60
+    # the apply's compactions work across workgroups on both tables (the hub scene removes no landmark: this scene carries the condition)
+    assert crosses_blocks(T[1]["id"], lms["id"]) == (True, True) and crosses_blocks(T[2]["id"], obs["id"]) == (True, True)
     rep0, _, lms0, obs0 = kr.cull(*T, drop_orphans=0, **P)
     assert rep0["n_landmarks_removed"] == 0 and (kr.rows_per_landmark(lms0, obs0) == 0).sum() == 60 and obs0["id"].tobytes() == obs["id"].tobytes()
     rec = kr.decide(*T, keep_recent=3, **P)

@@ -262,6 +262,13 @@ def test_the_object_scene_meets_its_conditions():
     assert out2["n_visible"] == out["n_visible"] - lcr.OBJECT_N and out2["status"] == mr.OK
 
 
+def test_the_apply_scene_fills_more_than_two_blocks_of_the_compaction():
+    """test_gpu_landmark_culling.py's "block" case takes ids[256:512] out: rows must stay on both sides, the later ones in a third 256-row block"""
+    from test_gpu_landmark_culling import BIG_SCENE
+    ref = _ref(br.make_scene(**BIG_SCENE)[:3])
+    assert len(ref.landmark_table()["id"]) >= 513 and ref.ties == 0
+
+
 def test_ref_from_tables_round_trips():
     ref = _ref(br.make_scene()[:3])
     again = lcr.ref_from_tables(ref.keyframe_table(), ref.landmark_table(), ref.observation_table(), dict(next_observation_id=ref.next_obs, next_landmark_id=ref.next_lm))

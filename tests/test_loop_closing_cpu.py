@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 
 import backend_ref as br
+from compaction_scenes import crosses_blocks
 import loop_closing_ref as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -161,8 +162,10 @@ def test_scene_fixture_conditions():
     assert last["n_associated"] == 0, "the drift must keep the last keyframe from associating with the old landmarks"
     duplicates = [lid for lid in lm_point if lid >= last["first_landmark_id"] and first[lm_point[lid]] != lid]
     assert len(duplicates) >= 150, len(duplicates)
+    ids_before = ref.landmark_table()["id"]
     out = lc.close_loop(ref, lc.scene_loop(), lc.ODO_W, fuse_params={})
     assert out["termination"] == 0 and out["n_landmarks_moved"] == len(lm_point)
+    assert crosses_blocks(ids_before, ref.landmark_table()["id"]) == (True, True), "fusion's compaction must work across workgroups"
     (pairs,) = out["pairs"]
     assert out["n_fused"] == len(pairs) >= 100, out["n_fused"]
     assert out["n_proposals"] > out["n_fused"], "some targets must choose among several proposals"

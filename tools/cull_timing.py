@@ -92,7 +92,7 @@ def mode_profile(out_dir):
     if not files:
         raise SystemExit(f"no kernel statistics under {out_dir}")
     # the kernels only the dry runs launch; the views CSR's kernels and the scans also serve the map's construction and cannot be told apart by name
-    mine =("k_cull_", "k_covis_first", "k_covis_scatter", "k_covis_order", "k_covis_blk_count")
+    mine =("k_cull_", "k_covis_first", "k_covis_scatter", "k_covis_order", "k_compact_")
     rows = []
     for r in csv.DictReader(open(files[0])):
         name = r.get("Name", "").split("(")[0]

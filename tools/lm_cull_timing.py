@@ -13,6 +13,7 @@ Wall figures are ms of a blocking call, the median (min .. max) of `reps` calls 
   stats        MappingBackend.landmark_stats(): the alignment, the views and five columns copied to the host
   cull_apply   five applied culls in a row, each removing every tenth landmark of the map as it then stands (rule F through counters
                set for it): the compaction of both tables and the statistics and the host's cascade; each figure is one call
+  prune        one MappingBackend.prune behind them that removes about a tenth of the landmarks (prune_line below), one call
 No time is promised for any of them; EXPERIMENTS.md "Landmark culling" says what has been run."""
 import argparse
 import json
@@ -36,6 +37,22 @@ def build(shape):
         mb.add_keyframe(kf["frame_id"], kf["stamp"], kf["t"], kf["q"], kf["xyz"], kf["px"], kf["desc"])
         last = kf
     return mb, last
+
+
+def prune_line(mb, last):
+    """one dvs_backend_prune that removes about a tenth of the landmarks: a keyframe of points nobody has seen joins the map, a ninth as
+    many as the map holds (one view each, behind every other row of both tables), and the prune comes 21 s after it"""
+    n = max(mb.counts()["n_landmarks"] // 9, 1)
+    rng = np.random.default_rng(77)
+    px = np.stack([rng.uniform(20, 620, n), rng.uniform(20, 460, n)], 1)
+    xyz = np.stack([rng.uniform(50, 60, n), rng.uniform(50, 60, n), rng.uniform(50, 60, n)], 1)      # far from every landmark of the map
+    stamp = (last["stamp"][0] + 1000, 0)
+    res = mb.add_keyframe(last["frame_id"] + 100000, stamp, last["t"], last["q"], xyz, px, rng.integers(0, 256, (n, 32), dtype=np.uint8))
+    c = mb.counts()
+    t0 = time.perf_counter()
+    removed = mb.prune((stamp[0] + 21, 0))
+    ms = (time.perf_counter() - t0) * 1e3
+    return {"ms": round(ms, 3), "landmarks": c["n_landmarks"], "observations": c["n_observations"], "created": res["n_created"], "removed": list(removed)}
 
 
 def mode_wall(reps):
@@ -76,6 +93,7 @@ def mode_wall(reps):
             applied.append({"ms": round(ms, 3), "landmarks": len(ids), "removed": rep["n_landmarks_removed"], "observations_removed": rep["n_observations_removed"],
                             "keyframes_touched": rep["n_keyframes_touched"]})
         row["cull_apply"] = applied
+        row["prune"] = prune_line(mb, last)
         d_k.free(); d_d.free(); mt.close(); mb.close()
         res["maps"].append(row)
         print(json.dumps(row), flush=True)
