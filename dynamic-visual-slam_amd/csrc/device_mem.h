@@ -86,12 +86,18 @@ dvs_status grow(Buf<T, Pinned>& buf, size_t& cap, size_t need) {
   return DVS_OK;
 }
 
-// Move-only owner of an event without timing.  Empty until create(): a handle can be built (and destroyed) without a device.
+// Move-only owner of another handle of the library (what a dvs_*_create returned), released by that handle's own destroy function.
+template <class T, void (*Destroy)(T*)>
+struct DestroyWith { void operator()(T* p) const { Destroy(p); } };
+template <class T, void (*Destroy)(T*)>
+using Owned = std::unique_ptr<T, DestroyWith<T, Destroy>>;
+
+// Move-only owner of an event, without timing unless asked.  Empty until create(): a handle can be built (and destroyed) without a device.
 class Event {
  public:
-  hipError_t create() {
+  hipError_t create(bool timing = false) {
     hipEvent_t e = nullptr;
-    const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    const hipError_t r = hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming);
     e_.reset(e);
     return r;
   }

@@ -485,9 +485,7 @@ struct dvs_maptrack {
   Column<double, 3> cX; Column<double, 2> cpx; Column<int> coct, ckp; Column<uint8_t> cinl;
   size_t c_corr = 0;
   DeviceBuf<dvs_maptrack_result> d_res;
-  // staging of the host form (grow-only)
-  DeviceBuf<float> s_xyz; DeviceBuf<uint8_t> s_ldesc, s_kdesc; DeviceBuf<long long> s_id; DeviceBuf<dvs_keypoint> s_kps;
-  size_t cs_lm = 0, cs_kp = 0;
+  FrameStaging stage;   // of the host form
   // the last call
   int last_n_kp = 0, last_n_lm = 0;
   bool last_search = false;
@@ -755,36 +753,9 @@ dvs_status dvs_maptrack_track(dvs_maptrack* h, const float* lm_xyz, const uint8_
   DVS_ARG((n_lm == 0 || (lm_xyz && lm_desc)) && (n_kp == 0 || (kps && desc)));
   MtPose T;
   DVS_TRY(maptrack_pose(R9, t3, &T));
-  const dvs_maptrack_params& P = h->P;
-  for (int k = 0; k < n_kp; k++)
-    DVS_ARG(kps[k].x >= 0.f && kps[k].x < (float)P.cols && kps[k].y >= 0.f && kps[k].y < (float)P.rows && kps[k].octave >= 0 && kps[k].octave < P.n_levels);
-  if (lm_id) for (int j = 1; j < n_lm; j++) DVS_ARG(lm_id[j - 1] < lm_id[j]);
-  DVS_HIP(hipSetDevice(h->device));
-  hipStream_t st = h->stream;
-  if ((size_t)n_lm > h->cs_lm || (size_t)n_kp > h->cs_kp) DVS_HIP(hipStreamSynchronize(st));
-  if ((size_t)n_lm > h->cs_lm) {
-    h->cs_lm = 0;
-    const size_t c = (size_t)n_lm + (size_t)n_lm / 4;
-    DVS_TRY(h->s_xyz.alloc(c * 3)); DVS_TRY(h->s_ldesc.alloc(c * 32)); DVS_TRY(h->s_id.alloc(c));
-    h->cs_lm = c;
-  }
-  if ((size_t)n_kp > h->cs_kp) {
-    h->cs_kp = 0;
-    const size_t c = (size_t)n_kp + (size_t)n_kp / 4;
-    DVS_TRY(h->s_kps.alloc(c)); DVS_TRY(h->s_kdesc.alloc(c * 32));
-    h->cs_kp = c;
-  }
-  if (n_lm > 0) {
-    DVS_HIP(hipMemcpyAsync(h->s_xyz.get(), lm_xyz, (size_t)n_lm * 12, hipMemcpyHostToDevice, st));
-    DVS_HIP(hipMemcpyAsync(h->s_ldesc.get(), lm_desc, (size_t)n_lm * 32, hipMemcpyHostToDevice, st));
-    if (lm_id) DVS_HIP(hipMemcpyAsync(h->s_id.get(), lm_id, (size_t)n_lm * 8, hipMemcpyHostToDevice, st));
-  }
-  if (n_kp > 0) {
-    DVS_HIP(hipMemcpyAsync(h->s_kps.get(), kps, (size_t)n_kp * sizeof(dvs_keypoint), hipMemcpyHostToDevice, st));
-    DVS_HIP(hipMemcpyAsync(h->s_kdesc.get(), desc, (size_t)n_kp * 32, hipMemcpyHostToDevice, st));
-  }
-  return dvs_maptrack_track_device(h, h->s_xyz.get(), h->s_ldesc.get(), (lm_id && n_lm > 0) ? (const int64_t*)h->s_id.get() : nullptr, n_lm, h->s_kps.get(),
-                                   h->s_kdesc.get(), n_kp, R9, t3, result);
+  DVS_TRY(stage_frame(h->stage, h->P, h->device, h->stream, lm_xyz, lm_desc, lm_id, n_lm, kps, desc, n_kp));
+  const FrameStaging& S = h->stage;
+  return dvs_maptrack_track_device(h, S.xyz.get(), S.ldesc.get(), S.ids(lm_id, n_lm), n_lm, S.kps.get(), S.kdesc.get(), n_kp, R9, t3, result);
 }
 
 dvs_status dvs_maptrack_get_matches(dvs_maptrack* h, int32_t cap, int32_t* lm_row, int64_t* lm_id, int32_t* dist, uint8_t* inlier, int32_t* n) {
@@ -798,10 +769,8 @@ dvs_status dvs_maptrack_get_matches(dvs_maptrack* h, int32_t cap, int32_t* lm_ro
   DVS_HIP(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t m = (size_t)h->last_n_kp;
-  if (lm_row) DVS_HIP(hipMemcpyAsync(lm_row, h->kp_lm.get(), m * 4, hipMemcpyDeviceToHost, st));
-  if (lm_id) DVS_HIP(hipMemcpyAsync(lm_id, h->kp_id.get(), m * 8, hipMemcpyDeviceToHost, st));
-  if (dist) DVS_HIP(hipMemcpyAsync(dist, h->kp_dist.get(), m * 4, hipMemcpyDeviceToHost, st));
-  if (inlier) DVS_HIP(hipMemcpyAsync(inlier, h->kp_inl.get(), m, hipMemcpyDeviceToHost, st));
+  DVS_TRY(copy_out(lm_row, h->kp_lm, m, st)); DVS_TRY(copy_out(lm_id, h->kp_id, m, st));
+  DVS_TRY(copy_out(dist, h->kp_dist, m, st)); DVS_TRY(copy_out(inlier, h->kp_inl, m, st));
   DVS_HIP(hipStreamSynchronize(st));
   return DVS_OK;
 }
@@ -872,10 +841,10 @@ dvs_status dvs_test_maptrack_cells(dvs_maptrack* h, int32_t cap_cells, int32_t c
   *n_binned = nb;
   if ((cell_start && h->ncell > cap_cells) || (order && nb > cap_kp)) { set_error("dvs_test_maptrack_cells: %d cells, %d keypoints", h->ncell, nb); return DVS_ERR_CAPACITY; }
   if (cell_start) {
-    if (h->last_search) DVS_HIP(hipMemcpy(cell_start, h->start.get(), ((size_t)h->ncell + 1) * 4, hipMemcpyDeviceToHost));
-    else memset(cell_start, 0, ((size_t)h->ncell + 1) * 4);
+    if (h->last_search) DVS_HIP(hipMemcpy(cell_start, h->start.get(), ((size_t)h->ncell + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    else memset(cell_start, 0, ((size_t)h->ncell + 1) * sizeof(int));
   }
-  if (order && nb > 0) DVS_HIP(hipMemcpy(order, h->order.get(), (size_t)nb * 4, hipMemcpyDeviceToHost));
+  if (order && nb > 0) DVS_HIP(hipMemcpy(order, h->order.get(), (size_t)nb * h->order.row_bytes, hipMemcpyDeviceToHost));
   return DVS_OK;
 }
 

@@ -521,8 +521,7 @@ __device__ __forceinline__ double wave_allsum(double v) {
 // One wavefront per problem: the inliers of the best model in index order, then solvePnP(SOLVEPNP_ITERATIVE) on them —
 // cvFindExtrinsicCameraParams2: planar test, homography / DLT initialisation, CvLevMarq(6, 2 count, (20, FLT_EPSILON)) on the analytic
 // projection Jacobian.  Sums over the inliers are lane-strided partial sums folded by a butterfly (every lane then holds the same
-// total and runs the same small dense arithmetic: no broadcasts).  out record per problem (64 B): {int nInliers, int success, pad,
-// double rvec[3], tvec[3]}.
+// total and runs the same small dense arithmetic: no broadcasts).  out: a PnpRecord per problem (ransac_layout.h).
 // In the test library alone (-DDVS_TEST_HOOKS) the kernel has one more parameter, `dbg` (may be NULL): 8 doubles per problem — the
 // initialisation handed to the LM (rvec, tvec), the path taken (0 no initialisation, 1 planar, 2 DLT), the LM's iteration count — for
 // dvs_test_pnpcv_refit; the product library's kernel does not have it.
@@ -537,16 +536,16 @@ __device__ __forceinline__ double wave_allsum(double v) {
 #endif
 __global__ __launch_bounds__(64) void k_pnpcv_refit(const float* __restrict__ obj, const float* __restrict__ img, const RansacProb* __restrict__ probs, int H,
                                                     const double* __restrict__ models, const int* __restrict__ sel, double fx, double fy, double cx,
-                                                    double cy, float thr, int* __restrict__ inl, unsigned char* __restrict__ out DVS_REFIT_DBG_PARAM) {
+                                                    double cy, float thr, int* __restrict__ inl, PnpRecord* __restrict__ out DVS_REFIT_DBG_PARAM) {
   using namespace pnpcv;
   __shared__ double wsA[145], wsV[145], wsOut[16];   // the 9 x 9 / 12 x 12 eigen-decompositions of the initialisation: lane 0, in LDS
   const RansacProb pb = probs[blockIdx.x];
   const int n = pb.n, lane = threadIdx.x;
   obj += 3 * (size_t)pb.off; img += 2 * (size_t)pb.off; inl += pb.off;
-  out += 64 * (size_t)blockIdx.x;
+  out += blockIdx.x;
   DVS_REFIT_DBG(dbg += 8 * (size_t)blockIdx.x; for (int k = 0; k < 8; k++) dbg[k] = 0.0);
   const int best = sel[4 * blockIdx.x];
-  if (best < 0) { if (lane < 16) ((int*)out)[lane] = 0; return; }
+  if (best < 0) { if (lane < (int)(sizeof(PnpRecord) / sizeof(int))) reinterpret_cast<int*>(out)[lane] = 0; return; }   // the whole record, a dword per lane
   const double* bm = models + 18 * ((size_t)H * blockIdx.x + best);
   double R[9], t[3];
   for (int k = 0; k < 9; k++) R[k] = bm[6 + k];
@@ -767,10 +766,8 @@ __global__ __launch_bounds__(64) void k_pnpcv_refit(const float* __restrict__ ob
     success = 1;
   }
   if (lane == 0) {
-    int* oi = (int*)out;
-    oi[0] = count; oi[1] = success; oi[2] = 0; oi[3] = 0;
-    double* od = (double*)(out + 16);
-    for (int k = 0; k < 3; k++) { od[k] = r[k]; od[3 + k] = tt[k]; }
+    out->n_inliers = count; out->success = success; out->unused[0] = 0; out->unused[1] = 0;
+    for (int k = 0; k < 3; k++) { out->rvec[k] = r[k]; out->tvec[k] = tt[k]; }
   }
 }
 

@@ -753,14 +753,12 @@ __device__ __forceinline__ void exp_so3(const double* w, double* E) {
 // Per problem (blockIdx.x): results record `res` = {nin, success, pad, pad (16 B) | rvec, tvec (48 B)}, inlier list at inliers + off.
 __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ obj, const float* __restrict__ img, const RansacProb* __restrict__ probs, int H4,
                                                     const double* __restrict__ poses, const int* __restrict__ sel, double fx, double fy, double cx, double cy,
-                                                    double thr2, int* __restrict__ inliers, unsigned char* __restrict__ resAll) {
+                                                    double thr2, int* __restrict__ inliers, PnpRecord* __restrict__ resAll) {
   const RansacProb pb = probs[blockIdx.x];
   const int n = pb.n;
   obj += 3 * (size_t)pb.off; img += 2 * (size_t)pb.off; inliers += pb.off;
   poses += 12 * (size_t)H4 * blockIdx.x; sel += 4 * (size_t)blockIdx.x;
-  int* nin = reinterpret_cast<int*>(resAll + 64 * (size_t)blockIdx.x);
-  int* success = nin + 1;
-  double* rt = reinterpret_cast<double*>(resAll + 64 * (size_t)blockIdx.x + 16);
+  PnpRecord& res = resAll[blockIdx.x];
   __shared__ double sm[256];
   __shared__ double sm27[27][256];   // 54 KB: all normal-equation sums of an iteration in one reduction tree
   __shared__ double sR[9], st[3], sRn[9], stn[3], sH[36], sg[6], sd[6];
@@ -769,7 +767,7 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
   __shared__ int s_stop;
   const int tid = threadIdx.x;
   const int best = sel[0];
-  if (best < 0) { if (tid == 0) { *nin = 0; *success = 0; for (int k = 0; k < 6; k++) rt[k] = 0; } return; }
+  if (best < 0) { if (tid == 0) { res.n_inliers = 0; res.success = 0; for (int k = 0; k < 3; k++) res.rvec[k] = 0; for (int k = 0; k < 3; k++) res.tvec[k] = 0; } return; }
   if (tid < 9) sR[tid] = poses[12 * (size_t)best + tid];
   if (tid < 3) st[tid] = poses[12 * (size_t)best + 9 + tid];
   if (tid == 0) { s_lambda = 1e-3; s_stop = 0; }
@@ -784,7 +782,7 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
     if (in) inliers[pos] = i;
     m += total;
   }
-  if (tid == 0) *nin = m;
+  if (tid == 0) res.n_inliers = m;
   auto cost_of = [&](const double* R, const double* t) -> double {
     double c = 0;
     for (int e = tid; e < m; e += 256) { const int i = inliers[e]; c += fmin(reproj_err2(R, t, fx, fy, cx, cy, obj + 3 * i, img + 2 * i), 1e12); }
@@ -912,8 +910,8 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const float* __restrict__ ob
   if (tid == 0) {
     double w[3];
     rotation_to_rodrigues(sR, w);
-    for (int k = 0; k < 3; k++) { rt[k] = w[k]; rt[3 + k] = st[k]; }
-    *success = m > 0 ? 1 : 0;
+    for (int k = 0; k < 3; k++) { res.rvec[k] = w[k]; res.tvec[k] = st[k]; }
+    res.success = m > 0 ? 1 : 0;
   }
 }
 
@@ -931,7 +929,7 @@ static void fm_own_pass(hipStream_t st, const FmLayout& d, int nprob, int n_boun
   hipLaunchKernelGGL(k_ransac_select, dim3(nprob), dim3(1), 0, st, d.counts, H, d.probs, 8, confidence, 1, d.sel);
   hipLaunchKernelGGL(k_f_mask, dim3((std::max(n_bound, 9) + 255) / 256, nprob), dim3(256), 0, st, d_p1, d_p2, d.probs, H, d.models, d.sel, threshold * threshold, d_mask, d.F, 0);
 }
-static void pnp_own_pass(hipStream_t st, const PnpLayout& d, int nprob, const float* d_obj, const float* d_img, int* d_inl, unsigned char* d_rec, int H,
+static void pnp_own_pass(hipStream_t st, const PnpLayout& d, int nprob, const float* d_obj, const float* d_img, int* d_inl, PnpRecord* d_rec, int H,
                          const double* K4, double reproj_err, double confidence) {
   const int H4 = kP3pPoses * H;
   const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3], thr2 = reproj_err * reproj_err;
@@ -988,7 +986,7 @@ static void fm_cv_pass(hipStream_t st, const PinnedIo* io, const FmLayout& d, co
 // cv::solvePnPRansac's procedure likewise: the 5-point samples depend on the counts alone; a problem below kPnpCvMinPoints gets none and runs
 // no iteration (n == 5 would be solvePnP on all points, n == 4 the P3P kernel: not what the reference can reach)
 static void pnp_cv_pass(hipStream_t st, const PinnedIo* io, const PnpLayout& d, const PnpLayout& h, int nprob, const int32_t* offsets, const float* d_obj,
-                        const float* d_img, int* d_inl, unsigned char* d_rec, int* d_sel, int H, const double* K4, double reproj_err, double confidence) {
+                        const float* d_img, int* d_inl, PnpRecord* d_rec, int* d_sel, int H, const double* K4, double reproj_err, double confidence) {
   memset(h.samples, 0, h.sampb);
   for (int b = 0; b < nprob; b++) {
     const int n = offsets[b + 1] - offsets[b];
@@ -1197,14 +1195,14 @@ dvs_status fm_own_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2,
 }
 
 dvs_status pnp_own_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, const int* d_n, unsigned long long seed, const double* K4,
-                          int iterations, double reproj_err, double confidence, int* d_inl, unsigned char* d_out64) {
-  DVS_ARG(ctx && d_obj && d_img && d_n && K4 && d_inl && d_out64 && iterations >= 1 && iterations <= kPnpMaxIters && reproj_err > 0);
+                          int iterations, double reproj_err, double confidence, int* d_inl, PnpRecord* d_out) {
+  DVS_ARG(ctx && d_obj && d_img && d_n && K4 && d_inl && d_out && iterations >= 1 && iterations <= kPnpMaxIters && reproj_err > 0);
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   PnpLayout d;
   DVS_TRY(lay_out(ctx, kFormDevice, false, 1, 0, iterations, &d));
   hipLaunchKernelGGL(k_ransac_prob, dim3(1), dim3(1), 0, st, d.probs, d_n, seed);
-  pnp_own_pass(st, d, 1, d_obj, d_img, d_inl, d_out64, iterations, K4, reproj_err, confidence);
+  pnp_own_pass(st, d, 1, d_obj, d_img, d_inl, d_out, iterations, K4, reproj_err, confidence);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
@@ -1243,8 +1241,8 @@ dvs_status fm_cv_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, 
 }
 
 dvs_status pnp_cv_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, int n, const double* K4, int iterations, double reproj_err,
-                         double confidence, int* d_inl, unsigned char* d_out64, int* d_sel4) {
-  DVS_ARG(ctx && d_obj && d_img && K4 && d_inl && d_out64 && d_sel4 && n >= kPnpCvMinPoints && iterations >= 1 && iterations <= kPnpMaxIters && reproj_err > 0 &&
+                         double confidence, int* d_inl, PnpRecord* d_out, SelRecord* d_sel) {
+  DVS_ARG(ctx && d_obj && d_img && K4 && d_inl && d_out && d_sel && n >= kPnpCvMinPoints && iterations >= 1 && iterations <= kPnpMaxIters && reproj_err > 0 &&
           confidence > 0 && confidence < 1);
   DVS_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -1255,7 +1253,7 @@ dvs_status pnp_cv_device(dvs_matcher* ctx, const float* d_obj, const float* d_im
   const PnpLayout h(io->h(), kFormPinned, true, 1, 0, iterations);
   const int32_t offsets[2] = {0, n};
   // (returns with the import still reading the block: PinnedIo::reserve waits before it releases one)
-  pnp_cv_pass(st, io, d, h, 1, offsets, d_obj, d_img, d_inl, d_out64, d_sel4, iterations, K4, reproj_err, confidence);
+  pnp_cv_pass(st, io, d, h, 1, offsets, d_obj, d_img, d_inl, d_out, &d_sel->best, iterations, K4, reproj_err, confidence);
   DVS_HIP(hipGetLastError());
   return DVS_OK;
 }
@@ -1420,21 +1418,21 @@ dvs_status dvs_test_ransac_select(const int32_t* counts, int32_t H, int32_t n, i
 dvs_status dvs_test_pnp_refine(const float* pts3d, const float* pts2d, int32_t n, const double* K4, const double* pose12, double reproj_err,
                                int32_t* inliers, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
   DVS_ARG(pts3d && pts2d && n >= 1 && K4 && reproj_err > 0 && inliers && n_inliers && success && rvec3 && tvec3);
-  DeviceBuf<float> dobj, dimg; DeviceBuf<RansacProb> dp; DeviceBuf<double> dpose; DeviceBuf<int> dsel, dinl; DeviceBuf<unsigned char> dres;
+  DeviceBuf<float> dobj, dimg; DeviceBuf<RansacProb> dp; DeviceBuf<double> dpose; DeviceBuf<int> dsel, dinl; DeviceBuf<PnpRecord> dres;
   DVS_TRY(dobj.upload(std::vector<float>(pts3d, pts3d + 3 * (size_t)n)));
   DVS_TRY(dimg.upload(std::vector<float>(pts2d, pts2d + 2 * (size_t)n)));
   DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb::seeded(0, n, 0ull))));
   DVS_TRY(dpose.upload(pose12 ? std::vector<double>(pose12, pose12 + 12) : std::vector<double>(12, 0.0)));
   DVS_TRY(dsel.upload(std::vector<int>{pose12 ? 0 : -1, 1, 0, 0}));
   DVS_TRY(dinl.upload(std::vector<int>((size_t)n, -1)));
-  DVS_TRY(dres.alloc(kPnpRecord));
+  DVS_TRY(dres.alloc(1));
   hipLaunchKernelGGL(k_pnp_refine, dim3(1), dim3(256), 0, 0, dobj.get(), dimg.get(), dp.get(), 1, dpose.get(), dsel.get(), K4[0], K4[1], K4[2], K4[3],
                      reproj_err * reproj_err, dinl.get(), dres.get());
   DVS_HIP(hipGetLastError());
-  unsigned char res[kPnpRecord];
-  DVS_HIP(hipMemcpy(res, dres.get(), kPnpRecord, hipMemcpyDeviceToHost));
+  PnpRecord res;
+  DVS_HIP(hipMemcpy(&res, dres.get(), sizeof(res), hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(inliers, dinl.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
-  memcpy(n_inliers, res, 4); memcpy(success, res + 4, 4); memcpy(rvec3, res + 16, 24); memcpy(tvec3, res + 40, 24);
+  *n_inliers = res.n_inliers; *success = res.success; memcpy(rvec3, res.rvec, sizeof(res.rvec)); memcpy(tvec3, res.tvec, sizeof(res.tvec));
   return DVS_OK;
 }
 
@@ -1526,7 +1524,7 @@ static __global__ void k_test_pnpcv_model(const double* __restrict__ model6, dou
 dvs_status dvs_test_pnpcv_refit(const float* pts3d, const float* pts2d, int32_t n, const double* K4, const double* model6, double reproj_err, int32_t* inliers,
                                 int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3, double* dbg8) {
   DVS_ARG(pts3d && pts2d && n >= 1 && K4 && reproj_err > 0 && inliers && n_inliers && success && rvec3 && tvec3 && dbg8);
-  DeviceBuf<float> dobj, dimg; DeviceBuf<RansacProb> dp; DeviceBuf<double> dm6, dm18, ddbg; DeviceBuf<int> dsel, dinl; DeviceBuf<unsigned char> dres;
+  DeviceBuf<float> dobj, dimg; DeviceBuf<RansacProb> dp; DeviceBuf<double> dm6, dm18, ddbg; DeviceBuf<int> dsel, dinl; DeviceBuf<PnpRecord> dres;
   DVS_TRY(dobj.upload(std::vector<float>(pts3d, pts3d + 3 * (size_t)n)));
   DVS_TRY(dimg.upload(std::vector<float>(pts2d, pts2d + 2 * (size_t)n)));
   DVS_TRY(dp.upload(std::vector<RansacProb>(1, RansacProb::sampled(0, n, 1))));
@@ -1535,16 +1533,17 @@ dvs_status dvs_test_pnpcv_refit(const float* pts3d, const float* pts2d, int32_t 
   DVS_TRY(ddbg.upload(std::vector<double>(8, -1.0)));
   DVS_TRY(dsel.upload(std::vector<int>{model6 ? 0 : -1, 1, 0, 0}));
   DVS_TRY(dinl.upload(std::vector<int>((size_t)n, -1)));
-  DVS_TRY(dres.upload(std::vector<unsigned char>(kPnpRecord, 0xff)));
+  DVS_TRY(dres.alloc(1));
+  DVS_HIP(hipMemset(dres.get(), 0xff, sizeof(PnpRecord)));
   if (model6) hipLaunchKernelGGL(k_test_pnpcv_model, dim3(1), dim3(1), 0, 0, dm6.get(), dm18.get());
   hipLaunchKernelGGL(k_pnpcv_refit, dim3(1), dim3(64), 0, 0, dobj.get(), dimg.get(), dp.get(), 1, dm18.get(), dsel.get(), K4[0], K4[1], K4[2], K4[3],
                      (float)(reproj_err * reproj_err), dinl.get(), dres.get(), ddbg.get());
   DVS_HIP(hipGetLastError());
-  unsigned char res[kPnpRecord];
-  DVS_HIP(hipMemcpy(res, dres.get(), kPnpRecord, hipMemcpyDeviceToHost));
+  PnpRecord res;
+  DVS_HIP(hipMemcpy(&res, dres.get(), sizeof(res), hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(inliers, dinl.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
   DVS_HIP(hipMemcpy(dbg8, ddbg.get(), 64, hipMemcpyDeviceToHost));
-  memcpy(n_inliers, res, 4); memcpy(success, res + 4, 4); memcpy(rvec3, res + 16, 24); memcpy(tvec3, res + 40, 24);
+  *n_inliers = res.n_inliers; *success = res.success; memcpy(rvec3, res.rvec, sizeof(res.rvec)); memcpy(tvec3, res.tvec, sizeof(res.tvec));
   return DVS_OK;
 }
 
@@ -1559,13 +1558,14 @@ dvs_status dvs_test_ransac_device_form(dvs_matcher* ctx, int32_t form, const flo
   const size_t wa = fm ? 2 : 3;
   std::vector<float> a((size_t)cap * wa, 0.f), b((size_t)cap * 2, 0.f);
   if (n) { memcpy(a.data(), pts_a, (size_t)n * wa * 4); memcpy(b.data(), pts_b, (size_t)n * 8); }
-  DeviceBuf<float> da, db; DeviceBuf<int> dn, dinl, dsel; DeviceBuf<unsigned char> dmask, drec;
+  DeviceBuf<float> da, db; DeviceBuf<int> dn, dinl; DeviceBuf<SelRecord> dsel; DeviceBuf<unsigned char> dmask; DeviceBuf<PnpRecord> drec;
   DVS_TRY(da.upload(a)); DVS_TRY(db.upload(b));
   DVS_TRY(dn.upload(std::vector<int>(1, n)));
   DVS_TRY(dmask.upload(std::vector<unsigned char>((size_t)cap, 0xff)));
-  DVS_TRY(drec.upload(std::vector<unsigned char>(kPnpRecord, 0xff)));
+  DVS_TRY(drec.alloc(1));
+  DVS_HIP(hipMemset(drec.get(), 0xff, sizeof(PnpRecord)));
   DVS_TRY(dinl.upload(std::vector<int>((size_t)cap, -1)));
-  DVS_TRY(dsel.upload(std::vector<int>(4, -1)));
+  DVS_TRY(dsel.upload(std::vector<SelRecord>(1, SelRecord{-1, -1, -1, -1})));
   if (form == 0) DVS_TRY(fm_own_device(ctx, da.get(), db.get(), dn.get(), cap, seed, threshold, confidence, iters, dmask.get()));
   if (form == 1) DVS_TRY(fm_cv_device(ctx, da.get(), db.get(), n, threshold, confidence, iters, dmask.get()));
   if (form == 2) DVS_TRY(pnp_own_device(ctx, da.get(), db.get(), dn.get(), seed, K4, iters, threshold, confidence, dinl.get(), drec.get()));
@@ -1575,7 +1575,7 @@ dvs_status dvs_test_ransac_device_form(dvs_matcher* ctx, int32_t form, const flo
   else {
     DVS_HIP(hipMemcpy(rec64, drec.get(), kPnpRecord, hipMemcpyDeviceToHost));
     DVS_HIP(hipMemcpy(inliers, dinl.get(), (size_t)cap * 4, hipMemcpyDeviceToHost));
-    if (form == 3) DVS_HIP(hipMemcpy(sel4, dsel.get(), 16, hipMemcpyDeviceToHost));
+    if (form == 3) DVS_HIP(hipMemcpy(sel4, dsel.get(), sizeof(SelRecord), hipMemcpyDeviceToHost));
   }
   return DVS_OK;
 }

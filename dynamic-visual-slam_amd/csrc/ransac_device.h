@@ -5,7 +5,7 @@
 // slot 0 (hypotheses, counts, selection: gone with the next call).
 #pragma once
 #include "matcher.h"
-#include "ransac_layout.h"   // RansacProb
+#include "ransac_layout.h"   // RansacProb, PnpRecord, SelRecord
 
 namespace dvs {
 
@@ -13,18 +13,18 @@ namespace dvs {
 // grids): d_mask[0 .. *d_n) = the inlier mask.  Fewer than 8 correspondences give a mask of zeros.  Asynchronous.
 dvs_status fm_own_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, const int* d_n, int n_bound, unsigned long long seed, double threshold,
                          double confidence, int max_iters, unsigned char* d_mask);
-// dvs_solve_pnp_ransac on d_obj (n x 3) / d_img (n x 2), count *d_n: d_out64 = the stage's 64-byte result record {int32 n_inliers,
-// int32 success, 8 bytes unused, double rvec[3], double tvec[3]}, d_inl = ascending inlier indices.  Asynchronous.
+// dvs_solve_pnp_ransac on d_obj (n x 3) / d_img (n x 2), count *d_n: d_out = the stage's result record (ransac_layout.h), d_inl = ascending
+// inlier indices.  Asynchronous.
 dvs_status pnp_own_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, const int* d_n, unsigned long long seed, const double* K4,
-                          int iterations, double reproj_err, double confidence, int* d_inl, unsigned char* d_out64);
+                          int iterations, double reproj_err, double confidence, int* d_inl, PnpRecord* d_out);
 // dvs_find_fundamental_cv: OpenCV's sample sequence is drawn on the host from the count AND the points (collinear samples are drawn again),
 // so the n (>= 8) correspondences are read back first; samples go up, the 16-byte selection record comes back (the 96-iteration pass may
 // ask for the full one).  The mask stays on the device.  Synchronises.
 dvs_status fm_cv_device(dvs_matcher* ctx, const float* d_p1, const float* d_p2, int n, double threshold, double confidence, int max_iters,
                         unsigned char* d_mask);
-// dvs_solve_pnp_ransac_cv: its 5-point samples depend on the count alone (host `n` >= 6); samples go up, nothing comes back.  d_out64 as
-// above (rvec / tvec are meaningful when d_sel4[0] >= 0), d_sel4 = {best model or -1, iterations run, its inlier count, 0}.  Asynchronous.
+// dvs_solve_pnp_ransac_cv: its 5-point samples depend on the count alone (host `n` >= 6); samples go up, nothing comes back.  d_out as
+// above (rvec / tvec are meaningful when d_sel->best >= 0), d_sel = {best model or -1, iterations run, its inlier count, 0}.  Asynchronous.
 dvs_status pnp_cv_device(dvs_matcher* ctx, const float* d_obj, const float* d_img, int n, const double* K4, int iterations, double reproj_err,
-                         double confidence, int* d_inl, unsigned char* d_out64, int* d_sel4);
+                         double confidence, int* d_inl, PnpRecord* d_out, SelRecord* d_sel);
 
 }  // namespace dvs

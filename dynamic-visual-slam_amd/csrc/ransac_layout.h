@@ -3,6 +3,7 @@
 // A layout is stated once and carved by the host batch bodies and by the device forms of ransac_device.h alike; nothing outside this
 // header computes an address inside such a block.  Needs device_mem.h alone (a stand-alone host program can include it).
 #pragma once
+#include <stddef.h>
 #include <string.h>
 #include "device_mem.h"
 
@@ -30,8 +31,16 @@ constexpr int kPnpOwnMinPoints = 4, kPnpCvMinPoints = 6;
 constexpr int kF7Roots = 3, kP3pPoses = 4;                // candidate models per sample: 7-point cubic, P3P quartic
 constexpr int kFmModel = 9, kPosePnp = 12, kModelPnpCv = 18, kSel = 4;   // doubles per F / (R, t) / (rvec, tvec, R, pad); ints per select record
 constexpr size_t kFmModelBytes = kFmModel * sizeof(double), kPosePnpBytes = kPosePnp * sizeof(double), kModelPnpCvBytes = kModelPnpCv * sizeof(double);
-constexpr size_t kPnpRecord = 64;                        // {int32 n_inliers, int32 success, 8 unused, double rvec[3], tvec[3]}
+constexpr size_t kPnpRecord = 64;                        // bytes of a PnpRecord
 constexpr size_t kScratchSlack = 64;                      // requested behind a device layout's last array
+
+// The result of one PnP problem, as k_pnp_refine / k_pnpcv_refit write it and every host reader sees it.  rvec / tvec are meaningful where
+// the estimator succeeded (the OpenCV-procedure form: wherever a model was selected); k_pnp_refine never writes `unused`.
+struct PnpRecord { int32_t n_inliers, success; int32_t unused[2]; double rvec[3], tvec[3]; };
+static_assert(sizeof(PnpRecord) == kPnpRecord && offsetof(PnpRecord, rvec) == 16 && offsetof(PnpRecord, tvec) == 40, "the 64-byte PnP result record");
+// What k_ransac_select leaves per problem: 16 bytes.  `more`: the loop wanted more iterations than it had models for (LMedS: it succeeded).
+struct SelRecord { int32_t best /* or -1 */, iterations, inliers, more; };
+static_assert(sizeof(SelRecord) == kSel * sizeof(int), "the 16-byte select record");
 
 // Which regions a block holds.  `points`: the correspondences and the per-correspondence results lie in the block (a host batch) or at
 // addresses of the caller's (a device form, which imports [problem records | samples] alone).  `work`: the device-only arrays.
@@ -41,8 +50,8 @@ constexpr RansacRegions kBatchDevice{true, true}, kBatchPinned{true, false}, kFo
 // Alignment, for every (nprob >= 1, total >= 0, H >= 1): the in region is carved in units of 16 bytes from a base that hipMalloc /
 // hipHostMalloc align far beyond that, so the problem records, every imported array and the end of the region sit on 16 bytes.  Behind
 // it the unit is 4 bytes, and every double array is preceded only by the in region, by double arrays, by PAIRS of int arrays of equal
-// length (valid + counts) and by 16-byte select records: every double* member sits on 8 bytes.  (The 64-byte PnP result records are
-// bytes to the host and dword stores to the kernels; behind an odd number of OpenCV-procedure models they sit on 4.)
+// length (valid + counts) and by 16-byte select records: every double* member sits on 8 bytes.  (Behind an odd number of
+// OpenCV-procedure models the 64-byte PnP result records sit on 4: the device stores through them as it did, the host copies one out.)
 
 // Fundamental matrix, own (cv = false: no samples, H models per problem) and OpenCV-procedure (7-point samples, 3 H models):
 //   in   [problem records | pts1 | pts2 | samples 7 x H per problem]            imported
@@ -86,7 +95,7 @@ struct FmLayout {
 struct PnpLayout {
   RansacProb* probs = nullptr; float *obj = nullptr, *img = nullptr; int32_t* samples = nullptr;
   double* models = nullptr; int *valid = nullptr, *counts = nullptr;
-  uint8_t* rec = nullptr; int *inl = nullptr, *sel = nullptr;
+  PnpRecord* rec = nullptr; int *inl = nullptr, *sel = nullptr;
   size_t sampb = 0, inb = 0, outb = 0, bytes = 0;
   PnpLayout() = default;
   PnpLayout(uint8_t* base, RansacRegions r, bool cv, int nprob, int total, int H) {
@@ -102,7 +111,7 @@ struct PnpLayout {
     if (r.work && !cv) { c.take(models, kPosePnp * nmodels); c.take(valid, nmodels); c.take(counts, nmodels); c.take(sel, kSel * (size_t)nprob); }
     const size_t out0 = c.used;
     if (r.points) {
-      c.take(rec, kPnpRecord * nprob); c.take(inl, total);
+      c.take(rec, nprob); c.take(inl, total);
       if (cv) c.take(sel, kSel * (size_t)nprob);
     }
     outb = c.used - out0; bytes = c.used;
@@ -111,13 +120,12 @@ struct PnpLayout {
   // wherever a model was selected
   void unpack(int nprob, const int32_t* offsets, bool by_sel, double* rvec3, double* tvec3, int32_t* inliers, int32_t* n_inliers, int32_t* success) const {
     for (int b = 0; b < nprob; b++) {
-      const uint8_t* r = rec + kPnpRecord * b;
-      int nin = 0, succ = 0;
-      memcpy(&nin, r, 4); memcpy(&succ, r + 4, 4);
-      if (n_inliers) n_inliers[b] = nin;
-      success[b] = succ;
-      if (by_sel ? sel[kSel * b] >= 0 : succ != 0) { memcpy(rvec3 + 3 * (size_t)b, r + 16, 24); memcpy(tvec3 + 3 * (size_t)b, r + 40, 24); }
-      if (inliers && nin > 0) memcpy(inliers + offsets[b], inl + offsets[b], (size_t)nin * 4);
+      PnpRecord r;
+      memcpy(&r, rec + b, sizeof(r));   // (a record may sit on 4 bytes)
+      if (n_inliers) n_inliers[b] = r.n_inliers;
+      success[b] = r.success;
+      if (by_sel ? sel[kSel * b] >= 0 : r.success != 0) { memcpy(rvec3 + 3 * (size_t)b, r.rvec, sizeof(r.rvec)); memcpy(tvec3 + 3 * (size_t)b, r.tvec, sizeof(r.tvec)); }
+      if (inliers && r.n_inliers > 0) memcpy(inliers + offsets[b], inl + offsets[b], (size_t)r.n_inliers * sizeof(int));
     }
   }
 };

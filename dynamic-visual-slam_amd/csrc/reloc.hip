@@ -24,14 +24,15 @@
 #include "ransac_device.h"
 #include "backend_internal.h"
 #include "maptrack_internal.h"
+#include "pose_host.h"
 
 namespace dvs {
 
 enum { RC_NLM = 0, RC_NKP = 1, RC_PROPOSED = 2, RC_PAIRS = 3, RC_NPNP = 4, RC_INTS = 8 };
 constexpr unsigned long long kRlNoKey = ~0ull;
 constexpr unsigned long long kRlRowMask = (1ull << 40) - 1ull;
-struct RlRec { int n_proposed, n_pairs, r0, r1, r2, r3, r4, r5; unsigned char pnp[64]; };   // what crosses to the host: 96 bytes
-static_assert(sizeof(RlRec) == 96, "record layout");
+struct RlRec { int n_proposed, n_pairs, r0, r1, r2, r3, r4, r5; PnpRecord pnp; };   // what crosses to the host: 96 bytes
+static_assert(sizeof(RlRec) == 96 && offsetof(RlRec, pnp) == 32, "record layout");
 
 __global__ __launch_bounds__(256) void k_rl_begin(int n_lm, int n_kp, unsigned long long* __restrict__ key, int* __restrict__ counters) {
   const int k = blockIdx.x * 256 + threadIdx.x;
@@ -83,14 +84,14 @@ __global__ __launch_bounds__(256) void k_rl_list(int n_kp, const unsigned long l
   if (threadIdx.x == 0) { counters[RC_PAIRS] = m; counters[RC_NPNP] = m >= min_pairs ? m : 0; }
 }
 
-__global__ void k_rl_record(const int* __restrict__ counters, const unsigned char* __restrict__ pnp64, RlRec* __restrict__ out) {
+__global__ void k_rl_record(const int* __restrict__ counters, const PnpRecord* __restrict__ pnp, RlRec* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   RlRec r;
   memset(&r, 0, sizeof(r));
   r.n_proposed = counters[RC_PROPOSED]; r.n_pairs = counters[RC_PAIRS];
-  if (counters[RC_NPNP] > 0) {
-    for (int k = 0; k < 8; k++) r.pnp[k] = pnp64[k];
-    for (int k = 16; k < 64; k++) r.pnp[k] = pnp64[k];
+  if (counters[RC_NPNP] > 0) {   // every field the estimator writes (`unused` stays zero)
+    r.pnp.n_inliers = pnp->n_inliers; r.pnp.success = pnp->success;
+    for (int k = 0; k < 3; k++) { r.pnp.rvec[k] = pnp->rvec[k]; r.pnp.tvec[k] = pnp->tvec[k]; }
   }
   *out = r;
 }
@@ -105,28 +106,6 @@ static dvs_status reloc_check_params(const dvs_reloc_params& P) {
   DVS_ARG(P.pnp_confidence > 0 && P.pnp_confidence < 1);
   DVS_ARG(P.min_pnp_inliers >= 0 && P.min_confirmed >= 0);
   return DVS_OK;
-}
-
-// camera-to-world from the PnP record (x_cam = R_cw X + tvec): R_cw by Rodrigues' formula in FP64, every expression as written
-static void reloc_pose(const double* rvec, const double* tvec, double* R9, double* t3) {
-  const double wx = rvec[0], wy = rvec[1], wz = rvec[2];
-  const double th2 = (wx * wx + wy * wy) + wz * wz, th = sqrt(th2);
-  const double K[9] = {0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0};
-  double Rcw[9];
-  if (th < 1e-12) {
-    for (int k = 0; k < 9; k++) Rcw[k] = (k % 4 == 0 ? 1.0 : 0.0) + K[k];
-  } else {
-    const double A = sin(th) / th, B = (1.0 - cos(th)) / th2;
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) {
-        const double k2 = (K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j]) + K[3 * i + 2] * K[6 + j];
-        Rcw[3 * i + j] = ((i == j ? 1.0 : 0.0) + A * K[3 * i + j]) + B * k2;
-      }
-  }
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) R9[3 * i + j] = Rcw[3 * j + i];
-    t3[i] = -((Rcw[i] * tvec[0] + Rcw[3 + i] * tvec[1]) + Rcw[6 + i] * tvec[2]);
-  }
 }
 
 }  // namespace dvs
@@ -144,17 +123,15 @@ struct dvs_reloc {
   // per keypoint (grow-only): the proposal keys and the list
   Column<unsigned long long> key; Column<float, 3> obj; Column<float, 2> img; Column<int> p_lm, p_kp, p_dist, p_inl;
   size_t c_kp = 0;
-  DeviceBuf<unsigned char> pnp64;
+  DeviceBuf<PnpRecord> pnp;
   DeviceBuf<RlRec> d_rec;
-  // staging of the host form (grow-only)
-  DeviceBuf<float> s_xyz; DeviceBuf<uint8_t> s_ldesc, s_kdesc; DeviceBuf<long long> s_id; DeviceBuf<dvs_keypoint> s_kps;
-  size_t cs_lm = 0, cs_kp = 0;
+  FrameStaging stage;              // of the host form
   // stage events, created by dvs_reloc_set_timing alone
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev[4];
   bool timing = false, timed = false;
   // the last call
   int last_n_lm = 0, last_n_kp = 0, last_pairs = 0, last_inliers = 0;
-  unsigned char last_pnp[64] = {0};   // stage 4's record as it came back (zeros when nothing was solved)
+  PnpRecord last_pnp = {};         // stage 4's record as it came back (zeros when nothing was solved)
 };
 
 static dvs_status rl_grow_kp(dvs_reloc* h, size_t n) { return grow_rows(h->c_kp, n, n + n / 4, h->key, h->obj, h->img, h->p_lm, h->p_kp, h->p_dist, h->p_inl); }
@@ -190,9 +167,9 @@ dvs_status dvs_reloc_create(const dvs_reloc_params* params, int32_t device, dvs_
   h->P = *params; h->device = device;
   auto alloc_all = [&]() -> dvs_status {
     DVS_TRY(dvs_matcher_create_on_stream(device, nullptr, &h->ctx));
-    DVS_TRY(h->counters.alloc(RC_INTS)); DVS_TRY(h->pnp64.alloc(64)); DVS_TRY(h->d_rec.alloc(1));
+    DVS_TRY(h->counters.alloc(RC_INTS)); DVS_TRY(h->pnp.alloc(1)); DVS_TRY(h->d_rec.alloc(1));
     DVS_HIP(hipMemset(h->counters.get(), 0, RC_INTS * sizeof(int)));
-    DVS_HIP(hipMemset(h->pnp64.get(), 0, 64));
+    DVS_HIP(hipMemset(h->pnp.get(), 0, sizeof(PnpRecord)));
     DVS_HIP(hipMemset(h->d_rec.get(), 0, sizeof(RlRec)));
     return DVS_OK;
   };
@@ -206,7 +183,6 @@ void dvs_reloc_destroy(dvs_reloc* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->ctx) (void)hipStreamSynchronize(h->ctx->stream);
-  for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
   dvs_matcher_destroy(h->ctx);
   delete h;
 }
@@ -222,7 +198,7 @@ dvs_status dvs_reloc_set_stream(dvs_reloc* h, void* hip_stream) {
 dvs_status dvs_reloc_set_timing(dvs_reloc* h, int32_t on) {
   DVS_ARG(h);
   DVS_HIP(hipSetDevice(h->device));
-  if (on) for (hipEvent_t& e : h->ev) if (!e) DVS_HIP(hipEventCreate(&e));
+  if (on) for (Event& e : h->ev) if (!(hipEvent_t)e) DVS_HIP(e.create(true));
   h->timing = on != 0; h->timed = false;
   return DVS_OK;
 }
@@ -267,8 +243,8 @@ dvs_status dvs_reloc_locate_device(dvs_reloc* h, dvs_maptrack* mt, const float* 
   if (h->timing) DVS_HIP(hipEventRecord(h->ev[2], st));
   // ---- stage 4
   DVS_TRY(pnp_own_device(h->ctx, h->obj.get(), h->img.get(), cnt + RC_NPNP, (unsigned long long)P.seed, P.K4, P.pnp_iterations, P.pnp_reproj_err,
-                         P.pnp_confidence, h->p_inl.get(), h->pnp64.get()));
-  hipLaunchKernelGGL(k_rl_record, dim3(1), dim3(64), 0, st, (const int*)cnt, (const unsigned char*)h->pnp64.get(), h->d_rec.get());
+                         P.pnp_confidence, h->p_inl.get(), h->pnp.get()));
+  hipLaunchKernelGGL(k_rl_record, dim3(1), dim3(64), 0, st, (const int*)cnt, (const PnpRecord*)h->pnp.get(), h->d_rec.get());
   DVS_HIP(hipGetLastError());
   PinnedIo* io;
   DVS_TRY(matcher_pinned(h->ctx, sizeof(RlRec), &io));
@@ -277,21 +253,19 @@ dvs_status dvs_reloc_locate_device(dvs_reloc* h, dvs_maptrack* mt, const float* 
   if (h->timing) { DVS_HIP(hipEventSynchronize(h->ev[3])); h->timed = true; }
   RlRec rec;
   memcpy(&rec, io->h(), sizeof(rec));
-  memcpy(h->last_pnp, rec.pnp, 64);
-  int32_t pnp_n = 0, pnp_ok = 0;
-  double rt[6];
-  memcpy(&pnp_n, rec.pnp, 4); memcpy(&pnp_ok, rec.pnp + 4, 4); memcpy(rt, rec.pnp + 16, 48);
+  h->last_pnp = rec.pnp;
+  const PnpRecord& pnp = rec.pnp;
   memset(result, 0, sizeof(*result));
   result->R[0] = result->R[4] = result->R[8] = 1.0;
   result->n_proposed = rec.n_proposed; result->n_pairs = rec.n_pairs;
   h->last_n_lm = n_lm; h->last_n_kp = n_kp; h->last_pairs = rec.n_pairs;
   if (rec.n_pairs < P.min_pairs) { result->status = DVS_RELOC_FEW_PAIRS; return DVS_OK; }
-  result->pnp_inliers = pnp_n; result->pnp_success = pnp_ok;
-  h->last_inliers = pnp_n;
+  result->pnp_inliers = pnp.n_inliers; result->pnp_success = pnp.success;
+  h->last_inliers = pnp.n_inliers;
   bool finite = true;
-  for (int k = 0; k < 6; k++) finite = finite && __builtin_isfinite(rt[k]);
-  if (!pnp_ok || pnp_n < P.min_pnp_inliers || !finite) { result->status = DVS_RELOC_NO_POSE; return DVS_OK; }
-  reloc_pose(rt, rt + 3, result->pnp_R, result->pnp_t);
+  for (int k = 0; k < 3; k++) finite = finite && __builtin_isfinite(pnp.rvec[k]) && __builtin_isfinite(pnp.tvec[k]);
+  if (!pnp.success || pnp.n_inliers < P.min_pnp_inliers || !finite) { result->status = DVS_RELOC_NO_POSE; return DVS_OK; }
+  reloc_pose(pnp.rvec, pnp.tvec, result->pnp_R, result->pnp_t);
   // ---- stage 5
   DVS_TRY(dvs_maptrack_track_device(mt, d_lm_xyz, d_lm_desc, d_lm_id, n_lm, d_kps, d_desc, n_kp, result->pnp_R, result->pnp_t, &result->track));
   if (result->track.status == DVS_MAPTRACK_OK && result->track.n_inliers >= P.min_confirmed) {
@@ -307,36 +281,10 @@ dvs_status dvs_reloc_locate(dvs_reloc* h, dvs_maptrack* mt, const float* lm_xyz,
                             const dvs_keypoint* kps, const uint8_t* desc, int32_t n_kp, dvs_reloc_result* result) {
   DVS_ARG(h && mt && result && n_lm >= 0 && n_kp >= 0 && n_lm <= (1 << 30) - 1 && n_kp <= (1 << 30));
   DVS_ARG((n_lm == 0 || (lm_xyz && lm_desc)) && (n_kp == 0 || (kps && desc)));
-  const dvs_maptrack_params& M = maptrack_params(mt);   // the image and the octave table are the confirming handle's
-  for (int k = 0; k < n_kp; k++)
-    DVS_ARG(kps[k].x >= 0.f && kps[k].x < (float)M.cols && kps[k].y >= 0.f && kps[k].y < (float)M.rows && kps[k].octave >= 0 && kps[k].octave < M.n_levels);
-  if (lm_id) for (int j = 1; j < n_lm; j++) DVS_ARG(lm_id[j - 1] < lm_id[j]);
-  DVS_HIP(hipSetDevice(h->device));
-  hipStream_t st = h->ctx->stream;
-  if ((size_t)n_lm > h->cs_lm || (size_t)n_kp > h->cs_kp) DVS_HIP(hipStreamSynchronize(st));
-  if ((size_t)n_lm > h->cs_lm) {
-    h->cs_lm = 0;
-    const size_t c = (size_t)n_lm + (size_t)n_lm / 4;
-    DVS_TRY(h->s_xyz.alloc(c * 3)); DVS_TRY(h->s_ldesc.alloc(c * 32)); DVS_TRY(h->s_id.alloc(c));
-    h->cs_lm = c;
-  }
-  if ((size_t)n_kp > h->cs_kp) {
-    h->cs_kp = 0;
-    const size_t c = (size_t)n_kp + (size_t)n_kp / 4;
-    DVS_TRY(h->s_kps.alloc(c)); DVS_TRY(h->s_kdesc.alloc(c * 32));
-    h->cs_kp = c;
-  }
-  if (n_lm > 0) {
-    DVS_HIP(hipMemcpyAsync(h->s_xyz.get(), lm_xyz, (size_t)n_lm * 12, hipMemcpyHostToDevice, st));
-    DVS_HIP(hipMemcpyAsync(h->s_ldesc.get(), lm_desc, (size_t)n_lm * 32, hipMemcpyHostToDevice, st));
-    if (lm_id) DVS_HIP(hipMemcpyAsync(h->s_id.get(), lm_id, (size_t)n_lm * 8, hipMemcpyHostToDevice, st));
-  }
-  if (n_kp > 0) {
-    DVS_HIP(hipMemcpyAsync(h->s_kps.get(), kps, (size_t)n_kp * sizeof(dvs_keypoint), hipMemcpyHostToDevice, st));
-    DVS_HIP(hipMemcpyAsync(h->s_kdesc.get(), desc, (size_t)n_kp * 32, hipMemcpyHostToDevice, st));
-  }
-  return dvs_reloc_locate_device(h, mt, h->s_xyz.get(), h->s_ldesc.get(), (lm_id && n_lm > 0) ? (const int64_t*)h->s_id.get() : nullptr, n_lm, h->s_kps.get(),
-                                 h->s_kdesc.get(), n_kp, result);
+  // the image and the octave table are the confirming handle's
+  DVS_TRY(stage_frame(h->stage, maptrack_params(mt), h->device, h->ctx->stream, lm_xyz, lm_desc, lm_id, n_lm, kps, desc, n_kp));
+  const FrameStaging& S = h->stage;
+  return dvs_reloc_locate_device(h, mt, S.xyz.get(), S.ldesc.get(), S.ids(lm_id, n_lm), n_lm, S.kps.get(), S.kdesc.get(), n_kp, result);
 }
 
 dvs_status dvs_reloc_get_pairs(dvs_reloc* h, int32_t cap, int32_t* lm_row, int32_t* kp_index, int32_t* dist, uint8_t* pnp_inlier, int32_t* n) {
@@ -348,13 +296,11 @@ dvs_status dvs_reloc_get_pairs(dvs_reloc* h, int32_t cap, int32_t* lm_row, int32
   DVS_HIP(hipSetDevice(h->device));
   hipStream_t st = h->ctx->stream;
   std::vector<int> inl;
-  if (lm_row) DVS_HIP(hipMemcpyAsync(lm_row, h->p_lm.get(), (size_t)m * 4, hipMemcpyDeviceToHost, st));
-  if (kp_index) DVS_HIP(hipMemcpyAsync(kp_index, h->p_kp.get(), (size_t)m * 4, hipMemcpyDeviceToHost, st));
-  if (dist) DVS_HIP(hipMemcpyAsync(dist, h->p_dist.get(), (size_t)m * 4, hipMemcpyDeviceToHost, st));
+  DVS_TRY(copy_out(lm_row, h->p_lm, (size_t)m, st)); DVS_TRY(copy_out(kp_index, h->p_kp, (size_t)m, st)); DVS_TRY(copy_out(dist, h->p_dist, (size_t)m, st));
   const int ni = h->last_inliers < m ? h->last_inliers : m;
   if (pnp_inlier && ni > 0) {
     inl.resize((size_t)ni);
-    DVS_HIP(hipMemcpyAsync(inl.data(), h->p_inl.get(), (size_t)ni * 4, hipMemcpyDeviceToHost, st));
+    DVS_TRY(copy_out(inl.data(), h->p_inl, (size_t)ni, st));
   }
   DVS_HIP(hipStreamSynchronize(st));
   if (pnp_inlier) {
@@ -387,10 +333,8 @@ dvs_status dvs_test_reloc_landmarks(dvs_reloc* h, int32_t cap, dvs_reloc_lm_reco
   std::vector<unsigned long long> key(nk);
   DVS_HIP(hipSetDevice(h->device));
   hipStream_t st = h->ctx->stream;
-  DVS_HIP(hipMemcpyAsync(ti.data(), h->top_idx.get(), 8 * nl, hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipMemcpyAsync(td.data(), h->top_dist.get(), 8 * nl, hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipMemcpyAsync(stt.data(), h->state.get(), nl, hipMemcpyDeviceToHost, st));
-  DVS_HIP(hipMemcpyAsync(key.data(), h->key.get(), 8 * nk, hipMemcpyDeviceToHost, st));
+  DVS_TRY(copy_out(ti.data(), h->top_idx, nl, st)); DVS_TRY(copy_out(td.data(), h->top_dist, nl, st));
+  DVS_TRY(copy_out(stt.data(), h->state, nl, st)); DVS_TRY(copy_out(key.data(), h->key, nk, st));
   DVS_HIP(hipStreamSynchronize(st));
   for (size_t j = 0; j < nl; j++) {
     if (stt[j] < 0) continue;   // a position that is not finite: never compared
@@ -404,7 +348,8 @@ dvs_status dvs_test_reloc_landmarks(dvs_reloc* h, int32_t cap, dvs_reloc_lm_reco
 // (no device work) stage 4's record of the last locate call: what dvs_solve_pnp_ransac would have returned
 dvs_status dvs_test_reloc_pnp_record(dvs_reloc* h, int32_t* n_inliers, int32_t* success, double* rvec3, double* tvec3) {
   DVS_ARG(h && n_inliers && success && rvec3 && tvec3);
-  memcpy(n_inliers, h->last_pnp, 4); memcpy(success, h->last_pnp + 4, 4); memcpy(rvec3, h->last_pnp + 16, 24); memcpy(tvec3, h->last_pnp + 40, 24);
+  const PnpRecord& r = h->last_pnp;
+  *n_inliers = r.n_inliers; *success = r.success; memcpy(rvec3, r.rvec, sizeof(r.rvec)); memcpy(tvec3, r.tvec, sizeof(r.tvec));
   return DVS_OK;
 }
 #endif

@@ -24,6 +24,16 @@ void dvs_test_cull_order(const float* response, const uint8_t* matched, int32_t 
 dvs_status dvs_test_cull_order_device(const float* response, const uint8_t* matched, int32_t n, int32_t max_new, float min_response,
                                       int32_t* order, int32_t* n_out, int32_t* heap_ranges);
 
+/* (no GPU needed) the tracker's pose step (csrc/pose_host.h, frontend.cpp:925-948): the inverse of PnP's motion (rvec3, tvec3), the
+ * motion-outlier test on it and — unless it is one — R9 <- R9 Ri, t3 <- t3 + R9 ti in place.  Returns 1 where the pose was updated, 0
+ * for a motion outlier (R9, t3 untouched).  rodrigues9 (may be NULL) = cv::Rodrigues(rvec3) as the step computes it. */
+int32_t dvs_test_tracker_pose_step(double* R9, double* t3, const double* rvec3, const double* tvec3, double max_translation, double max_rotation,
+                                   double* rodrigues9);
+
+/* (no GPU needed) the relative pose of the motion mask (csrc/pose_host.h): a12 = T(t-1), b12 = T(t-2) or NULL, ref12 = the reference
+ * frame's pose, each {R row-major, t}; R9 / t3 = the result.  quat_xyzw4 (may be NULL) = publishKeyframe's quaternion of a12's rotation. */
+void dvs_test_tracker_relative_pose(const double* a12, const double* b12, const double* ref12, double* R9, double* t3, double* quat_xyzw4);
+
 #ifdef __cplusplus
 }
 #endif

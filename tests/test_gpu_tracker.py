@@ -147,6 +147,31 @@ def test_three_channel_input_equals_the_gray_path(gpu, hooks):
     assert got3[5]["n_extracted"] > 500 and got3[5]["pose_updated"] == 1
 
 
+def _padded(a, extra, fill):
+    """the same pixels as rows of a wider buffer: strides[0] larger than the row, and `fill` in the padding"""
+    buf = np.full((a.shape[0], a.shape[1] + extra) + a.shape[2:], fill, a.dtype)
+    buf[:, :a.shape[1]] = a
+    view = buf[:, :a.shape[1]]
+    assert view.strides[0] > a.shape[1] * a.itemsize * (a.shape[2] if a.ndim == 3 else 1) and not view.flags["C_CONTIGUOUS"]
+    return view
+
+
+def test_row_padded_input_equals_the_contiguous_run(gpu, hooks):
+    """image.strides[0] and depth.strides[0] larger than the row (the row-by-row staging of dvs_tracker_track) over ten frames, gray and
+    BGR: everything equal to the contiguous run, R_ / t_ bit for bit.  The relief depth makes a wrong depth row show in filterDepth's
+    survivors and in the PnP points; the padding holds values no frame has."""
+    import tracker_ref as ref
+    a = _frames(range(10)); depths = _relief(10)
+    bgr = [np.ascontiguousarray(np.stack([x, np.roll(x, 5, axis=0), np.roll(x, 9, axis=1)], 2)) for x in a]
+    for frames in (a, bgr):
+        tc, tp = _tracker(), _tracker()
+        want = ref.run_tracker(tc, frames, depths)
+        got = ref.run_tracker(tp, [_padded(x, 24, 255) for x in frames], [_padded(d, 8, 65535) for d in depths])
+        tc.close(); tp.close()
+        assert ref.first_difference(got, want, poses_bitwise=True) is None, ref.first_difference(got, want, poses_bitwise=True)
+        assert want[9]["n_extracted"] > 500 and sum(r["pose_updated"] for r in want) >= 5      # the runs are not trivially equal
+
+
 def test_opencv_procedures_on_the_relief_scene(gpu, hooks):
     """fm_mode = pnp_mode = 1 (dvs_find_fundamental_cv / dvs_solve_pnp_ransac_cv) on the scene with a 200 mm depth relief, against the same
     loop over the host-pointer _cv entry points: the same equality as with the own estimators"""

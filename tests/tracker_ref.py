@@ -34,6 +34,27 @@ def rodrigues(w):
     return [[((c if i == j else 0.0) + c1 * (k[i] * k[j])) + s * K[i][j] for j in range(3)] for i in range(3)]
 
 
+def inverse_motion(rvec, tvec):
+    """frontend.cpp:937-938 and what isMotionOutlier (:549-570) looks at -> (Ri, ti, |ti|, cos of the angle BEFORE the clamp)"""
+    Rr = rodrigues([float(v) for v in rvec]); tv = [float(v) for v in tvec]
+    Ri = [[Rr[j][i] for j in range(3)] for i in range(3)]
+    ti = [-((Ri[i][0] * tv[0] + Ri[i][1] * tv[1]) + Ri[i][2] * tv[2]) for i in range(3)]
+    tn = math.sqrt((ti[0] * ti[0] + ti[1] * ti[1]) + ti[2] * ti[2])
+    ca = (((Ri[0][0] + Ri[1][1]) + Ri[2][2]) - 1.0) / 2.0
+    return Ri, ti, tn, ca
+
+
+def pose_step(R_, t_, rvec, tvec, max_translation=0.5, max_rotation=0.2):
+    """frontend.cpp:925-948 -> (updated, R_, t_): the pose composed with the inverse of PnP's motion unless that is a motion outlier"""
+    Ri, ti, tn, ca = inverse_motion(rvec, tvec)
+    ang = math.acos(-1.0 if ca < -1.0 else (1.0 if ca > 1.0 else ca))
+    if tn > max_translation or ang > max_rotation:                             # :549-570
+        return False, R_, t_
+    t_ = [t_[i] + ((R_[i][0] * ti[0] + R_[i][1] * ti[1]) + R_[i][2] * ti[2]) for i in range(3)]
+    R_ = [[(R_[i][0] * Ri[0][j] + R_[i][1] * Ri[1][j]) + R_[i][2] * Ri[2][j] for j in range(3)] for i in range(3)]
+    return True, R_, t_
+
+
 def quat_xyzw(R):
     tr1 = ((1.0 + R[0][0]) + R[1][1]) + R[2][2]
     w = math.sqrt(tr1 if tr1 > 0.0 else 0.0) / 2.0
@@ -124,18 +145,8 @@ def _track_ref(stages, hooks, frames, depths, f, cx, cy, fm_mode, seed_base, to_
                 if good:
                     r["rvec"], r["tvec"] = np.array(rvec), np.array(tvec)
                     r["n_pnp_inliers"] = nin
-                    Rr = rodrigues([float(v) for v in rvec]); tv = [float(v) for v in tvec]
-                    Ri = [[Rr[j][i] for j in range(3)] for i in range(3)]
-                    ti = [-((Ri[i][0] * tv[0] + Ri[i][1] * tv[1]) + Ri[i][2] * tv[2]) for i in range(3)]
-                    tn = math.sqrt((ti[0] * ti[0] + ti[1] * ti[1]) + ti[2] * ti[2])
-                    ca = (((Ri[0][0] + Ri[1][1]) + Ri[2][2]) - 1.0) / 2.0
-                    ang = math.acos(-1.0 if ca < -1.0 else (1.0 if ca > 1.0 else ca))
-                    if tn > 0.5 or ang > 0.2:                                  # :549-570
-                        r["motion_outlier"] = 1
-                    else:
-                        t_ = [t_[i] + ((R_[i][0] * ti[0] + R_[i][1] * ti[1]) + R_[i][2] * ti[2]) for i in range(3)]
-                        R_ = [[(R_[i][0] * Ri[0][j] + R_[i][1] * Ri[1][j]) + R_[i][2] * Ri[2][j] for j in range(3)] for i in range(3)]
-                        r["pose_updated"] = 1
+                    updated, R_, t_ = pose_step(R_, t_, rvec, tvec)
+                    r["pose_updated" if updated else "motion_outlier"] = 1
                 else:
                     r["pnp_failed"] = 1
                     if rt_pnp_is_cv() and rvec is not None:
